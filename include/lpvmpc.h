@@ -18,7 +18,7 @@
  *     once when the runtime initialises) before anything touches HIP: streams that share a hardware queue run in order, so a launch
  *     holding a slow instance blocks its queue's other streams (configs[1]: 1.3 M solves/s with 8 queues, 2.4 M with 16; with straggler
  *     deferral four streams on four queues reach 4.1 M; beyond ~20 queues the hardware time-slices).  The library does not set it: it is
- *     the process's to choose (bench.py sets 16);
+ *     the process's to choose (bench.py sets 2);
  *   - there is NO CPU fallback: without a usable HIP device every compute call fails with
  *     LPVMPC_E_NODEVICE.
  *

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Planner N = 30: the default kernel (equilibration vectors in global memory, three instances per CU) against kernel_variant 5
 (all vectors in LDS, two per CU) on a GPU box: timing of a 4096-instance host call and word-for-word equality."""
-import sys, time
-sys.path.insert(0, "/root/repo")
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, lpvmpc
 from lpvmpc import workloads
 w = workloads.planner_batch(4096, N=30, seed=1)

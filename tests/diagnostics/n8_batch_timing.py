@@ -1,4 +1,4 @@
-import sys, time; sys.path.insert(0, "/root/repo")
+import os, sys, time; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, lpvmpc
 from lpvmpc import workloads
 w = workloads.controller_batch(8192, N=8, seed=26)

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Per-block instruction mix of the hot region (reachable between HOT markers) of one kernel."""
-import re, sys
+import os, re, sys
 from collections import Counter
-sys.path.insert(0, '/root/repo/tools')
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from asm_mix import classify
 path, name = sys.argv[1], sys.argv[2]
 body, on = [], False

@@ -9,7 +9,7 @@ every instance's first 100 iterations), RESUME passes of the same kernel name (g
 The per-class tables (`*_kernel_classes.csv`: count, average / total / min / max ns per kernel and class) are what the bench
 line's kernel_avg_ms (MAIN only) and all_launches_avg_ms (all three) can be recomputed from.
 
-HBM bytes follow /opt/skills/guides/MI355X_MICROARCH.md (HBM section): FETCH_SIZE and WRITE_SIZE in separate passes, KB units,
+HBM bytes follow the MI355X counter conventions: FETCH_SIZE and WRITE_SIZE in separate passes, KB units,
 FETCH_SIZE doubled on gfx950 for coalesced streaming reads, WRITE_SIZE as reported.  SQ_ACTIVE_INST_* / SQ_WAVE_CYCLES /
 SQ_WAIT_* count quad-cycles (x4 = cycles), summed over all waves of the dispatch.
 Usage: pmc_summary.py <collect_pmc outdir> <profiles/rNN prefix>"""
