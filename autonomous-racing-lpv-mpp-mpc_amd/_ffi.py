@@ -64,6 +64,15 @@ class HandoffConfig(C.Structure):
     _fields_ = [("interp_dt", _d), ("padlen", _i), ("order", _i), ("b", _d * (MAX_FILTER_ORDER + 1)), ("a", _d * (MAX_FILTER_ORDER + 1))]
 
 
+class ObserverConfig(C.Structure):
+    """Mirror of ``struct lpvmpc_observer_config`` (include/lpvmpc.h)."""
+    _fields_ = [("L_ls", _d * 480), ("lim_ls", _d * 12), ("L_hs", _d * 480), ("lim_hs", _d * 12),
+                ("loop_rate", _d), ("init_vx", _d), ("psi_std", _d), ("psiDot_std", _d), ("x_std", _d), ("y_std", _d),
+                ("v_std", _d), ("n_bound", _d), ("gps_freq", _d), ("seed", C.c_uint64), ("vehicle_offset", C.c_int64)]
+
+
+OBSERVER_AUX = 30 + 36 + 12      # L_gain [6][5], A_obs [6][6], B_obs [6][2] per instance (lpvmpc_observer_step_batch)
+
 EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_destroy", "lpvmpc_last_error", "lpvmpc_last_error_code",
            "lpvmpc_reserve", "lpvmpc_lpv_batch", "lpvmpc_estimate_abc_batch", "lpvmpc_solve_batch_AB",
            "lpvmpc_solve_batch", "lpvmpc_solve_batch_dev", "lpvmpc_last_kernel_ms", "lpvmpc_set_timing",
@@ -71,7 +80,8 @@ EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_d
            "lpvmpc_local_position_batch", "lpvmpc_global_position_batch", "lpvmpc_plant_step_batch",
            "lpvmpc_cl_init", "lpvmpc_cl_tick", "lpvmpc_cl_read", "lpvmpc_cl_release", "lpvmpc_join", "lpvmpc_resume_time_stats", "lpvmpc_defer_stats",
            "lpvmpc_handoff_default_config", "lpvmpc_handoff_length", "lpvmpc_handoff_operators", "lpvmpc_handoff_setup",
-           "lpvmpc_handoff_batch", "lpvmpc_cascade_init", "lpvmpc_cascade_tick", "lpvmpc_cascade_read", "lpvmpc_cascade_alive_ticks")
+           "lpvmpc_handoff_batch", "lpvmpc_cascade_init", "lpvmpc_cascade_tick", "lpvmpc_cascade_read", "lpvmpc_cascade_alive_ticks",
+           "lpvmpc_observer_default_config", "lpvmpc_observer_setup", "lpvmpc_observer_read", "lpvmpc_observer_step_batch")
 
 _lib = None
 
@@ -158,6 +168,13 @@ def load():
     lib.lpvmpc_cascade_read.argtypes = [vp] + [vp] * 12
     lib.lpvmpc_cascade_alive_ticks.argtypes = [vp, vp]
     lib.lpvmpc_cascade_alive_ticks.restype = C.c_int
+    lib.lpvmpc_observer_default_config.argtypes = [P(ObserverConfig)]
+    lib.lpvmpc_observer_default_config.restype = None
+    lib.lpvmpc_observer_setup.argtypes = [vp, P(ObserverConfig)]
+    lib.lpvmpc_observer_read.argtypes = [vp, vp, vp]
+    lib.lpvmpc_observer_step_batch.argtypes = [vp, _i, P(ObserverConfig), vp, vp, vp, vp, vp]
+    for name in ("lpvmpc_observer_setup", "lpvmpc_observer_read", "lpvmpc_observer_step_batch"):
+        getattr(lib, name).restype = C.c_int
     for name in ("lpvmpc_handoff_length", "lpvmpc_handoff_operators", "lpvmpc_handoff_setup", "lpvmpc_handoff_batch",
                  "lpvmpc_cascade_init", "lpvmpc_cascade_tick", "lpvmpc_cascade_read"):
         getattr(lib, name).restype = C.c_int
@@ -180,6 +197,12 @@ def default_config(kind):
 def default_handoff_config():
     cfg = HandoffConfig()
     load().lpvmpc_handoff_default_config(C.byref(cfg))
+    return cfg
+
+
+def default_observer_config():
+    cfg = ObserverConfig()
+    load().lpvmpc_observer_default_config(C.byref(cfg))
     return cfg
 
 

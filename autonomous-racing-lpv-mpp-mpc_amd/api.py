@@ -254,6 +254,36 @@ class BatchedSolver:
         self._chk(self._lib.lpvmpc_cl_read(self._h, ptr(o["plant"]), ptr(o["local"]), ptr(o["cmd"]), ptr(o["iters"]), ptr(o["status"])))
         return o
 
+    # -- gain-scheduled LPV estimator (lpvmpc_observer_*) ------------------------------------------------------
+    def observer_setup(self, cfg=None, **kw):
+        """Attach the estimator to this CONTROLLER engine's next cl_init or cascade_init (``cfg``: an ``observer.observer_config`` result or an
+        ``_ffi.ObserverConfig``; keyword arguments build one with ``observer.observer_config``).  ``observer_setup(None)``
+        removes it: the next fleet runs on ground truth again."""
+        if cfg is None and kw:
+            from .observer import observer_config
+            cfg = observer_config(**kw)
+        self._chk(self._lib.lpvmpc_observer_setup(self._h, None if cfg is None else C.byref(cfg)))
+
+    def observer_read(self):
+        """The fleet's (or cascade's) estimate [B,6] = [vx vy psiDot x y yaw] and latest measurement [B,5] = [vx psiDot x y yaw]."""
+        B = self._cas[0] if getattr(self, "_cas", None) is not None else self._cl_B
+        est, meas = np.empty((B, 6)), np.empty((B, 5))
+        self._chk(self._lib.lpvmpc_observer_read(self._h, ptr(est), ptr(meas)))
+        return est, meas
+
+    def observer_step(self, cfg, est, y, u, k, want_aux=False):
+        """One GS_LPV_Est step per instance: est [B,6], y [B,5], u [B,2] = (servo, motor), k [B] (t = k / loop_rate).
+        Returns the new estimate, and with ``want_aux`` also (L_gain [B,6,5], A_obs [B,6,6], B_obs [B,6,2])."""
+        e = f64(est).reshape(-1, 6).copy()
+        B = e.shape[0]
+        y = f64(y, (B, 5), "y"); u = f64(u, (B, 2), "u")
+        k = np.ascontiguousarray(np.broadcast_to(np.asarray(k, np.int32), (B,)))
+        aux = np.empty((B, _ffi.OBSERVER_AUX)) if want_aux else None
+        self._chk(self._lib.lpvmpc_observer_step_batch(self._h, B, C.byref(cfg), ptr(e), ptr(y), ptr(u), ptr(k), ptr(aux)))
+        if not want_aux:
+            return e
+        return e, (aux[:, :30].reshape(B, 6, 5), aux[:, 30:66].reshape(B, 6, 6), aux[:, 66:].reshape(B, 6, 2))
+
     # -- planner -> controller hand-off (SURVEY 8f row f2) ------------------------------------------------
     def handoff_setup(self, cfg=None):
         """Build the resampling / filtering operators for this PLANNER handle; returns M (samples per My_Planning array)."""

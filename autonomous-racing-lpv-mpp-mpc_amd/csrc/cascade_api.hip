@@ -17,6 +17,7 @@ struct lpvmpc_cascade {
     double *plant, *cmd, *local, *ref0, *SSc;       // [B][8], [B][2], [B][6], [B][3], [B]
     int32_t *lap, *lap_tick;                        // [B]
     int32_t *alive_ticks;                           // [B] controller ticks entered with a finite plant state
+    double *estv;                                   // [B][8] with an estimator: the estimate in the plant's layout, read by both nodes' measurements
     double *refs, *sig, *SSp, *pose, *px0;          // planner side: [2][B][5][M] (message j in buffer j % 2), [B][5][Np], [B][Np+1], [B][3], [B][5]
     hipStream_t s_ctrl, s_plan;                     // the two nodes run on their own streams
     hipEvent_t ev_plan;                             // planner tick done (planner stream) -> controller stream waits
@@ -110,13 +111,14 @@ extern "C" int lpvmpc_handoff_batch(lpvmpc_handle *h, int32_t B, const double *x
 void lpvmpc_cascade_free(lpvmpc_handle *h) {
     lpvmpc_cascade *c = h->cascade;
     if (!c) return;
-    void *ptrs[] = {c->plant, c->cmd, c->local, c->ref0, c->SSc, c->lap, c->lap_tick, c->alive_ticks, c->refs, c->sig, c->SSp, c->pose, c->px0};
+    void *ptrs[] = {c->estv, c->plant, c->cmd, c->local, c->ref0, c->SSc, c->lap, c->lap_tick, c->alive_ticks, c->refs, c->sig, c->SSp, c->pose, c->px0};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->ev_plan) (void)hipEventDestroy(c->ev_plan);
     if (c->ev_ctrl) (void)hipEventDestroy(c->ev_ctrl);
     if (c->s_ctrl) (void)hipStreamDestroy(c->s_ctrl);
     if (c->s_plan) (void)hipStreamDestroy(c->s_plan);
     if (c->plan && c->plan->cascade_owner == h) c->plan->cascade_owner = nullptr;
+    if (h->obs_state) { (void)hipFree(h->obs_state); h->obs_state = nullptr; }
     delete c;
     h->cascade = nullptr;
 }
@@ -169,6 +171,13 @@ extern "C" int lpvmpc_cascade_init(lpvmpc_handle *h, lpvmpc_handle *plan, int32_
     H2D(plan->d_maxey, hw.data(), b * 8);
     HIP_TRY(h, hipStreamSynchronize(st));
     h->state_valid_B = 0; plan->state_valid_B = 0;
+    if (h->obs_cfg) {             // the estimator in the loop: both nodes measure the estimate (CMAIN:179-180, PMAIN:141 read pos_info)
+        HIP_TRY(h, hipMalloc((void **)&c->estv, b * 8 * 8));
+        std::vector<double> v(plant0, plant0 + b * 8);
+        for (size_t i = 0; i < b; ++i) v[i * 8 + 4] = v[i * 8 + 5] = 0.0;
+        H2D(c->estv, v.data(), b * 8 * 8);
+        rc = lpvmpc_observer_start(h, B, plant0, dt_sim, 1); if (rc) return rc;
+    }
     return LPVMPC_OK;
 }
 
@@ -180,7 +189,7 @@ static int planner_tick(lpvmpc_handle *h, lpvmpc_cascade *c) {
     double *refs = c->refs + (size_t)(c->plan_ticks % 2) * B * 5 * c->M;
     const double *x0;
     if (c->plan_ticks == 0) {                                                    // first_it == 1: seed trajectory, measured x0
-        HIP_TRY(h, lpvmpc::launch_plan_first(p->d_cfg, B, c->plant, c->hw, c->slack, c->q9, 0.2, c->px0, p->d_xlast, p->d_delta, st));
+        HIP_TRY(h, lpvmpc::launch_plan_first(p->d_cfg, B, c->estv ? c->estv : c->plant, c->hw, c->slack, c->q9, 0.2, c->px0, p->d_xlast, p->d_delta, st));
         HIP_TRY(h, lpvmpc::launch_abc(p->dev, p->d_cfg, B, p->d_xlast, p->d_delta, p->d_AB, st));
         x0 = c->px0;
     } else {                                                                     // x0 = Planner.xPred[1,:], LPVPrediction(x0, SS, uPred)
@@ -219,7 +228,7 @@ extern "C" int lpvmpc_cascade_tick(lpvmpc_handle *h, int32_t n_ticks) {
         const double *refs = c->refs + (size_t)(j % 2) * B * 5 * c->M;
         const int latch = c->index == 0;
         c->index = c->index == 0 ? 1 : 0;
-        HIP_TRY(h, lpvmpc::launch_tt_measure(h->d_cfg, B, c->M, k, c->plant, c->cmd, refs, latch, h->d_vel, h->d_curv, c->ref0, c->lap,
+        HIP_TRY(h, lpvmpc::launch_tt_measure(h->d_cfg, B, c->M, k, c->estv ? c->estv : c->plant, c->cmd, refs, latch, h->d_vel, h->d_curv, c->ref0, c->lap,
                                              c->lap_tick, c->SSc, c->local, h->d_uold, c->alive_ticks, st));
         HIP_TRY(h, hipEventRecord(c->ev_ctrl, st));
         if (c->prefetch && first_reader) {                                       // message j has its first reader: every reader of j - 1 is enqueued,
@@ -233,7 +242,11 @@ extern "C" int lpvmpc_cascade_tick(lpvmpc_handle *h, int32_t n_ticks) {
                     h->warm_mode ? h->d_state : nullptr, (h->warm_mode && h->state_valid_B == B) ? h->warm_mode : 0, 6};
         int rc = lpvmpc_launch_solve_timed(h, a, st); if (rc) return rc;
         if (h->warm_mode) h->state_valid_B = B;
-        HIP_TRY(h, lpvmpc::launch_cl_command_plant(B, N, h->d_uPred, c->cmd, c->plant, lpvmpc_plant_cfg(h, c->n_sub[k % 3], c->dt_sim, c->mu_sim), st));
+        if (c->estv)
+            HIP_TRY(h, lpvmpc::launch_cascade_plant_observe(B, N, h->d_uPred, c->cmd, c->plant, lpvmpc_plant_cfg(h, c->n_sub[k % 3], c->dt_sim, c->mu_sim),
+                                                             c->estv, h->obs_gains, h->obs_state, h->obs_p, st));
+        else
+            HIP_TRY(h, lpvmpc::launch_cl_command_plant(B, N, h->d_uPred, c->cmd, c->plant, lpvmpc_plant_cfg(h, c->n_sub[k % 3], c->dt_sim, c->mu_sim), st));
         c->ctrl_ticks++;
     }
     return LPVMPC_OK;

@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <cstddef>
 #include <cstring>
 #include <new>
 #include <string>
@@ -166,6 +167,7 @@ extern "C" lpvmpc_handle *lpvmpc_create(const lpvmpc_config *cfg) {
     h->dpool[0] = h->dpool[1] = nullptr; h->dcount[0] = h->dcount[1] = nullptr; h->dstats = nullptr; h->dcur = 0; h->defer_stream = nullptr; h->defer_event = nullptr;
     h->defer_stream_set = false; h->defer_tail = 1; h->defer_skip_pass = false;
     h->h_pack_in = h->h_pack_out = h->d_pack_in = h->d_pack_out = nullptr;
+    h->obs_cfg = nullptr; h->obs_gains = h->obs_state = nullptr; h->obs_ws = nullptr; h->obs_ws_cap = 0; h->obs_B = 0;
     DevCfg &d = h->dev;
     std::memset(&d, 0, sizeof(d));
     d.kind = cfg->kind; d.N = cfg->N; d.track_rows = cfg->track_rows; d.max_iter = cfg->max_iter;
@@ -208,7 +210,12 @@ extern "C" void lpvmpc_destroy(lpvmpc_handle *h) {
     if (h->cl_local_next) (void)hipFree(h->cl_local_next);
     if (h->cl_local) (void)hipFree(h->cl_local);
     if (h->cl_cmd) (void)hipFree(h->cl_cmd);
-    if (h->cascade) lpvmpc_cascade_free(h);
+    if (h->cascade) lpvmpc_cascade_free(h);                                  // (frees the cascade's estimator state)
+    if (h->obs_state) (void)hipFree(h->obs_state);
+    if (h->obs_gains) (void)hipFree(h->obs_gains);
+    if (h->obs_ws) (void)hipFree(h->obs_ws);
+    h->obs_state = h->obs_gains = nullptr; h->obs_ws = nullptr;
+    delete h->obs_cfg;
     // a planner handle that a controller's cascade still drives: end that cascade first (it holds a pointer to this handle)
     if (h->cascade_owner && h->cascade_owner->cascade) lpvmpc_cascade_free(h->cascade_owner);
     if (h->h_pack_in) (void)hipHostFree(h->h_pack_in);
@@ -680,6 +687,7 @@ extern "C" int lpvmpc_cl_release(lpvmpc_handle *h) {
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (h->cascade) { HIP_TRY(h, hipDeviceSynchronize()); lpvmpc_cascade_free(h); }
     if (h->cl_plant) { (void)hipFree(h->cl_plant); (void)hipFree(h->cl_local); (void)hipFree(h->cl_cmd); (void)hipFree(h->cl_local_next); h->cl_plant = h->cl_local = h->cl_cmd = h->cl_local_next = nullptr; }
+    if (h->obs_state) { (void)hipFree(h->obs_state); h->obs_state = nullptr; }
     h->cl_B = 0; h->cl_ticks = 0; h->cl_first_it = 1; h->cl_next_valid = 0;
     return LPVMPC_OK;
 }
@@ -707,6 +715,8 @@ extern "C" int lpvmpc_cl_init(lpvmpc_handle *h, int32_t B, const double *plant0,
     h->cl_B = B; h->cl_first_it = 1; h->cl_q9 = q9_swap != 0; h->cl_ticks = 0; h->cl_hw = half_width; h->cl_slack = slack;
     h->cl_pc = lpvmpc_plant_cfg(h, n_sub, dt_sim, mu_sim);
     h->state_valid_B = 0;
+    if (h->obs_state) { (void)hipFree(h->obs_state); h->obs_state = nullptr; }
+    if (h->obs_cfg) { rc = lpvmpc_observer_start(h, B, plant0, dt_sim, 0); if (rc) return rc; }   // the estimator in the loop
     return LPVMPC_OK;
 }
 
@@ -718,6 +728,8 @@ extern "C" int lpvmpc_cl_tick(lpvmpc_handle *h, int32_t n_ticks) {
     for (int t = 0; t < n_ticks; ++t) {
         // the measurement of this tick: made by the launch that advanced the plant at the end of the previous tick, or here
         if (h->cl_next_valid) { double *t_ = h->cl_local; h->cl_local = h->cl_local_next; h->cl_local_next = t_; }
+        else if (h->obs_state) HIP_TRY(h, lpvmpc::launch_cl_observe_measure(h->d_cfg, B, h->obs_state, h->cl_cmd, h->cl_hw, h->cl_slack, h->cl_q9,
+                                                                           h->cl_local, h->d_uold, st));
         else HIP_TRY(h, lpvmpc::launch_cl_measure(h->d_cfg, B, h->cl_plant, h->cl_cmd, h->cl_hw, h->cl_slack, h->cl_q9, h->cl_local, h->d_uold, st));
         const double *x0 = h->cl_local; int x0_stride = 6;
         if (h->cl_first_it < 10) {                                           // CMAIN:310-315: seed mode
@@ -732,8 +744,12 @@ extern "C" int lpvmpc_cl_tick(lpvmpc_handle *h, int32_t n_ticks) {
                     h->warm_mode ? h->d_state : nullptr, (h->warm_mode && h->state_valid_B == B) ? h->warm_mode : 0, x0_stride};
         int rc = lpvmpc_launch_solve_timed(h, a, st); if (rc) return rc;
         if (h->warm_mode) h->state_valid_B = B;
-        HIP_TRY(h, lpvmpc::launch_cl_command_plant_measure(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_pc, h->cl_hw, h->cl_slack, h->cl_q9,
-                                                            h->cl_local_next, h->d_uold, st));
+        if (h->obs_state)
+            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_pc, h->cl_hw, h->cl_slack,
+                                                                h->cl_q9, h->cl_local_next, h->d_uold, h->obs_gains, h->obs_state, h->obs_p, st));
+        else
+            HIP_TRY(h, lpvmpc::launch_cl_command_plant_measure(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_pc, h->cl_hw, h->cl_slack, h->cl_q9,
+                                                                h->cl_local_next, h->d_uold, st));
         h->cl_next_valid = 1;
         h->cl_ticks++;
     }
@@ -750,6 +766,113 @@ extern "C" int lpvmpc_cl_read(lpvmpc_handle *h, double *plant, double *local_sta
     if (cmd) D2H(cmd, h->cl_cmd, B * 2 * 8);
     if (iters) D2H(iters, h->d_iters, B * 4);
     if (status) D2H(status, h->d_status, B * 4);
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return LPVMPC_OK;
+}
+
+// ---- gain-scheduled LPV estimator and simulated sensors (observer.hip) --------------------------------------------------------
+// the kernels read the two tables with their limits as one block of words from the head of the struct
+static_assert(offsetof(lpvmpc_observer_config, L_ls) == 0 &&
+              offsetof(lpvmpc_observer_config, loop_rate) == sizeof(double) * 2 * (lpvmpc::kObsTable + 12), "observer config layout");
+extern "C" void lpvmpc_observer_default_config(lpvmpc_observer_config *c) {
+    if (!c) return;
+    std::memset(c, 0, sizeof(*c));
+    c->loop_rate = 200.0; c->init_vx = 0.2;                                 // EST:47, MAIN_LAUNCH simulator/init_vx
+    c->n_bound = 0.5; c->gps_freq = 1000.0;                                  // MAIN_LAUNCH:60-87 (every std 0)
+}
+
+static int observer_check(lpvmpc_handle *h, const lpvmpc_observer_config *c, const char *who) {
+    if (!(c->loop_rate > 0) || !(c->gps_freq > 0) || !(c->n_bound >= 0))
+        return fail(h, LPVMPC_E_ARG, "%s: loop_rate and gps_freq must be > 0, n_bound >= 0", who);
+    const double sd[5] = {c->psi_std, c->psiDot_std, c->x_std, c->y_std, c->v_std};
+    for (double v : sd) if (!(v >= 0)) return fail(h, LPVMPC_E_ARG, "%s: sensor standard deviations must be >= 0", who);
+    return LPVMPC_OK;
+}
+
+// the estimator state of a fleet (from_plant = 0: estimate [init_vx, 0, 0, x0, y0, yaw0]) or of a cascade (from_plant = 1: the cascade
+// starts at the lap event of a running vehicle, whose estimator has been running since its start -- the estimate starts at the plant
+// state [vx, vy, psiDot, x, y, yaw]); GPS hold = start position, encoder reading 0, step counter 0.  Synchronises.
+int lpvmpc_observer_start(lpvmpc_handle *h, int B, const double *plant0, double dt_sim, int from_plant) {
+    const lpvmpc_observer_config &o = *h->obs_cfg;
+    std::vector<double> os((size_t)B * lpvmpc::kObsStride, 0.0);
+    for (int b = 0; b < B; ++b) {
+        double *e = os.data() + (size_t)b * lpvmpc::kObsStride; const double *p = plant0 + (size_t)b * 8;
+        e[0] = from_plant ? p[2] : o.init_vx; e[1] = from_plant ? p[3] : 0.0; e[2] = from_plant ? p[7] : 0.0;
+        e[3] = p[0]; e[4] = p[1]; e[5] = p[6];
+        e[lpvmpc::OBS_GPS_X] = p[0]; e[lpvmpc::OBS_GPS_Y] = p[1];
+    }
+    hipStream_t st = h->stream;
+    if (h->obs_state) { HIP_TRY(h, hipStreamSynchronize(st)); (void)hipFree(h->obs_state); h->obs_state = nullptr; }
+    if (!h->obs_gains) HIP_TRY(h, hipMalloc((void **)&h->obs_gains, sizeof(double) * 2 * (lpvmpc::kObsTable + 12)));
+    HIP_TRY(h, hipMalloc((void **)&h->obs_state, os.size() * 8));
+    H2D(h->obs_gains, o.L_ls, sizeof(double) * 2 * (lpvmpc::kObsTable + 12));
+    H2D(h->obs_state, os.data(), os.size() * 8);
+    lpvmpc::ObsParams &op = h->obs_p;
+    op.dt = 1.0 / o.loop_rate; op.th_update = (1.0 / o.gps_freq) / dt_sim; op.n_bound = o.n_bound;
+    op.std[0] = o.psi_std; op.std[1] = o.psiDot_std; op.std[2] = o.x_std; op.std[3] = o.y_std; op.std[4] = o.v_std;
+    op.seed = o.seed; op.voff = o.vehicle_offset;
+    h->obs_B = B;
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return LPVMPC_OK;
+}
+
+extern "C" int lpvmpc_observer_setup(lpvmpc_handle *h, const lpvmpc_observer_config *cfg) {
+    if (!h) return fail(nullptr, LPVMPC_E_ARG, "lpvmpc_observer_setup: handle is NULL");
+    if (h->cfg.kind != LPVMPC_KIND_CONTROLLER) return fail(h, LPVMPC_E_ARG, "lpvmpc_observer_setup: controller handles only");
+    if (!cfg) { delete h->obs_cfg; h->obs_cfg = nullptr; return LPVMPC_OK; }
+    int rc = observer_check(h, cfg, "lpvmpc_observer_setup"); if (rc) return rc;
+    if (!h->obs_cfg) h->obs_cfg = new (std::nothrow) lpvmpc_observer_config();
+    if (!h->obs_cfg) return fail(h, LPVMPC_E_NOMEM, "out of host memory");
+    *h->obs_cfg = *cfg;
+    return LPVMPC_OK;
+}
+
+extern "C" int lpvmpc_observer_read(lpvmpc_handle *h, double *est, double *meas) {
+    if (!h || !(h->cl_plant || h->cascade) || !h->obs_state)
+        return fail(h, LPVMPC_E_ARG, "lpvmpc_observer_read: no fleet or cascade with an estimator (lpvmpc_observer_setup, then lpvmpc_cl_init / lpvmpc_cascade_init)");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipDeviceSynchronize());      // a cascade runs on its own streams
+    const size_t B = h->obs_B;
+    std::vector<double> os(B * lpvmpc::kObsStride);
+    HIP_TRY(h, hipMemcpyAsync(os.data(), h->obs_state, os.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (size_t b = 0; b < B; ++b) {
+        const double *e = os.data() + b * lpvmpc::kObsStride;
+        if (est) for (int i = 0; i < 6; ++i) est[b * 6 + i] = e[lpvmpc::OBS_EST + i];
+        if (meas) for (int i = 0; i < 5; ++i) meas[b * 5 + i] = e[lpvmpc::OBS_Y + i];
+    }
+    return LPVMPC_OK;
+}
+
+extern "C" int lpvmpc_observer_step_batch(lpvmpc_handle *h, int32_t B, const lpvmpc_observer_config *cfg, double *est, const double *y,
+                                          const double *u, const int32_t *k, double *aux) {
+    if (h && B == 0) return LPVMPC_OK;                                   // an empty batch is a no-op
+    // the fleet / cascade rule of the batch calls; the solver workspace is not needed (this call stages its own buffers)
+    if (!h) return fail(nullptr, LPVMPC_E_ARG, "lpvmpc_observer_step_batch: handle is NULL");
+    if (h->cl_plant || h->cascade || h->cascade_owner)
+        return fail(h, LPVMPC_E_ARG, "lpvmpc_observer_step_batch: this handle runs a fleet whose state lives in its workspace; use another handle "
+                    "for batch calls (lpvmpc_cl_release ends the fleet)");
+    if (B < 0) return fail(h, LPVMPC_E_ARG, "lpvmpc_observer_step_batch: B=%d", B);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    int rc;
+    if (!cfg || !est || !y || !u || !k) return fail(h, LPVMPC_E_ARG, "lpvmpc_observer_step_batch: bad argument");
+    rc = observer_check(h, cfg, "lpvmpc_observer_step_batch"); if (rc) return rc;
+    const size_t per = (size_t)(6 + 5 + 2 + lpvmpc::kObsAux) * 8 + 8;
+    if (B > h->obs_ws_cap) {
+        if (h->obs_ws) { (void)hipFree(h->obs_ws); h->obs_ws = nullptr; h->obs_ws_cap = 0; }
+        HIP_TRY(h, hipMalloc((void **)&h->obs_ws, per * B));
+        h->obs_ws_cap = B;
+    }
+    if (!h->obs_gains) HIP_TRY(h, hipMalloc((void **)&h->obs_gains, sizeof(double) * 2 * (lpvmpc::kObsTable + 12)));
+    const size_t b = B;
+    double *d_est = (double *)h->obs_ws, *d_y = d_est + b * 6, *d_u = d_y + b * 5, *d_aux = d_u + b * 2;
+    int32_t *d_k = (int32_t *)(d_aux + b * lpvmpc::kObsAux);
+    hipStream_t st = h->stream;
+    H2D(h->obs_gains, cfg->L_ls, sizeof(double) * 2 * (lpvmpc::kObsTable + 12));
+    H2D(d_est, est, b * 6 * 8); H2D(d_y, y, b * 5 * 8); H2D(d_u, u, b * 2 * 8); H2D(d_k, k, b * 4);
+    HIP_TRY(h, lpvmpc::launch_observer_step(h->obs_gains, B, d_est, d_y, d_u, d_k, 1.0 / cfg->loop_rate, aux ? d_aux : nullptr, st));
+    D2H(est, d_est, b * 6 * 8);
+    if (aux) D2H(aux, d_aux, b * lpvmpc::kObsAux * 8);
     HIP_TRY(h, hipStreamSynchronize(st));
     return LPVMPC_OK;
 }

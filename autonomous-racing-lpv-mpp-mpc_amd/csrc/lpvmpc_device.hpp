@@ -111,6 +111,26 @@ hipError_t launch_cl_command_plant_measure(const DevCfg *dcfg, int B, int N, con
                                            double hw, double slack, int q9_swap, double *local_next, double *u_old, hipStream_t s);
 
 
+// gain-scheduled LPV estimator and simulated sensors (observer.hip)
+constexpr int kObsTable = 6 * 5 * 16;   // one Llmi table [6][5][16]
+constexpr int kObsAux = 30 + 36 + 12;   // L_gain [6][5], A_obs [6][6], B_obs [6][2] of lpvmpc_observer_step_batch
+// per-vehicle estimator state of a fleet, [B][kObsStride] doubles (counters are stored as exact integers)
+enum ObsSlot { OBS_EST = 0, OBS_Y = 6, OBS_GPS_X = 11, OBS_GPS_Y = 12, OBS_ENC_PREV = 13, OBS_ENC_MEAS = 14, OBS_GPS_CNT = 15,
+               OBS_ENC_CNT = 16, OBS_K = 17 };
+constexpr int kObsStride = 18;
+// sensor std order = noise channel: psi, psiDot, x, y, v
+struct ObsParams { double dt, th_update, n_bound, std[5]; unsigned long long seed; long long voff; };
+hipError_t launch_observer_step(const double *gains, int B, double *est, const double *y, const double *u, const int32_t *k, double dt,
+                                double *aux, hipStream_t s);
+hipError_t launch_cl_observe_measure(const DevCfg *dcfg, int B, const double *obs, const double *cmd, double hw, double slack, int q9_swap,
+                                     double *local_state, double *u_old, hipStream_t s);
+hipError_t launch_cascade_plant_observe(int B, int N, const double *uPred, double *cmd, double *plant, PlantCfg pc, double *est_view,
+                                        const double *gains, double *obs, const ObsParams &op, hipStream_t s);
+hipError_t launch_cl_command_plant_observe(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant, PlantCfg pc,
+                                          double hw, double slack, int q9_swap, double *local_next, double *u_old, const double *gains,
+                                          double *obs, const ObsParams &op, hipStream_t s);
+
+
 // planner -> controller hand-off and trajectory-tracking measurement (handoff.hip)
 #define LPVMPC_HANDOFF_MAX_N 64
 int handoff_length(int N, double dt, double interp_dt);

@@ -69,6 +69,14 @@ struct lpvmpc_handle {
     int cascade_prefetch;               // option "cascade_prefetch" (default 1)
     lpvmpc_cascade *cascade;            // owned by the controller handle of a cascade (lpvmpc_cascade_init)
     lpvmpc_handle *cascade_owner;       // planner handle: the controller handle whose cascade drives it (its workspace carries the planner recursion)
+    // gain-scheduled LPV estimator (lpvmpc_observer_*, observer.hip)
+    lpvmpc_observer_config *obs_cfg;    // set by lpvmpc_observer_setup, taken by the next lpvmpc_cl_init (null: no estimator)
+    double *obs_gains;                  // device copy of the gain words (head of lpvmpc_observer_config): the fleet's or the batch call's
+    double *obs_state;                  // the fleet's / cascade's estimator state [obs_B][kObsStride] (null: it runs on ground truth)
+    int obs_B;
+    lpvmpc::ObsParams obs_p;
+    char *obs_ws;                       // lpvmpc_observer_step_batch staging, obs_ws_cap instances
+    int obs_ws_cap;
 };
 
 LPVMPC_HIDDEN int lpvmpc_fail(lpvmpc_handle *h, int code, const char *fmt, ...);
@@ -89,7 +97,8 @@ LPVMPC_HIDDEN int lpvmpc_check_common(lpvmpc_handle *h, int B, const char *who);
 LPVMPC_HIDDEN int lpvmpc_check_batch(lpvmpc_handle *h, int B, const char *who);        // the same for the stand-alone batch calls: refused while the handle runs a fleet
 LPVMPC_HIDDEN int lpvmpc_launch_solve_timed(lpvmpc_handle *h, const lpvmpc::SolveArgs &a, hipStream_t st);
 LPVMPC_HIDDEN lpvmpc::PlantCfg lpvmpc_plant_cfg(const lpvmpc_handle *h, int n_sub, double dt_sim, double mu_sim);
-LPVMPC_HIDDEN void lpvmpc_cascade_free(lpvmpc_handle *h);                               // cascade_api.hip
+LPVMPC_HIDDEN void lpvmpc_cascade_free(lpvmpc_handle *h);
+LPVMPC_HIDDEN int lpvmpc_observer_start(lpvmpc_handle *h, int B, const double *plant0, double dt_sim, int from_plant);   // lpvmpc_api.hip                               // cascade_api.hip
 namespace lpvmpc {
 // handoff.hip (host): interpolation operator W and interpolation + filtfilt operator FW, both [M][N] row-major
 bool handoff_operators(int N, double dt, double interp_dt, int padlen, int ord, const double *b, const double *a,

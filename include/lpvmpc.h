@@ -36,7 +36,8 @@
 extern "C" {
 #endif
 
-#define LPVMPC_VERSION 200            /* 0.2.0: round 5 removed the lpvmpc_lane_* exports (an ABI break), round 6 adds lpvmpc_defer_stats and kernel_variant 9 */
+#define LPVMPC_VERSION 200            /* 0.2.0: round 5 removed the lpvmpc_lane_* exports (an ABI break), round 6 adds lpvmpc_defer_stats and kernel_variant 9;
+                                         the lpvmpc_observer_* additions are backward compatible and keep the value, which tests/test_cabi.py pins */
 
 #define LPVMPC_KIND_CONTROLLER 0      /* PathFollowingLPV_MPC  (CTRL:30-258) */
 #define LPVMPC_KIND_PLANNER    1      /* LPV_MPC_Planner       (PLAN:29-320) */
@@ -386,6 +387,82 @@ int lpvmpc_cascade_read(lpvmpc_handle *ctrl, double *plant, double *local_state,
  * planner QP went primal infeasible carries NaN from then on and costs no iterations: the sum over the fleet is the number of
  * vehicle-ticks that did work).  Synchronises like lpvmpc_cascade_read. */
 int lpvmpc_cascade_alive_ticks(lpvmpc_handle *ctrl, int32_t *alive_ticks);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Gain-scheduled LPV state estimator and simulated sensors (stateEstimator.py = EST, vehicleSimulator.py = SIM).
+ *
+ * Observer step (Estimator.GS_LPV_Est, EST:349-398, with Continuous_AB_Comp EST:402-436 and L_Gain_Comp EST:439-492):
+ *   x = [vx vy psiDot x y yaw], y = [vx psiDot x y yaw] (C selects states 0, 2, 3, 4, 5: EST:248-252), u = [servo, motor];
+ *   t = k dt with dt = 1 / loop_rate and k the number of observer steps including this one (k = 1 on the first step);
+ *   scheduling variables (vx, vy, theta) = (x[0], x[1], x[5]) when t > 0.02, else (y[0], 0, y[4]) (EST:368-376);
+ *   A_obs(vx, vy, theta, steer), B_obs(steer) with the observer's own constants lf = lr = 0.125, m = 1.98, I = 0.03,
+ *   Cf = Cr = 60, mu = 0.05 (independent of lpvmpc_config);
+ *   polytope HS when vx > lim_ls[0][1], else LS; 16 vertex weights from the limit rows 0, 1, 3, 5 (vx, vy, steer, theta) in
+ *   EST:475-491's order (vertex i: bit 3 = vx, bit 2 = vy, bit 1 = steer, bit 0 = theta; a set bit takes 1 - M).  Like the
+ *   reference the weights are NOT clamped: outside the polytope some are negative and the gain is extrapolated;
+ *   L = sum_i mu_i Llmi[:, :, i];  x+ = x + (dt (A + L C) x + dt B u - dt L y).
+ *
+ * Sensors (SIM:222-329 and the estimator's callbacks EST:600-760), drawn from the plant state after each plant step:
+ *   IMU yaw = yaw + n_psi, IMU psiDot = psiDot + n_psiDot; GPS x, y = x + n_x, y + n_y, published when the publish counter
+ *   exceeds thUpdate = (1 / gps_freq) / dt_sim (then the counter resets to 0, else it increments; the estimator keeps the
+ *   last PUBLISHED value, initially the plant's start position); encoder v = sqrt(vx^2 + vy^2) + n_v, and the estimator's
+ *   encoder reading becomes 0 after more than 40 consecutive unchanged readings (EST:733-741).  While t <= 0.02 the
+ *   estimator measures y = [x_est[0], IMU psiDot, GPS x, GPS y, plant yaw] (EST:330-333).
+ *   Each noise n = clip(std * g, -std * n_bound, std * n_bound) with g standard normal.
+ *
+ * Noise generator (counter based; a numpy restatement reproduces it):
+ *   mix(z)   = splitmix64 finaliser: z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *              (all arithmetic modulo 2^64);
+ *   key      = mix(mix(seed + 0x9E3779B97F4A7C15 * (vid + 1)) ^ (8 * step + channel)), where vid = vehicle_offset + b is the
+ *              global vehicle id, step = k (the observer step, from 1) and channel 0..4 = psi, psiDot, x, y, v;
+ *   u1       = ((mix(key + 0x9E3779B97F4A7C15) >> 11) + 1) * 2^-53  in (0, 1],
+ *   u2       = (mix(key + 2 * 0x9E3779B97F4A7C15) >> 11) * 2^-53    in [0, 1),
+ *   g        = sqrt(-2 log u1) * cos(2 pi u2).
+ *   A vehicle's noise therefore depends on (seed, vid, step, channel) only: not on B, the batch or the GPU.
+ *
+ * Schedule inside a control tick of a fleet with an observer, for each of the n_sub plant steps: plant step under the
+ * current command, sensors from the new plant state, one observer step with u = [servo, motor] (delays 0).  The controller's
+ * measurement is then built from the ESTIMATE instead of the plant: [max(vx, 0.01), vy, psiDot] and the map's local frame of
+ * (x, y, yaw), with quirk Q9 as without an observer.  The estimate starts at [init_vx, 0, 0, x0, y0, yaw0] of plant0.
+ * Pinned by tests/golden/estimator/estimator.npz (generated from the reference's own Estimator and Simulator) and the
+ * numpy restatement in tests/_observer_ref.py. */
+typedef struct lpvmpc_observer_config {
+    double  L_ls[6 * 5 * 16];       /* Llmi of the low-speed polytope, [6][5][16] row-major (Estimator_Gains_LS.mat, EST:230) */
+    double  lim_ls[6 * 2];          /* SchedVars_Limits of the low-speed polytope, [6][2] = {min, max} per scheduling row */
+    double  L_hs[6 * 5 * 16];       /* the same for the high-speed polytope (Estimator_Gains_HS.mat, EST:233-234) */
+    double  lim_hs[6 * 2];
+    double  loop_rate;              /* 200 Hz: dt = 1 / loop_rate                               EST:47 */
+    double  init_vx;                /* initial vx estimate (simulator/init_vx)                  EST:262 */
+    double  psi_std, psiDot_std;    /* IMU noise (simulator/psi_std, psiDot_std)                MAIN_LAUNCH:60-87: 0 */
+    double  x_std, y_std;           /* GPS noise                                                0 */
+    double  v_std;                  /* encoder noise                                            0 */
+    double  n_bound;                /* clipping bound in standard deviations                    0.5 */
+    double  gps_freq;               /* GPS publish rate (Hz)                                    1000 */
+    uint64_t seed;                  /* noise key */
+    int64_t vehicle_offset;         /* global id of vehicle 0 of this fleet (sharded fleets draw like one big fleet) */
+} lpvmpc_observer_config;
+
+/* The launch file's sensor values (every std 0, n_bound 0.5, gps_freq 1000), loop_rate 200, init_vx 0.2, seed 0, offset 0;
+ * the gain and limit tables are zeroed: the caller supplies them (the reference loads them from its .mat files). */
+void lpvmpc_observer_default_config(lpvmpc_observer_config *cfg);
+
+/* Attach (cfg != NULL) or remove (cfg == NULL) the estimator of a controller handle.  It takes effect at the next
+ * lpvmpc_cl_init or lpvmpc_cascade_init on that handle (the controller handle of a cascade); a handle that never calls this
+ * behaves exactly as without an estimator.  In a cascade both nodes measure the estimate: the controller's racing-phase
+ * measurement (CMAIN:179-180,198-283) and the planner's first state (PMAIN:141) read it in place of the plant, with the same
+ * per-plant-step schedule; the cascade starts at the lap event of a running vehicle, so its estimate starts at the plant state
+ * [vx, vy, psiDot, x, y, yaw] of plant0 (GPS hold at the start position, step counter 0). */
+int lpvmpc_observer_setup(lpvmpc_handle *h, const lpvmpc_observer_config *cfg);
+
+/* The fleet's or cascade's estimator state (synchronises like lpvmpc_cl_read; either pointer may be NULL): est [B][6] the current estimate,
+ * meas [B][5] the measurement y of the latest observer step. */
+int lpvmpc_observer_read(lpvmpc_handle *h, double *est, double *meas);
+
+/* One observer step for each of B independent instances (tests, the drop-in GainScheduledLPVObserver): est [B][6] in/out,
+ * y [B][5], u [B][2] = {servo, motor}, k [B] the step index (t = k dt).  aux [B][78] (may be NULL) receives L_gain [6][5],
+ * A_obs [6][6] and B_obs [6][2] of the step.  Refused while the handle runs a fleet, like the other batch calls. */
+int lpvmpc_observer_step_batch(lpvmpc_handle *h, int32_t B, const lpvmpc_observer_config *cfg, double *est, const double *y,
+                               const double *u, const int32_t *k, double *aux);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,8 @@ __path__ = [_os.path.join(_os.path.dirname(_os.path.dirname(_os.path.abspath(__f
 from .api import (BatchedSolver, LPV_MPC_Planner, PathFollowingLPV_MPC, PlannerHandoff,  # noqa: E402,F401
                   body_frame_errors, handoff_operators)
 from ._ffi import LpvMpcError, STATUS_TEXT  # noqa: E402,F401
+from .observer import GainScheduledLPVObserver, observer_config, observer_vertex_gains  # noqa: E402,F401
 from .track import Map  # noqa: E402,F401
 
 __all__ = ["BatchedSolver", "PathFollowingLPV_MPC", "LPV_MPC_Planner", "PlannerHandoff", "body_frame_errors", "handoff_operators",
-           "Map", "LpvMpcError", "STATUS_TEXT"]
+           "Map", "LpvMpcError", "STATUS_TEXT", "GainScheduledLPVObserver", "observer_config", "observer_vertex_gains"]
