@@ -2448,8 +2448,8 @@ struct Solver {
     // update also files the state and the deltas in the arrays, where the checks, the re-factorisation, parking and the polish read
     // them (update_s, `want`).  The operations and their order are those of update()'s element() and of At_elem, written with explicit
     // fused operations (rhs_form): every output word is unchanged (tools/ab_equal.py).
-    // Handles with steeringDelay > 0 (a third box row in the right-hand side: a uniform branch the fused block does not carry) stay on
-    // the LDS form of the phases.
+    // Handles with steeringDelay > 0 (a third box row in the right-hand side: a uniform branch the fused block does not carry) never run
+    // these kernels: launch_solve sends delayed controller handles to the DPP kernel <6, 20, 2> (and launch_one refuses them).
     static constexpr bool kRegState = kFuse2;
     static_assert(!kFuse2 || kStride == 128, "element state in registers: the second round / second wavefront own elements 64 and up (el_load_s, BZ)");
     // the thread's elements in the fused element phases: e0, e1 (-1: none), e1c (a lane without a second element repeats its first one)
@@ -3376,9 +3376,9 @@ struct Solver {
 #else
             if constexpr (kFour) iterate4(sigma, alpha, checked);
             else if constexpr (kMf && kRegState) {
-                // the element state lives in registers (see kRegState); handles with steeringDelay > 0 run the LDS form
-                // (launch_solve sends controller handles with steeringDelay > 0 -- a third box row in the right-hand side, which the fused
-                // blocks do not carry -- to the DPP kernel: these kernels have no LDS form of the element phases)
+                // the element state lives in registers (see kRegState).  These kernels have no LDS form of the element phases for
+                // steeringDelay > 0 (a third box row in the right-hand side, which the fused blocks do not carry): launch_solve sends
+                // delayed controller handles to the DPP kernel <6, 20, 2>, and launch_one refuses to launch them here
                 rhs_s(sigma);
                 const MfLane m = mf_lane();     // (in front of the barrier: the sweeps' lane constants form while the stores drain)
                 sync();
@@ -3677,7 +3677,15 @@ __global__ void __launch_bounds__(64 * NW, (min_waves_per_simd<NT, NW, GS>())) a
 
 template <int NX, int NT, int NW, bool MF = false, bool GS = false, bool TAIL = false>
 static hipError_t launch_one(const DevCfg &cfg, const DevCfg *dcfg, const SolveArgs &a, hipStream_t stream) {
-    const size_t lds = Solver<NX, NT, NW, MF, GS, TAIL>::lds_doubles(cfg.N) * sizeof(double);
+    using S = Solver<NX, NT, NW, MF, GS, TAIL>;
+    // The controller kernels whose element phases carry two box rows per variable (the element state in registers, kRegState; the
+    // four-wavefront relay, kFour) have no third row for the pinned steering of steeringDelay > 0 (CTRL:518-527): launching one would
+    // solve another QP without a word of warning.  launch_solve never routes such a handle here; this keeps every build so (the
+    // diagnostic LPVMPC_DEV_* builds skip its routing) -- the call fails with LPVMPC_E_HIP instead.
+    if constexpr (NX == 6 && (S::kRegState || S::kFour)) {
+        if (cfg.steering_delay > 0) return hipErrorNotSupported;
+    }
+    const size_t lds = S::lds_doubles(cfg.N) * sizeof(double);
     // The LDS opt-in is a per-function AND per-device attribute: remember it per (instantiation, device ordinal).  Handles on
     // different devices may launch from different threads (lpvmpc.h: thread-safe across handles), hence the atomic mask.
     static std::atomic<uint64_t> attr_mask[4];           // 256 device ordinals
@@ -3718,7 +3726,7 @@ hipError_t launch_solve(const DevCfg &cfg, const DevCfg *dcfg, const SolveArgs &
 #if defined(LPVMPC_DEV_TAIL_ONLY)
     return hipErrorInvalidValue;       // development builds (seconds instead of minutes): the tail kernels only, for looking at their assembly
 #elif defined(LPVMPC_DEV_MAIN_ONLY)
-    return launch_one<6, 20, 2, true>(cfg, dcfg, a, stream);      // ... or the headline kernel only (no steeringDelay > 0 in this build)
+    return launch_one<6, 20, 2, true>(cfg, dcfg, a, stream);      // ... or the headline kernel only (steeringDelay > 0: refused by launch_one)
 #elif defined(LPVMPC_DEV_C10)
     return launch_one<6, 10, 1>(cfg, dcfg, a, stream);      // ... or the one-wavefront controller kernel at N = 10
 #elif defined(LPVMPC_DEV_C20_4W)

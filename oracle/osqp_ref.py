@@ -162,6 +162,68 @@ def ctrl_tick_batch(w, nthreads=1, params=None, warm=None, shift=True):
     return dict(xPred=xPred, uPred=uPred, status=status, iters=iters, z=z, y=y)
 
 
+def ctrl_delay_ordering(N, delay, nx=6, nu=2):
+    """Stage-wise KKT ordering of a controller QP with ``delay`` pinned-steering rows: the order oracle/lpv_ref.c hands the
+    solver for delay 0 (x_0 rows, then per stage its variables, box rows and the dynamics rows into the next stage), with
+    the pin of stage k (row 6N + (N+1)nx + k of ctrl_build_qp) placed after stage k's box rows."""
+    nz = (N + 1) * nx + N * nu
+    mi = 6 * N
+    perm = [nz + mi + r for r in range(nx)]
+    for k in range(N + 1):
+        perm += [k * nx + a for a in range(nx)]
+        if k < N:
+            perm += [(N + 1) * nx + k * nu + j for j in range(nu)]
+            perm += [nz + 2 * k, nz + 2 * k + 1] + [nz + 2 * N + 4 * k + t for t in range(4)]
+            if k < delay:
+                perm.append(nz + mi + (N + 1) * nx + k)
+            perm += [nz + mi + (k + 1) * nx + r for r in range(nx)]
+    return np.array(perm, dtype=np.int32)
+
+
+def ctrl_tick_batch_delay(w, nthreads=1, params=None):
+    """Controller tick with steeringDelay = d = u_old.shape[1] - 2 for a batch: per instance the LPV roll-out
+    (lpv_ref.ctrl_lpv_prediction), the reference's QP with d pinned-steering rows (lpv_ref.ctrl_build_qp, CTRL:518-527) and
+    the OSQP restatement.  ``w`` is a workload dict as for ctrl_tick_batch, with ``u_old`` in the device's layout
+    [OldSteering[0], OldAccelera[0], OldSteering[1..d]] (B, 2 + d).  Elimination order: the stage-wise one of
+    ctrl_delay_ordering (the C tick's order at d = 0); on tests/golden/ctrl_n20_delay.npz it reproduces the reference's
+    status, iteration count and polish flag of every case (as does solve_qp's RCM order, which the class-D rule of
+    tests/_tolerance.py takes as the other order).  Returns dict(xPred, uPred, status, iters, z, y, polish); ``nthreads``
+    solves run at a time (the solver releases the GIL)."""
+    from concurrent.futures import ThreadPoolExecutor
+    from . import lpv_ref as L
+    p = dict(L.DEFAULT_PARAMS)
+    if params:
+        p.update(params)
+    N = int(w["N"])
+    x0 = np.asarray(w["x0"], np.float64); B = x0.shape[0]
+    u_old = np.asarray(w["u_old"], np.float64).reshape(B, -1)
+    d = u_old.shape[1] - 2
+    perm = ctrl_delay_ordering(N, d)
+    curv = w["curv_s"]
+    nz, m = (N + 1) * 6 + N * 2, 6 * N + (N + 1) * 6 + d
+
+    def one(j):
+        # no answer (NaN, UNSOLVED -10): a roll-out that leaves the track table (the reference raises, UTIL:44-48) or a KKT
+        # factorisation that breaks down
+        try:
+            S, A, Bm = L.ctrl_lpv_prediction(p, w["dt"], N, w["track"], x0[j], w["u_prev"][j], w["vel_ref"][j],
+                                             None if curv is None else curv[j], w["cf_new"], w["lap"])
+            qp = L.ctrl_build_qp(w["Q"], w["R"], w["dR"], N, A, Bm, x0[j], u_old[j, :2], w["vel_ref"][j], p["max_vel"],
+                                 steer_hist=u_old[j, 2:])
+            r = solve_qp(qp.P, qp.q, qp.A, qp.l, qp.u, perm=perm)
+        except (ValueError, RuntimeError):
+            return np.full(nz, np.nan), np.full(m, np.nan), -10, 0, 0
+        return r.x, r.y, r.info.status_val, r.info.iter, r.info.status_polish
+
+    with ThreadPoolExecutor(max_workers=max(1, min(16, int(nthreads)))) as ex:
+        res = list(ex.map(one, range(B)))
+    z = np.array([r[0] for r in res]).reshape(B, nz)
+    out = dict(xPred=z[:, :(N + 1) * 6].reshape(B, N + 1, 6).copy(), uPred=z[:, (N + 1) * 6:].reshape(B, N, 2).copy(), z=z,
+               y=np.array([r[1] for r in res]).reshape(B, m), status=np.array([r[2] for r in res], np.int32).reshape(B),
+               iters=np.array([r[3] for r in res], np.int32).reshape(B), polish=np.array([r[4] for r in res], np.int32).reshape(B))
+    return out
+
+
 def plan_tick_batch(w, nthreads=1, params=None):
     """Whole planner tick for a batch in C (oracle/lpv_ref.c); ``w`` as produced by workloads.planner_batch."""
     from .lpv_ref import DEFAULT_PARAMS

@@ -55,12 +55,16 @@ def class_d(w, kind, j, out, ref):
 
 
 def instance_qp(w, kind, j):
-    """(P, q, A, l, u) of instance j of a workload dict, assembled on the host as the reference does."""
+    """(P, q, A, l, u) of instance j of a workload dict, assembled on the host as the reference does.  A controller u_old with
+    more than two columns is the device's layout of a handle with steeringDelay = d, [OldSteering[0], OldAccelera[0],
+    OldSteering[1..d]]: the QP then carries the d pinned-steering rows (CTRL:518-527)."""
     N = int(w["N"]); p = dict(P)
     if kind == "controller":
         S, A, B = L.ctrl_lpv_prediction(p, w["dt"], N, w["track"], w["x0"][j], w["u_prev"][j], w["vel_ref"][j],
                                         None if w["curv_s"] is None else w["curv_s"][j], w["cf_new"], w["lap"])
-        return L.ctrl_build_qp(w["Q"], w["R"], w["dR"], N, A, B, w["x0"][j], w["u_old"][j], w["vel_ref"][j], p["max_vel"])
+        u_old = np.asarray(w["u_old"][j], float).reshape(-1)
+        return L.ctrl_build_qp(w["Q"], w["R"], w["dR"], N, A, B, w["x0"][j], u_old[:2], w["vel_ref"][j], p["max_vel"],
+                               steer_hist=u_old[2:])
     S, A, B = L.plan_lpv_prediction(p, w["dt"], N, w["track"], w["x0"][j], w["curv_s"][j], w["u_prev"][j])
     mey = float(np.broadcast_to(w["max_ey"], (w["x0"].shape[0],))[j])
     return L.plan_build_qp(w["Q"], w["R"], w["dR"], w["L_cf"], N, A, B, w["x0"][j], w["u_old"][j], mey, p["max_vel"], p["min_vel"])

@@ -220,3 +220,49 @@ def test_planner_result_is_insensitive_to_the_rho_update_interval(name, interval
             base[i] = float(np.max(np.abs(r.x - xs)))
     if base:
         print("%s interval %d: distance to x* (reported only) max %.2e" % (name, interval, max(base.values())))
+
+
+def _delay_fixture_workload(c, track):
+    """One fixture case of ctrl_n20_delay as a B = 1 workload dict, u_old in the device's layout
+    [OldSteering[0], OldAccelera[0], OldSteering[1..d]]."""
+    N = int(c["N"])
+    v = np.asarray(c["vel_ref"], float).reshape(-1)
+    return dict(N=N, dt=float(c["dt"]), Q=c["Q"], R=c["R"], dR=c["dR"], track=track, x0=c["x0"][None],
+                u_prev=c["u_prev"][None], vel_ref=np.concatenate([v[:N], v[-1:]])[None], curv_s=c["curv_ref"][None],
+                u_old=np.concatenate([c["old_u"], c["steer_hist"]])[None], cf_new=float(c["cf_new"]), lap=int(c["lap"]))
+
+
+def test_delay_tick_matches_reference_fixture():
+    """osqp_ref.ctrl_tick_batch_delay (the oracle of the GPU steering-delay matrix) reproduces the reference's own solves
+    at steeringDelay = 1, 2, 3 (CTRL:518-527): status, iteration count, polish flag and xPred / uPred at the tolerances of
+    test_controller_steering_delay_matches_reference_fixture, on every case.  Its stage-wise elimination order and solve_qp's
+    RCM order both reproduce the fixture's iteration counts."""
+    tab = L.TrackMap("oval", 0.2).PointAndTangent
+    cs = cases("ctrl_n20_delay")
+    assert len(cs) == 8
+    for i, c in enumerate(cs):
+        d = int(c["steer_hist"].size)
+        r = O.ctrl_tick_batch_delay(_delay_fixture_workload(c, tab), nthreads=4)
+        assert (int(r["status"][0]), int(r["iters"][0]), int(r["polish"][0])) == \
+            (int(c["status_orc"]), int(c["iter_orc"]), int(c["polish_orc"])), (i, r["status"], r["iters"], r["polish"])
+        tol = 1e-6 if int(c["polish_orc"]) == 1 else 2e-4
+        assert np.max(np.abs(r["xPred"][0] - c["xPred"])) <= tol * max(1.0, float(np.max(np.abs(c["xPred"])))), i
+        assert np.max(np.abs(r["uPred"][0] - c["uPred"])) <= tol, i
+        assert np.max(np.abs(r["uPred"][0, :d, 0] - c["steer_hist"])) <= 2e-4, i          # the pins hold
+        assert r["y"].shape == (1, 6 * 20 + 6 * 21 + d)
+        qp = L.ctrl_build_qp(c["Q"], c["R"], c["dR"], 20, c["A"], c["B"], c["x0"], c["old_u"], c["vel_ref"], 5.0,
+                             steer_hist=c["steer_hist"])
+        rr = O.solve_qp(qp.P, qp.q, qp.A, qp.l, qp.u)
+        assert (rr.info.status_val, rr.info.iter) == (int(c["status_orc"]), int(c["iter_orc"])), i
+
+
+@pytest.mark.parametrize("N", [9, 20])
+def test_delay_tick_without_delay_is_the_c_tick(N):
+    """At steeringDelay = 0 the delay tick solves the QP of the C tick (oracle/lpv_ref.c) in the same elimination order:
+    equal statuses and iteration counts on a lap-0 batch, whose roll-out reads the map."""
+    from lpvmpc import workloads
+    w = dict(workloads.controller_batch(24, N=N, seed=31), curv_s=None, lap=0)
+    a, b = O.ctrl_tick_batch(w, nthreads=4), O.ctrl_tick_batch_delay(w, nthreads=4)
+    assert np.array_equal(a["status"], b["status"]) and np.array_equal(a["iters"], b["iters"]), (a["iters"], b["iters"])
+    ok = a["status"] == 1
+    assert ok.all() and np.max(np.abs(a["uPred"] - b["uPred"])) <= 1e-9 and np.max(np.abs(a["xPred"] - b["xPred"])) <= 1e-9
