@@ -71,6 +71,12 @@ class ObserverConfig(C.Structure):
                 ("v_std", _d), ("n_bound", _d), ("gps_freq", _d), ("seed", C.c_uint64), ("vehicle_offset", C.c_int64)]
 
 
+class RaceConfig(C.Structure):
+    """Mirror of ``struct lpvmpc_race_config`` (include/lpvmpc.h)."""
+    _fields_ = [("laps", _i), ("n_sub_lap0", _i), ("n_sub", _i * 3), ("q9_swap", _i), ("half_width", _d), ("slack", _d),
+                ("plan_max_ey", _d), ("dt_sim", _d), ("mu_sim", _d)]
+
+
 OBSERVER_AUX = 30 + 36 + 12      # L_gain [6][5], A_obs [6][6], B_obs [6][2] per instance (lpvmpc_observer_step_batch)
 
 EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_destroy", "lpvmpc_last_error", "lpvmpc_last_error_code",
@@ -81,7 +87,9 @@ EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_d
            "lpvmpc_cl_init", "lpvmpc_cl_tick", "lpvmpc_cl_read", "lpvmpc_cl_release", "lpvmpc_join", "lpvmpc_resume_time_stats", "lpvmpc_defer_stats",
            "lpvmpc_handoff_default_config", "lpvmpc_handoff_length", "lpvmpc_handoff_operators", "lpvmpc_handoff_setup",
            "lpvmpc_handoff_batch", "lpvmpc_cascade_init", "lpvmpc_cascade_tick", "lpvmpc_cascade_read", "lpvmpc_cascade_alive_ticks",
-           "lpvmpc_observer_default_config", "lpvmpc_observer_setup", "lpvmpc_observer_read", "lpvmpc_observer_step_batch")
+           "lpvmpc_observer_default_config", "lpvmpc_observer_setup", "lpvmpc_observer_read", "lpvmpc_observer_step_batch",
+           "lpvmpc_solve_batch_masked", "lpvmpc_race_default_config", "lpvmpc_race_init", "lpvmpc_race_tick", "lpvmpc_race_read",
+           "lpvmpc_race_laps", "lpvmpc_race_predictions")
 
 _lib = None
 
@@ -175,6 +183,20 @@ def load():
     lib.lpvmpc_observer_step_batch.argtypes = [vp, _i, P(ObserverConfig), vp, vp, vp, vp, vp]
     for name in ("lpvmpc_observer_setup", "lpvmpc_observer_read", "lpvmpc_observer_step_batch"):
         getattr(lib, name).restype = C.c_int
+    try:        # (older builds loaded by tools/ab_equal.py have no race engine)
+        lib.lpvmpc_solve_batch_masked.argtypes = [vp, _i, vp, vp, vp, vp, vp, vp, _d, _i, vp, vp, vp, vp, vp, vp, vp]
+        lib.lpvmpc_race_default_config.argtypes = [P(RaceConfig)]
+        lib.lpvmpc_race_default_config.restype = None
+        lib.lpvmpc_race_init.argtypes = [vp, vp, vp, _i, vp, vp, P(RaceConfig)]
+        lib.lpvmpc_race_tick.argtypes = [vp, _i]
+        lib.lpvmpc_race_read.argtypes = [vp] + [vp] * 10
+        lib.lpvmpc_race_laps.argtypes = [vp, vp, vp]
+        lib.lpvmpc_race_predictions.argtypes = [vp, vp, vp]
+        for name in ("lpvmpc_solve_batch_masked", "lpvmpc_race_init", "lpvmpc_race_tick", "lpvmpc_race_read", "lpvmpc_race_laps",
+                     "lpvmpc_race_predictions"):
+            getattr(lib, name).restype = C.c_int
+    except AttributeError:
+        pass
     for name in ("lpvmpc_handoff_length", "lpvmpc_handoff_operators", "lpvmpc_handoff_setup", "lpvmpc_handoff_batch",
                  "lpvmpc_cascade_init", "lpvmpc_cascade_tick", "lpvmpc_cascade_read"):
         getattr(lib, name).restype = C.c_int
@@ -197,6 +219,12 @@ def default_config(kind):
 def default_handoff_config():
     cfg = HandoffConfig()
     load().lpvmpc_handoff_default_config(C.byref(cfg))
+    return cfg
+
+
+def default_race_config():
+    cfg = RaceConfig()
+    load().lpvmpc_race_default_config(C.byref(cfg))
     return cfg
 
 

@@ -101,6 +101,7 @@ class BatchedSolver:
             raise LpvMpcError(lib.lpvmpc_last_error_code() or _ffi.E_ARG, msg.decode() if msg else "lpvmpc_create failed")
         self._ho_M = 0                       # samples per My_Planning array once handoff_setup() has run
         self._cas = self._cas_planner = None
+        self._race = None                    # (B, laps, tt, planner) while this engine owns a race
 
     # -- lifetime --------------------------------------------------------------------------------
     def close(self):
@@ -219,6 +220,33 @@ class BatchedSolver:
                                                ptr(o["status"]), ptr(o["iters"]), ptr(o["resid"]), ptr(o["polish"])))
         return o
 
+    def solve_batch_masked(self, active, x0, u_prev, vel_ref=None, curv_s=None, u_old=None, max_ey=None, cf_new=60.0, lap=1, out=None):
+        """``solve`` for the instances with ``active[i] != 0`` only.  The others are not solved and their rows of ``out`` (a dict
+        as ``solve`` returns; fresh arrays of zeros when None) are left as they are.  Returns ``out``."""
+        N, nx = self.N, self.nx
+        x0 = f64(x0).reshape(-1, nx)
+        B = x0.shape[0]
+        act = np.ascontiguousarray(active, np.int32)
+        if act.shape != (B,):
+            raise ValueError("active must have shape (%d,)" % B)
+        u_prev = f64(u_prev, (B, N, 2), "u_prev")
+        ctrl = self.kind == KIND_CONTROLLER
+        vel_ref = f64(vel_ref, (B, N + 1), "vel_ref") if ctrl else None
+        if curv_s is not None:
+            curv_s = f64(curv_s, (B, N) if ctrl else (B, N + 1), "curv_ref" if ctrl else "SS")
+        u_old = None if u_old is None else f64(u_old, (B, 2 + self.cfg.steering_delay), "u_old")
+        max_ey = None if ctrl else f64(np.broadcast_to(np.asarray(max_ey, float), (B,)), (B,), "max_ey")
+        if out is None:
+            out = {k: np.zeros_like(v) for k, v in self._outputs(B).items()}
+        for k, v in self._outputs(B).items():
+            a = out[k]
+            if not (isinstance(a, np.ndarray) and a.shape == v.shape and a.dtype == v.dtype and a.flags.c_contiguous):
+                raise ValueError("out[%r] must be a C-contiguous %s array of shape %s" % (k, v.dtype, v.shape))
+        self._chk(self._lib.lpvmpc_solve_batch_masked(self._h, B, ptr(x0), ptr(u_prev), ptr(vel_ref), ptr(curv_s), ptr(u_old),
+                                                      ptr(max_ey), float(cf_new), int(lap), ptr(out["xPred"]), ptr(out["uPred"]),
+                                                      ptr(out["status"]), ptr(out["iters"]), ptr(out["resid"]), ptr(out["polish"]), ptr(act)))
+        return out
+
     # -- caller-side helpers and the closed-loop fleet (SURVEY 8f row f1) ------------------------------------
     def local_position(self, xy_psi, half_width, slack):
         """Batched Map.getLocalPosition: [B,3] -> [B,4] = (s, ey, epsi, inside)."""
@@ -313,6 +341,7 @@ class BatchedSolver:
         self._chk(self._lib.lpvmpc_cl_release(self._h))
         self._cas = None
         self._cas_planner = None
+        self._race = None
 
     def cascade_init(self, planner, plant0, cmd0, uPred0, lap0=1, half_width=0.3, slack=0.15, plan_max_ey=0.2, q9_swap=True,
                      n_sub=(7, 7, 6), dt_sim=0.005, mu_sim=0.05):
@@ -351,6 +380,66 @@ class BatchedSolver:
         out = np.empty(self._cas[0], np.int32)
         self._chk(self._lib.lpvmpc_cascade_alive_ticks(self._h, ptr(out)))
         return out
+
+    # -- race engine: lap 0, per-vehicle lap events, racing (lpvmpc_race_*) ------------------------------------
+    def race_init(self, tt, planner, plant0, half_track0=None, **cfg):
+        """Start a race owned by this PATH controller engine, with ``tt`` (racing tuning) and ``planner`` (handoff_setup done).
+        plant0 [B,8]; half_track0 [B] (HalfTrack at the start, default 0); ``cfg``: fields of ``lpvmpc_race_config`` (laps,
+        n_sub_lap0, n_sub, q9_swap, half_width, slack, plan_max_ey, dt_sim, mu_sim)."""
+        p0 = f64(plant0).reshape(-1, 8)
+        B = p0.shape[0]
+        c = _ffi.default_race_config()
+        for k, v in cfg.items():
+            if k == "n_sub":
+                v = list(v)
+                if len(v) != 3:
+                    raise ValueError("n_sub must have 3 entries")
+                for i in range(3):
+                    c.n_sub[i] = int(v[i])
+            elif k in ("laps", "n_sub_lap0", "q9_swap"):
+                setattr(c, k, int(v))
+            elif k in ("half_width", "slack", "plan_max_ey", "dt_sim", "mu_sim"):
+                setattr(c, k, float(v))
+            else:
+                raise TypeError("unknown race option %r" % k)
+        ht = None if half_track0 is None else np.ascontiguousarray(np.broadcast_to(np.asarray(half_track0), (B,)), np.int32)
+        self._chk(self._lib.lpvmpc_race_init(self._h, tt._h, planner._h, B, ptr(p0), ptr(ht), C.byref(c)))
+        self._race = (B, int(c.laps), tt, planner)           # (keeps the two other engines alive as long as the race)
+
+    def race_tick(self, n_ticks=1):
+        self._chk(self._lib.lpvmpc_race_tick(self._h, int(n_ticks)))
+
+    def _race_B(self, who):
+        if self._race is None:
+            raise LpvMpcError(_ffi.E_ARG, "%s: call race_init first" % who)
+        return self._race[0]
+
+    def race_read(self):
+        """Synchronise and return the fleet: plant, local, cmd, phase (0 lap 0, 1 racing, 2 finished, 3 lost), lap, iters / status
+        (the vehicle's controller solve of the last tick; iters 0 when it did not solve), plan_iters / plan_status, ticks."""
+        B = self._race_B("race_read")
+        o = dict(plant=np.empty((B, 8)), local=np.empty((B, 6)), cmd=np.empty((B, 2)), phase=np.empty(B, np.int32),
+                 lap=np.empty(B, np.int32), iters=np.empty(B, np.int32), status=np.empty(B, np.int32),
+                 plan_iters=np.empty(B, np.int32), plan_status=np.empty(B, np.int32))
+        t = np.zeros(1, np.int32)
+        self._chk(self._lib.lpvmpc_race_read(self._h, ptr(o["plant"]), ptr(o["local"]), ptr(o["cmd"]), ptr(o["phase"]), ptr(o["lap"]),
+                                             ptr(o["iters"]), ptr(o["status"]), ptr(o["plan_iters"]), ptr(o["plan_status"]), ptr(t)))
+        o["ticks"] = int(t[0])
+        return o
+
+    def race_laps(self):
+        """lap_step [B, laps+2] (plant step at which each lap started, -1 not yet) and alive_ticks [B]."""
+        B = self._race_B("race_laps")
+        ls = np.empty((B, self._race[1] + 2), np.int32); al = np.empty(B, np.int32)
+        self._chk(self._lib.lpvmpc_race_laps(self._h, ptr(ls), ptr(al)))
+        return ls, al
+
+    def race_predictions(self):
+        """(path uPred, tt uPred), each [B, N, 2]: the u_prev of the two controllers' next roll-out."""
+        B = self._race_B("race_predictions")
+        pu = np.empty((B, self.N, 2)); tu = np.empty((B, self.N, 2))
+        self._chk(self._lib.lpvmpc_race_predictions(self._h, ptr(pu), ptr(tu)))
+        return pu, tu
 
     # -- device-pointer entry point (torch tensors or raw integers) -----------------------------------
     def solve_dev(self, B, x0, u_prev, vel_ref, curv_s, u_old, max_ey, xPred, uPred, status=None, iters=None,
@@ -651,3 +740,48 @@ def body_frame_errors(x, y, psi, xd, yd, psid, s0, vx, vy, curv, dt):
     epsi = 2 * np.pi + d if d < -np.pi else (d - 2 * np.pi if d > np.pi else d)            # TRACK:413-421 wrap()
     s = s0 + ((vx * np.cos(epsi) - vy * np.sin(epsi)) / (1 - ey * curv)) * dt
     return s, ex, ey, epsi
+
+
+class RaceFleet(object):
+    """A fleet of B vehicles running the reference's whole experiment on the device (lpvmpc_race_*): lap 0 under the
+    path-following controller at 1 m/s, each vehicle's own lap event, then planner + trajectory-tracking controller until it has
+    driven ``laps`` racing laps.  Three engines with the reference's tunings (CTRL_TUNINGS["path"], CTRL_TUNINGS["race"], the
+    PLAN_* weights).  ``options``: race options of ``BatchedSolver.race_init`` (n_sub_lap0, n_sub, q9_swap, plan_max_ey, dt_sim,
+    mu_sim) and engine settings (e.g. kernel_variant) applied to all three engines."""
+
+    def __init__(self, track_map, plant0, laps=1, N=20, Np=40, half_track0=None, device=0, **options):
+        from .workloads import CTRL_TUNINGS, PLAN_L, PLAN_Q, PLAN_R, PLAN_dR
+        race_keys = ("n_sub_lap0", "n_sub", "q9_swap", "plan_max_ey", "dt_sim", "mu_sim")
+        race_opts = {k: v for k, v in options.items() if k in race_keys}
+        engine_opts = {k: v for k, v in options.items() if k not in race_keys}
+        Qp, Rp, dRp = CTRL_TUNINGS["path"]; Qr, Rr, dRr = CTRL_TUNINGS["race"]
+        tab = track_map.PointAndTangent
+        self.map = track_map
+        self.path = BatchedSolver("controller", N, 1.0 / 30.0, Qp, Rp, dRp, track=tab, device=device)
+        self.tt = BatchedSolver("controller", N, 1.0 / 30.0, Qr, Rr, dRr, track=tab, device=device)
+        self.planner = BatchedSolver("planner", Np, 0.05, PLAN_Q, PLAN_R, PLAN_dR, L_cf=PLAN_L, track=tab, device=device)
+        for e in (self.path, self.tt, self.planner):
+            for k, v in engine_opts.items():
+                e.set_option(k, int(v))
+        self.planner.handoff_setup()
+        self.dt_sim = float(race_opts.get("dt_sim", 0.005))
+        self.path.race_init(self.tt, self.planner, plant0, half_track0=half_track0, laps=laps, half_width=track_map.halfWidth,
+                            slack=track_map.slack, **race_opts)
+
+    def run(self, n_ticks):
+        """Enqueue n_ticks controller ticks (no synchronisation)."""
+        self.path.race_tick(n_ticks)
+
+    def state(self):
+        return self.path.race_read()
+
+    def lap_times(self):
+        """[B, laps+1] simulated seconds of lap 0, 1, ..., laps (NaN where the lap has not been completed)."""
+        ls, _ = self.path.race_laps()
+        d = (ls[:, 1:] - ls[:, :-1]).astype(float) * self.dt_sim
+        d[(ls[:, 1:] < 0) | (ls[:, :-1] < 0)] = np.nan
+        return d
+
+    def close(self):
+        for e in (self.path, self.tt, self.planner):
+            e.close()

@@ -3670,7 +3670,7 @@ __global__ void __launch_bounds__(64 * NW, (min_waves_per_simd<NT, NW, GS>())) a
         entry = blockIdx.x;
         if (entry >= (n < a.pool_cap ? n : a.pool_cap)) return;
         __syncthreads();          // every wavefront has read the count before restore() stores the image over it
-    } else if (TAIL || inst >= a.B) return;
+    } else if (TAIL || inst >= a.B || (a.active && !a.active[inst])) return;      // (uniform: one scalar load per workgroup)
     Solver<NX, NT, NW, MF, GS, TAIL> s(*cfgp, smem);
     s.run(a, inst, entry);
 }

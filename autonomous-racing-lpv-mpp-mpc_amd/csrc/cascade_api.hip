@@ -131,6 +131,8 @@ extern "C" int lpvmpc_cascade_init(lpvmpc_handle *h, lpvmpc_handle *plan, int32_
     if (h->cfg.kind != LPVMPC_KIND_CONTROLLER || plan->cfg.kind != LPVMPC_KIND_PLANNER)
         return fail(h, LPVMPC_E_ARG, "lpvmpc_cascade_init: needs a controller handle and a planner handle");
     if (h->cfg.device != plan->cfg.device) return fail(h, LPVMPC_E_ARG, "lpvmpc_cascade_init: the two handles live on different devices");
+    if (h->race || h->race_owner || plan->race || plan->race_owner)
+        return fail(h, LPVMPC_E_ARG, "lpvmpc_cascade_init: a handle takes part in a race (lpvmpc_cl_release on its path handle ends it)");
     // the cascade's measurement kernel keeps u_old as [B][2]; a handle with steering delay reads it as [B][2 + delay]
     if (h->cfg.steering_delay != 0) return fail(h, LPVMPC_E_ARG, "lpvmpc_cascade_init: the fleet engines run the reference's steeringDelay = 0 (CMAIN:49)");
     if (!plan->d_Wop) return fail(h, LPVMPC_E_ARG, "lpvmpc_cascade_init: call lpvmpc_handoff_setup on the planner handle first");

@@ -51,12 +51,7 @@ __global__ void __launch_bounds__(64) cl_measure_kernel(const DevCfg *__restrict
                                                         double *__restrict__ local_state, double *__restrict__ u_old) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const double *p = plant + (size_t)b * 8;
-    double s, ey, epsi; int inside;
-    local_position(*cp, hw, slack, p[0], p[1], p[6], s, ey, epsi, inside);
-    double *ls = local_state + (size_t)b * 6;
-    ls[0] = p[2] < 0.01 ? 0.01 : p[2]; ls[1] = p[3]; ls[2] = p[7];
-    ls[3] = q9_swap ? ey : epsi; ls[4] = s; ls[5] = q9_swap ? epsi : ey;
+    cl_local(*cp, hw, slack, q9_swap, plant + (size_t)b * 8, local_state + (size_t)b * 6);
     u_old[b * 2 + 0] = cmd[b * 2 + 0]; u_old[b * 2 + 1] = cmd[b * 2 + 1];
 }
 

@@ -149,10 +149,11 @@ bool handoff_operators(int N, double dt, double interp_dt, int padlen, int ord, 
 // PMAIN:201-224, one lane per vehicle.  xPred [B][N+1][5]; SS [B][N+1] and pose [B][3] are carried between ticks
 // (in/out); sig [B][5][N] = xp, yp, yaw, vel, curv.
 __global__ void __launch_bounds__(64) plan_pose_kernel(const DevCfg *__restrict__ cp, int B, const double *__restrict__ xPred,
-                                                       double *__restrict__ SS, double *__restrict__ pose, double *__restrict__ sig) {
+                                                       double *__restrict__ SS, double *__restrict__ pose, double *__restrict__ sig,
+                                                       const int32_t *__restrict__ active) {
     const DevCfg &c = *cp;
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
+    if (b >= B || (active && !active[b])) return;
     const int N = c.N;
     const double *xp = xPred + (size_t)b * (N + 1) * 5;
     double *ss = SS + (size_t)b * (N + 1), *sg = sig + (size_t)b * 5 * N;
@@ -178,9 +179,10 @@ __global__ void __launch_bounds__(64) plan_pose_kernel(const DevCfg *__restrict_
 // refs [B][5][M] = operator x sig [B][5][N]; WT / FWT are the operators transposed ([N][M]) so that lanes (= output
 // samples) read consecutive words.  One workgroup per vehicle, the five signals staged in LDS.
 __global__ void __launch_bounds__(64) resample_kernel(int B, int N, int M, const double *__restrict__ WT, const double *__restrict__ FWT,
-                                                      const double *__restrict__ sig, double *__restrict__ refs) {
+                                                      const double *__restrict__ sig, double *__restrict__ refs, const int32_t *__restrict__ active) {
     __shared__ double sh[5 * LPVMPC_HANDOFF_MAX_N];
     const int b = blockIdx.x;
+    if (active && !active[b]) return;                                   // (uniform: the whole workgroup)
     for (int i = threadIdx.x; i < 5 * N; i += 64) sh[i] = sig[(size_t)b * 5 * N + i];
     __syncthreads();
     for (int m = threadIdx.x; m < M; m += 64) {
@@ -203,23 +205,10 @@ __global__ void __launch_bounds__(64) resample_kernel(int B, int N, int M, const
 __global__ void __launch_bounds__(64) plan_first_kernel(const DevCfg *__restrict__ cp, int B, const double *__restrict__ plant, double hw,
                                                         double slack, int q9_swap, double accel_rate, double *__restrict__ x0, double *__restrict__ xlast,
                                                         double *__restrict__ delta) {
-    const DevCfg &c = *cp;
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const int N = c.N;
-    const double *p = plant + (size_t)b * 8;
-    double s, ey, epsi; int inside;
-    local_position(c, hw, slack, p[0], p[1], p[6], s, ey, epsi, inside);
-    double *x = x0 + (size_t)b * 5;
-    x[0] = p[2]; x[1] = p[3]; x[2] = p[7]; x[3] = q9_swap ? epsi : ey; x[4] = q9_swap ? ey : epsi;
-    double vx = x[0], S = 0.0;
-    for (int i = 0; i < N; ++i) {
-        double *r = xlast + ((size_t)b * N + i) * 6;
-        r[0] = vx; r[1] = x[1]; r[2] = x[2]; r[3] = x[3]; r[4] = x[4]; r[5] = S;
-        delta[(size_t)b * N + i] = 0.0;
-        S = S + ((vx * cos(x[4]) - x[1] * sin(x[4])) / (1 - x[3] * 0)) * c.dt;
-        vx = vx + (0.1 + accel_rate * i) * c.dt;
-    }
+    const int N = cp->N;
+    plan_first_one(*cp, plant + (size_t)b * 8, hw, slack, q9_swap, accel_rate, x0 + (size_t)b * 5, xlast + (size_t)b * N * 6, delta + (size_t)b * N);
 }
 
 // controller, LapNumber >= 1 (CMAIN:176-182,198-248,268-283,289-298), one lane per vehicle.  refs [B][5][M] is the
@@ -246,15 +235,10 @@ __global__ void __launch_bounds__(64) tt_measure_kernel(const DevCfg *__restrict
         vel[(size_t)b * (N + 1) + N] = r[3 * M + N - 1];
         ref0[b * 3 + 0] = r[0]; ref0[b * 3 + 1] = r[M]; ref0[b * 3 + 2] = r[2 * M];
     }
-    const double vx = p[2] < 0.01 ? 0.01 : p[2], vy = p[3];
     const int lp = lap[b];
-    const double psi = wrap_pi(p[6] - 2 * kPi * lp);
-    const double xd = ref0[b * 3 + 0], yd = ref0[b * 3 + 1], psid = ref0[b * 3 + 2], cv0 = curv[(size_t)b * N];
-    const double ey = -(p[0] - xd) * sin(psid) + (p[1] - yd) * cos(psid);
-    const double epsi = wrap_pi(psi - psid);
-    const double s = SS[b] + ((vx * cos(epsi) - vy * sin(epsi)) / (1 - ey * cv0)) * c.dt;
     double *ls = local_state + (size_t)b * 6;
-    ls[0] = vx; ls[1] = vy; ls[2] = p[7]; ls[3] = epsi; ls[4] = s; ls[5] = ey;
+    tt_local(c, p, lp, ref0 + b * 3, curv[(size_t)b * N], SS[b], ls);
+    const double s = ls[4];
     const double L = c.track[(c.track_rows - 1) * 6 + 3] + c.track[(c.track_rows - 1) * 6 + 4];
     if (lp >= 1 && fabs(p[0]) < 0.1 && s >= L - L / 10) { lap[b] = lp + 1; lap_tick[b] = tick; SS[b] = 0.0; }
     else SS[b] = s;
@@ -262,12 +246,14 @@ __global__ void __launch_bounds__(64) tt_measure_kernel(const DevCfg *__restrict
 }
 
 #define LPVMPC_GRID(n) dim3(((n) + 63) / 64), dim3(64)
-hipError_t launch_plan_pose(const DevCfg *dcfg, int B, const double *xPred, double *SS, double *pose, double *sig, hipStream_t s) {
-    hipLaunchKernelGGL(plan_pose_kernel, LPVMPC_GRID(B), 0, s, dcfg, B, xPred, SS, pose, sig);
+hipError_t launch_plan_pose(const DevCfg *dcfg, int B, const double *xPred, double *SS, double *pose, double *sig, hipStream_t s,
+                            const int32_t *active) {
+    hipLaunchKernelGGL(plan_pose_kernel, LPVMPC_GRID(B), 0, s, dcfg, B, xPred, SS, pose, sig, active);
     return hipGetLastError();
 }
-hipError_t launch_resample(int B, int N, int M, const double *WT, const double *FWT, const double *sig, double *refs, hipStream_t s) {
-    hipLaunchKernelGGL(resample_kernel, dim3(B), dim3(64), 0, s, B, N, M, WT, FWT, sig, refs);
+hipError_t launch_resample(int B, int N, int M, const double *WT, const double *FWT, const double *sig, double *refs, hipStream_t s,
+                           const int32_t *active) {
+    hipLaunchKernelGGL(resample_kernel, dim3(B), dim3(64), 0, s, B, N, M, WT, FWT, sig, refs, active);
     return hipGetLastError();
 }
 hipError_t launch_plan_first(const DevCfg *dcfg, int B, const double *plant, double hw, double slack, int q9_swap, double accel_rate,

@@ -86,10 +86,10 @@ __global__ void __launch_bounds__(64) ctrl_lpv_kernel(const DevCfg *__restrict__
                                                       const double *__restrict__ u_prev,
                                                       const double *__restrict__ vel_ref,
                                                       const double *__restrict__ curv_ref, double cf_new, int lap,
-                                                      double *__restrict__ states, double *__restrict__ AB) {
+                                                      double *__restrict__ states, double *__restrict__ AB, const int32_t *__restrict__ active) {
     const DevCfg &c = *cp;
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
+    if (b >= B || (active && !active[b])) return;
     const int N = c.N;
     double st[6];
 #pragma unroll
@@ -139,12 +139,14 @@ __global__ void __launch_bounds__(64) ctrl_lpv_kernel(const DevCfg *__restrict__
 // structural zeros only ever added +-0), so the outputs are the same values (the sign of an exact zero aside).
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64) ctrl_lpv_pre_kernel(const DevCfg *__restrict__ cp, int B, const double *__restrict__ u_prev,
-                                                          const double *__restrict__ vel_ref, double cf_new, double *__restrict__ AB) {
+                                                          const double *__restrict__ vel_ref, double cf_new, double *__restrict__ AB,
+                                                          const int32_t *__restrict__ active) {
     const DevCfg &c = *cp;
     const int N = c.N;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= B * N) return;
     const int b = t / N, i = t - b * N;
+    if (active && !active[b]) return;
     const double vx = vel_ref[(size_t)b * (N + 1) + i], delta = u_prev[(size_t)t * 2];
     const double Cf = cf_new, Cr = cf_new, m = c.m, I = c.Iz, lf = c.lf, lr = c.lr, dt = c.dt;
     double sd, cd;
@@ -179,10 +181,11 @@ __global__ void __launch_bounds__(64) ctrl_lpv_pre_kernel(const DevCfg *__restri
 
 __global__ void __launch_bounds__(64) ctrl_lpv_roll_kernel(const DevCfg *__restrict__ cp, int B, const double *__restrict__ x0,
                                                            const double *__restrict__ u_prev, const double *__restrict__ curv_ref,
-                                                           int lap, double *__restrict__ states, double *__restrict__ AB) {
+                                                           int lap, double *__restrict__ states, double *__restrict__ AB,
+                                                           const int32_t *__restrict__ active) {
     const DevCfg &c = *cp;
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
+    if (b >= B || (active && !active[b])) return;
     const int N = c.N;
     const double dt = c.dt;
     double st[6];
@@ -226,11 +229,12 @@ __global__ void __launch_bounds__(64) ctrl_lpv_roll_kernel(const DevCfg *__restr
 
 // controller seed-mode linearisation, CTRL:732-809 (vx from the trajectory, curvature from the map)
 __global__ void __launch_bounds__(64) ctrl_abc_kernel(const DevCfg *__restrict__ cp, int B, const double *__restrict__ xlast,
-                                                      const double *__restrict__ delta, double *__restrict__ AB) {
+                                                      const double *__restrict__ delta, double *__restrict__ AB,
+                                                      const int32_t *__restrict__ active) {
     const DevCfg &c = *cp;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int N = c.N;
-    if (t >= B * N) return;
+    if (t >= B * N || (active && !active[t / N])) return;
     const double *x = xlast + (size_t)t * 6;
     const double cur = track_curvature(c, x[4]);
     double ab[6][8];
@@ -248,10 +252,10 @@ __global__ void __launch_bounds__(64) ctrl_abc_kernel(const DevCfg *__restrict__
 __global__ void __launch_bounds__(64) plan_lpv_kernel(const DevCfg *__restrict__ cp, int B, const double *__restrict__ x0,
                                                       const double *__restrict__ u_prev,
                                                       const double *__restrict__ SS, double *__restrict__ states,
-                                                      double *__restrict__ AB) {
+                                                      double *__restrict__ AB, const int32_t *__restrict__ active) {
     const DevCfg &c = *cp;
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
+    if (b >= B || (active && !active[b])) return;
     const int N = c.N;
     double st[5];
 #pragma unroll
@@ -286,11 +290,12 @@ __global__ void __launch_bounds__(64) plan_lpv_kernel(const DevCfg *__restrict__
 
 // planner seed-mode linearisation, PLAN:519-591; xlast columns [vx vy wz ey epsi s]
 __global__ void __launch_bounds__(64) plan_abc_kernel(const DevCfg *__restrict__ cp, int B, const double *__restrict__ xlast,
-                                                      const double *__restrict__ delta, double *__restrict__ AB) {
+                                                      const double *__restrict__ delta, double *__restrict__ AB,
+                                                      const int32_t *__restrict__ active) {
     const DevCfg &c = *cp;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int N = c.N;
-    if (t >= B * N) return;
+    if (t >= B * N || (active && !active[t / N])) return;
     const double *x = xlast + (size_t)t * 6;
     const double cur = track_curvature(c, x[5]);
     double ab[5][7];
@@ -303,24 +308,25 @@ __global__ void __launch_bounds__(64) plan_abc_kernel(const DevCfg *__restrict__
 }
 
 hipError_t launch_lpv(const DevCfg &cfg, const DevCfg *dcfg, int B, const double *x0, const double *u_prev, const double *vel_ref,
-                      const double *curv_s, double cf_new, int lap, double *states, double *AB, hipStream_t stream) {
+                      const double *curv_s, double cf_new, int lap, double *states, double *AB, hipStream_t stream, const int32_t *active) {
     const int blocks = (B + 63) / 64;
     if (cfg.kind == 0 && AB) {
-        hipLaunchKernelGGL(ctrl_lpv_pre_kernel, dim3((B * cfg.N + 63) / 64), dim3(64), 0, stream, dcfg, B, u_prev, vel_ref, cf_new, AB);
-        hipLaunchKernelGGL(ctrl_lpv_roll_kernel, dim3(blocks), dim3(64), 0, stream, dcfg, B, x0, u_prev, curv_s, lap, states, AB);
+        hipLaunchKernelGGL(ctrl_lpv_pre_kernel, dim3((B * cfg.N + 63) / 64), dim3(64), 0, stream, dcfg, B, u_prev, vel_ref, cf_new, AB, active);
+        hipLaunchKernelGGL(ctrl_lpv_roll_kernel, dim3(blocks), dim3(64), 0, stream, dcfg, B, x0, u_prev, curv_s, lap, states, AB, active);
     } else if (cfg.kind == 0)
-        hipLaunchKernelGGL(ctrl_lpv_kernel, dim3(blocks), dim3(64), 0, stream, dcfg, B, x0, u_prev, vel_ref, curv_s, cf_new, lap, states, AB);
+        hipLaunchKernelGGL(ctrl_lpv_kernel, dim3(blocks), dim3(64), 0, stream, dcfg, B, x0, u_prev, vel_ref, curv_s, cf_new, lap, states, AB, active);
     else
-        hipLaunchKernelGGL(plan_lpv_kernel, dim3(blocks), dim3(64), 0, stream, dcfg, B, x0, u_prev, curv_s, states, AB);
+        hipLaunchKernelGGL(plan_lpv_kernel, dim3(blocks), dim3(64), 0, stream, dcfg, B, x0, u_prev, curv_s, states, AB, active);
     return hipGetLastError();
 }
 
-hipError_t launch_abc(const DevCfg &cfg, const DevCfg *dcfg, int B, const double *xlast, const double *delta, double *AB, hipStream_t stream) {
+hipError_t launch_abc(const DevCfg &cfg, const DevCfg *dcfg, int B, const double *xlast, const double *delta, double *AB, hipStream_t stream,
+                      const int32_t *active) {
     const int blocks = (B * cfg.N + 63) / 64;
     if (cfg.kind == 0)
-        hipLaunchKernelGGL(ctrl_abc_kernel, dim3(blocks), dim3(64), 0, stream, dcfg, B, xlast, delta, AB);
+        hipLaunchKernelGGL(ctrl_abc_kernel, dim3(blocks), dim3(64), 0, stream, dcfg, B, xlast, delta, AB, active);
     else
-        hipLaunchKernelGGL(plan_abc_kernel, dim3(blocks), dim3(64), 0, stream, dcfg, B, xlast, delta, AB);
+        hipLaunchKernelGGL(plan_abc_kernel, dim3(blocks), dim3(64), 0, stream, dcfg, B, xlast, delta, AB, active);
     return hipGetLastError();
 }
 

@@ -63,11 +63,13 @@ extern "C" void lpvmpc_default_config(int32_t kind, lpvmpc_config *c) {
 
 static void free_ws(lpvmpc_handle *h) {
     void *ptrs[] = {h->d_x0, h->d_uprev, h->d_vel, h->d_curv, h->d_uold, h->d_maxey, h->d_AB, h->d_states,
-                    h->d_xPred, h->d_uPred, h->d_resid, h->d_xlast, h->d_delta, h->d_status, h->d_iters, h->d_polish, h->d_state, h->d_scal};
+                    h->d_xPred, h->d_uPred, h->d_resid, h->d_xlast, h->d_delta, h->d_status, h->d_iters, h->d_polish, h->d_state, h->d_scal,
+                    h->d_active};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     h->d_x0 = h->d_uprev = h->d_vel = h->d_curv = h->d_uold = h->d_maxey = h->d_AB = h->d_states = nullptr;
     h->d_xPred = h->d_uPred = h->d_resid = h->d_xlast = h->d_delta = nullptr;
     h->d_status = h->d_iters = h->d_polish = nullptr; h->d_state = nullptr; h->d_scal = nullptr; h->state_valid_B = 0;
+    h->d_active = nullptr;
     h->cap = 0;
 }
 
@@ -135,7 +137,7 @@ static int ensure_ws(lpvmpc_handle *h, int B) {
     ALLOC(h->d_xlast, b * N * 6 * 8); ALLOC(h->d_delta, b * N * 8);
     ALLOC(h->d_state, b * 3 * (N + 1) * 8 * 8);
     if (h->cfg.kind == LPVMPC_KIND_PLANNER && N == 30) ALLOC(h->d_scal, b * 3 * (N + 1) * 8 * 8);      // see SolveArgs::scal
-    ALLOC(h->d_status, b * 4); ALLOC(h->d_iters, b * 4); ALLOC(h->d_polish, b * 4);
+    ALLOC(h->d_status, b * 4); ALLOC(h->d_iters, b * 4); ALLOC(h->d_polish, b * 4); ALLOC(h->d_active, b * 4);
 #undef ALLOC
     h->cap = B;
     return LPVMPC_OK;
@@ -163,6 +165,7 @@ extern "C" lpvmpc_handle *lpvmpc_create(const lpvmpc_config *cfg) {
     h->d_status = h->d_iters = h->d_polish = nullptr; h->d_state = nullptr; h->d_scal = nullptr; h->warm_mode = 0; h->state_valid_B = 0;
     h->cl_plant = h->cl_local = h->cl_cmd = nullptr; h->cl_local_next = nullptr; h->cl_next_valid = 0; h->cl_B = 0; h->cl_first_it = 1; h->cl_q9 = 1; h->cl_ticks = 0;
     h->d_Wop = h->d_FWop = nullptr; h->ho_M = 0; h->cascade = nullptr; h->cascade_owner = nullptr; h->cascade_prefetch = 1;
+    h->race = nullptr; h->race_owner = nullptr; h->d_active = nullptr; h->solve_mask = nullptr;
     h->defer_after = 0; h->defer_budget = 200; h->defer_cap = 0; h->defer_cur_cap = 0; h->defer_stride = 0; h->rv_count = 0;
     h->dpool[0] = h->dpool[1] = nullptr; h->dcount[0] = h->dcount[1] = nullptr; h->dstats = nullptr; h->dcur = 0; h->defer_stream = nullptr; h->defer_event = nullptr;
     h->defer_stream_set = false; h->defer_tail = 1; h->defer_skip_pass = false;
@@ -211,6 +214,8 @@ extern "C" void lpvmpc_destroy(lpvmpc_handle *h) {
     if (h->cl_local) (void)hipFree(h->cl_local);
     if (h->cl_cmd) (void)hipFree(h->cl_cmd);
     if (h->cascade) lpvmpc_cascade_free(h);                                  // (frees the cascade's estimator state)
+    if (h->race) lpvmpc_race_free(h);
+    if (h->race_owner && h->race_owner->race) lpvmpc_race_free(h->race_owner);   // a handle the race of another one drives: end that race
     if (h->obs_state) (void)hipFree(h->obs_state);
     if (h->obs_gains) (void)hipFree(h->obs_gains);
     if (h->obs_ws) (void)hipFree(h->obs_ws);
@@ -330,6 +335,7 @@ int lpvmpc_launch_solve_timed(lpvmpc_handle *h, const SolveArgs &a, hipStream_t 
     if (h->timing) HIP_TRY(h, hipEventRecord(h->ev0[slot], st));
     SolveArgs b = a;
     if (h->d_scal && a.B <= h->cap) b.scal = h->d_scal;          // (the launcher ignores it for deferred / resumed launches)
+    if (h->solve_mask && !a.resume) b.active = h->solve_mask;      // lpvmpc_solve_batch_masked
     HIP_TRY(h, lpvmpc::launch_solve(h->dev, h->d_cfg, b, st, h->force_generic));
     if (h->timing) { HIP_TRY(h, hipEventRecord(h->ev1[slot], st)); h->ev_count++; }
     return LPVMPC_OK;
@@ -339,9 +345,9 @@ int lpvmpc_launch_solve_timed(lpvmpc_handle *h, const SolveArgs &a, hipStream_t 
 // windows, receding-horizon inputs, last commands, statuses): a stand-alone batch call on the same handle would overwrite it
 // -- or, with a larger B, reallocate it -- without any error.  Such calls are refused; use a second handle.
 int lpvmpc_check_batch(lpvmpc_handle *h, int B, const char *who) {
-    if (h && (h->cl_plant || h->cascade || h->cascade_owner))
+    if (h && (h->cl_plant || h->cascade || h->cascade_owner || h->race || h->race_owner))
         return fail(h, LPVMPC_E_ARG, "%s: this handle runs a %s whose state lives in its workspace; use another handle for batch calls "
-                    "(lpvmpc_cl_release ends the fleet)", who, h->cl_plant ? "closed-loop fleet" : "planner + controller cascade");
+                    "(lpvmpc_cl_release ends the fleet)", who, h->cl_plant ? "closed-loop fleet" : (h->race || h->race_owner) ? "race" : "planner + controller cascade");
     return lpvmpc_check_common(h, B, who);
 }
 
@@ -633,6 +639,39 @@ extern "C" int lpvmpc_solve_batch(lpvmpc_handle *h, int32_t B, const double *x0,
     return io.flush_out();
 }
 
+// the same for the flagged instances only: the others are not solved and the caller's rows of them are not written
+extern "C" int lpvmpc_solve_batch_masked(lpvmpc_handle *h, int32_t B, const double *x0, const double *u_prev,
+                                         const double *vel_ref, const double *curv_s, const double *u_old,
+                                         const double *max_ey, double cf_new, int32_t lap, double *xPred, double *uPred,
+                                         int32_t *status, int32_t *iters, double *resid, int32_t *polish, const int32_t *active) {
+    if (h && B == 0) return LPVMPC_OK;                                   // an empty batch is a no-op
+    int rc = lpvmpc_check_batch(h, B, "lpvmpc_solve_batch_masked"); if (rc) return rc;
+    if (!active) return fail(h, LPVMPC_E_ARG, "lpvmpc_solve_batch_masked: active is NULL");
+    std::vector<int32_t> rows;
+    for (int i = 0; i < B; ++i) if (active[i]) rows.push_back(i);
+    if (rows.empty()) return LPVMPC_OK;                                  // nothing flagged: no launch at all
+    const size_t N = h->cfg.N, nx = h->nx, b = B;
+    std::vector<int32_t> flags(b);
+    for (size_t i = 0; i < b; ++i) flags[i] = active[i] != 0;
+    std::vector<double> tx(b * (N + 1) * nx), tu(b * N * 2), tr(b * 4);
+    std::vector<int32_t> ts(b), ti(b), tp(b);
+    HIP_TRY(h, hipMemcpy(h->d_active, flags.data(), b * 4, hipMemcpyHostToDevice));
+    h->solve_mask = h->d_active;
+    rc = lpvmpc_solve_batch(h, B, x0, u_prev, vel_ref, curv_s, u_old, max_ey, cf_new, lap, tx.data(), tu.data(), ts.data(), ti.data(),
+                            tr.data(), tp.data());
+    h->solve_mask = nullptr;
+    if (rc) return rc;
+    for (int32_t i : rows) {
+        if (xPred) std::memcpy(xPred + (size_t)i * (N + 1) * nx, tx.data() + (size_t)i * (N + 1) * nx, (N + 1) * nx * 8);
+        if (uPred) std::memcpy(uPred + (size_t)i * N * 2, tu.data() + (size_t)i * N * 2, N * 2 * 8);
+        if (resid) std::memcpy(resid + (size_t)i * 4, tr.data() + (size_t)i * 4, 4 * 8);
+        if (status) status[i] = ts[i];
+        if (iters) iters[i] = ti[i];
+        if (polish) polish[i] = tp[i];
+    }
+    return LPVMPC_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // caller-side helpers of the reference, batched on the device
 // ------------------------------------------------------------------------------------------------
@@ -686,6 +725,7 @@ extern "C" int lpvmpc_cl_release(lpvmpc_handle *h) {
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (h->cascade) { HIP_TRY(h, hipDeviceSynchronize()); lpvmpc_cascade_free(h); }
+    if (h->race) lpvmpc_race_free(h);
     if (h->cl_plant) { (void)hipFree(h->cl_plant); (void)hipFree(h->cl_local); (void)hipFree(h->cl_cmd); (void)hipFree(h->cl_local_next); h->cl_plant = h->cl_local = h->cl_cmd = h->cl_local_next = nullptr; }
     if (h->obs_state) { (void)hipFree(h->obs_state); h->obs_state = nullptr; }
     h->cl_B = 0; h->cl_ticks = 0; h->cl_first_it = 1; h->cl_next_valid = 0;
@@ -696,6 +736,7 @@ extern "C" int lpvmpc_cl_init(lpvmpc_handle *h, int32_t B, const double *plant0,
                               int32_t n_sub, double dt_sim, double mu_sim) {
     int rc = lpvmpc_check_common(h, B, "lpvmpc_cl_init"); if (rc) return rc;
     if (h->cfg.kind != LPVMPC_KIND_CONTROLLER) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: controller handles only");
+    if (h->race || h->race_owner) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: this handle takes part in a race (lpvmpc_cl_release on its path handle ends it)");
     if (h->cfg.N > 20) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: the reference's seed trajectories have 20 rows (N <= 20)");
     if (h->cfg.steering_delay != 0) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: the fleet engines run the reference's steeringDelay = 0 (CMAIN:49)");
     if (!plant0 || n_sub < 1 || !(dt_sim > 0)) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: bad argument");
@@ -849,7 +890,7 @@ extern "C" int lpvmpc_observer_step_batch(lpvmpc_handle *h, int32_t B, const lpv
     if (h && B == 0) return LPVMPC_OK;                                   // an empty batch is a no-op
     // the fleet / cascade rule of the batch calls; the solver workspace is not needed (this call stages its own buffers)
     if (!h) return fail(nullptr, LPVMPC_E_ARG, "lpvmpc_observer_step_batch: handle is NULL");
-    if (h->cl_plant || h->cascade || h->cascade_owner)
+    if (h->cl_plant || h->cascade || h->cascade_owner || h->race || h->race_owner)
         return fail(h, LPVMPC_E_ARG, "lpvmpc_observer_step_batch: this handle runs a fleet whose state lives in its workspace; use another handle "
                     "for batch calls (lpvmpc_cl_release ends the fleet)");
     if (B < 0) return fail(h, LPVMPC_E_ARG, "lpvmpc_observer_step_batch: B=%d", B);

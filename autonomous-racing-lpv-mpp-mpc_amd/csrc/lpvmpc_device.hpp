@@ -85,6 +85,9 @@ struct SolveArgs {
     // resume launches that run to completion (defer_after == 0): 1 = take the whole-CU tail kernel where one exists for the
     // handle's (kind, N) (lpvmpc_set_option "defer_tail", default on); it continues the same pool entries
     int tail;
+    // [B] active-instance mask of a main launch (null: every instance).  A workgroup whose flag is 0 returns at its entry, before it
+    // reads or writes anything (its output rows and carried state stay as they are; it never parks).  Resume launches ignore it.
+    const int32_t *active;
 };
 constexpr int kParkScalars = 16;     // behind the LDS image of a pool entry: c, cinv, rho, iter, to_chk, to_adp, instance index and the
                                      // instance's output pointers (xPred, uPred, status, iters, polish, resid, state) as 64-bit words
@@ -94,9 +97,12 @@ constexpr int LPVMPC_PENDING_ = -11; // status of a parked instance until its re
 int solve_has_fast_path(int kind, int N);
 size_t solve_lds_bytes(int kind, int N);
 hipError_t launch_solve(const DevCfg &cfg, const DevCfg *dcfg, const SolveArgs &a, hipStream_t stream, int force_generic);
+// active: optional [B] instance mask (null: every instance); a masked instance's rows of states / AB are not written
 hipError_t launch_lpv(const DevCfg &cfg, const DevCfg *dcfg, int B, const double *x0, const double *u_prev, const double *vel_ref,
-                      const double *curv_s, double cf_new, int lap, double *states, double *AB, hipStream_t stream);
-hipError_t launch_abc(const DevCfg &cfg, const DevCfg *dcfg, int B, const double *xlast, const double *delta, double *AB, hipStream_t stream);
+                      const double *curv_s, double cf_new, int lap, double *states, double *AB, hipStream_t stream,
+                      const int32_t *active = nullptr);
+hipError_t launch_abc(const DevCfg &cfg, const DevCfg *dcfg, int B, const double *xlast, const double *delta, double *AB, hipStream_t stream,
+                      const int32_t *active = nullptr);
 
 // closed-loop helpers (closed_loop.hip)
 struct PlantCfg { double lf, lr, m, Iz, mu, dt; int n_sub; };
@@ -134,12 +140,37 @@ hipError_t launch_cl_command_plant_observe(const DevCfg *dcfg, int B, int N, con
 // planner -> controller hand-off and trajectory-tracking measurement (handoff.hip)
 #define LPVMPC_HANDOFF_MAX_N 64
 int handoff_length(int N, double dt, double interp_dt);
-hipError_t launch_plan_pose(const DevCfg *dcfg, int B, const double *xPred, double *SS, double *pose, double *sig, hipStream_t s);
-hipError_t launch_resample(int B, int N, int M, const double *WT, const double *FWT, const double *sig, double *refs, hipStream_t s);
+hipError_t launch_plan_pose(const DevCfg *dcfg, int B, const double *xPred, double *SS, double *pose, double *sig, hipStream_t s,
+                            const int32_t *active = nullptr);
+hipError_t launch_resample(int B, int N, int M, const double *WT, const double *FWT, const double *sig, double *refs, hipStream_t s,
+                           const int32_t *active = nullptr);
 hipError_t launch_plan_first(const DevCfg *dcfg, int B, const double *plant, double hw, double slack, int q9_swap, double accel_rate,
                              double *x0, double *xlast, double *delta, hipStream_t s);
 hipError_t launch_tt_measure(const DevCfg *dcfg, int B, int M, int tick, const double *plant, const double *cmd, const double *refs, int latch,
                              double *vel, double *curv, double *ref0, int32_t *lap, int32_t *lap_tick, double *SS, double *local_state,
                              double *u_old, int32_t *alive_ticks, hipStream_t s);
+
+// race engine: lap 0, lap events and racing with a phase per vehicle (race.hip)
+struct RaceDev {              // device pointers and constants of one race (lpvmpc_race_*), passed by value
+    int B, N, Np, M, laps, q9, n_sub_lap0, n_sub[3], lap_cols;
+    double hw, slack;
+    double *plant, *cmd, *local;                // [B][8], [B][2], [B][6]
+    int32_t *phase, *lap, *half, *rk, *plan_done, *idx;   // [B]: phase, lap counter, HalfTrack, racing ticks done, planner ticks done, `index`
+    int32_t *nstep, *src;                       // [B] this tick: plant steps; controller that solved (0 path, 1 TT, -1 none)
+    int32_t *step, *lap_step, *alive;           // [B] plant steps so far; [B][lap_cols] step at which each lap starts (-1: not yet); alive ticks
+    int32_t *iters, *status;                    // [B] the vehicle's controller solve of the last tick
+    int32_t *m_path, *m_tt, *m_plan, *m_pfirst, *m_pcont;   // [B] masks of this tick
+    double *SSc, *ref0, *refs;                  // [B], [B][3], [B][5][M] (the vehicle's latest planner message)
+    double *SSp, *pose, *sig;                   // planner carried state [B][Np+1], [B][3]; scratch [B][5][Np]
+    // the three handles' workspaces
+    double *p_uold, *p_uPred, *p_vel, *p_curv;  // path
+    int32_t *p_iters, *p_status;
+    double *t_uold, *t_uPred, *t_vel, *t_curv;  // trajectory tracking
+    int32_t *t_iters, *t_status;
+    double *q_x0, *q_xPred, *q_xlast, *q_delta; // planner
+};
+hipError_t launch_race_plan_start(const DevCfg *pcfg, const RaceDev &r, hipStream_t s);
+hipError_t launch_race_measure(const DevCfg *ccfg, const RaceDev &r, int seed_tick, hipStream_t s);
+hipError_t launch_race_command_plant(const RaceDev &r, PlantCfg pc, hipStream_t s);
 
 }  // namespace lpvmpc

@@ -1,5 +1,6 @@
 // lpvmpc_handle.hpp -- private host-side definitions shared by the translation units that implement the C ABI
-// (lpvmpc_api.hip: solver entry points and the lap-0 fleet; cascade_api.hip: hand-off and planner + controller cascade).
+// (lpvmpc_api.hip: solver entry points and the lap-0 fleet; cascade_api.hip: hand-off and planner + controller cascade;
+// race_api.hip: the race engine).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,6 +15,7 @@
 #define LPVMPC_HIDDEN __attribute__((visibility("hidden")))
 
 struct lpvmpc_cascade;       // cascade_api.hip
+struct lpvmpc_race;          // race_api.hip
 
 using lpvmpc::DevCfg;
 using lpvmpc::SolveArgs;
@@ -69,6 +71,10 @@ struct lpvmpc_handle {
     int cascade_prefetch;               // option "cascade_prefetch" (default 1)
     lpvmpc_cascade *cascade;            // owned by the controller handle of a cascade (lpvmpc_cascade_init)
     lpvmpc_handle *cascade_owner;       // planner handle: the controller handle whose cascade drives it (its workspace carries the planner recursion)
+    lpvmpc_race *race;                  // owned by the path controller handle of a race (lpvmpc_race_init)
+    lpvmpc_handle *race_owner;          // trajectory-tracking / planner handle of a race: the path handle that owns it
+    int32_t *d_active;                  // [cap] instance mask of lpvmpc_solve_batch_masked
+    const int32_t *solve_mask;          // transient: the mask lpvmpc_launch_solve_timed puts on the launches of a masked call
     // gain-scheduled LPV estimator (lpvmpc_observer_*, observer.hip)
     lpvmpc_observer_config *obs_cfg;    // set by lpvmpc_observer_setup, taken by the next lpvmpc_cl_init (null: no estimator)
     double *obs_gains;                  // device copy of the gain words (head of lpvmpc_observer_config): the fleet's or the batch call's
@@ -98,6 +104,7 @@ LPVMPC_HIDDEN int lpvmpc_check_batch(lpvmpc_handle *h, int B, const char *who); 
 LPVMPC_HIDDEN int lpvmpc_launch_solve_timed(lpvmpc_handle *h, const lpvmpc::SolveArgs &a, hipStream_t st);
 LPVMPC_HIDDEN lpvmpc::PlantCfg lpvmpc_plant_cfg(const lpvmpc_handle *h, int n_sub, double dt_sim, double mu_sim);
 LPVMPC_HIDDEN void lpvmpc_cascade_free(lpvmpc_handle *h);
+LPVMPC_HIDDEN void lpvmpc_race_free(lpvmpc_handle *h);                                  // race_api.hip
 LPVMPC_HIDDEN int lpvmpc_observer_start(lpvmpc_handle *h, int B, const double *plant0, double dt_sim, int from_plant);   // lpvmpc_api.hip                               // cascade_api.hip
 namespace lpvmpc {
 // handoff.hip (host): interpolation operator W and interpolation + filtfilt operator FW, both [M][N] row-major

@@ -1,0 +1,215 @@
+// race_api.hip -- C ABI of the race engine (include/lpvmpc.h, lpvmpc_race_*): lap 0, per-vehicle lap events and racing
+// for one fleet on the device, owned by the path controller handle.  Kernels: race.hip (per-tick glue), lpv_eval.hip,
+// admm_solve.hip and handoff.hip (masked launches).
+#include <cmath>
+#include <cstring>
+#include <new>
+
+#include "lpvmpc_handle.hpp"
+
+struct lpvmpc_race {
+    lpvmpc_handle *tt, *plan;
+    lpvmpc::RaceDev d;            // device pointers and constants (kernel argument)
+    int ticks;
+    lpvmpc::PlantCfg pc;
+};
+
+void lpvmpc_race_free(lpvmpc_handle *h) {
+    lpvmpc_race *r = h->race;
+    if (!r) return;
+    (void)hipSetDevice(h->cfg.device);
+    (void)hipStreamSynchronize(h->stream);
+    lpvmpc::RaceDev &d = r->d;
+    void *ptrs[] = {d.plant, d.cmd, d.local, d.phase, d.lap, d.half, d.rk, d.plan_done, d.idx, d.nstep, d.src, d.step, d.lap_step,
+                    d.alive, d.iters, d.status, d.m_path, d.m_tt, d.m_plan, d.m_pfirst, d.m_pcont, d.SSc, d.ref0, d.refs, d.SSp,
+                    d.pose, d.sig};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    if (r->tt && r->tt->race_owner == h) r->tt->race_owner = nullptr;
+    if (r->plan && r->plan->race_owner == h) r->plan->race_owner = nullptr;
+    delete r;
+    h->race = nullptr;
+}
+
+extern "C" void lpvmpc_race_default_config(lpvmpc_race_config *c) {
+    if (!c) return;
+    std::memset(c, 0, sizeof(*c));
+    c->laps = 1;
+    c->n_sub_lap0 = 7;                                          // 7 x 5 ms per 33 ms tick (tests/golden/make_golden.py section 2)
+    c->n_sub[0] = 7; c->n_sub[1] = 7; c->n_sub[2] = 6;          // 100 ms per three racing ticks
+    c->q9_swap = 1;
+    c->half_width = 0.3; c->slack = 0.15; c->plan_max_ey = 0.2; c->dt_sim = 0.005; c->mu_sim = 0.05;
+}
+
+static bool busy(const lpvmpc_handle *x) { return x->cl_plant || x->cascade || x->cascade_owner || x->race || x->race_owner; }
+
+extern "C" int lpvmpc_race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, int32_t B, const double *plant0,
+                                const int32_t *half_track0, const lpvmpc_race_config *cfg) {
+    if (!h) return fail(nullptr, LPVMPC_E_ARG, "lpvmpc_race_init: path handle is NULL");
+    if (!tt || !plan || !plant0 || !cfg || B <= 0) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: NULL argument or B <= 0");
+    if (h->cfg.kind != LPVMPC_KIND_CONTROLLER || tt->cfg.kind != LPVMPC_KIND_CONTROLLER || plan->cfg.kind != LPVMPC_KIND_PLANNER || h == tt)
+        return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: needs two controller handles (path, tt) and a planner handle");
+    if (h->cfg.device != tt->cfg.device || h->cfg.device != plan->cfg.device)
+        return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: the three handles live on different devices");
+    if (h->cfg.N != tt->cfg.N || h->cfg.dt != tt->cfg.dt || h->cfg.track_rows != tt->cfg.track_rows ||
+        std::memcmp(h->cfg.track, tt->cfg.track, sizeof(double) * 6 * h->cfg.track_rows) != 0)
+        return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: path and tt handles differ in N, dt or track");
+    if (h->cfg.N > 20) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: the reference's seed trajectories have 20 rows (N <= 20)");
+    if (h->cfg.steering_delay != 0 || tt->cfg.steering_delay != 0)
+        return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: the fleet engines run the reference's steeringDelay = 0 (CMAIN:49)");
+    if (!plan->d_Wop) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: call lpvmpc_handoff_setup on the planner handle first");
+    if (plan->ho_M < h->cfg.N) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: the planner message (%d samples) is shorter than the controller horizon", plan->ho_M);
+    if (h->warm_mode || tt->warm_mode || plan->warm_mode) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: warm_start must be 0 on all three handles");
+    if (h->obs_cfg) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: the race does not run the state estimator (remove it from the path handle)");
+    if (busy(h) || busy(tt) || busy(plan)) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: a handle already runs a fleet, cascade or race (lpvmpc_cl_release ends it)");
+    if (cfg->laps < 1 || cfg->n_sub_lap0 < 1 || cfg->n_sub[0] < 1 || cfg->n_sub[1] < 1 || cfg->n_sub[2] < 1 || !(cfg->dt_sim > 0))
+        return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: bad configuration (laps >= 1, step counts >= 1, dt_sim > 0)");
+    int rc = lpvmpc_need_track(h, "lpvmpc_race_init"); if (rc) return rc;
+    rc = lpvmpc_need_track(plan, "lpvmpc_race_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
+    rc = lpvmpc_check_common(h, B, "lpvmpc_race_init"); if (rc) return rc;
+    rc = lpvmpc_check_common(tt, B, "lpvmpc_race_init(tt)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
+    rc = lpvmpc_check_common(plan, B, "lpvmpc_race_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
+    lpvmpc_race *r = new (std::nothrow) lpvmpc_race();
+    if (!r) return fail(h, LPVMPC_E_NOMEM, "out of host memory");
+    std::memset(&r->d, 0, sizeof(r->d));
+    h->race = r; tt->race_owner = h; plan->race_owner = h;
+    r->tt = tt; r->plan = plan; r->ticks = 0;
+    r->pc = lpvmpc_plant_cfg(h, 1, cfg->dt_sim, cfg->mu_sim);
+    lpvmpc::RaceDev &d = r->d;
+    const size_t b = B, N = h->cfg.N, Np = plan->cfg.N, M = plan->ho_M;
+    d.B = B; d.N = (int)N; d.Np = (int)Np; d.M = (int)M; d.laps = cfg->laps; d.q9 = cfg->q9_swap != 0; d.n_sub_lap0 = cfg->n_sub_lap0;
+    for (int i = 0; i < 3; ++i) d.n_sub[i] = cfg->n_sub[i];
+    d.lap_cols = cfg->laps + 2; d.hw = cfg->half_width; d.slack = cfg->slack;
+#define ALLOC(p, n) HIP_TRY(h, hipMalloc((void **)&(p), (n)))
+    ALLOC(d.plant, b * 8 * 8); ALLOC(d.cmd, b * 2 * 8); ALLOC(d.local, b * 6 * 8);
+    ALLOC(d.phase, b * 4); ALLOC(d.lap, b * 4); ALLOC(d.half, b * 4); ALLOC(d.rk, b * 4); ALLOC(d.plan_done, b * 4); ALLOC(d.idx, b * 4);
+    ALLOC(d.nstep, b * 4); ALLOC(d.src, b * 4); ALLOC(d.step, b * 4); ALLOC(d.lap_step, b * d.lap_cols * 4); ALLOC(d.alive, b * 4);
+    ALLOC(d.iters, b * 4); ALLOC(d.status, b * 4);
+    ALLOC(d.m_path, b * 4); ALLOC(d.m_tt, b * 4); ALLOC(d.m_plan, b * 4); ALLOC(d.m_pfirst, b * 4); ALLOC(d.m_pcont, b * 4);
+    ALLOC(d.SSc, b * 8); ALLOC(d.ref0, b * 3 * 8); ALLOC(d.refs, b * 5 * M * 8);
+    ALLOC(d.SSp, b * (Np + 1) * 8); ALLOC(d.pose, b * 3 * 8); ALLOC(d.sig, b * 5 * Np * 8);
+#undef ALLOC
+    d.p_uold = h->d_uold; d.p_uPred = h->d_uPred; d.p_vel = h->d_vel; d.p_curv = h->d_curv; d.p_iters = h->d_iters; d.p_status = h->d_status;
+    d.t_uold = tt->d_uold; d.t_uPred = tt->d_uPred; d.t_vel = tt->d_vel; d.t_curv = tt->d_curv; d.t_iters = tt->d_iters; d.t_status = tt->d_status;
+    d.q_x0 = plan->d_x0; d.q_xPred = plan->d_xPred; d.q_xlast = plan->d_xlast; d.q_delta = plan->d_delta;
+    hipStream_t st = h->stream;
+    H2D(d.plant, plant0, b * 8 * 8);
+    std::vector<int32_t> half(b, 0), lap_step(b * d.lap_cols, -1);
+    if (half_track0) for (size_t i = 0; i < b; ++i) half[i] = half_track0[i] != 0;
+    for (size_t i = 0; i < b; ++i) lap_step[i * d.lap_cols] = 0;                       // lap 0 starts at step 0
+    H2D(d.half, half.data(), b * 4);
+    H2D(d.lap_step, lap_step.data(), lap_step.size() * 4);
+    int32_t *zero_i[] = {d.phase, d.lap, d.rk, d.plan_done, d.idx, d.nstep, d.step, d.alive, d.iters, d.status, d.m_path, d.m_tt, d.m_plan, d.m_pfirst, d.m_pcont};
+    for (int32_t *p : zero_i) HIP_TRY(h, hipMemsetAsync(p, 0, b * 4, st));
+    HIP_TRY(h, hipMemsetAsync(d.src, 0xff, b * 4, st));
+    HIP_TRY(h, hipMemsetAsync(d.cmd, 0, b * 2 * 8, st));                                 // servo = motor = 0 before the first tick
+    HIP_TRY(h, hipMemsetAsync(d.local, 0, b * 6 * 8, st));
+    HIP_TRY(h, hipMemsetAsync(d.SSc, 0, b * 8, st));
+    HIP_TRY(h, hipMemsetAsync(d.ref0, 0, b * 3 * 8, st));
+    HIP_TRY(h, hipMemsetAsync(d.SSp, 0, b * (Np + 1) * 8, st));
+    HIP_TRY(h, hipMemsetAsync(d.pose, 0, b * 3 * 8, st));
+    // the handles' carried rows: commands and predictions start at zero, lap-0 references vel_ref = ones (CMAIN:311,326)
+    HIP_TRY(h, hipMemsetAsync(h->d_uold, 0, b * 2 * 8, st)); HIP_TRY(h, hipMemsetAsync(tt->d_uold, 0, b * 2 * 8, st));
+    HIP_TRY(h, hipMemsetAsync(h->d_uPred, 0, b * N * 2 * 8, st)); HIP_TRY(h, hipMemsetAsync(tt->d_uPred, 0, b * N * 2 * 8, st));
+    HIP_TRY(h, hipMemsetAsync(plan->d_uPred, 0, b * Np * 2 * 8, st));
+    HIP_TRY(h, hipMemsetAsync(tt->d_curv, 0, b * (N + 1) * 8, st));
+    std::vector<double> ones(b * (N + 1), 1.0), mey(b, cfg->plan_max_ey);
+    H2D(h->d_vel, ones.data(), ones.size() * 8); H2D(tt->d_vel, ones.data(), ones.size() * 8);
+    H2D(plan->d_maxey, mey.data(), b * 8);                                                 // Planner.solve(..., HW)  (PMAIN:162,176)
+    HIP_TRY(h, hipStreamSynchronize(st));
+    h->state_valid_B = tt->state_valid_B = plan->state_valid_B = 0;
+    return LPVMPC_OK;
+}
+
+// one tick, in order on the path handle's stream: masked planner work, measurement, path LPV + solve, TT LPV + solve,
+// command + plant
+extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
+    if (!h || !h->race || n_ticks < 1) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_tick: call lpvmpc_race_init first");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    lpvmpc_race *r = h->race;
+    lpvmpc_handle *tt = r->tt, *p = r->plan;
+    const lpvmpc::RaceDev &d = r->d;
+    const int B = d.B, N = d.N;
+    hipStream_t st = h->stream;
+    for (int t = 0; t < n_ticks; ++t) {
+        // planner ticks of the racing vehicles whose controller tick reads a new message (PMAIN:126-224, 257-308)
+        HIP_TRY(h, lpvmpc::launch_race_plan_start(p->d_cfg, d, st));
+        HIP_TRY(h, lpvmpc::launch_lpv(p->dev, p->d_cfg, B, p->d_x0, p->d_uPred, nullptr, d.SSp, 60.0, 0, p->d_states, p->d_AB, st, d.m_pcont));
+        HIP_TRY(h, lpvmpc::launch_abc(p->dev, p->d_cfg, B, p->d_xlast, p->d_delta, p->d_AB, st, d.m_pfirst));
+        SolveArgs pa{B, p->d_x0, p->d_AB, nullptr, nullptr, p->d_maxey, p->d_xPred, p->d_uPred, p->d_status, p->d_iters, p->d_polish, p->d_resid,
+                     nullptr, 0, 5};
+        pa.active = d.m_plan;
+        int rc = lpvmpc_launch_solve_timed(p, pa, st); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(p));
+        HIP_TRY(h, lpvmpc::launch_plan_pose(p->d_cfg, B, p->d_xPred, d.SSp, d.pose, d.sig, st, d.m_plan));
+        HIP_TRY(h, lpvmpc::launch_resample(B, d.Np, d.M, p->d_Wop, p->d_FWop, d.sig, d.refs, st, d.m_plan));
+        // measurement, lap logic, masks of the two controllers
+        const int seed = r->ticks < 9;
+        HIP_TRY(h, lpvmpc::launch_race_measure(h->d_cfg, d, seed, st));
+        // path controller (CMAIN:310-336)
+        const double *x0 = d.local; int x0_stride = 6;
+        if (seed) {                                                          // scratch only: unmasked
+            HIP_TRY(h, lpvmpc::launch_cl_seed(B, N, d.local, h->d_xlast, h->d_delta, st));
+            HIP_TRY(h, lpvmpc::launch_abc(h->dev, h->d_cfg, B, h->d_xlast, h->d_delta, h->d_AB, st));
+        } else {
+            HIP_TRY(h, lpvmpc::launch_lpv(h->dev, h->d_cfg, B, d.local, h->d_uPred, h->d_vel, nullptr, 60.0, 0, h->d_states, h->d_AB, st, d.m_path));
+            x0 = h->d_states; x0_stride = N * 6;
+        }
+        SolveArgs ca{B, x0, h->d_AB, h->d_vel, h->d_uold, nullptr, h->d_xPred, h->d_uPred, h->d_status, h->d_iters, h->d_polish, h->d_resid,
+                     nullptr, 0, x0_stride};
+        ca.active = d.m_path;
+        rc = lpvmpc_launch_solve_timed(h, ca, st); if (rc) return rc;
+        // trajectory-tracking controller (CMAIN:361-363)
+        HIP_TRY(h, lpvmpc::launch_lpv(tt->dev, tt->d_cfg, B, d.local, tt->d_uPred, tt->d_vel, tt->d_curv, 60.0, 1, tt->d_states, tt->d_AB, st, d.m_tt));
+        SolveArgs ta{B, d.local, tt->d_AB, tt->d_vel, tt->d_uold, nullptr, tt->d_xPred, tt->d_uPred, tt->d_status, tt->d_iters, tt->d_polish,
+                     tt->d_resid, nullptr, 0, 6};
+        ta.active = d.m_tt;
+        rc = lpvmpc_launch_solve_timed(tt, ta, st); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
+        HIP_TRY(h, lpvmpc::launch_race_command_plant(d, r->pc, st));
+        r->ticks++;
+    }
+    return LPVMPC_OK;
+}
+
+extern "C" int lpvmpc_race_read(lpvmpc_handle *h, double *plant, double *local_state, double *cmd, int32_t *phase, int32_t *lap,
+                                int32_t *iters, int32_t *status, int32_t *plan_iters, int32_t *plan_status, int32_t *ticks) {
+    if (!h || !h->race) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_read: call lpvmpc_race_init first");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    lpvmpc_race *r = h->race;
+    const lpvmpc::RaceDev &d = r->d;
+    const size_t B = d.B;
+    hipStream_t st = h->stream;
+    if (plant) D2H(plant, d.plant, B * 8 * 8);
+    if (local_state) D2H(local_state, d.local, B * 6 * 8);
+    if (cmd) D2H(cmd, d.cmd, B * 2 * 8);
+    if (phase) D2H(phase, d.phase, B * 4);
+    if (lap) D2H(lap, d.lap, B * 4);
+    if (iters) D2H(iters, d.iters, B * 4);
+    if (status) D2H(status, d.status, B * 4);
+    if (plan_iters) D2H(plan_iters, r->plan->d_iters, B * 4);
+    if (plan_status) D2H(plan_status, r->plan->d_status, B * 4);
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (ticks) ticks[0] = r->ticks;
+    return LPVMPC_OK;
+}
+
+extern "C" int lpvmpc_race_laps(lpvmpc_handle *h, int32_t *lap_step, int32_t *alive_ticks) {
+    if (!h || !h->race) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_laps: call lpvmpc_race_init first");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const lpvmpc::RaceDev &d = h->race->d;
+    hipStream_t st = h->stream;
+    if (lap_step) D2H(lap_step, d.lap_step, (size_t)d.B * d.lap_cols * 4);
+    if (alive_ticks) D2H(alive_ticks, d.alive, (size_t)d.B * 4);
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return LPVMPC_OK;
+}
+
+extern "C" int lpvmpc_race_predictions(lpvmpc_handle *h, double *path_uPred, double *tt_uPred) {
+    if (!h || !h->race) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_predictions: call lpvmpc_race_init first");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const lpvmpc::RaceDev &d = h->race->d;
+    hipStream_t st = h->stream;
+    const size_t n = (size_t)d.B * d.N * 2 * 8;
+    if (path_uPred) D2H(path_uPred, d.p_uPred, n);
+    if (tt_uPred) D2H(tt_uPred, d.t_uPred, n);
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return LPVMPC_OK;
+}

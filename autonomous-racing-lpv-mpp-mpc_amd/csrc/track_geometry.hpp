@@ -129,4 +129,43 @@ __device__ inline void plant_step(const PlantCfg &p, double st[8], double ua, do
     st[7] = w + p.dt * (1.0 / p.Iz * (p.lf * FyF * cos(ud) - p.lr * FyR));
 }
 
+// ---- per-vehicle measurement recipes shared by the fleet engines (closed_loop.hip, handoff.hip, race.hip) ----
+// lap-0 measurement (CMAIN:183-188): local state from the plant's ground truth, vx clamped at 0.01; q9_swap = SURVEY quirk Q9
+__device__ inline void cl_local(const DevCfg &c, double hw, double slack, int q9_swap, const double *p, double *ls) {
+    double s, ey, epsi; int inside;
+    local_position(c, hw, slack, p[0], p[1], p[6], s, ey, epsi, inside);
+    ls[0] = p[2] < 0.01 ? 0.01 : p[2]; ls[1] = p[3]; ls[2] = p[7];
+    ls[3] = q9_swap ? ey : epsi; ls[4] = s; ls[5] = q9_swap ? epsi : ey;
+}
+
+// LapNumber >= 1 measurement (CMAIN:198-248): yaw unwound by the lap counter, Body_Frame_Errors against the first sample of
+// the reference window (ref0 = x, y, yaw; cv0 = its curvature), s dead-reckoned from SS
+__device__ inline void tt_local(const DevCfg &c, const double *p, int lap, const double *ref0, double cv0, double SS, double *ls) {
+    const double vx = p[2] < 0.01 ? 0.01 : p[2], vy = p[3];
+    const double psi = wrap_pi(p[6] - 2 * kPi * lap);
+    const double xd = ref0[0], yd = ref0[1], psid = ref0[2];
+    const double ey = -(p[0] - xd) * sin(psid) + (p[1] - yd) * cos(psid);
+    const double epsi = wrap_pi(psi - psid);
+    const double s = SS + ((vx * cos(epsi) - vy * sin(epsi)) / (1 - ey * cv0)) * c.dt;
+    ls[0] = vx; ls[1] = vy; ls[2] = p[7]; ls[3] = epsi; ls[4] = s; ls[5] = ey;
+}
+
+// planner's first tick (PMAIN:137-141, :152-162, seed of PMAIN:465-505); c is the planner's configuration.  x0 [5],
+// xlast [N][6], delta [N] of one vehicle
+__device__ inline void plan_first_one(const DevCfg &c, const double *p, double hw, double slack, int q9_swap, double accel_rate,
+                                      double *x, double *xlast, double *delta) {
+    const int N = c.N;
+    double s, ey, epsi; int inside;
+    local_position(c, hw, slack, p[0], p[1], p[6], s, ey, epsi, inside);
+    x[0] = p[2]; x[1] = p[3]; x[2] = p[7]; x[3] = q9_swap ? epsi : ey; x[4] = q9_swap ? ey : epsi;
+    double vx = x[0], S = 0.0;
+    for (int i = 0; i < N; ++i) {
+        double *r = xlast + (size_t)i * 6;
+        r[0] = vx; r[1] = x[1]; r[2] = x[2]; r[3] = x[3]; r[4] = x[4]; r[5] = S;
+        delta[i] = 0.0;
+        S = S + ((vx * cos(x[4]) - x[1] * sin(x[4])) / (1 - x[3] * 0)) * c.dt;
+        vx = vx + (0.1 + accel_rate * i) * c.dt;
+    }
+}
+
 }  // namespace lpvmpc

@@ -262,6 +262,14 @@ int lpvmpc_solve_batch(lpvmpc_handle *h, int32_t B, const double *x0, const doub
                        double *xPred, double *uPred, int32_t *status, int32_t *iters, double *resid,
                        int32_t *polish);
 
+/* lpvmpc_solve_batch for the instances with active[i] != 0 (active [B], host memory) only.  The other instances are not
+ * solved -- their workgroups return before reading or writing anything -- and their rows of xPred / uPred / status /
+ * iters / resid / polish are left exactly as the caller had them.  All-zero mask: no work, nothing written. */
+int lpvmpc_solve_batch_masked(lpvmpc_handle *h, int32_t B, const double *x0, const double *u_prev,
+                              const double *vel_ref, const double *curv_s, const double *u_old,
+                              const double *max_ey, double cf_new, int32_t lap, double *xPred, double *uPred,
+                              int32_t *status, int32_t *iters, double *resid, int32_t *polish, const int32_t *active);
+
 /* Same as lpvmpc_solve_batch but every pointer is a DEVICE pointer and the work is enqueued on `stream`
  * (a hipStream_t; NULL = default stream) without synchronising.  Used by the closed-loop / bench paths. */
 int lpvmpc_solve_batch_dev(lpvmpc_handle *h, int32_t B, const double *x0, const double *u_prev,
@@ -387,6 +395,63 @@ int lpvmpc_cascade_read(lpvmpc_handle *ctrl, double *plant, double *local_state,
  * planner QP went primal infeasible carries NaN from then on and costs no iterations: the sum over the fleet is the number of
  * vehicle-ticks that did work).  Synchronises like lpvmpc_cascade_read. */
 int lpvmpc_cascade_alive_ticks(lpvmpc_handle *ctrl, int32_t *alive_ticks);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Race engine: the reference's whole experiment (controllerMain.py + plannerMain.py from the grid to NumberOfLaps) for a
+ * fleet of B vehicles, each in its own phase, resident on the device; one lpvmpc_race_tick call enqueues n_ticks
+ * controller ticks (30 Hz) and nothing goes to the host between them.  Three handles: `path` (controller, path-following
+ * tuning: Controller), `tt` (controller, racing tuning: Controller_TT) and `planner` (lpvmpc_handoff_setup done).
+ * Per vehicle and tick, in this order on the path handle's stream:
+ *   phase 0 (lap 0): measurement of the lap-0 branch (Map.getLocalPosition, vx >= 0.01, quirk Q9 with q9_swap);
+ *     HalfTrack = 1 once s >= 3L/4; the race's first 9 ticks solve `path` on the seed trajectories (first_it < 10,
+ *     CMAIN:310-320), later ticks LPVPrediction(lap 0) + solve on `path` from the first rolled-out state (CMAIN:325-331);
+ *   lap event (HalfTrack && s <= L/4, CMAIN:254-262): lap = 1, SS = 0, HalfTrack = 0, phase 1.  On this tick `tt` solves
+ *     from the lap-0 measurement with vel_ref = ones(N+1), curv_ref = zeros(N), LapNumber = 1, uPred = the path handle's
+ *     uPred (CMAIN:336) and u_old = the last command (within the seed ticks `path` solves instead, as ControllerNode.step);
+ *   phase 1, racing tick k (k = 0 on the tick after the event): the vehicle's planner ticks 0 .. floor(2k/3) have run
+ *     before it (the first from the measured plant state with the seed of PMAIN:465-505, later ones open loop from
+ *     xPred[1]; each followed by the hand-off into the vehicle's message); measurement of the LapNumber >= 1 branch with
+ *     the vehicle's own `index` latch (windows re-read on even k); LPVPrediction + solve on `tt`; racing lap event
+ *     (|x| < 0.1 && s >= L - L/10, CMAIN:268-272);
+ *   command = uPred[0] of the controller of the vehicle's lap; the plant advances n_sub_lap0 simulator steps on lap-0
+ *     ticks (the event tick included) and n_sub[k % 3] on racing tick k.
+ * Definitions of this engine where the ROS run has none:
+ *   finish: when the lap counter exceeds `laps` (RunController = 0 in the reference) the vehicle is phase 2 and FROZEN from
+ *     that tick on -- plant and command are not advanced, it costs no iterations, its outputs stay readable;
+ *   lost: a vehicle entering a tick with a non-finite plant state is phase 3 and frozen the same way;
+ *   lap time: lap_step [B][laps + 2] holds the plant-step index at which lap 0, 1, ... started (-1: not reached), so
+ *     lap times are step differences x dt_sim (simulated time; the reference's TLAPTIME is wall-clock time).
+ * Kernel launches that only write per-tick scratch run unmasked (the seed-tick ABC linearisation of `path`); every launch
+ * that writes carried state -- LPV roll-outs, solves, hand-off -- is masked to this tick's vehicles (SolveArgs::active).
+ * Refused with LPVMPC_E_ARG: handles on different devices or of the wrong kinds, path / tt with different N, dt or track,
+ * N > 20 (the seed rows), steering_delay != 0, a planner without lpvmpc_handoff_setup or with a message shorter than N,
+ * warm_start != 0 on any of the three, an estimator on `path`, a handle already running a fleet, cascade or race.
+ * The race belongs to `path`: lpvmpc_cl_release(path) (or destroying any of the three) ends it; while it runs, batch calls
+ * on all three handles fail.  plant0 [B][8] = {x y vx vy ax ay yaw psiDot}; half_track0 [B] or NULL (= 0). */
+typedef struct lpvmpc_race_config {
+    int32_t laps;             /* NumberOfLaps: a vehicle finishes when its lap counter exceeds it (>= 1) */
+    int32_t n_sub_lap0;       /* plant steps per lap-0 tick (7) */
+    int32_t n_sub[3];         /* plant steps per racing tick k % 3 (7, 7, 6) */
+    int32_t q9_swap;          /* 1: SURVEY quirk Q9 in both measurements (CMAIN:188, PMAIN:141) */
+    double  half_width, slack, plan_max_ey, dt_sim, mu_sim;   /* the map's, the planner's max_ey, the simulator's (0.3, 0.15, 0.2, 0.005, 0.05) */
+} lpvmpc_race_config;
+void lpvmpc_race_default_config(lpvmpc_race_config *cfg);
+int  lpvmpc_race_init(lpvmpc_handle *path, lpvmpc_handle *tt, lpvmpc_handle *planner, int32_t B,
+                      const double *plant0, const int32_t *half_track0, const lpvmpc_race_config *cfg);
+/* enqueue n_ticks ticks; no synchronisation */
+int  lpvmpc_race_tick(lpvmpc_handle *path, int32_t n_ticks);
+/* synchronises and copies (any pointer may be NULL): plant [B][8], local_state [B][6] (the last measurement), cmd [B][2],
+ * phase / lap [B]; iters / status [B]: the controller solve of the vehicle's phase on the last tick (iters 0 and status
+ * unchanged when it did not solve: frozen, lost); plan_iters / plan_status [B] of the vehicle's last planner tick;
+ * ticks [1] = ticks run. */
+int  lpvmpc_race_read(lpvmpc_handle *path, double *plant, double *local_state, double *cmd, int32_t *phase,
+                      int32_t *lap, int32_t *iters, int32_t *status, int32_t *plan_iters, int32_t *plan_status,
+                      int32_t *ticks);
+/* lap_step [B][laps + 2] (see above), alive_ticks [B]: ticks entered with a finite plant state and not frozen (either may be NULL) */
+int  lpvmpc_race_laps(lpvmpc_handle *path, int32_t *lap_step, int32_t *alive_ticks);
+/* the two controllers' predicted inputs uPred [B][N][2] as they are now (the path handle's, the tt handle's; either may be NULL):
+ * the u_prev of their next LPV roll-out.  Synchronises like lpvmpc_race_read. */
+int  lpvmpc_race_predictions(lpvmpc_handle *path, double *path_uPred, double *tt_uPred);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Gain-scheduled LPV state estimator and simulated sensors (stateEstimator.py = EST, vehicleSimulator.py = SIM).

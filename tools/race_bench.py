@@ -1,0 +1,108 @@
+#!/usr/bin/env python3
+"""Race engine cost (lpvmpc_race_*) against the engines it composes, at B = 1024 and 8192 vehicles:
+  lap0     every vehicle in lap 0 (ticks 10 .. 10+K of a race from the grid)        vs lpvmpc_cl_tick at the same B
+  inphase  every vehicle racing, one common event tick (cascade.npz's lap-0 start)   vs lpvmpc_cascade_tick, prefetch 0
+  stagger  events spread over the last quarter of the lap (the engine's real case)   reported, not gated
+Prints ms per controller tick and alive vehicle-ticks per second; one line per (regime, B).
+Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--out FILE]"""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+
+
+def engines(mp):
+    import lpvmpc
+    from lpvmpc import workloads as W
+    Qp, Rp, dRp = W.CTRL_TUNINGS["path"]; Qr, Rr, dRr = W.CTRL_TUNINGS["race"]
+    path = lpvmpc.BatchedSolver("controller", 20, 1 / 30.0, Qp, Rp, dRp, track=mp.PointAndTangent)
+    tt = lpvmpc.BatchedSolver("controller", 20, 1 / 30.0, Qr, Rr, dRr, track=mp.PointAndTangent)
+    plan = lpvmpc.BatchedSolver("planner", 40, 0.05, W.PLAN_Q, W.PLAN_R, W.PLAN_dR, L_cf=W.PLAN_L, track=mp.PointAndTangent)
+    plan.handoff_setup()
+    return path, tt, plan
+
+
+def timed(tick, read, K):
+    read()
+    t0 = time.perf_counter()
+    tick(K)
+    read()
+    return (time.perf_counter() - t0) * 1e3 / K
+
+
+def race_run(mp, plant0, half, warm, K):
+    path, tt, plan = engines(mp)
+    path.race_init(tt, plan, plant0, half_track0=half, laps=5, half_width=mp.halfWidth, slack=mp.slack)
+    path.race_tick(warm)
+    a0 = path.race_laps()[1].sum()
+    ms = timed(path.race_tick, path.race_read, K)
+    alive = path.race_laps()[1].sum() - a0
+    ph = np.bincount(path.race_read()["phase"], minlength=4)
+    for e in (path, tt, plan):
+        e.close()
+    return ms, alive / (ms * K * 1e-3), ph
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ticks", type=int, default=30)
+    ap.add_argument("--sizes", default="1024,8192")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import lpvmpc
+    from lpvmpc import workloads as W
+    from tests._golden import load
+    from oracle import plant_ref as PR
+    mp = lpvmpc.Map("L_shape", 0.2)
+    c = load("cascade")
+    lines = []
+    for B in [int(x) for x in a.sizes.split(",")]:
+        rng = np.random.default_rng(3)
+        K = a.ticks
+        # lap 0: small offsets around the origin
+        grid = np.zeros((B, 8)); grid[:, 1] = rng.normal(0, 0.02, B); grid[:, 2] = rng.uniform(0.9, 1.1, B)
+        ms_r, vps_r, ph = race_run(mp, grid, 0, 10, K)
+        Qp, Rp, dRp = W.CTRL_TUNINGS["path"]
+        cl = lpvmpc.BatchedSolver("controller", 20, 1 / 30.0, Qp, Rp, dRp, track=mp.PointAndTangent)
+        cl.cl_init(grid, mp.halfWidth, mp.slack, q9_swap=True, n_sub=7)
+        cl.cl_tick(10)
+        ms_c = timed(cl.cl_tick, cl.cl_read, K)
+        cl.close()
+        lines.append("lap0     B=%5d  race %.3f ms/tick (%.3g alive vehicle-ticks/s, phases %s)  cl_tick %.3f ms/tick  ratio %.3f"
+                     % (B, ms_r, vps_r, ph.tolist(), ms_c, ms_r / ms_c))
+        # in phase: every vehicle at the fixture's lap-0 start, event on tick pre_ticks - 1; time racing ticks
+        P = int(c["pre_ticks"])
+        same = np.tile(c["pre_plant"][0], (B, 1))
+        ms_r, vps_r, ph = race_run(mp, same, 1, P + 3, K)
+        path, tt, plan = engines(mp)
+        tt.set_option("cascade_prefetch", 0)
+        tt.cascade_init(plan, np.tile(c["plant0"], (B, 1)), np.tile(c["cmd0"], (B, 1)), np.tile(c["uPred0"], (B, 1, 1)), lap0=1,
+                        half_width=mp.halfWidth, slack=mp.slack, plan_max_ey=0.2, q9_swap=True)
+        tt.cascade_tick(3)
+        ms_c = timed(tt.cascade_tick, lambda: tt.cascade_read(full=False), K)
+        for e in (path, tt, plan):
+            e.close()
+        lines.append("inphase  B=%5d  race %.3f ms/tick (%.3g alive vehicle-ticks/s, phases %s)  cascade %.3f ms/tick  ratio %.3f"
+                     % (B, ms_r, vps_r, ph.tolist(), ms_c, ms_r / ms_c))
+        # staggered: vehicles spread over the last quarter of the lap
+        L = mp.TrackLength
+        st = np.zeros((B, 8))
+        for b in range(B):
+            s = rng.uniform(0.8, 0.97) * L
+            x, y, th = PR.get_global_position(mp.PointAndTangent, s, rng.normal(0, 0.02))
+            st[b] = [x, y, rng.uniform(0.9, 1.1), 0, 0, 0, th, 0]
+        ms_r, vps_r, ph = race_run(mp, st, 1, 40, K)
+        lines.append("stagger  B=%5d  race %.3f ms/tick (%.3g alive vehicle-ticks/s, phases %s)" % (B, ms_r, vps_r, ph.tolist()))
+        for l in lines[-3:]:
+            print(l, flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
