@@ -89,7 +89,7 @@ EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_d
            "lpvmpc_handoff_batch", "lpvmpc_cascade_init", "lpvmpc_cascade_tick", "lpvmpc_cascade_read", "lpvmpc_cascade_alive_ticks",
            "lpvmpc_observer_default_config", "lpvmpc_observer_setup", "lpvmpc_observer_read", "lpvmpc_observer_step_batch",
            "lpvmpc_solve_batch_masked", "lpvmpc_race_default_config", "lpvmpc_race_init", "lpvmpc_race_tick", "lpvmpc_race_read",
-           "lpvmpc_race_laps", "lpvmpc_race_predictions")
+           "lpvmpc_race_laps", "lpvmpc_race_predictions", "lpvmpc_race_init_observed")
 
 _lib = None
 
@@ -195,6 +195,11 @@ def load():
         for name in ("lpvmpc_solve_batch_masked", "lpvmpc_race_init", "lpvmpc_race_tick", "lpvmpc_race_read", "lpvmpc_race_laps",
                      "lpvmpc_race_predictions"):
             getattr(lib, name).restype = C.c_int
+    except AttributeError:
+        pass
+    try:        # (nor the race with an estimator)
+        lib.lpvmpc_race_init_observed.argtypes = [vp, vp, vp, _i, vp, vp, P(RaceConfig), P(ObserverConfig)]
+        lib.lpvmpc_race_init_observed.restype = C.c_int
     except AttributeError:
         pass
     for name in ("lpvmpc_handoff_length", "lpvmpc_handoff_operators", "lpvmpc_handoff_setup", "lpvmpc_handoff_batch",

@@ -293,8 +293,14 @@ class BatchedSolver:
         self._chk(self._lib.lpvmpc_observer_setup(self._h, None if cfg is None else C.byref(cfg)))
 
     def observer_read(self):
-        """The fleet's (or cascade's) estimate [B,6] = [vx vy psiDot x y yaw] and latest measurement [B,5] = [vx psiDot x y yaw]."""
-        B = self._cas[0] if getattr(self, "_cas", None) is not None else self._cl_B
+        """The fleet's (or cascade's, or race's) estimate [B,6] = [vx vy psiDot x y yaw] and latest measurement [B,5] =
+        [vx psiDot x y yaw]."""
+        if getattr(self, "_race", None) is not None:
+            B = self._race[0]
+        elif getattr(self, "_cas", None) is not None:
+            B = self._cas[0]
+        else:
+            B = getattr(self, "_cl_B", 0)
         est, meas = np.empty((B, 6)), np.empty((B, 5))
         self._chk(self._lib.lpvmpc_observer_read(self._h, ptr(est), ptr(meas)))
         return est, meas
@@ -382,10 +388,13 @@ class BatchedSolver:
         return out
 
     # -- race engine: lap 0, per-vehicle lap events, racing (lpvmpc_race_*) ------------------------------------
-    def race_init(self, tt, planner, plant0, half_track0=None, **cfg):
+    def race_init(self, tt, planner, plant0, half_track0=None, estimator=None, **cfg):
         """Start a race owned by this PATH controller engine, with ``tt`` (racing tuning) and ``planner`` (handoff_setup done).
         plant0 [B,8]; half_track0 [B] (HalfTrack at the start, default 0); ``cfg``: fields of ``lpvmpc_race_config`` (laps,
-        n_sub_lap0, n_sub, q9_swap, half_width, slack, plan_max_ey, dt_sim, mu_sim)."""
+        n_sub_lap0, n_sub, q9_swap, half_width, slack, plan_max_ey, dt_sim, mu_sim).  ``estimator``: an
+        ``observer.observer_config`` result or an ``_ffi.ObserverConfig`` runs the race with the state estimator and the
+        simulated sensors in the loop (lpvmpc_race_init_observed; ``observer_read`` then returns its state); None runs it on
+        ground truth."""
         p0 = f64(plant0).reshape(-1, 8)
         B = p0.shape[0]
         c = _ffi.default_race_config()
@@ -403,7 +412,12 @@ class BatchedSolver:
             else:
                 raise TypeError("unknown race option %r" % k)
         ht = None if half_track0 is None else np.ascontiguousarray(np.broadcast_to(np.asarray(half_track0), (B,)), np.int32)
-        self._chk(self._lib.lpvmpc_race_init(self._h, tt._h, planner._h, B, ptr(p0), ptr(ht), C.byref(c)))
+        if estimator is None:
+            self._chk(self._lib.lpvmpc_race_init(self._h, tt._h, planner._h, B, ptr(p0), ptr(ht), C.byref(c)))
+        else:
+            if not isinstance(estimator, _ffi.ObserverConfig):
+                raise TypeError("estimator must be an observer.observer_config(...) result or an _ffi.ObserverConfig")
+            self._chk(self._lib.lpvmpc_race_init_observed(self._h, tt._h, planner._h, B, ptr(p0), ptr(ht), C.byref(c), C.byref(estimator)))
         self._race = (B, int(c.laps), tt, planner)           # (keeps the two other engines alive as long as the race)
 
     def race_tick(self, n_ticks=1):
@@ -747,9 +761,10 @@ class RaceFleet(object):
     path-following controller at 1 m/s, each vehicle's own lap event, then planner + trajectory-tracking controller until it has
     driven ``laps`` racing laps.  Three engines with the reference's tunings (CTRL_TUNINGS["path"], CTRL_TUNINGS["race"], the
     PLAN_* weights).  ``options``: race options of ``BatchedSolver.race_init`` (n_sub_lap0, n_sub, q9_swap, plan_max_ey, dt_sim,
-    mu_sim) and engine settings (e.g. kernel_variant) applied to all three engines."""
+    mu_sim) and engine settings (e.g. kernel_variant) applied to all three engines.  ``estimator``: an
+    ``observer.observer_config(...)`` result runs the race with the state estimator and the simulated sensors in the loop."""
 
-    def __init__(self, track_map, plant0, laps=1, N=20, Np=40, half_track0=None, device=0, **options):
+    def __init__(self, track_map, plant0, laps=1, N=20, Np=40, half_track0=None, device=0, estimator=None, **options):
         from .workloads import CTRL_TUNINGS, PLAN_L, PLAN_Q, PLAN_R, PLAN_dR
         race_keys = ("n_sub_lap0", "n_sub", "q9_swap", "plan_max_ey", "dt_sim", "mu_sim")
         race_opts = {k: v for k, v in options.items() if k in race_keys}
@@ -766,7 +781,7 @@ class RaceFleet(object):
         self.planner.handoff_setup()
         self.dt_sim = float(race_opts.get("dt_sim", 0.005))
         self.path.race_init(self.tt, self.planner, plant0, half_track0=half_track0, laps=laps, half_width=track_map.halfWidth,
-                            slack=track_map.slack, **race_opts)
+                            slack=track_map.slack, estimator=estimator, **race_opts)
 
     def run(self, n_ticks):
         """Enqueue n_ticks controller ticks (no synchronisation)."""
@@ -774,6 +789,11 @@ class RaceFleet(object):
 
     def state(self):
         return self.path.race_read()
+
+    def estimate(self):
+        """The estimator's state of a race started with ``estimator``: estimate [B,6] = [vx vy psiDot x y yaw] and the latest
+        sensor reading [B,5] = [vx psiDot x y yaw]."""
+        return self.path.observer_read()
 
     def lap_times(self):
         """[B, laps+1] simulated seconds of lap 0, 1, ..., laps (NaN where the lap has not been completed)."""

@@ -178,7 +178,7 @@ extern "C" int lpvmpc_cascade_init(lpvmpc_handle *h, lpvmpc_handle *plan, int32_
         std::vector<double> v(plant0, plant0 + b * 8);
         for (size_t i = 0; i < b; ++i) v[i * 8 + 4] = v[i * 8 + 5] = 0.0;
         H2D(c->estv, v.data(), b * 8 * 8);
-        rc = lpvmpc_observer_start(h, B, plant0, dt_sim, 1); if (rc) return rc;
+        rc = lpvmpc_observer_start(h, *h->obs_cfg, B, plant0, dt_sim, 1); if (rc) return rc;
     }
     return LPVMPC_OK;
 }

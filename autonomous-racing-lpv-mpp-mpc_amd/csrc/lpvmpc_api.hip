@@ -757,7 +757,7 @@ extern "C" int lpvmpc_cl_init(lpvmpc_handle *h, int32_t B, const double *plant0,
     h->cl_pc = lpvmpc_plant_cfg(h, n_sub, dt_sim, mu_sim);
     h->state_valid_B = 0;
     if (h->obs_state) { (void)hipFree(h->obs_state); h->obs_state = nullptr; }
-    if (h->obs_cfg) { rc = lpvmpc_observer_start(h, B, plant0, dt_sim, 0); if (rc) return rc; }   // the estimator in the loop
+    if (h->obs_cfg) { rc = lpvmpc_observer_start(h, *h->obs_cfg, B, plant0, dt_sim, 0); if (rc) return rc; }   // the estimator in the loop
     return LPVMPC_OK;
 }
 
@@ -822,7 +822,7 @@ extern "C" void lpvmpc_observer_default_config(lpvmpc_observer_config *c) {
     c->n_bound = 0.5; c->gps_freq = 1000.0;                                  // MAIN_LAUNCH:60-87 (every std 0)
 }
 
-static int observer_check(lpvmpc_handle *h, const lpvmpc_observer_config *c, const char *who) {
+int lpvmpc_observer_check(lpvmpc_handle *h, const lpvmpc_observer_config *c, const char *who) {
     if (!(c->loop_rate > 0) || !(c->gps_freq > 0) || !(c->n_bound >= 0))
         return fail(h, LPVMPC_E_ARG, "%s: loop_rate and gps_freq must be > 0, n_bound >= 0", who);
     const double sd[5] = {c->psi_std, c->psiDot_std, c->x_std, c->y_std, c->v_std};
@@ -833,8 +833,7 @@ static int observer_check(lpvmpc_handle *h, const lpvmpc_observer_config *c, con
 // the estimator state of a fleet (from_plant = 0: estimate [init_vx, 0, 0, x0, y0, yaw0]) or of a cascade (from_plant = 1: the cascade
 // starts at the lap event of a running vehicle, whose estimator has been running since its start -- the estimate starts at the plant
 // state [vx, vy, psiDot, x, y, yaw]); GPS hold = start position, encoder reading 0, step counter 0.  Synchronises.
-int lpvmpc_observer_start(lpvmpc_handle *h, int B, const double *plant0, double dt_sim, int from_plant) {
-    const lpvmpc_observer_config &o = *h->obs_cfg;
+int lpvmpc_observer_start(lpvmpc_handle *h, const lpvmpc_observer_config &o, int B, const double *plant0, double dt_sim, int from_plant) {
     std::vector<double> os((size_t)B * lpvmpc::kObsStride, 0.0);
     for (int b = 0; b < B; ++b) {
         double *e = os.data() + (size_t)b * lpvmpc::kObsStride; const double *p = plant0 + (size_t)b * 8;
@@ -861,7 +860,7 @@ extern "C" int lpvmpc_observer_setup(lpvmpc_handle *h, const lpvmpc_observer_con
     if (!h) return fail(nullptr, LPVMPC_E_ARG, "lpvmpc_observer_setup: handle is NULL");
     if (h->cfg.kind != LPVMPC_KIND_CONTROLLER) return fail(h, LPVMPC_E_ARG, "lpvmpc_observer_setup: controller handles only");
     if (!cfg) { delete h->obs_cfg; h->obs_cfg = nullptr; return LPVMPC_OK; }
-    int rc = observer_check(h, cfg, "lpvmpc_observer_setup"); if (rc) return rc;
+    int rc = lpvmpc_observer_check(h, cfg, "lpvmpc_observer_setup"); if (rc) return rc;
     if (!h->obs_cfg) h->obs_cfg = new (std::nothrow) lpvmpc_observer_config();
     if (!h->obs_cfg) return fail(h, LPVMPC_E_NOMEM, "out of host memory");
     *h->obs_cfg = *cfg;
@@ -869,8 +868,9 @@ extern "C" int lpvmpc_observer_setup(lpvmpc_handle *h, const lpvmpc_observer_con
 }
 
 extern "C" int lpvmpc_observer_read(lpvmpc_handle *h, double *est, double *meas) {
-    if (!h || !(h->cl_plant || h->cascade) || !h->obs_state)
-        return fail(h, LPVMPC_E_ARG, "lpvmpc_observer_read: no fleet or cascade with an estimator (lpvmpc_observer_setup, then lpvmpc_cl_init / lpvmpc_cascade_init)");
+    if (!h || !(h->cl_plant || h->cascade || h->race) || !h->obs_state)
+        return fail(h, LPVMPC_E_ARG, "lpvmpc_observer_read: no fleet, cascade or race with an estimator (lpvmpc_observer_setup, then lpvmpc_cl_init / "
+                                     "lpvmpc_cascade_init; or lpvmpc_race_init_observed)");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, hipDeviceSynchronize());      // a cascade runs on its own streams
     const size_t B = h->obs_B;
@@ -897,7 +897,7 @@ extern "C" int lpvmpc_observer_step_batch(lpvmpc_handle *h, int32_t B, const lpv
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     int rc;
     if (!cfg || !est || !y || !u || !k) return fail(h, LPVMPC_E_ARG, "lpvmpc_observer_step_batch: bad argument");
-    rc = observer_check(h, cfg, "lpvmpc_observer_step_batch"); if (rc) return rc;
+    rc = lpvmpc_observer_check(h, cfg, "lpvmpc_observer_step_batch"); if (rc) return rc;
     const size_t per = (size_t)(6 + 5 + 2 + lpvmpc::kObsAux) * 8 + 8;
     if (B > h->obs_ws_cap) {
         if (h->obs_ws) { (void)hipFree(h->obs_ws); h->obs_ws = nullptr; h->obs_ws_cap = 0; }

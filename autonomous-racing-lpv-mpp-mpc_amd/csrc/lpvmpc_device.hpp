@@ -155,6 +155,8 @@ struct RaceDev {              // device pointers and constants of one race (lpvm
     int B, N, Np, M, laps, q9, n_sub_lap0, n_sub[3], lap_cols;
     double hw, slack;
     double *plant, *cmd, *local;                // [B][8], [B][2], [B][6]
+    const double *meas;                         // [B][8] what the measurements read: the plant, or with an estimator estv
+    double *estv;                               // [B][8] with an estimator: the estimate in the plant's layout [x y vx vy 0 0 yaw psiDot]
     int32_t *phase, *lap, *half, *rk, *plan_done, *idx;   // [B]: phase, lap counter, HalfTrack, racing ticks done, planner ticks done, `index`
     int32_t *nstep, *src;                       // [B] this tick: plant steps; controller that solved (0 path, 1 TT, -1 none)
     int32_t *step, *lap_step, *alive;           // [B] plant steps so far; [B][lap_cols] step at which each lap starts (-1: not yet); alive ticks
@@ -172,5 +174,7 @@ struct RaceDev {              // device pointers and constants of one race (lpvm
 hipError_t launch_race_plan_start(const DevCfg *pcfg, const RaceDev &r, hipStream_t s);
 hipError_t launch_race_measure(const DevCfg *ccfg, const RaceDev &r, int seed_tick, hipStream_t s);
 hipError_t launch_race_command_plant(const RaceDev &r, PlantCfg pc, hipStream_t s);
+hipError_t launch_race_command_plant_observe(const RaceDev &r, PlantCfg pc, const double *gains, double *obs, const ObsParams &op,
+                                            hipStream_t s);
 
 }  // namespace lpvmpc

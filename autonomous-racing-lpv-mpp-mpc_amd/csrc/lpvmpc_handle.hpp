@@ -78,7 +78,8 @@ struct lpvmpc_handle {
     // gain-scheduled LPV estimator (lpvmpc_observer_*, observer.hip)
     lpvmpc_observer_config *obs_cfg;    // set by lpvmpc_observer_setup, taken by the next lpvmpc_cl_init (null: no estimator)
     double *obs_gains;                  // device copy of the gain words (head of lpvmpc_observer_config): the fleet's or the batch call's
-    double *obs_state;                  // the fleet's / cascade's estimator state [obs_B][kObsStride] (null: it runs on ground truth)
+    double *obs_state;                  // the fleet's / cascade's / race's estimator state [obs_B][kObsStride] (null: it runs on ground truth;
+                                        // a race's is set by lpvmpc_race_init_observed without obs_cfg and freed with the race)
     int obs_B;
     lpvmpc::ObsParams obs_p;
     char *obs_ws;                       // lpvmpc_observer_step_batch staging, obs_ws_cap instances
@@ -105,7 +106,9 @@ LPVMPC_HIDDEN int lpvmpc_launch_solve_timed(lpvmpc_handle *h, const lpvmpc::Solv
 LPVMPC_HIDDEN lpvmpc::PlantCfg lpvmpc_plant_cfg(const lpvmpc_handle *h, int n_sub, double dt_sim, double mu_sim);
 LPVMPC_HIDDEN void lpvmpc_cascade_free(lpvmpc_handle *h);
 LPVMPC_HIDDEN void lpvmpc_race_free(lpvmpc_handle *h);                                  // race_api.hip
-LPVMPC_HIDDEN int lpvmpc_observer_start(lpvmpc_handle *h, int B, const double *plant0, double dt_sim, int from_plant);   // lpvmpc_api.hip                               // cascade_api.hip
+LPVMPC_HIDDEN int lpvmpc_observer_start(lpvmpc_handle *h, const lpvmpc_observer_config &o, int B, const double *plant0, double dt_sim,
+                                        int from_plant);                                // lpvmpc_api.hip
+LPVMPC_HIDDEN int lpvmpc_observer_check(lpvmpc_handle *h, const lpvmpc_observer_config *c, const char *who);   // lpvmpc_api.hip
 namespace lpvmpc {
 // handoff.hip (host): interpolation operator W and interpolation + filtfilt operator FW, both [M][N] row-major
 bool handoff_operators(int N, double dt, double interp_dt, int padlen, int ord, const double *b, const double *a,

@@ -11,135 +11,10 @@
 // mostly at the same address across the wavefront.  They are staged in LDS once per workgroup: constant memory would need a
 // per-launch symbol copy (one table per handle, handles on different streams), and LDS reads of a common address broadcast.
 #include "lpvmpc_device.hpp"
+#include "observer_device.hpp"
 #include "track_geometry.hpp"
 
 namespace lpvmpc {
-
-constexpr int kObsGainWords = 2 * (kObsTable + 12);    // [L_ls][lim_ls][L_hs][lim_hs]: the head of lpvmpc_observer_config
-
-// ---- counter-based noise (documented in lpvmpc.h) -----------------------------------------------------------------------
-__device__ inline unsigned long long obs_mix(unsigned long long z) {
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27; z *= 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__device__ inline double obs_gauss(unsigned long long seed, long long vid, long long step, int ch) {
-    const unsigned long long g = 0x9E3779B97F4A7C15ull;
-    const unsigned long long key = obs_mix(obs_mix(seed + g * ((unsigned long long)vid + 1ull)) ^ (8ull * (unsigned long long)step + (unsigned long long)ch));
-    const double u1 = (double)((obs_mix(key + g) >> 11) + 1ull) * 0x1.0p-53;
-    const double u2 = (double)(obs_mix(key + 2ull * g) >> 11) * 0x1.0p-53;
-    return sqrt(-2.0 * log(u1)) * cos(2.0 * M_PI * u2);
-}
-// clip(std * g, +-std * n_bound); a channel whose std is 0 draws nothing and adds 0
-__device__ inline double obs_noise(const ObsParams &p, long long vid, long long step, int ch) {
-    const double sd = p.std[ch];
-    if (sd == 0.0) return 0.0;
-    const double n = sd * obs_gauss(p.seed, vid, step, ch), lim = sd * p.n_bound;
-    return n > lim ? lim : (n < -lim ? -lim : n);
-}
-
-// ---- one GS_LPV_Est step (EST:349-398) ------------------------------------------------------------------------------------
-// G: the gain words (LDS); x [6] in/out; y [5]; t = k dt.  L [30], A [36], Bm [12] receive the step's matrices.
-__device__ inline void obs_step(const double *G, double x[6], const double y[5], double servo, double motor, double k, double dt,
-                                double L[30], double A[36], double Bm[12]) {
-    const double t = k * dt;
-    const bool run = t > 0.02;
-    const double vx = run ? x[0] : y[0], vy = run ? x[1] : 0.0, th = run ? x[5] : y[4];
-    const double steer = servo;
-    // Continuous_AB_Comp (EST:402-436): the observer's own constants
-    const double lf = 0.125, lr = 0.125, m = 1.98, I = 0.03, Cf = 60, Cr = 60, mu = 0.05;
-    double ss, cs, sth, cth;
-    sincos(steer, &ss, &cs);
-    sincos(th, &sth, &cth);
-    Bm[0] = -(ss * Cf) / m; Bm[1] = 1.0;
-    Bm[2] = (cs * Cf) / m;  Bm[3] = 0.0;
-    Bm[4] = (lf * Cf * cs) / I; Bm[5] = 0.0;
-#pragma unroll
-    for (int i = 6; i < 12; ++i) Bm[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 36; ++i) A[i] = 0.0;
-    A[0] = -mu;
-    A[1] = (ss * Cf) / (m * vx);
-    A[2] = (ss * Cf * lf) / (m * vx) + vy;
-    A[7] = -(Cr + Cf * cs) / (m * vx);
-    A[8] = -(lf * Cf * cs - lr * Cr) / (m * vx) - vx;
-    A[13] = -(lf * Cf * cs - lr * Cr) / (I * vx);
-    A[14] = -(lf * lf * Cf * cs + lr * lr * Cr) / (I * vx);
-    A[18] = cth; A[19] = -sth;
-    A[24] = sth; A[25] = cth;
-    A[32] = 1.0;
-    // L_Gain_Comp (EST:439-492): polytope choice, unclamped vertex weights, blend
-    const double *Lg = vx > G[kObsTable + 1] ? G + kObsTable + 12 : G;
-    const double *lim = Lg + kObsTable;
-    const double Mvx = (lim[1] - vx) / (lim[1] - lim[0]);
-    const double Mvy = (lim[3] - vy) / (lim[3] - lim[2]);
-    const double Mst = (lim[7] - steer) / (lim[7] - lim[6]);
-    const double Mth = (lim[11] - th) / (lim[11] - lim[10]);
-    double w[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const double a = (i & 8) ? 1 - Mvx : Mvx, b = (i & 4) ? 1 - Mvy : Mvy, c = (i & 2) ? 1 - Mst : Mst, d = (i & 1) ? 1 - Mth : Mth;
-        w[i] = a * b * c * d;
-    }
-#pragma unroll
-    for (int e = 0; e < 30; ++e) {
-        double s = 0.0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) s += w[i] * Lg[e * 16 + i];
-        L[e] = s;
-    }
-    // x+ = x + (dt (A + L C) x + dt B u - dt L y), C = rows {0, 2, 3, 4, 5} of I6 (EST:248-252)
-    double xn[6];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-        const double M0 = A[r * 6 + 0] + L[r * 5 + 0], M1 = A[r * 6 + 1], M2 = A[r * 6 + 2] + L[r * 5 + 1],
-                     M3 = A[r * 6 + 3] + L[r * 5 + 2], M4 = A[r * 6 + 4] + L[r * 5 + 3], M5 = A[r * 6 + 5] + L[r * 5 + 4];
-        const double Mx = M0 * x[0] + M1 * x[1] + M2 * x[2] + M3 * x[3] + M4 * x[4] + M5 * x[5];
-        const double Bu = Bm[r * 2 + 0] * servo + Bm[r * 2 + 1] * motor;
-        const double Ly = L[r * 5 + 0] * y[0] + L[r * 5 + 1] * y[1] + L[r * 5 + 2] * y[2] + L[r * 5 + 3] * y[3] + L[r * 5 + 4] * y[4];
-        xn[r] = x[r] + (dt * Mx + dt * Bu - dt * Ly);
-    }
-#pragma unroll
-    for (int r = 0; r < 6; ++r) x[r] = xn[r];
-}
-
-// ---- sensors + one observer step after a plant step ------------------------------------------------------------------------
-// os [kObsStride]: see ObsSlot; st = plant state just advanced.
-__device__ inline void obs_substep(const double *G, const ObsParams &p, long long vid, double *os, const double st[8], double servo,
-                                   double motor) {
-    const double k = os[OBS_K] + 1.0;
-    os[OBS_K] = k;
-    const long long step = (long long)k;
-    const double imu_yaw = st[6] + obs_noise(p, vid, step, 0);
-    const double imu_w = st[7] + obs_noise(p, vid, step, 1);
-    const double gx = st[0] + obs_noise(p, vid, step, 2), gy = st[1] + obs_noise(p, vid, step, 3);
-    // SIM:296-305: publish when the counter exceeds thUpdate, then restart it
-    const bool pub = os[OBS_GPS_CNT] > p.th_update;
-    os[OBS_GPS_CNT] = pub ? 0.0 : os[OBS_GPS_CNT] + 1.0;
-    os[OBS_GPS_X] = pub ? gx : os[OBS_GPS_X];
-    os[OBS_GPS_Y] = pub ? gy : os[OBS_GPS_Y];
-    // EST:733-741: a changed reading is taken; more than 40 unchanged readings in a row read 0 (v_prev becomes v either way)
-    const double v = sqrt(st[2] * st[2] + st[3] * st[3]) + obs_noise(p, vid, step, 4);
-    const bool changed = v != os[OBS_ENC_PREV];
-    os[OBS_ENC_CNT] = changed ? 0.0 : os[OBS_ENC_CNT] + 1.0;
-    os[OBS_ENC_MEAS] = changed ? v : (os[OBS_ENC_CNT] > 40.0 ? 0.0 : os[OBS_ENC_MEAS]);
-    os[OBS_ENC_PREV] = v;
-    // EST:330-333: the start-up measurement
-    const bool run = k * p.dt > 0.02;
-    double y[5];
-    y[0] = run ? os[OBS_ENC_MEAS] : os[0];
-    y[1] = imu_w; y[2] = os[OBS_GPS_X]; y[3] = os[OBS_GPS_Y];
-    y[4] = run ? imu_yaw : st[6];
-    double L[30], A[36], Bm[12];
-    obs_step(G, os, y, servo, motor, k, p.dt, L, A, Bm);
-#pragma unroll
-    for (int i = 0; i < 5; ++i) os[OBS_Y + i] = y[i];
-}
-
-__device__ inline void obs_stage_gains(double *lds, const double *__restrict__ g) {
-    for (int i = threadIdx.x; i < kObsGainWords; i += blockDim.x) lds[i] = g[i];
-    __syncthreads();
-}
 
 __global__ void __launch_bounds__(64) observer_step_kernel(const double *__restrict__ gains, int B, double *__restrict__ est,
                                                            const double *__restrict__ y, const double *__restrict__ u,

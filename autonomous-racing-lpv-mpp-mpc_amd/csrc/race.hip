@@ -12,7 +12,12 @@
 //   controllerMain.py:381-386           command from the controller of the vehicle's lap, then the simulator steps
 //
 // The masks written here select the instances of this tick's masked launches (LPV, solve, hand-off: SolveArgs::active).
+//
+// With the estimator in the loop (lpvmpc_race_init_observed) every measurement -- both branches, both lap-event rules and the
+// planner's first state -- reads RaceDev::meas = the estimate view instead of the plant (CMAIN:179-180 and PMAIN:141 read
+// pos_info), and race_command_plant_observe_kernel runs sensors + one observer step after each plant step.
 #include "lpvmpc_device.hpp"
+#include "observer_device.hpp"
 #include "track_geometry.hpp"
 
 namespace lpvmpc {
@@ -26,20 +31,20 @@ __device__ inline bool plant_finite(const double *p) {
 // first launch of a tick: which racing vehicles run a planner tick before this controller tick (planner ticks
 // 0 .. floor(2k/3) precede racing tick k), and their initial state -- measured from the plant on the vehicle's first planner
 // tick (plus the seed trajectory the ABC linearisation needs), Planner.xPred[1] on the later ones (replaces the cascade's
-// strided device copy).  c is the planner's configuration.
+// strided device copy).  c is the planner's configuration.  "Measured" reads r.meas: the plant, or the estimate.
 __global__ void __launch_bounds__(64) race_plan_start_kernel(const DevCfg *__restrict__ cp, RaceDev r) {
     const DevCfg &c = *cp;
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= r.B) return;
     int first = 0, cont = 0;
-    const double *p = r.plant + (size_t)b * 8;
-    if (r.phase[b] == 1 && plant_finite(p)) {
+    const double *p = r.plant + (size_t)b * 8, *m = r.meas + (size_t)b * 8;
+    if (r.phase[b] == 1 && plant_finite(p) && plant_finite(m)) {
         const int k = r.rk[b], done = r.plan_done[b];
         if (done <= (2 * k) / 3) {
             const int Np = c.N;
             double *x0 = r.q_x0 + (size_t)b * 5;
             if (done == 0) {
-                plan_first_one(c, p, r.hw, r.slack, r.q9, 0.2, x0, r.q_xlast + (size_t)b * Np * 6, r.q_delta + (size_t)b * Np);
+                plan_first_one(c, m, r.hw, r.slack, r.q9, 0.2, x0, r.q_xlast + (size_t)b * Np * 6, r.q_delta + (size_t)b * Np);
                 first = 1;
             } else {
                 const double *xp = r.q_xPred + (size_t)b * (Np + 1) * 5 + 5;
@@ -52,7 +57,8 @@ __global__ void __launch_bounds__(64) race_plan_start_kernel(const DevCfg *__res
     r.m_pfirst[b] = first; r.m_pcont[b] = cont; r.m_plan[b] = first | cont;
 }
 
-// measurement, lap logic and this tick's controller masks.  c is the controllers' configuration (path and TT share N, dt, track).
+// measurement (from r.meas), lap logic and this tick's controller masks.  c is the controllers' configuration (path and TT share
+// N, dt, track).  A vehicle entering the tick with a non-finite plant or measurement source is lost.
 // seed_tick: the race's first 9 ticks (first_it < 10, CMAIN:310-320) solve the path controller on the seed trajectories.
 __global__ void __launch_bounds__(64) race_measure_kernel(const DevCfg *__restrict__ cp, RaceDev r, int seed_tick) {
     const DevCfg &c = *cp;
@@ -62,8 +68,8 @@ __global__ void __launch_bounds__(64) race_measure_kernel(const DevCfg *__restri
     r.m_path[b] = 0; r.m_tt[b] = 0; r.nstep[b] = 0; r.src[b] = -1;
     const int ph = r.phase[b];
     if (ph >= 2) return;                                                    // finished / lost: frozen
-    const double *p = r.plant + (size_t)b * 8;
-    if (!plant_finite(p)) { r.phase[b] = 3; return; }
+    const double *p = r.meas + (size_t)b * 8;
+    if (!plant_finite(r.plant + (size_t)b * 8) || !plant_finite(p)) { r.phase[b] = 3; return; }
     r.alive[b] += 1;
     const double L = c.track[(c.track_rows - 1) * 6 + 3] + c.track[(c.track_rows - 1) * 6 + 4];
     double *ls = r.local + (size_t)b * 6;
@@ -136,6 +142,45 @@ __global__ void __launch_bounds__(64) race_command_plant_kernel(RaceDev r, Plant
     r.step[b] += n;
 }
 
+// race_command_plant_kernel with the estimator in the loop: per plant step, plant -> sensors -> observer (obs_substep, the schedule
+// of cl_command_plant_observe_kernel), then the estimate view that the next tick's measurements read.  A frozen vehicle (nstep 0)
+// advances neither the plant nor its observer, so its noise keys (vid, step) depend on its own steps only.
+__global__ void __launch_bounds__(64) race_command_plant_observe_kernel(RaceDev r, PlantCfg pc, const double *__restrict__ gains,
+                                                                        double *__restrict__ obs, ObsParams op) {
+    __shared__ double G[kObsGainWords];
+    obs_stage_gains(G, gains);
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= r.B) return;
+    const int src = r.src[b], n = r.nstep[b], N = r.N;
+    if (src == 0) { r.iters[b] = r.p_iters[b]; r.status[b] = r.p_status[b]; }
+    else if (src == 1) { r.iters[b] = r.t_iters[b]; r.status[b] = r.t_status[b]; }
+    else r.iters[b] = 0;
+    if (n == 0) return;
+    const double *u = (r.lap[b] == 0 ? r.p_uPred : r.t_uPred) + (size_t)b * N * 2;
+    const double servo = u[0], motor = u[1];
+    r.cmd[b * 2 + 0] = servo; r.cmd[b * 2 + 1] = motor;
+    double st[8], os[kObsStride];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) st[i] = r.plant[(size_t)b * 8 + i];
+#pragma unroll
+    for (int i = 0; i < kObsStride; ++i) os[i] = obs[(size_t)b * kObsStride + i];
+    const long long vid = op.voff + b;
+    for (int k = 0; k < n; ++k) {
+        // compiler-only barrier: without it the gain words' LDS loads (read-only after the staging barrier) are hoisted out of
+        // the loop for both polytopes, 1968 registers' worth, and spill to scratch (6.7 KB per lane)
+        asm volatile("" ::: "memory");
+        plant_step(pc, st, motor, servo);
+        obs_substep(G, op, vid, os, st, servo, motor);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) r.plant[(size_t)b * 8 + i] = st[i];
+#pragma unroll
+    for (int i = 0; i < kObsStride; ++i) obs[(size_t)b * kObsStride + i] = os[i];
+    double *v = r.estv + (size_t)b * 8;
+    v[0] = os[3]; v[1] = os[4]; v[2] = os[0]; v[3] = os[1]; v[4] = 0.0; v[5] = 0.0; v[6] = os[5]; v[7] = os[2];
+    r.step[b] += n;
+}
+
 #define LPVMPC_GRID(n) dim3(((n) + 63) / 64), dim3(64)
 hipError_t launch_race_plan_start(const DevCfg *pcfg, const RaceDev &r, hipStream_t s) {
     hipLaunchKernelGGL(race_plan_start_kernel, LPVMPC_GRID(r.B), 0, s, pcfg, r);
@@ -147,6 +192,11 @@ hipError_t launch_race_measure(const DevCfg *ccfg, const RaceDev &r, int seed_ti
 }
 hipError_t launch_race_command_plant(const RaceDev &r, PlantCfg pc, hipStream_t s) {
     hipLaunchKernelGGL(race_command_plant_kernel, LPVMPC_GRID(r.B), 0, s, r, pc);
+    return hipGetLastError();
+}
+hipError_t launch_race_command_plant_observe(const RaceDev &r, PlantCfg pc, const double *gains, double *obs, const ObsParams &op,
+                                            hipStream_t s) {
+    hipLaunchKernelGGL(race_command_plant_observe_kernel, LPVMPC_GRID(r.B), 0, s, r, pc, gains, obs, op);
     return hipGetLastError();
 }
 

@@ -1,6 +1,8 @@
 // race_api.hip -- C ABI of the race engine (include/lpvmpc.h, lpvmpc_race_*): lap 0, per-vehicle lap events and racing
 // for one fleet on the device, owned by the path controller handle.  Kernels: race.hip (per-tick glue), lpv_eval.hip,
-// admm_solve.hip and handoff.hip (masked launches).
+// admm_solve.hip and handoff.hip (masked launches).  A race with the estimator in the loop (lpvmpc_race_init_observed) keeps
+// the estimator state, gains and parameters in the path handle's obs_state / obs_gains / obs_p (obs_cfg stays null, so the
+// handle's next lpvmpc_cl_init runs on ground truth); lpvmpc_race_free releases them.
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -22,8 +24,13 @@ void lpvmpc_race_free(lpvmpc_handle *h) {
     lpvmpc::RaceDev &d = r->d;
     void *ptrs[] = {d.plant, d.cmd, d.local, d.phase, d.lap, d.half, d.rk, d.plan_done, d.idx, d.nstep, d.src, d.step, d.lap_step,
                     d.alive, d.iters, d.status, d.m_path, d.m_tt, d.m_plan, d.m_pfirst, d.m_pcont, d.SSc, d.ref0, d.refs, d.SSp,
-                    d.pose, d.sig};
+                    d.pose, d.sig, d.estv};
     for (void *p : ptrs) if (p) (void)hipFree(p);
+    if (d.estv) {                                                // the race's estimator
+        if (h->obs_state) (void)hipFree(h->obs_state);
+        if (h->obs_gains) (void)hipFree(h->obs_gains);
+        h->obs_state = h->obs_gains = nullptr; h->obs_B = 0; h->obs_p = lpvmpc::ObsParams{};
+    }
     if (r->tt && r->tt->race_owner == h) r->tt->race_owner = nullptr;
     if (r->plan && r->plan->race_owner == h) r->plan->race_owner = nullptr;
     delete r;
@@ -42,8 +49,8 @@ extern "C" void lpvmpc_race_default_config(lpvmpc_race_config *c) {
 
 static bool busy(const lpvmpc_handle *x) { return x->cl_plant || x->cascade || x->cascade_owner || x->race || x->race_owner; }
 
-extern "C" int lpvmpc_race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, int32_t B, const double *plant0,
-                                const int32_t *half_track0, const lpvmpc_race_config *cfg) {
+static int race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, int32_t B, const double *plant0, const int32_t *half_track0,
+                     const lpvmpc_race_config *cfg, const lpvmpc_observer_config *obs, bool observed_call) {
     if (!h) return fail(nullptr, LPVMPC_E_ARG, "lpvmpc_race_init: path handle is NULL");
     if (!tt || !plan || !plant0 || !cfg || B <= 0) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: NULL argument or B <= 0");
     if (h->cfg.kind != LPVMPC_KIND_CONTROLLER || tt->cfg.kind != LPVMPC_KIND_CONTROLLER || plan->cfg.kind != LPVMPC_KIND_PLANNER || h == tt)
@@ -59,11 +66,15 @@ extern "C" int lpvmpc_race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_hand
     if (!plan->d_Wop) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: call lpvmpc_handoff_setup on the planner handle first");
     if (plan->ho_M < h->cfg.N) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: the planner message (%d samples) is shorter than the controller horizon", plan->ho_M);
     if (h->warm_mode || tt->warm_mode || plan->warm_mode) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: warm_start must be 0 on all three handles");
-    if (h->obs_cfg) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: the race does not run the state estimator (remove it from the path handle)");
+    if (h->obs_cfg && !observed_call) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: the race does not run the state estimator (remove it from the path handle)");
+    if (h->obs_cfg) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init_observed: the race's estimator is configured through the obs argument; "
+                                                 "remove the one lpvmpc_observer_setup attached to the path handle");
     if (busy(h) || busy(tt) || busy(plan)) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: a handle already runs a fleet, cascade or race (lpvmpc_cl_release ends it)");
     if (cfg->laps < 1 || cfg->n_sub_lap0 < 1 || cfg->n_sub[0] < 1 || cfg->n_sub[1] < 1 || cfg->n_sub[2] < 1 || !(cfg->dt_sim > 0))
         return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: bad configuration (laps >= 1, step counts >= 1, dt_sim > 0)");
-    int rc = lpvmpc_need_track(h, "lpvmpc_race_init"); if (rc) return rc;
+    int rc;
+    if (obs) { rc = lpvmpc_observer_check(h, obs, "lpvmpc_race_init_observed"); if (rc) return rc; }
+    rc = lpvmpc_need_track(h, "lpvmpc_race_init"); if (rc) return rc;
     rc = lpvmpc_need_track(plan, "lpvmpc_race_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
     rc = lpvmpc_check_common(h, B, "lpvmpc_race_init"); if (rc) return rc;
     rc = lpvmpc_check_common(tt, B, "lpvmpc_race_init(tt)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
@@ -88,6 +99,7 @@ extern "C" int lpvmpc_race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_hand
     ALLOC(d.SSc, b * 8); ALLOC(d.ref0, b * 3 * 8); ALLOC(d.refs, b * 5 * M * 8);
     ALLOC(d.SSp, b * (Np + 1) * 8); ALLOC(d.pose, b * 3 * 8); ALLOC(d.sig, b * 5 * Np * 8);
 #undef ALLOC
+    d.meas = d.plant;
     d.p_uold = h->d_uold; d.p_uPred = h->d_uPred; d.p_vel = h->d_vel; d.p_curv = h->d_curv; d.p_iters = h->d_iters; d.p_status = h->d_status;
     d.t_uold = tt->d_uold; d.t_uPred = tt->d_uPred; d.t_vel = tt->d_vel; d.t_curv = tt->d_curv; d.t_iters = tt->d_iters; d.t_status = tt->d_status;
     d.q_x0 = plan->d_x0; d.q_xPred = plan->d_xPred; d.q_xlast = plan->d_xlast; d.q_delta = plan->d_delta;
@@ -117,7 +129,28 @@ extern "C" int lpvmpc_race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_hand
     H2D(plan->d_maxey, mey.data(), b * 8);                                                 // Planner.solve(..., HW)  (PMAIN:162,176)
     HIP_TRY(h, hipStreamSynchronize(st));
     h->state_valid_B = tt->state_valid_B = plan->state_valid_B = 0;
+    if (obs) {    // the estimator in the loop: it starts as the lap-0 fleet's (from_plant = 0) and runs through the lap event
+        std::vector<double> v(b * 8, 0.0);                                              // the estimate in the plant's layout
+        for (size_t i = 0; i < b; ++i) {
+            const double *p = plant0 + i * 8;
+            v[i * 8 + 0] = p[0]; v[i * 8 + 1] = p[1]; v[i * 8 + 2] = obs->init_vx; v[i * 8 + 6] = p[6];
+        }
+        HIP_TRY(h, hipMalloc((void **)&d.estv, b * 8 * 8));
+        H2D(d.estv, v.data(), b * 8 * 8);
+        rc = lpvmpc_observer_start(h, *obs, B, plant0, cfg->dt_sim, 0); if (rc) return rc;     // (synchronises)
+        d.meas = d.estv;
+    }
     return LPVMPC_OK;
+}
+
+extern "C" int lpvmpc_race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, int32_t B, const double *plant0,
+                                const int32_t *half_track0, const lpvmpc_race_config *cfg) {
+    return race_init(h, tt, plan, B, plant0, half_track0, cfg, nullptr, false);
+}
+
+extern "C" int lpvmpc_race_init_observed(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, int32_t B, const double *plant0,
+                                         const int32_t *half_track0, const lpvmpc_race_config *cfg, const lpvmpc_observer_config *obs) {
+    return race_init(h, tt, plan, B, plant0, half_track0, cfg, obs, true);
 }
 
 // one tick, in order on the path handle's stream: masked planner work, measurement, path LPV + solve, TT LPV + solve,
@@ -163,7 +196,8 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
                      tt->d_resid, nullptr, 0, 6};
         ta.active = d.m_tt;
         rc = lpvmpc_launch_solve_timed(tt, ta, st); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
-        HIP_TRY(h, lpvmpc::launch_race_command_plant(d, r->pc, st));
+        if (d.estv) HIP_TRY(h, lpvmpc::launch_race_command_plant_observe(d, r->pc, h->obs_gains, h->obs_state, h->obs_p, st));
+        else HIP_TRY(h, lpvmpc::launch_race_command_plant(d, r->pc, st));
         r->ticks++;
     }
     return LPVMPC_OK;

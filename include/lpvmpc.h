@@ -418,7 +418,8 @@ int lpvmpc_cascade_alive_ticks(lpvmpc_handle *ctrl, int32_t *alive_ticks);
  * Definitions of this engine where the ROS run has none:
  *   finish: when the lap counter exceeds `laps` (RunController = 0 in the reference) the vehicle is phase 2 and FROZEN from
  *     that tick on -- plant and command are not advanced, it costs no iterations, its outputs stay readable;
- *   lost: a vehicle entering a tick with a non-finite plant state is phase 3 and frozen the same way;
+ *   lost: a vehicle entering a tick with a non-finite plant state (with an estimator: or a non-finite estimate) is phase 3
+ *     and frozen the same way;
  *   lap time: lap_step [B][laps + 2] holds the plant-step index at which lap 0, 1, ... started (-1: not reached), so
  *     lap times are step differences x dt_sim (simulated time; the reference's TLAPTIME is wall-clock time).
  * Kernel launches that only write per-tick scratch run unmasked (the seed-tick ABC linearisation of `path`); every launch
@@ -427,7 +428,27 @@ int lpvmpc_cascade_alive_ticks(lpvmpc_handle *ctrl, int32_t *alive_ticks);
  * N > 20 (the seed rows), steering_delay != 0, a planner without lpvmpc_handoff_setup or with a message shorter than N,
  * warm_start != 0 on any of the three, an estimator on `path`, a handle already running a fleet, cascade or race.
  * The race belongs to `path`: lpvmpc_cl_release(path) (or destroying any of the three) ends it; while it runs, batch calls
- * on all three handles fail.  plant0 [B][8] = {x y vx vy ax ay yaw psiDot}; half_track0 [B] or NULL (= 0). */
+ * on all three handles fail.  plant0 [B][8] = {x y vx vy ax ay yaw psiDot}; half_track0 [B] or NULL (= 0).
+ *
+ * lpvmpc_race_init_observed runs the race with the gain-scheduled LPV estimator and the simulated sensors in the loop
+ * (below: "Gain-scheduled LPV state estimator"); with obs == NULL it is exactly lpvmpc_race_init.  obs is checked like
+ * lpvmpc_observer_setup's config, and a path handle with lpvmpc_observer_setup attached is refused by both calls: the race's
+ * estimator is configured through obs only.  With an estimator:
+ *   start: each vehicle's estimator starts as the lap-0 fleet's: estimate [init_vx, 0, 0, x0, y0, yaw0] of plant0, GPS hold at
+ *     the start position, step counter 0.  ONE estimator runs for the whole race: it carries on through the lap event (the
+ *     reference's estimator node keeps running) and is not restarted from the plant as lpvmpc_cascade_init starts one;
+ *   plant steps: each of a vehicle's n_sub_lap0 / n_sub[k % 3] plant steps of a tick is followed by its sensors and one observer
+ *     step, as in a fleet with an estimator.  Finished and lost vehicles advance neither plant nor observer and their step
+ *     counter stays put, so a vehicle's noise depends on (seed, vehicle_offset + b, its own step) only -- not on the batch, the
+ *     other vehicles' phases or the sharding;
+ *   measurement: every measurement reads the ESTIMATE in the plant's layout [x y vx vy 0 0 yaw psiDot] in place of the plant:
+ *     the lap-0 branch with HalfTrack and the lap-0 event rule, the racing branch with the racing event rule (|x| < 0.1 with x
+ *     the estimate's), and the planner's first state (PMAIN:141);
+ *   outputs: lpvmpc_race_read's plant stays the ground truth, local_state is the measurement made from the estimate;
+ *     lap_step and alive_ticks keep their meaning; lpvmpc_observer_read(path, ...) returns the estimate [B][6] and the latest
+ *     sensor reading [B][5] (on a race without an estimator it fails with LPVMPC_E_ARG).
+ * The estimator state belongs to the race: lpvmpc_cl_release(path) (or destroying any of the three handles) frees it, and a
+ * later lpvmpc_cl_init on `path` runs on ground truth. */
 typedef struct lpvmpc_race_config {
     int32_t laps;             /* NumberOfLaps: a vehicle finishes when its lap counter exceeds it (>= 1) */
     int32_t n_sub_lap0;       /* plant steps per lap-0 tick (7) */
@@ -438,6 +459,10 @@ typedef struct lpvmpc_race_config {
 void lpvmpc_race_default_config(lpvmpc_race_config *cfg);
 int  lpvmpc_race_init(lpvmpc_handle *path, lpvmpc_handle *tt, lpvmpc_handle *planner, int32_t B,
                       const double *plant0, const int32_t *half_track0, const lpvmpc_race_config *cfg);
+struct lpvmpc_observer_config;
+int  lpvmpc_race_init_observed(lpvmpc_handle *path, lpvmpc_handle *tt, lpvmpc_handle *planner, int32_t B,
+                               const double *plant0, const int32_t *half_track0, const lpvmpc_race_config *cfg,
+                               const struct lpvmpc_observer_config *obs);
 /* enqueue n_ticks ticks; no synchronisation */
 int  lpvmpc_race_tick(lpvmpc_handle *path, int32_t n_ticks);
 /* synchronises and copies (any pointer may be NULL): plant [B][8], local_state [B][6] (the last measurement), cmd [B][2],
@@ -519,7 +544,7 @@ void lpvmpc_observer_default_config(lpvmpc_observer_config *cfg);
  * [vx, vy, psiDot, x, y, yaw] of plant0 (GPS hold at the start position, step counter 0). */
 int lpvmpc_observer_setup(lpvmpc_handle *h, const lpvmpc_observer_config *cfg);
 
-/* The fleet's or cascade's estimator state (synchronises like lpvmpc_cl_read; either pointer may be NULL): est [B][6] the current estimate,
+/* The fleet's, cascade's or race's estimator state (synchronises like lpvmpc_cl_read; either pointer may be NULL): est [B][6] the current estimate,
  * meas [B][5] the measurement y of the latest observer step. */
 int lpvmpc_observer_read(lpvmpc_handle *h, double *est, double *meas);
 

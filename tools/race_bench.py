@@ -4,7 +4,10 @@
   inphase  every vehicle racing, one common event tick (cascade.npz's lap-0 start)   vs lpvmpc_cascade_tick, prefetch 0
   stagger  events spread over the last quarter of the lap (the engine's real case)   reported, not gated
 Prints ms per controller tick and alive vehicle-ticks per second; one line per (regime, B).
-Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--out FILE]"""
+--estimator: instead, the lap0 and inphase races run without and with the state estimator in the loop (lpvmpc_race_init_observed,
+the reference's gain tables, noisy sensors), alternated --reps times per (regime, B); one line per (regime, B) with the median of each
+and the added ms per controller tick.
+Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator [--reps R]] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -34,9 +37,9 @@ def timed(tick, read, K):
     return (time.perf_counter() - t0) * 1e3 / K
 
 
-def race_run(mp, plant0, half, warm, K):
+def race_run(mp, plant0, half, warm, K, estimator=None):
     path, tt, plan = engines(mp)
-    path.race_init(tt, plan, plant0, half_track0=half, laps=5, half_width=mp.halfWidth, slack=mp.slack)
+    path.race_init(tt, plan, plant0, half_track0=half, laps=5, half_width=mp.halfWidth, slack=mp.slack, estimator=estimator)
     path.race_tick(warm)
     a0 = path.race_laps()[1].sum()
     ms = timed(path.race_tick, path.race_read, K)
@@ -52,7 +55,11 @@ def main():
     ap.add_argument("--ticks", type=int, default=30)
     ap.add_argument("--sizes", default="1024,8192")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--estimator", action="store_true")
+    ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
+    if a.estimator:
+        return estimator_main(a)
     import lpvmpc
     from lpvmpc import workloads as W
     from tests._golden import load
@@ -102,6 +109,38 @@ def main():
     if a.out:
         with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")
+
+
+def estimator_main(a):
+    import lpvmpc
+    from lpvmpc.observer import observer_config
+    from tests._golden import load
+    f = np.load(os.path.join(ROOT, "tests", "golden", "estimator", "estimator.npz"))
+    obs = observer_config(f["L_ls"], f["lim_ls"], f["L_hs"], f["lim_hs"], psi_std=0.01, psiDot_std=0.05, x_std=0.01, y_std=0.01,
+                          v_std=0.02, seed=7)
+    mp = lpvmpc.Map("L_shape", 0.2)
+    c = load("cascade")
+    P = int(c["pre_ticks"])
+    lines = []
+    for B in [int(x) for x in a.sizes.split(",")]:
+        rng = np.random.default_rng(3)
+        grid = np.zeros((B, 8)); grid[:, 1] = rng.normal(0, 0.02, B); grid[:, 2] = rng.uniform(0.9, 1.1, B)
+        same = np.tile(c["pre_plant"][0], (B, 1))
+        for name, plant0, half, warm in (("lap0", grid, 0, 10), ("inphase", same, 1, P + 3)):
+            ms = {False: [], True: []}
+            ph = {}
+            for _ in range(a.reps):
+                for est in (False, True):
+                    m, _vps, ph[est] = race_run(mp, plant0, half, warm, a.ticks, obs if est else None)
+                    ms[est].append(m)
+            m0, m1 = float(np.median(ms[False])), float(np.median(ms[True]))
+            lines.append("%-8s B=%5d  race %.3f ms/tick (runs %s, phases %s)  with estimator %.3f ms/tick (runs %s, phases %s)  "
+                         "added %+.3f ms/tick" % (name, B, m0, " ".join("%.3f" % x for x in ms[False]), ph[False].tolist(), m1,
+                                                  " ".join("%.3f" % x for x in ms[True]), ph[True].tolist(), m1 - m0))
+            print(lines[-1], flush=True)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
 
 
 if __name__ == "__main__":
