@@ -77,6 +77,14 @@ class RaceConfig(C.Structure):
                 ("plan_max_ey", _d), ("dt_sim", _d), ("mu_sim", _d)]
 
 
+class ActuatorConfig(C.Structure):
+    """Mirror of ``struct lpvmpc_actuator_config`` (include/lpvmpc.h)."""
+    _fields_ = [("delay_a", _i), ("delay_df", _i), ("low_level_dyn", _i), ("reserved", _i), ("servo_tf", _d)]
+
+
+ACT_MAX_DELAY = 64                       # LPVMPC_ACT_MAX_DELAY
+ACT_WORDS = 2 * ACT_MAX_DELAY + 2        # LPVMPC_ACT_WORDS: [motor ring, servo ring, servo_inp, k] per vehicle
+
 OBSERVER_AUX = 30 + 36 + 12      # L_gain [6][5], A_obs [6][6], B_obs [6][2] per instance (lpvmpc_observer_step_batch)
 
 EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_destroy", "lpvmpc_last_error", "lpvmpc_last_error_code",
@@ -89,7 +97,9 @@ EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_d
            "lpvmpc_handoff_batch", "lpvmpc_cascade_init", "lpvmpc_cascade_tick", "lpvmpc_cascade_read", "lpvmpc_cascade_alive_ticks",
            "lpvmpc_observer_default_config", "lpvmpc_observer_setup", "lpvmpc_observer_read", "lpvmpc_observer_step_batch",
            "lpvmpc_solve_batch_masked", "lpvmpc_race_default_config", "lpvmpc_race_init", "lpvmpc_race_tick", "lpvmpc_race_read",
-           "lpvmpc_race_laps", "lpvmpc_race_predictions", "lpvmpc_race_init_observed")
+           "lpvmpc_race_laps", "lpvmpc_race_predictions", "lpvmpc_race_init_observed",
+           "lpvmpc_actuator_default_config", "lpvmpc_plant_step_actuated_batch", "lpvmpc_cl_init_actuated", "lpvmpc_race_init_actuated",
+           "lpvmpc_actuator_read")
 
 _lib = None
 
@@ -202,6 +212,17 @@ def load():
         lib.lpvmpc_race_init_observed.restype = C.c_int
     except AttributeError:
         pass
+    try:        # (nor the actuator model)
+        lib.lpvmpc_actuator_default_config.argtypes = [P(ActuatorConfig)]
+        lib.lpvmpc_actuator_default_config.restype = None
+        lib.lpvmpc_plant_step_actuated_batch.argtypes = [vp, _i, vp, vp, vp, _i, _d, _d, P(ActuatorConfig), vp, vp]
+        lib.lpvmpc_cl_init_actuated.argtypes = [vp, _i, vp, _d, _d, _i, _i, _d, _d, P(ActuatorConfig), vp, vp]
+        lib.lpvmpc_race_init_actuated.argtypes = [vp, vp, vp, _i, vp, vp, P(RaceConfig), P(ObserverConfig), P(ActuatorConfig), vp, vp]
+        lib.lpvmpc_actuator_read.argtypes = [vp, vp, vp, vp]
+        for name in ("lpvmpc_plant_step_actuated_batch", "lpvmpc_cl_init_actuated", "lpvmpc_race_init_actuated", "lpvmpc_actuator_read"):
+            getattr(lib, name).restype = C.c_int
+    except AttributeError:
+        pass
     for name in ("lpvmpc_handoff_length", "lpvmpc_handoff_operators", "lpvmpc_handoff_setup", "lpvmpc_handoff_batch",
                  "lpvmpc_cascade_init", "lpvmpc_cascade_tick", "lpvmpc_cascade_read"):
         getattr(lib, name).restype = C.c_int
@@ -230,6 +251,12 @@ def default_handoff_config():
 def default_race_config():
     cfg = RaceConfig()
     load().lpvmpc_race_default_config(C.byref(cfg))
+    return cfg
+
+
+def default_actuator_config():
+    cfg = ActuatorConfig()
+    load().lpvmpc_actuator_default_config(C.byref(cfg))
     return cfg
 
 

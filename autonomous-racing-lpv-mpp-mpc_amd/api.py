@@ -266,11 +266,50 @@ class BatchedSolver:
         self._chk(self._lib.lpvmpc_plant_step_batch(self._h, st.shape[0], ptr(st), ptr(u), int(n_sub), float(dt_sim), float(mu_sim)))
         return st
 
-    def cl_init(self, plant0, half_width, slack, q9_swap=True, n_sub=7, dt_sim=0.005, mu_sim=0.05):
+    def plant_step_actuated(self, state, act_state, u, n_sub=1, dt_sim=0.005, mu_sim=0.05, actuator=None, delay_a=None, delay_df=None):
+        """n_sub steps of Simulator.f through the actuator stage (vehicleSimulator.py:53-78) under the held command u [B,2] =
+        (motor, servo).  act_state [B, ACT_WORDS] (None: fresh, all zeros) carries the command ring, servo_inp and the step
+        counter between calls.  ``actuator``: an ``actuator.actuator_config`` result (None: all off); delay_a / delay_df [B]
+        per-vehicle delays in steps (None: the config's).  Returns (state, act_state)."""
+        st = f64(state).reshape(-1, 8).copy(); B = st.shape[0]
+        u = f64(u, (B, 2), "u")
+        act = np.zeros((B, _ffi.ACT_WORDS)) if act_state is None else f64(act_state, (B, _ffi.ACT_WORDS), "act_state").copy()
+        cfg = _ffi.default_actuator_config() if actuator is None else actuator
+        la, ld = _delay_array(delay_a, B, "delay_a"), _delay_array(delay_df, B, "delay_df")
+        self._chk(self._lib.lpvmpc_plant_step_actuated_batch(self._h, B, ptr(st), ptr(act), ptr(u), int(n_sub), float(dt_sim), float(mu_sim),
+                                                             C.byref(cfg), ptr(la), ptr(ld)))
+        return st, act
+
+    def cl_init(self, plant0, half_width, slack, q9_swap=True, n_sub=7, dt_sim=0.005, mu_sim=0.05, actuator=None, delay_a=None,
+                delay_df=None):
+        """Start a lap-0 fleet.  ``actuator`` (an ``actuator.actuator_config`` result, even an all-off one) selects
+        lpvmpc_cl_init_actuated: the actuator in the plant, controllers of any steering delay, per-vehicle delays delay_a /
+        delay_df [B] in steps (None: the config's).  Without it the call is lpvmpc_cl_init."""
         p0 = f64(plant0).reshape(-1, 8)
         self._cl_B = p0.shape[0]
-        self._chk(self._lib.lpvmpc_cl_init(self._h, self._cl_B, ptr(p0), float(half_width), float(slack), 1 if q9_swap else 0,
-                                           int(n_sub), float(dt_sim), float(mu_sim)))
+        if actuator is None:
+            if delay_a is not None or delay_df is not None:
+                raise ValueError("per-vehicle delays need an actuator config")
+            self._chk(self._lib.lpvmpc_cl_init(self._h, self._cl_B, ptr(p0), float(half_width), float(slack), 1 if q9_swap else 0,
+                                               int(n_sub), float(dt_sim), float(mu_sim)))
+        else:
+            la, ld = _delay_array(delay_a, self._cl_B, "delay_a"), _delay_array(delay_df, self._cl_B, "delay_df")
+            self._chk(self._lib.lpvmpc_cl_init_actuated(self._h, self._cl_B, ptr(p0), float(half_width), float(slack), 1 if q9_swap else 0,
+                                                        int(n_sub), float(dt_sim), float(mu_sim), C.byref(_actuator_cfg(actuator)),
+                                                        ptr(la), ptr(ld)))
+
+    def actuator_read(self):
+        """Of a fleet / race started with ``actuator``: act_state [B, ACT_WORDS] and the controllers' u_old histories [B, 2 + d] =
+        [OldSteering[0], OldAccelera[0], OldSteering[1..d]] ("path"; a race also "tt").  A lap-0 fleet's history is what its next
+        solve reads, a race's what its last solve read (include/lpvmpc.h)."""
+        race = getattr(self, "_race", None) is not None
+        B = self._race[0] if race else self._cl_B
+        d = int(self.cfg.steering_delay)
+        o = dict(act_state=np.empty((B, _ffi.ACT_WORDS)), path=np.empty((B, 2 + d)))
+        if race:
+            o["tt"] = np.empty((B, 2 + d))
+        self._chk(self._lib.lpvmpc_actuator_read(self._h, ptr(o["act_state"]), ptr(o["path"]), ptr(o.get("tt"))))
+        return o
 
     def cl_tick(self, n_ticks=1):
         self._chk(self._lib.lpvmpc_cl_tick(self._h, int(n_ticks)))
@@ -388,13 +427,14 @@ class BatchedSolver:
         return out
 
     # -- race engine: lap 0, per-vehicle lap events, racing (lpvmpc_race_*) ------------------------------------
-    def race_init(self, tt, planner, plant0, half_track0=None, estimator=None, **cfg):
+    def race_init(self, tt, planner, plant0, half_track0=None, estimator=None, actuator=None, delay_a=None, delay_df=None, **cfg):
         """Start a race owned by this PATH controller engine, with ``tt`` (racing tuning) and ``planner`` (handoff_setup done).
         plant0 [B,8]; half_track0 [B] (HalfTrack at the start, default 0); ``cfg``: fields of ``lpvmpc_race_config`` (laps,
         n_sub_lap0, n_sub, q9_swap, half_width, slack, plan_max_ey, dt_sim, mu_sim).  ``estimator``: an
         ``observer.observer_config`` result or an ``_ffi.ObserverConfig`` runs the race with the state estimator and the
         simulated sensors in the loop (lpvmpc_race_init_observed; ``observer_read`` then returns its state); None runs it on
-        ground truth."""
+        ground truth.  ``actuator`` (an ``actuator.actuator_config`` result, even an all-off one) selects lpvmpc_race_init_actuated:
+        the actuator in the plant, path / tt of the same steering delay, per-vehicle delays delay_a / delay_df [B] in steps."""
         p0 = f64(plant0).reshape(-1, 8)
         B = p0.shape[0]
         c = _ffi.default_race_config()
@@ -412,7 +452,16 @@ class BatchedSolver:
             else:
                 raise TypeError("unknown race option %r" % k)
         ht = None if half_track0 is None else np.ascontiguousarray(np.broadcast_to(np.asarray(half_track0), (B,)), np.int32)
-        if estimator is None:
+        if estimator is not None and not isinstance(estimator, _ffi.ObserverConfig):
+            raise TypeError("estimator must be an observer.observer_config(...) result or an _ffi.ObserverConfig")
+        if actuator is not None:
+            la, ld = _delay_array(delay_a, B, "delay_a"), _delay_array(delay_df, B, "delay_df")
+            self._chk(self._lib.lpvmpc_race_init_actuated(self._h, tt._h, planner._h, B, ptr(p0), ptr(ht), C.byref(c),
+                                                          None if estimator is None else C.byref(estimator), C.byref(_actuator_cfg(actuator)),
+                                                          ptr(la), ptr(ld)))
+        elif delay_a is not None or delay_df is not None:
+            raise ValueError("per-vehicle delays need an actuator config")
+        elif estimator is None:
             self._chk(self._lib.lpvmpc_race_init(self._h, tt._h, planner._h, B, ptr(p0), ptr(ht), C.byref(c)))
         else:
             if not isinstance(estimator, _ffi.ObserverConfig):
@@ -467,6 +516,24 @@ class BatchedSolver:
                                                    dp(u_old), dp(max_ey), float(cf_new), int(lap), dp(xPred),
                                                    dp(uPred), dp(status), dp(iters), dp(resid), dp(polish),
                                                    C.c_void_p(int(stream))))
+
+
+def _delay_array(v, B, name):
+    """Per-vehicle delays in simulator steps: None, or exactly B integers."""
+    if v is None:
+        return None
+    a = np.asarray(v)
+    if a.ndim != 1 or a.shape[0] != B:
+        raise ValueError("%s must have %d entries (one per vehicle), got shape %s" % (name, B, a.shape))
+    if not np.all(a == np.round(a)):
+        raise ValueError("%s must be integer steps" % name)
+    return np.ascontiguousarray(a, np.int32)
+
+
+def _actuator_cfg(a):
+    if not isinstance(a, _ffi.ActuatorConfig):
+        raise TypeError("actuator must be an actuator.actuator_config(...) result or an _ffi.ActuatorConfig")
+    return a
 
 
 def handoff_operators(N, dt, cfg=None):
@@ -762,9 +829,13 @@ class RaceFleet(object):
     driven ``laps`` racing laps.  Three engines with the reference's tunings (CTRL_TUNINGS["path"], CTRL_TUNINGS["race"], the
     PLAN_* weights).  ``options``: race options of ``BatchedSolver.race_init`` (n_sub_lap0, n_sub, q9_swap, plan_max_ey, dt_sim,
     mu_sim) and engine settings (e.g. kernel_variant) applied to all three engines.  ``estimator``: an
-    ``observer.observer_config(...)`` result runs the race with the state estimator and the simulated sensors in the loop."""
+    ``observer.observer_config(...)`` result runs the race with the state estimator and the simulated sensors in the loop.
+    ``actuator``: an ``actuator.actuator_config(...)`` result puts the actuator delays / servo lag in the plant (per-vehicle
+    delay_a / delay_df in steps); ``steering_delay``: both controllers' steeringDelay (needs ``actuator``, e.g.
+    actuator.controller_delay(delay_df_s))."""
 
-    def __init__(self, track_map, plant0, laps=1, N=20, Np=40, half_track0=None, device=0, estimator=None, **options):
+    def __init__(self, track_map, plant0, laps=1, N=20, Np=40, half_track0=None, device=0, estimator=None, actuator=None,
+                 steering_delay=0, delay_a=None, delay_df=None, **options):
         from .workloads import CTRL_TUNINGS, PLAN_L, PLAN_Q, PLAN_R, PLAN_dR
         race_keys = ("n_sub_lap0", "n_sub", "q9_swap", "plan_max_ey", "dt_sim", "mu_sim")
         race_opts = {k: v for k, v in options.items() if k in race_keys}
@@ -772,8 +843,9 @@ class RaceFleet(object):
         Qp, Rp, dRp = CTRL_TUNINGS["path"]; Qr, Rr, dRr = CTRL_TUNINGS["race"]
         tab = track_map.PointAndTangent
         self.map = track_map
-        self.path = BatchedSolver("controller", N, 1.0 / 30.0, Qp, Rp, dRp, track=tab, device=device)
-        self.tt = BatchedSolver("controller", N, 1.0 / 30.0, Qr, Rr, dRr, track=tab, device=device)
+        sd = {"steering_delay": int(steering_delay)} if steering_delay else {}
+        self.path = BatchedSolver("controller", N, 1.0 / 30.0, Qp, Rp, dRp, track=tab, device=device, **sd)
+        self.tt = BatchedSolver("controller", N, 1.0 / 30.0, Qr, Rr, dRr, track=tab, device=device, **sd)
         self.planner = BatchedSolver("planner", Np, 0.05, PLAN_Q, PLAN_R, PLAN_dR, L_cf=PLAN_L, track=tab, device=device)
         for e in (self.path, self.tt, self.planner):
             for k, v in engine_opts.items():
@@ -781,7 +853,8 @@ class RaceFleet(object):
         self.planner.handoff_setup()
         self.dt_sim = float(race_opts.get("dt_sim", 0.005))
         self.path.race_init(self.tt, self.planner, plant0, half_track0=half_track0, laps=laps, half_width=track_map.halfWidth,
-                            slack=track_map.slack, estimator=estimator, **race_opts)
+                            slack=track_map.slack, estimator=estimator, actuator=actuator, delay_a=delay_a, delay_df=delay_df,
+                            **race_opts)
 
     def run(self, n_ticks):
         """Enqueue n_ticks controller ticks (no synchronisation)."""
@@ -794,6 +867,10 @@ class RaceFleet(object):
         """The estimator's state of a race started with ``estimator``: estimate [B,6] = [vx vy psiDot x y yaw] and the latest
         sensor reading [B,5] = [vx psiDot x y yaw]."""
         return self.path.observer_read()
+
+    def actuator(self):
+        """Of a race started with ``actuator``: act_state and the path / tt controllers' u_old histories (BatchedSolver.actuator_read)."""
+        return self.path.actuator_read()
 
     def lap_times(self):
         """[B, laps+1] simulated seconds of lap 0, 1, ..., laps (NaN where the lap has not been completed)."""

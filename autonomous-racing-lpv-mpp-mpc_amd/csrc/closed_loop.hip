@@ -86,6 +86,7 @@ __global__ void __launch_bounds__(64) cl_command_plant_kernel(int B, int N, cons
     for (int i = 0; i < 8; ++i) plant[(size_t)b * 8 + i] = st[i];
 }
 
+// (delayed copy: cl_command_plant_measure_act_kernel in actuator.hip -- change both)
 // the same followed by the NEXT tick's measurement (cl_measure_kernel on the state just advanced): one launch less per
 // control tick; the measurement goes to its own buffer, the previous tick's local state stays readable
 __global__ void __launch_bounds__(64) cl_command_plant_measure_kernel(const DevCfg *__restrict__ cp, int B, int N, const double *__restrict__ uPred,

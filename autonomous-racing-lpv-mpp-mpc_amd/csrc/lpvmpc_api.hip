@@ -164,6 +164,7 @@ extern "C" lpvmpc_handle *lpvmpc_create(const lpvmpc_config *cfg) {
     h->d_xPred = h->d_uPred = h->d_resid = h->d_xlast = h->d_delta = nullptr;
     h->d_status = h->d_iters = h->d_polish = nullptr; h->d_state = nullptr; h->d_scal = nullptr; h->warm_mode = 0; h->state_valid_B = 0;
     h->cl_plant = h->cl_local = h->cl_cmd = nullptr; h->cl_local_next = nullptr; h->cl_next_valid = 0; h->cl_B = 0; h->cl_first_it = 1; h->cl_q9 = 1; h->cl_ticks = 0;
+    h->cl_actuated = 0; h->cl_act = lpvmpc::ActDev{};
     h->d_Wop = h->d_FWop = nullptr; h->ho_M = 0; h->cascade = nullptr; h->cascade_owner = nullptr; h->cascade_prefetch = 1;
     h->race = nullptr; h->race_owner = nullptr; h->d_active = nullptr; h->solve_mask = nullptr;
     h->defer_after = 0; h->defer_budget = 200; h->defer_cap = 0; h->defer_cur_cap = 0; h->defer_stride = 0; h->rv_count = 0;
@@ -213,6 +214,7 @@ extern "C" void lpvmpc_destroy(lpvmpc_handle *h) {
     if (h->cl_local_next) (void)hipFree(h->cl_local_next);
     if (h->cl_local) (void)hipFree(h->cl_local);
     if (h->cl_cmd) (void)hipFree(h->cl_cmd);
+    lpvmpc_act_free(h->cl_act);
     if (h->cascade) lpvmpc_cascade_free(h);                                  // (frees the cascade's estimator state)
     if (h->race) lpvmpc_race_free(h);
     if (h->race_owner && h->race_owner->race) lpvmpc_race_free(h->race_owner);   // a handle the race of another one drives: end that race
@@ -728,20 +730,27 @@ extern "C" int lpvmpc_cl_release(lpvmpc_handle *h) {
     if (h->race) lpvmpc_race_free(h);
     if (h->cl_plant) { (void)hipFree(h->cl_plant); (void)hipFree(h->cl_local); (void)hipFree(h->cl_cmd); (void)hipFree(h->cl_local_next); h->cl_plant = h->cl_local = h->cl_cmd = h->cl_local_next = nullptr; }
     if (h->obs_state) { (void)hipFree(h->obs_state); h->obs_state = nullptr; }
+    lpvmpc_act_free(h->cl_act); h->cl_actuated = 0;
     h->cl_B = 0; h->cl_ticks = 0; h->cl_first_it = 1; h->cl_next_valid = 0;
     return LPVMPC_OK;
 }
 
-extern "C" int lpvmpc_cl_init(lpvmpc_handle *h, int32_t B, const double *plant0, double half_width, double slack, int32_t q9_swap,
-                              int32_t n_sub, double dt_sim, double mu_sim) {
+// act == nullptr: lpvmpc_cl_init (refuses delayed controllers); else lpvmpc_cl_init_actuated (any steering_delay, actuator in the plant)
+static int cl_init(lpvmpc_handle *h, int32_t B, const double *plant0, double half_width, double slack, int32_t q9_swap,
+                   int32_t n_sub, double dt_sim, double mu_sim, const lpvmpc_actuator_config *act, const int32_t *delay_a, const int32_t *delay_df) {
     int rc = lpvmpc_check_common(h, B, "lpvmpc_cl_init"); if (rc) return rc;
     if (h->cfg.kind != LPVMPC_KIND_CONTROLLER) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: controller handles only");
     if (h->race || h->race_owner) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: this handle takes part in a race (lpvmpc_cl_release on its path handle ends it)");
     if (h->cfg.N > 20) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: the reference's seed trajectories have 20 rows (N <= 20)");
-    if (h->cfg.steering_delay != 0) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: the fleet engines run the reference's steeringDelay = 0 (CMAIN:49)");
+    if (h->cfg.steering_delay != 0 && !act)
+        return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: the fleet engines run the reference's steeringDelay = 0 (CMAIN:49); lpvmpc_cl_init_actuated runs delayed controllers");
     if (!plant0 || n_sub < 1 || !(dt_sim > 0)) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: bad argument");
     rc = lpvmpc_need_track(h, "lpvmpc_cl_init"); if (rc) return rc;
+    lpvmpc::ActDev a{};
+    if (act) { rc = lpvmpc_act_alloc(h, B, act, delay_a, delay_df, dt_sim, "lpvmpc_cl_init_actuated", a); if (rc) { lpvmpc_act_free(a); return rc; } }
     if (h->cl_plant) { (void)hipFree(h->cl_plant); (void)hipFree(h->cl_local); (void)hipFree(h->cl_cmd); (void)hipFree(h->cl_local_next); h->cl_plant = h->cl_local = h->cl_cmd = h->cl_local_next = nullptr; }
+    lpvmpc_act_free(h->cl_act);
+    h->cl_act = a; h->cl_actuated = act != nullptr;
     h->cl_next_valid = 0;
     HIP_TRY(h, hipMalloc((void **)&h->cl_local_next, (size_t)B * 6 * 8));
     HIP_TRY(h, hipMalloc((void **)&h->cl_plant, (size_t)B * 8 * 8));
@@ -758,7 +767,23 @@ extern "C" int lpvmpc_cl_init(lpvmpc_handle *h, int32_t B, const double *plant0,
     h->state_valid_B = 0;
     if (h->obs_state) { (void)hipFree(h->obs_state); h->obs_state = nullptr; }
     if (h->obs_cfg) { rc = lpvmpc_observer_start(h, *h->obs_cfg, B, plant0, dt_sim, 0); if (rc) return rc; }   // the estimator in the loop
+    if (act) {                                                   // the controller's OldSteering / OldAccelera start at zero (CTRL:71-73)
+        HIP_TRY(h, hipMemsetAsync(h->d_uold, 0, (size_t)B * (2 + h->cfg.steering_delay) * 8, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
     return LPVMPC_OK;
+}
+
+extern "C" int lpvmpc_cl_init(lpvmpc_handle *h, int32_t B, const double *plant0, double half_width, double slack, int32_t q9_swap,
+                              int32_t n_sub, double dt_sim, double mu_sim) {
+    return cl_init(h, B, plant0, half_width, slack, q9_swap, n_sub, dt_sim, mu_sim, nullptr, nullptr, nullptr);
+}
+
+extern "C" int lpvmpc_cl_init_actuated(lpvmpc_handle *h, int32_t B, const double *plant0, double half_width, double slack, int32_t q9_swap,
+                                       int32_t n_sub, double dt_sim, double mu_sim, const lpvmpc_actuator_config *act,
+                                       const int32_t *delay_a, const int32_t *delay_df) {
+    if (!act) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init_actuated: actuator config is NULL");
+    return cl_init(h, B, plant0, half_width, slack, q9_swap, n_sub, dt_sim, mu_sim, act, delay_a, delay_df);
 }
 
 extern "C" int lpvmpc_cl_tick(lpvmpc_handle *h, int32_t n_ticks) {
@@ -769,6 +794,10 @@ extern "C" int lpvmpc_cl_tick(lpvmpc_handle *h, int32_t n_ticks) {
     for (int t = 0; t < n_ticks; ++t) {
         // the measurement of this tick: made by the launch that advanced the plant at the end of the previous tick, or here
         if (h->cl_next_valid) { double *t_ = h->cl_local; h->cl_local = h->cl_local_next; h->cl_local_next = t_; }
+        else if (h->cl_actuated && h->obs_state) HIP_TRY(h, lpvmpc::launch_cl_observe_measure_act(h->d_cfg, B, h->obs_state, h->cl_cmd, h->cl_hw, h->cl_slack,
+                                                                                                 h->cl_q9, h->cl_local, h->d_uold, h->cfg.steering_delay, st));
+        else if (h->cl_actuated) HIP_TRY(h, lpvmpc::launch_cl_measure_act(h->d_cfg, B, h->cl_plant, h->cl_cmd, h->cl_hw, h->cl_slack, h->cl_q9, h->cl_local,
+                                                                          h->d_uold, h->cfg.steering_delay, st));
         else if (h->obs_state) HIP_TRY(h, lpvmpc::launch_cl_observe_measure(h->d_cfg, B, h->obs_state, h->cl_cmd, h->cl_hw, h->cl_slack, h->cl_q9,
                                                                            h->cl_local, h->d_uold, st));
         else HIP_TRY(h, lpvmpc::launch_cl_measure(h->d_cfg, B, h->cl_plant, h->cl_cmd, h->cl_hw, h->cl_slack, h->cl_q9, h->cl_local, h->d_uold, st));
@@ -785,7 +814,14 @@ extern "C" int lpvmpc_cl_tick(lpvmpc_handle *h, int32_t n_ticks) {
                     h->warm_mode ? h->d_state : nullptr, (h->warm_mode && h->state_valid_B == B) ? h->warm_mode : 0, x0_stride};
         int rc = lpvmpc_launch_solve_timed(h, a, st); if (rc) return rc;
         if (h->warm_mode) h->state_valid_B = B;
-        if (h->obs_state)
+        if (h->cl_actuated && h->obs_state)
+            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_act(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_pc, h->cl_hw, h->cl_slack,
+                                                                    h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay, h->obs_gains,
+                                                                    h->obs_state, h->obs_p, h->cl_act, st));
+        else if (h->cl_actuated)
+            HIP_TRY(h, lpvmpc::launch_cl_command_plant_measure_act(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_pc, h->cl_hw, h->cl_slack,
+                                                                    h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay, h->cl_act, st));
+        else if (h->obs_state)
             HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_pc, h->cl_hw, h->cl_slack,
                                                                 h->cl_q9, h->cl_local_next, h->d_uold, h->obs_gains, h->obs_state, h->obs_p, st));
         else

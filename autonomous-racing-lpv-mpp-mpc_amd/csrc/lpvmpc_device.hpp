@@ -116,6 +116,27 @@ hipError_t launch_cl_command_plant(int B, int N, const double *uPred, double *cm
 hipError_t launch_cl_command_plant_measure(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant, PlantCfg pc,
                                            double hw, double slack, int q9_swap, double *local_next, double *u_old, hipStream_t s);
 
+// actuator stage of the simulator (actuator.hip; vehicleSimulator.py:53-78; lpvmpc_*_actuated, include/lpvmpc.h "Actuator delay and servo lag"):
+// per vehicle a ring of its last kActRing commands in global memory (a runtime-indexed per-lane array would live in scratch), the
+// servo state and the vehicle's own plant-step counter, which keys the ring
+constexpr int kActRing = 64;                 // = LPVMPC_ACT_MAX_DELAY: step k reads slot (k - L) % kActRing before overwriting slot k % kActRing
+struct ActDev {
+    double *ring;                            // [2][kActRing][B]: channel 0 motor, 1 servo; slot k % kActRing holds the command of plant step k
+    double *servo;                           // [B] servo_inp of the low-level servo model
+    int32_t *k;                              // [B] plant steps the vehicle has taken
+    const int32_t *La, *Ld;                  // [B] motor / steering delay in plant steps, 0 .. kActRing
+    int B, lld;                              // lld: lowLevelDyn
+    double c, c1;                            // T / Tf and 1 - T / Tf
+};
+hipError_t launch_plant_actuated(int B, double *plant, const double *u_a_delta, PlantCfg pc, const ActDev &a, hipStream_t s);
+// the delayed forms of the lap-0 fleet's kernels: the plant steps through the actuator stage, u_old [B][2 + sd] is the controller's
+// OldSteering / OldAccelera history (append the last command, drop the oldest entry, CMAIN:289-298) instead of the last command
+hipError_t launch_cl_measure_act(const DevCfg *dcfg, int B, const double *plant, const double *cmd, double half_width, double slack,
+                                 int q9_swap, double *local_state, double *u_old, int sd, hipStream_t s);
+hipError_t launch_cl_command_plant_measure_act(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant, PlantCfg pc,
+                                               double hw, double slack, int q9_swap, double *local_next, double *u_old, int sd,
+                                               const ActDev &a, hipStream_t s);
+
 
 // gain-scheduled LPV estimator and simulated sensors (observer.hip)
 constexpr int kObsTable = 6 * 5 * 16;   // one Llmi table [6][5][16]
@@ -135,6 +156,11 @@ hipError_t launch_cascade_plant_observe(int B, int N, const double *uPred, doubl
 hipError_t launch_cl_command_plant_observe(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant, PlantCfg pc,
                                           double hw, double slack, int q9_swap, double *local_next, double *u_old, const double *gains,
                                           double *obs, const ObsParams &op, hipStream_t s);
+hipError_t launch_cl_observe_measure_act(const DevCfg *dcfg, int B, const double *obs, const double *cmd, double hw, double slack, int q9_swap,
+                                         double *local_state, double *u_old, int sd, hipStream_t s);
+hipError_t launch_cl_command_plant_observe_act(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant, PlantCfg pc,
+                                              double hw, double slack, int q9_swap, double *local_next, double *u_old, int sd,
+                                              const double *gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s);
 
 
 // planner -> controller hand-off and trajectory-tracking measurement (handoff.hip)
@@ -176,5 +202,10 @@ hipError_t launch_race_measure(const DevCfg *ccfg, const RaceDev &r, int seed_ti
 hipError_t launch_race_command_plant(const RaceDev &r, PlantCfg pc, hipStream_t s);
 hipError_t launch_race_command_plant_observe(const RaceDev &r, PlantCfg pc, const double *gains, double *obs, const ObsParams &op,
                                             hipStream_t s);
+// the delayed forms (lpvmpc_race_init_actuated): u_old histories of path and TT (steering delay sd), actuator stage in the plant
+hipError_t launch_race_measure_act(const DevCfg *ccfg, const RaceDev &r, int seed_tick, int sd, hipStream_t s);
+hipError_t launch_race_command_plant_act(const RaceDev &r, PlantCfg pc, const ActDev &a, hipStream_t s);
+hipError_t launch_race_command_plant_observe_act(const RaceDev &r, PlantCfg pc, const double *gains, double *obs, const ObsParams &op,
+                                                const ActDev &a, hipStream_t s);
 
 }  // namespace lpvmpc

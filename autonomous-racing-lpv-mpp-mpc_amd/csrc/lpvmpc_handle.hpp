@@ -39,6 +39,8 @@ struct lpvmpc_handle {
     int cl_B, cl_first_it, cl_q9, cl_ticks;
     double cl_hw, cl_slack;
     lpvmpc::PlantCfg cl_pc;
+    int cl_actuated;                    // the fleet was started by lpvmpc_cl_init_actuated: delayed kernels, actuator state cl_act
+    lpvmpc::ActDev cl_act;
     int32_t *d_status, *d_iters, *d_polish;
     hipStream_t stream;
     std::vector<hipEvent_t> ev0, ev1;   // ring of event pairs around the solve-kernel launches
@@ -108,6 +110,12 @@ LPVMPC_HIDDEN void lpvmpc_cascade_free(lpvmpc_handle *h);
 LPVMPC_HIDDEN void lpvmpc_race_free(lpvmpc_handle *h);                                  // race_api.hip
 LPVMPC_HIDDEN int lpvmpc_observer_start(lpvmpc_handle *h, const lpvmpc_observer_config &o, int B, const double *plant0, double dt_sim,
                                         int from_plant);                                // lpvmpc_api.hip
+// actuator_api.hip: checks cfg / per-vehicle delays and allocates a zeroed actuator state for B vehicles (a.ring == null: none)
+LPVMPC_HIDDEN int lpvmpc_act_alloc(lpvmpc_handle *h, int B, const lpvmpc_actuator_config *cfg, const int32_t *delay_a, const int32_t *delay_df,
+                                   double dt_sim, const char *who, lpvmpc::ActDev &a);
+LPVMPC_HIDDEN void lpvmpc_act_free(lpvmpc::ActDev &a);
+LPVMPC_HIDDEN int lpvmpc_act_download(lpvmpc_handle *h, const lpvmpc::ActDev &a, double *act_state, hipStream_t st);   // device -> host layout
+LPVMPC_HIDDEN int lpvmpc_race_act_read(lpvmpc_handle *h, double *act_state, double *path_hist, double *tt_hist);        // race_api.hip
 LPVMPC_HIDDEN int lpvmpc_observer_check(lpvmpc_handle *h, const lpvmpc_observer_config *c, const char *who);   // lpvmpc_api.hip
 namespace lpvmpc {
 // handoff.hip (host): interpolation operator W and interpolation + filtfilt operator FW, both [M][N] row-major

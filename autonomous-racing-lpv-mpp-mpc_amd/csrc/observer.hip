@@ -48,6 +48,7 @@ __device__ inline void obs_local_state(const DevCfg &c, double hw, double slack,
     ls[3] = q9_swap ? ey : epsi; ls[4] = s; ls[5] = q9_swap ? epsi : ey;
 }
 
+// (delayed copy of modes 0 / 1: cl_command_plant_observe_act_kernel in actuator.hip -- change both)
 // cl_command_plant_measure_kernel with the estimator in the loop: per plant step, plant -> sensors -> observer; the next tick's
 // measurement is made from the estimate.  mode 0: only the measurement of the current estimate with u_old = cmd (the first
 // tick of a fleet; one kernel keeps local_position at a single call site, inlined).  mode 2 (the cascade): advance, then write the

@@ -57,6 +57,8 @@ __global__ void __launch_bounds__(64) race_plan_start_kernel(const DevCfg *__res
     r.m_pfirst[b] = first; r.m_pcont[b] = cont; r.m_plan[b] = first | cont;
 }
 
+// Copied in actuator.hip as race_measure_act_kernel (the delayed race), which differs only in the u_old write: change both
+// (tests/test_actuator_kernel_copies.py compares them).
 // measurement (from r.meas), lap logic and this tick's controller masks.  c is the controllers' configuration (path and TT share
 // N, dt, track).  A vehicle entering the tick with a non-finite plant or measurement source is lost.
 // seed_tick: the race's first 9 ticks (first_it < 10, CMAIN:310-320) solve the path controller on the seed trajectories.
@@ -121,7 +123,8 @@ __global__ void __launch_bounds__(64) race_measure_kernel(const DevCfg *__restri
     r.nstep[b] = ph == 0 ? r.n_sub_lap0 : r.n_sub[k % 3];
 }
 
-// last launch of a tick: the solve's report, the command of the vehicle's controller and its simulator steps
+// last launch of a tick: the solve's report, the command of the vehicle's controller and its simulator steps.  This kernel
+// and race_command_plant_observe_kernel have delayed copies in actuator.hip (the plant steps through act_stage): change both
 __global__ void __launch_bounds__(64) race_command_plant_kernel(RaceDev r, PlantCfg pc) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= r.B) return;

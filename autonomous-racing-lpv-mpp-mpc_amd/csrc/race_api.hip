@@ -14,6 +14,9 @@ struct lpvmpc_race {
     lpvmpc::RaceDev d;            // device pointers and constants (kernel argument)
     int ticks;
     lpvmpc::PlantCfg pc;
+    bool actuated;                // lpvmpc_race_init_actuated: delayed kernels, actuator state act, controller histories of steering delay sd
+    lpvmpc::ActDev act;
+    int sd;
 };
 
 void lpvmpc_race_free(lpvmpc_handle *h) {
@@ -31,6 +34,7 @@ void lpvmpc_race_free(lpvmpc_handle *h) {
         if (h->obs_gains) (void)hipFree(h->obs_gains);
         h->obs_state = h->obs_gains = nullptr; h->obs_B = 0; h->obs_p = lpvmpc::ObsParams{};
     }
+    lpvmpc_act_free(r->act);
     if (r->tt && r->tt->race_owner == h) r->tt->race_owner = nullptr;
     if (r->plan && r->plan->race_owner == h) r->plan->race_owner = nullptr;
     delete r;
@@ -50,7 +54,8 @@ extern "C" void lpvmpc_race_default_config(lpvmpc_race_config *c) {
 static bool busy(const lpvmpc_handle *x) { return x->cl_plant || x->cascade || x->cascade_owner || x->race || x->race_owner; }
 
 static int race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, int32_t B, const double *plant0, const int32_t *half_track0,
-                     const lpvmpc_race_config *cfg, const lpvmpc_observer_config *obs, bool observed_call) {
+                     const lpvmpc_race_config *cfg, const lpvmpc_observer_config *obs, bool observed_call,
+                     const lpvmpc_actuator_config *act = nullptr, const int32_t *delay_a = nullptr, const int32_t *delay_df = nullptr) {
     if (!h) return fail(nullptr, LPVMPC_E_ARG, "lpvmpc_race_init: path handle is NULL");
     if (!tt || !plan || !plant0 || !cfg || B <= 0) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: NULL argument or B <= 0");
     if (h->cfg.kind != LPVMPC_KIND_CONTROLLER || tt->cfg.kind != LPVMPC_KIND_CONTROLLER || plan->cfg.kind != LPVMPC_KIND_PLANNER || h == tt)
@@ -61,8 +66,10 @@ static int race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, i
         std::memcmp(h->cfg.track, tt->cfg.track, sizeof(double) * 6 * h->cfg.track_rows) != 0)
         return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: path and tt handles differ in N, dt or track");
     if (h->cfg.N > 20) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: the reference's seed trajectories have 20 rows (N <= 20)");
-    if (h->cfg.steering_delay != 0 || tt->cfg.steering_delay != 0)
-        return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: the fleet engines run the reference's steeringDelay = 0 (CMAIN:49)");
+    if ((h->cfg.steering_delay != 0 || tt->cfg.steering_delay != 0) && !act)
+        return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: the fleet engines run the reference's steeringDelay = 0 (CMAIN:49); lpvmpc_race_init_actuated runs delayed controllers");
+    if (act && h->cfg.steering_delay != tt->cfg.steering_delay)
+        return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init_actuated: path and tt handles differ in steeringDelay (%d, %d)", h->cfg.steering_delay, tt->cfg.steering_delay);
     if (!plan->d_Wop) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: call lpvmpc_handoff_setup on the planner handle first");
     if (plan->ho_M < h->cfg.N) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: the planner message (%d samples) is shorter than the controller horizon", plan->ho_M);
     if (h->warm_mode || tt->warm_mode || plan->warm_mode) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: warm_start must be 0 on all three handles");
@@ -79,11 +86,14 @@ static int race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, i
     rc = lpvmpc_check_common(h, B, "lpvmpc_race_init"); if (rc) return rc;
     rc = lpvmpc_check_common(tt, B, "lpvmpc_race_init(tt)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
     rc = lpvmpc_check_common(plan, B, "lpvmpc_race_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
+    lpvmpc::ActDev a{};
+    if (act) { rc = lpvmpc_act_alloc(h, B, act, delay_a, delay_df, cfg->dt_sim, "lpvmpc_race_init_actuated", a); if (rc) { lpvmpc_act_free(a); return rc; } }
     lpvmpc_race *r = new (std::nothrow) lpvmpc_race();
-    if (!r) return fail(h, LPVMPC_E_NOMEM, "out of host memory");
+    if (!r) { lpvmpc_act_free(a); return fail(h, LPVMPC_E_NOMEM, "out of host memory"); }
     std::memset(&r->d, 0, sizeof(r->d));
     h->race = r; tt->race_owner = h; plan->race_owner = h;
     r->tt = tt; r->plan = plan; r->ticks = 0;
+    r->actuated = act != nullptr; r->act = a; r->sd = h->cfg.steering_delay;
     r->pc = lpvmpc_plant_cfg(h, 1, cfg->dt_sim, cfg->mu_sim);
     lpvmpc::RaceDev &d = r->d;
     const size_t b = B, N = h->cfg.N, Np = plan->cfg.N, M = plan->ho_M;
@@ -120,7 +130,8 @@ static int race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, i
     HIP_TRY(h, hipMemsetAsync(d.SSp, 0, b * (Np + 1) * 8, st));
     HIP_TRY(h, hipMemsetAsync(d.pose, 0, b * 3 * 8, st));
     // the handles' carried rows: commands and predictions start at zero, lap-0 references vel_ref = ones (CMAIN:311,326)
-    HIP_TRY(h, hipMemsetAsync(h->d_uold, 0, b * 2 * 8, st)); HIP_TRY(h, hipMemsetAsync(tt->d_uold, 0, b * 2 * 8, st));
+    const size_t nu = 2 + r->sd;                                                           // u_old [B][2 + steering_delay]
+    HIP_TRY(h, hipMemsetAsync(h->d_uold, 0, b * nu * 8, st)); HIP_TRY(h, hipMemsetAsync(tt->d_uold, 0, b * nu * 8, st));
     HIP_TRY(h, hipMemsetAsync(h->d_uPred, 0, b * N * 2 * 8, st)); HIP_TRY(h, hipMemsetAsync(tt->d_uPred, 0, b * N * 2 * 8, st));
     HIP_TRY(h, hipMemsetAsync(plan->d_uPred, 0, b * Np * 2 * 8, st));
     HIP_TRY(h, hipMemsetAsync(tt->d_curv, 0, b * (N + 1) * 8, st));
@@ -146,6 +157,27 @@ static int race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, i
 extern "C" int lpvmpc_race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, int32_t B, const double *plant0,
                                 const int32_t *half_track0, const lpvmpc_race_config *cfg) {
     return race_init(h, tt, plan, B, plant0, half_track0, cfg, nullptr, false);
+}
+
+extern "C" int lpvmpc_race_init_actuated(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, int32_t B, const double *plant0,
+                                         const int32_t *half_track0, const lpvmpc_race_config *cfg, const lpvmpc_observer_config *obs,
+                                         const lpvmpc_actuator_config *act, const int32_t *delay_a, const int32_t *delay_df) {
+    if (!act) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init_actuated: actuator config is NULL");
+    return race_init(h, tt, plan, B, plant0, half_track0, cfg, obs, true, act, delay_a, delay_df);
+}
+
+// the race's actuator state and its two controllers' histories (lpvmpc_actuator_read)
+int lpvmpc_race_act_read(lpvmpc_handle *h, double *act_state, double *path_hist, double *tt_hist) {
+    lpvmpc_race *r = h->race;
+    if (!r->actuated) return fail(h, LPVMPC_E_ARG, "lpvmpc_actuator_read: the race was not started by lpvmpc_race_init_actuated");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = h->stream;
+    const size_t n = (size_t)r->d.B * (2 + r->sd) * 8;
+    if (path_hist) D2H(path_hist, r->d.p_uold, n);
+    if (tt_hist) D2H(tt_hist, r->d.t_uold, n);
+    if (act_state) { int rc = lpvmpc_act_download(h, r->act, act_state, st); if (rc) return rc; }
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return LPVMPC_OK;
 }
 
 extern "C" int lpvmpc_race_init_observed(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, int32_t B, const double *plant0,
@@ -176,7 +208,8 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
         HIP_TRY(h, lpvmpc::launch_resample(B, d.Np, d.M, p->d_Wop, p->d_FWop, d.sig, d.refs, st, d.m_plan));
         // measurement, lap logic, masks of the two controllers
         const int seed = r->ticks < 9;
-        HIP_TRY(h, lpvmpc::launch_race_measure(h->d_cfg, d, seed, st));
+        if (r->actuated) HIP_TRY(h, lpvmpc::launch_race_measure_act(h->d_cfg, d, seed, r->sd, st));
+        else HIP_TRY(h, lpvmpc::launch_race_measure(h->d_cfg, d, seed, st));
         // path controller (CMAIN:310-336)
         const double *x0 = d.local; int x0_stride = 6;
         if (seed) {                                                          // scratch only: unmasked
@@ -196,7 +229,9 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
                      tt->d_resid, nullptr, 0, 6};
         ta.active = d.m_tt;
         rc = lpvmpc_launch_solve_timed(tt, ta, st); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
-        if (d.estv) HIP_TRY(h, lpvmpc::launch_race_command_plant_observe(d, r->pc, h->obs_gains, h->obs_state, h->obs_p, st));
+        if (r->actuated && d.estv) HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_act(d, r->pc, h->obs_gains, h->obs_state, h->obs_p, r->act, st));
+        else if (r->actuated) HIP_TRY(h, lpvmpc::launch_race_command_plant_act(d, r->pc, r->act, st));
+        else if (d.estv) HIP_TRY(h, lpvmpc::launch_race_command_plant_observe(d, r->pc, h->obs_gains, h->obs_state, h->obs_p, st));
         else HIP_TRY(h, lpvmpc::launch_race_command_plant(d, r->pc, st));
         r->ticks++;
     }

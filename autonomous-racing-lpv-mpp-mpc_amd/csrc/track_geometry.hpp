@@ -36,7 +36,7 @@ __device__ inline double compute_angle(double p1x, double p1y, double ox, double
 __device__ inline double norm2(double x, double y) { return sqrt(x * x + y * y); }
 
 // Map.getLocalPosition: (x, y, psi) -> (s, ey, epsi, inside); 10000 sentinels when off the track (TRACK:376-379)
-__device__ inline void local_position(const DevCfg &c, double hw, double slack, double x, double y, double psi,
+__device__ __forceinline__ void local_position(const DevCfg &c, double hw, double slack, double x, double y, double psi,
                                       double &s, double &ey, double &epsi, int &inside) {
     const double *T = c.track;
     const int rows = c.track_rows;
@@ -129,9 +129,35 @@ __device__ inline void plant_step(const PlantCfg &p, double st[8], double ua, do
     st[7] = w + p.dt * (1.0 / p.Iz * (p.lf * FyF * cos(ud) - p.lr * FyR));
 }
 
+// Actuator stage of one simulator step (vehicleSimulator.py:67-76) for vehicle b at its plant step kk: the command (motor, servo)
+// enters the two FIFOs and the plant receives the entries La / Ld steps old -- 0 while kk < L, the FIFOs start filled with zeros;
+// L = 0 is the command itself.  With lowLevelDyn the servo filter sv runs on the delayed steering and is what the plant receives.
+// The slot of step kk - L is read before step kk's command overwrites it, so L = kActRing needs no extra slot.
+__device__ inline void act_stage(const ActDev &a, int b, int kk, int La, int Ld, double motor, double servo, double &sv, double &ua, double &ud) {
+    constexpr int m = kActRing - 1;
+    double *ra = a.ring + b, *rd = a.ring + (size_t)kActRing * a.B + b;
+    ua = La == 0 ? motor : (kk >= La ? ra[(size_t)((kk - La) & m) * a.B] : 0.0);
+    ud = Ld == 0 ? servo : (kk >= Ld ? rd[(size_t)((kk - Ld) & m) * a.B] : 0.0);
+    ra[(size_t)(kk & m) * a.B] = motor;
+    rd[(size_t)(kk & m) * a.B] = servo;
+    if (a.lld) { sv = a.c1 * sv + a.c * ud; ud = sv; }        // (1 - T/Tf) * servo_inp + (T/Tf) * df_his.pop(0)
+}
+
+// CMAIN:289-298 for a controller with steeringDelay sd: OldSteering (1 + sd entries) and OldAccelera (1 entry) append the last
+// command and drop their oldest entry.  u [2 + sd] = [OldSteering[0], OldAccelera[0], OldSteering[1 .. sd]] (include/lpvmpc.h, u_old);
+// sd = 0 leaves u = [servo, motor], the write of the fleets without a steering delay
+__device__ inline void uold_push(double *u, int sd, double servo, double motor) {
+    if (sd > 0) {
+        u[0] = u[2];
+        for (int j = 2; j < 1 + sd; ++j) u[j] = u[j + 1];
+        u[1 + sd] = servo;
+    } else u[0] = servo;
+    u[1] = motor;
+}
+
 // ---- per-vehicle measurement recipes shared by the fleet engines (closed_loop.hip, handoff.hip, race.hip) ----
 // lap-0 measurement (CMAIN:183-188): local state from the plant's ground truth, vx clamped at 0.01; q9_swap = SURVEY quirk Q9
-__device__ inline void cl_local(const DevCfg &c, double hw, double slack, int q9_swap, const double *p, double *ls) {
+__device__ __forceinline__ void cl_local(const DevCfg &c, double hw, double slack, int q9_swap, const double *p, double *ls) {
     double s, ey, epsi; int inside;
     local_position(c, hw, slack, p[0], p[1], p[6], s, ey, epsi, inside);
     ls[0] = p[2] < 0.01 ? 0.01 : p[2]; ls[1] = p[3]; ls[2] = p[7];
@@ -140,7 +166,7 @@ __device__ inline void cl_local(const DevCfg &c, double hw, double slack, int q9
 
 // LapNumber >= 1 measurement (CMAIN:198-248): yaw unwound by the lap counter, Body_Frame_Errors against the first sample of
 // the reference window (ref0 = x, y, yaw; cv0 = its curvature), s dead-reckoned from SS
-__device__ inline void tt_local(const DevCfg &c, const double *p, int lap, const double *ref0, double cv0, double SS, double *ls) {
+__device__ __forceinline__ void tt_local(const DevCfg &c, const double *p, int lap, const double *ref0, double cv0, double SS, double *ls) {
     const double vx = p[2] < 0.01 ? 0.01 : p[2], vy = p[3];
     const double psi = wrap_pi(p[6] - 2 * kPi * lap);
     const double xd = ref0[0], yd = ref0[1], psid = ref0[2];

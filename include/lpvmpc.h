@@ -425,7 +425,7 @@ int lpvmpc_cascade_alive_ticks(lpvmpc_handle *ctrl, int32_t *alive_ticks);
  * Kernel launches that only write per-tick scratch run unmasked (the seed-tick ABC linearisation of `path`); every launch
  * that writes carried state -- LPV roll-outs, solves, hand-off -- is masked to this tick's vehicles (SolveArgs::active).
  * Refused with LPVMPC_E_ARG: handles on different devices or of the wrong kinds, path / tt with different N, dt or track,
- * N > 20 (the seed rows), steering_delay != 0, a planner without lpvmpc_handoff_setup or with a message shorter than N,
+ * N > 20 (the seed rows), steering_delay != 0 (lpvmpc_race_init_actuated runs delayed controllers), a planner without lpvmpc_handoff_setup or with a message shorter than N,
  * warm_start != 0 on any of the three, an estimator on `path`, a handle already running a fleet, cascade or race.
  * The race belongs to `path`: lpvmpc_cl_release(path) (or destroying any of the three) ends it; while it runs, batch calls
  * on all three handles fail.  plant0 [B][8] = {x y vx vy ax ay yaw psiDot}; half_track0 [B] or NULL (= 0).
@@ -553,6 +553,69 @@ int lpvmpc_observer_read(lpvmpc_handle *h, double *est, double *meas);
  * A_obs [6][6] and B_obs [6][2] of the step.  Refused while the handle runs a fleet, like the other batch calls. */
 int lpvmpc_observer_step_batch(lpvmpc_handle *h, int32_t B, const lpvmpc_observer_config *cfg, double *est, const double *y,
                                const double *u, const int32_t *k, double *aux);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Actuator delay and servo lag (vehicleSimulator.py = SIM, main loop SIM:53-78) in the device plant, and fleets whose
+ * controllers carry a steering delay.  All entry points here are new; the calls above keep their behaviour and refusals.
+ *
+ * Per vehicle and simulator step k (the vehicle's own plant-step counter; dt = dt_sim) the plant receives
+ *   a     = motor command of step k - La   (0 while k < La)                  La = delay_a  (a_his, SIM:53)
+ *   delta = servo command of step k - Ld   (0 while k < Ld)                  Ld = delay_df (df_his, SIM:54)
+ * with La / Ld in simulator steps, 0 .. LPVMPC_ACT_MAX_DELAY; the reference's configuration is in seconds and its FIFO
+ * length is int(delay / dt), truncation included (int(0.145 / 0.005) = 28): the Python helper actuator_config converts.
+ * With low_level_dyn the servo filter runs on the DELAYED steering and is what the plant receives (SIM:70-72):
+ *   servo_inp = (1 - dt / servo_tf) * servo_inp + (dt / servo_tf) * delta,   servo_inp = 0 at the start, servo_tf = 0.07.
+ * The estimator, where it runs, is fed the COMMANDED input (it subscribes to `ecu`, stateEstimator.py:785); its own delays
+ * stay 0 (stateEstimator.py:42-43).  Frozen (finished, lost) race vehicles advance neither plant nor actuator.
+ *
+ * Actuator state of one vehicle, host layout of lpvmpc_plant_step_actuated_batch / lpvmpc_actuator_read:
+ *   act_state [B][LPVMPC_ACT_WORDS] = [motor ring (64), servo ring (64), servo_inp, k]: ring slot k % 64 holds the command of
+ *   plant step k (the last 64 commands), k is the number of plant steps taken (an exact integer).  A fresh state is all zeros.
+ *
+ * Controllers with steeringDelay d = 1 .. 8 (lpvmpc_config.steering_delay) in a fleet: each controller keeps its history
+ * u_old [B][2 + d] = [OldSteering[0], OldAccelera[0], OldSteering[1 .. d]] (CTRL:71-73, 395, 523), zeros at the start.  On each
+ * tick, before its solve, the controller of the vehicle's lap appends the last command and drops the oldest entry
+ * (CMAIN:289-298: `path` on lap 0, `tt` from the lap-event tick on).  Quirk kept: on the event tick `tt`'s history has only
+ * been updated once, so it is [0, .., 0, last servo] -- its dR term and its first d - 1 pinned steerings read zeros.  With d = 0
+ * the history is the last command, as in the calls above.  The reference pairs the two delays as
+ * Steering_Delay = int(delay_df / dt) (CMAIN:52; dt = 1/30): the Python helper controller_delay.
+ *
+ * Per-vehicle delays: delay_a / delay_df are arrays of B entries or NULL (NULL: cfg's value for every vehicle).
+ * Refused with LPVMPC_E_ARG: a delay < 0 or > LPVMPC_ACT_MAX_DELAY, servo_tf <= 0 with low_level_dyn, a race whose path and
+ * tt handles have different steering delays.  lpvmpc_cascade_init keeps refusing delayed controllers (not extended here).
+ * With cfg all off (no delays, no servo lag) and steering_delay 0 the new calls compute what the calls above compute, word
+ * for word (they run the delayed kernels, whose actuator stage then passes the command through). */
+#define LPVMPC_ACT_MAX_DELAY 64
+#define LPVMPC_ACT_WORDS (2 * LPVMPC_ACT_MAX_DELAY + 2)
+typedef struct lpvmpc_actuator_config {
+    int32_t delay_a, delay_df;   /* simulator steps (0) */
+    int32_t low_level_dyn;       /* 1: servo filter on the delayed steering (0) */
+    int32_t reserved;            /* 0 */
+    double  servo_tf;            /* filter time constant Tf, seconds (0.07, SIM:62) */
+} lpvmpc_actuator_config;
+void lpvmpc_actuator_default_config(lpvmpc_actuator_config *cfg);
+/* n_sub simulator steps of B vehicles through the actuator stage under the held command u [B][2] = (motor, servo):
+ * state [B][8] and act_state [B][LPVMPC_ACT_WORDS] are in / out, so a trace split over several calls equals one call.
+ * A batch call like lpvmpc_plant_step_batch (refused while the handle runs a fleet). */
+int  lpvmpc_plant_step_actuated_batch(lpvmpc_handle *h, int32_t B, double *state, double *act_state, const double *u,
+                                      int32_t n_sub, double dt_sim, double mu_sim, const lpvmpc_actuator_config *cfg,
+                                      const int32_t *delay_a, const int32_t *delay_df);
+/* lpvmpc_cl_init with the actuator in the plant (dt = dt_sim) and a controller of any steering_delay (0 .. 8); an estimator
+ * attached with lpvmpc_observer_setup runs as in lpvmpc_cl_init, fed the commanded input. */
+int  lpvmpc_cl_init_actuated(lpvmpc_handle *h, int32_t B, const double *plant0, double half_width, double slack, int32_t q9_swap,
+                             int32_t n_sub, double dt_sim, double mu_sim, const lpvmpc_actuator_config *act,
+                             const int32_t *delay_a, const int32_t *delay_df);
+/* lpvmpc_race_init / lpvmpc_race_init_observed (obs NULL: ground truth) with the actuator in the plant and path / tt handles
+ * of the same steering_delay (0 .. 8). */
+int  lpvmpc_race_init_actuated(lpvmpc_handle *path, lpvmpc_handle *tt, lpvmpc_handle *planner, int32_t B,
+                               const double *plant0, const int32_t *half_track0, const lpvmpc_race_config *cfg,
+                               const struct lpvmpc_observer_config *obs, const lpvmpc_actuator_config *act,
+                               const int32_t *delay_a, const int32_t *delay_df);
+/* of a fleet or race started by the two calls above (synchronises; any pointer may be NULL): act_state [B][LPVMPC_ACT_WORDS];
+ * path_hist [B][2 + d]: the u_old history of the fleet's controller -- the lap-0 fleet makes the history step in the launch that
+ * advances the plant, so this is what its NEXT solve reads -- or of the race's `path`, whose history steps in the next tick's
+ * measurement, so this is what its LAST solve read; tt_hist [B][2 + d]: the race's `tt`, likewise (NULL for a fleet). */
+int  lpvmpc_actuator_read(lpvmpc_handle *h, double *act_state, double *path_hist, double *tt_hist);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,8 @@ from .api import (BatchedSolver, LPV_MPC_Planner, PathFollowingLPV_MPC, PlannerH
 from ._ffi import LpvMpcError, STATUS_TEXT  # noqa: E402,F401
 from .observer import GainScheduledLPVObserver, observer_config, observer_vertex_gains  # noqa: E402,F401
 from .track import Map  # noqa: E402,F401
+from .actuator import actuator_config, controller_delay, delay_steps  # noqa: E402,F401
 
 __all__ = ["BatchedSolver", "PathFollowingLPV_MPC", "LPV_MPC_Planner", "PlannerHandoff", "body_frame_errors", "handoff_operators",
-           "Map", "LpvMpcError", "STATUS_TEXT", "GainScheduledLPVObserver", "observer_config", "observer_vertex_gains", "RaceFleet"]
+           "Map", "LpvMpcError", "STATUS_TEXT", "GainScheduledLPVObserver", "observer_config", "observer_vertex_gains", "RaceFleet",
+           "actuator_config", "controller_delay", "delay_steps"]

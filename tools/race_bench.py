@@ -7,7 +7,10 @@ Prints ms per controller tick and alive vehicle-ticks per second; one line per (
 --estimator: instead, the lap0 and inphase races run without and with the state estimator in the loop (lpvmpc_race_init_observed,
 the reference's gain tables, noisy sensors), alternated --reps times per (regime, B); one line per (regime, B) with the median of each
 and the added ms per controller tick.
-Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator [--reps R]] [--out FILE]"""
+--actuator: instead, the lap0 and inphase races run on the old entry (lpvmpc_race_init), on lpvmpc_race_init_actuated with the actuator
+all off, with plant delays La = Ld = 20 steps and the servo lag (steeringDelay 0), and the same with steeringDelay 3 on both
+controllers; alternated --reps times per (regime, B), medians and differences against the old entry.
+Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator | --actuator [--reps R]] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -18,12 +21,13 @@ sys.path.insert(0, ROOT)
 import numpy as np
 
 
-def engines(mp):
+def engines(mp, sd=0):
     import lpvmpc
     from lpvmpc import workloads as W
     Qp, Rp, dRp = W.CTRL_TUNINGS["path"]; Qr, Rr, dRr = W.CTRL_TUNINGS["race"]
-    path = lpvmpc.BatchedSolver("controller", 20, 1 / 30.0, Qp, Rp, dRp, track=mp.PointAndTangent)
-    tt = lpvmpc.BatchedSolver("controller", 20, 1 / 30.0, Qr, Rr, dRr, track=mp.PointAndTangent)
+    kw = {"steering_delay": sd} if sd else {}
+    path = lpvmpc.BatchedSolver("controller", 20, 1 / 30.0, Qp, Rp, dRp, track=mp.PointAndTangent, **kw)
+    tt = lpvmpc.BatchedSolver("controller", 20, 1 / 30.0, Qr, Rr, dRr, track=mp.PointAndTangent, **kw)
     plan = lpvmpc.BatchedSolver("planner", 40, 0.05, W.PLAN_Q, W.PLAN_R, W.PLAN_dR, L_cf=W.PLAN_L, track=mp.PointAndTangent)
     plan.handoff_setup()
     return path, tt, plan
@@ -37,9 +41,10 @@ def timed(tick, read, K):
     return (time.perf_counter() - t0) * 1e3 / K
 
 
-def race_run(mp, plant0, half, warm, K, estimator=None):
-    path, tt, plan = engines(mp)
-    path.race_init(tt, plan, plant0, half_track0=half, laps=5, half_width=mp.halfWidth, slack=mp.slack, estimator=estimator)
+def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0):
+    path, tt, plan = engines(mp, sd)
+    path.race_init(tt, plan, plant0, half_track0=half, laps=5, half_width=mp.halfWidth, slack=mp.slack, estimator=estimator,
+                   actuator=actuator)
     path.race_tick(warm)
     a0 = path.race_laps()[1].sum()
     ms = timed(path.race_tick, path.race_read, K)
@@ -57,9 +62,12 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--estimator", action="store_true")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--actuator", action="store_true")
     a = ap.parse_args()
     if a.estimator:
         return estimator_main(a)
+    if a.actuator:
+        return actuator_main(a)
     import lpvmpc
     from lpvmpc import workloads as W
     from tests._golden import load
@@ -141,6 +149,45 @@ def estimator_main(a):
     if a.out:
         with open(a.out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
+
+
+def actuator_main(a):
+    import lpvmpc
+    from tests._golden import load
+    mp = lpvmpc.Map("L_shape", 0.2)
+    c = load("cascade")
+    P = int(c["pre_ticks"])
+    cfgs = (("old", None, 0), ("all-off", lpvmpc.actuator_config(), 0),
+            ("La=Ld=20+servo", _act20(), 0), ("La=Ld=20+servo,sd=3", _act20(), 3))
+    lines = []
+    for B in [int(x) for x in a.sizes.split(",")]:
+        rng = np.random.default_rng(3)
+        grid = np.zeros((B, 8)); grid[:, 1] = rng.normal(0, 0.02, B); grid[:, 2] = rng.uniform(0.9, 1.1, B)
+        same = np.tile(c["pre_plant"][0], (B, 1))
+        for name, plant0, half, warm in (("lap0", grid, 0, 10), ("inphase", same, 1, P + 3)):
+            ms = {k: [] for k, _, _ in cfgs}
+            ph = {}
+            for _ in range(a.reps):
+                for k, act, sd in cfgs:
+                    m, _vps, ph[k] = race_run(mp, plant0, half, warm, a.ticks, actuator=act, sd=sd)
+                    ms[k].append(m)
+            m0 = float(np.median(ms["old"]))
+            for k, _, _ in cfgs:
+                m = float(np.median(ms[k]))
+                lines.append("%-8s B=%5d  %-20s %.3f ms/tick (runs %s, phases %s)  vs old %+.3f ms/tick"
+                             % (name, B, k, m, " ".join("%.3f" % x for x in ms[k]), ph[k].tolist(), m - m0))
+                print(lines[-1], flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+def _act20():
+    import lpvmpc
+    cfg = lpvmpc.actuator_config(low_level_dyn=True)
+    cfg.delay_a = cfg.delay_df = 20
+    return cfg
+
 
 
 if __name__ == "__main__":
