@@ -1,6 +1,7 @@
 // actuator_api.hip -- C ABI of the actuator model (include/lpvmpc.h, "Actuator delay and servo lag"): the stand-alone batch call,
 // the configuration and the read-back of a delayed fleet's or race's actuator state and controller histories.  The fleet entry
-// points themselves are lpvmpc_cl_init_actuated (lpvmpc_api.hip) and lpvmpc_race_init_actuated (race_api.hip).  Kernels: actuator.hip.
+// points themselves are lpvmpc_cl_init_actuated (lpvmpc_api.hip) and lpvmpc_race_init_actuated (race_api.hip).  Kernels: the <true>
+// forms of fleet_kernels.hpp, launched from actuator.hip.
 #include <cstring>
 #include <vector>
 

@@ -8,8 +8,11 @@
 //   Map.getGlobalPosition               Utilities/trackInitialization.py:205-262
 //   lap-0 measurement / command glue    controllerMain.py:179-190, 289-298, 381-386
 //   predicted_vectors_generation        controllerMain.py:510-553 (seed trajectories of the first 9 ticks)
+//
+// The kernels that advance the plant or write u_old are in fleet_kernels.hpp (this file launches their plain forms).
 #include "lpvmpc_device.hpp"
 #include "track_geometry.hpp"
+#include "fleet_kernels.hpp"
 
 namespace lpvmpc {
 
@@ -29,32 +32,6 @@ __global__ void __launch_bounds__(64) global_position_kernel(const DevCfg *__res
     global_position(*cp, in[b * 2 + 0], in[b * 2 + 1], x, y, th);
     out[b * 3 + 0] = x; out[b * 3 + 1] = y; out[b * 3 + 2] = th;
 }
-__global__ void __launch_bounds__(64) plant_kernel(int B, double *__restrict__ plant, const double *__restrict__ u, PlantCfg pc) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    double st[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) st[i] = plant[(size_t)b * 8 + i];
-    const double ua = u[b * 2 + 0], ud = u[b * 2 + 1];
-    for (int k = 0; k < pc.n_sub; ++k) plant_step(pc, st, ua, ud);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) plant[(size_t)b * 8 + i] = st[i];
-}
-
-// lap-0 measurement: GlobalState = [vx vy psiDot x y psi] from the plant (ground truth), vx clamped at 0.01
-// (CMAIN:183-184), local coordinates from the map.  q9_swap reproduces CMAIN:188, which stores the returned
-// (s, ey, epsi) as LocalState[4], LocalState[3], LocalState[5], i.e. ey lands in the epsi slot and vice versa
-// (SURVEY quirk Q9); with q9_swap = 0 the slots are filled as the state definition says.
-// u_old = last command [servo, motor] (CMAIN:289-298 leaves exactly that in OldSteering[0] / OldAccelera[0]).
-__global__ void __launch_bounds__(64) cl_measure_kernel(const DevCfg *__restrict__ cp, int B, const double *__restrict__ plant,
-                                                        const double *__restrict__ cmd, double hw, double slack, int q9_swap,
-                                                        double *__restrict__ local_state, double *__restrict__ u_old) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    cl_local(*cp, hw, slack, q9_swap, plant + (size_t)b * 8, local_state + (size_t)b * 6);
-    u_old[b * 2 + 0] = cmd[b * 2 + 0]; u_old[b * 2 + 1] = cmd[b * 2 + 1];
-}
-
 // predicted_vectors_generation (CMAIN:510-553): 20 fixed rows built on the local state; delta seeds are zero
 __constant__ double kSeedDvx[20] = {0.05, 0.2, 0.4, 0.6, 0.7, 0.8, 0.9, 0.9, 0.9, 0.9, 0.9, 0.9, 0.9, 0.9, 0.9, 0.9, 0.9, 0.9, 0.9, 0.9};
 __constant__ double kSeedDs[20] = {0, 0.01, 0.02, 0.04, 0.07, 0.1, 0.14, 0.18, 0.23, 0.55, 0.66, 0.77, 0.89, 1.00, 1.19, 1.39, 1.59, 1.79, 1.89, 1.999};
@@ -86,31 +63,6 @@ __global__ void __launch_bounds__(64) cl_command_plant_kernel(int B, int N, cons
     for (int i = 0; i < 8; ++i) plant[(size_t)b * 8 + i] = st[i];
 }
 
-// (delayed copy: cl_command_plant_measure_act_kernel in actuator.hip -- change both)
-// the same followed by the NEXT tick's measurement (cl_measure_kernel on the state just advanced): one launch less per
-// control tick; the measurement goes to its own buffer, the previous tick's local state stays readable
-__global__ void __launch_bounds__(64) cl_command_plant_measure_kernel(const DevCfg *__restrict__ cp, int B, int N, const double *__restrict__ uPred,
-                                                                      double *__restrict__ cmd, double *__restrict__ plant, PlantCfg pc,
-                                                                      double hw, double slack, int q9_swap, double *__restrict__ local_next,
-                                                                      double *__restrict__ u_old) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const double servo = uPred[(size_t)b * N * 2 + 0], motor = uPred[(size_t)b * N * 2 + 1];
-    cmd[b * 2 + 0] = servo; cmd[b * 2 + 1] = motor;
-    double st[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) st[i] = plant[(size_t)b * 8 + i];
-    for (int k = 0; k < pc.n_sub; ++k) plant_step(pc, st, motor, servo);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) plant[(size_t)b * 8 + i] = st[i];
-    double s, ey, epsi; int inside;
-    local_position(*cp, hw, slack, st[0], st[1], st[6], s, ey, epsi, inside);
-    double *ls = local_next + (size_t)b * 6;
-    ls[0] = st[2] < 0.01 ? 0.01 : st[2]; ls[1] = st[3]; ls[2] = st[7];
-    ls[3] = q9_swap ? ey : epsi; ls[4] = s; ls[5] = q9_swap ? epsi : ey;
-    u_old[b * 2 + 0] = servo; u_old[b * 2 + 1] = motor;
-}
-
 #define LPVMPC_GRID(n) dim3(((n) + 63) / 64), dim3(64)
 hipError_t launch_local_position(const DevCfg *dcfg, int B, const double *xypsi, double hw, double slack, double *out, hipStream_t s) {
     hipLaunchKernelGGL(local_position_kernel, LPVMPC_GRID(B), 0, s, dcfg, B, xypsi, hw, slack, out);
@@ -121,12 +73,12 @@ hipError_t launch_global_position(const DevCfg *dcfg, int B, const double *sey, 
     return hipGetLastError();
 }
 hipError_t launch_plant(int B, double *plant, const double *u, PlantCfg pc, hipStream_t s) {
-    hipLaunchKernelGGL(plant_kernel, LPVMPC_GRID(B), 0, s, B, plant, u, pc);
+    hipLaunchKernelGGL(plant_kernel<false>, LPVMPC_GRID(B), 0, s, B, plant, u, pc, ActDev{});
     return hipGetLastError();
 }
 hipError_t launch_cl_measure(const DevCfg *dcfg, int B, const double *plant, const double *cmd, double hw, double slack, int q9_swap,
                              double *local_state, double *u_old, hipStream_t s) {
-    hipLaunchKernelGGL(cl_measure_kernel, LPVMPC_GRID(B), 0, s, dcfg, B, plant, cmd, hw, slack, q9_swap, local_state, u_old);
+    hipLaunchKernelGGL(cl_measure_kernel<false>, LPVMPC_GRID(B), 0, s, dcfg, B, plant, cmd, hw, slack, q9_swap, local_state, u_old, 0);
     return hipGetLastError();
 }
 hipError_t launch_cl_seed(int B, int N, const double *local_state, double *xlast, double *delta, hipStream_t s) {
@@ -140,7 +92,8 @@ hipError_t launch_cl_command_plant(int B, int N, const double *uPred, double *cm
 
 hipError_t launch_cl_command_plant_measure(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant, PlantCfg pc,
                                            double hw, double slack, int q9_swap, double *local_next, double *u_old, hipStream_t s) {
-    hipLaunchKernelGGL(cl_command_plant_measure_kernel, LPVMPC_GRID(B), 0, s, dcfg, B, N, uPred, cmd, plant, pc, hw, slack, q9_swap, local_next, u_old);
+    hipLaunchKernelGGL(cl_command_plant_measure_kernel<false>, LPVMPC_GRID(B), 0, s, dcfg, B, N, uPred, cmd, plant, pc, hw, slack, q9_swap, local_next,
+                       u_old, 0, ActDev{});
     return hipGetLastError();
 }
 

@@ -116,7 +116,7 @@ hipError_t launch_cl_command_plant(int B, int N, const double *uPred, double *cm
 hipError_t launch_cl_command_plant_measure(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant, PlantCfg pc,
                                            double hw, double slack, int q9_swap, double *local_next, double *u_old, hipStream_t s);
 
-// actuator stage of the simulator (actuator.hip; vehicleSimulator.py:53-78; lpvmpc_*_actuated, include/lpvmpc.h "Actuator delay and servo lag"):
+// actuator stage of the simulator (fleet_kernels.hpp, actuator.hip; vehicleSimulator.py:53-78; lpvmpc_*_actuated, include/lpvmpc.h "Actuator delay and servo lag"):
 // per vehicle a ring of its last kActRing commands in global memory (a runtime-indexed per-lane array would live in scratch), the
 // servo state and the vehicle's own plant-step counter, which keys the ring
 constexpr int kActRing = 64;                 // = LPVMPC_ACT_MAX_DELAY: step k reads slot (k - L) % kActRing before overwriting slot k % kActRing

@@ -1,9 +1,10 @@
 // observer_device.hpp -- device functions of the gain-scheduled LPV state estimator and its simulated sensors, shared by
-// observer.hip (the fleet's and the cascade's kernels) and race.hip (the race's): the noise generator, one observer step,
-// sensors + one observer step after a plant step, and the LDS staging of the gain words.  Both objects are compiled with
-// -ffp-contract=off, so every includer computes the same words.
+// observer.hip, race.hip and the estimator kernels of fleet_kernels.hpp: the noise generator, one observer step, sensors + one
+// observer step after a plant step, the LDS staging of the gain words and the controller's measurement from the estimate.  Every
+// includer is compiled with -ffp-contract=off, so every includer computes the same words.
 #pragma once
 #include "lpvmpc_device.hpp"
+#include "track_geometry.hpp"
 
 namespace lpvmpc {
 
@@ -131,6 +132,15 @@ __device__ inline void obs_substep(const double *G, const ObsParams &p, long lon
 __device__ inline void obs_stage_gains(double *lds, const double *__restrict__ g) {
     for (int i = threadIdx.x; i < kObsGainWords; i += blockDim.x) lds[i] = g[i];
     __syncthreads();
+}
+
+// controller measurement from the estimate (the estimator path's cl_measure_kernel): [max(vx, 0.01), vy, psiDot] and the map's
+// local frame of (x, y, yaw) with quirk Q9 as in cl_local
+__device__ inline void obs_local_state(const DevCfg &c, double hw, double slack, int q9_swap, const double *e, double *ls) {
+    double s, ey, epsi; int inside;
+    local_position(c, hw, slack, e[3], e[4], e[5], s, ey, epsi, inside);
+    ls[0] = e[0] < 0.01 ? 0.01 : e[0]; ls[1] = e[1]; ls[2] = e[2];
+    ls[3] = q9_swap ? ey : epsi; ls[4] = s; ls[5] = q9_swap ? epsi : ey;
 }
 
 }  // namespace lpvmpc

@@ -155,6 +155,13 @@ __device__ inline void uold_push(double *u, int sd, double servo, double motor) 
     u[1] = motor;
 }
 
+// a plant state (or the estimate view in its layout) whose 8 words are finite
+__device__ inline bool plant_finite(const double *p) {
+    bool fin = true;
+    for (int i = 0; i < 8; ++i) fin = fin && __builtin_isfinite(p[i]);
+    return fin;
+}
+
 // ---- per-vehicle measurement recipes shared by the fleet engines (closed_loop.hip, handoff.hip, race.hip) ----
 // lap-0 measurement (CMAIN:183-188): local state from the plant's ground truth, vx clamped at 0.01; q9_swap = SURVEY quirk Q9
 __device__ __forceinline__ void cl_local(const DevCfg &c, double hw, double slack, int q9_swap, const double *p, double *ls) {
