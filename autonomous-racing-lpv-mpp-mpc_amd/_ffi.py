@@ -82,6 +82,39 @@ class ActuatorConfig(C.Structure):
     _fields_ = [("delay_a", _i), ("delay_df", _i), ("low_level_dyn", _i), ("reserved", _i), ("servo_tf", _d)]
 
 
+class RaceRecordConfig(C.Structure):
+    """Mirror of ``struct lpvmpc_race_record_config`` (include/lpvmpc.h)."""
+    _fields_ = [("capacity", _i), ("stride", _i)]
+
+
+# race recorder channels (LPVMPC_REC_*): f64 [REC_F64][B] and i32 [REC_I32][B] per record, named in channel order
+REC_F64, REC_I32 = 29, 8
+REC_PLANT, REC_LOCAL, REC_CMD, REC_REF, REC_TRACK, REC_EST = 0, 8, 14, 16, 20, 23
+REC_PHASE, REC_LAP, REC_SRC, REC_ITERS, REC_STATUS, REC_PLAN_ITERS, REC_PLAN_STATUS, REC_INSIDE = range(8)
+REC_F64_NAMES = ("x", "y", "vx", "vy", "ax", "ay", "yaw", "psiDot",
+                 "local_vx", "local_vy", "local_w", "local_epsi", "local_s", "local_ey",
+                 "servo", "motor", "x_ref", "y_ref", "yaw_ref", "vel_ref", "track_s", "track_ey", "track_epsi",
+                 "est_vx", "est_vy", "est_psiDot", "est_x", "est_y", "est_yaw")
+REC_I32_NAMES = ("phase", "lap", "src", "iters", "status", "plan_iters", "plan_status", "inside")
+# per-lap statistics (LPVMPC_LAPSTAT_*): [B][laps + 1][K]
+LAPSTAT_F64, LAPSTAT_I32 = 6, 9
+LAPSTAT_SSE_V, LAPSTAT_SSE_EY, LAPSTAT_SSE_EPSI, LAPSTAT_MAX_EY, LAPSTAT_SUM_VX, LAPSTAT_MAX_EY_TRACK = range(6)
+(LAPSTAT_TICKS, LAPSTAT_CTRL_ITERS, LAPSTAT_CTRL_ITERS_MAX, LAPSTAT_CTRL_NOT_SOLVED, LAPSTAT_PLAN_TICKS, LAPSTAT_PLAN_ITERS,
+ LAPSTAT_PLAN_ITERS_MAX, LAPSTAT_PLAN_NOT_SOLVED, LAPSTAT_OFF_TRACK) = range(9)
+LAPSTAT_F64_NAMES = ("sse_v", "sse_ey", "sse_epsi", "max_ey", "sum_vx", "max_ey_track")
+LAPSTAT_I32_NAMES = ("ticks", "ctrl_iters", "ctrl_iters_max", "ctrl_not_solved", "plan_ticks", "plan_iters", "plan_iters_max",
+                     "plan_not_solved", "off_track")
+
+
+def lap_stats_dict(f, i, end_tick):
+    """Per-lap statistics planes f [B, laps+1, LAPSTAT_F64], i [B, laps+1, LAPSTAT_I32] -> dict of named [B, laps+1] arrays, the
+    planes themselves (f64, i32) and end_tick [B]."""
+    out = {k: f[:, :, c] for c, k in enumerate(LAPSTAT_F64_NAMES)}
+    out.update({k: i[:, :, c] for c, k in enumerate(LAPSTAT_I32_NAMES)})
+    out.update(f64=f, i32=i, end_tick=end_tick)
+    return out
+
+
 ACT_MAX_DELAY = 64                       # LPVMPC_ACT_MAX_DELAY
 ACT_WORDS = 2 * ACT_MAX_DELAY + 2        # LPVMPC_ACT_WORDS: [motor ring, servo ring, servo_inp, k] per vehicle
 
@@ -99,7 +132,7 @@ EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_d
            "lpvmpc_solve_batch_masked", "lpvmpc_race_default_config", "lpvmpc_race_init", "lpvmpc_race_tick", "lpvmpc_race_read",
            "lpvmpc_race_laps", "lpvmpc_race_predictions", "lpvmpc_race_init_observed",
            "lpvmpc_actuator_default_config", "lpvmpc_plant_step_actuated_batch", "lpvmpc_cl_init_actuated", "lpvmpc_race_init_actuated",
-           "lpvmpc_actuator_read")
+           "lpvmpc_actuator_read", "lpvmpc_race_record", "lpvmpc_race_record_read", "lpvmpc_race_lap_stats")
 
 _lib = None
 
@@ -220,6 +253,14 @@ def load():
         lib.lpvmpc_race_init_actuated.argtypes = [vp, vp, vp, _i, vp, vp, P(RaceConfig), P(ObserverConfig), P(ActuatorConfig), vp, vp]
         lib.lpvmpc_actuator_read.argtypes = [vp, vp, vp, vp]
         for name in ("lpvmpc_plant_step_actuated_batch", "lpvmpc_cl_init_actuated", "lpvmpc_race_init_actuated", "lpvmpc_actuator_read"):
+            getattr(lib, name).restype = C.c_int
+    except AttributeError:
+        pass
+    try:        # (nor the race recorder)
+        lib.lpvmpc_race_record.argtypes = [vp, P(RaceRecordConfig)]
+        lib.lpvmpc_race_record_read.argtypes = [vp, _i, vp, vp, vp, vp]
+        lib.lpvmpc_race_lap_stats.argtypes = [vp, vp, vp, vp]
+        for name in ("lpvmpc_race_record", "lpvmpc_race_record_read", "lpvmpc_race_lap_stats"):
             getattr(lib, name).restype = C.c_int
     except AttributeError:
         pass

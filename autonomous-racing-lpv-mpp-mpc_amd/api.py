@@ -102,6 +102,7 @@ class BatchedSolver:
         self._ho_M = 0                       # samples per My_Planning array once handoff_setup() has run
         self._cas = self._cas_planner = None
         self._race = None                    # (B, laps, tt, planner) while this engine owns a race
+        self._rec = None                     # (capacity, stride) while the race records
 
     # -- lifetime --------------------------------------------------------------------------------
     def close(self):
@@ -387,6 +388,7 @@ class BatchedSolver:
         self._cas = None
         self._cas_planner = None
         self._race = None
+        self._rec = None
 
     def cascade_init(self, planner, plant0, cmd0, uPred0, lap0=1, half_width=0.3, slack=0.15, plan_max_ey=0.2, q9_swap=True,
                      n_sub=(7, 7, 6), dt_sim=0.005, mu_sim=0.05):
@@ -468,6 +470,7 @@ class BatchedSolver:
                 raise TypeError("estimator must be an observer.observer_config(...) result or an _ffi.ObserverConfig")
             self._chk(self._lib.lpvmpc_race_init_observed(self._h, tt._h, planner._h, B, ptr(p0), ptr(ht), C.byref(c), C.byref(estimator)))
         self._race = (B, int(c.laps), tt, planner)           # (keeps the two other engines alive as long as the race)
+        self._rec = None
 
     def race_tick(self, n_ticks=1):
         self._chk(self._lib.lpvmpc_race_tick(self._h, int(n_ticks)))
@@ -503,6 +506,52 @@ class BatchedSolver:
         pu = np.empty((B, self.N, 2)); tu = np.empty((B, self.N, 2))
         self._chk(self._lib.lpvmpc_race_predictions(self._h, ptr(pu), ptr(tu)))
         return pu, tu
+
+    def race_record(self, capacity, stride=1):
+        """Record the race from the next tick on (lpvmpc_race_record): a ring of the last ``capacity`` records, one every
+        ``stride`` ticks, and the per-lap statistics of every tick.  Restarting resets both; ``capacity`` 0 stops recording."""
+        self._race_B("race_record")
+        cfg = _ffi.RaceRecordConfig(int(capacity), int(stride))
+        try:
+            self._chk(self._lib.lpvmpc_race_record(self._h, C.byref(cfg)))
+        except LpvMpcError as e:
+            if e.code != _ffi.E_ARG:                 # (a refused argument leaves the recorder as it was; a failed allocation stops it)
+                self._rec = None
+            raise
+        self._rec = (int(capacity), int(stride)) if capacity else None
+
+    def race_record_read(self, last=None):
+        """The last ``last`` (default: all kept) records, oldest first: a dict of [n, B] arrays named as _ffi.REC_F64_NAMES /
+        REC_I32_NAMES, the same channels grouped (plant [n,B,8], local [n,B,6], cmd [n,B,2], ref [n,B,4], track [n,B,3],
+        est [n,B,6]), tick [n] and total (records written since recording started)."""
+        B = self._race_B("race_record_read")
+        if last is not None and int(last) < 0:               # the library's refusal
+            self._chk(self._lib.lpvmpc_race_record_read(self._h, int(last), None, None, None, None))
+        rec = getattr(self, "_rec", None)
+        cap = rec[0] if rec else 0
+        n = cap if last is None else min(int(last), cap)
+        f = np.empty((n, _ffi.REC_F64, B)); i = np.empty((n, _ffi.REC_I32, B), np.int32); tick = np.empty(n, np.int32)
+        total = np.zeros(1, np.int32)
+        self._chk(self._lib.lpvmpc_race_record_read(self._h, n, ptr(total), ptr(tick), ptr(f), ptr(i)))
+        m = min(n, int(total[0]))                        # records copied (n <= capacity)
+        f, i, tick = f[:m], i[:m], tick[:m]
+        out = {k: f[:, c] for c, k in enumerate(_ffi.REC_F64_NAMES)}
+        out.update({k: i[:, c] for c, k in enumerate(_ffi.REC_I32_NAMES)})
+        for k, c, w in (("plant", _ffi.REC_PLANT, 8), ("local", _ffi.REC_LOCAL, 6), ("cmd", _ffi.REC_CMD, 2), ("ref", _ffi.REC_REF, 4),
+                        ("track", _ffi.REC_TRACK, 3), ("est", _ffi.REC_EST, 6)):
+            out[k] = np.ascontiguousarray(f[:, c:c + w].transpose(0, 2, 1))
+        out["tick"] = tick
+        out["total"] = int(total[0])
+        return out
+
+    def race_lap_stats(self):
+        """Per-lap statistics of the recorded ticks: a dict of [B, laps+1] arrays named as _ffi.LAPSTAT_F64_NAMES /
+        LAPSTAT_I32_NAMES, the raw planes f64 [B, laps+1, 6] / i32 [B, laps+1, 9], and end_tick [B]."""
+        B = self._race_B("race_lap_stats")
+        L1 = self._race[1] + 1
+        f = np.empty((B, L1, _ffi.LAPSTAT_F64)); i = np.empty((B, L1, _ffi.LAPSTAT_I32), np.int32); e = np.empty(B, np.int32)
+        self._chk(self._lib.lpvmpc_race_lap_stats(self._h, ptr(f), ptr(i), ptr(e)))
+        return _ffi.lap_stats_dict(f, i, e)
 
     # -- device-pointer entry point (torch tensors or raw integers) -----------------------------------
     def solve_dev(self, B, x0, u_prev, vel_ref, curv_s, u_old, max_ey, xPred, uPred, status=None, iters=None,
@@ -878,6 +927,21 @@ class RaceFleet(object):
         d = (ls[:, 1:] - ls[:, :-1]).astype(float) * self.dt_sim
         d[(ls[:, 1:] < 0) | (ls[:, :-1] < 0)] = np.nan
         return d
+
+    def record(self, capacity, stride=1):
+        """Record the race from the next tick on (BatchedSolver.race_record): the last ``capacity`` records, one every ``stride``
+        ticks, and the per-lap statistics of every tick.  ``record(0)`` stops recording."""
+        self.path.race_record(capacity, stride)
+
+    def trace(self, last=None):
+        """The kept records, oldest first (BatchedSolver.race_record_read)."""
+        return self.path.race_record_read(last)
+
+    def lap_stats(self):
+        """Per-lap statistics of the recorded ticks (BatchedSolver.race_lap_stats) with rmse_v / rmse_ey / rmse_epsi [B, laps+1]
+        (RMSE_ve / RMSE_ye / RMSE_thetae of CMAIN:101-106; NaN where the lap has no counted tick)."""
+        from .telemetry import add_rmse
+        return add_rmse(self.path.race_lap_stats())
 
     def close(self):
         for e in (self.path, self.tt, self.planner):

@@ -2,12 +2,20 @@
 // for one fleet on the device, owned by the path controller handle.  Kernels: race.hip (per-tick glue), lpv_eval.hip,
 // admm_solve.hip and handoff.hip (masked launches).  A race with the estimator in the loop (lpvmpc_race_init_observed) keeps
 // the estimator state, gains and parameters in the path handle's obs_state / obs_gains / obs_p (obs_cfg stays null, so the
-// handle's next lpvmpc_cl_init runs on ground truth); lpvmpc_race_free releases them.
+// handle's next lpvmpc_cl_init runs on ground truth); lpvmpc_race_free releases them.  The recorder (lpvmpc_race_record,
+// record.hip) belongs to the race as well.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <new>
 
 #include "lpvmpc_handle.hpp"
+#include "record.hpp"
+
+struct lpvmpc_race_recorder {
+    lpvmpc::RecDev d;             // kernel argument: race state pointers and the recorder's buffers
+    int capacity, stride, t_start, total;
+};
 
 struct lpvmpc_race {
     lpvmpc_handle *tt, *plan;
@@ -17,7 +25,17 @@ struct lpvmpc_race {
     bool actuated;                // lpvmpc_race_init_actuated: delayed kernels, actuator state act, controller histories of steering delay sd
     lpvmpc::ActDev act;
     int sd;
+    lpvmpc_race_recorder *rec;    // lpvmpc_race_record (null: not recording)
 };
+
+static void recorder_free(lpvmpc_race *r) {
+    lpvmpc_race_recorder *q = r->rec;
+    if (!q) return;
+    void *ptrs[] = {q->d.rec_f, q->d.rec_i, q->d.stat_f, q->d.stat_i, q->d.prev_phase, q->d.end_tick};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    delete q;
+    r->rec = nullptr;
+}
 
 void lpvmpc_race_free(lpvmpc_handle *h) {
     lpvmpc_race *r = h->race;
@@ -35,6 +53,7 @@ void lpvmpc_race_free(lpvmpc_handle *h) {
         h->obs_state = h->obs_gains = nullptr; h->obs_B = 0; h->obs_p = lpvmpc::ObsParams{};
     }
     lpvmpc_act_free(r->act);
+    recorder_free(r);
     if (r->tt && r->tt->race_owner == h) r->tt->race_owner = nullptr;
     if (r->plan && r->plan->race_owner == h) r->plan->race_owner = nullptr;
     delete r;
@@ -233,6 +252,11 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
         else if (r->actuated) HIP_TRY(h, lpvmpc::launch_race_command_plant_act(d, r->pc, r->act, st));
         else if (d.estv) HIP_TRY(h, lpvmpc::launch_race_command_plant_observe(d, r->pc, h->obs_gains, h->obs_state, h->obs_p, st));
         else HIP_TRY(h, lpvmpc::launch_race_command_plant(d, r->pc, st));
+        if (lpvmpc_race_recorder *q = r->rec) {                               // the recorder (record.hip)
+            int slot = -1;
+            if ((r->ticks - q->t_start) % q->stride == 0) { slot = q->total % q->capacity; q->total++; }
+            HIP_TRY(h, lpvmpc::launch_race_record(h->d_cfg, q->d, r->ticks, slot, st));
+        }
         r->ticks++;
     }
     return LPVMPC_OK;
@@ -279,6 +303,94 @@ extern "C" int lpvmpc_race_predictions(lpvmpc_handle *h, double *path_uPred, dou
     const size_t n = (size_t)d.B * d.N * 2 * 8;
     if (path_uPred) D2H(path_uPred, d.p_uPred, n);
     if (tt_uPred) D2H(tt_uPred, d.t_uPred, n);
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return LPVMPC_OK;
+}
+
+// the race recorder (include/lpvmpc.h, "Race recorder"; kernel: record.hip)
+static bool mul_size(size_t &acc, size_t x) { return !__builtin_mul_overflow(acc, x, &acc); }
+
+extern "C" int lpvmpc_race_record(lpvmpc_handle *h, const lpvmpc_race_record_config *cfg) {
+    if (!h || !h->race) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_record: call lpvmpc_race_init first");
+    if (!cfg || cfg->capacity < 0 || cfg->stride < 1)
+        return fail(h, LPVMPC_E_ARG, "lpvmpc_race_record: NULL configuration, capacity < 0 or stride < 1");
+    lpvmpc_race *r = h->race;
+    const lpvmpc::RaceDev &d = r->d;
+    const size_t B = d.B, cap = cfg->capacity, laps1 = (size_t)d.laps + 1;
+    size_t nf = cap, ni = cap, sf = B, si = B;
+    if (!mul_size(nf, LPVMPC_REC_F64) || !mul_size(nf, B) || !mul_size(nf, sizeof(double)) || !mul_size(ni, LPVMPC_REC_I32) ||
+        !mul_size(ni, B) || !mul_size(ni, sizeof(int32_t)) || !mul_size(sf, laps1) || !mul_size(sf, LPVMPC_LAPSTAT_F64 * sizeof(double)) ||
+        !mul_size(si, laps1) || !mul_size(si, LPVMPC_LAPSTAT_I32 * sizeof(int32_t)))
+        return fail(h, LPVMPC_E_ARG, "lpvmpc_race_record: capacity %d x %d vehicles overflows the buffer size", cfg->capacity, d.B);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = h->stream;
+    HIP_TRY(h, hipStreamSynchronize(st));                                       // no tick in flight reads the old recorder
+    recorder_free(r);
+    if (cap == 0) return LPVMPC_OK;
+    lpvmpc_race_recorder *q = new (std::nothrow) lpvmpc_race_recorder();
+    if (!q) return fail(h, LPVMPC_E_NOMEM, "out of host memory");
+    r->rec = q;
+    lpvmpc::RecDev &e = q->d;
+    struct { void **p; size_t n; } bufs[] = {{(void **)&e.rec_f, nf}, {(void **)&e.rec_i, ni}, {(void **)&e.stat_f, sf},
+                                             {(void **)&e.stat_i, si}, {(void **)&e.prev_phase, B * 4}, {(void **)&e.end_tick, B * 4}};
+    for (auto &x : bufs) {
+        const hipError_t err = hipMalloc(x.p, x.n);
+        if (err != hipSuccess) {
+            (void)hipGetLastError();                                            // leave no error pending for the race's launches
+            recorder_free(r);
+            return fail(h, LPVMPC_E_NOMEM, "lpvmpc_race_record: hipMalloc of %zu B failed: %s", x.n, hipGetErrorString(err));
+        }
+    }
+    e.B = d.B; e.N = d.N; e.laps = d.laps; e.q9 = d.q9; e.hw = d.hw; e.slack = d.slack;
+    e.plant = d.plant; e.local = d.local; e.cmd = d.cmd; e.ref0 = d.ref0; e.t_vel = d.t_vel;
+    e.obs = d.estv ? h->obs_state : nullptr;
+    e.phase = d.phase; e.lap = d.lap; e.rk = d.rk; e.src = d.src; e.iters = d.iters; e.status = d.status; e.m_plan = d.m_plan;
+    e.q_iters = r->plan->d_iters; e.q_status = r->plan->d_status;
+    q->capacity = cfg->capacity; q->stride = cfg->stride; q->t_start = r->ticks; q->total = 0;
+    hipError_t err = hipMemsetAsync(e.stat_f, 0, sf, st);
+    if (err == hipSuccess) err = hipMemsetAsync(e.stat_i, 0, si, st);
+    if (err == hipSuccess) err = hipMemsetAsync(e.end_tick, 0xff, B * 4, st);
+    if (err == hipSuccess) err = hipMemcpyAsync(e.prev_phase, d.phase, B * 4, hipMemcpyDeviceToDevice, st);
+    if (err != hipSuccess) {                                                    // no recorder with statistics that were never zeroed
+        (void)hipStreamSynchronize(st);
+        recorder_free(r);
+        return fail(h, LPVMPC_E_HIP, "lpvmpc_race_record: resetting the recorder failed: %s", hipGetErrorString(err));
+    }
+    return LPVMPC_OK;
+}
+
+extern "C" int lpvmpc_race_record_read(lpvmpc_handle *h, int32_t n, int32_t *total, int32_t *tick, double *f64, int32_t *i32) {
+    if (!h || !h->race) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_record_read: call lpvmpc_race_init first");
+    if (n < 0) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_record_read: n < 0");
+    const lpvmpc_race_recorder *q = h->race->rec;
+    if (!q) { if (total) total[0] = 0; return LPVMPC_OK; }
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = h->stream;
+    const size_t B = q->d.B, wf = (size_t)LPVMPC_REC_F64 * B, wi = (size_t)LPVMPC_REC_I32 * B;
+    const int kept = q->total < q->capacity ? q->total : q->capacity, m = n < kept ? n : kept;
+    const int k0 = q->total - m;                                                // the first record copied (0-based since the start)
+    for (int j = 0; j < m;) {                                                   // at most two runs of the ring
+        const int slot = (k0 + j) % q->capacity, run = std::min(m - j, q->capacity - slot);
+        if (f64) D2H(f64 + (size_t)j * wf, q->d.rec_f + (size_t)slot * wf, (size_t)run * wf * 8);
+        if (i32) D2H(i32 + (size_t)j * wi, q->d.rec_i + (size_t)slot * wi, (size_t)run * wi * 4);
+        j += run;
+    }
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (tick) for (int j = 0; j < m; ++j) tick[j] = q->t_start + (k0 + j) * q->stride;
+    if (total) total[0] = q->total;
+    return LPVMPC_OK;
+}
+
+extern "C" int lpvmpc_race_lap_stats(lpvmpc_handle *h, double *f64, int32_t *i32, int32_t *end_tick) {
+    if (!h || !h->race) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_lap_stats: call lpvmpc_race_init first");
+    const lpvmpc_race_recorder *q = h->race->rec;
+    if (!q) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_lap_stats: recording is off (lpvmpc_race_record)");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = h->stream;
+    const size_t n = (size_t)q->d.B * (q->d.laps + 1);
+    if (f64) D2H(f64, q->d.stat_f, n * LPVMPC_LAPSTAT_F64 * 8);
+    if (i32) D2H(i32, q->d.stat_i, n * LPVMPC_LAPSTAT_I32 * 4);
+    if (end_tick) D2H(end_tick, q->d.end_tick, (size_t)q->d.B * 4);
     HIP_TRY(h, hipStreamSynchronize(st));
     return LPVMPC_OK;
 }

@@ -617,6 +617,91 @@ int  lpvmpc_race_init_actuated(lpvmpc_handle *path, lpvmpc_handle *tt, lpvmpc_ha
  * measurement, so this is what its LAST solve read; tt_hist [B][2 + d]: the race's `tt`, likewise (NULL for a fleet). */
 int  lpvmpc_actuator_read(lpvmpc_handle *h, double *act_state, double *path_hist, double *tt_hist);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Race recorder: telemetry and per-lap tracking statistics of a race, kept on the device (the controller node's ALL_LOCAL_DATA,
+ * GLOBAL_DATA, References and the RMSE_ve / RMSE_ye / RMSE_thetae it declares, CMAIN:101-106,115,194-195,217-218,411-419).
+ * While recording is on, lpvmpc_race_tick launches one more kernel per tick, after the command / plant kernel; with it off a
+ * tick issues the launches it always did.  Recording changes no output of the race.
+ *
+ * Ring of records: recording keeps the last `capacity` records.  Tick t (the race's tick number as lpvmpc_race_read reports it,
+ * counted before the tick) is recorded when (t - t_start) % stride == 0, t_start = the first tick after lpvmpc_race_record; record
+ * k (0-based since the start) is tick t_start + k * stride.  Each record holds, per vehicle, the vehicle's state after the tick --
+ * what lpvmpc_race_read would return after it -- in two planes, channel-major and vehicle-minor: f64 [LPVMPC_REC_F64][B] and
+ * i32 [LPVMPC_REC_I32][B]:
+ *   plant [x y vx vy ax ay yaw psiDot]; local: the tick's measurement [vx vy w epsi s ey] in lpvmpc_race_read's slots (quirk Q9
+ *   swaps slots 3 / 5 in lap 0 with q9_swap); cmd [servo motor] applied on this tick; ref [x_ref y_ref yaw_ref vel_ref];
+ *   track [s ey epsi]: Map.getLocalPosition of the ground-truth plant (lpvmpc_local_position_batch's function and sentinels);
+ *   est [vx vy psiDot x y yaw]: the estimator's state (NaN on a race without one);
+ *   phase, lap, src (controller that solved: -1 none, 0 path, 1 tt), iters, status (as lpvmpc_race_read), plan_iters /
+ *   plan_status of a planner solve on this tick (-1 when the vehicle ran none), inside (the track frame's flag).
+ * ref follows the node's References: [0 0 0 1] on every tick measured by the lap-0 branch, the event tick included
+ * (CMAIN:194-195); on a racing tick the point the measurement's Body_Frame_Errors used and vel_ref[0] of the tt controller.  On
+ * odd racing ticks this differs from the node's References row, which logs planning_data.*[0] of the newest message while the
+ * `index` latch measures against the window read one tick earlier.
+ *
+ * Per-lap statistics, updated on every tick while recording is on (whatever the stride), per vehicle and lap l = 0 .. laps:
+ * f64 [B][laps + 1][LPVMPC_LAPSTAT_F64], i32 [B][laps + 1][LPVMPC_LAPSTAT_I32].  A tick counts when the vehicle's controller
+ * solved on it (src >= 0: not frozen, lost or finishing -- nothing of a finishing tick is applied) and goes to l = the lap counter
+ * after its measurement, with the planner solve of the same tick, if any.  With e_v = local vx - vel_ref, ey / epsi the lateral /
+ * heading error of the measurement -- local[5] / local[3], except on ticks measured by the lap-0 branch (phase 0 after the tick,
+ * or the event tick) of a race with q9_swap, whose measurement stores them in local[3] / local[5] -- and ey_track = track ey,
+ * in tick order:
+ *   sse_v += e_v * e_v; sse_ey += ey * ey; sse_epsi += epsi * epsi; sum_vx += local vx (each s = s + x * x, rounded twice,
+ *   no fused multiply-add); max_ey = |ey| if |ey| > max_ey; max_ey_track likewise (all start at 0; a NaN never replaces them);
+ *   ticks, ctrl_iters (sum), ctrl_iters_max, ctrl_not_solved (status != LPVMPC_SOLVED), plan_ticks, plan_iters (sum),
+ *   plan_iters_max, plan_not_solved, off_track (inside == 0).
+ * RMSE_ve = sqrt(sse_v / ticks), likewise ey and epsi.  end_tick [B]: the tick on which the vehicle became finished or lost,
+ * -1 while it runs or when it ended before recording started.
+ *
+ * lpvmpc_race_record starts recording from the next tick: it frees a previous recorder, allocates the ring and the statistics and
+ * zeroes them.  capacity == 0 stops recording and frees them.  Refused with LPVMPC_E_ARG: no race on the handle, capacity < 0,
+ * stride < 1, a size that overflows; with LPVMPC_E_NOMEM: a failed allocation, after which the race runs on unrecorded.  The
+ * recorder belongs to the race: lpvmpc_cl_release(path) or destroying a handle frees it, and a new race starts unrecorded. */
+#define LPVMPC_REC_F64            29
+#define LPVMPC_REC_PLANT           0  /* 8 channels */
+#define LPVMPC_REC_LOCAL           8  /* 6 */
+#define LPVMPC_REC_CMD            14  /* 2 */
+#define LPVMPC_REC_REF            16  /* 4 */
+#define LPVMPC_REC_TRACK          20  /* 3 */
+#define LPVMPC_REC_EST            23  /* 6 */
+#define LPVMPC_REC_I32             8
+#define LPVMPC_REC_PHASE           0
+#define LPVMPC_REC_LAP             1
+#define LPVMPC_REC_SRC             2
+#define LPVMPC_REC_ITERS           3
+#define LPVMPC_REC_STATUS          4
+#define LPVMPC_REC_PLAN_ITERS      5
+#define LPVMPC_REC_PLAN_STATUS     6
+#define LPVMPC_REC_INSIDE          7
+#define LPVMPC_LAPSTAT_F64              6
+#define LPVMPC_LAPSTAT_SSE_V            0
+#define LPVMPC_LAPSTAT_SSE_EY           1
+#define LPVMPC_LAPSTAT_SSE_EPSI         2
+#define LPVMPC_LAPSTAT_MAX_EY           3
+#define LPVMPC_LAPSTAT_SUM_VX           4
+#define LPVMPC_LAPSTAT_MAX_EY_TRACK     5
+#define LPVMPC_LAPSTAT_I32              9
+#define LPVMPC_LAPSTAT_TICKS            0
+#define LPVMPC_LAPSTAT_CTRL_ITERS       1
+#define LPVMPC_LAPSTAT_CTRL_ITERS_MAX   2
+#define LPVMPC_LAPSTAT_CTRL_NOT_SOLVED  3
+#define LPVMPC_LAPSTAT_PLAN_TICKS       4
+#define LPVMPC_LAPSTAT_PLAN_ITERS       5
+#define LPVMPC_LAPSTAT_PLAN_ITERS_MAX   6
+#define LPVMPC_LAPSTAT_PLAN_NOT_SOLVED  7
+#define LPVMPC_LAPSTAT_OFF_TRACK        8
+typedef struct lpvmpc_race_record_config {
+    int32_t capacity;         /* records kept (0: stop recording) */
+    int32_t stride;           /* record every stride-th tick (>= 1) */
+} lpvmpc_race_record_config;
+int  lpvmpc_race_record(lpvmpc_handle *path, const lpvmpc_race_record_config *cfg);
+/* synchronises and copies the last min(n, kept) records, oldest first (kept = min(total, capacity)): tick [m], f64 [m][LPVMPC_REC_F64][B],
+ * i32 [m][LPVMPC_REC_I32][B] (any of the three may be NULL); total [1] = records written since recording started (0, and nothing
+ * copied, while recording is off). */
+int  lpvmpc_race_record_read(lpvmpc_handle *path, int32_t n, int32_t *total, int32_t *tick, double *f64, int32_t *i32);
+/* synchronises and copies the per-lap statistics (any pointer may be NULL); refused with LPVMPC_E_ARG while recording is off */
+int  lpvmpc_race_lap_stats(lpvmpc_handle *path, double *f64, int32_t *i32, int32_t *end_tick);
+
 #ifdef __cplusplus
 }
 #endif

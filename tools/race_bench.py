@@ -10,7 +10,9 @@ and the added ms per controller tick.
 --actuator: instead, the lap0 and inphase races run on the old entry (lpvmpc_race_init), on lpvmpc_race_init_actuated with the actuator
 all off, with plant delays La = Ld = 20 steps and the servo lag (steeringDelay 0), and the same with steeringDelay 3 on both
 controllers; alternated --reps times per (regime, B), medians and differences against the old entry.
-Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator | --actuator [--reps R]] [--out FILE]"""
+--record: instead, the lap0 and inphase races run with recording off and on (lpvmpc_race_record, stride 1, a ring as long as the timed
+window), alternated --reps times per (regime, B); medians and the added ms per controller tick.
+Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator | --actuator | --record [--reps R]] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -41,11 +43,13 @@ def timed(tick, read, K):
     return (time.perf_counter() - t0) * 1e3 / K
 
 
-def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0):
+def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, record=False):
     path, tt, plan = engines(mp, sd)
     path.race_init(tt, plan, plant0, half_track0=half, laps=5, half_width=mp.halfWidth, slack=mp.slack, estimator=estimator,
                    actuator=actuator)
     path.race_tick(warm)
+    if record:
+        path.race_record(K, 1)
     a0 = path.race_laps()[1].sum()
     ms = timed(path.race_tick, path.race_read, K)
     alive = path.race_laps()[1].sum() - a0
@@ -63,7 +67,10 @@ def main():
     ap.add_argument("--estimator", action="store_true")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--actuator", action="store_true")
+    ap.add_argument("--record", action="store_true")
     a = ap.parse_args()
+    if a.record:
+        return record_main(a)
     if a.estimator:
         return estimator_main(a)
     if a.actuator:
@@ -180,6 +187,34 @@ def actuator_main(a):
     if a.out:
         with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")
+
+
+def record_main(a):
+    import lpvmpc
+    from tests._golden import load
+    mp = lpvmpc.Map("L_shape", 0.2)
+    c = load("cascade")
+    P = int(c["pre_ticks"])
+    lines = []
+    for B in [int(x) for x in a.sizes.split(",")]:
+        rng = np.random.default_rng(3)
+        grid = np.zeros((B, 8)); grid[:, 1] = rng.normal(0, 0.02, B); grid[:, 2] = rng.uniform(0.9, 1.1, B)
+        same = np.tile(c["pre_plant"][0], (B, 1))
+        for name, plant0, half, warm in (("lap0", grid, 0, 10), ("inphase", same, 1, P + 3)):
+            ms = {False: [], True: []}
+            ph = {}
+            for _ in range(a.reps):
+                for rec in (False, True):
+                    m, _vps, ph[rec] = race_run(mp, plant0, half, warm, a.ticks, record=rec)
+                    ms[rec].append(m)
+            m0, m1 = float(np.median(ms[False])), float(np.median(ms[True]))
+            lines.append("%-8s B=%5d  race %.3f ms/tick (runs %s, phases %s)  recording %.3f ms/tick (runs %s, phases %s)  "
+                         "added %+.3f ms/tick" % (name, B, m0, " ".join("%.3f" % x for x in ms[False]), ph[False].tolist(), m1,
+                                                  " ".join("%.3f" % x for x in ms[True]), ph[True].tolist(), m1 - m0))
+            print(lines[-1], flush=True)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
 
 
 def _act20():
