@@ -47,7 +47,8 @@ class Config(C.Structure):
 SETTING_FIELDS = ("rho", "sigma", "alpha", "eps_abs", "eps_rel", "eps_prim_inf", "eps_dual_inf", "polish_delta",
                   "adaptive_rho_tolerance", "max_iter", "check_termination", "scaling", "adaptive_rho",
                   "adaptive_rho_interval", "polish", "polish_refine_iter",
-                  "ctrl_vx_min", "ctrl_delta_max", "ctrl_a_max", "ctrl_a_min_abs", "steering_delay")
+                  "ctrl_vx_min", "ctrl_delta_max", "ctrl_a_max", "ctrl_a_min_abs", "steering_delay",
+                  "plan_xmin", "plan_xmax", "plan_umin", "plan_umax")
 
 
 class LpvMpcError(RuntimeError):

@@ -45,8 +45,10 @@ class BatchedSolver:
     """Batched LPV-MPC (``kind="controller"``) / LPV-MPP (``kind="planner"``) solver on one MI355X.
 
     Parameters follow the reference constructors; ``track`` is a PointAndTangent table (or None when only
-    caller-supplied curvature / LPV matrices are used); ``settings`` overrides OSQP settings and the
-    controller limits (see ``_ffi.SETTING_FIELDS``)."""
+    caller-supplied curvature / LPV matrices are used); ``settings`` overrides OSQP settings, the
+    controller limits and the planner's boxes (see ``_ffi.SETTING_FIELDS``; ``plan_xmin`` / ``plan_xmax``
+    take 5 values, ``plan_umin`` / ``plan_umax`` 2, slots 0 and 3 of the state box are always set from
+    min_vel / max_vel and max_ey)."""
 
     def __init__(self, kind, N, dt, Q, R, dR, L_cf=None, track=None, params=None, device=0, **settings):
         self.kind = {"controller": KIND_CONTROLLER, "planner": KIND_PLANNER}.get(kind, kind)
@@ -85,7 +87,12 @@ class BatchedSolver:
         for k, v in settings.items():
             if k not in _ffi.SETTING_FIELDS:
                 raise TypeError("unknown setting %r" % k)
-            setattr(cfg, k, v)
+            if k.startswith("plan_"):
+                arr = getattr(cfg, k)
+                for i, x in enumerate(f64(v, (len(arr),), k)):
+                    arr[i] = x
+            else:
+                setattr(cfg, k, v)
         if track is not None:
             tab = f64(track, name="track")
             if tab.ndim != 2 or tab.shape[1] != 6 or tab.shape[0] > _ffi.MAX_TRACK_ROWS:

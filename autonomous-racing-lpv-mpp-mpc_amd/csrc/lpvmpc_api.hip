@@ -152,6 +152,12 @@ extern "C" lpvmpc_handle *lpvmpc_create(const lpvmpc_config *cfg) {
     if (cfg->track_rows < 0 || cfg->track_rows > LPVMPC_MAX_TRACK_ROWS) { fail(nullptr, LPVMPC_E_ARG, "lpvmpc_create: track_rows=%d outside [0,%d]", cfg->track_rows, LPVMPC_MAX_TRACK_ROWS); return nullptr; }
     if (!(cfg->dt > 0) || !(cfg->rho > 0) || !(cfg->sigma > 0) || !(cfg->alpha > 0 && cfg->alpha < 2) || !(cfg->polish_delta > 0)) {
         fail(nullptr, LPVMPC_E_ARG, "lpvmpc_create: dt, rho, sigma, polish_delta must be > 0 and 0 < alpha < 2"); return nullptr; }
+    // the remaining settings OSQP 0.6 (validate_settings) refuses
+    if (!(cfg->eps_abs >= 0) || !(cfg->eps_rel >= 0) || (cfg->eps_abs == 0 && cfg->eps_rel == 0) || !(cfg->eps_prim_inf > 0) || !(cfg->eps_dual_inf > 0)) {
+        fail(nullptr, LPVMPC_E_ARG, "lpvmpc_create: eps_abs, eps_rel must be >= 0 and not both 0; eps_prim_inf, eps_dual_inf must be > 0"); return nullptr; }
+    if (cfg->max_iter <= 0 || cfg->scaling < 0 || cfg->polish_refine_iter < 0 || cfg->check_termination < 0 || cfg->adaptive_rho_interval < 0) {
+        fail(nullptr, LPVMPC_E_ARG, "lpvmpc_create: max_iter must be > 0; scaling, polish_refine_iter, check_termination, adaptive_rho_interval >= 0"); return nullptr; }
+    if (!(cfg->adaptive_rho_tolerance >= 1)) { fail(nullptr, LPVMPC_E_ARG, "lpvmpc_create: adaptive_rho_tolerance must be >= 1"); return nullptr; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { fail(nullptr, LPVMPC_E_NODEVICE, "lpvmpc_create: no HIP device available (there is no CPU fallback)"); return nullptr; }
     if (cfg->device < 0 || cfg->device >= ndev) { fail(nullptr, LPVMPC_E_ARG, "lpvmpc_create: device %d of %d", cfg->device, ndev); return nullptr; }

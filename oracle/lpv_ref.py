@@ -305,9 +305,14 @@ class QP:
     meta: dict = field(default_factory=dict)
 
 
-def ctrl_build_qp(Q, R, dR, N, A, B, x0, u_old, vel_ref, max_vel, steer_hist=()):
+def ctrl_build_qp(Q, R, dR, N, A, B, x0, u_old, vel_ref, max_vel, steer_hist=(), vx_min=0.01, delta_max=0.249, a_max=4.0,
+                  a_min_abs=1.0):
     """QP of PathFollowingLPV_MPC.solve (CTRL:89-162 with a4/a5/a6/a8 of
     SURVEY section 8): inequalities first, then equalities (CTRL:303-308).
+
+    ``vx_min``, ``delta_max``, ``a_max``, ``a_min_abs``: the limits of the
+    inequality rows (CTRL:334-348; the settings ctrl_vx_min / ctrl_delta_max /
+    ctrl_a_max / ctrl_a_min_abs of lpvmpc_config), defaults the reference's.
 
     ``u_old`` = [OldSteering[0], OldAccelera[0]] (CTRL:395).  The vel_ref
     tracking point of stage N is vel_ref[-1] (CTRL:438).  ``steer_hist`` =
@@ -332,14 +337,14 @@ def ctrl_build_qp(Q, R, dR, N, A, B, x0, u_old, vel_ref, max_vel, steer_hist=())
     F = np.zeros((6 * N, nz))
     b = np.zeros(6 * N)
     for k in range(N):
-        F[2 * k, k * nx] = -1.0;      b[2 * k] = -0.01
+        F[2 * k, k * nx] = -1.0;      b[2 * k] = -vx_min
         F[2 * k + 1, k * nx] = 1.0;   b[2 * k + 1] = max_vel
         c = (N + 1) * nx + k * nu
         r = 2 * N + 4 * k
-        F[r, c] = 1.0;        b[r] = 0.249
-        F[r + 1, c] = -1.0;   b[r + 1] = 0.249
-        F[r + 2, c + 1] = 1.0;  b[r + 2] = 4.0
-        F[r + 3, c + 1] = -1.0; b[r + 3] = 1.0
+        F[r, c] = 1.0;        b[r] = delta_max
+        F[r + 1, c] = -1.0;   b[r + 1] = delta_max
+        F[r + 2, c + 1] = 1.0;  b[r + 2] = a_max
+        F[r + 3, c + 1] = -1.0; b[r + 3] = a_min_abs
     G, E = eq_constraints(A, B, nx, nu, N)
     beq = E @ np.asarray(x0, float).reshape(nx)          # quirk Q1: Eu*uOld dropped
     steer_hist = np.asarray(steer_hist, float).reshape(-1)
@@ -354,9 +359,14 @@ def ctrl_build_qp(Q, R, dR, N, A, B, x0, u_old, vel_ref, max_vel, steer_hist=())
     return QP(P, q, Aqp, l, u, dict(kind="controller", N=N, nx=nx, nu=nu))
 
 
-def plan_build_qp(Q, R, dR, L_cf, N, A, B, x0, u_old, max_ey, max_vel, min_vel):
+def plan_build_qp(Q, R, dR, L_cf, N, A, B, x0, u_old, max_ey, max_vel, min_vel, xmin=None, xmax=None, umin=None, umax=None):
     """QP of LPV_MPC_Planner.solve (PLAN:86-236): equalities first, then the
-    identity box on every variable including x_0 (PLAN:173-181,200-202)."""
+    identity box on every variable including x_0 (PLAN:173-181,200-202).
+
+    ``xmin`` / ``xmax`` (5) and ``umin`` / ``umax`` (2): the boxes of the
+    settings plan_xmin / plan_xmax / plan_umin / plan_umax of lpvmpc_config,
+    defaults the reference's; as there, slots 0 and 3 of the state box always
+    come from min_vel / max_vel and max_ey."""
     nx, nu = 5, 2
     Q = np.asarray(Q, float); R = np.asarray(R, float); dR = np.asarray(dR, float)
     L_cf = np.asarray(L_cf, float)
@@ -370,9 +380,11 @@ def plan_build_qp(Q, R, dR, L_cf, N, A, B, x0, u_old, max_ey, max_vel, min_vel):
     P = 2.0 * M0
     G, E = eq_constraints(A, B, nx, nu, N)
     beq = E @ np.asarray(x0, float).reshape(nx)
-    umin = np.array([-0.249, -0.7]); umax = np.array([0.249, 2.0])
-    xmin = np.array([min_vel, -1, -2, -max_ey, -0.8])
-    xmax = np.array([max_vel, 1, 2, max_ey, 0.8])
+    umin = np.array([-0.249, -0.7] if umin is None else umin, float)
+    umax = np.array([0.249, 2.0] if umax is None else umax, float)
+    xmin = np.array([min_vel, -1, -2, -max_ey, -0.8] if xmin is None else xmin, float)
+    xmax = np.array([max_vel, 1, 2, max_ey, 0.8] if xmax is None else xmax, float)
+    xmin[0], xmin[3], xmax[0], xmax[3] = min_vel, -max_ey, max_vel, max_ey
     lo = np.concatenate([np.tile(xmin, N + 1), np.tile(umin, N)])
     hi = np.concatenate([np.tile(xmax, N + 1), np.tile(umax, N)])
     Aqp = np.vstack([G, np.eye(nz)])

@@ -180,6 +180,102 @@ def ctrl_delay_ordering(N, delay, nx=6, nu=2):
     return np.array(perm, dtype=np.int32)
 
 
+def plan_ordering(N, nx=5, nu=2):
+    """Stage-wise KKT ordering of a planner QP: the order oracle/lpv_ref.c hands the solver (oracle_plan_tick_batch): the
+    x_0 equality rows, then per stage each state with its box row, each input with its box row and the dynamics rows into
+    the next stage."""
+    nz = (N + 1) * nx + N * nu
+    me = (N + 1) * nx
+    perm = [nz + r for r in range(nx)]
+    for k in range(N + 1):
+        for a in range(nx):
+            perm += [k * nx + a, nz + me + k * nx + a]
+        if k < N:
+            for j in range(nu):
+                v = (N + 1) * nx + k * nu + j
+                perm += [v, nz + me + v]
+            perm += [nz + (k + 1) * nx + r for r in range(nx)]
+    return np.array(perm, dtype=np.int32)
+
+
+def osqp_settings(settings=None):
+    """The OSQP part of a BatchedSolver settings dict as keyword arguments of solve_qp (polish_delta -> delta); the
+    controller limits, the planner boxes and steering_delay are not solver settings and are dropped."""
+    out = {}
+    for k, v in (settings or {}).items():
+        if k == "polish_delta":
+            out["delta"] = v
+        elif hasattr(Settings, k):
+            out[k] = v
+    return out
+
+
+def instance_qp(w, kind, j, params=None, limits=None):
+    """(P, q, A, l, u) of instance j of a workload dict, assembled on the host as the reference does, for the vehicle
+    ``params`` (DEFAULT_PARAMS updated by it) and the QP ``limits`` (keywords of ctrl_build_qp: vx_min / delta_max / a_max /
+    a_min_abs; of plan_build_qp: xmin / xmax / umin / umax).  A controller u_old with more than two columns is the device's
+    layout of a handle with steeringDelay = d, [OldSteering[0], OldAccelera[0], OldSteering[1..d]]: the QP then carries
+    the d pinned-steering rows (CTRL:518-527)."""
+    from . import lpv_ref as L
+    p = dict(L.DEFAULT_PARAMS)
+    if params:
+        p.update(params)
+    N = int(w["N"])
+    lim = dict(limits or {})
+    if kind == "controller":
+        S, A, B = L.ctrl_lpv_prediction(p, w["dt"], N, w["track"], w["x0"][j], w["u_prev"][j], w["vel_ref"][j],
+                                        None if w["curv_s"] is None else w["curv_s"][j], w["cf_new"], w["lap"])
+        u_old = np.asarray(w["u_old"][j], float).reshape(-1)
+        return L.ctrl_build_qp(w["Q"], w["R"], w["dR"], N, A, B, w["x0"][j], u_old[:2], w["vel_ref"][j], p["max_vel"],
+                               steer_hist=u_old[2:], **lim)
+    S, A, B = L.plan_lpv_prediction(p, w["dt"], N, w["track"], w["x0"][j], w["curv_s"][j], w["u_prev"][j])
+    mey = float(np.broadcast_to(w["max_ey"], (np.asarray(w["x0"]).shape[0],))[j])
+    return L.plan_build_qp(w["Q"], w["R"], w["dR"], w["L_cf"], N, A, B, w["x0"][j], w["u_old"][j], mey, p["max_vel"],
+                           p["min_vel"], **lim)
+
+
+def tick_batch_qp(w, kind, settings=None, params=None, limits=None, nthreads=16, qps=None):
+    """One tick of a batch, instance by instance: the LPV roll-out and the reference's QP (instance_qp: vehicle ``params``,
+    QP ``limits``) solved by the OSQP restatement under ``settings`` (a BatchedSolver settings dict, see osqp_settings).
+    ``kind`` "controller" (``u_old`` (B, 2 + d): d = steeringDelay pinned-steering rows) or "planner".  Elimination order:
+    the stage-wise one of the C ticks (ctrl_delay_ordering, plan_ordering): at default arguments the statuses and iteration
+    counts equal ctrl_tick_batch / plan_tick_batch's; the solutions differ by the round-off of the C ticks' own LPV / QP assembly
+    (polished within 1e-10, tests/test_settings_host.py).  Returns dict(xPred, uPred, status, iters, polish, z, y); ``nthreads``
+    (<= 16) solves run at a time (the solver releases the GIL).  ``qps``: the instances' QPs (a list of instance_qp results
+    or None entries for a roll-out that left the track) when the caller solves the same batch under several settings."""
+    from concurrent.futures import ThreadPoolExecutor
+    N = int(w["N"])
+    x0 = np.asarray(w["x0"], np.float64); B = x0.shape[0]
+    ctrl = kind == "controller"
+    nx = 6 if ctrl else 5
+    nz = (N + 1) * nx + N * 2
+    if ctrl:
+        d = np.asarray(w["u_old"], np.float64).reshape(B, -1).shape[1] - 2
+        perm, m = ctrl_delay_ordering(N, d), 6 * N + (N + 1) * 6 + d
+    else:
+        perm, m = plan_ordering(N), (N + 1) * nx + nz
+    kw = osqp_settings(settings)
+
+    def one(j):
+        # no answer (NaN, UNSOLVED -10): a roll-out that leaves the track table (the reference raises, UTIL:44-48) or a KKT
+        # factorisation that breaks down
+        try:
+            qp = instance_qp(w, kind, j, params, limits) if qps is None else qps[j]
+            if qp is None:
+                raise ValueError("no QP")
+            r = solve_qp(qp.P, qp.q, qp.A, qp.l, qp.u, perm=perm, **kw)
+        except (ValueError, RuntimeError):
+            return np.full(nz, np.nan), np.full(m, np.nan), -10, 0, 0
+        return r.x, r.y, r.info.status_val, r.info.iter, r.info.status_polish
+
+    with ThreadPoolExecutor(max_workers=max(1, min(16, int(nthreads)))) as ex:
+        res = list(ex.map(one, range(B)))
+    z = np.array([r[0] for r in res]).reshape(B, nz)
+    return dict(xPred=z[:, :(N + 1) * nx].reshape(B, N + 1, nx).copy(), uPred=z[:, (N + 1) * nx:].reshape(B, N, 2).copy(), z=z,
+                y=np.array([r[1] for r in res]).reshape(B, m), status=np.array([r[2] for r in res], np.int32).reshape(B),
+                iters=np.array([r[3] for r in res], np.int32).reshape(B), polish=np.array([r[4] for r in res], np.int32).reshape(B))
+
+
 def ctrl_tick_batch_delay(w, nthreads=1, params=None):
     """Controller tick with steeringDelay = d = u_old.shape[1] - 2 for a batch: per instance the LPV roll-out
     (lpv_ref.ctrl_lpv_prediction), the reference's QP with d pinned-steering rows (lpv_ref.ctrl_build_qp, CTRL:518-527) and
@@ -188,40 +284,8 @@ def ctrl_tick_batch_delay(w, nthreads=1, params=None):
     ctrl_delay_ordering (the C tick's order at d = 0); on tests/golden/ctrl_n20_delay.npz it reproduces the reference's
     status, iteration count and polish flag of every case (as does solve_qp's RCM order, which the class-D rule of
     tests/_tolerance.py takes as the other order).  Returns dict(xPred, uPred, status, iters, z, y, polish); ``nthreads``
-    solves run at a time (the solver releases the GIL)."""
-    from concurrent.futures import ThreadPoolExecutor
-    from . import lpv_ref as L
-    p = dict(L.DEFAULT_PARAMS)
-    if params:
-        p.update(params)
-    N = int(w["N"])
-    x0 = np.asarray(w["x0"], np.float64); B = x0.shape[0]
-    u_old = np.asarray(w["u_old"], np.float64).reshape(B, -1)
-    d = u_old.shape[1] - 2
-    perm = ctrl_delay_ordering(N, d)
-    curv = w["curv_s"]
-    nz, m = (N + 1) * 6 + N * 2, 6 * N + (N + 1) * 6 + d
-
-    def one(j):
-        # no answer (NaN, UNSOLVED -10): a roll-out that leaves the track table (the reference raises, UTIL:44-48) or a KKT
-        # factorisation that breaks down
-        try:
-            S, A, Bm = L.ctrl_lpv_prediction(p, w["dt"], N, w["track"], x0[j], w["u_prev"][j], w["vel_ref"][j],
-                                             None if curv is None else curv[j], w["cf_new"], w["lap"])
-            qp = L.ctrl_build_qp(w["Q"], w["R"], w["dR"], N, A, Bm, x0[j], u_old[j, :2], w["vel_ref"][j], p["max_vel"],
-                                 steer_hist=u_old[j, 2:])
-            r = solve_qp(qp.P, qp.q, qp.A, qp.l, qp.u, perm=perm)
-        except (ValueError, RuntimeError):
-            return np.full(nz, np.nan), np.full(m, np.nan), -10, 0, 0
-        return r.x, r.y, r.info.status_val, r.info.iter, r.info.status_polish
-
-    with ThreadPoolExecutor(max_workers=max(1, min(16, int(nthreads)))) as ex:
-        res = list(ex.map(one, range(B)))
-    z = np.array([r[0] for r in res]).reshape(B, nz)
-    out = dict(xPred=z[:, :(N + 1) * 6].reshape(B, N + 1, 6).copy(), uPred=z[:, (N + 1) * 6:].reshape(B, N, 2).copy(), z=z,
-               y=np.array([r[1] for r in res]).reshape(B, m), status=np.array([r[2] for r in res], np.int32).reshape(B),
-               iters=np.array([r[3] for r in res], np.int32).reshape(B), polish=np.array([r[4] for r in res], np.int32).reshape(B))
-    return out
+    solves run at a time (the solver releases the GIL).  tick_batch_qp at default settings and limits."""
+    return tick_batch_qp(w, "controller", params=params, nthreads=nthreads)
 
 
 def plan_tick_batch(w, nthreads=1, params=None):

@@ -12,8 +12,12 @@ from oracle import cascade_ref as CR, lpv_ref as L, osqp_ref, plant_ref as PR
 
 class RaceRef:
     def __init__(self, track, plant0, half_track0=None, laps=1, N=20, dt=1.0 / 30, half_width=0.2, slack=0.15, plan_max_ey=0.2,
-                 n_sub_lap0=7, n_sub=(7, 7, 6)):
+                 n_sub_lap0=7, n_sub=(7, 7, 6), params=None):
+        """``params``: the vehicle (DEFAULT_PARAMS updated by it) of the lap-0 and event ticks' LPV, QP and plant steps.  The
+        racing ticks (CascadeRef) know the default vehicle only: a vehicle of another kind reaching its lap event raises."""
         from lpvmpc import workloads as W
+        self.p = dict(L.DEFAULT_PARAMS, **(params or {}))
+        self.sim_p = dict(PR.SIM_PARAMS, **{k: self.p[k] for k in ("lf", "lr", "m", "Iz")})
         self.track = np.asarray(track, float)
         self.TL = float(self.track[-1, 3] + self.track[-1, 4])
         self.plant = np.array(plant0, float).reshape(-1, 8)
@@ -35,7 +39,7 @@ class RaceRef:
         self.t = 0
 
     def _solve_path(self, b, x_meas, seed):
-        p, N = L.DEFAULT_PARAMS, self.N
+        p, N = self.p, self.N
         Q, R, dR = self.path_tuning
         if seed:
             xx, uu = L.ctrl_seed_vectors(x_meas)
@@ -50,7 +54,7 @@ class RaceRef:
         return u, r.info.iter, r.info.status_val
 
     def _solve_tt_event(self, b, x_meas):
-        p, N = L.DEFAULT_PARAMS, self.N
+        p, N = self.p, self.N
         Q, R, dR = self.tt_tuning
         S, A, Bm = L.ctrl_lpv_prediction(p, self.dt, N, self.track, x_meas, self.uPred_path[b], np.ones(N + 1), np.zeros(N), 60.0, 1)
         qp = L.ctrl_build_qp(Q, R, dR, N, A, Bm, x_meas, self.cmd[b], np.ones(N + 1), p["max_vel"])
@@ -85,6 +89,8 @@ class RaceRef:
             if s >= 3 * self.TL / 4:
                 self.half[b] = 1
             event = self.half[b] == 1 and s <= self.TL / 4
+            if event and self.p != L.DEFAULT_PARAMS:
+                raise NotImplementedError("RaceRef: the racing ticks (CascadeRef) replay the default vehicle only")
             if event and not seed:
                 u, it, stt = self._solve_tt_event(b, Lc)
             else:
@@ -93,7 +99,7 @@ class RaceRef:
             self.iters[b], self.status[b] = it, stt
             self.cmd[b] = u[0]
             for _ in range(self.n_sub_lap0):
-                st = PR.simulator_f(st, [self.cmd[b, 1], self.cmd[b, 0]])
+                st = PR.simulator_f(st, [self.cmd[b, 1], self.cmd[b, 0]], self.sim_p)
             self.plant[b] = st
             if event:
                 self.half[b] = 0; self.lap[b] = 1; self.phase[b] = 1; self.event_tick[b] = self.t

@@ -40,34 +40,26 @@ NO_SOLUTION = (-3, 3, -4, 4)        # primal / dual infeasible, exact or inaccur
 CLASS_C_DU = 2e-2                   # (round 6: 5e-2 -> 2e-2; observed <= 1.01e-2)
 
 
-def class_d(w, kind, j, out, ref):
+def class_d(w, kind, j, out, ref, settings=None, params=None, limits=None):
     """Class D: an infeasible QP whose certificate fires one check apart.  True iff statuses are equal, neither side returns a
-    solution and the device's iteration count is the oracle's under its OTHER elimination order (solve_qp: RCM) of the same data."""
+    solution and the device's iteration count is the oracle's under its OTHER elimination order (solve_qp: RCM) of the same data,
+    solved under the same settings."""
     from oracle import osqp_ref as O
     st, sr = int(out["status"][j]), int(ref["status"][j])
     if st != sr or st not in NO_SOLUTION:
         return False
     if np.isfinite(out["uPred"][j]).any() or np.isfinite(ref["uPred"][j]).any():
         return False
-    qp = instance_qp(w, kind, j)
-    r = O.solve_qp(qp.P, qp.q, qp.A, qp.l, qp.u)
+    qp = instance_qp(w, kind, j, params, limits)
+    r = O.solve_qp(qp.P, qp.q, qp.A, qp.l, qp.u, **O.osqp_settings(settings))
     return r.info.status_val == st and int(r.info.iter) == int(out["iters"][j])
 
 
-def instance_qp(w, kind, j):
-    """(P, q, A, l, u) of instance j of a workload dict, assembled on the host as the reference does.  A controller u_old with
-    more than two columns is the device's layout of a handle with steeringDelay = d, [OldSteering[0], OldAccelera[0],
-    OldSteering[1..d]]: the QP then carries the d pinned-steering rows (CTRL:518-527)."""
-    N = int(w["N"]); p = dict(P)
-    if kind == "controller":
-        S, A, B = L.ctrl_lpv_prediction(p, w["dt"], N, w["track"], w["x0"][j], w["u_prev"][j], w["vel_ref"][j],
-                                        None if w["curv_s"] is None else w["curv_s"][j], w["cf_new"], w["lap"])
-        u_old = np.asarray(w["u_old"][j], float).reshape(-1)
-        return L.ctrl_build_qp(w["Q"], w["R"], w["dR"], N, A, B, w["x0"][j], u_old[:2], w["vel_ref"][j], p["max_vel"],
-                               steer_hist=u_old[2:])
-    S, A, B = L.plan_lpv_prediction(p, w["dt"], N, w["track"], w["x0"][j], w["curv_s"][j], w["u_prev"][j])
-    mey = float(np.broadcast_to(w["max_ey"], (w["x0"].shape[0],))[j])
-    return L.plan_build_qp(w["Q"], w["R"], w["dR"], w["L_cf"], N, A, B, w["x0"][j], w["u_old"][j], mey, p["max_vel"], p["min_vel"])
+def instance_qp(w, kind, j, params=None, limits=None):
+    """(P, q, A, l, u) of instance j of a workload dict, assembled on the host as the reference does (oracle/osqp_ref.py
+    instance_qp: vehicle ``params``, QP ``limits``)."""
+    from oracle import osqp_ref as O
+    return O.instance_qp(w, kind, j, params, limits)
 
 
 def primal_residual(qp, z, eps=1e-3):
@@ -84,19 +76,19 @@ def objective(qp, z):
     return float(0.5 * z @ Pm @ z + np.asarray(qp.q, float) @ z)
 
 
-def outlier_report(w, kind, j, out, ref):
+def outlier_report(w, kind, j, out, ref, settings=None, params=None, limits=None):
     """Class-C evidence for instance j: a dict with the fields the sweep prints and `class` in {"C", "FAIL: ..."}."""
     st, st_ref = int(out["status"][j]), int(ref["status"][j])
     pol = int(out["polish"][j]) if "polish" in out else 0
     du = float(np.max(np.abs(out["uPred"][j] - ref["uPred"][j])))
-    qp = instance_qp(w, kind, j)
+    qp = instance_qp(w, kind, j, params, limits)
     zd = np.concatenate([out["xPred"][j].reshape(-1), out["uPred"][j].reshape(-1)])
     zr = np.concatenate([ref["xPred"][j].reshape(-1), ref["uPred"][j].reshape(-1)])
     fd, fr = objective(qp, zd), objective(qp, zr)
     gap = abs(fd - fr) / max(1.0, abs(fr))
     pri, tol = primal_residual(qp, zd)
     pri_ref, _ = primal_residual(qp, zr)
-    capped = int(out["iters"][j]) == int(ref["iters"][j]) == int(w.get("max_iter", 4000))
+    capped = int(out["iters"][j]) == int(ref["iters"][j]) == int((settings or {}).get("max_iter", w.get("max_iter", 4000)))
     why = []
     if not ({st, st_ref} <= {SOLVED_INACC, MAX_ITER}):
         why.append("status (only runs that end at the cap may differ beyond class B)")
@@ -109,8 +101,10 @@ def outlier_report(w, kind, j, out, ref):
                 pri=pri, pri_tol=lim, pri_ref=pri_ref, **{"class": "C" if not why else "FAIL: " + ", ".join(why)})
 
 
-def check_batch(w, kind, out, ref, allow_status_flip_at_max_iter=True):
-    """The whole rule set on a batch; returns counts per class and raises AssertionError on the first violation."""
+def check_batch(w, kind, out, ref, allow_status_flip_at_max_iter=True, settings=None, params=None, limits=None):
+    """The whole rule set on a batch; returns counts per class and raises AssertionError on the first violation.  ``settings``,
+    ``params`` and ``limits``: those of the handle (BatchedSolver settings, vehicle parameters, QP limits as for
+    oracle/osqp_ref.py tick_batch_qp), for the host's own solves of classes C and D."""
     sane = (ref["status"] != -10) & ~(np.isnan(ref["uPred"]).any(axis=(1, 2)) & (ref["status"] == 1))
     counts = dict(A=0, B=0, C=0, D=0, no_solution=0, flips=0)
     for j in np.nonzero(sane)[0]:
@@ -119,7 +113,7 @@ def check_batch(w, kind, out, ref, allow_status_flip_at_max_iter=True):
             assert allow_status_flip_at_max_iter and {st, sr} <= {SOLVED_INACC, MAX_ITER} and int(out["iters"][j]) == int(ref["iters"][j]), (int(j), st, sr)
             counts["flips"] += 1
         if int(out["iters"][j]) != int(ref["iters"][j]):
-            assert class_d(w, kind, int(j), out, ref), (int(j), st, sr, int(out["iters"][j]), int(ref["iters"][j]))
+            assert class_d(w, kind, int(j), out, ref, settings, params, limits), (int(j), st, sr, int(out["iters"][j]), int(ref["iters"][j]))
             counts["D"] += 1
         fo, fr = np.isfinite(out["uPred"][j]).all(), np.isfinite(ref["uPred"][j]).all()
         assert fo == fr, (int(j), "finite", fo, fr)
@@ -133,7 +127,7 @@ def check_batch(w, kind, out, ref, allow_status_flip_at_max_iter=True):
         elif not polished and d <= 2e-4:
             counts["B"] += 1
         else:
-            r = outlier_report(w, kind, int(j), out, ref)
+            r = outlier_report(w, kind, int(j), out, ref, settings, params, limits)
             assert r["class"] == "C", (int(j), r)
             counts["C"] += 1
     return counts

@@ -14,7 +14,7 @@ Captured (all float64):
   * oracle solutions with their KKT-certified optimum            -> solution pins
 Nothing of the reference's source text is stored: only inputs and numeric outputs.
 
-Usage:  python tests/golden/make_golden.py [--out DIR] [handoff | delay]   (needs /root/reference; NOT run on the GPU box)
+Usage:  python tests/golden/make_golden.py [--out DIR] [handoff | delay | params]   (needs /root/reference; NOT run on the GPU box)
 
 Every file written is also entered in MANIFEST.json (its keys, with shape and dtype): tests/test_oracle_golden.py fails when a
 committed fixture's key set differs from what this generator writes.
@@ -399,6 +399,53 @@ def gen_handoff(CTRL, PLAN, TRACK, UTIL):
     print("wrote cascade.npz")
 
 
+VEHICLE = {"lf": 0.14, "lr": 0.11, "m": 2.3, "Iz": 0.04, "Cf": 65.0, "Cr": 52.0, "mu": 0.07}
+
+
+def gen_params(CTRL, PLAN, TRACK, UTIL):
+    """params.npz: the reference's classes built with an asymmetric vehicle (VEHICLE), so that a swap of lf / lr or Cf / Cr
+    shows.  Controller LPV roll-out + QP (N = 20, oval), planner LPV + QP (N = 30, L_shape), and a Simulator.f trajectory;
+    the simulator reads lf, lr, m, Iz and its own simulator/mu (set to the vehicle's mu here), its tyres are fixed at 60."""
+    import vehicleSimulator as SIM
+    PARAMS.update(VEHICLE)
+    PARAMS["simulator/mu"] = VEHICLE["mu"]
+    out = {k: np.array(v) for k, v in VEHICLE.items()}
+    oval = make_map(TRACK, "oval")
+    rng = np.random.default_rng(11)
+    N = 20; dt = 1.0 / 30.0
+    for i in range(6):
+        s = rng.uniform(0, 13); vx = rng.uniform(1.0, 3.0)
+        x0 = np.array([vx, rng.normal(0, 0.05), rng.normal(0, 0.3), rng.normal(0, 0.1), s, rng.normal(0, 0.1)])
+        u_prev = np.column_stack([rng.uniform(-0.2, 0.2, N), rng.normal(0.2, 0.3, N)])     # per-stage steering: every tyre term varies
+        lap = 0 if i % 3 == 2 else 1
+        curv = np.full(N, UTIL.Curvature(s, oval.PointAndTangent))
+        c = ctrl_case(CTRL, oval, "race" if i % 2 == 0 else "path", N, dt, x0, u_prev, np.full(N + 1, vx), curv, lap, u_prev[0])
+        for k in ("x0", "u_prev", "vel_ref", "curv_ref", "lap", "old_u", "cf_new", "Q", "R", "dR", "states", "A", "B", "P", "q",
+                  "Aqp", "l", "u"):
+            out["ctrl%d_%s" % (i, k)] = np.asarray(c[k])
+    lsh = make_map(TRACK, "L_shape")
+    N = 30; dtp = 0.05
+    for i in range(4):
+        vx = rng.uniform(1, 4)
+        x0 = np.array([vx, rng.normal(0, 0.03), rng.normal(0, 0.2), rng.normal(0, 0.05), rng.normal(0, 0.05)])
+        SS = rng.uniform(0, 19.2) + np.arange(N + 1) * vx * dtp
+        u_prev = np.column_stack([rng.uniform(-0.2, 0.2, N), rng.normal(0.2, 0.2, N)])
+        c = plan_case(PLAN, lsh, N, dtp, x0, SS, u_prev, 0.2)
+        for k in ("x0", "SS", "u_prev", "max_ey", "states", "A", "B", "P", "q", "Aqp", "l", "u"):
+            out["plan%d_%s" % (i, k)] = np.asarray(c[k])
+    sim = SIM.Simulator()
+    sim.vx = 1.5
+    init = np.array([sim.x, sim.y, sim.vx, sim.vy, sim.ax, sim.ay, sim.yaw, sim.psiDot], float)
+    useq = np.column_stack([rng.uniform(-1.0, 2.0, 200), rng.uniform(-0.25, 0.25, 200)])     # [a, delta]
+    sts = []
+    for u_ in useq:
+        sim.f([float(u_[0]), float(u_[1])])
+        sts.append([sim.x, sim.y, sim.vx, sim.vy, sim.ax, sim.ay, sim.yaw, sim.psiDot])
+    out.update(sim_init=init, sim_u=useq, sim_states=np.array(sts), sim_dt=np.array(sim.dt), sim_mu=np.array(sim.mu))
+    save_npz("params.npz", out)
+    print("wrote params.npz")
+
+
 def main():
     global OUT
     warnings.simplefilter("ignore")
@@ -435,6 +482,9 @@ def generate(CTRL, PLAN, TRACK, UTIL):
                 cases.append(ctrl_case(CTRL, oval, "race" if i % 2 == 0 else "path", N, dt, x0, u_prev, np.full(N + 1, vx), curv,
                                        0 if i % 4 == 3 else 1, u_prev[0], steer_hist=hist))
             save_cases("ctrl_n20_delay", cases)
+            return
+        if "params" in sys.argv[1:]:                        # only params.npz: an asymmetric vehicle (lf != lr, Cf != Cr)
+            gen_params(CTRL, PLAN, TRACK, UTIL)
             return
         # ---------------- track tables + curvature samples ----------------
         tracks = {}

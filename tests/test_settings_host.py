@@ -1,0 +1,216 @@
+"""CPU: what a user configures, on the host side.
+
+  * lpvmpc_create refuses the settings OSQP 0.6 refuses (LPVMPC_E_ARG; the argument checks run before the device probe).
+  * The oracle pinned to the reference away from its symmetric vehicle (tests/golden/params.npz: lf != lr, Cf != Cr): the LPV
+    roll-outs, the QPs and Simulator.f, at the golden tolerance 1e-12.
+  * oracle/osqp_ref.py tick_batch_qp (the per-instance batch oracle that takes settings, vehicle and limits) at default arguments
+    reproduces the C ticks' statuses, iteration counts and polish decisions; its limit keywords change the QP rows they name."""
+import numpy as np
+import pytest
+
+from oracle import lpv_ref as L, osqp_ref as O, plant_ref as PR
+from tests import _tolerance as T
+from tests import test_gpu_settings as G
+from tests._golden import load
+
+TOL = 1e-12
+
+
+def close(a, b, tol=TOL):
+    a = np.asarray(a, float); b = np.asarray(b, float)
+    assert a.shape == b.shape, (a.shape, b.shape)
+    fin = np.isfinite(b)
+    assert np.array_equal(np.isfinite(a), fin)
+    scale = max(1.0, float(np.max(np.abs(b[fin]), initial=0.0)))
+    assert float(np.max(np.abs(a[fin] - b[fin]), initial=0.0)) <= tol * scale
+
+
+# ---- refusals ----------------------------------------------------------------------------------------------------------------
+REFUSED = [dict(eps_abs=-1e-3), dict(eps_rel=-1e-3), dict(eps_abs=0.0, eps_rel=0.0), dict(eps_prim_inf=0.0), dict(eps_prim_inf=-1e-4),
+           dict(eps_dual_inf=0.0), dict(max_iter=0), dict(max_iter=-5), dict(scaling=-1), dict(polish_refine_iter=-1),
+           dict(check_termination=-1), dict(adaptive_rho_interval=-1), dict(adaptive_rho_tolerance=0.999),
+           dict(adaptive_rho_tolerance=float("nan")), dict(eps_abs=float("nan"))]
+
+
+@pytest.mark.parametrize("kind", ["controller", "planner"])
+@pytest.mark.parametrize("bad", REFUSED, ids=lambda d: ",".join("%s=%g" % kv for kv in d.items()))
+def test_create_refuses_what_osqp_refuses(kind, bad):
+    import lpvmpc
+    from lpvmpc import _ffi
+    nx = 6 if kind == "controller" else 5
+    with pytest.raises(lpvmpc.LpvMpcError) as e:
+        lpvmpc.BatchedSolver(kind, 20, 0.05, np.eye(nx), np.eye(2), np.ones(2), L_cf=np.zeros(5) if nx == 5 else None, **bad)
+    assert e.value.code == _ffi.E_ARG, str(e.value)
+    assert "lpvmpc_create" in str(e.value)
+
+
+def test_boundary_settings_are_accepted_by_the_argument_checks():
+    """The edges OSQP accepts pass the argument checks (one of eps_abs / eps_rel 0, zero counts, tolerance 1): without a device
+    the failure is then the missing device, with one the handle is created."""
+    import lpvmpc
+    from lpvmpc import _ffi
+    for ok in (dict(eps_abs=0.0), dict(eps_rel=0.0), dict(scaling=0, polish_refine_iter=0, check_termination=0, adaptive_rho_interval=0),
+               dict(adaptive_rho_tolerance=1.0), dict(max_iter=1)):
+        try:
+            lpvmpc.BatchedSolver("controller", 20, 1 / 30.0, np.eye(6), np.eye(2), np.ones(2), **ok).close()
+        except lpvmpc.LpvMpcError as e:
+            assert e.code == _ffi.E_NODEVICE, (ok, str(e))
+
+
+def test_planner_boxes_are_settings():
+    from lpvmpc import _ffi
+    import lpvmpc
+    for k in ("plan_xmin", "plan_xmax", "plan_umin", "plan_umax"):
+        assert k in _ffi.SETTING_FIELDS
+    with pytest.raises(ValueError):
+        lpvmpc.BatchedSolver("planner", 20, 0.05, np.eye(5), np.eye(2), np.ones(2), L_cf=np.zeros(5), plan_umin=[0.1, 0.2, 0.3])
+
+
+# ---- the asymmetric vehicle of params.npz ------------------------------------------------------------------------------------
+def _vehicle(g):
+    p = dict(L.DEFAULT_PARAMS)
+    p.update({k: float(g[k]) for k in ("lf", "lr", "m", "Iz", "Cf", "Cr", "mu")})
+    assert p["lf"] != p["lr"] and p["Cf"] != p["Cr"]
+    return p
+
+
+def test_params_fixture_controller():
+    g = load("params")
+    p = _vehicle(g)
+    tab = L.TrackMap("oval", 0.2).PointAndTangent
+    n = 0
+    while "ctrl%d_x0" % n in g.files:
+        c = {k.split("_", 1)[1]: g[k] for k in g.files if k.startswith("ctrl%d_" % n)}
+        N = c["u_prev"].shape[0]
+        S, A, B = L.ctrl_lpv_prediction(p, 1.0 / 30.0, N, tab, c["x0"], c["u_prev"], c["vel_ref"], c["curv_ref"], float(c["cf_new"]),
+                                        int(c["lap"]))
+        close(S, c["states"]); close(A, c["A"]); close(B, c["B"])
+        qp = L.ctrl_build_qp(c["Q"], c["R"], c["dR"], N, A, B, c["x0"], c["old_u"], c["vel_ref"], p["max_vel"])
+        close(qp.P, c["P"]); close(qp.q, c["q"]); close(qp.A, c["Aqp"]); close(qp.l, c["l"]); close(qp.u, c["u"])
+        n += 1
+    assert n == 6
+
+
+def test_params_fixture_planner():
+    from lpvmpc import workloads as W
+    g = load("params")
+    p = _vehicle(g)
+    tab = L.TrackMap("L_shape", 0.2).PointAndTangent
+    n = 0
+    while "plan%d_x0" % n in g.files:
+        c = {k.split("_", 1)[1]: g[k] for k in g.files if k.startswith("plan%d_" % n)}
+        N = c["u_prev"].shape[0]
+        S, A, B = L.plan_lpv_prediction(p, 0.05, N, tab, c["x0"], c["SS"], c["u_prev"])
+        close(S, c["states"]); close(A, c["A"]); close(B, c["B"])
+        qp = L.plan_build_qp(W.PLAN_Q, W.PLAN_R, W.PLAN_dR, W.PLAN_L, N, A, B, c["x0"], [0.0, 0.0], float(c["max_ey"]), p["max_vel"],
+                             p["min_vel"])
+        close(qp.P, c["P"]); close(qp.q, c["q"]); close(qp.A, c["Aqp"]); close(qp.l, c["l"]); close(qp.u, c["u"])
+        n += 1
+    assert n == 4
+
+
+def test_params_fixture_simulator():
+    g = load("params")
+    p = _vehicle(g)
+    sp = dict(PR.SIM_PARAMS, lf=p["lf"], lr=p["lr"], m=p["m"], Iz=p["Iz"], mu=float(g["sim_mu"]), dt=float(g["sim_dt"]))
+    st = g["sim_init"].copy()
+    for u, ref in zip(g["sim_u"], g["sim_states"]):
+        st = PR.simulator_f(st, u, sp)
+        assert np.max(np.abs(st - ref)) <= TOL * max(1.0, np.max(np.abs(ref)))
+    swapped = dict(sp, lf=sp["lr"], lr=sp["lf"])                # the fixture tells lf from lr
+    st = g["sim_init"].copy()
+    for u in g["sim_u"]:
+        st = PR.simulator_f(st, u, swapped)
+    assert np.max(np.abs(st - g["sim_states"][-1])) > 1e-3
+
+
+# ---- the batch oracle that takes settings ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind,N", [("controller", 8), ("controller", 20), ("planner", 20), ("planner", 30)])
+def test_tick_batch_qp_reproduces_the_c_ticks_at_defaults(kind, N):
+    """Same elimination order as the C ticks: statuses and iteration counts equal.  The C ticks assemble the LPV and QP data in
+    C, which differs from numpy's by round-off: polished solutions within 1e-10, other converged ones within the class-B bar of
+    tests/_tolerance.py (2e-4), iterates at the iteration cap (4000 ADMM iterations amplify that round-off) within class C's."""
+    from lpvmpc import workloads
+    w = workloads.controller_batch(41, N=N, seed=31) if kind == "controller" else workloads.planner_batch(41, N=N, seed=31)
+    a = O.tick_batch_qp(w, kind, nthreads=4)
+    b = O.ctrl_tick_batch(w, nthreads=4) if kind == "controller" else O.plan_tick_batch(w, nthreads=4)
+    assert np.array_equal(a["status"], b["status"]) and np.array_equal(a["iters"], b["iters"])
+    pol = a["polish"] == 1
+    assert pol.sum() >= 10
+    for k in ("xPred", "uPred"):
+        assert np.array_equal(np.isfinite(a[k]), np.isfinite(b[k]))
+        fin = np.isfinite(b[k]).all(axis=tuple(range(1, b[k].ndim)))
+        d = np.max(np.abs(a[k][fin] - b[k][fin]), axis=tuple(range(1, b[k].ndim))) / np.maximum(1.0, np.max(np.abs(b[k][fin]), axis=tuple(range(1, b[k].ndim))))
+        assert float(np.max(d[pol[fin]], initial=0.0)) <= 1e-10, k
+        capped = (a["iters"] == 4000)[fin]
+        assert float(np.max(d[~capped], initial=0.0)) <= 2e-4, k
+        if k == "uPred":                                        # class C bounds |du| only
+            assert float(np.max(d, initial=0.0)) <= T.CLASS_C_DU, k
+    if kind == "controller":
+        c = O.ctrl_tick_batch_delay(w, nthreads=4)
+        for k in ("status", "iters", "polish", "xPred", "uPred"):
+            assert np.array_equal(c[k], a[k], equal_nan=True), k
+
+
+def test_limits_reach_the_rows_they_name():
+    """Default limit keywords give the reference's rows word for word; each non-default one moves its own rows only."""
+    from lpvmpc import workloads
+    w = workloads.controller_batch(1, N=10, seed=3)
+    base = O.instance_qp(w, "controller", 0)
+    same = O.instance_qp(w, "controller", 0, limits=dict(vx_min=0.01, delta_max=0.249, a_max=4.0, a_min_abs=1.0))
+    assert np.array_equal(base.u, same.u) and np.array_equal(base.A, same.A)
+    N = 10
+    for key, val, rows in (("vx_min", 0.3, [2 * k for k in range(N)]), ("delta_max", 0.2, [2 * N + 4 * k + r for k in range(N) for r in (0, 1)]),
+                           ("a_max", 3.0, [2 * N + 4 * k + 2 for k in range(N)]), ("a_min_abs", 0.6, [2 * N + 4 * k + 3 for k in range(N)])):
+        q = O.instance_qp(w, "controller", 0, limits={key: val})
+        changed = np.nonzero(q.u != base.u)[0]
+        assert list(changed) == rows, key
+        assert np.allclose(np.abs(q.u[changed]), val)
+    wp = workloads.planner_batch(1, N=20, seed=3)
+    basep = O.instance_qp(wp, "planner", 0)
+    q = O.instance_qp(wp, "planner", 0, limits=dict(xmin=[0.0, -0.5, -1.5, 0.0, -0.6], xmax=[9.0, 0.5, 1.5, 0.0, 0.6],
+                                                    umin=[-0.2, -0.5], umax=[0.2, 1.5]))
+    assert np.array_equal(q.l[:105], basep.l[:105])             # the dynamics rows
+    box_l, box_u = q.l[105:].reshape(-1), q.u[105:].reshape(-1)
+    st_l = box_l[:21 * 5].reshape(21, 5); st_u = box_u[:21 * 5].reshape(21, 5)
+    assert np.all(st_l[:, 0] == L.DEFAULT_PARAMS["min_vel"]) and np.all(st_u[:, 0] == L.DEFAULT_PARAMS["max_vel"])   # slot 0: min/max_vel
+    assert np.all(st_u[:, 3] == float(wp["max_ey"][0])) and np.all(st_l[:, 3] == -float(wp["max_ey"][0]))           # slot 3: max_ey
+    assert np.all(st_l[:, 1] == -0.5) and np.all(st_u[:, 4] == 0.6)
+    assert np.all(box_l[105:].reshape(-1, 2) == [-0.2, -0.5]) and np.all(box_u[105:].reshape(-1, 2) == [0.2, 1.5])
+
+
+def test_osqp_settings_names():
+    assert O.osqp_settings(dict(polish_delta=1e-8, alpha=1.2, ctrl_vx_min=0.3, plan_umin=[0, 0], steering_delay=2, scaling=3)) == \
+        dict(delta=1e-8, alpha=1.2, scaling=3)
+
+
+# ---- non-vacuity of tests/test_gpu_settings.py, on the oracle side ---------------------------------------------------------------
+# share of the instances (over the GPU module's workloads) whose iteration count or solution words differ from the defaults'
+# (observed: sigma 24 %, the infeasibility tolerances 6 %, every other case 38-100 %; each bar is at most two thirds of the lowest
+# share observed for its cases)
+MIN_SHARE = {"sigma1e-4": 0.1, "inf_p1e-6_d1e-2": 0.025, "inf_p1e-2_d1e-6": 0.025}
+
+
+@pytest.mark.parametrize("case", list(G.SETTINGS))
+def test_each_departure_changes_the_oracle(case):
+    changed = total = 0
+    for name in G.WORKLOADS:
+        a, b = G.oracle(name, None), G.oracle(name, case)
+        diff = (a["iters"] != b["iters"]) | (a["status"] != b["status"]) | \
+            ~np.all((a["z"] == b["z"]) | (np.isnan(a["z"]) & np.isnan(b["z"])), axis=1)
+        changed += int(diff.sum()); total += diff.size
+    share = changed / total
+    print("%s: %d of %d instances differ from the defaults (%.1f %%)" % (case, changed, total, 100 * share))
+    assert share >= MIN_SHARE.get(case, 0.25), (case, share)
+
+
+@pytest.mark.parametrize("a,b", G.SWAPS)
+def test_swapped_pairs_are_told_apart(a, b):
+    """eps_abs / eps_rel and eps_prim_inf / eps_dual_inf swapped change decisions: statuses or iteration counts.  The
+    infeasibility pair shows on the planner workloads' PRIMAL INFEASIBLE instances."""
+    n = 0
+    for name in G.WORKLOADS:
+        ra, rb = G.oracle(name, a), G.oracle(name, b)
+        n += int(np.sum((ra["status"] != rb["status"]) | (ra["iters"] != rb["iters"])))
+    print("%s vs %s: %d instances decide differently" % (a, b, n))
+    assert n >= {"eps_a1e-4_r1e-2": 250}.get(a, 20), n            # (observed: 544 and 42)
