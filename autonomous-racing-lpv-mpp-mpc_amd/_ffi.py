@@ -119,6 +119,9 @@ def lap_stats_dict(f, i, end_tick):
 ACT_MAX_DELAY = 64                       # LPVMPC_ACT_MAX_DELAY
 ACT_WORDS = 2 * ACT_MAX_DELAY + 2        # LPVMPC_ACT_WORDS: [motor ring, servo ring, servo_inp, k] per vehicle
 
+PLANT_WORDS = 7                          # LPVMPC_PLANT_WORDS: [lf, lr, m, Iz, Cf, Cr, mu] per vehicle
+PLANT_WORD_NAMES = ("lf", "lr", "m", "Iz", "Cf", "Cr", "mu")
+
 OBSERVER_AUX = 30 + 36 + 12      # L_gain [6][5], A_obs [6][6], B_obs [6][2] per instance (lpvmpc_observer_step_batch)
 
 EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_destroy", "lpvmpc_last_error", "lpvmpc_last_error_code",
@@ -133,7 +136,8 @@ EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_d
            "lpvmpc_solve_batch_masked", "lpvmpc_race_default_config", "lpvmpc_race_init", "lpvmpc_race_tick", "lpvmpc_race_read",
            "lpvmpc_race_laps", "lpvmpc_race_predictions", "lpvmpc_race_init_observed",
            "lpvmpc_actuator_default_config", "lpvmpc_plant_step_actuated_batch", "lpvmpc_cl_init_actuated", "lpvmpc_race_init_actuated",
-           "lpvmpc_actuator_read", "lpvmpc_race_record", "lpvmpc_race_record_read", "lpvmpc_race_lap_stats")
+           "lpvmpc_actuator_read", "lpvmpc_race_record", "lpvmpc_race_record_read", "lpvmpc_race_lap_stats",
+           "lpvmpc_plant_step_vehicles_batch", "lpvmpc_cl_init_vehicles", "lpvmpc_race_init_vehicles", "lpvmpc_plant_params_read")
 
 _lib = None
 
@@ -254,6 +258,15 @@ def load():
         lib.lpvmpc_race_init_actuated.argtypes = [vp, vp, vp, _i, vp, vp, P(RaceConfig), P(ObserverConfig), P(ActuatorConfig), vp, vp]
         lib.lpvmpc_actuator_read.argtypes = [vp, vp, vp, vp]
         for name in ("lpvmpc_plant_step_actuated_batch", "lpvmpc_cl_init_actuated", "lpvmpc_race_init_actuated", "lpvmpc_actuator_read"):
+            getattr(lib, name).restype = C.c_int
+    except AttributeError:
+        pass
+    try:        # (nor the per-vehicle plant parameters)
+        lib.lpvmpc_plant_step_vehicles_batch.argtypes = [vp, _i, vp, vp, vp, _i, _d, _d, P(ActuatorConfig), vp, vp, vp]
+        lib.lpvmpc_cl_init_vehicles.argtypes = [vp, _i, vp, _d, _d, _i, _i, _d, _d, P(ActuatorConfig), vp, vp, vp]
+        lib.lpvmpc_race_init_vehicles.argtypes = [vp, vp, vp, _i, vp, vp, P(RaceConfig), P(ObserverConfig), P(ActuatorConfig), vp, vp, vp]
+        lib.lpvmpc_plant_params_read.argtypes = [vp, vp]
+        for name in ("lpvmpc_plant_step_vehicles_batch", "lpvmpc_cl_init_vehicles", "lpvmpc_race_init_vehicles", "lpvmpc_plant_params_read"):
             getattr(lib, name).restype = C.c_int
     except AttributeError:
         pass

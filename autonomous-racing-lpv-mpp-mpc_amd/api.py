@@ -288,12 +288,48 @@ class BatchedSolver:
                                                              C.byref(cfg), ptr(la), ptr(ld)))
         return st, act
 
+    def plant_step_vehicles(self, state, u, plant_params=None, act_state=None, n_sub=1, dt_sim=0.005, mu_sim=0.05, actuator=None,
+                            delay_a=None, delay_df=None):
+        """plant_step_actuated with each vehicle's own plant row: plant_params [B, 7] = (lf, lr, m, Iz, Cf, Cr, mu) per vehicle
+        (None: the nominal row of this engine, plant.plant_params; mu_sim is ignored when rows are given).  Returns (state, act_state)."""
+        st = f64(state).reshape(-1, 8).copy(); B = st.shape[0]
+        u = f64(u, (B, 2), "u")
+        rows = _plant_rows(plant_params, B)
+        act = np.zeros((B, _ffi.ACT_WORDS)) if act_state is None else f64(act_state, (B, _ffi.ACT_WORDS), "act_state").copy()
+        cfg = _ffi.default_actuator_config() if actuator is None else _actuator_cfg(actuator)
+        la, ld = _delay_array(delay_a, B, "delay_a"), _delay_array(delay_df, B, "delay_df")
+        self._chk(self._lib.lpvmpc_plant_step_vehicles_batch(self._h, B, ptr(st), ptr(act), ptr(u), int(n_sub), float(dt_sim), float(mu_sim),
+                                                             C.byref(cfg), ptr(la), ptr(ld), ptr(rows)))
+        return st, act
+
+    def plant_params_read(self):
+        """The plant rows [B, 7] of the fleet / race this engine runs, started with ``plant_params`` (lpvmpc_plant_params_read)."""
+        race = getattr(self, "_race", None) is not None
+        B = self._race[0] if race else getattr(self, "_cl_B", 0)
+        out = np.empty((B, _ffi.PLANT_WORDS))
+        self._chk(self._lib.lpvmpc_plant_params_read(self._h, ptr(out)))
+        return out
+
     def cl_init(self, plant0, half_width, slack, q9_swap=True, n_sub=7, dt_sim=0.005, mu_sim=0.05, actuator=None, delay_a=None,
-                delay_df=None):
+                delay_df=None, plant_params=None):
         """Start a lap-0 fleet.  ``actuator`` (an ``actuator.actuator_config`` result, even an all-off one) selects
         lpvmpc_cl_init_actuated: the actuator in the plant, controllers of any steering delay, per-vehicle delays delay_a /
-        delay_df [B] in steps (None: the config's).  Without it the call is lpvmpc_cl_init."""
+        delay_df [B] in steps (None: the config's).  Without it the call is lpvmpc_cl_init.  ``plant_params`` [B, 7] (or
+        "nominal": the nominal rows) selects lpvmpc_cl_init_vehicles: each vehicle's plant steps with its own row (lf, lr, m, Iz,
+        Cf, Cr, mu; mu_sim is then ignored), the actuator all off unless ``actuator`` is given."""
         p0 = f64(plant0).reshape(-1, 8)
+        if plant_params is not None:
+            B = p0.shape[0]
+            rows = None if _is_nominal(plant_params) else _plant_rows(plant_params, B)
+            la, ld = _delay_array(delay_a, B, "delay_a"), _delay_array(delay_df, B, "delay_df")
+            if actuator is None and (la is not None or ld is not None):
+                raise ValueError("per-vehicle delays need an actuator config")
+            self._cl_B = B
+            self._chk(self._lib.lpvmpc_cl_init_vehicles(self._h, B, ptr(p0), float(half_width), float(slack), 1 if q9_swap else 0,
+                                                        int(n_sub), float(dt_sim), float(mu_sim),
+                                                        None if actuator is None else C.byref(_actuator_cfg(actuator)),
+                                                        ptr(la), ptr(ld), ptr(rows)))
+            return
         self._cl_B = p0.shape[0]
         if actuator is None:
             if delay_a is not None or delay_df is not None:
@@ -436,14 +472,17 @@ class BatchedSolver:
         return out
 
     # -- race engine: lap 0, per-vehicle lap events, racing (lpvmpc_race_*) ------------------------------------
-    def race_init(self, tt, planner, plant0, half_track0=None, estimator=None, actuator=None, delay_a=None, delay_df=None, **cfg):
+    def race_init(self, tt, planner, plant0, half_track0=None, estimator=None, actuator=None, delay_a=None, delay_df=None, plant_params=None,
+                  **cfg):
         """Start a race owned by this PATH controller engine, with ``tt`` (racing tuning) and ``planner`` (handoff_setup done).
         plant0 [B,8]; half_track0 [B] (HalfTrack at the start, default 0); ``cfg``: fields of ``lpvmpc_race_config`` (laps,
         n_sub_lap0, n_sub, q9_swap, half_width, slack, plan_max_ey, dt_sim, mu_sim).  ``estimator``: an
         ``observer.observer_config`` result or an ``_ffi.ObserverConfig`` runs the race with the state estimator and the
         simulated sensors in the loop (lpvmpc_race_init_observed; ``observer_read`` then returns its state); None runs it on
         ground truth.  ``actuator`` (an ``actuator.actuator_config`` result, even an all-off one) selects lpvmpc_race_init_actuated:
-        the actuator in the plant, path / tt of the same steering delay, per-vehicle delays delay_a / delay_df [B] in steps."""
+        the actuator in the plant, path / tt of the same steering delay, per-vehicle delays delay_a / delay_df [B] in steps.
+        ``plant_params`` [B, 7] (or "nominal") selects lpvmpc_race_init_vehicles: each vehicle's plant steps with its own row (lf,
+        lr, m, Iz, Cf, Cr, mu; cfg mu_sim is then ignored), with or without ``estimator`` / ``actuator``."""
         p0 = f64(plant0).reshape(-1, 8)
         B = p0.shape[0]
         c = _ffi.default_race_config()
@@ -463,7 +502,16 @@ class BatchedSolver:
         ht = None if half_track0 is None else np.ascontiguousarray(np.broadcast_to(np.asarray(half_track0), (B,)), np.int32)
         if estimator is not None and not isinstance(estimator, _ffi.ObserverConfig):
             raise TypeError("estimator must be an observer.observer_config(...) result or an _ffi.ObserverConfig")
-        if actuator is not None:
+        if plant_params is not None:
+            rows = None if _is_nominal(plant_params) else _plant_rows(plant_params, B)
+            la, ld = _delay_array(delay_a, B, "delay_a"), _delay_array(delay_df, B, "delay_df")
+            if actuator is None and (la is not None or ld is not None):
+                raise ValueError("per-vehicle delays need an actuator config")
+            self._chk(self._lib.lpvmpc_race_init_vehicles(self._h, tt._h, planner._h, B, ptr(p0), ptr(ht), C.byref(c),
+                                                          None if estimator is None else C.byref(estimator),
+                                                          None if actuator is None else C.byref(_actuator_cfg(actuator)), ptr(la), ptr(ld),
+                                                          ptr(rows)))
+        elif actuator is not None:
             la, ld = _delay_array(delay_a, B, "delay_a"), _delay_array(delay_df, B, "delay_df")
             self._chk(self._lib.lpvmpc_race_init_actuated(self._h, tt._h, planner._h, B, ptr(p0), ptr(ht), C.byref(c),
                                                           None if estimator is None else C.byref(estimator), C.byref(_actuator_cfg(actuator)),
@@ -584,6 +632,18 @@ def _delay_array(v, B, name):
     if not np.all(a == np.round(a)):
         raise ValueError("%s must be integer steps" % name)
     return np.ascontiguousarray(a, np.int32)
+
+
+def _is_nominal(v):
+    return isinstance(v, str) and v == "nominal"
+
+
+def _plant_rows(v, B):
+    """Per-vehicle plant rows: None (the nominal rows, chosen by the library), or exactly [B, 7] finite words."""
+    if v is None:
+        return None
+    from .plant import check_plant_params
+    return check_plant_params(v, B)
 
 
 def _actuator_cfg(a):
@@ -888,10 +948,11 @@ class RaceFleet(object):
     ``observer.observer_config(...)`` result runs the race with the state estimator and the simulated sensors in the loop.
     ``actuator``: an ``actuator.actuator_config(...)`` result puts the actuator delays / servo lag in the plant (per-vehicle
     delay_a / delay_df in steps); ``steering_delay``: both controllers' steeringDelay (needs ``actuator``, e.g.
-    actuator.controller_delay(delay_df_s))."""
+    actuator.controller_delay(delay_df_s)).  ``plant_params``: [B, 7] rows (lf, lr, m, Iz, Cf, Cr, mu) give every vehicle its own
+    plant (plant.sample_plant_params for a mismatch sweep); the controllers and the planner keep the nominal model."""
 
     def __init__(self, track_map, plant0, laps=1, N=20, Np=40, half_track0=None, device=0, estimator=None, actuator=None,
-                 steering_delay=0, delay_a=None, delay_df=None, **options):
+                 steering_delay=0, delay_a=None, delay_df=None, plant_params=None, **options):
         from .workloads import CTRL_TUNINGS, PLAN_L, PLAN_Q, PLAN_R, PLAN_dR
         race_keys = ("n_sub_lap0", "n_sub", "q9_swap", "plan_max_ey", "dt_sim", "mu_sim")
         race_opts = {k: v for k, v in options.items() if k in race_keys}
@@ -910,7 +971,7 @@ class RaceFleet(object):
         self.dt_sim = float(race_opts.get("dt_sim", 0.005))
         self.path.race_init(self.tt, self.planner, plant0, half_track0=half_track0, laps=laps, half_width=track_map.halfWidth,
                             slack=track_map.slack, estimator=estimator, actuator=actuator, delay_a=delay_a, delay_df=delay_df,
-                            **race_opts)
+                            plant_params=plant_params, **race_opts)
 
     def run(self, n_ticks):
         """Enqueue n_ticks controller ticks (no synchronisation)."""
@@ -927,6 +988,10 @@ class RaceFleet(object):
     def actuator(self):
         """Of a race started with ``actuator``: act_state and the path / tt controllers' u_old histories (BatchedSolver.actuator_read)."""
         return self.path.actuator_read()
+
+    def plant_params(self):
+        """The vehicles' plant rows [B, 7] of a race started with ``plant_params`` (BatchedSolver.plant_params_read)."""
+        return self.path.plant_params_read()
 
     def lap_times(self):
         """[B, laps+1] simulated seconds of lap 0, 1, ..., laps (NaN where the lap has not been completed)."""

@@ -5,7 +5,13 @@
 // where the plain form writes the last command.  Its estimator kernels feed the observer the COMMANDED input (it subscribes to `ecu`,
 // stateEstimator.py:785) and the plant the actuator stage's output.  The plain forms take (and ignore) sd and ActDev.
 //
-// One instantiation per translation unit: the .hip files above instantiate <false> only, actuator.hip <true> only.  With both
+// Five of them -- the kernels that step the plant -- have a per-vehicle form (kVeh = true, always with kAct = true): their plant
+// argument is the fleet's table of per-vehicle parameters (VehPlantCfg, PlantArg<kVeh>) instead of one PlantCfg, and each simulator
+// step reads the vehicle's row (plant_step_at, track_geometry.hpp).  kVeh defaults to false, so the plain and delayed forms keep
+// their code.
+//
+// One instantiation per translation unit: the .hip files above instantiate <false> only, actuator.hip <true> only, plant_params.hip
+// <true, true> only.  With both
 // forms of a kernel in one translation unit LLVM compiles the plain form differently (other registers, other instructions); with
 // one per translation unit each form compiles to the code it has alone (docs/HISTORY.md, "Fleet kernels as templates").
 // tests/test_fleet_kernel_instances.py guards the rule.
@@ -17,8 +23,9 @@
 namespace lpvmpc {
 
 // n_sub simulator steps under u = [motor, servo] per vehicle (lpvmpc_plant_step_batch / _actuated_batch)
-template <bool kAct>
-__global__ void __launch_bounds__(64) plant_kernel(int B, double *__restrict__ plant, const double *__restrict__ u, PlantCfg pc, ActDev a) {
+template <bool kAct, bool kVeh = false>
+__global__ void __launch_bounds__(64) plant_kernel(int B, double *__restrict__ plant, const double *__restrict__ u, PlantArg<kVeh> pc, ActDev a) {
+    static_assert(kAct || !kVeh, "the per-vehicle forms are delayed forms");
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     double st[8];
@@ -31,7 +38,7 @@ __global__ void __launch_bounds__(64) plant_kernel(int B, double *__restrict__ p
         for (int k = 0; k < pc.n_sub; ++k) {
             double ua, ud;
             act_stage(a, b, k0 + k, La, Ld, motor, servo, sv, ua, ud);
-            plant_step(pc, st, ua, ud);
+            plant_step_at(pc, b, st, ua, ud);
         }
         a.k[b] = k0 + pc.n_sub; a.servo[b] = sv;
     } else {
@@ -60,11 +67,12 @@ __global__ void __launch_bounds__(64) cl_measure_kernel(const DevCfg *__restrict
 // command = first predicted input (CMAIN:381-386: servo = uPred[0,0], motor = uPred[0,1]), n_sub simulator steps under it
 // (u = [motor, servo], vehicleSimulator.py:330), then the NEXT tick's measurement (cl_measure_kernel on the state just advanced):
 // one launch less per control tick; the measurement goes to its own buffer, the previous tick's local state stays readable
-template <bool kAct>
+template <bool kAct, bool kVeh = false>
 __global__ void __launch_bounds__(64) cl_command_plant_measure_kernel(const DevCfg *__restrict__ cp, int B, int N, const double *__restrict__ uPred,
-                                                                      double *__restrict__ cmd, double *__restrict__ plant, PlantCfg pc,
+                                                                      double *__restrict__ cmd, double *__restrict__ plant, PlantArg<kVeh> pc,
                                                                       double hw, double slack, int q9_swap, double *__restrict__ local_next,
                                                                       double *__restrict__ u_old, int sd, ActDev a) {
+    static_assert(kAct || !kVeh, "the per-vehicle forms are delayed forms");
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const double servo = uPred[(size_t)b * N * 2 + 0], motor = uPred[(size_t)b * N * 2 + 1];
@@ -78,7 +86,7 @@ __global__ void __launch_bounds__(64) cl_command_plant_measure_kernel(const DevC
         for (int k = 0; k < pc.n_sub; ++k) {
             double ua, ud;
             act_stage(a, b, k0 + k, La, Ld, motor, servo, sv, ua, ud);
-            plant_step(pc, st, ua, ud);
+            plant_step_at(pc, b, st, ua, ud);
         }
         a.k[b] = k0 + pc.n_sub; a.servo[b] = sv;
     } else {
@@ -106,12 +114,13 @@ __global__ void __launch_bounds__(64) cl_command_plant_measure_kernel(const DevC
 // tick of a fleet; one kernel keeps local_position at a single call site, inlined).  mode 2 (the cascade, plain form only):
 // advance, then write the estimate in the plant's layout [x y vx vy 0 0 yaw psiDot] to local_next [B][8], which the cascade's
 // measurement kernels read in place of the plant; u_old is left to them
-template <bool kAct>
+template <bool kAct, bool kVeh = false>
 __global__ void __launch_bounds__(64) cl_command_plant_observe_kernel(const DevCfg *__restrict__ cp, int B, int N, const double *__restrict__ uPred,
-                                                                      double *__restrict__ cmd, double *__restrict__ plant, PlantCfg pc,
+                                                                      double *__restrict__ cmd, double *__restrict__ plant, PlantArg<kVeh> pc,
                                                                       double hw, double slack, int q9_swap, double *__restrict__ local_next,
                                                                       double *__restrict__ u_old, const double *__restrict__ gains,
                                                                       double *__restrict__ obs, ObsParams op, int mode, int sd, ActDev a) {
+    static_assert(kAct || !kVeh, "the per-vehicle forms are delayed forms");
     __shared__ double G[kObsGainWords];
     if (mode != 0) obs_stage_gains(G, gains);
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -137,7 +146,7 @@ __global__ void __launch_bounds__(64) cl_command_plant_observe_kernel(const DevC
                 asm volatile("" ::: "memory");
                 double ua, ud;
                 act_stage(a, b, k0 + k, La, Ld, motor, servo, sv, ua, ud);
-                plant_step(pc, st, ua, ud);
+                plant_step_at(pc, b, st, ua, ud);
             } else {
                 plant_step(pc, st, motor, servo);
             }
@@ -229,8 +238,9 @@ __global__ void __launch_bounds__(64) race_measure_kernel(const DevCfg *__restri
 
 // last launch of a tick: the solve's report, the command of the vehicle's controller and its simulator steps.  A frozen vehicle
 // (nstep 0) advances neither plant nor actuator
-template <bool kAct>
-__global__ void __launch_bounds__(64) race_command_plant_kernel(RaceDev r, PlantCfg pc, ActDev a) {
+template <bool kAct, bool kVeh = false>
+__global__ void __launch_bounds__(64) race_command_plant_kernel(RaceDev r, PlantArg<kVeh> pc, ActDev a) {
+    static_assert(kAct || !kVeh, "the per-vehicle forms are delayed forms");
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= r.B) return;
     const int src = r.src[b], n = r.nstep[b], N = r.N;
@@ -250,7 +260,7 @@ __global__ void __launch_bounds__(64) race_command_plant_kernel(RaceDev r, Plant
         for (int k = 0; k < n; ++k) {
             double ua, ud;
             act_stage(a, b, k0 + k, La, Ld, motor, servo, sv, ua, ud);
-            plant_step(pc, st, ua, ud);
+            plant_step_at(pc, b, st, ua, ud);
         }
         a.k[b] = k0 + n; a.servo[b] = sv;
     } else {
@@ -264,9 +274,10 @@ __global__ void __launch_bounds__(64) race_command_plant_kernel(RaceDev r, Plant
 // race_command_plant_kernel with the estimator in the loop: per plant step, plant -> sensors -> observer (obs_substep, the schedule
 // of cl_command_plant_observe_kernel), then the estimate view that the next tick's measurements read.  A frozen vehicle (nstep 0)
 // advances neither the plant, its actuator nor its observer, so its noise keys (vid, step) depend on its own steps only.
-template <bool kAct>
-__global__ void __launch_bounds__(64) race_command_plant_observe_kernel(RaceDev r, PlantCfg pc, const double *__restrict__ gains,
+template <bool kAct, bool kVeh = false>
+__global__ void __launch_bounds__(64) race_command_plant_observe_kernel(RaceDev r, PlantArg<kVeh> pc, const double *__restrict__ gains,
                                                                         double *__restrict__ obs, ObsParams op, ActDev a) {
+    static_assert(kAct || !kVeh, "the per-vehicle forms are delayed forms");
     __shared__ double G[kObsGainWords];
     obs_stage_gains(G, gains);
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -295,7 +306,7 @@ __global__ void __launch_bounds__(64) race_command_plant_observe_kernel(RaceDev 
         if constexpr (kAct) {
             double ua, ud;
             act_stage(a, b, k0 + k, La, Ld, motor, servo, sv, ua, ud);
-            plant_step(pc, st, ua, ud);
+            plant_step_at(pc, b, st, ua, ud);
         } else {
             plant_step(pc, st, motor, servo);
         }

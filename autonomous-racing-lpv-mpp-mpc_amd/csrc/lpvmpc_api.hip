@@ -170,7 +170,7 @@ extern "C" lpvmpc_handle *lpvmpc_create(const lpvmpc_config *cfg) {
     h->d_xPred = h->d_uPred = h->d_resid = h->d_xlast = h->d_delta = nullptr;
     h->d_status = h->d_iters = h->d_polish = nullptr; h->d_state = nullptr; h->d_scal = nullptr; h->warm_mode = 0; h->state_valid_B = 0;
     h->cl_plant = h->cl_local = h->cl_cmd = nullptr; h->cl_local_next = nullptr; h->cl_next_valid = 0; h->cl_B = 0; h->cl_first_it = 1; h->cl_q9 = 1; h->cl_ticks = 0;
-    h->cl_actuated = 0; h->cl_act = lpvmpc::ActDev{};
+    h->cl_actuated = 0; h->cl_act = lpvmpc::ActDev{}; h->cl_veh = lpvmpc::VehPlantCfg{};
     h->d_Wop = h->d_FWop = nullptr; h->ho_M = 0; h->cascade = nullptr; h->cascade_owner = nullptr; h->cascade_prefetch = 1;
     h->race = nullptr; h->race_owner = nullptr; h->d_active = nullptr; h->solve_mask = nullptr;
     h->defer_after = 0; h->defer_budget = 200; h->defer_cap = 0; h->defer_cur_cap = 0; h->defer_stride = 0; h->rv_count = 0;
@@ -221,6 +221,7 @@ extern "C" void lpvmpc_destroy(lpvmpc_handle *h) {
     if (h->cl_local) (void)hipFree(h->cl_local);
     if (h->cl_cmd) (void)hipFree(h->cl_cmd);
     lpvmpc_act_free(h->cl_act);
+    lpvmpc_plant_free(h->cl_veh);
     if (h->cascade) lpvmpc_cascade_free(h);                                  // (frees the cascade's estimator state)
     if (h->race) lpvmpc_race_free(h);
     if (h->race_owner && h->race_owner->race) lpvmpc_race_free(h->race_owner);   // a handle the race of another one drives: end that race
@@ -737,13 +738,16 @@ extern "C" int lpvmpc_cl_release(lpvmpc_handle *h) {
     if (h->cl_plant) { (void)hipFree(h->cl_plant); (void)hipFree(h->cl_local); (void)hipFree(h->cl_cmd); (void)hipFree(h->cl_local_next); h->cl_plant = h->cl_local = h->cl_cmd = h->cl_local_next = nullptr; }
     if (h->obs_state) { (void)hipFree(h->obs_state); h->obs_state = nullptr; }
     lpvmpc_act_free(h->cl_act); h->cl_actuated = 0;
+    lpvmpc_plant_free(h->cl_veh);
     h->cl_B = 0; h->cl_ticks = 0; h->cl_first_it = 1; h->cl_next_valid = 0;
     return LPVMPC_OK;
 }
 
-// act == nullptr: lpvmpc_cl_init (refuses delayed controllers); else lpvmpc_cl_init_actuated (any steering_delay, actuator in the plant)
+// act == nullptr: lpvmpc_cl_init (refuses delayed controllers); else lpvmpc_cl_init_actuated (any steering_delay, actuator in the plant).
+// veh: the plant table [7][B] of lpvmpc_cl_init_vehicles (checked; act is then set), else null
 static int cl_init(lpvmpc_handle *h, int32_t B, const double *plant0, double half_width, double slack, int32_t q9_swap,
-                   int32_t n_sub, double dt_sim, double mu_sim, const lpvmpc_actuator_config *act, const int32_t *delay_a, const int32_t *delay_df) {
+                   int32_t n_sub, double dt_sim, double mu_sim, const lpvmpc_actuator_config *act, const int32_t *delay_a, const int32_t *delay_df,
+                   const std::vector<double> *veh = nullptr) {
     int rc = lpvmpc_check_common(h, B, "lpvmpc_cl_init"); if (rc) return rc;
     if (h->cfg.kind != LPVMPC_KIND_CONTROLLER) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: controller handles only");
     if (h->race || h->race_owner) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: this handle takes part in a race (lpvmpc_cl_release on its path handle ends it)");
@@ -753,7 +757,9 @@ static int cl_init(lpvmpc_handle *h, int32_t B, const double *plant0, double hal
     if (!plant0 || n_sub < 1 || !(dt_sim > 0)) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: bad argument");
     rc = lpvmpc_need_track(h, "lpvmpc_cl_init"); if (rc) return rc;
     lpvmpc::ActDev a{};
-    if (act) { rc = lpvmpc_act_alloc(h, B, act, delay_a, delay_df, dt_sim, "lpvmpc_cl_init_actuated", a); if (rc) { lpvmpc_act_free(a); return rc; } }
+    if (act) { rc = lpvmpc_act_alloc(h, B, act, delay_a, delay_df, dt_sim, veh ? "lpvmpc_cl_init_vehicles" : "lpvmpc_cl_init_actuated", a); if (rc) { lpvmpc_act_free(a); return rc; } }
+    lpvmpc_plant_free(h->cl_veh);
+    if (veh) { rc = lpvmpc_plant_upload(h, B, *veh, dt_sim, n_sub, h->cl_veh); if (rc) { lpvmpc_act_free(a); lpvmpc_plant_free(h->cl_veh); return rc; } }
     if (h->cl_plant) { (void)hipFree(h->cl_plant); (void)hipFree(h->cl_local); (void)hipFree(h->cl_cmd); (void)hipFree(h->cl_local_next); h->cl_plant = h->cl_local = h->cl_cmd = h->cl_local_next = nullptr; }
     lpvmpc_act_free(h->cl_act);
     h->cl_act = a; h->cl_actuated = act != nullptr;
@@ -792,6 +798,20 @@ extern "C" int lpvmpc_cl_init_actuated(lpvmpc_handle *h, int32_t B, const double
     return cl_init(h, B, plant0, half_width, slack, q9_swap, n_sub, dt_sim, mu_sim, act, delay_a, delay_df);
 }
 
+extern "C" int lpvmpc_cl_init_vehicles(lpvmpc_handle *h, int32_t B, const double *plant0, double half_width, double slack, int32_t q9_swap,
+                                       int32_t n_sub, double dt_sim, double mu_sim, const lpvmpc_actuator_config *act,
+                                       const int32_t *delay_a, const int32_t *delay_df, const double *plant_params) {
+    const char *who = "lpvmpc_cl_init_vehicles";
+    if (!h) return fail(nullptr, LPVMPC_E_ARG, "%s: handle is NULL", who);
+    if (B <= 0) return fail(h, LPVMPC_E_ARG, "%s: B <= 0", who);
+    std::vector<double> tab;
+    int rc = lpvmpc_plant_rows(h, B, plant_params, h->cfg, mu_sim, who, tab); if (rc) return rc;
+    lpvmpc_actuator_config off;
+    lpvmpc_actuator_default_config(&off);
+    if (!act) { act = &off; delay_a = delay_df = nullptr; }               // all off: the delayed kernels pass the command through
+    return cl_init(h, B, plant0, half_width, slack, q9_swap, n_sub, dt_sim, mu_sim, act, delay_a, delay_df, &tab);
+}
+
 extern "C" int lpvmpc_cl_tick(lpvmpc_handle *h, int32_t n_ticks) {
     if (!h || !h->cl_plant || n_ticks < 1) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_tick: call lpvmpc_cl_init first");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -820,7 +840,14 @@ extern "C" int lpvmpc_cl_tick(lpvmpc_handle *h, int32_t n_ticks) {
                     h->warm_mode ? h->d_state : nullptr, (h->warm_mode && h->state_valid_B == B) ? h->warm_mode : 0, x0_stride};
         int rc = lpvmpc_launch_solve_timed(h, a, st); if (rc) return rc;
         if (h->warm_mode) h->state_valid_B = B;
-        if (h->cl_actuated && h->obs_state)
+        if (h->cl_veh.p && h->obs_state)
+            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_veh(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_veh, h->cl_hw, h->cl_slack,
+                                                                    h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay, h->obs_gains,
+                                                                    h->obs_state, h->obs_p, h->cl_act, st));
+        else if (h->cl_veh.p)
+            HIP_TRY(h, lpvmpc::launch_cl_command_plant_measure_veh(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_veh, h->cl_hw, h->cl_slack,
+                                                                    h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay, h->cl_act, st));
+        else if (h->cl_actuated && h->obs_state)
             HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_act(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_pc, h->cl_hw, h->cl_slack,
                                                                     h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay, h->obs_gains,
                                                                     h->obs_state, h->obs_p, h->cl_act, st));

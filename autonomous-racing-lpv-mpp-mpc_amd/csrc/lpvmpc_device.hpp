@@ -137,6 +137,25 @@ hipError_t launch_cl_command_plant_measure_act(const DevCfg *dcfg, int B, int N,
                                                double hw, double slack, int q9_swap, double *local_next, double *u_old, int sd,
                                                const ActDev &a, hipStream_t s);
 
+// per-vehicle plant parameters (plant_params.hip; lpvmpc_*_vehicles, include/lpvmpc.h "Per-vehicle plant parameters"): the fleet's
+// table [kPlantWords][B], parameter-major and vehicle-minor like the actuator ring, so that a wavefront's loads of one word coalesce.
+// It is the per-vehicle forms' own kernel argument: PlantCfg, which every other fleet kernel takes by value, keeps its layout
+constexpr int kPlantWords = 7;               // = LPVMPC_PLANT_WORDS: lf, lr, m, Iz, Cf, Cr, mu
+struct VehPlantCfg {
+    const double *p;                         // [kPlantWords][B]
+    int B;                                   // the table's row stride (vehicles)
+    double dt; int n_sub;                    // fleet-wide, as in PlantCfg
+};
+// the plant argument of a fleet kernel (fleet_kernels.hpp): one PlantCfg for the fleet, or the table (kVeh)
+template <bool kVeh> struct PlantArgT { using type = PlantCfg; };
+template <> struct PlantArgT<true> { using type = VehPlantCfg; };
+template <bool kVeh> using PlantArg = typename PlantArgT<kVeh>::type;
+// the per-vehicle forms of the kernels that step the plant: always the delayed forms (an all-off actuator is a pass-through)
+hipError_t launch_plant_veh(int B, double *plant, const double *u_a_delta, const VehPlantCfg &pc, const ActDev &a, hipStream_t s);
+hipError_t launch_cl_command_plant_measure_veh(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
+                                               const VehPlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
+                                               int sd, const ActDev &a, hipStream_t s);
+
 
 // gain-scheduled LPV estimator and simulated sensors (observer.hip)
 constexpr int kObsTable = 6 * 5 * 16;   // one Llmi table [6][5][16]
@@ -161,6 +180,9 @@ hipError_t launch_cl_observe_measure_act(const DevCfg *dcfg, int B, const double
 hipError_t launch_cl_command_plant_observe_act(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant, PlantCfg pc,
                                               double hw, double slack, int q9_swap, double *local_next, double *u_old, int sd,
                                               const double *gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s);
+hipError_t launch_cl_command_plant_observe_veh(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
+                                               const VehPlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
+                                               int sd, const double *gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s);
 
 
 // planner -> controller hand-off and trajectory-tracking measurement (handoff.hip)
@@ -206,6 +228,10 @@ hipError_t launch_race_command_plant_observe(const RaceDev &r, PlantCfg pc, cons
 hipError_t launch_race_measure_act(const DevCfg *ccfg, const RaceDev &r, int seed_tick, int sd, hipStream_t s);
 hipError_t launch_race_command_plant_act(const RaceDev &r, PlantCfg pc, const ActDev &a, hipStream_t s);
 hipError_t launch_race_command_plant_observe_act(const RaceDev &r, PlantCfg pc, const double *gains, double *obs, const ObsParams &op,
+                                                const ActDev &a, hipStream_t s);
+// the per-vehicle forms (lpvmpc_race_init_vehicles, plant_params.hip): the delayed forms with the fleet's plant table
+hipError_t launch_race_command_plant_veh(const RaceDev &r, const VehPlantCfg &pc, const ActDev &a, hipStream_t s);
+hipError_t launch_race_command_plant_observe_veh(const RaceDev &r, const VehPlantCfg &pc, const double *gains, double *obs, const ObsParams &op,
                                                 const ActDev &a, hipStream_t s);
 
 }  // namespace lpvmpc

@@ -41,6 +41,7 @@ struct lpvmpc_handle {
     lpvmpc::PlantCfg cl_pc;
     int cl_actuated;                    // the fleet was started by lpvmpc_cl_init_actuated: delayed kernels, actuator state cl_act
     lpvmpc::ActDev cl_act;
+    lpvmpc::VehPlantCfg cl_veh;         // the fleet was started by lpvmpc_cl_init_vehicles: its plant table (cl_veh.p; null: one PlantCfg)
     int32_t *d_status, *d_iters, *d_polish;
     hipStream_t stream;
     std::vector<hipEvent_t> ev0, ev1;   // ring of event pairs around the solve-kernel launches
@@ -117,6 +118,14 @@ LPVMPC_HIDDEN void lpvmpc_act_free(lpvmpc::ActDev &a);
 LPVMPC_HIDDEN int lpvmpc_act_download(lpvmpc_handle *h, const lpvmpc::ActDev &a, double *act_state, hipStream_t st);   // device -> host layout
 LPVMPC_HIDDEN int lpvmpc_race_act_read(lpvmpc_handle *h, double *act_state, double *path_hist, double *tt_hist);        // race_api.hip
 LPVMPC_HIDDEN int lpvmpc_observer_check(lpvmpc_handle *h, const lpvmpc_observer_config *c, const char *who);   // lpvmpc_api.hip
+// plant_params_api.hip: per-vehicle plant parameters (lpvmpc_*_vehicles).  lpvmpc_plant_rows checks the host rows [B][7] (null: the
+// nominal row lf, lr, m, Iz, 60, 60, mu for every vehicle) and returns the device layout [7][B] in t; nothing is allocated.
+// lpvmpc_plant_upload allocates and fills the fleet's table (synchronises); lpvmpc_plant_free releases it
+LPVMPC_HIDDEN int lpvmpc_plant_rows(lpvmpc_handle *h, int B, const double *rows, const lpvmpc_config &nominal, double mu, const char *who,
+                                    std::vector<double> &t);
+LPVMPC_HIDDEN int lpvmpc_plant_upload(lpvmpc_handle *h, int B, const std::vector<double> &t, double dt_sim, int n_sub, lpvmpc::VehPlantCfg &v);
+LPVMPC_HIDDEN void lpvmpc_plant_free(lpvmpc::VehPlantCfg &v);
+LPVMPC_HIDDEN const lpvmpc::VehPlantCfg *lpvmpc_race_plant(const lpvmpc_handle *h);                     // race_api.hip: the race's table
 namespace lpvmpc {
 // handoff.hip (host): interpolation operator W and interpolation + filtfilt operator FW, both [M][N] row-major
 bool handoff_operators(int N, double dt, double interp_dt, int padlen, int ord, const double *b, const double *a,

@@ -25,6 +25,7 @@ struct lpvmpc_race {
     bool actuated;                // lpvmpc_race_init_actuated: delayed kernels, actuator state act, controller histories of steering delay sd
     lpvmpc::ActDev act;
     int sd;
+    lpvmpc::VehPlantCfg veh;      // lpvmpc_race_init_vehicles: the plant table (veh.p; null: one PlantCfg), with the delayed kernels' actuator
     lpvmpc_race_recorder *rec;    // lpvmpc_race_record (null: not recording)
 };
 
@@ -53,6 +54,7 @@ void lpvmpc_race_free(lpvmpc_handle *h) {
         h->obs_state = h->obs_gains = nullptr; h->obs_B = 0; h->obs_p = lpvmpc::ObsParams{};
     }
     lpvmpc_act_free(r->act);
+    lpvmpc_plant_free(r->veh);
     recorder_free(r);
     if (r->tt && r->tt->race_owner == h) r->tt->race_owner = nullptr;
     if (r->plan && r->plan->race_owner == h) r->plan->race_owner = nullptr;
@@ -74,7 +76,8 @@ static bool busy(const lpvmpc_handle *x) { return x->cl_plant || x->cascade || x
 
 static int race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, int32_t B, const double *plant0, const int32_t *half_track0,
                      const lpvmpc_race_config *cfg, const lpvmpc_observer_config *obs, bool observed_call,
-                     const lpvmpc_actuator_config *act = nullptr, const int32_t *delay_a = nullptr, const int32_t *delay_df = nullptr) {
+                     const lpvmpc_actuator_config *act = nullptr, const int32_t *delay_a = nullptr, const int32_t *delay_df = nullptr,
+                     const std::vector<double> *veh = nullptr) {
     if (!h) return fail(nullptr, LPVMPC_E_ARG, "lpvmpc_race_init: path handle is NULL");
     if (!tt || !plan || !plant0 || !cfg || B <= 0) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: NULL argument or B <= 0");
     if (h->cfg.kind != LPVMPC_KIND_CONTROLLER || tt->cfg.kind != LPVMPC_KIND_CONTROLLER || plan->cfg.kind != LPVMPC_KIND_PLANNER || h == tt)
@@ -106,13 +109,15 @@ static int race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, i
     rc = lpvmpc_check_common(tt, B, "lpvmpc_race_init(tt)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
     rc = lpvmpc_check_common(plan, B, "lpvmpc_race_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
     lpvmpc::ActDev a{};
-    if (act) { rc = lpvmpc_act_alloc(h, B, act, delay_a, delay_df, cfg->dt_sim, "lpvmpc_race_init_actuated", a); if (rc) { lpvmpc_act_free(a); return rc; } }
+    if (act) { rc = lpvmpc_act_alloc(h, B, act, delay_a, delay_df, cfg->dt_sim, veh ? "lpvmpc_race_init_vehicles" : "lpvmpc_race_init_actuated", a); if (rc) { lpvmpc_act_free(a); return rc; } }
+    lpvmpc::VehPlantCfg v{};
+    if (veh) { rc = lpvmpc_plant_upload(h, B, *veh, cfg->dt_sim, 1, v); if (rc) { lpvmpc_act_free(a); lpvmpc_plant_free(v); return rc; } }
     lpvmpc_race *r = new (std::nothrow) lpvmpc_race();
-    if (!r) { lpvmpc_act_free(a); return fail(h, LPVMPC_E_NOMEM, "out of host memory"); }
+    if (!r) { lpvmpc_act_free(a); lpvmpc_plant_free(v); return fail(h, LPVMPC_E_NOMEM, "out of host memory"); }
     std::memset(&r->d, 0, sizeof(r->d));
     h->race = r; tt->race_owner = h; plan->race_owner = h;
     r->tt = tt; r->plan = plan; r->ticks = 0;
-    r->actuated = act != nullptr; r->act = a; r->sd = h->cfg.steering_delay;
+    r->actuated = act != nullptr; r->act = a; r->sd = h->cfg.steering_delay; r->veh = v;
     r->pc = lpvmpc_plant_cfg(h, 1, cfg->dt_sim, cfg->mu_sim);
     lpvmpc::RaceDev &d = r->d;
     const size_t b = B, N = h->cfg.N, Np = plan->cfg.N, M = plan->ho_M;
@@ -185,6 +190,23 @@ extern "C" int lpvmpc_race_init_actuated(lpvmpc_handle *h, lpvmpc_handle *tt, lp
     return race_init(h, tt, plan, B, plant0, half_track0, cfg, obs, true, act, delay_a, delay_df);
 }
 
+extern "C" int lpvmpc_race_init_vehicles(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, int32_t B, const double *plant0,
+                                         const int32_t *half_track0, const lpvmpc_race_config *cfg, const lpvmpc_observer_config *obs,
+                                         const lpvmpc_actuator_config *act, const int32_t *delay_a, const int32_t *delay_df,
+                                         const double *plant_params) {
+    const char *who = "lpvmpc_race_init_vehicles";
+    if (!h) return fail(nullptr, LPVMPC_E_ARG, "%s: path handle is NULL", who);
+    if (!cfg || B <= 0) return fail(h, LPVMPC_E_ARG, "%s: NULL configuration or B <= 0", who);
+    std::vector<double> tab;
+    int rc = lpvmpc_plant_rows(h, B, plant_params, h->cfg, cfg->mu_sim, who, tab); if (rc) return rc;
+    lpvmpc_actuator_config off;
+    lpvmpc_actuator_default_config(&off);
+    if (!act) { act = &off; delay_a = delay_df = nullptr; }               // all off: the delayed kernels pass the command through
+    return race_init(h, tt, plan, B, plant0, half_track0, cfg, obs, true, act, delay_a, delay_df, &tab);
+}
+
+const lpvmpc::VehPlantCfg *lpvmpc_race_plant(const lpvmpc_handle *h) { return h->race ? &h->race->veh : nullptr; }
+
 // the race's actuator state and its two controllers' histories (lpvmpc_actuator_read)
 int lpvmpc_race_act_read(lpvmpc_handle *h, double *act_state, double *path_hist, double *tt_hist) {
     lpvmpc_race *r = h->race;
@@ -248,7 +270,9 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
                      tt->d_resid, nullptr, 0, 6};
         ta.active = d.m_tt;
         rc = lpvmpc_launch_solve_timed(tt, ta, st); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
-        if (r->actuated && d.estv) HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_act(d, r->pc, h->obs_gains, h->obs_state, h->obs_p, r->act, st));
+        if (r->veh.p && d.estv) HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_veh(d, r->veh, h->obs_gains, h->obs_state, h->obs_p, r->act, st));
+        else if (r->veh.p) HIP_TRY(h, lpvmpc::launch_race_command_plant_veh(d, r->veh, r->act, st));
+        else if (r->actuated && d.estv) HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_act(d, r->pc, h->obs_gains, h->obs_state, h->obs_p, r->act, st));
         else if (r->actuated) HIP_TRY(h, lpvmpc::launch_race_command_plant_act(d, r->pc, r->act, st));
         else if (d.estv) HIP_TRY(h, lpvmpc::launch_race_command_plant_observe(d, r->pc, h->obs_gains, h->obs_state, h->obs_p, st));
         else HIP_TRY(h, lpvmpc::launch_race_command_plant(d, r->pc, st));

@@ -129,6 +129,37 @@ __device__ inline void plant_step(const PlantCfg &p, double st[8], double ua, do
     st[7] = w + p.dt * (1.0 / p.Iz * (p.lf * FyF * cos(ud) - p.lr * FyR));
 }
 
+// Simulator.f with one vehicle's parameter row q = [lf lr m Iz Cf Cr mu] (lpvmpc_*_vehicles): plant_step's expressions with the tyre
+// stiffnesses Cf, Cr where Simulator.f has 60, so that the nominal row (Cf = Cr = 60) gives plant_step's bits
+__device__ inline void plant_step_row(const double q[kPlantWords], double dt, double st[8], double ua, double ud) {
+    const double lf = q[0], lr = q[1], m = q[2], Iz = q[3], Cf = q[4], Cr = q[5], mu = q[6];
+    const double x = st[0], y = st[1], vx = st[2], vy = st[3], ax = st[4], ay = st[5], yaw = st[6], w = st[7];
+    double aF = 0.0, aR = 0.0;
+    if (fabs(vx) > 0.2) {
+        aF = ud - atan((vy + lf * w) / fabs(vx));
+        aR = atan((-vy + lr * w) / fabs(vx));
+    }
+    const double FyF = Cf * aF, FyR = Cr * aR;
+    st[0] = x + dt * (cos(yaw) * vx - sin(yaw) * vy);
+    st[1] = y + dt * (sin(yaw) * vx + cos(yaw) * vy);
+    st[2] = fabs(vx + dt * (ax + w * vy));
+    st[3] = vy + dt * (ay - w * vx);
+    st[4] = ua - mu * vx - FyF / m * sin(ud);
+    st[5] = 1.0 / m * (FyF * cos(ud) + FyR);
+    st[6] = yaw + dt * w;
+    st[7] = w + dt * (1.0 / Iz * (lf * FyF * cos(ud) - lr * FyR));
+}
+
+// one simulator step of vehicle b in a fleet kernel: the fleet's PlantCfg (plain and delayed forms), or the vehicle's row of the
+// table (per-vehicle forms), read at every step -- a cached, coalesced load instead of seven more registers held across the loop
+__device__ __forceinline__ void plant_step_at(const PlantCfg &p, int, double st[8], double ua, double ud) { plant_step(p, st, ua, ud); }
+__device__ __forceinline__ void plant_step_at(const VehPlantCfg &p, int b, double st[8], double ua, double ud) {
+    double q[kPlantWords];
+#pragma unroll
+    for (int i = 0; i < kPlantWords; ++i) q[i] = p.p[(size_t)i * p.B + b];
+    plant_step_row(q, p.dt, st, ua, ud);
+}
+
 // Actuator stage of one simulator step (vehicleSimulator.py:67-76) for vehicle b at its plant step kk: the command (motor, servo)
 // enters the two FIFOs and the plant receives the entries La / Ld steps old -- 0 while kk < L, the FIFOs start filled with zeros;
 // L = 0 is the command itself.  With lowLevelDyn the servo filter sv runs on the delayed steering and is what the plant receives.

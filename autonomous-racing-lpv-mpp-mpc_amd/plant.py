@@ -1,0 +1,80 @@
+"""Per-vehicle plant parameters for the device fleets and races (include/lpvmpc.h, "Per-vehicle plant parameters"): rows
+[lf, lr, m, Iz, Cf, Cr, mu] per vehicle, with which each vehicle's simulated plant (Simulator.f, vehicleSimulator.py:164-199)
+steps while the controllers, the planner and the estimator keep their nominal model.  Cf and Cr are the plant's linear tyre
+stiffnesses (Simulator.f's constant 60), mu its drag coefficient (simulator/mu).  These helpers build and sample the rows; the
+library checks them again."""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _ffi
+
+WORDS = _ffi.PLANT_WORD_NAMES
+NOMINAL = dict(lf=0.125, lr=0.125, m=1.98, Iz=0.03, Cf=60.0, Cr=60.0, mu=0.05)   # MAIN_LAUNCH.launch; Simulator.f's tyre; simulator/mu
+
+
+def check_plant_params(rows, B):
+    """rows as a contiguous float64 [B, 7] array; ValueError on another shape, a non-finite word, lf / lr / m / Iz <= 0 or
+    Cf / Cr / mu < 0 (the library's refusals, raised before any call into it)."""
+    a = np.asarray(rows)
+    if a.dtype.kind not in "fiu":
+        raise ValueError("plant_params must be numeric, got dtype %s" % a.dtype)
+    a = np.ascontiguousarray(a, np.float64)
+    if a.shape != (B, _ffi.PLANT_WORDS):
+        raise ValueError("plant_params has shape %s, expected (%d, %d) = (B, [lf lr m Iz Cf Cr mu])" % (a.shape, B, _ffi.PLANT_WORDS))
+    if not np.all(np.isfinite(a)):
+        b, i = np.argwhere(~np.isfinite(a))[0]
+        raise ValueError("plant_params: vehicle %d: %s is not finite" % (b, WORDS[i]))
+    bad = np.argwhere(np.concatenate([a[:, :4] <= 0, a[:, 4:] < 0], axis=1))
+    if bad.size:
+        b, i = bad[0]
+        raise ValueError("plant_params: vehicle %d: %s = %g (lf, lr, m, Iz must be > 0; Cf, Cr, mu >= 0)" % (b, WORDS[i], a[b, i]))
+    return a
+
+
+def plant_params(B, engine=None, mu_sim=0.05, **fields):
+    """[B, 7] nominal rows -- lf, lr, m, Iz of ``engine`` (a BatchedSolver; None: the launch file's), Cf = Cr = 60 (the simulator's
+    tyre, not the controller's Cf) and mu = mu_sim -- with any field overridden by a scalar or a [B] array, e.g.
+    plant_params(B, eng, m=np.linspace(1.7, 2.3, B))."""
+    B = int(B)
+    if B < 1:
+        raise ValueError("B must be >= 1")
+    base = dict(NOMINAL, mu=float(mu_sim))
+    if engine is not None:
+        base.update({k: float(getattr(engine.cfg, k)) for k in ("lf", "lr", "m", "Iz")})
+    unknown = set(fields) - set(WORDS)
+    if unknown:
+        raise TypeError("unknown plant field(s) %s (fields: %s)" % (sorted(unknown), ", ".join(WORDS)))
+    out = np.empty((B, _ffi.PLANT_WORDS))
+    for i, k in enumerate(WORDS):
+        v = np.asarray(fields.get(k, base[k]), np.float64)
+        if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != B):
+            raise ValueError("%s must be a scalar or have %d entries, got shape %s" % (k, B, v.shape))
+        out[:, i] = v
+    return check_plant_params(out, B)
+
+
+# relative spread of each field for sample_plant_params: m, Iz +-15 %, Cf, Cr +-30 %, mu x [0.5, 1.5]
+DEFAULT_SPREAD = dict(m=0.15, Iz=0.15, Cf=0.30, Cr=0.30, mu=0.50)
+
+
+def sample_plant_params(B, seed, spread=None, engine=None, mu_sim=0.05, offset=0):
+    """[B, 7] rows: each field of the nominal row (plant_params(B, engine, mu_sim)) times an independent uniform factor in
+    [1 - s, 1 + s], s = spread[field] (dict; None: DEFAULT_SPREAD; fields not named stay nominal).  Seeded: vehicle b of a fleet
+    gets the same row for the same seed whatever the batch, so shard k of a sharded fleet takes sample_plant_params(n, seed,
+    offset=k * n) -- the rows of vehicles offset .. offset + n - 1 of one fleet."""
+    B, offset = int(B), int(offset)
+    spread = DEFAULT_SPREAD if spread is None else dict(spread)
+    unknown = set(spread) - set(WORDS)
+    if unknown:
+        raise TypeError("unknown plant field(s) %s (fields: %s)" % (sorted(unknown), ", ".join(WORDS)))
+    for k, s in spread.items():
+        if not (np.isfinite(s) and 0 <= s < 1):
+            raise ValueError("spread of %s must be in [0, 1), got %r" % (k, s))
+    base = plant_params(B, engine, mu_sim)
+    # one stream per (seed, field); a vehicle's factor is the stream's entry at its global index, so slices agree with the whole
+    for i, k in enumerate(WORDS):
+        if k in spread:
+            u = np.random.default_rng([int(seed), i]).uniform(-1.0, 1.0, offset + B)[offset:]
+            base[:, i] *= 1.0 + float(spread[k]) * u
+    return check_plant_params(base, B)

@@ -702,6 +702,45 @@ int  lpvmpc_race_record_read(lpvmpc_handle *path, int32_t n, int32_t *total, int
 /* synchronises and copies the per-lap statistics (any pointer may be NULL); refused with LPVMPC_E_ARG while recording is off */
 int  lpvmpc_race_lap_stats(lpvmpc_handle *path, double *f64, int32_t *i32, int32_t *end_tick);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Per-vehicle plant parameters: every vehicle of a lap-0 fleet or a race steps the simulated plant (Simulator.f, SIM:164-199)
+ * with its own row of parameters, held on the device.  The controllers, the planner and the estimator keep the nominal model of
+ * their handles (the mismatch is the point: a Monte-Carlo sweep of how the controller holds up when the car is not the model it
+ * was tuned on).  All entry points here are new; the calls above keep their behaviour and refusals.
+ *
+ * Host layout: plant_params [B][LPVMPC_PLANT_WORDS] = {lf, lr, m, Iz, Cf, Cr, mu} per vehicle.  Cf and Cr are the linear tyre
+ * stiffnesses of the plant, FyF = Cf * aF, FyR = Cr * aR, where Simulator.f has the constant 60; mu is the simulator's drag
+ * coefficient (simulator/mu).  n_sub and dt_sim stay fleet-wide.
+ *   plant_params == NULL: every vehicle has the nominal row -- the handle's lf, lr, m, Iz (the path handle's, for a race),
+ *     Cf = Cr = 60 (the simulator's constant, not the controller's Cf) and mu = mu_sim (cfg->mu_sim for a race).  With the nominal
+ *     row each call computes what its _actuated counterpart computes, word for word.
+ *   plant_params given: mu_sim (cfg->mu_sim for a race) is ignored.
+ *   act == NULL: the actuator is all off (lpvmpc_actuator_default_config; delay_a / delay_df are ignored).  The calls run the
+ *     delayed fleets' kernels in any case, so a fleet or race started here is read with lpvmpc_actuator_read as well, and its
+ *     controllers may carry a steering delay as in the _actuated calls.
+ * Refused with LPVMPC_E_ARG, nothing started or allocated: a non-finite word, lf, lr, m or Iz <= 0, Cf, Cr or mu < 0, and
+ * everything the _actuated calls refuse.  The rows belong to the fleet or race: lpvmpc_cl_release frees them, and a later
+ * lpvmpc_cl_init* on the handle runs nominal.  lpvmpc_cascade_init stays nominal (not extended here). */
+#define LPVMPC_PLANT_WORDS 7
+/* lpvmpc_plant_step_actuated_batch with a row per vehicle; act_state may be NULL when act is NULL (a fresh all-off actuator,
+ * not returned). */
+int  lpvmpc_plant_step_vehicles_batch(lpvmpc_handle *h, int32_t B, double *state, double *act_state, const double *u,
+                                      int32_t n_sub, double dt_sim, double mu_sim, const lpvmpc_actuator_config *act,
+                                      const int32_t *delay_a, const int32_t *delay_df, const double *plant_params);
+/* lpvmpc_cl_init_actuated with a row per vehicle; an estimator attached with lpvmpc_observer_setup runs as in
+ * lpvmpc_cl_init_actuated. */
+int  lpvmpc_cl_init_vehicles(lpvmpc_handle *h, int32_t B, const double *plant0, double half_width, double slack, int32_t q9_swap,
+                             int32_t n_sub, double dt_sim, double mu_sim, const lpvmpc_actuator_config *act,
+                             const int32_t *delay_a, const int32_t *delay_df, const double *plant_params);
+/* lpvmpc_race_init_actuated with a row per vehicle (obs NULL: ground truth). */
+int  lpvmpc_race_init_vehicles(lpvmpc_handle *path, lpvmpc_handle *tt, lpvmpc_handle *planner, int32_t B,
+                               const double *plant0, const int32_t *half_track0, const lpvmpc_race_config *cfg,
+                               const struct lpvmpc_observer_config *obs, const lpvmpc_actuator_config *act,
+                               const int32_t *delay_a, const int32_t *delay_df, const double *plant_params);
+/* the rows [B][LPVMPC_PLANT_WORDS] of the fleet or race that h runs (the path handle, for a race), started by the two calls
+ * above (synchronises). */
+int  lpvmpc_plant_params_read(lpvmpc_handle *h, double *plant_params);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,11 @@ all off, with plant delays La = Ld = 20 steps and the servo lag (steeringDelay 0
 controllers; alternated --reps times per (regime, B), medians and differences against the old entry.
 --record: instead, the lap0 and inphase races run with recording off and on (lpvmpc_race_record, stride 1, a ring as long as the timed
 window), alternated --reps times per (regime, B); medians and the added ms per controller tick.
-Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator | --actuator | --record [--reps R]] [--out FILE]"""
+--plant-params: instead, the lap0 and inphase races run on lpvmpc_race_init_actuated with the actuator all off, on
+lpvmpc_race_init_vehicles with the nominal rows and with rows from plant.sample_plant_params (seed 1); alternated --reps times per
+(regime, B), medians and differences against the all-off entry.  The sampled rows drive other trajectories, so their in-phase
+lines also carry the solvers' changed iteration counts.
+Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator | --actuator | --record | --plant-params [--reps R]] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -43,10 +47,10 @@ def timed(tick, read, K):
     return (time.perf_counter() - t0) * 1e3 / K
 
 
-def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, record=False):
+def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, record=False, plant_params=None):
     path, tt, plan = engines(mp, sd)
     path.race_init(tt, plan, plant0, half_track0=half, laps=5, half_width=mp.halfWidth, slack=mp.slack, estimator=estimator,
-                   actuator=actuator)
+                   actuator=actuator, plant_params=plant_params)
     path.race_tick(warm)
     if record:
         path.race_record(K, 1)
@@ -68,7 +72,10 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--actuator", action="store_true")
     ap.add_argument("--record", action="store_true")
+    ap.add_argument("--plant-params", action="store_true")
     a = ap.parse_args()
+    if a.plant_params:
+        return plant_params_main(a)
     if a.record:
         return record_main(a)
     if a.estimator:
@@ -182,6 +189,37 @@ def actuator_main(a):
             for k, _, _ in cfgs:
                 m = float(np.median(ms[k]))
                 lines.append("%-8s B=%5d  %-20s %.3f ms/tick (runs %s, phases %s)  vs old %+.3f ms/tick"
+                             % (name, B, k, m, " ".join("%.3f" % x for x in ms[k]), ph[k].tolist(), m - m0))
+                print(lines[-1], flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+def plant_params_main(a):
+    import lpvmpc
+    from tests._golden import load
+    mp = lpvmpc.Map("L_shape", 0.2)
+    c = load("cascade")
+    P = int(c["pre_ticks"])
+    lines = []
+    for B in [int(x) for x in a.sizes.split(",")]:
+        rng = np.random.default_rng(3)
+        grid = np.zeros((B, 8)); grid[:, 1] = rng.normal(0, 0.02, B); grid[:, 2] = rng.uniform(0.9, 1.1, B)
+        same = np.tile(c["pre_plant"][0], (B, 1))
+        cfgs = (("all-off", dict(actuator=lpvmpc.actuator_config())), ("nominal rows", dict(plant_params=lpvmpc.plant_params(B))),
+                ("sampled rows", dict(plant_params=lpvmpc.sample_plant_params(B, 1))))
+        for name, plant0, half, warm in (("lap0", grid, 0, 10), ("inphase", same, 1, P + 3)):
+            ms = {k: [] for k, _ in cfgs}
+            ph = {}
+            for _ in range(a.reps):
+                for k, kw in cfgs:
+                    m, _vps, ph[k] = race_run(mp, plant0, half, warm, a.ticks, **kw)
+                    ms[k].append(m)
+            m0 = float(np.median(ms["all-off"]))
+            for k, _ in cfgs:
+                m = float(np.median(ms[k]))
+                lines.append("%-8s B=%5d  %-13s %.3f ms/tick (runs %s, phases %s)  vs all-off %+.3f ms/tick"
                              % (name, B, k, m, " ".join("%.3f" % x for x in ms[k]), ph[k].tolist(), m - m0))
                 print(lines[-1], flush=True)
     if a.out:

@@ -1,0 +1,93 @@
+#!/usr/bin/env python3
+"""Model-mismatch sweep: one race of B vehicles (default 8192) whose plants carry their own parameters (lpvmpc_race_init_vehicles,
+rows from plant.sample_plant_params) while the controllers and the planner keep the nominal model.  Default spreads: m, Iz +-15 %,
+Cf, Cr +-30 %, mu x [0.5, 1.5]; two racing laps, the recorder on (its per-lap statistics).  The vehicles start near the end of the
+lap (HalfTrack = 1), so lap 0 is short.  The race runs until every vehicle has finished or is lost (or --max-ticks).
+Reports, binned by each sampled parameter (quartiles of its factor against the nominal row): vehicles, the fractions finished and
+lost, the median and p90 racing lap time (laps 1 .. laps of the finished vehicles' laps) and the median per-lap RMSE_ey of the
+racing laps (RaceFleet.lap_stats, CMAIN:101-106).
+Usage: tools/robustness_sweep.py [--B 8192] [--laps 2] [--seed 1] [--max-ticks 3000] [--out FILE]"""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=8192)
+    ap.add_argument("--laps", type=int, default=2)
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--max-ticks", type=int, default=3000)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import lpvmpc
+    from lpvmpc import plant
+    from tests._race_observer_ref import start_line_fleet
+    mp = lpvmpc.Map("L_shape", 0.2)
+    B = a.B
+    spread = plant.DEFAULT_SPREAD
+    rows = lpvmpc.sample_plant_params(B, a.seed, spread)
+    nom = lpvmpc.plant_params(B)
+    plant0 = start_line_fleet(mp.PointAndTangent, B, a.seed, 0.8, 0.97)
+
+    def race(r):
+        f = lpvmpc.RaceFleet(mp, plant0, laps=a.laps, half_track0=1, plant_params=r)
+        assert np.array_equal(f.plant_params(), r)
+        f.record(1, 1 << 20)                                          # statistics of every tick; one record kept
+        t0, n = time.perf_counter(), 0
+        while n < a.max_ticks:
+            f.run(100); n += 100
+            if np.all(f.state()["phase"] >= 2):
+                break
+        return f, n, time.perf_counter() - t0
+
+    base, _n, _w = race(nom)                                          # the same starts with the nominal car: the baseline
+    ph_nom = base.state()["phase"]
+    base.close()
+    fleet, ticks, wall = race(rows)
+    ph = fleet.state()["phase"]
+    lt = fleet.lap_times()[:, 1:a.laps + 1]                          # racing laps, seconds (NaN: not completed)
+    st = fleet.lap_stats()
+    rmse = st["rmse_ey"][:, 1:a.laps + 1]
+    fin, lost = ph == 2, ph == 3
+    fin_nom = ph_nom == 2
+    lines = ["# tools/robustness_sweep.py --B %d --laps %d --seed %d on one MI355X: one race, rows from sample_plant_params(B, %d) with spreads %s"
+             % (B, a.laps, a.seed, a.seed, ", ".join("%s %+.0f %%" % (k, 100 * v) for k, v in spread.items())),
+             "# the controllers and the planner keep the nominal model (lf = lr = 0.125, m = 1.98, Iz = 0.03, Cf = Cr = 60, mu = 0.05).",
+             "# %d ticks (%.1f s wall); all vehicles: %.1f %% finished, %.1f %% lost, %.1f %% still running; racing lap time median %.3f s, "
+             "p90 %.3f s; RMSE_ey median %.4f m" % (ticks, wall, 100 * fin.mean(), 100 * lost.mean(), 100 * (ph < 2).mean(),
+                                                     np.nanmedian(lt), np.nanpercentile(lt, 90), np.nanmedian(rmse)),
+             "# the same starts with the nominal car: %.1f %% finished, %.1f %% lost (the starts near the end of the lap lose vehicles in "
+             "lap 0 and on the first racing laps whatever the car); of the vehicles that finish with the nominal car, %.1f %% are lost "
+             "with their own" % (100 * fin_nom.mean(), 100 * (ph_nom == 3).mean(), 100 * lost[fin_nom].mean()),
+             "# bins: quartiles of each parameter's factor (row / nominal); lost|nom: lost among the bin's vehicles that finish with the "
+             "nominal car; lap time and RMSE_ey over the completed racing laps of the bin",
+             "%-4s %-15s %6s %9s %7s %9s %11s %9s %12s" % ("par", "factor bin", "veh", "finished", "lost", "lost|nom", "lap med s", "lap p90",
+                                                           "RMSE_ey med")]
+    for i, k in enumerate(plant.WORDS):
+        if k not in spread:
+            continue
+        f = rows[:, i] / nom[:, i]
+        edges = np.quantile(f, [0, 0.25, 0.5, 0.75, 1.0])
+        for j in range(4):
+            sel = (f >= edges[j]) & ((f < edges[j + 1]) if j < 3 else (f <= edges[j + 1]))
+            l_, r_ = lt[sel], rmse[sel]
+            has = np.isfinite(l_).any()
+            lines.append("%-4s [%.3f, %.3f] %6d %8.1f%% %6.1f%% %8.1f%% %11s %9s %12s"
+                         % (k, edges[j], edges[j + 1], sel.sum(), 100 * fin[sel].mean(), 100 * lost[sel].mean(), 100 * lost[sel & fin_nom].mean(),
+                            "%.3f" % np.nanmedian(l_) if has else "-", "%.3f" % np.nanpercentile(l_, 90) if has else "-",
+                            "%.4f" % np.nanmedian(r_) if np.isfinite(r_).any() else "-"))
+    fleet.close()
+    print("\n".join(lines), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
