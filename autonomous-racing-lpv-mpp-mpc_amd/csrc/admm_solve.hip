@@ -1,4 +1,4 @@
-// admm_solve.hip -- batched horizon-QP build + OSQP-style ADMM solve, one wavefront per MPC instance.
+// admm_solve.hip -- batched horizon-QP build + OSQP-style ADMM solve: every instantiation of admm_solve_kernel.
 //
 // Replaces, per instance, the reference chain
 //   _buildMatEqConst (CTRL:477-529 / PLAN:434-486), _buildMatCost (CTRL:382-473 / PLAN:145-169),
@@ -7,20 +7,27 @@
 //
 // Design (CDNA4): the whole solve of one instance -- Ruiz equilibration, KKT factorisation, every ADMM
 // iteration, adaptive-rho refactorisations, termination / infeasibility tests and the polish step --
-// runs inside ONE 64-lane wavefront with all state resident in LDS, so HBM sees only the LPV blocks
-// going in and the trajectory coming out.  The QP is never materialised as sparse matrices: the
-// decision vector is kept stage-interleaved, w_k = (x_k, u_k), which makes
+// runs inside ONE workgroup with all state resident in LDS, so HBM sees only the LPV blocks going in
+// and the trajectory coming out.  The QP is never materialised as sparse matrices: the decision vector
+// is kept stage-interleaved, w_k = (x_k, u_k), which makes
 //     K = P + sigma I + A' diag(rho) A
-// block tridiagonal with 8x8 blocks.  K is factored as a block L D L' with explicit inverses of the
-// pivots (S_k^-1) so that a solve is 3 tile mat-vecs per stage.  Tile element [i][j] lives in lane
-// 8*i+j; reductions across i or j are wave shuffles.
+// block tridiagonal with 8x8 blocks.  K is factored as a block L S L' from both ends of the horizon
+// towards a middle stage; each pivot block is factored S_k = C C' and only the triangular factor is
+// inverted (see "block tridiagonal factorisation" below), so that a KKT solve is two sweeps of tile
+// mat-vecs per chain.
 //
-// Two instantiations per model: Solver<NX, NT> with a compile-time horizon NT keeps the factor tiles
-// (S_k^-1, L_k: 2 doubles per stage per lane) in REGISTERS and fully unrolls the two KKT sweeps;
-// Solver<NX, 0> takes the horizon at run time and keeps those tiles in LDS.
-// LDS per instance (doubles): scaled [A|B] tiles [NS][72] and 19 vectors [NS][8] (NS = N+1, everything
-// padded to 8 per stage so that index = 8*stage + component): 37.7 KB at N = 20, i.e. 4 instances per
-// CU (one wavefront per SIMD), which is exactly BASELINE configs[1] (1024 instances) in one residency.
+// Solver<NX, NT, NW, MF, GS, TAIL> is one template for all 21 kernels (DESIGN.md section 4 has the table):
+//   NW = 1   one wavefront per instance, tiles [i][j] in lane 8 i + j, products through LDS tiles; NT = 0
+//            takes the horizon at run time and keeps the factor tiles in LDS (validation kernels)
+//   NW = 2   the two elimination chains on two wavefronts.  MF: every 8x8 product on the matrix cores
+//            (v_mfma_f64_4x4x4, matrices in "D form", see mm8), the factor tiles in the operand registers
+//            of the MFMA sweeps, the element state of an iteration in registers.  This is the headline
+//            kernel, admm_solve_kernel<6, 20, 2, true>: 39.9 KB of LDS and 256 registers per wavefront,
+//            i.e. four instances per CU, and configs[1] (1024 instances) is exactly one residency
+//   NW = 4   each chain relayed over two wavefronts (latency forms, kernel_variant 9, and the long planner horizons)
+//   NW = 8, TAIL   the whole-CU kernel that finishes parked stragglers with a dense K^-1 in registers
+// LDS per instance (doubles): scaled [A|B] tiles [NS][72] and the vectors [NS][8] (NS = N+1, everything
+// padded to 8 per stage so that index = 8*stage + component).
 #include <atomic>
 #include <type_traits>
 
@@ -994,6 +1001,50 @@ struct Solver {
     __device__ __forceinline__ static double mm8(double at, double b, double c) { return mm8r(rep_a(at), rep_b(b), c); }
     __device__ __forceinline__ double transpose_d(double v) const { return __shfl(v, tlane); }
     // Cholesky S = C C' merged with the forward substitution C W = I, in D form (see chol_inverse)
+    // The update of W at pivot T -- row T takes w[T][.] rs, the rows below it w -= c[i][T] (w[T][.] rs), the rows above stay -- is written
+    // with the execution mask instead of selects: which lanes hold row T and which the rows below it is a compile-time constant of the
+    // unrolled step (row i sits in the 8 lanes of group dgroup(i)), so scalar instructions with literal masks replace four v_cndmask per
+    // pivot (and the sixteen mask pairs the selects kept in scalar registers).  The fused multiply-add runs on rows T .. 7 -- the same
+    // v_fma_f64 on the same operands as the select form's -- and row T is then overwritten: the values are those of
+    // "if (li == T) w = wtj; else if (li > T) w -= cit * wtj", bit for bit (tools/ab_equal.py).  The masks are applied to the two halves
+    // of exec as 32-bit literals: handed over as 64-bit values in scalar register pairs, the two masks that are sign-extended 32-bit
+    // numbers were materialised by "s_mov_b64 <pair>, <32-bit literal>" and every D-form kernel computed wrong values on the device, as
+    // if the upper 32 lanes were masked off (docs/HISTORY.md); literals also keep the masks out of the scalar registers.  The trailing s_nop covers
+    // the two wait states a DPP move needs behind a vector write of its source (the compiler does not look into the statement).
+    __device__ __forceinline__ static constexpr unsigned long long row_mask_d(int i) { return 0xFFull << (8 * dgroup(i)); }
+    __device__ __forceinline__ static constexpr unsigned long long rows_from_d(int t) {
+        unsigned long long m = 0;
+        for (int i = t; i < 8; ++i) m |= row_mask_d(i);
+        return m;
+    }
+    template <int T>
+    __device__ __forceinline__ static double chol_w_update(double w, double cit, double wtj) {
+        unsigned long long sv;
+        constexpr unsigned long long ge = rows_from_d(T), mt = row_mask_d(T);
+        if constexpr (T < 7)
+            asm("s_mov_b64 %[sv], exec\n\t"
+                "s_and_b32 exec_lo, exec_lo, %[gl]\n\t"
+                "s_and_b32 exec_hi, exec_hi, %[gh]\n\t"
+                "v_fma_f64 %[w], -%[c], %[t], %[w]\n\t"
+                "s_and_b32 exec_lo, exec_lo, %[tl]\n\t"
+                "s_and_b32 exec_hi, exec_hi, %[th]\n\t"
+                "v_mov_b64 %[w], %[t]\n\t"
+                "s_mov_b64 exec, %[sv]\n\t"
+                "s_nop 1"
+                : [w] "+v"(w), [sv] "=&s"(sv)
+                : [c] "v"(cit), [t] "v"(wtj), [gl] "i"((int)(unsigned)(ge & 0xFFFFFFFFull)), [gh] "i"((int)(unsigned)(ge >> 32)),
+                  [tl] "i"((int)(unsigned)(mt & 0xFFFFFFFFull)), [th] "i"((int)(unsigned)(mt >> 32)) : "scc");
+        else
+            asm("s_mov_b64 %[sv], exec\n\t"
+                "s_and_b32 exec_lo, exec_lo, %[tl]\n\t"
+                "s_and_b32 exec_hi, exec_hi, %[th]\n\t"
+                "v_mov_b64 %[w], %[t]\n\t"
+                "s_mov_b64 exec, %[sv]\n\t"
+                "s_nop 1"
+                : [w] "+v"(w), [sv] "=&s"(sv)
+                : [t] "v"(wtj), [tl] "i"((int)(unsigned)(mt & 0xFFFFFFFFull)), [th] "i"((int)(unsigned)(mt >> 32)) : "scc");
+        return w;
+    }
     __device__ __forceinline__ double chol_inverse_d(double s) const {
         double w = (li == lj) ? 1.0 : 0.0;
 #define LPVMPC_CHOL_STEP_D(T)                                                                                 \
@@ -1006,7 +1057,7 @@ struct Solver {
             const double wtj = __shfl(w, G * 8 + lj) * rs;                                                        \
             s -= cit * cjt;     /* (unconditional: rows / columns <= T are never read again -- pivot, column and row of a later */ \
                                 /* step T' lie in the trailing block, and s itself is not returned) */                    \
-            if (li == (T)) w = wtj; else if (li > (T)) w -= cit * wtj;                                            \
+            w = chol_w_update<(T)>(w, cit, wtj);                                                                  \
         }
         LPVMPC_CHOL_STEP_D(0) LPVMPC_CHOL_STEP_D(1) LPVMPC_CHOL_STEP_D(2) LPVMPC_CHOL_STEP_D(3)
         LPVMPC_CHOL_STEP_D(4) LPVMPC_CHOL_STEP_D(5) LPVMPC_CHOL_STEP_D(6)

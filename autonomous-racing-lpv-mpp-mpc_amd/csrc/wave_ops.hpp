@@ -102,7 +102,9 @@ __device__ inline double bcast_lane(double v) {
 template <int T>
 __device__ inline double bcast_row(double v) {
     const long x = __double_as_longlong(v);
-    long y = __builtin_amdgcn_update_dpp(x, x, 0x150 + T, 0xF, 0x3, false);         // row_newbcast:T     -> lanes 0..7 of the row
+    long y;                                          // every lane is written by one of the two moves: the start value is irrelevant
+    asm volatile("" : "=v"(y));                      // (started from x the destination costs a 64-bit copy whenever v stays live)
+    y = __builtin_amdgcn_update_dpp(y, x, 0x150 + T, 0xF, 0x3, false);              // row_newbcast:T     -> lanes 0..7 of the row
     y = __builtin_amdgcn_update_dpp(y, x, 0x158 + T, 0xF, 0xC, false);              // row_newbcast:8 + T -> lanes 8..15
     return __longlong_as_double(y);
 }
