@@ -121,6 +121,7 @@ ACT_WORDS = 2 * ACT_MAX_DELAY + 2        # LPVMPC_ACT_WORDS: [motor ring, servo 
 
 PLANT_WORDS = 7                          # LPVMPC_PLANT_WORDS: [lf, lr, m, Iz, Cf, Cr, mu] per vehicle
 PLANT_WORD_NAMES = ("lf", "lr", "m", "Iz", "Cf", "Cr", "mu")
+MODEL_WORDS = 7                          # LPVMPC_MODEL_WORDS: the same words, as a controller's / planner's model of the vehicle
 
 OBSERVER_AUX = 30 + 36 + 12      # L_gain [6][5], A_obs [6][6], B_obs [6][2] per instance (lpvmpc_observer_step_batch)
 
@@ -137,7 +138,8 @@ EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_d
            "lpvmpc_race_laps", "lpvmpc_race_predictions", "lpvmpc_race_init_observed",
            "lpvmpc_actuator_default_config", "lpvmpc_plant_step_actuated_batch", "lpvmpc_cl_init_actuated", "lpvmpc_race_init_actuated",
            "lpvmpc_actuator_read", "lpvmpc_race_record", "lpvmpc_race_record_read", "lpvmpc_race_lap_stats",
-           "lpvmpc_plant_step_vehicles_batch", "lpvmpc_cl_init_vehicles", "lpvmpc_race_init_vehicles", "lpvmpc_plant_params_read")
+           "lpvmpc_plant_step_vehicles_batch", "lpvmpc_cl_init_vehicles", "lpvmpc_race_init_vehicles", "lpvmpc_plant_params_read",
+           "lpvmpc_set_model_params", "lpvmpc_model_params_read")
 
 _lib = None
 
@@ -267,6 +269,13 @@ def load():
         lib.lpvmpc_race_init_vehicles.argtypes = [vp, vp, vp, _i, vp, vp, P(RaceConfig), P(ObserverConfig), P(ActuatorConfig), vp, vp, vp]
         lib.lpvmpc_plant_params_read.argtypes = [vp, vp]
         for name in ("lpvmpc_plant_step_vehicles_batch", "lpvmpc_cl_init_vehicles", "lpvmpc_race_init_vehicles", "lpvmpc_plant_params_read"):
+            getattr(lib, name).restype = C.c_int
+    except AttributeError:
+        pass
+    try:        # (nor the per-vehicle model parameters)
+        lib.lpvmpc_set_model_params.argtypes = [vp, _i, vp]
+        lib.lpvmpc_model_params_read.argtypes = [vp, P(_i), vp]
+        for name in ("lpvmpc_set_model_params", "lpvmpc_model_params_read"):
             getattr(lib, name).restype = C.c_int
     except AttributeError:
         pass

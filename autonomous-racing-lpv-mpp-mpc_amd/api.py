@@ -310,6 +310,31 @@ class BatchedSolver:
         self._chk(self._lib.lpvmpc_plant_params_read(self._h, ptr(out)))
         return out
 
+    def set_model_params(self, rows):
+        """Bind per-vehicle model rows [B, 7] = (lf, lr, m, Iz, Cf, Cr, mu) to this engine (lpvmpc_set_model_params): every call
+        that linearises -- lpv, estimate_abc, solve*, and a fleet, cascade or race started afterwards -- then takes vehicle b's row
+        instead of the engine's own vehicle, must have batch size B, and in the controller roll-out takes the row's Cf for both
+        axles (cf_new is ignored).  ``None`` unbinds.  Refused while the engine runs a fleet, cascade or race."""
+        if rows is None:
+            self._chk(self._lib.lpvmpc_set_model_params(self._h, 0, None))
+            return
+        a = np.asarray(rows)
+        if a.ndim != 2 or a.shape[0] < 1:
+            raise ValueError("model_params has shape %s, expected (B, %d) with B >= 1" % (a.shape, _ffi.MODEL_WORDS))
+        from .model import check_model_params
+        a = check_model_params(a, a.shape[0])
+        self._chk(self._lib.lpvmpc_set_model_params(self._h, a.shape[0], ptr(a)))
+
+    def model_params_read(self):
+        """The bound model rows [B, 7] (lpvmpc_model_params_read), or None while nothing is bound."""
+        B = C.c_int32(0)
+        self._chk(self._lib.lpvmpc_model_params_read(self._h, C.byref(B), None))
+        if B.value == 0:
+            return None
+        out = np.empty((B.value, _ffi.MODEL_WORDS))
+        self._chk(self._lib.lpvmpc_model_params_read(self._h, C.byref(B), ptr(out)))
+        return out
+
     def cl_init(self, plant0, half_width, slack, q9_swap=True, n_sub=7, dt_sim=0.005, mu_sim=0.05, actuator=None, delay_a=None,
                 delay_df=None, plant_params=None):
         """Start a lap-0 fleet.  ``actuator`` (an ``actuator.actuator_config`` result, even an all-off one) selects
@@ -949,10 +974,13 @@ class RaceFleet(object):
     ``actuator``: an ``actuator.actuator_config(...)`` result puts the actuator delays / servo lag in the plant (per-vehicle
     delay_a / delay_df in steps); ``steering_delay``: both controllers' steeringDelay (needs ``actuator``, e.g.
     actuator.controller_delay(delay_df_s)).  ``plant_params``: [B, 7] rows (lf, lr, m, Iz, Cf, Cr, mu) give every vehicle its own
-    plant (plant.sample_plant_params for a mismatch sweep); the controllers and the planner keep the nominal model."""
+    plant (plant.sample_plant_params for a mismatch sweep); the controllers and the planner keep the nominal model unless
+    ``model_params`` is given: [B, 7] rows bound to the path, tt and planner engines (BatchedSolver.set_model_params), or the string
+    "plant": each vehicle's model is its plant row (the matched experiment; the nominal plant rows where plant_params is None or
+    "nominal")."""
 
     def __init__(self, track_map, plant0, laps=1, N=20, Np=40, half_track0=None, device=0, estimator=None, actuator=None,
-                 steering_delay=0, delay_a=None, delay_df=None, plant_params=None, **options):
+                 steering_delay=0, delay_a=None, delay_df=None, plant_params=None, model_params=None, **options):
         from .workloads import CTRL_TUNINGS, PLAN_L, PLAN_Q, PLAN_R, PLAN_dR
         race_keys = ("n_sub_lap0", "n_sub", "q9_swap", "plan_max_ey", "dt_sim", "mu_sim")
         race_opts = {k: v for k, v in options.items() if k in race_keys}
@@ -969,6 +997,19 @@ class RaceFleet(object):
                 e.set_option(k, int(v))
         self.planner.handoff_setup()
         self.dt_sim = float(race_opts.get("dt_sim", 0.005))
+        if model_params is not None:
+            B = f64(plant0).reshape(-1, 8).shape[0]
+            if isinstance(model_params, str):
+                if model_params != "plant":
+                    raise ValueError("model_params must be [B, 7] rows or \"plant\", got %r" % (model_params,))
+                from .plant import plant_params as nominal_plant
+                rows = (nominal_plant(B, self.path, race_opts.get("mu_sim", 0.05)) if plant_params is None or _is_nominal(plant_params)
+                        else _plant_rows(plant_params, B))
+            else:
+                from .model import check_model_params
+                rows = check_model_params(model_params, B)
+            for e in (self.path, self.tt, self.planner):
+                e.set_model_params(rows)
         self.path.race_init(self.tt, self.planner, plant0, half_track0=half_track0, laps=laps, half_width=track_map.halfWidth,
                             slack=track_map.slack, estimator=estimator, actuator=actuator, delay_a=delay_a, delay_df=delay_df,
                             plant_params=plant_params, **race_opts)
@@ -992,6 +1033,10 @@ class RaceFleet(object):
     def plant_params(self):
         """The vehicles' plant rows [B, 7] of a race started with ``plant_params`` (BatchedSolver.plant_params_read)."""
         return self.path.plant_params_read()
+
+    def model_params(self):
+        """The model rows [B, 7] bound to the race's three engines by ``model_params`` (read from the path engine), or None."""
+        return self.path.model_params_read()
 
     def lap_times(self):
         """[B, laps+1] simulated seconds of lap 0, 1, ..., laps (NaN where the lap has not been completed)."""

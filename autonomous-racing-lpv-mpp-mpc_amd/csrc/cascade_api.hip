@@ -141,6 +141,8 @@ extern "C" int lpvmpc_cascade_init(lpvmpc_handle *h, lpvmpc_handle *plan, int32_
         return fail(h, LPVMPC_E_ARG, "lpvmpc_cascade_init: bad argument (lap0 must be >= 1: the cascade is the racing phase)");
     rc = lpvmpc_need_track(h, "lpvmpc_cascade_init"); if (rc) return rc;
     rc = lpvmpc_check_common(plan, B, "lpvmpc_cascade_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
+    rc = lpvmpc_model_check(h, B, "lpvmpc_cascade_init"); if (rc) return rc;
+    rc = lpvmpc_model_check(plan, B, "lpvmpc_cascade_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
     lpvmpc_cascade_free(h);
     lpvmpc_cascade *c = new (std::nothrow) lpvmpc_cascade();
     if (!c) return fail(h, LPVMPC_E_NOMEM, "out of host memory");
@@ -192,11 +194,11 @@ static int planner_tick(lpvmpc_handle *h, lpvmpc_cascade *c) {
     const double *x0;
     if (c->plan_ticks == 0) {                                                    // first_it == 1: seed trajectory, measured x0
         HIP_TRY(h, lpvmpc::launch_plan_first(p->d_cfg, B, c->estv ? c->estv : c->plant, c->hw, c->slack, c->q9, 0.2, c->px0, p->d_xlast, p->d_delta, st));
-        HIP_TRY(h, lpvmpc::launch_abc(p->dev, p->d_cfg, B, p->d_xlast, p->d_delta, p->d_AB, st));
+        HIP_TRY(h, lpvmpc::launch_abc(p->dev, p->d_cfg, p->d_model, B, p->d_xlast, p->d_delta, p->d_AB, st));
         x0 = c->px0;
     } else {                                                                     // x0 = Planner.xPred[1,:], LPVPrediction(x0, SS, uPred)
         HIP_TRY(h, hipMemcpy2DAsync(p->d_x0, 5 * 8, p->d_xPred + 5, (size_t)(Np + 1) * 5 * 8, 5 * 8, B, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(h, lpvmpc::launch_lpv(p->dev, p->d_cfg, B, p->d_x0, p->d_uPred, nullptr, c->SSp, 60.0, 0, p->d_states, p->d_AB, st));
+        HIP_TRY(h, lpvmpc::launch_lpv(p->dev, p->d_cfg, p->d_model, B, p->d_x0, p->d_uPred, nullptr, c->SSp, 60.0, 0, p->d_states, p->d_AB, st));
         x0 = p->d_x0;
     }
     // uOld of the planner is always (0, 0): its node only appends to OldSteering / OldAccelera
@@ -239,7 +241,7 @@ extern "C" int lpvmpc_cascade_tick(lpvmpc_handle *h, int32_t n_ticks) {
             HIP_TRY(h, hipEventRecord(c->ev_plan, sp));
         }
         // Controller_TT.LPVPrediction(LocalState, uPred, vel_ref, curv_ref, Cf_new, LapNumber >= 1); solve(LocalState, ...)  (CMAIN:361-363)
-        HIP_TRY(h, lpvmpc::launch_lpv(h->dev, h->d_cfg, B, c->local, h->d_uPred, h->d_vel, h->d_curv, 60.0, 1, h->d_states, h->d_AB, st));
+        HIP_TRY(h, lpvmpc::launch_lpv(h->dev, h->d_cfg, h->d_model, B, c->local, h->d_uPred, h->d_vel, h->d_curv, 60.0, 1, h->d_states, h->d_AB, st));
         SolveArgs a{B, c->local, h->d_AB, h->d_vel, h->d_uold, nullptr, h->d_xPred, h->d_uPred, h->d_status, h->d_iters, h->d_polish, h->d_resid,
                     h->warm_mode ? h->d_state : nullptr, (h->warm_mode && h->state_valid_B == B) ? h->warm_mode : 0, 6};
         int rc = lpvmpc_launch_solve_timed(h, a, st); if (rc) return rc;

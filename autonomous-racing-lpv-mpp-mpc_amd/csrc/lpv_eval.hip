@@ -307,23 +307,32 @@ __global__ void __launch_bounds__(64) plan_abc_kernel(const DevCfg *__restrict__
         for (int a = 0; a < 7; ++a) o[r * 7 + a] = ab[r][a];
 }
 
-hipError_t launch_lpv(const DevCfg &cfg, const DevCfg *dcfg, int B, const double *x0, const double *u_prev, const double *vel_ref,
-                      const double *curv_s, double cf_new, int lap, double *states, double *AB, hipStream_t stream, const int32_t *active) {
+// model: the handle's model table [kModelWords][B] (lpvmpc_set_model_params), null: the handle's own words.  With a table the kernels
+// that read vehicle words are replaced by their per-vehicle forms (veh_lpv_eval.hip), which take vehicle b's row and, in the
+// controller roll-out, its Cf for both axles instead of cf_new; ctrl_lpv_roll_kernel reads no vehicle word and is launched as it is
+hipError_t launch_lpv(const DevCfg &cfg, const DevCfg *dcfg, const double *model, int B, const double *x0, const double *u_prev,
+                      const double *vel_ref, const double *curv_s, double cf_new, int lap, double *states, double *AB, hipStream_t stream,
+                      const int32_t *active) {
     const int blocks = (B + 63) / 64;
     if (cfg.kind == 0 && AB) {
-        hipLaunchKernelGGL(ctrl_lpv_pre_kernel, dim3((B * cfg.N + 63) / 64), dim3(64), 0, stream, dcfg, B, u_prev, vel_ref, cf_new, AB, active);
+        if (model) launch_ctrl_lpv_pre_veh(dcfg, model, B, cfg.N, u_prev, vel_ref, AB, stream, active);
+        else hipLaunchKernelGGL(ctrl_lpv_pre_kernel, dim3((B * cfg.N + 63) / 64), dim3(64), 0, stream, dcfg, B, u_prev, vel_ref, cf_new, AB, active);
         hipLaunchKernelGGL(ctrl_lpv_roll_kernel, dim3(blocks), dim3(64), 0, stream, dcfg, B, x0, u_prev, curv_s, lap, states, AB, active);
-    } else if (cfg.kind == 0)
+    } else if (model)
+        launch_lpv_veh(cfg.kind, dcfg, model, B, x0, u_prev, vel_ref, curv_s, lap, states, AB, stream, active);
+    else if (cfg.kind == 0)
         hipLaunchKernelGGL(ctrl_lpv_kernel, dim3(blocks), dim3(64), 0, stream, dcfg, B, x0, u_prev, vel_ref, curv_s, cf_new, lap, states, AB, active);
     else
         hipLaunchKernelGGL(plan_lpv_kernel, dim3(blocks), dim3(64), 0, stream, dcfg, B, x0, u_prev, curv_s, states, AB, active);
     return hipGetLastError();
 }
 
-hipError_t launch_abc(const DevCfg &cfg, const DevCfg *dcfg, int B, const double *xlast, const double *delta, double *AB, hipStream_t stream,
-                      const int32_t *active) {
+hipError_t launch_abc(const DevCfg &cfg, const DevCfg *dcfg, const double *model, int B, const double *xlast, const double *delta, double *AB,
+                      hipStream_t stream, const int32_t *active) {
     const int blocks = (B * cfg.N + 63) / 64;
-    if (cfg.kind == 0)
+    if (model)
+        launch_abc_veh(cfg.kind, dcfg, model, B, cfg.N, xlast, delta, AB, stream, active);
+    else if (cfg.kind == 0)
         hipLaunchKernelGGL(ctrl_abc_kernel, dim3(blocks), dim3(64), 0, stream, dcfg, B, xlast, delta, AB, active);
     else
         hipLaunchKernelGGL(plan_abc_kernel, dim3(blocks), dim3(64), 0, stream, dcfg, B, xlast, delta, AB, active);

@@ -178,6 +178,7 @@ extern "C" lpvmpc_handle *lpvmpc_create(const lpvmpc_config *cfg) {
     h->defer_stream_set = false; h->defer_tail = 1; h->defer_skip_pass = false;
     h->h_pack_in = h->h_pack_out = h->d_pack_in = h->d_pack_out = nullptr;
     h->obs_cfg = nullptr; h->obs_gains = h->obs_state = nullptr; h->obs_ws = nullptr; h->obs_ws_cap = 0; h->obs_B = 0;
+    h->d_model = nullptr; h->model_B = 0;
     DevCfg &d = h->dev;
     std::memset(&d, 0, sizeof(d));
     d.kind = cfg->kind; d.N = cfg->N; d.track_rows = cfg->track_rows; d.max_iter = cfg->max_iter;
@@ -222,6 +223,7 @@ extern "C" void lpvmpc_destroy(lpvmpc_handle *h) {
     if (h->cl_cmd) (void)hipFree(h->cl_cmd);
     lpvmpc_act_free(h->cl_act);
     lpvmpc_plant_free(h->cl_veh);
+    lpvmpc_model_free(h);
     if (h->cascade) lpvmpc_cascade_free(h);                                  // (frees the cascade's estimator state)
     if (h->race) lpvmpc_race_free(h);
     if (h->race_owner && h->race_owner->race) lpvmpc_race_free(h->race_owner);   // a handle the race of another one drives: end that race
@@ -335,7 +337,7 @@ int lpvmpc_need_track(lpvmpc_handle *h, const char *who) {
 
 static int launch_lpv(lpvmpc_handle *h, int B, const double *x0, const double *u_prev, const double *vel_ref,
                       const double *curv_s, double cf_new, int lap, double *states, double *AB, hipStream_t st) {
-    HIP_TRY(h, lpvmpc::launch_lpv(h->dev, h->d_cfg, B, x0, u_prev, vel_ref, curv_s, cf_new, lap, states, AB, st));
+    HIP_TRY(h, lpvmpc::launch_lpv(h->dev, h->d_cfg, h->d_model, B, x0, u_prev, vel_ref, curv_s, cf_new, lap, states, AB, st));
     return LPVMPC_OK;
 }
 
@@ -426,6 +428,7 @@ extern "C" int lpvmpc_lpv_batch(lpvmpc_handle *h, int32_t B, const double *x0, c
                                 double *states, double *A, double *Bm) {
     if (h && B == 0) return LPVMPC_OK;                                   // an empty batch is a no-op
     int rc = lpvmpc_check_batch(h, B, "lpvmpc_lpv_batch"); if (rc) return rc;
+    rc = lpvmpc_model_check(h, B, "lpvmpc_lpv_batch"); if (rc) return rc;
     const bool ctrl = h->cfg.kind == LPVMPC_KIND_CONTROLLER;
     if (!x0 || !u_prev) return fail(h, LPVMPC_E_ARG, "lpvmpc_lpv_batch: x0 / u_prev is NULL");
     if (ctrl && !vel_ref) return fail(h, LPVMPC_E_ARG, "lpvmpc_lpv_batch: controller needs vel_ref");
@@ -466,12 +469,13 @@ extern "C" int lpvmpc_estimate_abc_batch(lpvmpc_handle *h, int32_t B, const doub
                                          double *A, double *Bm) {
     if (h && B == 0) return LPVMPC_OK;                                   // an empty batch is a no-op
     int rc = lpvmpc_check_batch(h, B, "lpvmpc_estimate_abc_batch"); if (rc) return rc;
+    rc = lpvmpc_model_check(h, B, "lpvmpc_estimate_abc_batch"); if (rc) return rc;
     if (!xlast || !delta) return fail(h, LPVMPC_E_ARG, "lpvmpc_estimate_abc_batch: NULL input");
     rc = lpvmpc_need_track(h, "lpvmpc_estimate_abc_batch"); if (rc) return rc;
     const size_t N = h->cfg.N, nx = h->nx, nb = h->nb, b = B;
     hipStream_t st = h->stream;
     H2D(h->d_xlast, xlast, b * N * 6 * 8); H2D(h->d_delta, delta, b * N * 8);
-    HIP_TRY(h, lpvmpc::launch_abc(h->dev, h->d_cfg, B, h->d_xlast, h->d_delta, h->d_AB, st));
+    HIP_TRY(h, lpvmpc::launch_abc(h->dev, h->d_cfg, h->d_model, B, h->d_xlast, h->d_delta, h->d_AB, st));
     std::vector<double> ab(b * N * nx * nb);
     D2H(ab.data(), h->d_AB, ab.size() * 8);
     HIP_TRY(h, hipStreamSynchronize(st));
@@ -534,6 +538,7 @@ extern "C" int lpvmpc_solve_batch_dev(lpvmpc_handle *h, int32_t B, const double 
                                       int32_t *status, int32_t *iters, double *resid, int32_t *polish, void *stream) {
     if (h && B == 0) return LPVMPC_OK;                                   // an empty batch is a no-op
     int rc = lpvmpc_check_batch(h, B, "lpvmpc_solve_batch_dev"); if (rc) return rc;
+    rc = lpvmpc_model_check(h, B, "lpvmpc_solve_batch_dev"); if (rc) return rc;
     const bool ctrl = h->cfg.kind == LPVMPC_KIND_CONTROLLER;
     if (!x0 || !u_prev || !xPred || !uPred) return fail(h, LPVMPC_E_ARG, "lpvmpc_solve_batch_dev: NULL x0 / u_prev / xPred / uPred");
     if (ctrl && !vel_ref) return fail(h, LPVMPC_E_ARG, "lpvmpc_solve_batch_dev: controller needs vel_ref");
@@ -618,6 +623,7 @@ extern "C" int lpvmpc_solve_batch(lpvmpc_handle *h, int32_t B, const double *x0,
                                   int32_t *status, int32_t *iters, double *resid, int32_t *polish) {
     if (h && B == 0) return LPVMPC_OK;                                   // an empty batch is a no-op
     int rc = lpvmpc_check_batch(h, B, "lpvmpc_solve_batch"); if (rc) return rc;
+    rc = lpvmpc_model_check(h, B, "lpvmpc_solve_batch"); if (rc) return rc;
     const bool ctrl = h->cfg.kind == LPVMPC_KIND_CONTROLLER;
     if (!x0 || !u_prev) return fail(h, LPVMPC_E_ARG, "lpvmpc_solve_batch: x0 / u_prev is NULL");
     if (ctrl && !vel_ref) return fail(h, LPVMPC_E_ARG, "lpvmpc_solve_batch: controller needs vel_ref");
@@ -655,6 +661,7 @@ extern "C" int lpvmpc_solve_batch_masked(lpvmpc_handle *h, int32_t B, const doub
                                          int32_t *status, int32_t *iters, double *resid, int32_t *polish, const int32_t *active) {
     if (h && B == 0) return LPVMPC_OK;                                   // an empty batch is a no-op
     int rc = lpvmpc_check_batch(h, B, "lpvmpc_solve_batch_masked"); if (rc) return rc;
+    rc = lpvmpc_model_check(h, B, "lpvmpc_solve_batch_masked"); if (rc) return rc;
     if (!active) return fail(h, LPVMPC_E_ARG, "lpvmpc_solve_batch_masked: active is NULL");
     std::vector<int32_t> rows;
     for (int i = 0; i < B; ++i) if (active[i]) rows.push_back(i);
@@ -749,6 +756,7 @@ static int cl_init(lpvmpc_handle *h, int32_t B, const double *plant0, double hal
                    int32_t n_sub, double dt_sim, double mu_sim, const lpvmpc_actuator_config *act, const int32_t *delay_a, const int32_t *delay_df,
                    const std::vector<double> *veh = nullptr) {
     int rc = lpvmpc_check_common(h, B, "lpvmpc_cl_init"); if (rc) return rc;
+    rc = lpvmpc_model_check(h, B, "lpvmpc_cl_init"); if (rc) return rc;
     if (h->cfg.kind != LPVMPC_KIND_CONTROLLER) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: controller handles only");
     if (h->race || h->race_owner) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: this handle takes part in a race (lpvmpc_cl_release on its path handle ends it)");
     if (h->cfg.N > 20) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: the reference's seed trajectories have 20 rows (N <= 20)");
@@ -830,10 +838,10 @@ extern "C" int lpvmpc_cl_tick(lpvmpc_handle *h, int32_t n_ticks) {
         const double *x0 = h->cl_local; int x0_stride = 6;
         if (h->cl_first_it < 10) {                                           // CMAIN:310-315: seed mode
             HIP_TRY(h, lpvmpc::launch_cl_seed(B, N, h->cl_local, h->d_xlast, h->d_delta, st));
-            HIP_TRY(h, lpvmpc::launch_abc(h->dev, h->d_cfg, B, h->d_xlast, h->d_delta, h->d_AB, st));
+            HIP_TRY(h, lpvmpc::launch_abc(h->dev, h->d_cfg, h->d_model, B, h->d_xlast, h->d_delta, h->d_AB, st));
             h->cl_first_it++;
         } else {                                                             // CMAIN:325-331: LPV prediction, x0 = first rolled-out state
-            HIP_TRY(h, lpvmpc::launch_lpv(h->dev, h->d_cfg, B, h->cl_local, h->d_uPred, h->d_vel, nullptr, 60.0, 0, h->d_states, h->d_AB, st));
+            HIP_TRY(h, lpvmpc::launch_lpv(h->dev, h->d_cfg, h->d_model, B, h->cl_local, h->d_uPred, h->d_vel, nullptr, 60.0, 0, h->d_states, h->d_AB, st));
             x0 = h->d_states; x0_stride = N * 6;
         }
         SolveArgs a{B, x0, h->d_AB, h->d_vel, h->d_uold, nullptr, h->d_xPred, h->d_uPred, h->d_status, h->d_iters, h->d_polish, h->d_resid,

@@ -97,12 +97,23 @@ constexpr int LPVMPC_PENDING_ = -11; // status of a parked instance until its re
 int solve_has_fast_path(int kind, int N);
 size_t solve_lds_bytes(int kind, int N);
 hipError_t launch_solve(const DevCfg &cfg, const DevCfg *dcfg, const SolveArgs &a, hipStream_t stream, int force_generic);
-// active: optional [B] instance mask (null: every instance); a masked instance's rows of states / AB are not written
-hipError_t launch_lpv(const DevCfg &cfg, const DevCfg *dcfg, int B, const double *x0, const double *u_prev, const double *vel_ref,
-                      const double *curv_s, double cf_new, int lap, double *states, double *AB, hipStream_t stream,
+// active: optional [B] instance mask (null: every instance); a masked instance's rows of states / AB are not written.
+// model: the handle's per-vehicle model table (below), or null: the handle's own vehicle words
+hipError_t launch_lpv(const DevCfg &cfg, const DevCfg *dcfg, const double *model, int B, const double *x0, const double *u_prev,
+                      const double *vel_ref, const double *curv_s, double cf_new, int lap, double *states, double *AB, hipStream_t stream,
                       const int32_t *active = nullptr);
-hipError_t launch_abc(const DevCfg &cfg, const DevCfg *dcfg, int B, const double *xlast, const double *delta, double *AB, hipStream_t stream,
-                      const int32_t *active = nullptr);
+hipError_t launch_abc(const DevCfg &cfg, const DevCfg *dcfg, const double *model, int B, const double *xlast, const double *delta, double *AB,
+                      hipStream_t stream, const int32_t *active = nullptr);
+// per-vehicle model parameters (veh_lpv_eval.hip; lpvmpc_set_model_params, include/lpvmpc.h "Per-vehicle model parameters"): the
+// handle's table [kModelWords][B], parameter-major and vehicle-minor like the plant table below, indexed by vehicle (not by launch
+// slot: masked launches read the rows of the vehicles they run).  The launchers of the per-vehicle forms, called by the two above
+constexpr int kModelWords = 7;               // = LPVMPC_MODEL_WORDS: lf, lr, m, Iz, Cf, Cr, mu
+void launch_ctrl_lpv_pre_veh(const DevCfg *dcfg, const double *model, int B, int N, const double *u_prev, const double *vel_ref, double *AB,
+                             hipStream_t stream, const int32_t *active);
+void launch_lpv_veh(int kind, const DevCfg *dcfg, const double *model, int B, const double *x0, const double *u_prev, const double *vel_ref,
+                    const double *curv_s, int lap, double *states, double *AB, hipStream_t stream, const int32_t *active);
+void launch_abc_veh(int kind, const DevCfg *dcfg, const double *model, int B, int N, const double *xlast, const double *delta, double *AB,
+                    hipStream_t stream, const int32_t *active);
 
 // closed-loop helpers (closed_loop.hip)
 struct PlantCfg { double lf, lr, m, Iz, mu, dt; int n_sub; };

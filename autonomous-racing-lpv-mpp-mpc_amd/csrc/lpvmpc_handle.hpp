@@ -87,6 +87,10 @@ struct lpvmpc_handle {
     lpvmpc::ObsParams obs_p;
     char *obs_ws;                       // lpvmpc_observer_step_batch staging, obs_ws_cap instances
     int obs_ws_cap;
+    // per-vehicle model parameters (lpvmpc_set_model_params, model_params_api.hip): the table [kModelWords][model_B] that every LPV /
+    // ABC launch of this handle takes (lpvmpc::launch_lpv / launch_abc), null: the handle's own vehicle words
+    double *d_model;
+    int model_B;
 };
 
 LPVMPC_HIDDEN int lpvmpc_fail(lpvmpc_handle *h, int code, const char *fmt, ...);
@@ -126,6 +130,10 @@ LPVMPC_HIDDEN int lpvmpc_plant_rows(lpvmpc_handle *h, int B, const double *rows,
 LPVMPC_HIDDEN int lpvmpc_plant_upload(lpvmpc_handle *h, int B, const std::vector<double> &t, double dt_sim, int n_sub, lpvmpc::VehPlantCfg &v);
 LPVMPC_HIDDEN void lpvmpc_plant_free(lpvmpc::VehPlantCfg &v);
 LPVMPC_HIDDEN const lpvmpc::VehPlantCfg *lpvmpc_race_plant(const lpvmpc_handle *h);                     // race_api.hip: the race's table
+// model_params_api.hip: lpvmpc_model_check refuses a batch size other than that of the handle's bound model rows (unbound: any);
+// called by every entry point that linearises, before anything is launched.  lpvmpc_model_free unbinds and frees the table
+LPVMPC_HIDDEN int lpvmpc_model_check(lpvmpc_handle *h, int B, const char *who);
+LPVMPC_HIDDEN void lpvmpc_model_free(lpvmpc_handle *h);
 namespace lpvmpc {
 // handoff.hip (host): interpolation operator W and interpolation + filtfilt operator FW, both [M][N] row-major
 bool handoff_operators(int N, double dt, double interp_dt, int padlen, int ord, const double *b, const double *a,

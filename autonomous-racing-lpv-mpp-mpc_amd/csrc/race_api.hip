@@ -108,6 +108,9 @@ static int race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, i
     rc = lpvmpc_check_common(h, B, "lpvmpc_race_init"); if (rc) return rc;
     rc = lpvmpc_check_common(tt, B, "lpvmpc_race_init(tt)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
     rc = lpvmpc_check_common(plan, B, "lpvmpc_race_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
+    rc = lpvmpc_model_check(h, B, "lpvmpc_race_init"); if (rc) return rc;
+    rc = lpvmpc_model_check(tt, B, "lpvmpc_race_init(tt)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
+    rc = lpvmpc_model_check(plan, B, "lpvmpc_race_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
     lpvmpc::ActDev a{};
     if (act) { rc = lpvmpc_act_alloc(h, B, act, delay_a, delay_df, cfg->dt_sim, veh ? "lpvmpc_race_init_vehicles" : "lpvmpc_race_init_actuated", a); if (rc) { lpvmpc_act_free(a); return rc; } }
     lpvmpc::VehPlantCfg v{};
@@ -239,8 +242,8 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
     for (int t = 0; t < n_ticks; ++t) {
         // planner ticks of the racing vehicles whose controller tick reads a new message (PMAIN:126-224, 257-308)
         HIP_TRY(h, lpvmpc::launch_race_plan_start(p->d_cfg, d, st));
-        HIP_TRY(h, lpvmpc::launch_lpv(p->dev, p->d_cfg, B, p->d_x0, p->d_uPred, nullptr, d.SSp, 60.0, 0, p->d_states, p->d_AB, st, d.m_pcont));
-        HIP_TRY(h, lpvmpc::launch_abc(p->dev, p->d_cfg, B, p->d_xlast, p->d_delta, p->d_AB, st, d.m_pfirst));
+        HIP_TRY(h, lpvmpc::launch_lpv(p->dev, p->d_cfg, p->d_model, B, p->d_x0, p->d_uPred, nullptr, d.SSp, 60.0, 0, p->d_states, p->d_AB, st, d.m_pcont));
+        HIP_TRY(h, lpvmpc::launch_abc(p->dev, p->d_cfg, p->d_model, B, p->d_xlast, p->d_delta, p->d_AB, st, d.m_pfirst));
         SolveArgs pa{B, p->d_x0, p->d_AB, nullptr, nullptr, p->d_maxey, p->d_xPred, p->d_uPred, p->d_status, p->d_iters, p->d_polish, p->d_resid,
                      nullptr, 0, 5};
         pa.active = d.m_plan;
@@ -255,9 +258,9 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
         const double *x0 = d.local; int x0_stride = 6;
         if (seed) {                                                          // scratch only: unmasked
             HIP_TRY(h, lpvmpc::launch_cl_seed(B, N, d.local, h->d_xlast, h->d_delta, st));
-            HIP_TRY(h, lpvmpc::launch_abc(h->dev, h->d_cfg, B, h->d_xlast, h->d_delta, h->d_AB, st));
+            HIP_TRY(h, lpvmpc::launch_abc(h->dev, h->d_cfg, h->d_model, B, h->d_xlast, h->d_delta, h->d_AB, st));
         } else {
-            HIP_TRY(h, lpvmpc::launch_lpv(h->dev, h->d_cfg, B, d.local, h->d_uPred, h->d_vel, nullptr, 60.0, 0, h->d_states, h->d_AB, st, d.m_path));
+            HIP_TRY(h, lpvmpc::launch_lpv(h->dev, h->d_cfg, h->d_model, B, d.local, h->d_uPred, h->d_vel, nullptr, 60.0, 0, h->d_states, h->d_AB, st, d.m_path));
             x0 = h->d_states; x0_stride = N * 6;
         }
         SolveArgs ca{B, x0, h->d_AB, h->d_vel, h->d_uold, nullptr, h->d_xPred, h->d_uPred, h->d_status, h->d_iters, h->d_polish, h->d_resid,
@@ -265,7 +268,7 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
         ca.active = d.m_path;
         rc = lpvmpc_launch_solve_timed(h, ca, st); if (rc) return rc;
         // trajectory-tracking controller (CMAIN:361-363)
-        HIP_TRY(h, lpvmpc::launch_lpv(tt->dev, tt->d_cfg, B, d.local, tt->d_uPred, tt->d_vel, tt->d_curv, 60.0, 1, tt->d_states, tt->d_AB, st, d.m_tt));
+        HIP_TRY(h, lpvmpc::launch_lpv(tt->dev, tt->d_cfg, tt->d_model, B, d.local, tt->d_uPred, tt->d_vel, tt->d_curv, 60.0, 1, tt->d_states, tt->d_AB, st, d.m_tt));
         SolveArgs ta{B, d.local, tt->d_AB, tt->d_vel, tt->d_uold, nullptr, tt->d_xPred, tt->d_uPred, tt->d_status, tt->d_iters, tt->d_polish,
                      tt->d_resid, nullptr, 0, 6};
         ta.active = d.m_tt;

@@ -13,23 +13,30 @@ WORDS = _ffi.PLANT_WORD_NAMES
 NOMINAL = dict(lf=0.125, lr=0.125, m=1.98, Iz=0.03, Cf=60.0, Cr=60.0, mu=0.05)   # MAIN_LAUNCH.launch; Simulator.f's tyre; simulator/mu
 
 
-def check_plant_params(rows, B):
-    """rows as a contiguous float64 [B, 7] array; ValueError on another shape, a non-finite word, lf / lr / m / Iz <= 0 or
-    Cf / Cr / mu < 0 (the library's refusals, raised before any call into it)."""
+def check_rows(rows, B, what="plant_params"):
+    """The row check shared by the plant rows and the model rows (model.py): rows as a contiguous float64 [B, 7] array; ValueError
+    naming ``what``, the vehicle and the field on another shape, a non-finite word, lf / lr / m / Iz <= 0 or Cf / Cr / mu < 0 (the
+    library's refusals, raised before any call into it)."""
     a = np.asarray(rows)
     if a.dtype.kind not in "fiu":
-        raise ValueError("plant_params must be numeric, got dtype %s" % a.dtype)
+        raise ValueError("%s must be numeric, got dtype %s" % (what, a.dtype))
     a = np.ascontiguousarray(a, np.float64)
     if a.shape != (B, _ffi.PLANT_WORDS):
-        raise ValueError("plant_params has shape %s, expected (%d, %d) = (B, [lf lr m Iz Cf Cr mu])" % (a.shape, B, _ffi.PLANT_WORDS))
+        raise ValueError("%s has shape %s, expected (%d, %d) = (B, [lf lr m Iz Cf Cr mu])" % (what, a.shape, B, _ffi.PLANT_WORDS))
     if not np.all(np.isfinite(a)):
         b, i = np.argwhere(~np.isfinite(a))[0]
-        raise ValueError("plant_params: vehicle %d: %s is not finite" % (b, WORDS[i]))
+        raise ValueError("%s: vehicle %d: %s is not finite" % (what, b, WORDS[i]))
     bad = np.argwhere(np.concatenate([a[:, :4] <= 0, a[:, 4:] < 0], axis=1))
     if bad.size:
         b, i = bad[0]
-        raise ValueError("plant_params: vehicle %d: %s = %g (lf, lr, m, Iz must be > 0; Cf, Cr, mu >= 0)" % (b, WORDS[i], a[b, i]))
+        raise ValueError("%s: vehicle %d: %s = %g (lf, lr, m, Iz must be > 0; Cf, Cr, mu >= 0)" % (what, b, WORDS[i], a[b, i]))
     return a
+
+
+def check_plant_params(rows, B):
+    """rows as a contiguous float64 [B, 7] array; ValueError on another shape, a non-finite word, lf / lr / m / Iz <= 0 or
+    Cf / Cr / mu < 0 (the library's refusals, raised before any call into it)."""
+    return check_rows(rows, B, "plant_params")
 
 
 def plant_params(B, engine=None, mu_sim=0.05, **fields):

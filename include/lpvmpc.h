@@ -741,6 +741,39 @@ int  lpvmpc_race_init_vehicles(lpvmpc_handle *path, lpvmpc_handle *tt, lpvmpc_ha
  * above (synchronises). */
 int  lpvmpc_plant_params_read(lpvmpc_handle *h, double *plant_params);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Per-vehicle model parameters: every instance of a batch -- every vehicle of a fleet, cascade or race -- is linearised with a
+ * model row of its own instead of the vehicle words lf, lr, m, Iz, Cf, Cr, mu of the handle's configuration: a heterogeneous batch
+ * on one handle, or the model side of a mismatch study (matched to each vehicle's plant row, or off by a chosen error).  dt, the
+ * track table, limits, weights and the OSQP settings stay the handle's.  Both entry points are new; every call above keeps its
+ * behaviour and refusals, and a handle without a binding (the default) launches what it launched before.
+ *
+ * Host layout: model_params [B][LPVMPC_MODEL_WORDS] = {lf, lr, m, Iz, Cf, Cr, mu} per vehicle, the word order of the plant rows.
+ *
+ * The binding belongs to the handle and acts wherever the handle linearises: lpvmpc_lpv_batch, lpvmpc_estimate_abc_batch,
+ * lpvmpc_solve_batch, _masked and _dev, seed mode, the lap-0 fleet (lpvmpc_cl_init*), the cascade (lpvmpc_cascade_init; bind the
+ * controller and the planner handle separately) and the race (lpvmpc_race_init*; path, tt and planner handle separately: the same
+ * rows, or not).  Vehicle b takes row b: the row is indexed by vehicle, not by launch slot, so masked launches work unchanged.
+ *   - Bound, every such call must have the binding's batch size: another B is refused with LPVMPC_E_ARG before anything is
+ *     launched (the engines check it at init).
+ *   - The controller roll-out (lpvmpc_lpv_batch and the solves of a controller handle) takes the row's Cf for BOTH axles -- the
+ *     reference passes Cf_new for both (CTRL:203-218) -- and the call's cf_new (the literal 60.0 of the fleet, cascade and race
+ *     engines) is ignored, as mu_sim is ignored when plant rows are given.  The controller's seed-mode linearisation and the
+ *     planner take the row's Cf and Cr, as they take the handle's without a binding.
+ *   - Every value is formed by the same operations in the same order as without a binding: a row equal to the handle's words (and
+ *     Cf equal to the call's cf_new, for the controller roll-out) gives the same words as the unbound handle.
+ *   - lpvmpc_solve_batch_AB takes the caller's blocks and is unaffected (any B).  The estimator keeps the nominal model: its gain
+ *     tables are designed on the nominal polytope's vertices.
+ * lpvmpc_set_model_params copies the rows to the device (synchronises); B = 0 unbinds (model_params is then ignored).  Refused with
+ * LPVMPC_E_ARG, the binding unchanged: a non-finite word, lf, lr, m or Iz <= 0, Cf, Cr or mu < 0 (the plant rows' rules), B < 0,
+ * B > 0 with model_params NULL, and any call while the handle runs a fleet, cascade or race (as stand-alone batch calls are
+ * refused then; lpvmpc_cl_release ends it).  lpvmpc_destroy frees the table.
+ * lpvmpc_model_params_read: *B = the binding's batch size (0: unbound) and, if model_params is not NULL, the bound rows
+ * [*B][LPVMPC_MODEL_WORDS] as they were set (synchronises). */
+#define LPVMPC_MODEL_WORDS 7
+int  lpvmpc_set_model_params(lpvmpc_handle *h, int32_t B, const double *model_params);
+int  lpvmpc_model_params_read(lpvmpc_handle *h, int32_t *B, double *model_params);
+
 #ifdef __cplusplus
 }
 #endif

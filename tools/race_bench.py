@@ -16,7 +16,12 @@ window), alternated --reps times per (regime, B); medians and the added ms per c
 lpvmpc_race_init_vehicles with the nominal rows and with rows from plant.sample_plant_params (seed 1); alternated --reps times per
 (regime, B), medians and differences against the all-off entry.  The sampled rows drive other trajectories, so their in-phase
 lines also carry the solvers' changed iteration counts.
-Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator | --actuator | --record | --plant-params [--reps R]] [--out FILE]"""
+--models: instead, the lap0 and inphase races run unbound and with explicit nominal model rows bound to the three engines
+(lpvmpc_set_model_params: the per-vehicle forms of the LPV kernels), and, with --parent-lib FILE (another build of the library, a file
+name inside the package directory), unbound on that build; alternated --reps times per (regime, B), one child process per run (a
+process loads one build); medians, each configuration's spread over the alternations and the differences against the unbound race.
+Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator | --actuator | --record | --plant-params | --models
+       [--parent-lib FILE] [--reps R]] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -47,8 +52,11 @@ def timed(tick, read, K):
     return (time.perf_counter() - t0) * 1e3 / K
 
 
-def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, record=False, plant_params=None):
+def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, record=False, plant_params=None, model_params=None):
     path, tt, plan = engines(mp, sd)
+    if model_params is not None:
+        for e in (path, tt, plan):
+            e.set_model_params(model_params)
     path.race_init(tt, plan, plant0, half_track0=half, laps=5, half_width=mp.halfWidth, slack=mp.slack, estimator=estimator,
                    actuator=actuator, plant_params=plant_params)
     path.race_tick(warm)
@@ -73,7 +81,14 @@ def main():
     ap.add_argument("--actuator", action="store_true")
     ap.add_argument("--record", action="store_true")
     ap.add_argument("--plant-params", action="store_true")
+    ap.add_argument("--models", action="store_true")
+    ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--models-child", nargs=4, default=None, help=argparse.SUPPRESS)      # lib regime B bind: one run of --models
     a = ap.parse_args()
+    if a.models_child:
+        return models_child(a)
+    if a.models:
+        return models_main(a)
     if a.plant_params:
         return plant_params_main(a)
     if a.record:
@@ -221,6 +236,53 @@ def plant_params_main(a):
                 m = float(np.median(ms[k]))
                 lines.append("%-8s B=%5d  %-13s %.3f ms/tick (runs %s, phases %s)  vs all-off %+.3f ms/tick"
                              % (name, B, k, m, " ".join("%.3f" % x for x in ms[k]), ph[k].tolist(), m - m0))
+                print(lines[-1], flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+def _models_starts(B):
+    from tests._golden import load
+    c = load("cascade")
+    rng = np.random.default_rng(3)
+    grid = np.zeros((B, 8)); grid[:, 1] = rng.normal(0, 0.02, B); grid[:, 2] = rng.uniform(0.9, 1.1, B)
+    return {"lap0": (grid, 0, 10), "inphase": (np.tile(c["pre_plant"][0], (B, 1)), 1, int(c["pre_ticks"]) + 3)}
+
+
+def models_child(a):
+    lib, regime, B, bind = a.models_child
+    from lpvmpc import _ffi
+    _ffi.LIB_PATH = os.path.join(os.path.dirname(_ffi.LIB_PATH), lib)
+    import lpvmpc
+    mp = lpvmpc.Map("L_shape", 0.2)
+    plant0, half, warm = _models_starts(int(B))[regime]
+    rows = lpvmpc.model_params(int(B)) if int(bind) else None
+    ms, _vps, ph = race_run(mp, plant0, half, warm, a.ticks, model_params=rows)
+    print("MODELS_RUN %.6f %s" % (ms, ",".join(str(int(x)) for x in ph)), flush=True)
+
+
+def models_main(a):
+    import subprocess
+    cfgs = [("unbound", "liblpvmpc.so", 0), ("nominal rows bound", "liblpvmpc.so", 1)]
+    if a.parent_lib:
+        cfgs.append(("parent, unbound", a.parent_lib, 0))
+    lines = []
+    for B in [int(x) for x in a.sizes.split(",")]:
+        for regime in ("lap0", "inphase"):
+            ms = {k: [] for k, _, _ in cfgs}
+            ph = {}
+            for _ in range(a.reps):
+                for k, lib, bind in cfgs:
+                    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--ticks", str(a.ticks), "--models-child", lib, regime, str(B),
+                                          str(bind)], check=True, capture_output=True, text=True, timeout=600).stdout
+                    f = [l for l in out.splitlines() if l.startswith("MODELS_RUN")][-1].split()
+                    ms[k].append(float(f[1])); ph[k] = f[2]
+            m0 = float(np.median(ms["unbound"]))
+            for k, _, _ in cfgs:
+                m = float(np.median(ms[k]))
+                lines.append("%-8s B=%5d  %-19s %.3f ms/tick (runs %s, spread %.3f, phases [%s])  vs unbound %+.3f ms/tick"
+                             % (regime, B, k, m, " ".join("%.3f" % x for x in ms[k]), max(ms[k]) - min(ms[k]), ph[k], m - m0))
                 print(lines[-1], flush=True)
     if a.out:
         with open(a.out, "w") as f:

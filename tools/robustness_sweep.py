@@ -6,7 +6,11 @@ lap (HalfTrack = 1), so lap 0 is short.  The race runs until every vehicle has f
 Reports, binned by each sampled parameter (quartiles of its factor against the nominal row): vehicles, the fractions finished and
 lost, the median and p90 racing lap time (laps 1 .. laps of the finished vehicles' laps) and the median per-lap RMSE_ey of the
 racing laps (RaceFleet.lap_stats, CMAIN:101-106).
-Usage: tools/robustness_sweep.py [--B 8192] [--laps 2] [--seed 1] [--max-ticks 3000] [--out FILE]"""
+--model selects the controllers' and the planner's model of each vehicle (lpvmpc_set_model_params, RaceFleet(model_params=...)):
+nominal (default: today's run, same output), plant (each vehicle's model is its plant row: the matched experiment) or noisy:REL
+(the plant row times an independent uniform factor in [1 - REL, 1 + REL] per field: an identification error).  The nominal-car
+baseline race keeps the nominal model.
+Usage: tools/robustness_sweep.py [--B 8192] [--laps 2] [--seed 1] [--max-ticks 3000] [--model nominal|plant|noisy:REL] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -23,10 +27,13 @@ def main():
     ap.add_argument("--laps", type=int, default=2)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--max-ticks", type=int, default=3000)
+    ap.add_argument("--model", default="nominal")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.model not in ("nominal", "plant") and not a.model.startswith("noisy:"):
+        ap.error("--model must be nominal, plant or noisy:REL")
     import lpvmpc
-    from lpvmpc import plant
+    from lpvmpc import model, plant
     from tests._race_observer_ref import start_line_fleet
     mp = lpvmpc.Map("L_shape", 0.2)
     B = a.B
@@ -35,9 +42,19 @@ def main():
     nom = lpvmpc.plant_params(B)
     plant0 = start_line_fleet(mp.PointAndTangent, B, a.seed, 0.8, 0.97)
 
-    def race(r):
-        f = lpvmpc.RaceFleet(mp, plant0, laps=a.laps, half_track0=1, plant_params=r)
+    if a.model == "nominal":
+        model_rows, model_text = None, "keep the nominal model (lf = lr = 0.125, m = 1.98, Iz = 0.03, Cf = Cr = 60, mu = 0.05)"
+    elif a.model == "plant":
+        model_rows, model_text = rows, "take each vehicle's plant row as its model (--model plant: no mismatch)"
+    else:
+        rel = float(a.model.split(":", 1)[1])
+        model_rows = model.perturb_rows(rows, a.seed, {k: rel for k in plant.WORDS})
+        model_text = "take each vehicle's plant row times an independent uniform factor in [%g, %g] per field as its model (--model %s)" % (1 - rel, 1 + rel, a.model)
+
+    def race(r, m=None):
+        f = lpvmpc.RaceFleet(mp, plant0, laps=a.laps, half_track0=1, plant_params=r, model_params=m)
         assert np.array_equal(f.plant_params(), r)
+        assert m is None or np.array_equal(f.model_params(), m)
         f.record(1, 1 << 20)                                          # statistics of every tick; one record kept
         t0, n = time.perf_counter(), 0
         while n < a.max_ticks:
@@ -49,7 +66,7 @@ def main():
     base, _n, _w = race(nom)                                          # the same starts with the nominal car: the baseline
     ph_nom = base.state()["phase"]
     base.close()
-    fleet, ticks, wall = race(rows)
+    fleet, ticks, wall = race(rows, model_rows)
     ph = fleet.state()["phase"]
     lt = fleet.lap_times()[:, 1:a.laps + 1]                          # racing laps, seconds (NaN: not completed)
     st = fleet.lap_stats()
@@ -58,7 +75,7 @@ def main():
     fin_nom = ph_nom == 2
     lines = ["# tools/robustness_sweep.py --B %d --laps %d --seed %d on one MI355X: one race, rows from sample_plant_params(B, %d) with spreads %s"
              % (B, a.laps, a.seed, a.seed, ", ".join("%s %+.0f %%" % (k, 100 * v) for k, v in spread.items())),
-             "# the controllers and the planner keep the nominal model (lf = lr = 0.125, m = 1.98, Iz = 0.03, Cf = Cr = 60, mu = 0.05).",
+             "# the controllers and the planner %s." % model_text,
              "# %d ticks (%.1f s wall); all vehicles: %.1f %% finished, %.1f %% lost, %.1f %% still running; racing lap time median %.3f s, "
              "p90 %.3f s; RMSE_ey median %.4f m" % (ticks, wall, 100 * fin.mean(), 100 * lost.mean(), 100 * (ph < 2).mean(),
                                                      np.nanmedian(lt), np.nanpercentile(lt, 90), np.nanmedian(rmse)),
