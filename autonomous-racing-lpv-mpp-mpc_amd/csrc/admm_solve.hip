@@ -3163,14 +3163,17 @@ struct Solver {
         atomicAdd(a.defer_stats + (s >= 0 ? 0 : 1), 1ull);
         return s;
     }
-    // AGE-ORDERED ADMISSION (round 6).  A main launch parks into a pool of pool_cap entries that is emptied only by the resume pass
-    // behind it.  First come, first served let the many nearly-done instances of a small defer_after = K fill the pool at their first
+    // AGE-ORDERED ADMISSION (round 6).  A main launch parks into a pool of pool_cap entries that is emptied only by the riders of the next
+    // launch (or by the resume pass behind it).  First come, first served let the many nearly-done instances of a small defer_after = K fill the pool at their first
     // check beyond K, and the one 4000-iteration instance of the batch then stayed resident in the main launch for all of its
     // iterations (defer_after 50: 0.99 M solves/s against 2.0 M at 75 / 100 / 125, profiles/r05_burst_sweep_driver.txt).  Now the
     // instances are admitted by age class: the YOUNG ones (fewer than 2 K iterations) may take three quarters of the pool, the MIDDLE
     // ones (2 K .. 4 K) an eighth of their own, and whoever is beyond 4 K takes any free entry -- at least the last eighth.  An instance
     // that is refused goes on iterating and asks again at its next check, older by then: the long runners always find room, however
     // many young ones wanted in.  Resume passes park into an empty pool of the size of the one they consume: nothing is refused there.
+    // RIDERS share the pool they park into with the new instances of their launch (which may take up to 3/4 + 1/8 of it): a rider that finds
+    // no free entry is refused like anyone else and goes on iterating in place -- in a pool much smaller than the stragglers in flight a long
+    // runner can then hold its main launch, and the stream, to its end (lpvmpc.h, "defer_pool"; lpvmpc_defer_stats shows the refusals).
     // lpvmpc_defer_stats reports the instances parked and the requests refused.
     __device__ __forceinline__ bool try_park(const SolveArgs &a, int entry, int inst, int iter, int to_chk, int to_adp) {
         if (tid == 0) RED[79] = (double)park_slot(a, iter);
@@ -3726,6 +3729,38 @@ __global__ void __launch_bounds__(64 * NW, (min_waves_per_simd<NT, NW, GS>())) a
     s.run(a, inst, entry);
 }
 
+// A main launch WITH RIDERS (SolveArgs::resume 2, grid pool_cap + B): the same Solver behind an entry of its own, so that the kernel above
+// -- every plain, resume and tail launch -- compiles as it did before there were riders.  Workgroups 0 .. pool_cap-1 are the riders: workgroups
+// of a resume launch, with the riders' budget, in all but the launch they travel in (the low block indices are dispatched first, so the
+// long runners start first); workgroups pool_cap .. pool_cap+B-1 are instances blockIdx.x - pool_cap of the call, and B, active and
+// defer_after apply to them only.  Decided here, once, on the workgroup's own copy of the arguments (block-uniform: scalar registers);
+// Solver::run does not know the third mode.  (No caller of the library combines an active mask with riders today -- lpvmpc_solve_batch_masked
+// goes through the synchronous entry point, which launches without riders -- so the mask beside riders is untested.)
+template <int NX, int NT, int NW, bool MF = false, bool GS = false>
+__global__ void __launch_bounds__(64 * NW, (min_waves_per_simd<NT, NW, GS>())) admm_solve_riders_kernel(const DevCfg *__restrict__ cfgp, SolveArgs a) {
+    extern __shared__ __align__(16) double smem[];
+    int inst = blockIdx.x, entry = -1;
+    if ((int)blockIdx.x < a.pool_cap) { a.resume = 1; a.defer_after = a.defer_budget; }
+    else { a.resume = 0; inst = (int)blockIdx.x - a.pool_cap; }
+    if (a.resume) {
+        // every rider reads the number of parked entries; the last one to have read it clears the counters (this launch consumes the
+        // pool; the launch behind it in the stream parks into it again).  Riders are counted, not the grid: one per pool entry.
+        int &n_parked = *reinterpret_cast<int *>(smem);          // (the instance's LDS image is restored over it afterwards)
+        if (threadIdx.x == 0) {
+            n_parked = atomicAdd(a.pool_in_count, 0);
+            __threadfence();
+            if (atomicAdd(a.pool_in_count + 1, 1) == a.pool_cap - 1) { a.pool_in_count[0] = 0; a.pool_in_count[1] = 0; a.pool_in_count[2] = 0; a.pool_in_count[3] = 0; }
+        }
+        __syncthreads();
+        const int n = n_parked;
+        entry = blockIdx.x;
+        if (entry >= (n < a.pool_cap ? n : a.pool_cap)) return;
+        __syncthreads();          // every wavefront has read the count before restore() stores the image over it
+    } else if (inst >= a.B || (a.active && !a.active[inst])) return;      // (uniform: one scalar load per workgroup)
+    Solver<NX, NT, NW, MF, GS, false> s(*cfgp, smem);
+    s.run(a, inst, entry);
+}
+
 template <int NX, int NT, int NW, bool MF = false, bool GS = false, bool TAIL = false>
 static hipError_t launch_one(const DevCfg &cfg, const DevCfg *dcfg, const SolveArgs &a, hipStream_t stream) {
     using S = Solver<NX, NT, NW, MF, GS, TAIL>;
@@ -3748,6 +3783,20 @@ static hipError_t launch_one(const DevCfg &cfg, const DevCfg *dcfg, const SolveA
         hipError_t err = hipFuncSetAttribute((const void *)admm_solve_kernel<NX, NT, NW, MF, GS, TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (err != hipSuccess) return err;
         word.fetch_or(bit, std::memory_order_release);
+    }
+    if (a.resume == 2) {          // a main launch with riders: the entry of its own (the LDS opt-in is per function: its own mask)
+        if constexpr (TAIL || GS) return hipErrorInvalidValue;          // (never routed here: both run without deferral / to completion only)
+        else {
+            static std::atomic<uint64_t> riders_mask[4];
+            std::atomic<uint64_t> &rword = riders_mask[(dev >> 6) & 3];
+            if (!(rword.load(std::memory_order_acquire) & bit)) {
+                hipError_t err = hipFuncSetAttribute((const void *)admm_solve_riders_kernel<NX, NT, NW, MF, GS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                if (err != hipSuccess) return err;
+                rword.fetch_or(bit, std::memory_order_release);
+            }
+            hipLaunchKernelGGL((admm_solve_riders_kernel<NX, NT, NW, MF, GS>), dim3(a.pool_cap + a.B), dim3(64 * NW), lds, stream, dcfg, a);
+            return hipGetLastError();
+        }
     }
     hipLaunchKernelGGL((admm_solve_kernel<NX, NT, NW, MF, GS, TAIL>), dim3(a.resume ? a.pool_cap : a.B), dim3(64 * NW), lds, stream, dcfg, a);
     return hipGetLastError();

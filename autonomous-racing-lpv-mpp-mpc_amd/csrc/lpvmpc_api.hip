@@ -108,7 +108,8 @@ static int ensure_defer(lpvmpc_handle *h, int B, hipStream_t st) {
     return LPVMPC_OK;
 }
 // one resume pass on `st`: continues the entries of pool[dcur] for `budget` more iterations (0 = to completion), parks the
-// unfinished ones in the other pool, which becomes the current one
+// unfinished ones in the other pool, which becomes the current one.  (Only the passes to completion are left: lpvmpc_join and
+// defer_budget 0.  The bounded continuation rides in the next deferred call's main launch, lpvmpc_solve_batch_dev.)
 static int resume_pass(lpvmpc_handle *h, int budget, hipStream_t st) {
     const int A = h->dcur, Bp = 1 - A;
     SolveArgs a{};
@@ -346,7 +347,7 @@ int lpvmpc_launch_solve_timed(lpvmpc_handle *h, const SolveArgs &a, hipStream_t 
     if (h->timing) HIP_TRY(h, hipEventRecord(h->ev0[slot], st));
     SolveArgs b = a;
     if (h->d_scal && a.B <= h->cap) b.scal = h->d_scal;          // (the launcher ignores it for deferred / resumed launches)
-    if (h->solve_mask && !a.resume) b.active = h->solve_mask;      // lpvmpc_solve_batch_masked
+    if (h->solve_mask && !a.resume) b.active = h->solve_mask;      // lpvmpc_solve_batch_masked (synchronous: its launch carries no riders)
     HIP_TRY(h, lpvmpc::launch_solve(h->dev, h->d_cfg, b, st, h->force_generic));
     if (h->timing) { HIP_TRY(h, hipEventRecord(h->ev1[slot], st)); h->ev_count++; }
     return LPVMPC_OK;
@@ -552,22 +553,34 @@ extern "C" int lpvmpc_solve_batch_dev(lpvmpc_handle *h, int32_t B, const double 
     SolveArgs a{B, x0, h->d_AB, ctrl ? vel_ref : nullptr, u_old, ctrl ? nullptr : max_ey, xPred, uPred, status, iters, polish, resid,
                 h->warm_mode ? h->d_state : nullptr, (h->warm_mode && h->state_valid_B == B) ? h->warm_mode : 0, h->nx};
     if (h->defer_after > 0) {
-        // Straggler deferral: this launch parks what is still unsolved after defer_after iterations; the resume pass behind it
-        // (same stream) continues everything that is parked on this handle -- from this call and from earlier ones -- for
-        // defer_budget more iterations.  No launch lasts much longer than its budget, so the stream is never held by one slow
-        // instance; lpvmpc_join runs the pass that finishes whatever is still parked.
+        // Straggler deferral: this launch parks what is still unsolved after defer_after iterations.  With defer_budget > 0 it also
+        // carries the RIDERS: everything that earlier calls of this handle left parked continues, for defer_budget more iterations,
+        // in workgroups of this same launch (SolveArgs::resume 2) -- they run beside the new instances, in the residency slots that
+        // free up as those finish, instead of holding the stream with a launch of their own.  The launch reads pool[dcur] and parks
+        // -- riders and new instances alike -- into the other pool, which becomes the current one.  No workgroup lasts much longer than
+        // its budget, so the stream is never held by one slow instance; lpvmpc_join runs the pass that finishes whatever is still parked.
         rc = ensure_defer(h, B, st); if (rc) return rc;
         if (h->defer_stream_set && h->defer_stream != st) {        // the pools are ordered by stream: hand them over
             HIP_TRY(h, hipEventRecord(h->defer_event, h->defer_stream));
             HIP_TRY(h, hipStreamWaitEvent(st, h->defer_event, 0));
         }
         h->defer_stream = st; h->defer_stream_set = true;
-        a.defer_after = h->defer_after; a.resume = 0; a.pool = h->dpool[h->dcur]; a.pool_count = h->dcount[h->dcur];
-        a.pool_cap = h->defer_cur_cap; a.pool_stride = h->defer_stride; a.defer_stats = h->dstats;
-        rc = lpvmpc_launch_solve_timed(h, a, st); if (rc) return rc;
-        // the bounded pass behind the call -- unless the caller joins right away (budget -1, and the synchronous host-array entry
-        // point): then the closing pass (the tail kernel) takes the parked instances straight from this launch
-        if (h->defer_budget >= 0 && !h->defer_skip_pass) { rc = resume_pass(h, h->defer_budget, st); if (rc) return rc; }
+        a.defer_after = h->defer_after; a.pool_cap = h->defer_cur_cap; a.pool_stride = h->defer_stride; a.defer_stats = h->dstats;
+        if (h->defer_budget > 0 && !h->defer_skip_pass) {
+            const int A = h->dcur, Bp = 1 - A;
+            a.resume = 2; a.defer_budget = h->defer_budget;
+            a.pool_in = h->dpool[A]; a.pool_in_count = h->dcount[A];
+            a.pool = h->dpool[Bp]; a.pool_count = h->dcount[Bp];
+            rc = lpvmpc_launch_solve_timed(h, a, st); if (rc) return rc;
+            h->dcur = Bp;
+        } else {
+            // budget 0: the pass behind the call runs everything that is parked to completion.  Budget -1, and the synchronous
+            // host-array entry point, which joins right away: no pass -- the closing pass (the tail kernel) takes the parked
+            // instances straight from this launch.  Either way this launch parks behind what pool[dcur] already holds.
+            a.resume = 0; a.pool = h->dpool[h->dcur]; a.pool_count = h->dcount[h->dcur];
+            rc = lpvmpc_launch_solve_timed(h, a, st); if (rc) return rc;
+            if (h->defer_budget == 0 && !h->defer_skip_pass) { rc = resume_pass(h, 0, st); if (rc) return rc; }
+        }
     } else {
         rc = lpvmpc_launch_solve_timed(h, a, st); if (rc) return rc;
     }

@@ -70,6 +70,10 @@ struct SolveArgs {
     int defer_after;        // main launch: park at the first check with iter >= defer_after; resume launch: after that many more
                             // iterations; 0: run to completion
     int resume;             // 1: continue the parked instances of pool_in (blockIdx.x = entry)
+                            // 2: a main launch that carries riders (grid pool_cap + B): workgroups 0 .. pool_cap-1 continue the entries of
+                            // pool_in for defer_budget more iterations as a resume launch would -- the low block indices are dispatched first,
+                            // so the long runners start first -- and workgroups pool_cap .. pool_cap+B-1 are instances blockIdx.x - pool_cap
+                            // of the call (B, active and defer_after apply to them only); both park into pool
     double *pool;           // [pool_cap][pool_stride] entries written by this launch
     int32_t *pool_count;    // [4]: slots requested so far in pool (may exceed pool_cap: the surplus instances were not parked), [1] see pool_in_count,
                             // [2] / [3] requests of the young / middle age class (admission by age: Solver::park_slot)
@@ -88,6 +92,8 @@ struct SolveArgs {
     // [B] active-instance mask of a main launch (null: every instance).  A workgroup whose flag is 0 returns at its entry, before it
     // reads or writes anything (its output rows and carried state stay as they are; it never parks).  Resume launches ignore it.
     const int32_t *active;
+    int defer_budget;       // resume = 2: iterations the riders continue for before they park again (defer_after is the new instances' word there;
+                            // a resume launch carries its budget in defer_after, as before)
 };
 constexpr int kParkScalars = 16;     // behind the LDS image of a pool entry: c, cinv, rho, iter, to_chk, to_adp, instance index and the
                                      // instance's output pointers (xPred, uPred, status, iters, polish, resid, state) as 64-bit words

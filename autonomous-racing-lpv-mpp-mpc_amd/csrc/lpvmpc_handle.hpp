@@ -56,11 +56,12 @@ struct lpvmpc_handle {
     double *d_Wop, *d_FWop;
     int ho_M;
     // straggler deferral (options "defer_after" / "defer_budget" / "defer_pool", lpvmpc_solve_batch_dev only): two pools of
-    // parked instances used alternately -- launches park into pool[dcur], the resume pass that follows continues the entries
-    // of pool[dcur] and parks what is still unsolved after its budget into the other pool, which becomes dcur
-    int defer_after, defer_budget, defer_cap;   // iterations before parking (0 = off); iterations per resume pass; pool entries (0 = default)
+    // parked instances used alternately -- with defer_budget > 0 a call's main launch continues the entries of pool[dcur] in its
+    // rider workgroups and parks, riders and new instances alike, into the other pool, which becomes dcur; otherwise launches park
+    // into pool[dcur] and a resume pass (lpvmpc_join; budget 0: behind every call) runs its entries to completion
+    int defer_after, defer_budget, defer_cap;   // iterations before parking (0 = off); iterations a rider continues for (0 / -1: see lpvmpc.h); pool entries (0 = default)
     int defer_tail;                     // option "defer_tail" (default 1): passes that run to completion take the whole-CU tail kernel
-    bool defer_skip_pass;               // transient: the synchronous entry point joins at once, no bounded pass in between
+    bool defer_skip_pass;               // transient: the synchronous entry point joins at once, no riders and no pass in between
     int defer_cur_cap, defer_stride;
     double *dpool[2];
     int32_t *dcount[2];

@@ -63,8 +63,8 @@ extern "C" {
 #define LPVMPC_NON_CVX                      -7
 #define LPVMPC_UNSOLVED                    -10      /* also: non-finite input data (NaN / Inf in x0, A, B, vel_ref, uOld,
                                                       max_ey) -- no iteration is run, xPred / uPred are NaN, iters = 0 */
-#define LPVMPC_PENDING                     -11      /* straggler deferral only (option "defer_after"): the instance was parked by the
-                                                      * main launch; its resume launch has not written the final status yet */
+#define LPVMPC_PENDING                     -11      /* straggler deferral only (option "defer_after"): the instance is parked; the launch
+                                                      * that finishes it has not written the final status yet */
 
 typedef struct lpvmpc_config {
     int32_t kind;            /* LPVMPC_KIND_* */
@@ -147,17 +147,27 @@ int lpvmpc_last_error_code(void);
  * "defer_after" (iterations, 0 = off, default): STRAGGLER DEFERRAL for lpvmpc_solve_batch_dev.  One OSQP solve in a thousand
  * needs thousands of ADMM iterations where the typical one needs 50; a launch lasts as long as its slowest instance, so those
  * few hold the caller's stream for milliseconds.  With defer_after = K an instance that is still unsolved at a termination
- * check with iter >= K is parked (status LPVMPC_PENDING, whole solver state saved) and the launch ends.  Every deferred call
- * is followed, on the same stream, by a resume pass of the same kernel that continues everything parked on the handle -- from
- * this call and from earlier ones -- for "defer_budget" more iterations (default 200; 0 = to completion) and parks again what
- * is still unsolved.  With "defer_tail" 0 the results are bit-identical to the plain call (a restored instance re-factors K
- * from its saved state); with the default "defer_tail" 1 the closing passes use the tail kernel: equal to round-off, see there.
- * Completion contract: an instance's outputs are final when its status is no longer LPVMPC_PENDING; lpvmpc_join(h, stream)
+ * check with iter >= K is parked (status LPVMPC_PENDING, whole solver state saved) and its workgroup ends.
+ * "defer_budget" (iterations, default 200) says how the parked instances go on.  > 0: they RIDE IN THE HANDLE'S NEXT DEFERRED CALL.
+ * That call's main launch carries, in front of its own instances, one workgroup per pool entry (grid pool + B); these riders continue
+ * everything parked on the handle -- by the previous call and by earlier ones -- for defer_budget more iterations beside the new
+ * instances, in the residency slots those free as they finish, and park again what is still unsolved.  No launch follows a call on
+ * its stream (before, a bounded resume pass of a quarter of a millisecond did, and the stream's next call waited for it).  A parked
+ * instance therefore advances with the handle's next deferred call, or at lpvmpc_join -- a call that nothing follows leaves its
+ * stragglers as they are until the join -- and its results arrive one call of the handle later than with a pass behind every call.
+ * 0: every deferred call is followed, on the same stream, by a resume pass of the same kernel that runs everything parked to completion.
+ * -1: no pass behind a deferred call and no riders; the parked instances wait for lpvmpc_join (what a caller that joins after every
+ * call wants: one batch, then the tail kernel; lpvmpc_solve_batch does this by itself).
+ * With "defer_tail" 0 the results are bit-identical to the plain call (a restored instance re-factors K from its saved state); with
+ * the default "defer_tail" 1 the passes to completion use the tail kernel: equal to round-off, see there.
+ * Completion contract (unchanged): an instance's outputs are final when its status is no longer LPVMPC_PENDING; lpvmpc_join(h, stream)
  * enqueues the pass that finishes whatever is still parked, so work behind it in `stream` sees complete outputs.  Until then
- * the output buffers of the deferred calls must stay valid and must not be reused for other data.  The synchronous host-array
- * call lpvmpc_solve_batch joins by itself before it copies the outputs back (it never returns LPVMPC_PENDING).
- * "defer_budget" -1: no pass behind a deferred call at all; the parked instances wait for lpvmpc_join (what a caller that joins
- * after every call wants: one batch, then the tail kernel; lpvmpc_solve_batch does this by itself).
+ * the buffers of the deferred calls -- outputs, and the inputs while the call itself runs -- must stay valid and must not be reused
+ * for other data while one of the call's instances is LPVMPC_PENDING.  A caller that cycles through a ring of output sets without
+ * joining needs one more set per handle than with a pass behind every call: a straggler of call j is written by the launches of
+ * calls j + 1, j + 2, ... of its handle (forty of them for a 4000-iteration instance at a budget of 100, as before).  The
+ * synchronous host-array calls (lpvmpc_solve_batch, lpvmpc_solve_batch_masked) join by themselves before they copy the outputs back:
+ * they never return LPVMPC_PENDING and carry no riders -- what earlier deferred calls left parked is finished by their join.
  * "defer_pool" (entries, 0 = max(64, B / 8), default): capacity of each of the two pools.  ADMISSION IS ORDERED BY AGE (K = defer_after):
  * instances with fewer than 2 K iterations may take three quarters of a pool, those between 2 K and 4 K an eighth of their own, and an
  * instance beyond 4 K takes any free entry (at least the last eighth).  An instance that finds its class's share full is not parked at
@@ -168,7 +178,10 @@ int lpvmpc_last_error_code(void);
  * are within 3 % of each other).  K is still a cost parameter: every parked instance is restored and re-factored by the pass that
  * continues it, so park what is rare -- choose K near the point where ~99 % of the instances are done (100 for the controller workloads
  * here; K = 25 parks most of a batch once and runs a burst at three quarters of the rate).  lpvmpc_defer_stats tells how many requests
- * were refused, i.e. whether "defer_pool" should grow.
+ * were refused, i.e. whether "defer_pool" should grow.  With "defer_budget" > 0 the riders of a launch park into the same pool as its new
+ * instances (which may take up to seven eighths of it), so the pool must hold the stragglers of ALL calls in flight on the handle, not of one:
+ * a rider that finds no free entry is refused like any other instance and goes on iterating in place -- a many-thousand-iteration rider then
+ * holds its main launch, and the stream, to its end.
  * "defer_tail" (0 | 1, default 1): the passes that run parked instances to completion (lpvmpc_join, the synchronous entry
  * points, "defer_budget" 0) use the whole-CU tail kernel where one exists for the handle (controller or planner, N = 20): a 512-thread
  * workgroup per instance that applies K^-1 as a dense matrix held in registers, runs two phases per ADMM iteration and evaluates the
@@ -192,14 +205,17 @@ int lpvmpc_last_error_code(void);
  * planner N = 40: device 50, batch oracle 75, oracle with the other order 50).  The reference discards such a tick either way. */
 int lpvmpc_set_option(lpvmpc_handle *h, const char *name, int32_t value);
 /* Straggler deferral (see "defer_after"): enqueues on `stream` (a hipStream_t; ordered behind the stream of the handle's last
- * deferred call if it is another one) the resume pass that runs every parked instance to completion.  No-op without deferral. */
+ * deferred call if it is another one) the resume pass that runs every parked instance to completion.  With "defer_budget" > 0 this
+ * is also what continues the stragglers of a handle's LAST call: riders need a next call to travel in.  No-op without deferral. */
 int lpvmpc_join(lpvmpc_handle *h, void *stream);
 /* Straggler deferral counters of the handle since its first deferred call: *parked = instances parked (every parking counts, also a
- * re-parking by a bounded resume pass), *refused = parking requests turned down because the pool share of the instance's age class was
+ * re-parking by a rider), *refused = parking requests turned down because the pool share of the instance's age class was
  * full (see "defer_pool": the instance went on in its launch and asked again later).  Waits for the stream of the handle's last
  * deferred call, so every launch enqueued so far is counted.  Either pointer may be NULL. */
 int lpvmpc_defer_stats(lpvmpc_handle *h, int64_t *parked, int64_t *refused);
-/* Like lpvmpc_kernel_time_stats (below) for the resume launches of the straggler deferral. */
+/* Like lpvmpc_kernel_time_stats (below) for the resume launches of the straggler deferral: the passes to completion of lpvmpc_join
+ * and of "defer_budget" 0.  (The bounded continuation of "defer_budget" > 0 has no launch of its own: its riders are part of the main
+ * launches that lpvmpc_kernel_time_stats times.) */
 int lpvmpc_resume_time_stats(lpvmpc_handle *h, double *total_ms, int32_t *count);
 
 /* (Round 4 shipped an experimental "long-runner lane" here -- lpvmpc_lane_*: reserved compute units for the whole-CU tail kernel.
