@@ -16,15 +16,10 @@ extern "C" void lpvmpc_actuator_default_config(lpvmpc_actuator_config *c) {
     c->servo_tf = 0.07;                                          // Tf (vehicleSimulator.py:62)
 }
 
-void lpvmpc_act_free(lpvmpc::ActDev &a) {
-    void *ptrs[] = {a.ring, a.servo, a.k, const_cast<int32_t *>(a.La), const_cast<int32_t *>(a.Ld)};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    a = lpvmpc::ActDev{};
-}
-
 int lpvmpc_act_alloc(lpvmpc_handle *h, int B, const lpvmpc_actuator_config *cfg, const int32_t *delay_a, const int32_t *delay_df,
-                     double dt_sim, const char *who, lpvmpc::ActDev &a) {
-    a = lpvmpc::ActDev{};
+                     double dt_sim, const char *who, ActState &as) {
+    as = {};
+    lpvmpc::ActDev &a = as.d;
     if (!cfg) return fail(h, LPVMPC_E_ARG, "%s: actuator config is NULL", who);
     if (cfg->low_level_dyn && !(cfg->servo_tf > 0)) return fail(h, LPVMPC_E_ARG, "%s: servo_tf must be > 0 with low_level_dyn", who);
     std::vector<int32_t> La(B, cfg->delay_a), Ld(B, cfg->delay_df);
@@ -37,11 +32,11 @@ int lpvmpc_act_alloc(lpvmpc_handle *h, int B, const lpvmpc_actuator_config *cfg,
     const size_t n = B;
     hipStream_t st = h->stream;
     int32_t *dLa = nullptr, *dLd = nullptr;
-    HIP_TRY(h, hipMalloc((void **)&a.ring, n * 2 * lpvmpc::kActRing * 8));
-    HIP_TRY(h, hipMalloc((void **)&a.servo, n * 8));
-    HIP_TRY(h, hipMalloc((void **)&a.k, n * 4));
-    HIP_TRY(h, hipMalloc((void **)&dLa, n * 4)); a.La = dLa;
-    HIP_TRY(h, hipMalloc((void **)&dLd, n * 4)); a.Ld = dLd;
+    HIP_TRY(h, as.mem.alloc(a.ring, n * 2 * lpvmpc::kActRing * 8));
+    HIP_TRY(h, as.mem.alloc(a.servo, n * 8));
+    HIP_TRY(h, as.mem.alloc(a.k, n * 4));
+    HIP_TRY(h, as.mem.alloc(dLa, n * 4)); a.La = dLa;
+    HIP_TRY(h, as.mem.alloc(dLd, n * 4)); a.Ld = dLd;
     HIP_TRY(h, hipMemsetAsync(a.ring, 0, n * 2 * lpvmpc::kActRing * 8, st));
     HIP_TRY(h, hipMemsetAsync(a.servo, 0, n * 8, st));
     HIP_TRY(h, hipMemsetAsync(a.k, 0, n * 4, st));
@@ -90,20 +85,15 @@ extern "C" int lpvmpc_plant_step_actuated_batch(lpvmpc_handle *h, int32_t B, dou
             for (size_t j = 0; j < R; ++j) ring[(c * R + j) * b + i] = o[c * R + j];
         sv[i] = o[2 * R]; k[i] = (int32_t)kk;
     }
-    lpvmpc::ActDev a{};
-    rc = lpvmpc_act_alloc(h, B, cfg, delay_a, delay_df, dt_sim, who, a);
-    if (rc) { lpvmpc_act_free(a); return rc; }
+    ActState as;                                                    // (freed when the call returns)
+    rc = lpvmpc_act_alloc(h, B, cfg, delay_a, delay_df, dt_sim, who, as); if (rc) return rc;
+    const lpvmpc::ActDev &a = as.d;
     hipStream_t st = h->stream;
-    auto run = [&]() -> int {
-        H2D(a.ring, ring.data(), ring.size() * 8); H2D(a.servo, sv.data(), b * 8); H2D(a.k, k.data(), b * 4);
-        H2D(h->d_xlast, state, b * 8 * 8); H2D(h->d_states, u, b * 2 * 8);
-        HIP_TRY(h, lpvmpc::launch_plant_actuated(B, h->d_xlast, h->d_states, lpvmpc_plant_cfg(h, n_sub, dt_sim, mu_sim), a, st));
-        D2H(state, h->d_xlast, b * 8 * 8);
-        return lpvmpc_act_download(h, a, act_state, st);            // (synchronises)
-    };
-    rc = run();
-    lpvmpc_act_free(a);
-    return rc;
+    H2D(a.ring, ring.data(), ring.size() * 8); H2D(a.servo, sv.data(), b * 8); H2D(a.k, k.data(), b * 4);
+    H2D(h->d_xlast, state, b * 8 * 8); H2D(h->d_states, u, b * 2 * 8);
+    HIP_TRY(h, lpvmpc::launch_plant_actuated(B, h->d_xlast, h->d_states, lpvmpc_plant_cfg(h, n_sub, dt_sim, mu_sim), a, st));
+    D2H(state, h->d_xlast, b * 8 * 8);
+    return lpvmpc_act_download(h, a, act_state, st);                // (synchronises)
 }
 
 extern "C" int lpvmpc_actuator_read(lpvmpc_handle *h, double *act_state, double *path_hist, double *tt_hist) {
@@ -114,7 +104,7 @@ extern "C" int lpvmpc_actuator_read(lpvmpc_handle *h, double *act_state, double 
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t st = h->stream;
     if (path_hist) D2H(path_hist, h->d_uold, (size_t)h->cl_B * (2 + h->cfg.steering_delay) * 8);
-    if (act_state) { int rc = lpvmpc_act_download(h, h->cl_act, act_state, st); if (rc) return rc; }
+    if (act_state) { int rc = lpvmpc_act_download(h, h->cl_act.d, act_state, st); if (rc) return rc; }
     HIP_TRY(h, hipStreamSynchronize(st));
     return LPVMPC_OK;
 }

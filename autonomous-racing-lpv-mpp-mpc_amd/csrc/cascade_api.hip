@@ -8,20 +8,28 @@
 
 // fleet state of a cascade, owned by the controller handle
 struct lpvmpc_cascade {
-    lpvmpc_handle *plan;
-    int B, M, q9;
-    int ctrl_ticks, plan_ticks, index;       // `index` of CMAIN:219-235 (0: re-read the windows on this tick)
-    int prefetch;                            // 1: planner tick j+1 is enqueued as soon as message j has its first reader
-    int n_sub[3];
-    double hw, slack, dt_sim, mu_sim;
-    double *plant, *cmd, *local, *ref0, *SSc;       // [B][8], [B][2], [B][6], [B][3], [B]
-    int32_t *lap, *lap_tick;                        // [B]
-    int32_t *alive_ticks;                           // [B] controller ticks entered with a finite plant state
-    double *estv;                                   // [B][8] with an estimator: the estimate in the plant's layout, read by both nodes' measurements
-    double *refs, *sig, *SSp, *pose, *px0;          // planner side: [2][B][5][M] (message j in buffer j % 2), [B][5][Np], [B][Np+1], [B][3], [B][5]
-    hipStream_t s_ctrl, s_plan;                     // the two nodes run on their own streams
-    hipEvent_t ev_plan;                             // planner tick done (planner stream) -> controller stream waits
-    hipEvent_t ev_ctrl;                             // readers of the other message buffer done -> planner stream waits
+    lpvmpc_handle *plan = nullptr;
+    int B = 0, M = 0, q9 = 0;
+    int ctrl_ticks = 0, plan_ticks = 0, index = 0;   // `index` of CMAIN:219-235 (0: re-read the windows on this tick)
+    int prefetch = 0;                        // 1: planner tick j+1 is enqueued as soon as message j has its first reader
+    int n_sub[3] = {0, 0, 0};
+    double hw = 0, slack = 0, dt_sim = 0, mu_sim = 0;
+    DevArena mem;                            // the buffers below
+    double *plant = nullptr, *cmd = nullptr, *local = nullptr, *ref0 = nullptr, *SSc = nullptr;   // [B][8], [B][2], [B][6], [B][3], [B]
+    int32_t *lap = nullptr, *lap_tick = nullptr;    // [B]
+    int32_t *alive_ticks = nullptr;                 // [B] controller ticks entered with a finite plant state
+    double *estv = nullptr;                         // [B][8] with an estimator: the estimate in the plant's layout, read by both nodes' measurements
+    double *refs = nullptr, *sig = nullptr, *SSp = nullptr, *pose = nullptr, *px0 = nullptr;   // planner side: [2][B][5][M] (message j in buffer j % 2), [B][5][Np], [B][Np+1], [B][3], [B][5]
+    hipStream_t s_ctrl = nullptr, s_plan = nullptr; // the two nodes run on their own streams
+    hipEvent_t ev_plan = nullptr;                   // planner tick done (planner stream) -> controller stream waits
+    hipEvent_t ev_ctrl = nullptr;                   // readers of the other message buffer done -> planner stream waits
+    ~lpvmpc_cascade() {                             // buffers, events, streams
+        mem.release();
+        if (ev_plan) (void)hipEventDestroy(ev_plan);
+        if (ev_ctrl) (void)hipEventDestroy(ev_ctrl);
+        if (s_ctrl) (void)hipStreamDestroy(s_ctrl);
+        if (s_plan) (void)hipStreamDestroy(s_plan);
+    }
 };
 
 extern "C" void lpvmpc_handoff_default_config(lpvmpc_handoff_config *c) {
@@ -71,12 +79,14 @@ extern "C" int lpvmpc_handoff_setup(lpvmpc_handle *h, const lpvmpc_handoff_confi
     std::vector<double> wt((size_t)N * M), fwt((size_t)N * M);                 // device copies are transposed: [N][M]
     for (int m = 0; m < M; ++m) for (int n = 0; n < N; ++n) { wt[(size_t)n * M + m] = w[(size_t)m * N + n]; fwt[(size_t)n * M + m] = fw[(size_t)m * N + n]; }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if (h->d_Wop) { (void)hipFree(h->d_Wop); (void)hipFree(h->d_FWop); h->d_Wop = h->d_FWop = nullptr; h->ho_M = 0; }
-    HIP_TRY(h, hipMalloc((void **)&h->d_Wop, wt.size() * 8));
-    HIP_TRY(h, hipMalloc((void **)&h->d_FWop, fwt.size() * 8));
-    HIP_TRY(h, hipMemcpy(h->d_Wop, wt.data(), wt.size() * 8, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_FWop, fwt.data(), fwt.size() * 8, hipMemcpyHostToDevice));
-    h->ho_M = M;
+    release<Handoff>(*h);
+    Handoff o;
+    HIP_TRY(h, o.ho_mem.alloc(o.d_Wop, wt.size() * 8));
+    HIP_TRY(h, o.ho_mem.alloc(o.d_FWop, fwt.size() * 8));
+    HIP_TRY(h, hipMemcpy(o.d_Wop, wt.data(), wt.size() * 8, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(o.d_FWop, fwt.data(), fwt.size() * 8, hipMemcpyHostToDevice));
+    o.ho_M = M;
+    static_cast<Handoff &>(*h) = std::move(o);
     return M;
 }
 
@@ -89,20 +99,16 @@ extern "C" int lpvmpc_handoff_batch(lpvmpc_handle *h, int32_t B, const double *x
     hipStream_t st = h->stream;
     // workspace reuse: xPred -> d_xPred, SS -> d_curv ([cap][N+1]), pose -> d_uold ([cap][2] is too small: use d_resid [cap][4]),
     // sig -> d_states ([cap][N][5] = [cap][5][N]); refs need [B][5][M] words: a temporary
+    DevArena tmp;
     double *d_refs = nullptr;
-    HIP_TRY(h, hipMalloc((void **)&d_refs, b * 5 * M * 8));
-    auto body = [&]() -> int {
-        H2D(h->d_xPred, xPred, b * (N + 1) * 5 * 8); H2D(h->d_curv, SS, b * (N + 1) * 8); H2D(h->d_resid, pose, b * 3 * 8);
-        HIP_TRY(h, lpvmpc::launch_plan_pose(h->d_cfg, B, h->d_xPred, h->d_curv, h->d_resid, h->d_states, st));
-        HIP_TRY(h, lpvmpc::launch_resample(B, (int)N, (int)M, h->d_Wop, h->d_FWop, h->d_states, d_refs, st));
-        D2H(SS, h->d_curv, b * (N + 1) * 8); D2H(pose, h->d_resid, b * 3 * 8); D2H(refs, d_refs, b * 5 * M * 8);
-        if (sig) D2H(sig, h->d_states, b * 5 * N * 8);
-        HIP_TRY(h, hipStreamSynchronize(st));
-        return LPVMPC_OK;
-    };
-    rc = body();
-    (void)hipFree(d_refs);
-    return rc;
+    HIP_TRY(h, tmp.alloc(d_refs, b * 5 * M * 8));
+    H2D(h->d_xPred, xPred, b * (N + 1) * 5 * 8); H2D(h->d_curv, SS, b * (N + 1) * 8); H2D(h->d_resid, pose, b * 3 * 8);
+    HIP_TRY(h, lpvmpc::launch_plan_pose(h->d_cfg, B, h->d_xPred, h->d_curv, h->d_resid, h->d_states, st));
+    HIP_TRY(h, lpvmpc::launch_resample(B, (int)N, (int)M, h->d_Wop, h->d_FWop, h->d_states, d_refs, st));
+    D2H(SS, h->d_curv, b * (N + 1) * 8); D2H(pose, h->d_resid, b * 3 * 8); D2H(refs, d_refs, b * 5 * M * 8);
+    if (sig) D2H(sig, h->d_states, b * 5 * N * 8);
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return LPVMPC_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -111,16 +117,10 @@ extern "C" int lpvmpc_handoff_batch(lpvmpc_handle *h, int32_t B, const double *x
 void lpvmpc_cascade_free(lpvmpc_handle *h) {
     lpvmpc_cascade *c = h->cascade;
     if (!c) return;
-    void *ptrs[] = {c->estv, c->plant, c->cmd, c->local, c->ref0, c->SSc, c->lap, c->lap_tick, c->alive_ticks, c->refs, c->sig, c->SSp, c->pose, c->px0};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (c->ev_plan) (void)hipEventDestroy(c->ev_plan);
-    if (c->ev_ctrl) (void)hipEventDestroy(c->ev_ctrl);
-    if (c->s_ctrl) (void)hipStreamDestroy(c->s_ctrl);
-    if (c->s_plan) (void)hipStreamDestroy(c->s_plan);
-    if (c->plan && c->plan->cascade_owner == h) c->plan->cascade_owner = nullptr;
-    if (h->obs_state) { (void)hipFree(h->obs_state); h->obs_state = nullptr; }
+    if (c->plan->cascade_owner == h) c->plan->cascade_owner = nullptr;
     delete c;
     h->cascade = nullptr;
+    release<ObsState>(*h);                   // the cascade's estimator state (the gains stay with the handle)
 }
 
 extern "C" int lpvmpc_cascade_init(lpvmpc_handle *h, lpvmpc_handle *plan, int32_t B, const double *plant0, const double *cmd0,
@@ -144,20 +144,17 @@ extern "C" int lpvmpc_cascade_init(lpvmpc_handle *h, lpvmpc_handle *plan, int32_
     rc = lpvmpc_model_check(h, B, "lpvmpc_cascade_init"); if (rc) return rc;
     rc = lpvmpc_model_check(plan, B, "lpvmpc_cascade_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
     lpvmpc_cascade_free(h);
-    lpvmpc_cascade *c = new (std::nothrow) lpvmpc_cascade();
+    // the cascade is built in c and installed in the two handles after the last step that can fail: a failed call leaves none
+    std::unique_ptr<lpvmpc_cascade> c(new (std::nothrow) lpvmpc_cascade());
     if (!c) return fail(h, LPVMPC_E_NOMEM, "out of host memory");
-    std::memset(c, 0, sizeof(*c));
-    h->cascade = c;
     c->prefetch = h->cascade_prefetch;
-    plan->cascade_owner = h;
     c->plan = plan; c->B = B; c->M = plan->ho_M; c->q9 = q9_swap != 0; c->hw = half_width; c->slack = slack; c->dt_sim = dt_sim; c->mu_sim = mu_sim;
     for (int i = 0; i < 3; ++i) c->n_sub[i] = n_sub[i];
     const size_t b = B, N = h->cfg.N, Np = plan->cfg.N, M = c->M;
-#define ALLOC(p, n) HIP_TRY(h, hipMalloc((void **)&(p), (n)))
+#define ALLOC(p, n) HIP_TRY(h, c->mem.alloc(p, (n)))
     ALLOC(c->plant, b * 8 * 8); ALLOC(c->cmd, b * 2 * 8); ALLOC(c->local, b * 6 * 8); ALLOC(c->ref0, b * 3 * 8); ALLOC(c->SSc, b * 8);
     ALLOC(c->lap, b * 4); ALLOC(c->lap_tick, b * 4); ALLOC(c->alive_ticks, b * 4);
     ALLOC(c->refs, 2 * b * 5 * M * 8); ALLOC(c->sig, b * 5 * Np * 8); ALLOC(c->SSp, b * (Np + 1) * 8); ALLOC(c->pose, b * 3 * 8); ALLOC(c->px0, b * 5 * 8);
-#undef ALLOC
     HIP_TRY(h, hipEventCreateWithFlags(&c->ev_plan, hipEventDisableTiming));
     HIP_TRY(h, hipEventCreateWithFlags(&c->ev_ctrl, hipEventDisableTiming));
     HIP_TRY(h, hipStreamCreateWithFlags(&c->s_ctrl, hipStreamNonBlocking));
@@ -176,12 +173,14 @@ extern "C" int lpvmpc_cascade_init(lpvmpc_handle *h, lpvmpc_handle *plan, int32_
     HIP_TRY(h, hipStreamSynchronize(st));
     h->state_valid_B = 0; plan->state_valid_B = 0;
     if (h->obs_cfg) {             // the estimator in the loop: both nodes measure the estimate (CMAIN:179-180, PMAIN:141 read pos_info)
-        HIP_TRY(h, hipMalloc((void **)&c->estv, b * 8 * 8));
+        ALLOC(c->estv, b * 8 * 8);
         std::vector<double> v(plant0, plant0 + b * 8);
         for (size_t i = 0; i < b; ++i) v[i * 8 + 4] = v[i * 8 + 5] = 0.0;
         H2D(c->estv, v.data(), b * 8 * 8);
         rc = lpvmpc_observer_start(h, *h->obs_cfg, B, plant0, dt_sim, 1); if (rc) return rc;
     }
+#undef ALLOC
+    h->cascade = c.release(); plan->cascade_owner = h;
     return LPVMPC_OK;
 }
 
@@ -203,9 +202,8 @@ static int planner_tick(lpvmpc_handle *h, lpvmpc_cascade *c) {
     }
     // uOld of the planner is always (0, 0): its node only appends to OldSteering / OldAccelera
     SolveArgs a{B, x0, p->d_AB, nullptr, nullptr, p->d_maxey, p->d_xPred, p->d_uPred, p->d_status, p->d_iters, p->d_polish, p->d_resid,
-                p->warm_mode ? p->d_state : nullptr, (p->warm_mode && p->state_valid_B == B) ? p->warm_mode : 0, 5};
-    int rc = lpvmpc_launch_solve_timed(p, a, st); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(p));
-    if (p->warm_mode) p->state_valid_B = B;
+                nullptr, 0, 5};
+    int rc = lpvmpc_launch_solve_warm(p, a, st); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(p));
     HIP_TRY(h, lpvmpc::launch_plan_pose(p->d_cfg, B, p->d_xPred, c->SSp, c->pose, c->sig, st));
     HIP_TRY(h, lpvmpc::launch_resample(B, Np, c->M, p->d_Wop, p->d_FWop, c->sig, refs, st));
     c->plan_ticks++;
@@ -243,9 +241,8 @@ extern "C" int lpvmpc_cascade_tick(lpvmpc_handle *h, int32_t n_ticks) {
         // Controller_TT.LPVPrediction(LocalState, uPred, vel_ref, curv_ref, Cf_new, LapNumber >= 1); solve(LocalState, ...)  (CMAIN:361-363)
         HIP_TRY(h, lpvmpc::launch_lpv(h->dev, h->d_cfg, h->d_model, B, c->local, h->d_uPred, h->d_vel, h->d_curv, 60.0, 1, h->d_states, h->d_AB, st));
         SolveArgs a{B, c->local, h->d_AB, h->d_vel, h->d_uold, nullptr, h->d_xPred, h->d_uPred, h->d_status, h->d_iters, h->d_polish, h->d_resid,
-                    h->warm_mode ? h->d_state : nullptr, (h->warm_mode && h->state_valid_B == B) ? h->warm_mode : 0, 6};
-        int rc = lpvmpc_launch_solve_timed(h, a, st); if (rc) return rc;
-        if (h->warm_mode) h->state_valid_B = B;
+                    nullptr, 0, 6};
+        int rc = lpvmpc_launch_solve_warm(h, a, st); if (rc) return rc;
         if (c->estv)
             HIP_TRY(h, lpvmpc::launch_cascade_plant_observe(B, N, h->d_uPred, c->cmd, c->plant, lpvmpc_plant_cfg(h, c->n_sub[k % 3], c->dt_sim, c->mu_sim),
                                                              c->estv, h->obs_gains, h->obs_state, h->obs_p, st));

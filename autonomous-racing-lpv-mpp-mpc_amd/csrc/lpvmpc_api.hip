@@ -61,29 +61,9 @@ extern "C" void lpvmpc_default_config(int32_t kind, lpvmpc_config *c) {
     c->track_rows = 0;
 }
 
-static void free_ws(lpvmpc_handle *h) {
-    void *ptrs[] = {h->d_x0, h->d_uprev, h->d_vel, h->d_curv, h->d_uold, h->d_maxey, h->d_AB, h->d_states,
-                    h->d_xPred, h->d_uPred, h->d_resid, h->d_xlast, h->d_delta, h->d_status, h->d_iters, h->d_polish, h->d_state, h->d_scal,
-                    h->d_active};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    h->d_x0 = h->d_uprev = h->d_vel = h->d_curv = h->d_uold = h->d_maxey = h->d_AB = h->d_states = nullptr;
-    h->d_xPred = h->d_uPred = h->d_resid = h->d_xlast = h->d_delta = nullptr;
-    h->d_status = h->d_iters = h->d_polish = nullptr; h->d_state = nullptr; h->d_scal = nullptr; h->state_valid_B = 0;
-    h->d_active = nullptr;
-    h->cap = 0;
-}
-
 static const int kEventRing = 1024;      // event pairs kept by lpvmpc_set_timing (main launches, and separately resume passes)
 extern "C" int lpvmpc_join(lpvmpc_handle *h, void *stream);
 // ---- straggler deferral: the two pools ---------------------------------------------------------------------------------
-static void free_defer(lpvmpc_handle *h) {
-    for (int i = 0; i < 2; ++i) {
-        if (h->dpool[i]) (void)hipFree(h->dpool[i]);
-        if (h->dcount[i]) (void)hipFree(h->dcount[i]);
-        h->dpool[i] = nullptr; h->dcount[i] = nullptr;
-    }
-    h->defer_cur_cap = 0;                   // (the counters of lpvmpc_defer_stats live as long as the handle: see ensure_defer / lpvmpc_destroy)
-}
 // an entry holds the LDS image of whichever kernel variant runs (the run-time-horizon kernel keeps its factor tiles in LDS:
 // the largest image) plus the loop scalars and output pointers
 static int entry_stride_for(int N) { return (N + 1) * (3 * lpvmpc::kTS + 19 * 8 + 8) + 16 + 64 + 8 + 80 + 64 + lpvmpc::kParkScalars; }
@@ -96,15 +76,17 @@ static int ensure_defer(lpvmpc_handle *h, int B, hipStream_t st) {
         int rc = lpvmpc_join(h, (void *)(h->defer_stream_set ? h->defer_stream : st)); if (rc) return rc;
         HIP_TRY(h, hipStreamSynchronize(h->defer_stream_set ? h->defer_stream : st));
     }
-    free_defer(h);
+    release<DeferPools>(*h);
+    DeferPools p;
     for (int i = 0; i < 2; ++i) {
-        HIP_TRY(h, hipMalloc((void **)&h->dpool[i], (size_t)cap * stride * 8));
-        HIP_TRY(h, hipMalloc((void **)&h->dcount[i], 16));
-        HIP_TRY(h, hipMemsetAsync(h->dcount[i], 0, 16, st));
+        HIP_TRY(h, p.defer_mem.alloc(p.dpool[i], (size_t)cap * stride * 8));
+        HIP_TRY(h, p.defer_mem.alloc(p.dcount[i], 16));
+        HIP_TRY(h, hipMemsetAsync(p.dcount[i], 0, 16, st));
     }
     if (!h->defer_event) HIP_TRY(h, hipEventCreateWithFlags(&h->defer_event, hipEventDisableTiming));
-    if (!h->dstats) { HIP_TRY(h, hipMalloc((void **)&h->dstats, 16)); HIP_TRY(h, hipMemsetAsync(h->dstats, 0, 16, st)); }
-    h->defer_cur_cap = cap; h->defer_stride = stride; h->dcur = 0;
+    if (!h->dstats) { HIP_TRY(h, h->mem.alloc(h->dstats, 16)); HIP_TRY(h, hipMemsetAsync(h->dstats, 0, 16, st)); }
+    p.defer_cur_cap = cap; p.defer_stride = stride;
+    static_cast<DeferPools &>(*h) = std::move(p); h->dcur = 0;
     return LPVMPC_OK;
 }
 // one resume pass on `st`: continues the entries of pool[dcur] for `budget` more iterations (0 = to completion), parks the
@@ -117,30 +99,42 @@ static int resume_pass(lpvmpc_handle *h, int budget, hipStream_t st) {
     a.pool_in = h->dpool[A]; a.pool_in_count = h->dcount[A];
     a.pool = h->dpool[Bp]; a.pool_count = h->dcount[Bp];
     a.pool_cap = h->defer_cur_cap; a.pool_stride = h->defer_stride; a.x0_stride = h->nx; a.defer_stats = h->dstats;
-    const int slot = h->rv_count % kEventRing;
-    if (h->timing) HIP_TRY(h, hipEventRecord(h->rv0[slot], st));
+    const int slot = h->rv.count % kEventRing;
+    if (h->timing) HIP_TRY(h, hipEventRecord(h->rv.e0[slot], st));
     HIP_TRY(h, lpvmpc::launch_solve(h->dev, h->d_cfg, a, st, h->force_generic));
-    if (h->timing) { HIP_TRY(h, hipEventRecord(h->rv1[slot], st)); h->rv_count++; }
+    if (h->timing) { HIP_TRY(h, hipEventRecord(h->rv.e1[slot], st)); h->rv.count++; }
     h->dcur = Bp;
+    return LPVMPC_OK;
+}
+
+// the pools are ordered by stream: hands them over from the stream of the last deferred call to st
+static int defer_take_stream(lpvmpc_handle *h, hipStream_t st) {
+    if (h->defer_stream_set && h->defer_stream != st) {
+        HIP_TRY(h, hipEventRecord(h->defer_event, h->defer_stream));
+        HIP_TRY(h, hipStreamWaitEvent(st, h->defer_event, 0));
+    }
+    h->defer_stream = st; h->defer_stream_set = true;
     return LPVMPC_OK;
 }
 
 static int ensure_ws(lpvmpc_handle *h, int B) {
     if (B <= h->cap) return LPVMPC_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    free_ws(h);
+    release<Workspace>(*h); h->state_valid_B = 0;     // engines cache workspace pointers: batch calls are refused on busy handles
+    Workspace w;
     const size_t N = h->cfg.N, nx = h->nx, nb = h->nb, b = B;
-#define ALLOC(p, n) HIP_TRY(h, hipMalloc((void **)&(p), (n)))
-    ALLOC(h->d_x0, b * nx * 8); ALLOC(h->d_uprev, b * N * 2 * 8); ALLOC(h->d_vel, b * (N + 1) * 8);
-    ALLOC(h->d_curv, b * (N + 1) * 8); ALLOC(h->d_uold, b * (2 + h->cfg.steering_delay) * 8); ALLOC(h->d_maxey, b * 8);
-    ALLOC(h->d_AB, b * N * nx * nb * 8); ALLOC(h->d_states, b * N * nx * 8);
-    ALLOC(h->d_xPred, b * (N + 1) * nx * 8); ALLOC(h->d_uPred, b * N * 2 * 8); ALLOC(h->d_resid, b * 4 * 8);
-    ALLOC(h->d_xlast, b * N * 6 * 8); ALLOC(h->d_delta, b * N * 8);
-    ALLOC(h->d_state, b * 3 * (N + 1) * 8 * 8);
-    if (h->cfg.kind == LPVMPC_KIND_PLANNER && N == 30) ALLOC(h->d_scal, b * 3 * (N + 1) * 8 * 8);      // see SolveArgs::scal
-    ALLOC(h->d_status, b * 4); ALLOC(h->d_iters, b * 4); ALLOC(h->d_polish, b * 4); ALLOC(h->d_active, b * 4);
+#define ALLOC(p, n) HIP_TRY(h, w.ws_mem.alloc(w.p, (n)))
+    ALLOC(d_x0, b * nx * 8); ALLOC(d_uprev, b * N * 2 * 8); ALLOC(d_vel, b * (N + 1) * 8);
+    ALLOC(d_curv, b * (N + 1) * 8); ALLOC(d_uold, b * (2 + h->cfg.steering_delay) * 8); ALLOC(d_maxey, b * 8);
+    ALLOC(d_AB, b * N * nx * nb * 8); ALLOC(d_states, b * N * nx * 8);
+    ALLOC(d_xPred, b * (N + 1) * nx * 8); ALLOC(d_uPred, b * N * 2 * 8); ALLOC(d_resid, b * 4 * 8);
+    ALLOC(d_xlast, b * N * 6 * 8); ALLOC(d_delta, b * N * 8);
+    ALLOC(d_state, b * 3 * (N + 1) * 8 * 8);
+    if (h->cfg.kind == LPVMPC_KIND_PLANNER && N == 30) ALLOC(d_scal, b * 3 * (N + 1) * 8 * 8);      // see SolveArgs::scal
+    ALLOC(d_status, b * 4); ALLOC(d_iters, b * 4); ALLOC(d_polish, b * 4); ALLOC(d_active, b * 4);
 #undef ALLOC
-    h->cap = B;
+    w.cap = B;
+    static_cast<Workspace &>(*h) = std::move(w);
     return LPVMPC_OK;
 }
 
@@ -166,20 +160,6 @@ extern "C" lpvmpc_handle *lpvmpc_create(const lpvmpc_config *cfg) {
     if (!h) { fail(nullptr, LPVMPC_E_NOMEM, "out of host memory"); return nullptr; }
     h->cfg = *cfg;
     h->nx = cfg->kind == LPVMPC_KIND_CONTROLLER ? 6 : 5; h->nb = h->nx + 2;
-    h->d_cfg = nullptr; h->cap = 0; h->force_generic = 0; h->timing = false; h->last_ms = -1.0; h->stream = nullptr; h->ev_count = 0;
-    h->d_x0 = h->d_uprev = h->d_vel = h->d_curv = h->d_uold = h->d_maxey = h->d_AB = h->d_states = nullptr;
-    h->d_xPred = h->d_uPred = h->d_resid = h->d_xlast = h->d_delta = nullptr;
-    h->d_status = h->d_iters = h->d_polish = nullptr; h->d_state = nullptr; h->d_scal = nullptr; h->warm_mode = 0; h->state_valid_B = 0;
-    h->cl_plant = h->cl_local = h->cl_cmd = nullptr; h->cl_local_next = nullptr; h->cl_next_valid = 0; h->cl_B = 0; h->cl_first_it = 1; h->cl_q9 = 1; h->cl_ticks = 0;
-    h->cl_actuated = 0; h->cl_act = lpvmpc::ActDev{}; h->cl_veh = lpvmpc::VehPlantCfg{};
-    h->d_Wop = h->d_FWop = nullptr; h->ho_M = 0; h->cascade = nullptr; h->cascade_owner = nullptr; h->cascade_prefetch = 1;
-    h->race = nullptr; h->race_owner = nullptr; h->d_active = nullptr; h->solve_mask = nullptr;
-    h->defer_after = 0; h->defer_budget = 200; h->defer_cap = 0; h->defer_cur_cap = 0; h->defer_stride = 0; h->rv_count = 0;
-    h->dpool[0] = h->dpool[1] = nullptr; h->dcount[0] = h->dcount[1] = nullptr; h->dstats = nullptr; h->dcur = 0; h->defer_stream = nullptr; h->defer_event = nullptr;
-    h->defer_stream_set = false; h->defer_tail = 1; h->defer_skip_pass = false;
-    h->h_pack_in = h->h_pack_out = h->d_pack_in = h->d_pack_out = nullptr;
-    h->obs_cfg = nullptr; h->obs_gains = h->obs_state = nullptr; h->obs_ws = nullptr; h->obs_ws_cap = 0; h->obs_B = 0;
-    h->d_model = nullptr; h->model_B = 0;
     DevCfg &d = h->dev;
     std::memset(&d, 0, sizeof(d));
     d.kind = cfg->kind; d.N = cfg->N; d.track_rows = cfg->track_rows; d.max_iter = cfg->max_iter;
@@ -205,7 +185,7 @@ extern "C" lpvmpc_handle *lpvmpc_create(const lpvmpc_config *cfg) {
     d.rho_tol = cfg->adaptive_rho_tolerance;
     std::memcpy(d.track, cfg->track, sizeof(double) * 6 * cfg->track_rows);
     if (hipSetDevice(cfg->device) != hipSuccess) { fail(nullptr, LPVMPC_E_HIP, "hipSetDevice(%d) failed", cfg->device); delete h; return nullptr; }
-    if (hipMalloc((void **)&h->d_cfg, sizeof(DevCfg)) != hipSuccess ||
+    if (h->mem.alloc(h->d_cfg, sizeof(DevCfg)) != hipSuccess ||
         hipMemcpy(h->d_cfg, &h->dev, sizeof(DevCfg), hipMemcpyHostToDevice) != hipSuccess) {
         fail(nullptr, LPVMPC_E_HIP, "uploading the configuration failed"); lpvmpc_destroy(h); return nullptr; }
     const size_t lds = lpvmpc::solve_lds_bytes(cfg->kind, cfg->N);
@@ -217,38 +197,11 @@ extern "C" void lpvmpc_destroy(lpvmpc_handle *h) {
     if (!h) return;
     (void)hipSetDevice(h->cfg.device);
     (void)hipDeviceSynchronize();          // launches of this handle may still be running on the caller's streams (deferred calls: their resume passes)
-    free_ws(h);
-    if (h->cl_plant) (void)hipFree(h->cl_plant);
-    if (h->cl_local_next) (void)hipFree(h->cl_local_next);
-    if (h->cl_local) (void)hipFree(h->cl_local);
-    if (h->cl_cmd) (void)hipFree(h->cl_cmd);
-    lpvmpc_act_free(h->cl_act);
-    lpvmpc_plant_free(h->cl_veh);
-    lpvmpc_model_free(h);
     if (h->cascade) lpvmpc_cascade_free(h);                                  // (frees the cascade's estimator state)
     if (h->race) lpvmpc_race_free(h);
     if (h->race_owner && h->race_owner->race) lpvmpc_race_free(h->race_owner);   // a handle the race of another one drives: end that race
-    if (h->obs_state) (void)hipFree(h->obs_state);
-    if (h->obs_gains) (void)hipFree(h->obs_gains);
-    if (h->obs_ws) (void)hipFree(h->obs_ws);
-    h->obs_state = h->obs_gains = nullptr; h->obs_ws = nullptr;
-    delete h->obs_cfg;
     // a planner handle that a controller's cascade still drives: end that cascade first (it holds a pointer to this handle)
     if (h->cascade_owner && h->cascade_owner->cascade) lpvmpc_cascade_free(h->cascade_owner);
-    if (h->h_pack_in) (void)hipHostFree(h->h_pack_in);
-    if (h->h_pack_out) (void)hipHostFree(h->h_pack_out);
-    if (h->d_pack_in) (void)hipFree(h->d_pack_in);
-    if (h->d_pack_out) (void)hipFree(h->d_pack_out);
-    if (h->d_Wop) (void)hipFree(h->d_Wop);
-    if (h->d_FWop) (void)hipFree(h->d_FWop);
-    if (h->d_cfg) (void)hipFree(h->d_cfg);
-    free_defer(h);
-    if (h->dstats) (void)hipFree(h->dstats);
-    if (h->defer_event) (void)hipEventDestroy(h->defer_event);
-    for (hipEvent_t e : h->rv0) (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->rv1) (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->ev0) (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->ev1) (void)hipEventDestroy(e);
     delete h;
 }
 
@@ -281,7 +234,7 @@ extern "C" int lpvmpc_set_option(lpvmpc_handle *h, const char *name, int32_t val
         if (value < 0) return fail(h, LPVMPC_E_ARG, "defer_pool must be >= 0 (pool entries; 0 = max(64, B / 8))");
         HIP_TRY(h, hipSetDevice(h->cfg.device));
         if (h->dpool[0]) { int rc = lpvmpc_join(h, (void *)h->defer_stream); if (rc) return rc; HIP_TRY(h, hipStreamSynchronize(h->defer_stream)); }
-        free_defer(h); h->defer_cap = value; return LPVMPC_OK;
+        release<DeferPools>(*h); h->defer_cap = value; return LPVMPC_OK;
     }
     if (std::strcmp(name, "defer_tail") == 0) { h->defer_tail = value != 0 ? 1 : 0; return LPVMPC_OK; }      // both kernels continue the same pool entries
     if (std::strcmp(name, "cascade_prefetch") == 0) { h->cascade_prefetch = value != 0 ? 1 : 0; return LPVMPC_OK; }   // read by lpvmpc_cascade_init
@@ -297,30 +250,33 @@ extern "C" int lpvmpc_reserve(lpvmpc_handle *h, int32_t B) {
 extern "C" int lpvmpc_set_timing(lpvmpc_handle *h, int32_t on) {
     if (!h) return LPVMPC_E_ARG;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if (on && h->ev0.empty()) {
-        h->ev0.resize(kEventRing); h->ev1.resize(kEventRing);
-        for (int i = 0; i < kEventRing; ++i) { HIP_TRY(h, hipEventCreate(&h->ev0[i])); HIP_TRY(h, hipEventCreate(&h->ev1[i])); }
+    for (EventRing *r : {&h->ev, &h->rv})
+        if (on && r->e0.empty()) {
+            r->e0.resize(kEventRing); r->e1.resize(kEventRing);
+            for (int i = 0; i < kEventRing; ++i) { HIP_TRY(h, hipEventCreate(&r->e0[i])); HIP_TRY(h, hipEventCreate(&r->e1[i])); }
+        }
+    h->timing = on != 0; h->ev.count = 0; h->rv.count = 0; h->last_ms = -1.0;
+    return LPVMPC_OK;
+}
+
+// total time between the pairs of a ring (waits for them); last: the time of the newest pair, if wanted
+static int ring_time_stats(lpvmpc_handle *h, const EventRing &r, double *total_ms, int32_t *count, double *last) {
+    if (!total_ms || !count) return LPVMPC_E_ARG;
+    const int n = r.count < kEventRing ? r.count : kEventRing;
+    double tot = 0.0;
+    for (int i = 0; i < n; ++i) {
+        float ms = 0.f;
+        HIP_TRY(h, hipEventSynchronize(r.e1[i]));
+        HIP_TRY(h, hipEventElapsedTime(&ms, r.e0[i], r.e1[i]));
+        tot += ms;
+        if (last) *last = ms;
     }
-    if (on && h->rv0.empty()) {
-        h->rv0.resize(kEventRing); h->rv1.resize(kEventRing);
-        for (int i = 0; i < kEventRing; ++i) { HIP_TRY(h, hipEventCreate(&h->rv0[i])); HIP_TRY(h, hipEventCreate(&h->rv1[i])); }
-    }
-    h->timing = on != 0; h->ev_count = 0; h->rv_count = 0; h->last_ms = -1.0;
+    *total_ms = tot; *count = n;
     return LPVMPC_OK;
 }
 
 extern "C" int lpvmpc_kernel_time_stats(lpvmpc_handle *h, double *total_ms, int32_t *count) {
-    if (!h || !total_ms || !count) return LPVMPC_E_ARG;
-    const int n = h->ev_count < kEventRing ? h->ev_count : kEventRing;
-    double tot = 0.0;
-    for (int i = 0; i < n; ++i) {
-        float ms = 0.f;
-        HIP_TRY(h, hipEventSynchronize(h->ev1[i]));
-        HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0[i], h->ev1[i]));
-        tot += ms; h->last_ms = ms;
-    }
-    *total_ms = tot; *count = n;
-    return LPVMPC_OK;
+    return h ? ring_time_stats(h, h->ev, total_ms, count, &h->last_ms) : LPVMPC_E_ARG;
 }
 
 extern "C" double lpvmpc_last_kernel_ms(lpvmpc_handle *h) {
@@ -343,13 +299,21 @@ static int launch_lpv(lpvmpc_handle *h, int B, const double *x0, const double *u
 }
 
 int lpvmpc_launch_solve_timed(lpvmpc_handle *h, const SolveArgs &a, hipStream_t st) {
-    const int slot = h->ev_count % kEventRing;
-    if (h->timing) HIP_TRY(h, hipEventRecord(h->ev0[slot], st));
+    const int slot = h->ev.count % kEventRing;
+    if (h->timing) HIP_TRY(h, hipEventRecord(h->ev.e0[slot], st));
     SolveArgs b = a;
     if (h->d_scal && a.B <= h->cap) b.scal = h->d_scal;          // (the launcher ignores it for deferred / resumed launches)
     if (h->solve_mask && !a.resume) b.active = h->solve_mask;      // lpvmpc_solve_batch_masked (synchronous: its launch carries no riders)
     HIP_TRY(h, lpvmpc::launch_solve(h->dev, h->d_cfg, b, st, h->force_generic));
-    if (h->timing) { HIP_TRY(h, hipEventRecord(h->ev1[slot], st)); h->ev_count++; }
+    if (h->timing) { HIP_TRY(h, hipEventRecord(h->ev.e1[slot], st)); h->ev.count++; }
+    return LPVMPC_OK;
+}
+
+int lpvmpc_launch_solve_warm(lpvmpc_handle *h, SolveArgs a, hipStream_t st) {
+    a.state = h->warm_mode ? h->d_state : nullptr;
+    a.warm = (h->warm_mode && h->state_valid_B == a.B) ? h->warm_mode : 0;
+    int rc = lpvmpc_launch_solve_timed(h, a, st); if (rc) return rc;
+    if (h->warm_mode) h->state_valid_B = a.B;
     return LPVMPC_OK;
 }
 
@@ -357,7 +321,7 @@ int lpvmpc_launch_solve_timed(lpvmpc_handle *h, const SolveArgs &a, hipStream_t 
 // windows, receding-horizon inputs, last commands, statuses): a stand-alone batch call on the same handle would overwrite it
 // -- or, with a larger B, reallocate it -- without any error.  Such calls are refused; use a second handle.
 int lpvmpc_check_batch(lpvmpc_handle *h, int B, const char *who) {
-    if (h && (h->cl_plant || h->cascade || h->cascade_owner || h->race || h->race_owner))
+    if (h && busy(h))
         return fail(h, LPVMPC_E_ARG, "%s: this handle runs a %s whose state lives in its workspace; use another handle for batch calls "
                     "(lpvmpc_cl_release ends the fleet)", who, h->cl_plant ? "closed-loop fleet" : (h->race || h->race_owner) ? "race" : "planner + controller cascade");
     return lpvmpc_check_common(h, B, who);
@@ -386,9 +350,11 @@ struct IoPack {
     int begin(lpvmpc_handle *h_, hipStream_t st_, size_t in_bytes, size_t out_bytes, int n_arrays) {
         h = h_; st = st_; in_off = out_off = 0; n_out = 0;
         on = in_bytes + 256 * (size_t)n_arrays <= kPackBytes && out_bytes + 256 * (size_t)n_arrays <= kPackBytes;
-        if (on && !h->h_pack_in) {
-            HIP_TRY(h, hipHostMalloc((void **)&h->h_pack_in, kPackBytes)); HIP_TRY(h, hipHostMalloc((void **)&h->h_pack_out, kPackBytes));
-            HIP_TRY(h, hipMalloc((void **)&h->d_pack_in, kPackBytes)); HIP_TRY(h, hipMalloc((void **)&h->d_pack_out, kPackBytes));
+        if (on && !h->d_pack_out) {                       // (the last of the four: set once all are there)
+            if (!h->h_pack_in) HIP_TRY(h, hipHostMalloc((void **)&h->h_pack_in, kPackBytes));
+            if (!h->h_pack_out) HIP_TRY(h, hipHostMalloc((void **)&h->h_pack_out, kPackBytes));
+            if (!h->d_pack_in) HIP_TRY(h, h->mem.alloc(h->d_pack_in, kPackBytes));
+            HIP_TRY(h, h->mem.alloc(h->d_pack_out, kPackBytes));
         }
         return LPVMPC_OK;
     }
@@ -424,6 +390,17 @@ struct IoPack {
 };
 #define IO_TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 
+// rows [A|B] of the device layout [rows][nx][nx + 2] -> the caller's A [rows][nx][nx] and B [rows][nx][2] (either may be NULL)
+static void split_ab(const double *src, size_t rows, size_t nx, double *A, double *Bm) {
+    const size_t nb = nx + 2;
+    for (size_t t = 0; t < rows; ++t)
+        for (size_t r = 0; r < nx; ++r) {
+            const double *row = src + (t * nx + r) * nb;
+            if (A) for (size_t a = 0; a < nx; ++a) A[(t * nx + r) * nx + a] = row[a];
+            if (Bm) { Bm[(t * nx + r) * 2 + 0] = row[nx]; Bm[(t * nx + r) * 2 + 1] = row[nx + 1]; }
+        }
+}
+
 extern "C" int lpvmpc_lpv_batch(lpvmpc_handle *h, int32_t B, const double *x0, const double *u_prev,
                                 const double *vel_ref, const double *curv_s, double cf_new, int32_t lap,
                                 double *states, double *A, double *Bm) {
@@ -454,15 +431,7 @@ extern "C" int lpvmpc_lpv_batch(lpvmpc_handle *h, int32_t B, const double *x0, c
     rc = launch_lpv(h, B, (const double *)p_x0, (const double *)p_up, (const double *)p_vel, (const double *)p_curv, cf_new, lap, p_states, p_ab, st);
     if (rc) return rc;
     IO_TRY(io.flush_out());
-    if (A || Bm) {
-        const double *src = io.on ? (const double *)io.host_of(0) : ab.data();
-        for (size_t t = 0; t < b * N; ++t)
-            for (size_t r = 0; r < nx; ++r) {
-                const double *row = src + (t * nx + r) * nb;
-                if (A) for (size_t a = 0; a < nx; ++a) A[(t * nx + r) * nx + a] = row[a];
-                if (Bm) { Bm[(t * nx + r) * 2 + 0] = row[nx]; Bm[(t * nx + r) * 2 + 1] = row[nx + 1]; }
-            }
-    }
+    if (A || Bm) split_ab(io.on ? (const double *)io.host_of(0) : ab.data(), b * N, nx, A, Bm);
     return LPVMPC_OK;
 }
 
@@ -480,12 +449,7 @@ extern "C" int lpvmpc_estimate_abc_batch(lpvmpc_handle *h, int32_t B, const doub
     std::vector<double> ab(b * N * nx * nb);
     D2H(ab.data(), h->d_AB, ab.size() * 8);
     HIP_TRY(h, hipStreamSynchronize(st));
-    for (size_t t = 0; t < b * N; ++t)
-        for (size_t r = 0; r < nx; ++r) {
-            const double *row = ab.data() + (t * nx + r) * nb;
-            if (A) for (size_t a = 0; a < nx; ++a) A[(t * nx + r) * nx + a] = row[a];
-            if (Bm) { Bm[(t * nx + r) * 2 + 0] = row[nx]; Bm[(t * nx + r) * 2 + 1] = row[nx + 1]; }
-        }
+    split_ab(ab.data(), b * N, nx, A, Bm);
     return LPVMPC_OK;
 }
 
@@ -526,10 +490,8 @@ extern "C" int lpvmpc_solve_batch_AB(lpvmpc_handle *h, int32_t B, const double *
     double *o_res = (double *)io.out(resid, h->d_resid, b * 4 * 8);
     int32_t *o_pol = (int32_t *)io.out(polish, h->d_polish, b * 4);
     SolveArgs a{B, (const double *)p_x0, (const double *)p_ab, (const double *)p_vel, (const double *)p_uold, (const double *)p_mey,
-                o_x, o_u, o_st, o_it, o_pol, o_res,
-                h->warm_mode ? h->d_state : nullptr, (h->warm_mode && h->state_valid_B == B) ? h->warm_mode : 0, h->nx};
-    rc = lpvmpc_launch_solve_timed(h, a, st); if (rc) return rc;
-    if (h->warm_mode) h->state_valid_B = B;
+                o_x, o_u, o_st, o_it, o_pol, o_res, nullptr, 0, h->nx};
+    rc = lpvmpc_launch_solve_warm(h, a, st); if (rc) return rc;
     return io.flush_out();
 }
 
@@ -551,7 +513,7 @@ extern "C" int lpvmpc_solve_batch_dev(lpvmpc_handle *h, int32_t B, const double 
     if (h->warm_mode && h->defer_after > 0 && h->dpool[0]) { rc = lpvmpc_join(h, stream); if (rc) return rc; }
     rc = launch_lpv(h, B, x0, u_prev, vel_ref, curv_s, cf_new, lap, nullptr, h->d_AB, st); if (rc) return rc;
     SolveArgs a{B, x0, h->d_AB, ctrl ? vel_ref : nullptr, u_old, ctrl ? nullptr : max_ey, xPred, uPred, status, iters, polish, resid,
-                h->warm_mode ? h->d_state : nullptr, (h->warm_mode && h->state_valid_B == B) ? h->warm_mode : 0, h->nx};
+                nullptr, 0, h->nx};
     if (h->defer_after > 0) {
         // Straggler deferral: this launch parks what is still unsolved after defer_after iterations.  With defer_budget > 0 it also
         // carries the RIDERS: everything that earlier calls of this handle left parked continues, for defer_budget more iterations,
@@ -560,31 +522,26 @@ extern "C" int lpvmpc_solve_batch_dev(lpvmpc_handle *h, int32_t B, const double 
         // -- riders and new instances alike -- into the other pool, which becomes the current one.  No workgroup lasts much longer than
         // its budget, so the stream is never held by one slow instance; lpvmpc_join runs the pass that finishes whatever is still parked.
         rc = ensure_defer(h, B, st); if (rc) return rc;
-        if (h->defer_stream_set && h->defer_stream != st) {        // the pools are ordered by stream: hand them over
-            HIP_TRY(h, hipEventRecord(h->defer_event, h->defer_stream));
-            HIP_TRY(h, hipStreamWaitEvent(st, h->defer_event, 0));
-        }
-        h->defer_stream = st; h->defer_stream_set = true;
+        rc = defer_take_stream(h, st); if (rc) return rc;
         a.defer_after = h->defer_after; a.pool_cap = h->defer_cur_cap; a.pool_stride = h->defer_stride; a.defer_stats = h->dstats;
         if (h->defer_budget > 0 && !h->defer_skip_pass) {
             const int A = h->dcur, Bp = 1 - A;
             a.resume = 2; a.defer_budget = h->defer_budget;
             a.pool_in = h->dpool[A]; a.pool_in_count = h->dcount[A];
             a.pool = h->dpool[Bp]; a.pool_count = h->dcount[Bp];
-            rc = lpvmpc_launch_solve_timed(h, a, st); if (rc) return rc;
+            rc = lpvmpc_launch_solve_warm(h, a, st); if (rc) return rc;
             h->dcur = Bp;
         } else {
             // budget 0: the pass behind the call runs everything that is parked to completion.  Budget -1, and the synchronous
             // host-array entry point, which joins right away: no pass -- the closing pass (the tail kernel) takes the parked
             // instances straight from this launch.  Either way this launch parks behind what pool[dcur] already holds.
             a.resume = 0; a.pool = h->dpool[h->dcur]; a.pool_count = h->dcount[h->dcur];
-            rc = lpvmpc_launch_solve_timed(h, a, st); if (rc) return rc;
+            rc = lpvmpc_launch_solve_warm(h, a, st); if (rc) return rc;
             if (h->defer_budget == 0 && !h->defer_skip_pass) { rc = resume_pass(h, 0, st); if (rc) return rc; }
         }
     } else {
-        rc = lpvmpc_launch_solve_timed(h, a, st); if (rc) return rc;
+        rc = lpvmpc_launch_solve_warm(h, a, st); if (rc) return rc;
     }
-    if (h->warm_mode) h->state_valid_B = B;
     return LPVMPC_OK;
 }
 
@@ -593,26 +550,12 @@ extern "C" int lpvmpc_join(lpvmpc_handle *h, void *stream) {
     if (!h->dpool[0]) return LPVMPC_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t st = (hipStream_t)stream;
-    if (h->defer_stream_set && h->defer_stream != st) {
-        HIP_TRY(h, hipEventRecord(h->defer_event, h->defer_stream));
-        HIP_TRY(h, hipStreamWaitEvent(st, h->defer_event, 0));
-    }
-    h->defer_stream = st; h->defer_stream_set = true;
+    int rc = defer_take_stream(h, st); if (rc) return rc;
     return resume_pass(h, 0, st);                                  // to completion: nothing stays parked
 }
 
 extern "C" int lpvmpc_resume_time_stats(lpvmpc_handle *h, double *total_ms, int32_t *count) {
-    if (!h || !total_ms || !count) return LPVMPC_E_ARG;
-    const int n = h->rv_count < kEventRing ? h->rv_count : kEventRing;
-    double tot = 0.0;
-    for (int i = 0; i < n; ++i) {
-        float ms = 0.f;
-        HIP_TRY(h, hipEventSynchronize(h->rv1[i]));
-        HIP_TRY(h, hipEventElapsedTime(&ms, h->rv0[i], h->rv1[i]));
-        tot += ms;
-    }
-    *total_ms = tot; *count = n;
-    return LPVMPC_OK;
+    return h ? ring_time_stats(h, h->rv, total_ms, count, nullptr) : LPVMPC_E_ARG;
 }
 
 // instances parked / parking requests refused by the launches of this handle that have COMPLETED on the stream of its last deferred
@@ -755,11 +698,8 @@ extern "C" int lpvmpc_cl_release(lpvmpc_handle *h) {
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (h->cascade) { HIP_TRY(h, hipDeviceSynchronize()); lpvmpc_cascade_free(h); }
     if (h->race) lpvmpc_race_free(h);
-    if (h->cl_plant) { (void)hipFree(h->cl_plant); (void)hipFree(h->cl_local); (void)hipFree(h->cl_cmd); (void)hipFree(h->cl_local_next); h->cl_plant = h->cl_local = h->cl_cmd = h->cl_local_next = nullptr; }
-    if (h->obs_state) { (void)hipFree(h->obs_state); h->obs_state = nullptr; }
-    lpvmpc_act_free(h->cl_act); h->cl_actuated = 0;
-    lpvmpc_plant_free(h->cl_veh);
-    h->cl_B = 0; h->cl_ticks = 0; h->cl_first_it = 1; h->cl_next_valid = 0;
+    release<Fleet>(*h);
+    release<ObsState>(*h);
     return LPVMPC_OK;
 }
 
@@ -777,33 +717,31 @@ static int cl_init(lpvmpc_handle *h, int32_t B, const double *plant0, double hal
         return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: the fleet engines run the reference's steeringDelay = 0 (CMAIN:49); lpvmpc_cl_init_actuated runs delayed controllers");
     if (!plant0 || n_sub < 1 || !(dt_sim > 0)) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: bad argument");
     rc = lpvmpc_need_track(h, "lpvmpc_cl_init"); if (rc) return rc;
-    lpvmpc::ActDev a{};
-    if (act) { rc = lpvmpc_act_alloc(h, B, act, delay_a, delay_df, dt_sim, veh ? "lpvmpc_cl_init_vehicles" : "lpvmpc_cl_init_actuated", a); if (rc) { lpvmpc_act_free(a); return rc; } }
-    lpvmpc_plant_free(h->cl_veh);
-    if (veh) { rc = lpvmpc_plant_upload(h, B, *veh, dt_sim, n_sub, h->cl_veh); if (rc) { lpvmpc_act_free(a); lpvmpc_plant_free(h->cl_veh); return rc; } }
-    if (h->cl_plant) { (void)hipFree(h->cl_plant); (void)hipFree(h->cl_local); (void)hipFree(h->cl_cmd); (void)hipFree(h->cl_local_next); h->cl_plant = h->cl_local = h->cl_cmd = h->cl_local_next = nullptr; }
-    lpvmpc_act_free(h->cl_act);
-    h->cl_act = a; h->cl_actuated = act != nullptr;
-    h->cl_next_valid = 0;
-    HIP_TRY(h, hipMalloc((void **)&h->cl_local_next, (size_t)B * 6 * 8));
-    HIP_TRY(h, hipMalloc((void **)&h->cl_plant, (size_t)B * 8 * 8));
-    HIP_TRY(h, hipMalloc((void **)&h->cl_local, (size_t)B * 6 * 8));
-    HIP_TRY(h, hipMalloc((void **)&h->cl_cmd, (size_t)B * 2 * 8));
+    // the new fleet is built in f and installed after the last step that can fail: a failed call leaves no fleet (a refused
+    // actuator configuration leaves the old one), never half of one
+    Fleet f;
+    if (act) { rc = lpvmpc_act_alloc(h, B, act, delay_a, delay_df, dt_sim, veh ? "lpvmpc_cl_init_vehicles" : "lpvmpc_cl_init_actuated", f.cl_act); if (rc) return rc; }
+    release<Fleet>(*h);                                          // the old fleet first: never two at once
+    release<ObsState>(*h);
+    if (veh) { rc = lpvmpc_plant_upload(h, B, *veh, dt_sim, n_sub, f.cl_veh); if (rc) return rc; }
+    f.cl_actuated = act != nullptr;
+    HIP_TRY(h, f.cl_mem.alloc(f.cl_local_next, (size_t)B * 6 * 8));
+    HIP_TRY(h, f.cl_mem.alloc(f.cl_plant, (size_t)B * 8 * 8));
+    HIP_TRY(h, f.cl_mem.alloc(f.cl_local, (size_t)B * 6 * 8));
+    HIP_TRY(h, f.cl_mem.alloc(f.cl_cmd, (size_t)B * 2 * 8));
     hipStream_t st = h->stream;
-    H2D(h->cl_plant, plant0, (size_t)B * 8 * 8);
-    HIP_TRY(h, hipMemsetAsync(h->cl_cmd, 0, (size_t)B * 2 * 8, st));
+    H2D(f.cl_plant, plant0, (size_t)B * 8 * 8);
+    HIP_TRY(h, hipMemsetAsync(f.cl_cmd, 0, (size_t)B * 2 * 8, st));
     std::vector<double> ones((size_t)B * (h->cfg.N + 1), 1.0);                  // vel_ref = 1 m/s on lap 0 (CMAIN:311,326)
     H2D(h->d_vel, ones.data(), ones.size() * 8);
+    // the controller's OldSteering / OldAccelera start at zero (CTRL:71-73)
+    if (act) HIP_TRY(h, hipMemsetAsync(h->d_uold, 0, (size_t)B * (2 + h->cfg.steering_delay) * 8, st));
     HIP_TRY(h, hipStreamSynchronize(st));
-    h->cl_B = B; h->cl_first_it = 1; h->cl_q9 = q9_swap != 0; h->cl_ticks = 0; h->cl_hw = half_width; h->cl_slack = slack;
-    h->cl_pc = lpvmpc_plant_cfg(h, n_sub, dt_sim, mu_sim);
+    f.cl_B = B; f.cl_q9 = q9_swap != 0; f.cl_hw = half_width; f.cl_slack = slack;
+    f.cl_pc = lpvmpc_plant_cfg(h, n_sub, dt_sim, mu_sim);
     h->state_valid_B = 0;
-    if (h->obs_state) { (void)hipFree(h->obs_state); h->obs_state = nullptr; }
     if (h->obs_cfg) { rc = lpvmpc_observer_start(h, *h->obs_cfg, B, plant0, dt_sim, 0); if (rc) return rc; }   // the estimator in the loop
-    if (act) {                                                   // the controller's OldSteering / OldAccelera start at zero (CTRL:71-73)
-        HIP_TRY(h, hipMemsetAsync(h->d_uold, 0, (size_t)B * (2 + h->cfg.steering_delay) * 8, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-    }
+    static_cast<Fleet &>(*h) = std::move(f);
     return LPVMPC_OK;
 }
 
@@ -858,23 +796,22 @@ extern "C" int lpvmpc_cl_tick(lpvmpc_handle *h, int32_t n_ticks) {
             x0 = h->d_states; x0_stride = N * 6;
         }
         SolveArgs a{B, x0, h->d_AB, h->d_vel, h->d_uold, nullptr, h->d_xPred, h->d_uPred, h->d_status, h->d_iters, h->d_polish, h->d_resid,
-                    h->warm_mode ? h->d_state : nullptr, (h->warm_mode && h->state_valid_B == B) ? h->warm_mode : 0, x0_stride};
-        int rc = lpvmpc_launch_solve_timed(h, a, st); if (rc) return rc;
-        if (h->warm_mode) h->state_valid_B = B;
-        if (h->cl_veh.p && h->obs_state)
-            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_veh(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_veh, h->cl_hw, h->cl_slack,
+                    nullptr, 0, x0_stride};
+        int rc = lpvmpc_launch_solve_warm(h, a, st); if (rc) return rc;
+        if (h->cl_veh.d.p && h->obs_state)
+            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_veh(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_veh.d, h->cl_hw, h->cl_slack,
                                                                     h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay, h->obs_gains,
-                                                                    h->obs_state, h->obs_p, h->cl_act, st));
-        else if (h->cl_veh.p)
-            HIP_TRY(h, lpvmpc::launch_cl_command_plant_measure_veh(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_veh, h->cl_hw, h->cl_slack,
-                                                                    h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay, h->cl_act, st));
+                                                                    h->obs_state, h->obs_p, h->cl_act.d, st));
+        else if (h->cl_veh.d.p)
+            HIP_TRY(h, lpvmpc::launch_cl_command_plant_measure_veh(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_veh.d, h->cl_hw, h->cl_slack,
+                                                                    h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay, h->cl_act.d, st));
         else if (h->cl_actuated && h->obs_state)
             HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_act(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_pc, h->cl_hw, h->cl_slack,
                                                                     h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay, h->obs_gains,
-                                                                    h->obs_state, h->obs_p, h->cl_act, st));
+                                                                    h->obs_state, h->obs_p, h->cl_act.d, st));
         else if (h->cl_actuated)
             HIP_TRY(h, lpvmpc::launch_cl_command_plant_measure_act(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_pc, h->cl_hw, h->cl_slack,
-                                                                    h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay, h->cl_act, st));
+                                                                    h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay, h->cl_act.d, st));
         else if (h->obs_state)
             HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_pc, h->cl_hw, h->cl_slack,
                                                                 h->cl_q9, h->cl_local_next, h->d_uold, h->obs_gains, h->obs_state, h->obs_p, st));
@@ -932,26 +869,28 @@ int lpvmpc_observer_start(lpvmpc_handle *h, const lpvmpc_observer_config &o, int
         e[lpvmpc::OBS_GPS_X] = p[0]; e[lpvmpc::OBS_GPS_Y] = p[1];
     }
     hipStream_t st = h->stream;
-    if (h->obs_state) { HIP_TRY(h, hipStreamSynchronize(st)); (void)hipFree(h->obs_state); h->obs_state = nullptr; }
-    if (!h->obs_gains) HIP_TRY(h, hipMalloc((void **)&h->obs_gains, sizeof(double) * 2 * (lpvmpc::kObsTable + 12)));
-    HIP_TRY(h, hipMalloc((void **)&h->obs_state, os.size() * 8));
+    if (h->obs_state) { HIP_TRY(h, hipStreamSynchronize(st)); release<ObsState>(*h); }
+    ObsState s;
+    if (!h->obs_gains) HIP_TRY(h, h->gains_mem.alloc(h->obs_gains, sizeof(double) * 2 * (lpvmpc::kObsTable + 12)));
+    HIP_TRY(h, s.obs_mem.alloc(s.obs_state, os.size() * 8));
     H2D(h->obs_gains, o.L_ls, sizeof(double) * 2 * (lpvmpc::kObsTable + 12));
-    H2D(h->obs_state, os.data(), os.size() * 8);
-    lpvmpc::ObsParams &op = h->obs_p;
+    H2D(s.obs_state, os.data(), os.size() * 8);
+    lpvmpc::ObsParams &op = s.obs_p;
     op.dt = 1.0 / o.loop_rate; op.th_update = (1.0 / o.gps_freq) / dt_sim; op.n_bound = o.n_bound;
     op.std[0] = o.psi_std; op.std[1] = o.psiDot_std; op.std[2] = o.x_std; op.std[3] = o.y_std; op.std[4] = o.v_std;
     op.seed = o.seed; op.voff = o.vehicle_offset;
-    h->obs_B = B;
+    s.obs_B = B;
     HIP_TRY(h, hipStreamSynchronize(st));
+    static_cast<ObsState &>(*h) = std::move(s);
     return LPVMPC_OK;
 }
 
 extern "C" int lpvmpc_observer_setup(lpvmpc_handle *h, const lpvmpc_observer_config *cfg) {
     if (!h) return fail(nullptr, LPVMPC_E_ARG, "lpvmpc_observer_setup: handle is NULL");
     if (h->cfg.kind != LPVMPC_KIND_CONTROLLER) return fail(h, LPVMPC_E_ARG, "lpvmpc_observer_setup: controller handles only");
-    if (!cfg) { delete h->obs_cfg; h->obs_cfg = nullptr; return LPVMPC_OK; }
+    if (!cfg) { h->obs_cfg.reset(); return LPVMPC_OK; }
     int rc = lpvmpc_observer_check(h, cfg, "lpvmpc_observer_setup"); if (rc) return rc;
-    if (!h->obs_cfg) h->obs_cfg = new (std::nothrow) lpvmpc_observer_config();
+    if (!h->obs_cfg) h->obs_cfg.reset(new (std::nothrow) lpvmpc_observer_config());
     if (!h->obs_cfg) return fail(h, LPVMPC_E_NOMEM, "out of host memory");
     *h->obs_cfg = *cfg;
     return LPVMPC_OK;
@@ -980,7 +919,7 @@ extern "C" int lpvmpc_observer_step_batch(lpvmpc_handle *h, int32_t B, const lpv
     if (h && B == 0) return LPVMPC_OK;                                   // an empty batch is a no-op
     // the fleet / cascade rule of the batch calls; the solver workspace is not needed (this call stages its own buffers)
     if (!h) return fail(nullptr, LPVMPC_E_ARG, "lpvmpc_observer_step_batch: handle is NULL");
-    if (h->cl_plant || h->cascade || h->cascade_owner || h->race || h->race_owner)
+    if (busy(h))
         return fail(h, LPVMPC_E_ARG, "lpvmpc_observer_step_batch: this handle runs a fleet whose state lives in its workspace; use another handle "
                     "for batch calls (lpvmpc_cl_release ends the fleet)");
     if (B < 0) return fail(h, LPVMPC_E_ARG, "lpvmpc_observer_step_batch: B=%d", B);
@@ -990,11 +929,11 @@ extern "C" int lpvmpc_observer_step_batch(lpvmpc_handle *h, int32_t B, const lpv
     rc = lpvmpc_observer_check(h, cfg, "lpvmpc_observer_step_batch"); if (rc) return rc;
     const size_t per = (size_t)(6 + 5 + 2 + lpvmpc::kObsAux) * 8 + 8;
     if (B > h->obs_ws_cap) {
-        if (h->obs_ws) { (void)hipFree(h->obs_ws); h->obs_ws = nullptr; h->obs_ws_cap = 0; }
-        HIP_TRY(h, hipMalloc((void **)&h->obs_ws, per * B));
+        release<ObsStage>(*h);
+        HIP_TRY(h, h->stage_mem.alloc(h->obs_ws, per * B));
         h->obs_ws_cap = B;
     }
-    if (!h->obs_gains) HIP_TRY(h, hipMalloc((void **)&h->obs_gains, sizeof(double) * 2 * (lpvmpc::kObsTable + 12)));
+    if (!h->obs_gains) HIP_TRY(h, h->gains_mem.alloc(h->obs_gains, sizeof(double) * 2 * (lpvmpc::kObsTable + 12)));
     const size_t b = B;
     double *d_est = (double *)h->obs_ws, *d_y = d_est + b * 6, *d_u = d_y + b * 5, *d_aux = d_u + b * 2;
     int32_t *d_k = (int32_t *)(d_aux + b * lpvmpc::kObsAux);

@@ -14,15 +14,10 @@ int lpvmpc_model_check(lpvmpc_handle *h, int B, const char *who) {
     return LPVMPC_OK;
 }
 
-void lpvmpc_model_free(lpvmpc_handle *h) {
-    if (h->d_model) (void)hipFree(h->d_model);      // (waits for the launches that read it)
-    h->d_model = nullptr; h->model_B = 0;
-}
-
 extern "C" int lpvmpc_set_model_params(lpvmpc_handle *h, int32_t B, const double *model_params) {
     const char *who = "lpvmpc_set_model_params";
     if (!h) return fail(nullptr, LPVMPC_E_ARG, "%s: handle is NULL", who);
-    if (h->cl_plant || h->cascade || h->cascade_owner || h->race || h->race_owner)
+    if (busy(h))
         return fail(h, LPVMPC_E_ARG, "%s: this handle runs a %s; bind the model rows before it starts (lpvmpc_cl_release ends it)", who,
                     h->cl_plant ? "closed-loop fleet" : (h->race || h->race_owner) ? "race" : "planner + controller cascade");
     if (B < 0) return fail(h, LPVMPC_E_ARG, "%s: B=%d", who, B);
@@ -30,16 +25,14 @@ extern "C" int lpvmpc_set_model_params(lpvmpc_handle *h, int32_t B, const double
     std::vector<double> tab;                                             // [7][B], checked by the plant rows' rules
     if (B > 0) { int rc = lpvmpc_plant_rows(h, B, model_params, h->cfg, 0.0, who, tab); if (rc) return rc; }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    double *d = nullptr;
+    ModelTable m;                                                        // B = 0: none
     if (B > 0) {
-        HIP_TRY(h, hipMalloc((void **)&d, tab.size() * 8));
-        if (hipMemcpy(d, tab.data(), tab.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
+        HIP_TRY(h, m.model_mem.alloc(m.d_model, tab.size() * 8));
+        if (hipMemcpy(m.d_model, tab.data(), tab.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
             return fail(h, LPVMPC_E_HIP, "%s: uploading the rows failed", who);
-        }
+        m.model_B = B;
     }
-    lpvmpc_model_free(h);
-    h->d_model = d; h->model_B = B;
+    static_cast<ModelTable &>(*h) = std::move(m);                        // (freeing the old table waits for the launches that read it)
     return LPVMPC_OK;
 }
 

@@ -27,16 +27,11 @@ int lpvmpc_plant_rows(lpvmpc_handle *h, int B, const double *rows, const lpvmpc_
     return LPVMPC_OK;
 }
 
-void lpvmpc_plant_free(lpvmpc::VehPlantCfg &v) {
-    if (v.p) (void)hipFree(const_cast<double *>(v.p));
-    v = lpvmpc::VehPlantCfg{};
-}
-
-int lpvmpc_plant_upload(lpvmpc_handle *h, int B, const std::vector<double> &t, double dt_sim, int n_sub, lpvmpc::VehPlantCfg &v) {
-    v = lpvmpc::VehPlantCfg{};
+int lpvmpc_plant_upload(lpvmpc_handle *h, int B, const std::vector<double> &t, double dt_sim, int n_sub, PlantTable &v) {
+    v = {};
     double *d = nullptr;
-    HIP_TRY(h, hipMalloc((void **)&d, t.size() * 8));
-    v.p = d; v.B = B; v.dt = dt_sim; v.n_sub = n_sub;
+    HIP_TRY(h, v.mem.alloc(d, t.size() * 8));
+    v.d.p = d; v.d.B = B; v.d.dt = dt_sim; v.d.n_sub = n_sub;
     hipStream_t st = h->stream;
     H2D(d, t.data(), t.size() * 8);
     HIP_TRY(h, hipStreamSynchronize(st));
@@ -67,16 +62,16 @@ extern "C" int lpvmpc_plant_step_vehicles_batch(lpvmpc_handle *h, int32_t B, dou
                 for (size_t j = 0; j < R; ++j) ring[(c * R + j) * b + i] = o[c * R + j];
             sv[i] = o[2 * R]; k[i] = (int32_t)kk;
         }
-    lpvmpc::ActDev a{};
-    rc = lpvmpc_act_alloc(h, B, act, delay_a, delay_df, dt_sim, who, a);
-    if (rc) { lpvmpc_act_free(a); return rc; }
-    lpvmpc::VehPlantCfg v{};
+    ActState as;                                                    // (both freed when the call returns)
+    PlantTable v;
+    rc = lpvmpc_act_alloc(h, B, act, delay_a, delay_df, dt_sim, who, as); if (rc) return rc;
+    const lpvmpc::ActDev &a = as.d;
     rc = lpvmpc_plant_upload(h, B, tab, dt_sim, n_sub, v);
     hipStream_t st = h->stream;
     auto run = [&]() -> int {
         H2D(a.ring, ring.data(), ring.size() * 8); H2D(a.servo, sv.data(), b * 8); H2D(a.k, k.data(), b * 4);
         H2D(h->d_xlast, state, b * 8 * 8); H2D(h->d_states, u, b * 2 * 8);
-        HIP_TRY(h, lpvmpc::launch_plant_veh(B, h->d_xlast, h->d_states, v, a, st));
+        HIP_TRY(h, lpvmpc::launch_plant_veh(B, h->d_xlast, h->d_states, v.d, a, st));
         D2H(state, h->d_xlast, b * 8 * 8);
         if (act_state) return lpvmpc_act_download(h, a, act_state, st);   // (synchronises)
         HIP_TRY(h, hipStreamSynchronize(st));
@@ -84,8 +79,6 @@ extern "C" int lpvmpc_plant_step_vehicles_batch(lpvmpc_handle *h, int32_t B, dou
     };
     if (rc == LPVMPC_OK) rc = run();
     (void)hipStreamSynchronize(st);
-    lpvmpc_plant_free(v);
-    lpvmpc_act_free(a);
     return rc;
 }
 
@@ -94,7 +87,7 @@ extern "C" int lpvmpc_plant_params_read(lpvmpc_handle *h, double *plant_params) 
     const char *who = "lpvmpc_plant_params_read";
     const lpvmpc::VehPlantCfg *v = nullptr;
     if (h && h->race) v = lpvmpc_race_plant(h);
-    else if (h && h->cl_plant && h->cl_veh.p) v = &h->cl_veh;
+    else if (h && h->cl_plant && h->cl_veh.d.p) v = &h->cl_veh.d;
     if (!v || !v->p) return fail(h, LPVMPC_E_ARG, "%s: no fleet or race started by lpvmpc_cl_init_vehicles / lpvmpc_race_init_vehicles", who);
     if (!plant_params) return fail(h, LPVMPC_E_ARG, "%s: plant_params is NULL", who);
     HIP_TRY(h, hipSetDevice(h->cfg.device));

@@ -13,51 +13,32 @@
 #include "record.hpp"
 
 struct lpvmpc_race_recorder {
-    lpvmpc::RecDev d;             // kernel argument: race state pointers and the recorder's buffers
-    int capacity, stride, t_start, total;
+    lpvmpc::RecDev d{};           // kernel argument: race state pointers and the recorder's buffers
+    DevArena mem;                 // the recorder's buffers
+    int capacity = 0, stride = 0, t_start = 0, total = 0;
 };
 
 struct lpvmpc_race {
-    lpvmpc_handle *tt, *plan;
-    lpvmpc::RaceDev d;            // device pointers and constants (kernel argument)
-    int ticks;
-    lpvmpc::PlantCfg pc;
-    bool actuated;                // lpvmpc_race_init_actuated: delayed kernels, actuator state act, controller histories of steering delay sd
-    lpvmpc::ActDev act;
-    int sd;
-    lpvmpc::VehPlantCfg veh;      // lpvmpc_race_init_vehicles: the plant table (veh.p; null: one PlantCfg), with the delayed kernels' actuator
-    lpvmpc_race_recorder *rec;    // lpvmpc_race_record (null: not recording)
+    lpvmpc_handle *tt = nullptr, *plan = nullptr;
+    lpvmpc::RaceDev d{};          // device pointers and constants (kernel argument)
+    DevArena mem;                 // the race's own buffers of d (the p_ / t_ / q_ pointers are the three handles' workspaces)
+    int ticks = 0;
+    lpvmpc::PlantCfg pc{};
+    bool actuated = false;        // lpvmpc_race_init_actuated: delayed kernels, actuator state act, controller histories of steering delay sd
+    ActState act;
+    int sd = 0;
+    PlantTable veh;               // lpvmpc_race_init_vehicles: the plant table (veh.d.p; null: one PlantCfg), with the delayed kernels' actuator
+    std::unique_ptr<lpvmpc_race_recorder> rec;   // lpvmpc_race_record (null: not recording)
 };
-
-static void recorder_free(lpvmpc_race *r) {
-    lpvmpc_race_recorder *q = r->rec;
-    if (!q) return;
-    void *ptrs[] = {q->d.rec_f, q->d.rec_i, q->d.stat_f, q->d.stat_i, q->d.prev_phase, q->d.end_tick};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    delete q;
-    r->rec = nullptr;
-}
 
 void lpvmpc_race_free(lpvmpc_handle *h) {
     lpvmpc_race *r = h->race;
     if (!r) return;
     (void)hipSetDevice(h->cfg.device);
     (void)hipStreamSynchronize(h->stream);
-    lpvmpc::RaceDev &d = r->d;
-    void *ptrs[] = {d.plant, d.cmd, d.local, d.phase, d.lap, d.half, d.rk, d.plan_done, d.idx, d.nstep, d.src, d.step, d.lap_step,
-                    d.alive, d.iters, d.status, d.m_path, d.m_tt, d.m_plan, d.m_pfirst, d.m_pcont, d.SSc, d.ref0, d.refs, d.SSp,
-                    d.pose, d.sig, d.estv};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (d.estv) {                                                // the race's estimator
-        if (h->obs_state) (void)hipFree(h->obs_state);
-        if (h->obs_gains) (void)hipFree(h->obs_gains);
-        h->obs_state = h->obs_gains = nullptr; h->obs_B = 0; h->obs_p = lpvmpc::ObsParams{};
-    }
-    lpvmpc_act_free(r->act);
-    lpvmpc_plant_free(r->veh);
-    recorder_free(r);
-    if (r->tt && r->tt->race_owner == h) r->tt->race_owner = nullptr;
-    if (r->plan && r->plan->race_owner == h) r->plan->race_owner = nullptr;
+    if (r->d.estv) { release<ObsState>(*h); release<ObsGains>(*h); }   // the race's estimator
+    if (r->tt->race_owner == h) r->tt->race_owner = nullptr;
+    if (r->plan->race_owner == h) r->plan->race_owner = nullptr;
     delete r;
     h->race = nullptr;
 }
@@ -71,8 +52,6 @@ extern "C" void lpvmpc_race_default_config(lpvmpc_race_config *c) {
     c->q9_swap = 1;
     c->half_width = 0.3; c->slack = 0.15; c->plan_max_ey = 0.2; c->dt_sim = 0.005; c->mu_sim = 0.05;
 }
-
-static bool busy(const lpvmpc_handle *x) { return x->cl_plant || x->cascade || x->cascade_owner || x->race || x->race_owner; }
 
 static int race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, int32_t B, const double *plant0, const int32_t *half_track0,
                      const lpvmpc_race_config *cfg, const lpvmpc_observer_config *obs, bool observed_call,
@@ -111,23 +90,20 @@ static int race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, i
     rc = lpvmpc_model_check(h, B, "lpvmpc_race_init"); if (rc) return rc;
     rc = lpvmpc_model_check(tt, B, "lpvmpc_race_init(tt)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
     rc = lpvmpc_model_check(plan, B, "lpvmpc_race_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
-    lpvmpc::ActDev a{};
-    if (act) { rc = lpvmpc_act_alloc(h, B, act, delay_a, delay_df, cfg->dt_sim, veh ? "lpvmpc_race_init_vehicles" : "lpvmpc_race_init_actuated", a); if (rc) { lpvmpc_act_free(a); return rc; } }
-    lpvmpc::VehPlantCfg v{};
-    if (veh) { rc = lpvmpc_plant_upload(h, B, *veh, cfg->dt_sim, 1, v); if (rc) { lpvmpc_act_free(a); lpvmpc_plant_free(v); return rc; } }
-    lpvmpc_race *r = new (std::nothrow) lpvmpc_race();
-    if (!r) { lpvmpc_act_free(a); lpvmpc_plant_free(v); return fail(h, LPVMPC_E_NOMEM, "out of host memory"); }
-    std::memset(&r->d, 0, sizeof(r->d));
-    h->race = r; tt->race_owner = h; plan->race_owner = h;
-    r->tt = tt; r->plan = plan; r->ticks = 0;
-    r->actuated = act != nullptr; r->act = a; r->sd = h->cfg.steering_delay; r->veh = v;
+    // the race is built in r and installed in the three handles after the last step that can fail: a failed call leaves them idle
+    std::unique_ptr<lpvmpc_race> r(new (std::nothrow) lpvmpc_race());
+    if (!r) return fail(h, LPVMPC_E_NOMEM, "out of host memory");
+    if (act) { rc = lpvmpc_act_alloc(h, B, act, delay_a, delay_df, cfg->dt_sim, veh ? "lpvmpc_race_init_vehicles" : "lpvmpc_race_init_actuated", r->act); if (rc) return rc; }
+    if (veh) { rc = lpvmpc_plant_upload(h, B, *veh, cfg->dt_sim, 1, r->veh); if (rc) return rc; }
+    r->tt = tt; r->plan = plan;
+    r->actuated = act != nullptr; r->sd = h->cfg.steering_delay;
     r->pc = lpvmpc_plant_cfg(h, 1, cfg->dt_sim, cfg->mu_sim);
     lpvmpc::RaceDev &d = r->d;
     const size_t b = B, N = h->cfg.N, Np = plan->cfg.N, M = plan->ho_M;
     d.B = B; d.N = (int)N; d.Np = (int)Np; d.M = (int)M; d.laps = cfg->laps; d.q9 = cfg->q9_swap != 0; d.n_sub_lap0 = cfg->n_sub_lap0;
     for (int i = 0; i < 3; ++i) d.n_sub[i] = cfg->n_sub[i];
     d.lap_cols = cfg->laps + 2; d.hw = cfg->half_width; d.slack = cfg->slack;
-#define ALLOC(p, n) HIP_TRY(h, hipMalloc((void **)&(p), (n)))
+#define ALLOC(p, n) HIP_TRY(h, r->mem.alloc(p, (n)))
     ALLOC(d.plant, b * 8 * 8); ALLOC(d.cmd, b * 2 * 8); ALLOC(d.local, b * 6 * 8);
     ALLOC(d.phase, b * 4); ALLOC(d.lap, b * 4); ALLOC(d.half, b * 4); ALLOC(d.rk, b * 4); ALLOC(d.plan_done, b * 4); ALLOC(d.idx, b * 4);
     ALLOC(d.nstep, b * 4); ALLOC(d.src, b * 4); ALLOC(d.step, b * 4); ALLOC(d.lap_step, b * d.lap_cols * 4); ALLOC(d.alive, b * 4);
@@ -173,11 +149,12 @@ static int race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, i
             const double *p = plant0 + i * 8;
             v[i * 8 + 0] = p[0]; v[i * 8 + 1] = p[1]; v[i * 8 + 2] = obs->init_vx; v[i * 8 + 6] = p[6];
         }
-        HIP_TRY(h, hipMalloc((void **)&d.estv, b * 8 * 8));
+        HIP_TRY(h, r->mem.alloc(d.estv, b * 8 * 8));
         H2D(d.estv, v.data(), b * 8 * 8);
-        rc = lpvmpc_observer_start(h, *obs, B, plant0, cfg->dt_sim, 0); if (rc) return rc;     // (synchronises)
         d.meas = d.estv;
+        rc = lpvmpc_observer_start(h, *obs, B, plant0, cfg->dt_sim, 0); if (rc) return rc;     // (synchronises)
     }
+    h->race = r.release(); tt->race_owner = h; plan->race_owner = h;
     return LPVMPC_OK;
 }
 
@@ -208,7 +185,7 @@ extern "C" int lpvmpc_race_init_vehicles(lpvmpc_handle *h, lpvmpc_handle *tt, lp
     return race_init(h, tt, plan, B, plant0, half_track0, cfg, obs, true, act, delay_a, delay_df, &tab);
 }
 
-const lpvmpc::VehPlantCfg *lpvmpc_race_plant(const lpvmpc_handle *h) { return h->race ? &h->race->veh : nullptr; }
+const lpvmpc::VehPlantCfg *lpvmpc_race_plant(const lpvmpc_handle *h) { return h->race ? &h->race->veh.d : nullptr; }
 
 // the race's actuator state and its two controllers' histories (lpvmpc_actuator_read)
 int lpvmpc_race_act_read(lpvmpc_handle *h, double *act_state, double *path_hist, double *tt_hist) {
@@ -219,7 +196,7 @@ int lpvmpc_race_act_read(lpvmpc_handle *h, double *act_state, double *path_hist,
     const size_t n = (size_t)r->d.B * (2 + r->sd) * 8;
     if (path_hist) D2H(path_hist, r->d.p_uold, n);
     if (tt_hist) D2H(tt_hist, r->d.t_uold, n);
-    if (act_state) { int rc = lpvmpc_act_download(h, r->act, act_state, st); if (rc) return rc; }
+    if (act_state) { int rc = lpvmpc_act_download(h, r->act.d, act_state, st); if (rc) return rc; }
     HIP_TRY(h, hipStreamSynchronize(st));
     return LPVMPC_OK;
 }
@@ -273,13 +250,13 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
                      tt->d_resid, nullptr, 0, 6};
         ta.active = d.m_tt;
         rc = lpvmpc_launch_solve_timed(tt, ta, st); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
-        if (r->veh.p && d.estv) HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_veh(d, r->veh, h->obs_gains, h->obs_state, h->obs_p, r->act, st));
-        else if (r->veh.p) HIP_TRY(h, lpvmpc::launch_race_command_plant_veh(d, r->veh, r->act, st));
-        else if (r->actuated && d.estv) HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_act(d, r->pc, h->obs_gains, h->obs_state, h->obs_p, r->act, st));
-        else if (r->actuated) HIP_TRY(h, lpvmpc::launch_race_command_plant_act(d, r->pc, r->act, st));
+        if (r->veh.d.p && d.estv) HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_veh(d, r->veh.d, h->obs_gains, h->obs_state, h->obs_p, r->act.d, st));
+        else if (r->veh.d.p) HIP_TRY(h, lpvmpc::launch_race_command_plant_veh(d, r->veh.d, r->act.d, st));
+        else if (r->actuated && d.estv) HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_act(d, r->pc, h->obs_gains, h->obs_state, h->obs_p, r->act.d, st));
+        else if (r->actuated) HIP_TRY(h, lpvmpc::launch_race_command_plant_act(d, r->pc, r->act.d, st));
         else if (d.estv) HIP_TRY(h, lpvmpc::launch_race_command_plant_observe(d, r->pc, h->obs_gains, h->obs_state, h->obs_p, st));
         else HIP_TRY(h, lpvmpc::launch_race_command_plant(d, r->pc, st));
-        if (lpvmpc_race_recorder *q = r->rec) {                               // the recorder (record.hip)
+        if (lpvmpc_race_recorder *q = r->rec.get()) {                               // the recorder (record.hip)
             int slot = -1;
             if ((r->ticks - q->t_start) % q->stride == 0) { slot = q->total % q->capacity; q->total++; }
             HIP_TRY(h, lpvmpc::launch_race_record(h->d_cfg, q->d, r->ticks, slot, st));
@@ -352,44 +329,38 @@ extern "C" int lpvmpc_race_record(lpvmpc_handle *h, const lpvmpc_race_record_con
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t st = h->stream;
     HIP_TRY(h, hipStreamSynchronize(st));                                       // no tick in flight reads the old recorder
-    recorder_free(r);
+    r->rec.reset();                                                             // the old recorder first: a ring may fill the card
     if (cap == 0) return LPVMPC_OK;
-    lpvmpc_race_recorder *q = new (std::nothrow) lpvmpc_race_recorder();
+    std::unique_ptr<lpvmpc_race_recorder> q(new (std::nothrow) lpvmpc_race_recorder());   // installed once it is complete
     if (!q) return fail(h, LPVMPC_E_NOMEM, "out of host memory");
-    r->rec = q;
     lpvmpc::RecDev &e = q->d;
-    struct { void **p; size_t n; } bufs[] = {{(void **)&e.rec_f, nf}, {(void **)&e.rec_i, ni}, {(void **)&e.stat_f, sf},
-                                             {(void **)&e.stat_i, si}, {(void **)&e.prev_phase, B * 4}, {(void **)&e.end_tick, B * 4}};
-    for (auto &x : bufs) {
-        const hipError_t err = hipMalloc(x.p, x.n);
-        if (err != hipSuccess) {
-            (void)hipGetLastError();                                            // leave no error pending for the race's launches
-            recorder_free(r);
-            return fail(h, LPVMPC_E_NOMEM, "lpvmpc_race_record: hipMalloc of %zu B failed: %s", x.n, hipGetErrorString(err));
-        }
-    }
+    hipError_t err = hipSuccess;
+    size_t want = 0;
+    auto take = [&](auto *&p, size_t n) { if (err == hipSuccess) { want = n; err = q->mem.alloc(p, n); } };
+    take(e.rec_f, nf); take(e.rec_i, ni); take(e.stat_f, sf); take(e.stat_i, si); take(e.prev_phase, B * 4); take(e.end_tick, B * 4);
+    if (err != hipSuccess) return fail(h, LPVMPC_E_NOMEM, "lpvmpc_race_record: hipMalloc of %zu B failed: %s", want, hipGetErrorString(err));
     e.B = d.B; e.N = d.N; e.laps = d.laps; e.q9 = d.q9; e.hw = d.hw; e.slack = d.slack;
     e.plant = d.plant; e.local = d.local; e.cmd = d.cmd; e.ref0 = d.ref0; e.t_vel = d.t_vel;
     e.obs = d.estv ? h->obs_state : nullptr;
     e.phase = d.phase; e.lap = d.lap; e.rk = d.rk; e.src = d.src; e.iters = d.iters; e.status = d.status; e.m_plan = d.m_plan;
     e.q_iters = r->plan->d_iters; e.q_status = r->plan->d_status;
     q->capacity = cfg->capacity; q->stride = cfg->stride; q->t_start = r->ticks; q->total = 0;
-    hipError_t err = hipMemsetAsync(e.stat_f, 0, sf, st);
+    err = hipMemsetAsync(e.stat_f, 0, sf, st);
     if (err == hipSuccess) err = hipMemsetAsync(e.stat_i, 0, si, st);
     if (err == hipSuccess) err = hipMemsetAsync(e.end_tick, 0xff, B * 4, st);
     if (err == hipSuccess) err = hipMemcpyAsync(e.prev_phase, d.phase, B * 4, hipMemcpyDeviceToDevice, st);
     if (err != hipSuccess) {                                                    // no recorder with statistics that were never zeroed
         (void)hipStreamSynchronize(st);
-        recorder_free(r);
         return fail(h, LPVMPC_E_HIP, "lpvmpc_race_record: resetting the recorder failed: %s", hipGetErrorString(err));
     }
+    r->rec = std::move(q);
     return LPVMPC_OK;
 }
 
 extern "C" int lpvmpc_race_record_read(lpvmpc_handle *h, int32_t n, int32_t *total, int32_t *tick, double *f64, int32_t *i32) {
     if (!h || !h->race) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_record_read: call lpvmpc_race_init first");
     if (n < 0) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_record_read: n < 0");
-    const lpvmpc_race_recorder *q = h->race->rec;
+    const lpvmpc_race_recorder *q = h->race->rec.get();
     if (!q) { if (total) total[0] = 0; return LPVMPC_OK; }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t st = h->stream;
@@ -410,7 +381,7 @@ extern "C" int lpvmpc_race_record_read(lpvmpc_handle *h, int32_t n, int32_t *tot
 
 extern "C" int lpvmpc_race_lap_stats(lpvmpc_handle *h, double *f64, int32_t *i32, int32_t *end_tick) {
     if (!h || !h->race) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_lap_stats: call lpvmpc_race_init first");
-    const lpvmpc_race_recorder *q = h->race->rec;
+    const lpvmpc_race_recorder *q = h->race->rec.get();
     if (!q) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_lap_stats: recording is off (lpvmpc_race_record)");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t st = h->stream;

@@ -317,3 +317,62 @@ def test_race_refusals():
     refused(path.race_tick, 1)
     for e in (path, tt, bare, short, other_dt, long_, long_tt, delayed):
         e.close()
+
+
+def same_words(a, b, what=""):
+    """Word for word, where a NaN matches a NaN (its payload is not specified)."""
+    a, b = np.asarray(a), np.asarray(b)
+    assert a.shape == b.shape and a.dtype == b.dtype, (what, a.shape, b.shape)
+    if a.dtype.kind == "f":
+        na, nb = np.isnan(a), np.isnan(b)
+        diff = (na != nb) | (~na & (a.view(np.int64) != b.view(np.int64)))
+    else:
+        diff = a != b
+    assert not diff.any(), "%s: %d words differ" % (what, int(diff.sum()))
+
+
+def test_failed_race_init_leaves_the_three_handles_idle():
+    """A race_init whose lap_step table ([256][laps + 2] int32 with laps = 2e9: ~2 TB) hipMalloc refuses, after the smaller buffers
+    before it were allocated: the call fails, none of the three engines is left in a race, no HIP error stays pending, and a second
+    race on the same engines equals one on fresh engines.  (No tick between the failed call and the second init: harmless on any build.)
+    No vehicle reaches its planner in 12 ticks, and race_read's plan_iters / plan_status of a vehicle that never planned are what the
+    planner's workspace held (docs/HISTORY.md, "Race recorder"): each planner first solves one 256-instance batch, so that every
+    word compared is defined."""
+    import lpvmpc
+    from lpvmpc import _ffi, workloads as W
+    mp = lshape()
+    B = 256
+    plant0 = start_line_fleet(mp, B, 11)
+    kw = dict(half_track0=1, half_width=mp.halfWidth, slack=mp.slack)
+    pw = W.planner_batch(B, N=40, seed=7)
+    path, tt, plan = engines(mp)
+    fresh = engines(mp)
+    for q in (plan, fresh[2]):
+        q.solve(pw["x0"], pw["u_prev"], None, pw["curv_s"], pw["u_old"], pw["max_ey"])
+    with pytest.raises(lpvmpc.LpvMpcError):                                          # (a)
+        path.race_init(tt, plan, plant0, laps=2_000_000_000, **kw)
+
+    def run(p, t, q, first_tick):
+        p.race_init(t, q, plant0, laps=1, **kw)                                      # (b): accepted on the same three engines
+        first_tick(p)
+        p.race_tick(11)                                                              # 9 seed ticks + 3 on the LPV branch
+        ls, al = p.race_laps()
+        pu, tu = p.race_predictions()
+        out = dict(p.race_read(), lap_step=ls, alive=al, path_uPred=pu, tt_uPred=tu)
+        p.cl_release()
+        sol = q.solve(pw["x0"], pw["u_prev"], None, pw["curv_s"], pw["u_old"], pw["max_ey"])   # (c): the planner is free again
+        return out, sol
+
+    def checked_tick(p):                                                             # (d): the first launches after the failed call
+        lib = _ffi.load()
+        assert lib.lpvmpc_race_tick(p._h, 1) == 0, lib.lpvmpc_last_error(p._h).decode()
+
+    a, sa = run(path, tt, plan, checked_tick)
+    b, sb = run(*fresh, lambda p: p.race_tick(1))
+    assert a["ticks"] == b["ticks"] == 12
+    for k in a:
+        same_words(a[k], b[k], k)
+    for k in sa:
+        same_words(sa[k], sb[k], "planner solve " + k)
+    for e in (path, tt, plan) + tuple(fresh):
+        e.close()
