@@ -122,6 +122,7 @@ ACT_WORDS = 2 * ACT_MAX_DELAY + 2        # LPVMPC_ACT_WORDS: [motor ring, servo 
 PLANT_WORDS = 7                          # LPVMPC_PLANT_WORDS: [lf, lr, m, Iz, Cf, Cr, mu] per vehicle
 PLANT_WORD_NAMES = ("lf", "lr", "m", "Iz", "Cf", "Cr", "mu")
 MODEL_WORDS = 7                          # LPVMPC_MODEL_WORDS: the same words, as a controller's / planner's model of the vehicle
+TUNING_WORDS = 64                        # LPVMPC_TUNING_WORDS: Q[36] R[4] dR[2] L_cf[6] limits[16] per instance (tuning.py)
 
 OBSERVER_AUX = 30 + 36 + 12      # L_gain [6][5], A_obs [6][6], B_obs [6][2] per instance (lpvmpc_observer_step_batch)
 
@@ -139,7 +140,8 @@ EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_d
            "lpvmpc_actuator_default_config", "lpvmpc_plant_step_actuated_batch", "lpvmpc_cl_init_actuated", "lpvmpc_race_init_actuated",
            "lpvmpc_actuator_read", "lpvmpc_race_record", "lpvmpc_race_record_read", "lpvmpc_race_lap_stats",
            "lpvmpc_plant_step_vehicles_batch", "lpvmpc_cl_init_vehicles", "lpvmpc_race_init_vehicles", "lpvmpc_plant_params_read",
-           "lpvmpc_set_model_params", "lpvmpc_model_params_read")
+           "lpvmpc_set_model_params", "lpvmpc_model_params_read",
+           "lpvmpc_set_tunings", "lpvmpc_tunings_read", "lpvmpc_tuning_from_config", "lpvmpc_tuning_device_row")
 
 _lib = None
 
@@ -276,6 +278,15 @@ def load():
         lib.lpvmpc_set_model_params.argtypes = [vp, _i, vp]
         lib.lpvmpc_model_params_read.argtypes = [vp, P(_i), vp]
         for name in ("lpvmpc_set_model_params", "lpvmpc_model_params_read"):
+            getattr(lib, name).restype = C.c_int
+    except AttributeError:
+        pass
+    try:        # (nor the per-vehicle tunings)
+        lib.lpvmpc_set_tunings.argtypes = [vp, _i, vp]
+        lib.lpvmpc_tunings_read.argtypes = [vp, P(_i), vp]
+        lib.lpvmpc_tuning_from_config.argtypes = [P(Config), vp]
+        lib.lpvmpc_tuning_device_row.argtypes = [_i, vp, vp]
+        for name in ("lpvmpc_set_tunings", "lpvmpc_tunings_read", "lpvmpc_tuning_from_config", "lpvmpc_tuning_device_row"):
             getattr(lib, name).restype = C.c_int
     except AttributeError:
         pass

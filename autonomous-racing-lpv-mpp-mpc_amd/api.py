@@ -41,6 +41,57 @@ def _vehicle_params(params, need_min_vel):
     return out
 
 
+def build_config(kind, N, dt, Q, R, dR, L_cf=None, track=None, params=None, device=0, **settings):
+    """The lpvmpc_config of BatchedSolver(kind, N, dt, Q, R, dR, ...) -- same arguments -- without creating a handle (host only)."""
+    kind = {"controller": KIND_CONTROLLER, "planner": KIND_PLANNER}.get(kind, kind)
+    if kind not in (KIND_CONTROLLER, KIND_PLANNER):
+        raise ValueError("kind must be 'controller' or 'planner'")
+    nx = 6 if kind == KIND_CONTROLLER else 5
+    cfg = _ffi.default_config(kind)
+    cfg.N = int(N)
+    cfg.device = int(device)
+    cfg.dt = float(dt)
+    p = dict(DEFAULT_PARAMS)
+    if params:
+        p.update(params)
+    for k in ("lf", "lr", "m", "Iz", "Cf", "Cr", "mu", "max_vel", "min_vel"):
+        setattr(cfg, k, float(p[k]))
+    Q = f64(Q, (nx, nx), "Q")
+    R = f64(R, (2, 2), "R")
+    dR = f64(dR, (2,), "dR")
+    for i in range(36):
+        cfg.Q[i] = 0.0
+    for i, v in enumerate(Q.reshape(-1)):
+        cfg.Q[i] = v
+    for i, v in enumerate(R.reshape(-1)):
+        cfg.R[i] = v
+    cfg.dR[0], cfg.dR[1] = dR
+    for i in range(6):
+        cfg.L_cf[i] = 0.0
+    if kind == KIND_PLANNER:
+        if L_cf is None:
+            raise ValueError("the planner needs L_cf")
+        for i, v in enumerate(f64(L_cf, (5,), "L_cf")):
+            cfg.L_cf[i] = v
+    for k, v in settings.items():
+        if k not in _ffi.SETTING_FIELDS:
+            raise TypeError("unknown setting %r" % k)
+        if k.startswith("plan_"):
+            arr = getattr(cfg, k)
+            for i, x in enumerate(f64(v, (len(arr),), k)):
+                arr[i] = x
+        else:
+            setattr(cfg, k, v)
+    if track is not None:
+        tab = f64(track, name="track")
+        if tab.ndim != 2 or tab.shape[1] != 6 or tab.shape[0] > _ffi.MAX_TRACK_ROWS:
+            raise ValueError("track table must be (rows<=%d, 6)" % _ffi.MAX_TRACK_ROWS)
+        cfg.track_rows = tab.shape[0]
+        for i, v in enumerate(tab.reshape(-1)):
+            cfg.track[i] = v
+    return cfg
+
+
 class BatchedSolver:
     """Batched LPV-MPC (``kind="controller"``) / LPV-MPP (``kind="planner"``) solver on one MI355X.
 
@@ -51,55 +102,12 @@ class BatchedSolver:
     min_vel / max_vel and max_ey)."""
 
     def __init__(self, kind, N, dt, Q, R, dR, L_cf=None, track=None, params=None, device=0, **settings):
-        self.kind = {"controller": KIND_CONTROLLER, "planner": KIND_PLANNER}.get(kind, kind)
-        if self.kind not in (KIND_CONTROLLER, KIND_PLANNER):
-            raise ValueError("kind must be 'controller' or 'planner'")
+        cfg = build_config(kind, N, dt, Q, R, dR, L_cf=L_cf, track=track, params=params, device=device, **settings)
+        self.kind = cfg.kind
         self.nx = 6 if self.kind == KIND_CONTROLLER else 5
         self.nu = 2
         self.N = int(N)
         lib = _ffi.load()
-        cfg = _ffi.default_config(self.kind)
-        cfg.N = self.N
-        cfg.device = int(device)
-        cfg.dt = float(dt)
-        p = dict(DEFAULT_PARAMS)
-        if params:
-            p.update(params)
-        for k in ("lf", "lr", "m", "Iz", "Cf", "Cr", "mu", "max_vel", "min_vel"):
-            setattr(cfg, k, float(p[k]))
-        Q = f64(Q, (self.nx, self.nx), "Q")
-        R = f64(R, (2, 2), "R")
-        dR = f64(dR, (2,), "dR")
-        for i in range(36):
-            cfg.Q[i] = 0.0
-        for i, v in enumerate(Q.reshape(-1)):
-            cfg.Q[i] = v
-        for i, v in enumerate(R.reshape(-1)):
-            cfg.R[i] = v
-        cfg.dR[0], cfg.dR[1] = dR
-        for i in range(6):
-            cfg.L_cf[i] = 0.0
-        if self.kind == KIND_PLANNER:
-            if L_cf is None:
-                raise ValueError("the planner needs L_cf")
-            for i, v in enumerate(f64(L_cf, (5,), "L_cf")):
-                cfg.L_cf[i] = v
-        for k, v in settings.items():
-            if k not in _ffi.SETTING_FIELDS:
-                raise TypeError("unknown setting %r" % k)
-            if k.startswith("plan_"):
-                arr = getattr(cfg, k)
-                for i, x in enumerate(f64(v, (len(arr),), k)):
-                    arr[i] = x
-            else:
-                setattr(cfg, k, v)
-        if track is not None:
-            tab = f64(track, name="track")
-            if tab.ndim != 2 or tab.shape[1] != 6 or tab.shape[0] > _ffi.MAX_TRACK_ROWS:
-                raise ValueError("track table must be (rows<=%d, 6)" % _ffi.MAX_TRACK_ROWS)
-            cfg.track_rows = tab.shape[0]
-            for i, v in enumerate(tab.reshape(-1)):
-                cfg.track[i] = v
         self.cfg = cfg
         self._lib = lib
         self._h = lib.lpvmpc_create(C.byref(cfg))
@@ -333,6 +341,31 @@ class BatchedSolver:
             return None
         out = np.empty((B.value, _ffi.MODEL_WORDS))
         self._chk(self._lib.lpvmpc_model_params_read(self._h, C.byref(B), ptr(out)))
+        return out
+
+    def set_tunings(self, rows):
+        """Bind per-instance tuning rows [B, 64] (tuning.py: Q, R, dR, L_cf and the limits) to this engine (lpvmpc_set_tunings): every
+        call that solves -- solve, solve_AB, solve_batch_masked, solve_dev, and a fleet, cascade or race started afterwards -- then
+        builds instance b's QP with row b instead of the engine's own tuning and must have batch size B.  ``None`` unbinds.  Refused
+        while the engine runs a fleet, cascade or race."""
+        if rows is None:
+            self._chk(self._lib.lpvmpc_set_tunings(self._h, 0, None))
+            return
+        a = np.asarray(rows)
+        if a.ndim != 2 or a.shape[0] < 1:
+            raise ValueError("tunings has shape %s, expected (B, %d) with B >= 1" % (a.shape, _ffi.TUNING_WORDS))
+        from .tuning import check_tuning_rows
+        a = check_tuning_rows(a, a.shape[0], self.kind)
+        self._chk(self._lib.lpvmpc_set_tunings(self._h, a.shape[0], ptr(a)))
+
+    def tunings_read(self):
+        """The bound tuning rows [B, 64] as they were set (lpvmpc_tunings_read), or None while nothing is bound."""
+        B = C.c_int32(0)
+        self._chk(self._lib.lpvmpc_tunings_read(self._h, C.byref(B), None))
+        if B.value == 0:
+            return None
+        out = np.empty((B.value, _ffi.TUNING_WORDS))
+        self._chk(self._lib.lpvmpc_tunings_read(self._h, C.byref(B), ptr(out)))
         return out
 
     def cl_init(self, plant0, half_width, slack, q9_swap=True, n_sub=7, dt_sim=0.005, mu_sim=0.05, actuator=None, delay_a=None,
@@ -977,10 +1010,12 @@ class RaceFleet(object):
     plant (plant.sample_plant_params for a mismatch sweep); the controllers and the planner keep the nominal model unless
     ``model_params`` is given: [B, 7] rows bound to the path, tt and planner engines (BatchedSolver.set_model_params), or the string
     "plant": each vehicle's model is its plant row (the matched experiment; the nominal plant rows where plant_params is None or
-    "nominal")."""
+    "nominal").  ``path_tunings`` / ``tt_tunings`` / ``plan_tunings``: [B, 64] tuning rows (tuning.tuning_rows, tuning.sample_tunings)
+    bound to the path, tt and planner engine (BatchedSolver.set_tunings): vehicle b races with its own weights and limits."""
 
     def __init__(self, track_map, plant0, laps=1, N=20, Np=40, half_track0=None, device=0, estimator=None, actuator=None,
-                 steering_delay=0, delay_a=None, delay_df=None, plant_params=None, model_params=None, **options):
+                 steering_delay=0, delay_a=None, delay_df=None, plant_params=None, model_params=None, path_tunings=None,
+                 tt_tunings=None, plan_tunings=None, **options):
         from .workloads import CTRL_TUNINGS, PLAN_L, PLAN_Q, PLAN_R, PLAN_dR
         race_keys = ("n_sub_lap0", "n_sub", "q9_swap", "plan_max_ey", "dt_sim", "mu_sim")
         race_opts = {k: v for k, v in options.items() if k in race_keys}
@@ -1010,6 +1045,10 @@ class RaceFleet(object):
                 rows = check_model_params(model_params, B)
             for e in (self.path, self.tt, self.planner):
                 e.set_model_params(rows)
+        for e, rows in ((self.path, path_tunings), (self.tt, tt_tunings), (self.planner, plan_tunings)):
+            if rows is not None:
+                from .tuning import check_tuning_rows
+                e.set_tunings(check_tuning_rows(rows, f64(plant0).reshape(-1, 8).shape[0], e.kind))
         self.path.race_init(self.tt, self.planner, plant0, half_track0=half_track0, laps=laps, half_width=track_map.halfWidth,
                             slack=track_map.slack, estimator=estimator, actuator=actuator, delay_a=delay_a, delay_df=delay_df,
                             plant_params=plant_params, **race_opts)
@@ -1037,6 +1076,10 @@ class RaceFleet(object):
     def model_params(self):
         """The model rows [B, 7] bound to the race's three engines by ``model_params`` (read from the path engine), or None."""
         return self.path.model_params_read()
+
+    def tunings(self):
+        """The tuning rows bound to the (path, tt, planner) engines, each [B, 64] or None."""
+        return self.path.tunings_read(), self.tt.tunings_read(), self.planner.tunings_read()
 
     def lap_times(self):
         """[B, laps+1] simulated seconds of lap 0, 1, ..., laps (NaN where the lap has not been completed)."""

@@ -285,7 +285,8 @@ struct Solver {
         mS = tT = 0.0;
         set_fac_ids(lane);
     }
-    // the part of the LDS block that a pool entry carries (try_park / restore): everything up to and including SINK
+    // the part of the LDS block that a pool entry carries (try_park / restore): everything up to and including SINK.  It holds every
+    // copy of the instance's tuning words (Pm, dRl, Qv, Lo, Hi): resume, riders and tail launches read nothing from SolveArgs::tune
     static constexpr __host__ __device__ size_t image_doubles(int N) {
         return (size_t)(N + 1) * ((kFixN ? 1 : 3) * kTS + (GS ? 16 : 19) * 8 + 8) + 16 + 64 + 8 + kRedSize + 64;
     }
@@ -3245,15 +3246,20 @@ struct Solver {
             ++iter0;
         } else if constexpr (!TAIL) {
         // ---------- load + build the unscaled problem ----------
+        // the tuning words (Q R dR Lcf box_lo box_hi: kTuneWords contiguous doubles): the instance's row of the handle's table
+        // (lpvmpc_set_tunings), or the configuration block's own.  Read here and nowhere else: everything below works on LDS copies
+        const double *const tw = a.tune ? a.tune + (size_t)inst * kTuneWords : cfg.Q;
+        const double *const twR = tw + kTuneR, *const twdR = tw + kTunedR, *const twLcf = tw + kTuneLcf, *const twLo = tw + kTuneLo,
+                     *const twHi = tw + kTuneHi;
         {   // weights -> LDS (the configuration block itself stays in global memory)
             double v = 0.0;
-            if (ti < NX && tj < NX) v = 2.0 * cfg.Q[ti * NX + tj];
+            if (ti < NX && tj < NX) v = 2.0 * tw[ti * NX + tj];
             else if (ti >= NX && tj >= NX && ti < NB && tj < NB) {
-                v = 2.0 * cfg.R[(ti - NX) * 2 + (tj - NX)];
-                if (ti == tj) v += 4.0 * cfg.dR[ti - NX];
+                v = 2.0 * twR[(ti - NX) * 2 + (tj - NX)];
+                if (ti == tj) v += 4.0 * twdR[ti - NX];
             }
             Pm[lane] = v;
-            if (tid < 8) dRl[tid] = tid < 2 ? cfg.dR[tid] : 0.0;
+            if (tid < 8) dRl[tid] = tid < 2 ? twdR[tid] : 0.0;
         }
         for (int e = tid; e < NS * kTS; e += kStride) { tA[e] = 0.0; }
         for (int e = tid; e < 64 + 8 * NS; e += kStride) SINK[e] = 0.0;        // the MFMA sweeps read their zeros here (nothing writes it in those kernels)
@@ -3312,15 +3318,15 @@ struct Solver {
 #pragma unroll
                         for (int i = 1; i < kVr; ++i) if (round_ == i) vr_ = vref[i];
                     } else vr_ = a.vel_ref[(size_t)inst * (N + 1) + k];
-                    q = -cfg.Q[0 * NX + r] * 2.0 * vr_;
+                    q = -tw[0 * NX + r] * 2.0 * vr_;
                 }
-                else q = cfg.Lcf[r];
-            } else if (r < NB && k == 0) q = -2.0 * (r == NX ? uo0 : uo1) * cfg.dR[r - NX];   // CTRL:462 / PLAN:167
+                else q = twLcf[r];
+            } else if (r < NB && k == 0) q = -2.0 * (r == NX ? uo0 : uo1) * twdR[r - NX];   // CTRL:462 / PLAN:167
             bad |= !__builtin_isfinite(q);
             Qv[e] = q;
             // box rows (CTRL:334-348 / PLAN:173-181); infinities clipped to +-1e30 like OSQP's front end
             if (r < nbox(k)) {
-                double lo = cfg.box_lo[r], hi = cfg.box_hi[r];
+                double lo = twLo[r], hi = twHi[r];
                 if (!kCtrl && r == 3) { lo = -mey; hi = mey; }
                 if (kCtrl && r == 6) { lo = hi = a.u_old ? a.u_old[(size_t)inst * (2 + delay) + 2 + k] : 0.0; bad |= !__builtin_isfinite(lo); }   // delta_k = OldSteering[k+1]
                 Lo[e] = fmax(lo, -kInfty); Hi[e] = fmin(hi, kInfty);

@@ -143,6 +143,8 @@ extern "C" int lpvmpc_cascade_init(lpvmpc_handle *h, lpvmpc_handle *plan, int32_
     rc = lpvmpc_check_common(plan, B, "lpvmpc_cascade_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
     rc = lpvmpc_model_check(h, B, "lpvmpc_cascade_init"); if (rc) return rc;
     rc = lpvmpc_model_check(plan, B, "lpvmpc_cascade_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
+    rc = lpvmpc_tuning_check(h, B, "lpvmpc_cascade_init"); if (rc) return rc;
+    rc = lpvmpc_tuning_check(plan, B, "lpvmpc_cascade_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
     lpvmpc_cascade_free(h);
     // the cascade is built in c and installed in the two handles after the last step that can fail: a failed call leaves none
     std::unique_ptr<lpvmpc_cascade> c(new (std::nothrow) lpvmpc_cascade());

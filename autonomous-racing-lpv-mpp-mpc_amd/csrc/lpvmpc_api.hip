@@ -168,17 +168,10 @@ extern "C" lpvmpc_handle *lpvmpc_create(const lpvmpc_config *cfg) {
     d.steering_delay = cfg->steering_delay;
     d.dt = cfg->dt; d.lf = cfg->lf; d.lr = cfg->lr; d.m = cfg->m; d.Iz = cfg->Iz; d.Cf = cfg->Cf; d.Cr = cfg->Cr; d.mu = cfg->mu;
     d.max_vel = cfg->max_vel; d.min_vel = cfg->min_vel;
-    std::memcpy(d.Q, cfg->Q, sizeof(d.Q)); std::memcpy(d.R, cfg->R, sizeof(d.R));
-    std::memcpy(d.dR, cfg->dR, sizeof(d.dR)); std::memcpy(d.Lcf, cfg->L_cf, sizeof(d.Lcf));
-    const double inf = INFINITY;
-    if (cfg->kind == LPVMPC_KIND_CONTROLLER) {
-        // rows: -vx <= -vx_min, vx <= max_vel, d <= dmax, -d <= dmax, a <= amax, -a <= amin   (CTRL:334-348)
-        const double hi[6] = {-cfg->ctrl_vx_min, cfg->max_vel, cfg->ctrl_delta_max, cfg->ctrl_delta_max, cfg->ctrl_a_max, cfg->ctrl_a_min_abs};
-        for (int r = 0; r < 6; ++r) { d.box_lo[r] = -inf; d.box_hi[r] = hi[r]; }
-    } else {
-        for (int r = 0; r < 5; ++r) { d.box_lo[r] = cfg->plan_xmin[r]; d.box_hi[r] = cfg->plan_xmax[r]; }
-        d.box_lo[0] = cfg->min_vel; d.box_hi[0] = cfg->max_vel;                 // PLAN:176-177
-        for (int r = 0; r < 2; ++r) { d.box_lo[5 + r] = cfg->plan_umin[r]; d.box_hi[5 + r] = cfg->plan_umax[r]; }
+    {   // the tuning words Q R dR Lcf box_lo box_hi: the device row of the configuration's own tuning (tunings_api.hip)
+        double row[LPVMPC_TUNING_WORDS];
+        lpvmpc_tuning_from_config(cfg, row);
+        lpvmpc_tuning_device_row(cfg->kind, row, d.Q);
     }
     d.rho = cfg->rho; d.sigma = cfg->sigma; d.alpha = cfg->alpha; d.eps_abs = cfg->eps_abs; d.eps_rel = cfg->eps_rel;
     d.eps_prim_inf = cfg->eps_prim_inf; d.eps_dual_inf = cfg->eps_dual_inf; d.delta = cfg->polish_delta;
@@ -304,6 +297,7 @@ int lpvmpc_launch_solve_timed(lpvmpc_handle *h, const SolveArgs &a, hipStream_t 
     SolveArgs b = a;
     if (h->d_scal && a.B <= h->cap) b.scal = h->d_scal;          // (the launcher ignores it for deferred / resumed launches)
     if (h->solve_mask && !a.resume) b.active = h->solve_mask;      // lpvmpc_solve_batch_masked (synchronous: its launch carries no riders)
+    { int rc = lpvmpc_solve_tune(h, b); if (rc) return rc; }       // the handle's tuning rows (every main launch of every route comes through here)
     HIP_TRY(h, lpvmpc::launch_solve(h->dev, h->d_cfg, b, st, h->force_generic));
     if (h->timing) { HIP_TRY(h, hipEventRecord(h->ev.e1[slot], st)); h->ev.count++; }
     return LPVMPC_OK;
@@ -459,6 +453,7 @@ extern "C" int lpvmpc_solve_batch_AB(lpvmpc_handle *h, int32_t B, const double *
                                      int32_t *polish) {
     if (h && B == 0) return LPVMPC_OK;                                   // an empty batch is a no-op
     int rc = lpvmpc_check_batch(h, B, "lpvmpc_solve_batch_AB"); if (rc) return rc;
+    rc = lpvmpc_tuning_check(h, B, "lpvmpc_solve_batch_AB"); if (rc) return rc;
     const bool ctrl = h->cfg.kind == LPVMPC_KIND_CONTROLLER;
     if (!x0 || !A || !Bm) return fail(h, LPVMPC_E_ARG, "lpvmpc_solve_batch_AB: x0 / A / B is NULL");
     if (ctrl && !vel_ref) return fail(h, LPVMPC_E_ARG, "lpvmpc_solve_batch_AB: controller needs vel_ref");
@@ -502,6 +497,7 @@ extern "C" int lpvmpc_solve_batch_dev(lpvmpc_handle *h, int32_t B, const double 
     if (h && B == 0) return LPVMPC_OK;                                   // an empty batch is a no-op
     int rc = lpvmpc_check_batch(h, B, "lpvmpc_solve_batch_dev"); if (rc) return rc;
     rc = lpvmpc_model_check(h, B, "lpvmpc_solve_batch_dev"); if (rc) return rc;
+    rc = lpvmpc_tuning_check(h, B, "lpvmpc_solve_batch_dev"); if (rc) return rc;
     const bool ctrl = h->cfg.kind == LPVMPC_KIND_CONTROLLER;
     if (!x0 || !u_prev || !xPred || !uPred) return fail(h, LPVMPC_E_ARG, "lpvmpc_solve_batch_dev: NULL x0 / u_prev / xPred / uPred");
     if (ctrl && !vel_ref) return fail(h, LPVMPC_E_ARG, "lpvmpc_solve_batch_dev: controller needs vel_ref");
@@ -580,6 +576,7 @@ extern "C" int lpvmpc_solve_batch(lpvmpc_handle *h, int32_t B, const double *x0,
     if (h && B == 0) return LPVMPC_OK;                                   // an empty batch is a no-op
     int rc = lpvmpc_check_batch(h, B, "lpvmpc_solve_batch"); if (rc) return rc;
     rc = lpvmpc_model_check(h, B, "lpvmpc_solve_batch"); if (rc) return rc;
+    rc = lpvmpc_tuning_check(h, B, "lpvmpc_solve_batch"); if (rc) return rc;
     const bool ctrl = h->cfg.kind == LPVMPC_KIND_CONTROLLER;
     if (!x0 || !u_prev) return fail(h, LPVMPC_E_ARG, "lpvmpc_solve_batch: x0 / u_prev is NULL");
     if (ctrl && !vel_ref) return fail(h, LPVMPC_E_ARG, "lpvmpc_solve_batch: controller needs vel_ref");
@@ -618,6 +615,7 @@ extern "C" int lpvmpc_solve_batch_masked(lpvmpc_handle *h, int32_t B, const doub
     if (h && B == 0) return LPVMPC_OK;                                   // an empty batch is a no-op
     int rc = lpvmpc_check_batch(h, B, "lpvmpc_solve_batch_masked"); if (rc) return rc;
     rc = lpvmpc_model_check(h, B, "lpvmpc_solve_batch_masked"); if (rc) return rc;
+    rc = lpvmpc_tuning_check(h, B, "lpvmpc_solve_batch_masked"); if (rc) return rc;
     if (!active) return fail(h, LPVMPC_E_ARG, "lpvmpc_solve_batch_masked: active is NULL");
     std::vector<int32_t> rows;
     for (int i = 0; i < B; ++i) if (active[i]) rows.push_back(i);
@@ -710,6 +708,7 @@ static int cl_init(lpvmpc_handle *h, int32_t B, const double *plant0, double hal
                    const std::vector<double> *veh = nullptr) {
     int rc = lpvmpc_check_common(h, B, "lpvmpc_cl_init"); if (rc) return rc;
     rc = lpvmpc_model_check(h, B, "lpvmpc_cl_init"); if (rc) return rc;
+    rc = lpvmpc_tuning_check(h, B, "lpvmpc_cl_init"); if (rc) return rc;
     if (h->cfg.kind != LPVMPC_KIND_CONTROLLER) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: controller handles only");
     if (h->race || h->race_owner) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: this handle takes part in a race (lpvmpc_cl_release on its path handle ends it)");
     if (h->cfg.N > 20) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: the reference's seed trajectories have 20 rows (N <= 20)");

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stddef.h>
 
 namespace lpvmpc {
 
@@ -18,6 +19,8 @@ struct DevCfg {
     int32_t check_termination, scaling, adaptive_rho, adaptive_rho_interval;
     int32_t polish, polish_refine_iter, steering_delay, pad1;
     double dt, lf, lr, m, Iz, Cf, Cr, mu, max_vel, min_vel;
+    // the tuning words: kTuneWords contiguous doubles, the device row of lpvmpc_set_tunings (a row of the handle's table replaces them
+    // per instance in the solve kernel's set-up block; nothing else on the device reads them)
     double Q[36], R[4], dR[2], Lcf[6];
     double box_lo[8], box_hi[8];   // per-stage box rows, unscaled (planner row 3 = ey is per instance)
     double rho, sigma, alpha, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, delta, rho_tol;
@@ -46,6 +49,14 @@ __device__ inline double track_curvature(const DevCfg &c, double s) {
     }
     return __builtin_nan("");
 }
+
+// offsets of the tuning words within their block (DevCfg::Q onward) and within a device row of the tuning table
+constexpr int kTuneWords = 64;               // = LPVMPC_TUNING_WORDS
+constexpr int kTuneR = 36, kTunedR = 40, kTuneLcf = 42, kTuneLo = 48, kTuneHi = 56;
+static_assert(offsetof(DevCfg, R) - offsetof(DevCfg, Q) == kTuneR * sizeof(double) && offsetof(DevCfg, dR) - offsetof(DevCfg, Q) == kTunedR * sizeof(double) &&
+              offsetof(DevCfg, Lcf) - offsetof(DevCfg, Q) == kTuneLcf * sizeof(double) && offsetof(DevCfg, box_lo) - offsetof(DevCfg, Q) == kTuneLo * sizeof(double) &&
+              offsetof(DevCfg, box_hi) - offsetof(DevCfg, Q) == kTuneHi * sizeof(double) && offsetof(DevCfg, rho) - offsetof(DevCfg, Q) == kTuneWords * sizeof(double),
+              "the tuning words are one contiguous block of DevCfg");
 
 // arguments of the solve kernel (device pointers)
 struct SolveArgs {
@@ -94,6 +105,10 @@ struct SolveArgs {
     const int32_t *active;
     int defer_budget;       // resume = 2: iterations the riders continue for before they park again (defer_after is the new instances' word there;
                             // a resume launch carries its budget in defer_after, as before)
+    // [B][kTuneWords] per-instance tuning words (lpvmpc_set_tunings), instance-major: one workgroup reads one 512-byte row at
+    // wave-uniform addresses.  Indexed by instance of the call (a masked launch reads the rows of the vehicles it runs).  null: the
+    // configuration block's own words.  Resume, riders and tail launches read nothing from it: the parked image carries the words
+    const double *tune;
 };
 constexpr int kParkScalars = 16;     // behind the LDS image of a pool entry: c, cinv, rho, iter, to_chk, to_adp, instance index and the
                                      // instance's output pointers (xPred, uPred, status, iters, polish, resid, state) as 64-bit words

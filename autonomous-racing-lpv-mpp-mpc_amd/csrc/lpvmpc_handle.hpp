@@ -101,8 +101,14 @@ struct ModelTable {                     // per-vehicle model parameters (lpvmpc_
     double *d_model = nullptr;
     int model_B = 0;
 };
+struct TuneTable {                      // per-vehicle tunings (lpvmpc_set_tunings, tunings_api.hip): the device rows [tune_B][kTuneWords], instance-major, that
+    DevArena tune_mem;                  // every main solve launch of this handle takes (SolveArgs::tune, lpvmpc_solve_tune), null: the configuration's own
+    double *d_tune = nullptr;           // words; the public rows as they were set stay on the host for the read-back
+    int tune_B = 0;
+    std::vector<double> tune_rows;
+};
 
-struct lpvmpc_handle : Workspace, Fleet, ObsState, ObsGains, ObsStage, DeferPools, Handoff, ModelTable {
+struct lpvmpc_handle : Workspace, Fleet, ObsState, ObsGains, ObsStage, DeferPools, Handoff, ModelTable, TuneTable {
     lpvmpc_config cfg{};
     DevCfg dev{};
     DevArena mem;                       // what lives as long as the handle: d_cfg, dstats, the device staging buffers
@@ -189,6 +195,11 @@ LPVMPC_HIDDEN const lpvmpc::VehPlantCfg *lpvmpc_race_plant(const lpvmpc_handle *
 // model_params_api.hip: lpvmpc_model_check refuses a batch size other than that of the handle's bound model rows (unbound: any);
 // called by every entry point that linearises, before anything is launched
 LPVMPC_HIDDEN int lpvmpc_model_check(lpvmpc_handle *h, int B, const char *who);
+// tunings_api.hip: lpvmpc_tuning_check refuses a batch size other than that of the handle's bound tuning rows (unbound: any);
+// called by every entry point that solves, before anything is launched.  lpvmpc_solve_tune fills SolveArgs::tune of a launch that
+// sets instances up (main launches, with or without riders; a resume pass reads no row) and refuses one the table does not cover
+LPVMPC_HIDDEN int lpvmpc_tuning_check(lpvmpc_handle *h, int B, const char *who);
+LPVMPC_HIDDEN int lpvmpc_solve_tune(lpvmpc_handle *h, lpvmpc::SolveArgs &a);
 namespace lpvmpc {
 // handoff.hip (host): interpolation operator W and interpolation + filtfilt operator FW, both [M][N] row-major
 bool handoff_operators(int N, double dt, double interp_dt, int padlen, int ord, const double *b, const double *a,

@@ -90,6 +90,9 @@ static int race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, i
     rc = lpvmpc_model_check(h, B, "lpvmpc_race_init"); if (rc) return rc;
     rc = lpvmpc_model_check(tt, B, "lpvmpc_race_init(tt)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
     rc = lpvmpc_model_check(plan, B, "lpvmpc_race_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
+    rc = lpvmpc_tuning_check(h, B, "lpvmpc_race_init"); if (rc) return rc;
+    rc = lpvmpc_tuning_check(tt, B, "lpvmpc_race_init(tt)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
+    rc = lpvmpc_tuning_check(plan, B, "lpvmpc_race_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
     // the race is built in r and installed in the three handles after the last step that can fail: a failed call leaves them idle
     std::unique_ptr<lpvmpc_race> r(new (std::nothrow) lpvmpc_race());
     if (!r) return fail(h, LPVMPC_E_NOMEM, "out of host memory");

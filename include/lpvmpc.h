@@ -790,6 +790,52 @@ int  lpvmpc_plant_params_read(lpvmpc_handle *h, double *plant_params);
 int  lpvmpc_set_model_params(lpvmpc_handle *h, int32_t B, const double *model_params);
 int  lpvmpc_model_params_read(lpvmpc_handle *h, int32_t *B, double *model_params);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Per-vehicle tunings: every instance of a batch -- every vehicle of a fleet, cascade or race -- builds its QP with weights and box
+ * limits of its own instead of Q, R, dR, L_cf and the ctrl_* / plan_* limits of the handle's configuration: one batch, fleet or race
+ * evaluates as many controller or planner tunings as it has instances.  The OSQP settings, the horizon, steering_delay, dt, the
+ * track table and the vehicle words stay the handle's.  All four entry points are new; every call above keeps its behaviour and
+ * refusals, and a handle without a binding (the default) computes what it computed before.
+ *
+ * Public row, LPVMPC_TUNING_WORDS doubles in the units of lpvmpc_config:
+ *   [0..35]  Q, nx*nx row-major in the first nx*nx slots        [36..39] R        [40..41] dR
+ *   [42..47] L_cf (planner; ignored by a controller)
+ *   [48..63] limits.  Controller: [48] vx_min, [49] max_vel, [50] delta_max, [51] a_max, [52] a_min_abs; the rest is ignored.
+ *            Planner: [48..52] xmin, [53..57] xmax, [58..59] umin, [60..61] umax; xmin[0] and xmax[0] are min_vel and max_vel;
+ *            slot 3 (ey) of xmin / xmax is ignored: max_ey stays the per-instance argument it is.
+ * Ignored words are stored and read back as set.
+ *
+ * Table layout: rows [B][LPVMPC_TUNING_WORDS], instance-major, on the host and on the device.  The consumer is the solve kernel's
+ * set-up block, one workgroup per instance, which reads its 512-byte row at wave-uniform addresses.  (The plant and model tables
+ * are parameter-major on the device because their consumers are one lane per vehicle.)
+ *
+ * lpvmpc_tuning_from_config (host only): the public row a handle created from cfg solves with.
+ * lpvmpc_tuning_device_row (host only): the 64 words the kernel reads for a public row -- the block Q R dR Lcf box_lo[8] box_hi[8]
+ * of the device configuration (controller box rows: -vx <= -vx_min, vx <= max_vel, +-delta <= delta_max, a <= a_max,
+ * -a <= a_min_abs, lower bounds -inf; planner: the state and input boxes).  lpvmpc_create fills its configuration block through
+ * these two: the device row of a handle's own configuration is that handle's block, bit for bit.
+ *
+ * The binding belongs to the handle and acts wherever the handle solves: lpvmpc_solve_batch, _AB (unlike the model binding), _dev
+ * and _masked, seed mode, warm starts, straggler deferral, the lap-0 fleet (lpvmpc_cl_init*), the cascade and the race started
+ * afterwards (bind each handle they are made of separately: the same rows, or not).  Instance b takes row b: the row is indexed by
+ * vehicle, not by launch slot, so masked launches work unchanged.  A parked instance carries its words in its image: resume
+ * passes, riders and the tail kernel read nothing from the table.
+ *   - Bound, every such call must have the binding's batch size: another B is refused with LPVMPC_E_ARG before anything is
+ *     launched (the engines check it at init).
+ *   - Every value is formed by the same operations in the same order as without a binding: the handle's own row bound to every
+ *     instance gives the same words as the unbound handle.
+ * lpvmpc_set_tunings joins the handle's parked work, copies the rows to the device and synchronises; B = 0 unbinds (rows is then
+ * ignored).  Refused with LPVMPC_E_ARG, the binding unchanged: a non-finite weight word (of those the handle's kind reads), a NaN
+ * limit (infinite limits stay legal: the kernel clips to +-1e30), a lower limit above its upper one (vx_min > max_vel,
+ * delta_max < 0, a_max < -a_min_abs, xmin > xmax, umin > umax), B < 0, B > 0 with rows NULL, and any call while the handle runs a
+ * fleet, cascade or race.  lpvmpc_destroy frees the table.
+ * lpvmpc_tunings_read: *B = the binding's batch size (0: unbound) and, if rows is not NULL, the bound public rows as they were set. */
+#define LPVMPC_TUNING_WORDS 64
+int  lpvmpc_set_tunings(lpvmpc_handle *h, int32_t B, const double *rows);
+int  lpvmpc_tunings_read(lpvmpc_handle *h, int32_t *B, double *rows);
+int  lpvmpc_tuning_from_config(const lpvmpc_config *cfg, double *row);
+int  lpvmpc_tuning_device_row(int32_t kind, const double *row, double *dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,11 @@ lines also carry the solvers' changed iteration counts.
 (lpvmpc_set_model_params: the per-vehicle forms of the LPV kernels), and, with --parent-lib FILE (another build of the library, a file
 name inside the package directory), unbound on that build; alternated --reps times per (regime, B), one child process per run (a
 process loads one build); medians, each configuration's spread over the alternations and the differences against the unbound race.
-Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator | --actuator | --record | --plant-params | --models
+--tunings: the same protocol for the per-vehicle tunings (lpvmpc_set_tunings): unbound, each handle's own tuning row bound to every
+vehicle of the three engines (the cost of the binding: one 512-byte row per workgroup at set-up), and sampled rows on all three
+(tuning.sample_tunings, seed 1, weights +-30 %: other QPs, so other iteration counts -- a launch ends in its slowest instance; reported,
+not a regression), and, with --parent-lib FILE, unbound on that build.
+Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator | --actuator | --record | --plant-params | --models | --tunings
        [--parent-lib FILE] [--reps R]] [--out FILE]"""
 import argparse
 import os
@@ -52,8 +56,13 @@ def timed(tick, read, K):
     return (time.perf_counter() - t0) * 1e3 / K
 
 
-def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, record=False, plant_params=None, model_params=None):
+def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, record=False, plant_params=None, model_params=None, tunings=None):
     path, tt, plan = engines(mp, sd)
+    if tunings is not None:                                           # "own": each handle's own row; "sampled": sample_tunings around it
+        from lpvmpc import tuning
+        for e in (path, tt, plan):
+            B = plant0.shape[0]
+            e.set_tunings(tuning.tuning_rows(B, e) if tunings == "own" else tuning.sample_tunings(B, 1, engine=e))
     if model_params is not None:
         for e in (path, tt, plan):
             e.set_model_params(model_params)
@@ -82,6 +91,7 @@ def main():
     ap.add_argument("--record", action="store_true")
     ap.add_argument("--plant-params", action="store_true")
     ap.add_argument("--models", action="store_true")
+    ap.add_argument("--tunings", action="store_true")
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--models-child", nargs=4, default=None, help=argparse.SUPPRESS)      # lib regime B bind: one run of --models
     a = ap.parse_args()
@@ -89,6 +99,8 @@ def main():
         return models_child(a)
     if a.models:
         return models_main(a)
+    if a.tunings:
+        return models_main(a, [("unbound", "liblpvmpc.so", 0), ("own rows bound", "liblpvmpc.so", 2), ("sampled rows bound", "liblpvmpc.so", 3)])
     if a.plant_params:
         return plant_params_main(a)
     if a.record:
@@ -257,14 +269,14 @@ def models_child(a):
     import lpvmpc
     mp = lpvmpc.Map("L_shape", 0.2)
     plant0, half, warm = _models_starts(int(B))[regime]
-    rows = lpvmpc.model_params(int(B)) if int(bind) else None
-    ms, _vps, ph = race_run(mp, plant0, half, warm, a.ticks, model_params=rows)
+    rows = lpvmpc.model_params(int(B)) if int(bind) == 1 else None                # bind: 0 nothing, 1 nominal model rows, 2 / 3 tuning rows
+    ms, _vps, ph = race_run(mp, plant0, half, warm, a.ticks, model_params=rows, tunings={2: "own", 3: "sampled"}.get(int(bind)))
     print("MODELS_RUN %.6f %s" % (ms, ",".join(str(int(x)) for x in ph)), flush=True)
 
 
-def models_main(a):
+def models_main(a, cfgs=None):
     import subprocess
-    cfgs = [("unbound", "liblpvmpc.so", 0), ("nominal rows bound", "liblpvmpc.so", 1)]
+    cfgs = list(cfgs or [("unbound", "liblpvmpc.so", 0), ("nominal rows bound", "liblpvmpc.so", 1)])
     if a.parent_lib:
         cfgs.append(("parent, unbound", a.parent_lib, 0))
     lines = []
