@@ -121,6 +121,8 @@ ACT_WORDS = 2 * ACT_MAX_DELAY + 2        # LPVMPC_ACT_WORDS: [motor ring, servo 
 
 PLANT_WORDS = 7                          # LPVMPC_PLANT_WORDS: [lf, lr, m, Iz, Cf, Cr, mu] per vehicle
 PLANT_WORD_NAMES = ("lf", "lr", "m", "Iz", "Cf", "Cr", "mu")
+TYRE_WORDS = 4                           # LPVMPC_TYRE_WORDS: [kind, B, C, c_f] per vehicle (plant.py, "tyre rows")
+TYRE_WORD_NAMES = ("kind", "B", "C", "c_f")
 MODEL_WORDS = 7                          # LPVMPC_MODEL_WORDS: the same words, as a controller's / planner's model of the vehicle
 TUNING_WORDS = 64                        # LPVMPC_TUNING_WORDS: Q[36] R[4] dR[2] L_cf[6] limits[16] per instance (tuning.py)
 
@@ -141,7 +143,9 @@ EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_d
            "lpvmpc_actuator_read", "lpvmpc_race_record", "lpvmpc_race_record_read", "lpvmpc_race_lap_stats",
            "lpvmpc_plant_step_vehicles_batch", "lpvmpc_cl_init_vehicles", "lpvmpc_race_init_vehicles", "lpvmpc_plant_params_read",
            "lpvmpc_set_model_params", "lpvmpc_model_params_read",
-           "lpvmpc_set_tunings", "lpvmpc_tunings_read", "lpvmpc_tuning_from_config", "lpvmpc_tuning_device_row")
+           "lpvmpc_set_tunings", "lpvmpc_tunings_read", "lpvmpc_tuning_from_config", "lpvmpc_tuning_device_row",
+           "lpvmpc_plant_step_tyres_batch", "lpvmpc_cl_init_tyres", "lpvmpc_race_init_tyres", "lpvmpc_tyre_params_read",
+           "lpvmpc_tyre_force_batch")
 
 _lib = None
 
@@ -287,6 +291,17 @@ def load():
         lib.lpvmpc_tuning_from_config.argtypes = [P(Config), vp]
         lib.lpvmpc_tuning_device_row.argtypes = [_i, vp, vp]
         for name in ("lpvmpc_set_tunings", "lpvmpc_tunings_read", "lpvmpc_tuning_from_config", "lpvmpc_tuning_device_row"):
+            getattr(lib, name).restype = C.c_int
+    except AttributeError:
+        pass
+    try:        # (nor the tyre model)
+        lib.lpvmpc_plant_step_tyres_batch.argtypes = [vp, _i, vp, vp, vp, _i, _d, _d, P(ActuatorConfig), vp, vp, vp, vp]
+        lib.lpvmpc_cl_init_tyres.argtypes = [vp, _i, vp, _d, _d, _i, _i, _d, _d, P(ActuatorConfig), vp, vp, vp, vp]
+        lib.lpvmpc_race_init_tyres.argtypes = [vp, vp, vp, _i, vp, vp, P(RaceConfig), P(ObserverConfig), P(ActuatorConfig), vp, vp, vp, vp]
+        lib.lpvmpc_tyre_params_read.argtypes = [vp, vp]
+        lib.lpvmpc_tyre_force_batch.argtypes = [vp, _i, vp, vp, vp, vp]
+        for name in ("lpvmpc_plant_step_tyres_batch", "lpvmpc_cl_init_tyres", "lpvmpc_race_init_tyres", "lpvmpc_tyre_params_read",
+                     "lpvmpc_tyre_force_batch"):
             getattr(lib, name).restype = C.c_int
     except AttributeError:
         pass

@@ -297,18 +297,41 @@ class BatchedSolver:
         return st, act
 
     def plant_step_vehicles(self, state, u, plant_params=None, act_state=None, n_sub=1, dt_sim=0.005, mu_sim=0.05, actuator=None,
-                            delay_a=None, delay_df=None):
+                            delay_a=None, delay_df=None, tyre_params=None):
         """plant_step_actuated with each vehicle's own plant row: plant_params [B, 7] = (lf, lr, m, Iz, Cf, Cr, mu) per vehicle
-        (None: the nominal row of this engine, plant.plant_params; mu_sim is ignored when rows are given).  Returns (state, act_state)."""
+        (None: the nominal row of this engine, plant.plant_params; mu_sim is ignored when rows are given).  ``tyre_params`` [B, 4] =
+        (kind, B, C, c_f) per vehicle, "pacejka" (the launch file's tyre for every vehicle) or "linear" (kind 0 for every vehicle),
+        selects lpvmpc_plant_step_tyres_batch: kind 1 vehicles step with Simulator.pacejka on both axles.  Returns (state, act_state)."""
         st = f64(state).reshape(-1, 8).copy(); B = st.shape[0]
         u = f64(u, (B, 2), "u")
         rows = _plant_rows(plant_params, B)
         act = np.zeros((B, _ffi.ACT_WORDS)) if act_state is None else f64(act_state, (B, _ffi.ACT_WORDS), "act_state").copy()
         cfg = _ffi.default_actuator_config() if actuator is None else _actuator_cfg(actuator)
         la, ld = _delay_array(delay_a, B, "delay_a"), _delay_array(delay_df, B, "delay_df")
+        if tyre_params is not None:
+            self._chk(self._lib.lpvmpc_plant_step_tyres_batch(self._h, B, ptr(st), ptr(act), ptr(u), int(n_sub), float(dt_sim), float(mu_sim),
+                                                              C.byref(cfg), ptr(la), ptr(ld), ptr(rows), ptr(_tyre_rows(tyre_params, B))))
+            return st, act
         self._chk(self._lib.lpvmpc_plant_step_vehicles_batch(self._h, B, ptr(st), ptr(act), ptr(u), int(n_sub), float(dt_sim), float(mu_sim),
                                                              C.byref(cfg), ptr(la), ptr(ld), ptr(rows)))
         return st, act
+
+    def tyre_force(self, tyre_params, m, alpha):
+        """The tyre curve on the device (lpvmpc_tyre_force_batch): force [B] of tyre row b at slip angle alpha [B] for mass m
+        (scalar or [B]); tyre_params [B, 4] or "pacejka"."""
+        al = f64(alpha).reshape(-1); B = al.shape[0]
+        mm = np.ascontiguousarray(np.broadcast_to(np.asarray(m, np.float64), (B,)))
+        out = np.empty(B)
+        self._chk(self._lib.lpvmpc_tyre_force_batch(self._h, B, ptr(_tyre_rows(tyre_params, B)), ptr(mm), ptr(al), ptr(out)))
+        return out
+
+    def tyre_params_read(self):
+        """The tyre rows [B, 4] of the fleet / race this engine runs, started with ``tyre_params`` (lpvmpc_tyre_params_read)."""
+        race = getattr(self, "_race", None) is not None
+        B = self._race[0] if race else getattr(self, "_cl_B", 0)
+        out = np.empty((B, _ffi.TYRE_WORDS))
+        self._chk(self._lib.lpvmpc_tyre_params_read(self._h, ptr(out)))
+        return out
 
     def plant_params_read(self):
         """The plant rows [B, 7] of the fleet / race this engine runs, started with ``plant_params`` (lpvmpc_plant_params_read)."""
@@ -369,19 +392,29 @@ class BatchedSolver:
         return out
 
     def cl_init(self, plant0, half_width, slack, q9_swap=True, n_sub=7, dt_sim=0.005, mu_sim=0.05, actuator=None, delay_a=None,
-                delay_df=None, plant_params=None):
+                delay_df=None, plant_params=None, tyre_params=None):
         """Start a lap-0 fleet.  ``actuator`` (an ``actuator.actuator_config`` result, even an all-off one) selects
         lpvmpc_cl_init_actuated: the actuator in the plant, controllers of any steering delay, per-vehicle delays delay_a /
         delay_df [B] in steps (None: the config's).  Without it the call is lpvmpc_cl_init.  ``plant_params`` [B, 7] (or
         "nominal": the nominal rows) selects lpvmpc_cl_init_vehicles: each vehicle's plant steps with its own row (lf, lr, m, Iz,
-        Cf, Cr, mu; mu_sim is then ignored), the actuator all off unless ``actuator`` is given."""
+        Cf, Cr, mu; mu_sim is then ignored), the actuator all off unless ``actuator`` is given.  ``tyre_params`` [B, 4] = (kind, B,
+        C, c_f) per vehicle, or "pacejka", selects lpvmpc_cl_init_tyres: the same fleet (plant_params None: nominal rows) whose kind
+        1 vehicles step with Simulator.pacejka on both axles."""
         p0 = f64(plant0).reshape(-1, 8)
-        if plant_params is not None:
+        if plant_params is not None or tyre_params is not None:
             B = p0.shape[0]
-            rows = None if _is_nominal(plant_params) else _plant_rows(plant_params, B)
+            rows = None if plant_params is None or _is_nominal(plant_params) else _plant_rows(plant_params, B)
             la, ld = _delay_array(delay_a, B, "delay_a"), _delay_array(delay_df, B, "delay_df")
             if actuator is None and (la is not None or ld is not None):
                 raise ValueError("per-vehicle delays need an actuator config")
+            if tyre_params is not None:
+                tyres = _tyre_rows(tyre_params, B)
+                self._chk(self._lib.lpvmpc_cl_init_tyres(self._h, B, ptr(p0), float(half_width), float(slack), 1 if q9_swap else 0,
+                                                         int(n_sub), float(dt_sim), float(mu_sim),
+                                                         None if actuator is None else C.byref(_actuator_cfg(actuator)),
+                                                         ptr(la), ptr(ld), ptr(rows), ptr(tyres)))
+                self._cl_B = B
+                return
             self._cl_B = B
             self._chk(self._lib.lpvmpc_cl_init_vehicles(self._h, B, ptr(p0), float(half_width), float(slack), 1 if q9_swap else 0,
                                                         int(n_sub), float(dt_sim), float(mu_sim),
@@ -531,7 +564,7 @@ class BatchedSolver:
 
     # -- race engine: lap 0, per-vehicle lap events, racing (lpvmpc_race_*) ------------------------------------
     def race_init(self, tt, planner, plant0, half_track0=None, estimator=None, actuator=None, delay_a=None, delay_df=None, plant_params=None,
-                  **cfg):
+                  tyre_params=None, **cfg):
         """Start a race owned by this PATH controller engine, with ``tt`` (racing tuning) and ``planner`` (handoff_setup done).
         plant0 [B,8]; half_track0 [B] (HalfTrack at the start, default 0); ``cfg``: fields of ``lpvmpc_race_config`` (laps,
         n_sub_lap0, n_sub, q9_swap, half_width, slack, plan_max_ey, dt_sim, mu_sim).  ``estimator``: an
@@ -540,7 +573,9 @@ class BatchedSolver:
         ground truth.  ``actuator`` (an ``actuator.actuator_config`` result, even an all-off one) selects lpvmpc_race_init_actuated:
         the actuator in the plant, path / tt of the same steering delay, per-vehicle delays delay_a / delay_df [B] in steps.
         ``plant_params`` [B, 7] (or "nominal") selects lpvmpc_race_init_vehicles: each vehicle's plant steps with its own row (lf,
-        lr, m, Iz, Cf, Cr, mu; cfg mu_sim is then ignored), with or without ``estimator`` / ``actuator``."""
+        lr, m, Iz, Cf, Cr, mu; cfg mu_sim is then ignored), with or without ``estimator`` / ``actuator``.  ``tyre_params`` [B, 4] =
+        (kind, B, C, c_f) per vehicle, or "pacejka", selects lpvmpc_race_init_tyres: the same race (plant_params None: nominal rows)
+        whose kind 1 vehicles step with Simulator.pacejka on both axles."""
         p0 = f64(plant0).reshape(-1, 8)
         B = p0.shape[0]
         c = _ffi.default_race_config()
@@ -560,15 +595,17 @@ class BatchedSolver:
         ht = None if half_track0 is None else np.ascontiguousarray(np.broadcast_to(np.asarray(half_track0), (B,)), np.int32)
         if estimator is not None and not isinstance(estimator, _ffi.ObserverConfig):
             raise TypeError("estimator must be an observer.observer_config(...) result or an _ffi.ObserverConfig")
-        if plant_params is not None:
-            rows = None if _is_nominal(plant_params) else _plant_rows(plant_params, B)
+        if plant_params is not None or tyre_params is not None:
+            rows = None if plant_params is None or _is_nominal(plant_params) else _plant_rows(plant_params, B)
             la, ld = _delay_array(delay_a, B, "delay_a"), _delay_array(delay_df, B, "delay_df")
             if actuator is None and (la is not None or ld is not None):
                 raise ValueError("per-vehicle delays need an actuator config")
-            self._chk(self._lib.lpvmpc_race_init_vehicles(self._h, tt._h, planner._h, B, ptr(p0), ptr(ht), C.byref(c),
-                                                          None if estimator is None else C.byref(estimator),
-                                                          None if actuator is None else C.byref(_actuator_cfg(actuator)), ptr(la), ptr(ld),
-                                                          ptr(rows)))
+            args = (self._h, tt._h, planner._h, B, ptr(p0), ptr(ht), C.byref(c), None if estimator is None else C.byref(estimator),
+                    None if actuator is None else C.byref(_actuator_cfg(actuator)), ptr(la), ptr(ld), ptr(rows))
+            if tyre_params is not None:
+                self._chk(self._lib.lpvmpc_race_init_tyres(*(args + (ptr(_tyre_rows(tyre_params, B)),))))
+            else:
+                self._chk(self._lib.lpvmpc_race_init_vehicles(*args))
         elif actuator is not None:
             la, ld = _delay_array(delay_a, B, "delay_a"), _delay_array(delay_df, B, "delay_df")
             self._chk(self._lib.lpvmpc_race_init_actuated(self._h, tt._h, planner._h, B, ptr(p0), ptr(ht), C.byref(c),
@@ -702,6 +739,17 @@ def _plant_rows(v, B):
         return None
     from .plant import check_plant_params
     return check_plant_params(v, B)
+
+
+def _tyre_rows(v, B):
+    """Per-vehicle tyre rows: "pacejka" (the launch file's tyre for every vehicle), "linear" (None: the library's kind 0 rows), or
+    exactly [B, 4] checked words."""
+    from .plant import check_tyre_params, tyre_params
+    if isinstance(v, str):
+        if v not in ("pacejka", "linear"):
+            raise ValueError("tyre_params must be [B, 4] rows, \"pacejka\" or \"linear\", got %r" % (v,))
+        return tyre_params(B) if v == "pacejka" else None
+    return check_tyre_params(v, B)
 
 
 def _actuator_cfg(a):
@@ -1007,7 +1055,8 @@ class RaceFleet(object):
     ``actuator``: an ``actuator.actuator_config(...)`` result puts the actuator delays / servo lag in the plant (per-vehicle
     delay_a / delay_df in steps); ``steering_delay``: both controllers' steeringDelay (needs ``actuator``, e.g.
     actuator.controller_delay(delay_df_s)).  ``plant_params``: [B, 7] rows (lf, lr, m, Iz, Cf, Cr, mu) give every vehicle its own
-    plant (plant.sample_plant_params for a mismatch sweep); the controllers and the planner keep the nominal model unless
+    plant (plant.sample_plant_params for a mismatch sweep), ``tyre_params`` [B, 4] rows (kind, B, C, c_f; or "pacejka") its own tyre
+    (plant.tyre_params, plant.sample_tyre_params); the controllers and the planner keep the nominal, linear-tyre model unless
     ``model_params`` is given: [B, 7] rows bound to the path, tt and planner engines (BatchedSolver.set_model_params), or the string
     "plant": each vehicle's model is its plant row (the matched experiment; the nominal plant rows where plant_params is None or
     "nominal").  ``path_tunings`` / ``tt_tunings`` / ``plan_tunings``: [B, 64] tuning rows (tuning.tuning_rows, tuning.sample_tunings)
@@ -1015,7 +1064,7 @@ class RaceFleet(object):
 
     def __init__(self, track_map, plant0, laps=1, N=20, Np=40, half_track0=None, device=0, estimator=None, actuator=None,
                  steering_delay=0, delay_a=None, delay_df=None, plant_params=None, model_params=None, path_tunings=None,
-                 tt_tunings=None, plan_tunings=None, **options):
+                 tt_tunings=None, plan_tunings=None, tyre_params=None, **options):
         from .workloads import CTRL_TUNINGS, PLAN_L, PLAN_Q, PLAN_R, PLAN_dR
         race_keys = ("n_sub_lap0", "n_sub", "q9_swap", "plan_max_ey", "dt_sim", "mu_sim")
         race_opts = {k: v for k, v in options.items() if k in race_keys}
@@ -1051,7 +1100,7 @@ class RaceFleet(object):
                 e.set_tunings(check_tuning_rows(rows, f64(plant0).reshape(-1, 8).shape[0], e.kind))
         self.path.race_init(self.tt, self.planner, plant0, half_track0=half_track0, laps=laps, half_width=track_map.halfWidth,
                             slack=track_map.slack, estimator=estimator, actuator=actuator, delay_a=delay_a, delay_df=delay_df,
-                            plant_params=plant_params, **race_opts)
+                            plant_params=plant_params, tyre_params=tyre_params, **race_opts)
 
     def run(self, n_ticks):
         """Enqueue n_ticks controller ticks (no synchronisation)."""
@@ -1072,6 +1121,10 @@ class RaceFleet(object):
     def plant_params(self):
         """The vehicles' plant rows [B, 7] of a race started with ``plant_params`` (BatchedSolver.plant_params_read)."""
         return self.path.plant_params_read()
+
+    def tyre_params(self):
+        """The vehicles' tyre rows [B, 4] of a race started with ``tyre_params`` (BatchedSolver.tyre_params_read)."""
+        return self.path.tyre_params_read()
 
     def model_params(self):
         """The model rows [B, 7] bound to the race's three engines by ``model_params`` (read from the path engine), or None."""

@@ -8,10 +8,11 @@
 // Five of them -- the kernels that step the plant -- have a per-vehicle form (kVeh = true, always with kAct = true): their plant
 // argument is the fleet's table of per-vehicle parameters (VehPlantCfg, PlantArg<kVeh>) instead of one PlantCfg, and each simulator
 // step reads the vehicle's row (plant_step_at, track_geometry.hpp).  kVeh defaults to false, so the plain and delayed forms keep
-// their code.
+// their code.  The same five have a tyre form (kTyre = true, always with kVeh = true): the argument is the plant table plus the
+// fleet's tyre table (TyrePlantCfg), and plant_step_at takes the vehicle's tyre row as well (linear or Pacejka, per vehicle).
 //
 // One instantiation per translation unit: the .hip files above instantiate <false> only, actuator.hip <true> only, plant_params.hip
-// <true, true> only.  With both
+// <true, true> only, tyre.hip <true, true, true> only.  With both
 // forms of a kernel in one translation unit LLVM compiles the plain form differently (other registers, other instructions); with
 // one per translation unit each form compiles to the code it has alone (docs/HISTORY.md, "Fleet kernels as templates").
 // tests/test_fleet_kernel_instances.py guards the rule.
@@ -23,9 +24,9 @@
 namespace lpvmpc {
 
 // n_sub simulator steps under u = [motor, servo] per vehicle (lpvmpc_plant_step_batch / _actuated_batch)
-template <bool kAct, bool kVeh = false>
-__global__ void __launch_bounds__(64) plant_kernel(int B, double *__restrict__ plant, const double *__restrict__ u, PlantArg<kVeh> pc, ActDev a) {
-    static_assert(kAct || !kVeh, "the per-vehicle forms are delayed forms");
+template <bool kAct, bool kVeh = false, bool kTyre = false>
+__global__ void __launch_bounds__(64) plant_kernel(int B, double *__restrict__ plant, const double *__restrict__ u, PlantArg<kVeh, kTyre> pc, ActDev a) {
+    static_assert((kAct || !kVeh) && (kVeh || !kTyre), "the per-vehicle forms are delayed forms, the tyre forms per-vehicle forms");
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     double st[8];
@@ -67,12 +68,12 @@ __global__ void __launch_bounds__(64) cl_measure_kernel(const DevCfg *__restrict
 // command = first predicted input (CMAIN:381-386: servo = uPred[0,0], motor = uPred[0,1]), n_sub simulator steps under it
 // (u = [motor, servo], vehicleSimulator.py:330), then the NEXT tick's measurement (cl_measure_kernel on the state just advanced):
 // one launch less per control tick; the measurement goes to its own buffer, the previous tick's local state stays readable
-template <bool kAct, bool kVeh = false>
+template <bool kAct, bool kVeh = false, bool kTyre = false>
 __global__ void __launch_bounds__(64) cl_command_plant_measure_kernel(const DevCfg *__restrict__ cp, int B, int N, const double *__restrict__ uPred,
-                                                                      double *__restrict__ cmd, double *__restrict__ plant, PlantArg<kVeh> pc,
+                                                                      double *__restrict__ cmd, double *__restrict__ plant, PlantArg<kVeh, kTyre> pc,
                                                                       double hw, double slack, int q9_swap, double *__restrict__ local_next,
                                                                       double *__restrict__ u_old, int sd, ActDev a) {
-    static_assert(kAct || !kVeh, "the per-vehicle forms are delayed forms");
+    static_assert((kAct || !kVeh) && (kVeh || !kTyre), "the per-vehicle forms are delayed forms, the tyre forms per-vehicle forms");
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const double servo = uPred[(size_t)b * N * 2 + 0], motor = uPred[(size_t)b * N * 2 + 1];
@@ -114,13 +115,13 @@ __global__ void __launch_bounds__(64) cl_command_plant_measure_kernel(const DevC
 // tick of a fleet; one kernel keeps local_position at a single call site, inlined).  mode 2 (the cascade, plain form only):
 // advance, then write the estimate in the plant's layout [x y vx vy 0 0 yaw psiDot] to local_next [B][8], which the cascade's
 // measurement kernels read in place of the plant; u_old is left to them
-template <bool kAct, bool kVeh = false>
+template <bool kAct, bool kVeh = false, bool kTyre = false>
 __global__ void __launch_bounds__(64) cl_command_plant_observe_kernel(const DevCfg *__restrict__ cp, int B, int N, const double *__restrict__ uPred,
-                                                                      double *__restrict__ cmd, double *__restrict__ plant, PlantArg<kVeh> pc,
+                                                                      double *__restrict__ cmd, double *__restrict__ plant, PlantArg<kVeh, kTyre> pc,
                                                                       double hw, double slack, int q9_swap, double *__restrict__ local_next,
                                                                       double *__restrict__ u_old, const double *__restrict__ gains,
                                                                       double *__restrict__ obs, ObsParams op, int mode, int sd, ActDev a) {
-    static_assert(kAct || !kVeh, "the per-vehicle forms are delayed forms");
+    static_assert((kAct || !kVeh) && (kVeh || !kTyre), "the per-vehicle forms are delayed forms, the tyre forms per-vehicle forms");
     __shared__ double G[kObsGainWords];
     if (mode != 0) obs_stage_gains(G, gains);
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -238,9 +239,9 @@ __global__ void __launch_bounds__(64) race_measure_kernel(const DevCfg *__restri
 
 // last launch of a tick: the solve's report, the command of the vehicle's controller and its simulator steps.  A frozen vehicle
 // (nstep 0) advances neither plant nor actuator
-template <bool kAct, bool kVeh = false>
-__global__ void __launch_bounds__(64) race_command_plant_kernel(RaceDev r, PlantArg<kVeh> pc, ActDev a) {
-    static_assert(kAct || !kVeh, "the per-vehicle forms are delayed forms");
+template <bool kAct, bool kVeh = false, bool kTyre = false>
+__global__ void __launch_bounds__(64) race_command_plant_kernel(RaceDev r, PlantArg<kVeh, kTyre> pc, ActDev a) {
+    static_assert((kAct || !kVeh) && (kVeh || !kTyre), "the per-vehicle forms are delayed forms, the tyre forms per-vehicle forms");
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= r.B) return;
     const int src = r.src[b], n = r.nstep[b], N = r.N;
@@ -274,10 +275,10 @@ __global__ void __launch_bounds__(64) race_command_plant_kernel(RaceDev r, Plant
 // race_command_plant_kernel with the estimator in the loop: per plant step, plant -> sensors -> observer (obs_substep, the schedule
 // of cl_command_plant_observe_kernel), then the estimate view that the next tick's measurements read.  A frozen vehicle (nstep 0)
 // advances neither the plant, its actuator nor its observer, so its noise keys (vid, step) depend on its own steps only.
-template <bool kAct, bool kVeh = false>
-__global__ void __launch_bounds__(64) race_command_plant_observe_kernel(RaceDev r, PlantArg<kVeh> pc, const double *__restrict__ gains,
+template <bool kAct, bool kVeh = false, bool kTyre = false>
+__global__ void __launch_bounds__(64) race_command_plant_observe_kernel(RaceDev r, PlantArg<kVeh, kTyre> pc, const double *__restrict__ gains,
                                                                         double *__restrict__ obs, ObsParams op, ActDev a) {
-    static_assert(kAct || !kVeh, "the per-vehicle forms are delayed forms");
+    static_assert((kAct || !kVeh) && (kVeh || !kTyre), "the per-vehicle forms are delayed forms, the tyre forms per-vehicle forms");
     __shared__ double G[kObsGainWords];
     obs_stage_gains(G, gains);
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -320,6 +321,19 @@ __global__ void __launch_bounds__(64) race_command_plant_observe_kernel(RaceDev 
     double *v = r.estv + (size_t)b * 8;
     v[0] = os[3]; v[1] = os[4]; v[2] = os[0]; v[3] = os[1]; v[4] = 0.0; v[5] = 0.0; v[6] = os[5]; v[7] = os[2];
     r.step[b] += n;
+}
+
+// the tyre curve alone (lpvmpc_tyre_force_batch): a template like the fleet kernels, so that only tyre.hip holds its code
+template <bool kTyre>
+__global__ void __launch_bounds__(64) tyre_force_kernel(int B, const double *__restrict__ tyre, const double *__restrict__ m,
+                                                        const double *__restrict__ alpha, double *__restrict__ force) {
+    static_assert(kTyre, "tyre.hip's kernel");
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double ty[kTyreWords];
+#pragma unroll
+    for (int i = 0; i < kTyreWords; ++i) ty[i] = tyre[(size_t)i * B + b];
+    force[b] = tyre_force(ty, m[b], 60.0, alpha[b]);                        // a linear row: Simulator.f's 60
 }
 
 }  // namespace lpvmpc

@@ -702,10 +702,11 @@ extern "C" int lpvmpc_cl_release(lpvmpc_handle *h) {
 }
 
 // act == nullptr: lpvmpc_cl_init (refuses delayed controllers); else lpvmpc_cl_init_actuated (any steering_delay, actuator in the plant).
-// veh: the plant table [7][B] of lpvmpc_cl_init_vehicles (checked; act is then set), else null
+// veh: the plant table [7][B] of lpvmpc_cl_init_vehicles (checked; act is then set), else null; tyre: with veh, the tyre table [4][B]
+// of lpvmpc_cl_init_tyres (checked), else null
 static int cl_init(lpvmpc_handle *h, int32_t B, const double *plant0, double half_width, double slack, int32_t q9_swap,
                    int32_t n_sub, double dt_sim, double mu_sim, const lpvmpc_actuator_config *act, const int32_t *delay_a, const int32_t *delay_df,
-                   const std::vector<double> *veh = nullptr) {
+                   const std::vector<double> *veh = nullptr, const std::vector<double> *tyre = nullptr) {
     int rc = lpvmpc_check_common(h, B, "lpvmpc_cl_init"); if (rc) return rc;
     rc = lpvmpc_model_check(h, B, "lpvmpc_cl_init"); if (rc) return rc;
     rc = lpvmpc_tuning_check(h, B, "lpvmpc_cl_init"); if (rc) return rc;
@@ -723,6 +724,7 @@ static int cl_init(lpvmpc_handle *h, int32_t B, const double *plant0, double hal
     release<Fleet>(*h);                                          // the old fleet first: never two at once
     release<ObsState>(*h);
     if (veh) { rc = lpvmpc_plant_upload(h, B, *veh, dt_sim, n_sub, f.cl_veh); if (rc) return rc; }
+    if (tyre) { rc = lpvmpc_tyre_upload(h, *tyre, f.cl_tyre); if (rc) return rc; }
     f.cl_actuated = act != nullptr;
     HIP_TRY(h, f.cl_mem.alloc(f.cl_local_next, (size_t)B * 6 * 8));
     HIP_TRY(h, f.cl_mem.alloc(f.cl_plant, (size_t)B * 8 * 8));
@@ -756,18 +758,25 @@ extern "C" int lpvmpc_cl_init_actuated(lpvmpc_handle *h, int32_t B, const double
     return cl_init(h, B, plant0, half_width, slack, q9_swap, n_sub, dt_sim, mu_sim, act, delay_a, delay_df);
 }
 
-extern "C" int lpvmpc_cl_init_vehicles(lpvmpc_handle *h, int32_t B, const double *plant0, double half_width, double slack, int32_t q9_swap,
-                                       int32_t n_sub, double dt_sim, double mu_sim, const lpvmpc_actuator_config *act,
-                                       const int32_t *delay_a, const int32_t *delay_df, const double *plant_params) {
-    const char *who = "lpvmpc_cl_init_vehicles";
+int lpvmpc_cl_init_rows(lpvmpc_handle *h, int32_t B, const double *plant0, double half_width, double slack, int32_t q9_swap, int32_t n_sub,
+                        double dt_sim, double mu_sim, const lpvmpc_actuator_config *act, const int32_t *delay_a, const int32_t *delay_df,
+                        const double *plant_params, bool tyres, const double *tyre_params) {
+    const char *who = tyres ? "lpvmpc_cl_init_tyres" : "lpvmpc_cl_init_vehicles";
     if (!h) return fail(nullptr, LPVMPC_E_ARG, "%s: handle is NULL", who);
     if (B <= 0) return fail(h, LPVMPC_E_ARG, "%s: B <= 0", who);
-    std::vector<double> tab;
+    std::vector<double> tab, tyr;
     int rc = lpvmpc_plant_rows(h, B, plant_params, h->cfg, mu_sim, who, tab); if (rc) return rc;
+    if (tyres) { rc = lpvmpc_tyre_rows(h, B, tyre_params, who, tyr); if (rc) return rc; }
     lpvmpc_actuator_config off;
     lpvmpc_actuator_default_config(&off);
     if (!act) { act = &off; delay_a = delay_df = nullptr; }               // all off: the delayed kernels pass the command through
-    return cl_init(h, B, plant0, half_width, slack, q9_swap, n_sub, dt_sim, mu_sim, act, delay_a, delay_df, &tab);
+    return cl_init(h, B, plant0, half_width, slack, q9_swap, n_sub, dt_sim, mu_sim, act, delay_a, delay_df, &tab, tyres ? &tyr : nullptr);
+}
+
+extern "C" int lpvmpc_cl_init_vehicles(lpvmpc_handle *h, int32_t B, const double *plant0, double half_width, double slack, int32_t q9_swap,
+                                       int32_t n_sub, double dt_sim, double mu_sim, const lpvmpc_actuator_config *act,
+                                       const int32_t *delay_a, const int32_t *delay_df, const double *plant_params) {
+    return lpvmpc_cl_init_rows(h, B, plant0, half_width, slack, q9_swap, n_sub, dt_sim, mu_sim, act, delay_a, delay_df, plant_params, false, nullptr);
 }
 
 extern "C" int lpvmpc_cl_tick(lpvmpc_handle *h, int32_t n_ticks) {
@@ -797,7 +806,15 @@ extern "C" int lpvmpc_cl_tick(lpvmpc_handle *h, int32_t n_ticks) {
         SolveArgs a{B, x0, h->d_AB, h->d_vel, h->d_uold, nullptr, h->d_xPred, h->d_uPred, h->d_status, h->d_iters, h->d_polish, h->d_resid,
                     nullptr, 0, x0_stride};
         int rc = lpvmpc_launch_solve_warm(h, a, st); if (rc) return rc;
-        if (h->cl_veh.d.p && h->obs_state)
+        if (h->cl_tyre.t && h->obs_state)
+            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_tyre(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, tyre_plant(h->cl_veh, h->cl_tyre),
+                                                                     h->cl_hw, h->cl_slack, h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay,
+                                                                     h->obs_gains, h->obs_state, h->obs_p, h->cl_act.d, st));
+        else if (h->cl_tyre.t)
+            HIP_TRY(h, lpvmpc::launch_cl_command_plant_measure_tyre(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, tyre_plant(h->cl_veh, h->cl_tyre),
+                                                                     h->cl_hw, h->cl_slack, h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay,
+                                                                     h->cl_act.d, st));
+        else if (h->cl_veh.d.p && h->obs_state)
             HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_veh(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_veh.d, h->cl_hw, h->cl_slack,
                                                                     h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay, h->obs_gains,
                                                                     h->obs_state, h->obs_p, h->cl_act.d, st));

@@ -178,15 +178,30 @@ struct VehPlantCfg {
     int B;                                   // the table's row stride (vehicles)
     double dt; int n_sub;                    // fleet-wide, as in PlantCfg
 };
-// the plant argument of a fleet kernel (fleet_kernels.hpp): one PlantCfg for the fleet, or the table (kVeh)
-template <bool kVeh> struct PlantArgT { using type = PlantCfg; };
-template <> struct PlantArgT<true> { using type = VehPlantCfg; };
-template <bool kVeh> using PlantArg = typename PlantArgT<kVeh>::type;
+// tyre model (tyre.hip; lpvmpc_*_tyres, include/lpvmpc.h "Tyre model"): the per-vehicle forms' argument plus the fleet's tyre table
+// [kTyreWords][B], laid out and read like the plant table
+constexpr int kTyreWords = 4;                // = LPVMPC_TYRE_WORDS: kind (0 linear, 1 Pacejka), B, C, c_f
+struct TyrePlantCfg : VehPlantCfg {
+    const double *t;                         // [kTyreWords][B], the stride is VehPlantCfg::B
+};
+// the plant argument of a fleet kernel (fleet_kernels.hpp): one PlantCfg for the fleet, the table (kVeh), or the table and the tyre
+// table (kTyre)
+template <bool kVeh, bool kTyre = false> struct PlantArgT { using type = PlantCfg; };
+template <> struct PlantArgT<true, false> { using type = VehPlantCfg; };
+template <> struct PlantArgT<true, true> { using type = TyrePlantCfg; };
+template <bool kVeh, bool kTyre = false> using PlantArg = typename PlantArgT<kVeh, kTyre>::type;
 // the per-vehicle forms of the kernels that step the plant: always the delayed forms (an all-off actuator is a pass-through)
 hipError_t launch_plant_veh(int B, double *plant, const double *u_a_delta, const VehPlantCfg &pc, const ActDev &a, hipStream_t s);
 hipError_t launch_cl_command_plant_measure_veh(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
                                                const VehPlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
                                                int sd, const ActDev &a, hipStream_t s);
+// the tyre forms of the same kernels (tyre.hip): the per-vehicle forms whose simulator step takes the vehicle's tyre row
+hipError_t launch_plant_tyre(int B, double *plant, const double *u_a_delta, const TyrePlantCfg &pc, const ActDev &a, hipStream_t s);
+hipError_t launch_cl_command_plant_measure_tyre(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
+                                                const TyrePlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
+                                                int sd, const ActDev &a, hipStream_t s);
+// force [B] = the tyre curve of row b of tyre [kTyreWords][B] at slip angle alpha [B] for a vehicle of mass m [B]
+hipError_t launch_tyre_force(int B, const double *tyre, const double *m, const double *alpha, double *force, hipStream_t s);
 
 
 // gain-scheduled LPV estimator and simulated sensors (observer.hip)
@@ -215,6 +230,9 @@ hipError_t launch_cl_command_plant_observe_act(const DevCfg *dcfg, int B, int N,
 hipError_t launch_cl_command_plant_observe_veh(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
                                                const VehPlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
                                                int sd, const double *gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s);
+hipError_t launch_cl_command_plant_observe_tyre(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
+                                                const TyrePlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
+                                                int sd, const double *gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s);
 
 
 // planner -> controller hand-off and trajectory-tracking measurement (handoff.hip)
@@ -265,5 +283,9 @@ hipError_t launch_race_command_plant_observe_act(const RaceDev &r, PlantCfg pc, 
 hipError_t launch_race_command_plant_veh(const RaceDev &r, const VehPlantCfg &pc, const ActDev &a, hipStream_t s);
 hipError_t launch_race_command_plant_observe_veh(const RaceDev &r, const VehPlantCfg &pc, const double *gains, double *obs, const ObsParams &op,
                                                 const ActDev &a, hipStream_t s);
+// the tyre forms (lpvmpc_race_init_tyres, tyre.hip)
+hipError_t launch_race_command_plant_tyre(const RaceDev &r, const TyrePlantCfg &pc, const ActDev &a, hipStream_t s);
+hipError_t launch_race_command_plant_observe_tyre(const RaceDev &r, const TyrePlantCfg &pc, const double *gains, double *obs, const ObsParams &op,
+                                                 const ActDev &a, hipStream_t s);
 
 }  // namespace lpvmpc

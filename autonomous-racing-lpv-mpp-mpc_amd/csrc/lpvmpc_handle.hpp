@@ -45,6 +45,9 @@ template <class T> void release(T &x) { x = T{}; }          // release<Workspace
 
 struct ActState { lpvmpc::ActDev d{}; DevArena mem; };          // actuator state of a delayed fleet or race (lpvmpc_act_alloc; d.ring == null: none)
 struct PlantTable { lpvmpc::VehPlantCfg d{}; DevArena mem; };   // plant table of a per-vehicle fleet or race (lpvmpc_plant_upload; d.p == null: one PlantCfg)
+struct TyreTable { const double *t = nullptr; DevArena mem; };   // tyre table [4][B] next to the plant table (lpvmpc_tyre_upload; t == null: the linear tyre's kernels)
+// the tyre forms' kernel argument: the plant table with its tyre table
+inline lpvmpc::TyrePlantCfg tyre_plant(const PlantTable &v, const TyreTable &y) { lpvmpc::TyrePlantCfg c; static_cast<lpvmpc::VehPlantCfg &>(c) = v.d; c.t = y.t; return c; }
 
 struct EventRing {                      // ring of event pairs around launches (lpvmpc_set_timing)
     std::vector<hipEvent_t> e0, e1;
@@ -76,6 +79,7 @@ struct Fleet {                          // closed-loop fleet (lpvmpc_cl_*): plan
     int cl_actuated = 0;                // the fleet was started by lpvmpc_cl_init_actuated: delayed kernels, actuator state cl_act
     ActState cl_act;
     PlantTable cl_veh;                  // the fleet was started by lpvmpc_cl_init_vehicles: its plant table
+    TyreTable cl_tyre;                  // the fleet was started by lpvmpc_cl_init_tyres: its tyre table as well
 };
 struct ObsState {                       // the fleet's / cascade's / race's estimator state [obs_B][kObsStride] (null: it runs on ground truth;
     DevArena obs_mem;                   // a race's is set by lpvmpc_race_init_observed without obs_cfg and freed with the race)
@@ -192,6 +196,24 @@ LPVMPC_HIDDEN int lpvmpc_plant_rows(lpvmpc_handle *h, int B, const double *rows,
                                     std::vector<double> &t);
 LPVMPC_HIDDEN int lpvmpc_plant_upload(lpvmpc_handle *h, int B, const std::vector<double> &t, double dt_sim, int n_sub, PlantTable &v);
 LPVMPC_HIDDEN const lpvmpc::VehPlantCfg *lpvmpc_race_plant(const lpvmpc_handle *h);                     // race_api.hip: the race's table
+// lpvmpc_plant_step_vehicles_batch with the checked tyre table [4][B] of tyre_api.hip (null: the per-vehicle forms' kernel)
+LPVMPC_HIDDEN int lpvmpc_plant_step_rows(lpvmpc_handle *h, int32_t B, double *state, double *act_state, const double *u, int32_t n_sub, double dt_sim,
+                                         double mu_sim, const lpvmpc_actuator_config *act, const int32_t *delay_a, const int32_t *delay_df,
+                                         const double *plant_params, const std::vector<double> *tyre, const char *who);
+// tyre_api.hip: tyre rows (lpvmpc_*_tyres).  lpvmpc_tyre_rows checks the host rows [B][4] (null: kind 0 for every vehicle) and returns
+// the device layout [4][B] in t; nothing is allocated.  lpvmpc_tyre_upload allocates and fills the table in y, released first (synchronises)
+LPVMPC_HIDDEN int lpvmpc_tyre_rows(lpvmpc_handle *h, int B, const double *rows, const char *who, std::vector<double> &t);
+LPVMPC_HIDDEN int lpvmpc_tyre_upload(lpvmpc_handle *h, const std::vector<double> &t, TyreTable &y);
+LPVMPC_HIDDEN const double *lpvmpc_race_tyre(const lpvmpc_handle *h);                                  // race_api.hip: the race's tyre table (null: none)
+// the fleet / race starts shared by the _vehicles and _tyres entry points (lpvmpc_api.hip, race_api.hip); tyre_params: see lpvmpc_tyre_rows,
+// tyres false: the _vehicles call
+LPVMPC_HIDDEN int lpvmpc_cl_init_rows(lpvmpc_handle *h, int32_t B, const double *plant0, double half_width, double slack, int32_t q9_swap,
+                                      int32_t n_sub, double dt_sim, double mu_sim, const lpvmpc_actuator_config *act, const int32_t *delay_a,
+                                      const int32_t *delay_df, const double *plant_params, bool tyres, const double *tyre_params);
+LPVMPC_HIDDEN int lpvmpc_race_init_rows(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, int32_t B, const double *plant0,
+                                        const int32_t *half_track0, const lpvmpc_race_config *cfg, const lpvmpc_observer_config *obs,
+                                        const lpvmpc_actuator_config *act, const int32_t *delay_a, const int32_t *delay_df,
+                                        const double *plant_params, bool tyres, const double *tyre_params);
 // model_params_api.hip: lpvmpc_model_check refuses a batch size other than that of the handle's bound model rows (unbound: any);
 // called by every entry point that linearises, before anything is launched
 LPVMPC_HIDDEN int lpvmpc_model_check(lpvmpc_handle *h, int B, const char *who);

@@ -38,10 +38,9 @@ int lpvmpc_plant_upload(lpvmpc_handle *h, int B, const std::vector<double> &t, d
     return LPVMPC_OK;
 }
 
-extern "C" int lpvmpc_plant_step_vehicles_batch(lpvmpc_handle *h, int32_t B, double *state, double *act_state, const double *u, int32_t n_sub,
-                                                double dt_sim, double mu_sim, const lpvmpc_actuator_config *act, const int32_t *delay_a,
-                                                const int32_t *delay_df, const double *plant_params) {
-    const char *who = "lpvmpc_plant_step_vehicles_batch";
+int lpvmpc_plant_step_rows(lpvmpc_handle *h, int32_t B, double *state, double *act_state, const double *u, int32_t n_sub, double dt_sim,
+                           double mu_sim, const lpvmpc_actuator_config *act, const int32_t *delay_a, const int32_t *delay_df,
+                           const double *plant_params, const std::vector<double> *tyre, const char *who) {
     if (h && B == 0) return LPVMPC_OK;
     int rc = lpvmpc_check_batch(h, B, who); if (rc) return rc;
     if (!state || !u || n_sub < 1 || !(dt_sim > 0) || (act && !act_state)) return fail(h, LPVMPC_E_ARG, "%s: bad argument", who);
@@ -62,16 +61,19 @@ extern "C" int lpvmpc_plant_step_vehicles_batch(lpvmpc_handle *h, int32_t B, dou
                 for (size_t j = 0; j < R; ++j) ring[(c * R + j) * b + i] = o[c * R + j];
             sv[i] = o[2 * R]; k[i] = (int32_t)kk;
         }
-    ActState as;                                                    // (both freed when the call returns)
+    ActState as;                                                    // (all freed when the call returns)
     PlantTable v;
+    TyreTable y;
     rc = lpvmpc_act_alloc(h, B, act, delay_a, delay_df, dt_sim, who, as); if (rc) return rc;
     const lpvmpc::ActDev &a = as.d;
     rc = lpvmpc_plant_upload(h, B, tab, dt_sim, n_sub, v);
+    if (rc == LPVMPC_OK && tyre) rc = lpvmpc_tyre_upload(h, *tyre, y);
     hipStream_t st = h->stream;
     auto run = [&]() -> int {
         H2D(a.ring, ring.data(), ring.size() * 8); H2D(a.servo, sv.data(), b * 8); H2D(a.k, k.data(), b * 4);
         H2D(h->d_xlast, state, b * 8 * 8); H2D(h->d_states, u, b * 2 * 8);
-        HIP_TRY(h, lpvmpc::launch_plant_veh(B, h->d_xlast, h->d_states, v.d, a, st));
+        if (y.t) HIP_TRY(h, lpvmpc::launch_plant_tyre(B, h->d_xlast, h->d_states, tyre_plant(v, y), a, st));
+        else HIP_TRY(h, lpvmpc::launch_plant_veh(B, h->d_xlast, h->d_states, v.d, a, st));
         D2H(state, h->d_xlast, b * 8 * 8);
         if (act_state) return lpvmpc_act_download(h, a, act_state, st);   // (synchronises)
         HIP_TRY(h, hipStreamSynchronize(st));
@@ -80,6 +82,13 @@ extern "C" int lpvmpc_plant_step_vehicles_batch(lpvmpc_handle *h, int32_t B, dou
     if (rc == LPVMPC_OK) rc = run();
     (void)hipStreamSynchronize(st);
     return rc;
+}
+
+extern "C" int lpvmpc_plant_step_vehicles_batch(lpvmpc_handle *h, int32_t B, double *state, double *act_state, const double *u, int32_t n_sub,
+                                                double dt_sim, double mu_sim, const lpvmpc_actuator_config *act, const int32_t *delay_a,
+                                                const int32_t *delay_df, const double *plant_params) {
+    return lpvmpc_plant_step_rows(h, B, state, act_state, u, n_sub, dt_sim, mu_sim, act, delay_a, delay_df, plant_params, nullptr,
+                                  "lpvmpc_plant_step_vehicles_batch");
 }
 
 // device [7][B] -> host [B][7]

@@ -28,6 +28,7 @@ struct lpvmpc_race {
     ActState act;
     int sd = 0;
     PlantTable veh;               // lpvmpc_race_init_vehicles: the plant table (veh.d.p; null: one PlantCfg), with the delayed kernels' actuator
+    TyreTable tyre;               // lpvmpc_race_init_tyres: the tyre table next to veh (tyre.t; null: the linear tyre's kernels)
     std::unique_ptr<lpvmpc_race_recorder> rec;   // lpvmpc_race_record (null: not recording)
 };
 
@@ -56,7 +57,7 @@ extern "C" void lpvmpc_race_default_config(lpvmpc_race_config *c) {
 static int race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, int32_t B, const double *plant0, const int32_t *half_track0,
                      const lpvmpc_race_config *cfg, const lpvmpc_observer_config *obs, bool observed_call,
                      const lpvmpc_actuator_config *act = nullptr, const int32_t *delay_a = nullptr, const int32_t *delay_df = nullptr,
-                     const std::vector<double> *veh = nullptr) {
+                     const std::vector<double> *veh = nullptr, const std::vector<double> *tyre = nullptr) {
     if (!h) return fail(nullptr, LPVMPC_E_ARG, "lpvmpc_race_init: path handle is NULL");
     if (!tt || !plan || !plant0 || !cfg || B <= 0) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: NULL argument or B <= 0");
     if (h->cfg.kind != LPVMPC_KIND_CONTROLLER || tt->cfg.kind != LPVMPC_KIND_CONTROLLER || plan->cfg.kind != LPVMPC_KIND_PLANNER || h == tt)
@@ -98,6 +99,7 @@ static int race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, i
     if (!r) return fail(h, LPVMPC_E_NOMEM, "out of host memory");
     if (act) { rc = lpvmpc_act_alloc(h, B, act, delay_a, delay_df, cfg->dt_sim, veh ? "lpvmpc_race_init_vehicles" : "lpvmpc_race_init_actuated", r->act); if (rc) return rc; }
     if (veh) { rc = lpvmpc_plant_upload(h, B, *veh, cfg->dt_sim, 1, r->veh); if (rc) return rc; }
+    if (tyre) { rc = lpvmpc_tyre_upload(h, *tyre, r->tyre); if (rc) return rc; }
     r->tt = tt; r->plan = plan;
     r->actuated = act != nullptr; r->sd = h->cfg.steering_delay;
     r->pc = lpvmpc_plant_cfg(h, 1, cfg->dt_sim, cfg->mu_sim);
@@ -173,22 +175,30 @@ extern "C" int lpvmpc_race_init_actuated(lpvmpc_handle *h, lpvmpc_handle *tt, lp
     return race_init(h, tt, plan, B, plant0, half_track0, cfg, obs, true, act, delay_a, delay_df);
 }
 
+int lpvmpc_race_init_rows(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, int32_t B, const double *plant0, const int32_t *half_track0,
+                          const lpvmpc_race_config *cfg, const lpvmpc_observer_config *obs, const lpvmpc_actuator_config *act,
+                          const int32_t *delay_a, const int32_t *delay_df, const double *plant_params, bool tyres, const double *tyre_params) {
+    const char *who = tyres ? "lpvmpc_race_init_tyres" : "lpvmpc_race_init_vehicles";
+    if (!h) return fail(nullptr, LPVMPC_E_ARG, "%s: path handle is NULL", who);
+    if (!cfg || B <= 0) return fail(h, LPVMPC_E_ARG, "%s: NULL configuration or B <= 0", who);
+    std::vector<double> tab, tyr;
+    int rc = lpvmpc_plant_rows(h, B, plant_params, h->cfg, cfg->mu_sim, who, tab); if (rc) return rc;
+    if (tyres) { rc = lpvmpc_tyre_rows(h, B, tyre_params, who, tyr); if (rc) return rc; }
+    lpvmpc_actuator_config off;
+    lpvmpc_actuator_default_config(&off);
+    if (!act) { act = &off; delay_a = delay_df = nullptr; }               // all off: the delayed kernels pass the command through
+    return race_init(h, tt, plan, B, plant0, half_track0, cfg, obs, true, act, delay_a, delay_df, &tab, tyres ? &tyr : nullptr);
+}
+
 extern "C" int lpvmpc_race_init_vehicles(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, int32_t B, const double *plant0,
                                          const int32_t *half_track0, const lpvmpc_race_config *cfg, const lpvmpc_observer_config *obs,
                                          const lpvmpc_actuator_config *act, const int32_t *delay_a, const int32_t *delay_df,
                                          const double *plant_params) {
-    const char *who = "lpvmpc_race_init_vehicles";
-    if (!h) return fail(nullptr, LPVMPC_E_ARG, "%s: path handle is NULL", who);
-    if (!cfg || B <= 0) return fail(h, LPVMPC_E_ARG, "%s: NULL configuration or B <= 0", who);
-    std::vector<double> tab;
-    int rc = lpvmpc_plant_rows(h, B, plant_params, h->cfg, cfg->mu_sim, who, tab); if (rc) return rc;
-    lpvmpc_actuator_config off;
-    lpvmpc_actuator_default_config(&off);
-    if (!act) { act = &off; delay_a = delay_df = nullptr; }               // all off: the delayed kernels pass the command through
-    return race_init(h, tt, plan, B, plant0, half_track0, cfg, obs, true, act, delay_a, delay_df, &tab);
+    return lpvmpc_race_init_rows(h, tt, plan, B, plant0, half_track0, cfg, obs, act, delay_a, delay_df, plant_params, false, nullptr);
 }
 
 const lpvmpc::VehPlantCfg *lpvmpc_race_plant(const lpvmpc_handle *h) { return h->race ? &h->race->veh.d : nullptr; }
+const double *lpvmpc_race_tyre(const lpvmpc_handle *h) { return h->race ? h->race->tyre.t : nullptr; }
 
 // the race's actuator state and its two controllers' histories (lpvmpc_actuator_read)
 int lpvmpc_race_act_read(lpvmpc_handle *h, double *act_state, double *path_hist, double *tt_hist) {
@@ -253,7 +263,10 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
                      tt->d_resid, nullptr, 0, 6};
         ta.active = d.m_tt;
         rc = lpvmpc_launch_solve_timed(tt, ta, st); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
-        if (r->veh.d.p && d.estv) HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_veh(d, r->veh.d, h->obs_gains, h->obs_state, h->obs_p, r->act.d, st));
+        if (r->tyre.t && d.estv)
+            HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_tyre(d, tyre_plant(r->veh, r->tyre), h->obs_gains, h->obs_state, h->obs_p, r->act.d, st));
+        else if (r->tyre.t) HIP_TRY(h, lpvmpc::launch_race_command_plant_tyre(d, tyre_plant(r->veh, r->tyre), r->act.d, st));
+        else if (r->veh.d.p && d.estv) HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_veh(d, r->veh.d, h->obs_gains, h->obs_state, h->obs_p, r->act.d, st));
         else if (r->veh.d.p) HIP_TRY(h, lpvmpc::launch_race_command_plant_veh(d, r->veh.d, r->act.d, st));
         else if (r->actuated && d.estv) HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_act(d, r->pc, h->obs_gains, h->obs_state, h->obs_p, r->act.d, st));
         else if (r->actuated) HIP_TRY(h, lpvmpc::launch_race_command_plant_act(d, r->pc, r->act.d, st));

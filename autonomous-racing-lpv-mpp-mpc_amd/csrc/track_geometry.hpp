@@ -150,14 +150,54 @@ __device__ inline void plant_step_row(const double q[kPlantWords], double dt, do
     st[7] = w + dt * (1.0 / Iz * (lf * FyF * cos(ud) - lr * FyR));
 }
 
+// one tyre's lateral force at slip angle ang for the tyre row ty = [kind B C c_f]: kind 0 the linear tyre C_lin * ang, kind 1
+// Simulator.pacejka (vehicleSimulator.py:202-205), D sin(C atan(B ang)) with D = c_f m g / 2 associated as the reference writes it
+__device__ inline double tyre_force(const double ty[kTyreWords], double m, double C_lin, double ang) {
+    if (ty[0] == 0.0) return C_lin * ang;
+    const double D = ty[3] * m * 9.81 / 2;
+    return D * sin(ty[2] * atan(ty[1] * ang));
+}
+
+// plant_step_row with the vehicle's tyre row on both axles (lpvmpc_*_tyres): its expressions, written out again because sharing them
+// with plant_step_row through a helper changes the per-vehicle forms' code, with tyre_force where it has Cf * aF, Cr * aR -- a kind 0
+// row gives plant_step_row's bits
+__device__ inline void plant_step_tyre_row(const double q[kPlantWords], const double ty[kTyreWords], double dt, double st[8], double ua,
+                                           double ud) {
+    const double lf = q[0], lr = q[1], m = q[2], Iz = q[3], Cf = q[4], Cr = q[5], mu = q[6];
+    const double x = st[0], y = st[1], vx = st[2], vy = st[3], ax = st[4], ay = st[5], yaw = st[6], w = st[7];
+    double aF = 0.0, aR = 0.0;
+    if (fabs(vx) > 0.2) {
+        aF = ud - atan((vy + lf * w) / fabs(vx));
+        aR = atan((-vy + lr * w) / fabs(vx));
+    }
+    const double FyF = tyre_force(ty, m, Cf, aF), FyR = tyre_force(ty, m, Cr, aR);
+    st[0] = x + dt * (cos(yaw) * vx - sin(yaw) * vy);
+    st[1] = y + dt * (sin(yaw) * vx + cos(yaw) * vy);
+    st[2] = fabs(vx + dt * (ax + w * vy));
+    st[3] = vy + dt * (ay - w * vx);
+    st[4] = ua - mu * vx - FyF / m * sin(ud);
+    st[5] = 1.0 / m * (FyF * cos(ud) + FyR);
+    st[6] = yaw + dt * w;
+    st[7] = w + dt * (1.0 / Iz * (lf * FyF * cos(ud) - lr * FyR));
+}
+
 // one simulator step of vehicle b in a fleet kernel: the fleet's PlantCfg (plain and delayed forms), or the vehicle's row of the
-// table (per-vehicle forms), read at every step -- a cached, coalesced load instead of seven more registers held across the loop
+// table (per-vehicle forms) and of the tyre table (tyre forms), read at every step -- a cached, coalesced load instead of seven or
+// eleven more registers held across the loop
 __device__ __forceinline__ void plant_step_at(const PlantCfg &p, int, double st[8], double ua, double ud) { plant_step(p, st, ua, ud); }
 __device__ __forceinline__ void plant_step_at(const VehPlantCfg &p, int b, double st[8], double ua, double ud) {
     double q[kPlantWords];
 #pragma unroll
     for (int i = 0; i < kPlantWords; ++i) q[i] = p.p[(size_t)i * p.B + b];
     plant_step_row(q, p.dt, st, ua, ud);
+}
+__device__ __forceinline__ void plant_step_at(const TyrePlantCfg &p, int b, double st[8], double ua, double ud) {
+    double q[kPlantWords], ty[kTyreWords];
+#pragma unroll
+    for (int i = 0; i < kPlantWords; ++i) q[i] = p.p[(size_t)i * p.B + b];
+#pragma unroll
+    for (int i = 0; i < kTyreWords; ++i) ty[i] = p.t[(size_t)i * p.B + b];
+    plant_step_tyre_row(q, ty, p.dt, st, ua, ud);
 }
 
 // Actuator stage of one simulator step (vehicleSimulator.py:67-76) for vehicle b at its plant step kk: the command (motor, servo)

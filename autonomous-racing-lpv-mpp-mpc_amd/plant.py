@@ -85,3 +85,69 @@ def sample_plant_params(B, seed, spread=None, engine=None, mu_sim=0.05, offset=0
             u = np.random.default_rng([int(seed), i]).uniform(-1.0, 1.0, offset + B)[offset:]
             base[:, i] *= 1.0 + float(spread[k]) * u
     return check_plant_params(base, B)
+
+
+# ---- tyre rows (include/lpvmpc.h, "Tyre model"): [kind, B, C, c_f] per vehicle -- kind 0 the linear tyre of the plant row, kind 1
+# Simulator.pacejka (vehicleSimulator.py:202-205) on both axles
+TYRE_WORDS = _ffi.TYRE_WORD_NAMES
+PACEJKA = (1.0, 6.0, 1.6, 0.8)           # MAIN_LAUNCH.launch: simulator/B, simulator/C, simulator/c_f
+DEFAULT_TYRE_SPREAD = dict(B=0.20, C=0.10, c_f=0.25)
+
+
+def check_tyre_params(rows, B):
+    """rows as a contiguous float64 [B, 4] array; ValueError on another shape, a kind other than exactly 0 or 1, or a non-finite or
+    negative B, C, c_f (the library's refusals, raised before any call into it)."""
+    a = np.asarray(rows)
+    if a.dtype.kind not in "fiu":
+        raise ValueError("tyre_params must be numeric, got dtype %s" % a.dtype)
+    a = np.ascontiguousarray(a, np.float64)
+    if a.shape != (B, _ffi.TYRE_WORDS):
+        raise ValueError("tyre_params has shape %s, expected (%d, %d) = (B, [kind B C c_f])" % (a.shape, B, _ffi.TYRE_WORDS))
+    bad = np.argwhere(np.concatenate([~np.isin(a[:, :1], (0.0, 1.0)), ~(np.isfinite(a[:, 1:]) & (a[:, 1:] >= 0))], axis=1))
+    if bad.size:
+        b, i = bad[0]
+        raise ValueError("tyre_params: vehicle %d: %s = %g (kind must be 0 or 1; B, C, c_f finite and >= 0)" % (b, TYRE_WORDS[i], a[b, i]))
+    return a
+
+
+def tyre_params(B, kind=1, B_=PACEJKA[1], C=PACEJKA[2], c_f=PACEJKA[3]):
+    """[B, 4] tyre rows [kind, B, C, c_f]: the launch file's Pacejka tyre by default, any word overridden by a scalar or a [B]
+    array (the curve's B is spelt ``B_``), e.g. tyre_params(B, kind=np.arange(B) % 2) for an A/B inside one fleet."""
+    B = int(B)
+    if B < 1:
+        raise ValueError("B must be >= 1")
+    out = np.empty((B, _ffi.TYRE_WORDS))
+    for i, (k, v) in enumerate(zip(TYRE_WORDS, (kind, B_, C, c_f))):
+        v = np.asarray(v, np.float64)
+        if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != B):
+            raise ValueError("%s must be a scalar or have %d entries, got shape %s" % (k, B, v.shape))
+        out[:, i] = v
+    return check_tyre_params(out, B)
+
+
+def pacejka(alpha, m, row=PACEJKA):
+    """The lateral force of tyre row [kind, B, C, c_f] at slip angle alpha for a vehicle of mass m: Simulator.pacejka's
+    D sin(C arctan(B alpha)), D = c_f m g / 2 in the reference's association (kind is not read: this is the curve)."""
+    _, Bq, Cq, cf = (float(v) for v in row)
+    D = cf * m * 9.81 / 2
+    return D * np.sin(Cq * np.arctan(Bq * np.asarray(alpha, np.float64)))
+
+
+def sample_tyre_params(B, seed, spread=None, kind=1, offset=0):
+    """[B, 4] rows: the launch file's Pacejka words times independent uniform factors in [1 - s, 1 + s], s = spread[word] (dict over
+    "B", "C", "c_f"; None: DEFAULT_TYRE_SPREAD), with ``kind`` (scalar or [B]) as given.  Seeded per vehicle like
+    sample_plant_params: shard k of a sharded fleet takes sample_tyre_params(n, seed, offset=k * n)."""
+    B, offset = int(B), int(offset)
+    spread = DEFAULT_TYRE_SPREAD if spread is None else dict(spread)
+    unknown = set(spread) - set(TYRE_WORDS[1:])
+    if unknown:
+        raise TypeError("unknown tyre word(s) %s (words: %s)" % (sorted(unknown), ", ".join(TYRE_WORDS[1:])))
+    for k, s in spread.items():
+        if not (np.isfinite(s) and 0 <= s < 1):
+            raise ValueError("spread of %s must be in [0, 1), got %r" % (k, s))
+    base = tyre_params(B, kind=kind)
+    for i, k in enumerate(TYRE_WORDS):
+        if k in spread:                   # (streams keyed apart from the plant rows': the third key word)
+            u = np.random.default_rng([int(seed), i, 1]).uniform(-1.0, 1.0, offset + B)[offset:]
+            base[:, i] *= 1.0 + float(spread[k]) * u
+    return check_tyre_params(base, B)

@@ -836,6 +836,47 @@ int  lpvmpc_tunings_read(lpvmpc_handle *h, int32_t *B, double *rows);
 int  lpvmpc_tuning_from_config(const lpvmpc_config *cfg, double *row);
 int  lpvmpc_tuning_device_row(int32_t kind, const double *row, double *dev);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Tyre model: every vehicle of a lap-0 fleet or a race steps the simulated plant with a tyre row of its own next to its plant row.
+ * The reference's simulator ships two tyres: the linear one that Simulator.f uses (FyF = 60 * a_F, SIM:174-175) and
+ * Simulator.pacejka (SIM:202-205), whose two calls in f are commented out (SIM:172-173) and whose parameters the launch file sets
+ * (simulator/B = 6.0, simulator/C = 1.6, simulator/c_f = 0.8).  The controllers, the planner and the estimator keep their linear
+ * model.  All entry points here are new; the calls above keep their behaviour and refusals.
+ *
+ * Host layout: tyre_params [B][LPVMPC_TYRE_WORDS] = {kind, B, C, c_f} per vehicle.
+ *   kind 0: the linear tyre of the vehicle's plant row, FyF = Cf * aF, FyR = Cr * aR; B, C, c_f are ignored (stored and read back).
+ *     A kind 0 vehicle computes what it computes in the _vehicles call, word for word.
+ *   kind 1: Pacejka on both axles, Fy = D * sin(C * atan(B * a)) with D = ((c_f * m) * 9.81) / 2 and m the mass of the vehicle's plant
+ *     row.  Slip angles and the |vx| > 0.2 gate are Simulator.f's.
+ *   tyre_params == NULL: kind 0 for every vehicle.
+ * kind is per vehicle: one fleet may mix both.  plant_params, act, delay_a, delay_df: as in the _vehicles calls.
+ * Refused with LPVMPC_E_ARG, nothing started or allocated and a running fleet or race left as it is: kind other than exactly 0 or 1,
+ * a non-finite or negative B, C or c_f, and everything the _vehicles calls refuse.  The rows belong to the fleet or race:
+ * lpvmpc_cl_release frees them.  lpvmpc_cascade_init keeps the linear tyre (not extended here). */
+#define LPVMPC_TYRE_WORDS 4
+/* lpvmpc_plant_step_vehicles_batch with a tyre row per vehicle */
+int  lpvmpc_plant_step_tyres_batch(lpvmpc_handle *h, int32_t B, double *state, double *act_state, const double *u,
+                                   int32_t n_sub, double dt_sim, double mu_sim, const lpvmpc_actuator_config *act,
+                                   const int32_t *delay_a, const int32_t *delay_df, const double *plant_params,
+                                   const double *tyre_params);
+/* lpvmpc_cl_init_vehicles with a tyre row per vehicle */
+int  lpvmpc_cl_init_tyres(lpvmpc_handle *h, int32_t B, const double *plant0, double half_width, double slack, int32_t q9_swap,
+                          int32_t n_sub, double dt_sim, double mu_sim, const lpvmpc_actuator_config *act,
+                          const int32_t *delay_a, const int32_t *delay_df, const double *plant_params, const double *tyre_params);
+/* lpvmpc_race_init_vehicles with a tyre row per vehicle */
+int  lpvmpc_race_init_tyres(lpvmpc_handle *path, lpvmpc_handle *tt, lpvmpc_handle *planner, int32_t B,
+                            const double *plant0, const int32_t *half_track0, const lpvmpc_race_config *cfg,
+                            const struct lpvmpc_observer_config *obs, const lpvmpc_actuator_config *act,
+                            const int32_t *delay_a, const int32_t *delay_df, const double *plant_params, const double *tyre_params);
+/* the rows [B][LPVMPC_TYRE_WORDS] of the fleet or race that h runs (the path handle, for a race), started by the two calls above
+ * (synchronises); lpvmpc_plant_params_read returns its plant rows. */
+int  lpvmpc_tyre_params_read(lpvmpc_handle *h, double *tyre_params);
+/* the curve alone, on the device: force [B] = the lateral force of tyre row b at slip angle alpha [B] for a vehicle of mass m [B]
+ * (finite, > 0).  A kind 0 row has no stiffness of its own here and gives Simulator.f's 60 * alpha.  Refused while the handle runs a
+ * fleet, cascade or race, like the other batch calls. */
+int  lpvmpc_tyre_force_batch(lpvmpc_handle *h, int32_t B, const double *tyre_params, const double *m, const double *alpha,
+                             double *force);
+
 #ifdef __cplusplus
 }
 #endif

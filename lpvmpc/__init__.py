@@ -11,11 +11,11 @@ from ._ffi import LpvMpcError, STATUS_TEXT  # noqa: E402,F401
 from .observer import GainScheduledLPVObserver, observer_config, observer_vertex_gains  # noqa: E402,F401
 from .track import Map  # noqa: E402,F401
 from .actuator import actuator_config, controller_delay, delay_steps  # noqa: E402,F401
-from .plant import plant_params, sample_plant_params  # noqa: E402,F401
+from .plant import plant_params, sample_plant_params, sample_tyre_params, tyre_params  # noqa: E402,F401
 from .model import model_params, sample_model_params  # noqa: E402,F401
 from .tuning import check_tuning_rows, sample_tunings, tuning_rows  # noqa: E402,F401
 
 __all__ = ["BatchedSolver", "PathFollowingLPV_MPC", "LPV_MPC_Planner", "PlannerHandoff", "body_frame_errors", "handoff_operators",
            "Map", "LpvMpcError", "STATUS_TEXT", "GainScheduledLPVObserver", "observer_config", "observer_vertex_gains", "RaceFleet",
-           "actuator_config", "controller_delay", "delay_steps", "plant_params", "sample_plant_params",
+           "actuator_config", "controller_delay", "delay_steps", "plant_params", "sample_plant_params", "tyre_params", "sample_tyre_params",
            "model_params", "sample_model_params", "tuning_rows", "sample_tunings", "check_tuning_rows"]

@@ -24,8 +24,12 @@ process loads one build); medians, each configuration's spread over the alternat
 vehicle of the three engines (the cost of the binding: one 512-byte row per workgroup at set-up), and sampled rows on all three
 (tuning.sample_tunings, seed 1, weights +-30 %: other QPs, so other iteration counts -- a launch ends in its slowest instance; reported,
 not a regression), and, with --parent-lib FILE, unbound on that build.
-Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator | --actuator | --record | --plant-params | --models | --tunings
-       [--parent-lib FILE] [--reps R]] [--out FILE]"""
+--tyres: the same protocol for the tyre model: the lpvmpc_race_init_vehicles race with nominal rows (the baseline), the
+lpvmpc_race_init_tyres race with kind 0 rows (the tyre forms of the kernels on the linear tyre) and with the launch file's Pacejka tyre on
+every vehicle (other trajectories, so its in-phase lines also carry the solvers' changed iteration counts), and, with --parent-lib FILE,
+the _vehicles race on that build.
+Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator | --actuator | --record | --plant-params | --models | --tunings |
+       --tyres [--parent-lib FILE] [--reps R]] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -56,7 +60,8 @@ def timed(tick, read, K):
     return (time.perf_counter() - t0) * 1e3 / K
 
 
-def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, record=False, plant_params=None, model_params=None, tunings=None):
+def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, record=False, plant_params=None, model_params=None, tunings=None,
+             tyre_params=None):
     path, tt, plan = engines(mp, sd)
     if tunings is not None:                                           # "own": each handle's own row; "sampled": sample_tunings around it
         from lpvmpc import tuning
@@ -67,7 +72,7 @@ def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, rec
         for e in (path, tt, plan):
             e.set_model_params(model_params)
     path.race_init(tt, plan, plant0, half_track0=half, laps=5, half_width=mp.halfWidth, slack=mp.slack, estimator=estimator,
-                   actuator=actuator, plant_params=plant_params)
+                   actuator=actuator, plant_params=plant_params, **({} if tyre_params is None else {"tyre_params": tyre_params}))
     path.race_tick(warm)
     if record:
         path.race_record(K, 1)
@@ -92,6 +97,7 @@ def main():
     ap.add_argument("--plant-params", action="store_true")
     ap.add_argument("--models", action="store_true")
     ap.add_argument("--tunings", action="store_true")
+    ap.add_argument("--tyres", action="store_true")
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--models-child", nargs=4, default=None, help=argparse.SUPPRESS)      # lib regime B bind: one run of --models
     a = ap.parse_args()
@@ -101,6 +107,9 @@ def main():
         return models_main(a)
     if a.tunings:
         return models_main(a, [("unbound", "liblpvmpc.so", 0), ("own rows bound", "liblpvmpc.so", 2), ("sampled rows bound", "liblpvmpc.so", 3)])
+    if a.tyres:
+        return models_main(a, [("vehicles, nominal rows", "liblpvmpc.so", 4), ("tyres, kind 0 rows", "liblpvmpc.so", 5),
+                               ("tyres, Pacejka", "liblpvmpc.so", 6)], parent=("parent, vehicles", 4))
     if a.plant_params:
         return plant_params_main(a)
     if a.record:
@@ -269,16 +278,19 @@ def models_child(a):
     import lpvmpc
     mp = lpvmpc.Map("L_shape", 0.2)
     plant0, half, warm = _models_starts(int(B))[regime]
-    rows = lpvmpc.model_params(int(B)) if int(bind) == 1 else None                # bind: 0 nothing, 1 nominal model rows, 2 / 3 tuning rows
-    ms, _vps, ph = race_run(mp, plant0, half, warm, a.ticks, model_params=rows, tunings={2: "own", 3: "sampled"}.get(int(bind)))
+    rows = lpvmpc.model_params(int(B)) if int(bind) == 1 else None                # bind: 0 nothing, 1 nominal model rows, 2 / 3 tuning rows,
+    tyres = {5: lpvmpc.tyre_params(int(B), kind=0), 6: "pacejka"}.get(int(bind))   # 4 nominal plant rows (_vehicles), 5 / 6 tyre rows on top
+    ms, _vps, ph = race_run(mp, plant0, half, warm, a.ticks, model_params=rows, tunings={2: "own", 3: "sampled"}.get(int(bind)),
+                            plant_params="nominal" if int(bind) >= 4 else None, tyre_params=tyres)
     print("MODELS_RUN %.6f %s" % (ms, ",".join(str(int(x)) for x in ph)), flush=True)
 
 
-def models_main(a, cfgs=None):
+def models_main(a, cfgs=None, parent=("parent, unbound", 0)):
     import subprocess
     cfgs = list(cfgs or [("unbound", "liblpvmpc.so", 0), ("nominal rows bound", "liblpvmpc.so", 1)])
+    base = cfgs[0][0]                                                                 # the differences are against the first configuration
     if a.parent_lib:
-        cfgs.append(("parent, unbound", a.parent_lib, 0))
+        cfgs.append((parent[0], a.parent_lib, parent[1]))
     lines = []
     for B in [int(x) for x in a.sizes.split(",")]:
         for regime in ("lap0", "inphase"):
@@ -290,11 +302,11 @@ def models_main(a, cfgs=None):
                                           str(bind)], check=True, capture_output=True, text=True, timeout=600).stdout
                     f = [l for l in out.splitlines() if l.startswith("MODELS_RUN")][-1].split()
                     ms[k].append(float(f[1])); ph[k] = f[2]
-            m0 = float(np.median(ms["unbound"]))
+            m0 = float(np.median(ms[base]))
             for k, _, _ in cfgs:
                 m = float(np.median(ms[k]))
-                lines.append("%-8s B=%5d  %-19s %.3f ms/tick (runs %s, spread %.3f, phases [%s])  vs unbound %+.3f ms/tick"
-                             % (regime, B, k, m, " ".join("%.3f" % x for x in ms[k]), max(ms[k]) - min(ms[k]), ph[k], m - m0))
+                lines.append("%-8s B=%5d  %-22s %.3f ms/tick (runs %s, spread %.3f, phases [%s])  vs %s %+.3f ms/tick"
+                             % (regime, B, k, m, " ".join("%.3f" % x for x in ms[k]), max(ms[k]) - min(ms[k]), ph[k], base.split(",")[0], m - m0))
                 print(lines[-1], flush=True)
     if a.out:
         with open(a.out, "w") as f:

@@ -10,7 +10,11 @@ racing laps (RaceFleet.lap_stats, CMAIN:101-106).
 nominal (default: today's run, same output), plant (each vehicle's model is its plant row: the matched experiment) or noisy:REL
 (the plant row times an independent uniform factor in [1 - REL, 1 + REL] per field: an identification error).  The nominal-car
 baseline race keeps the nominal model.
-Usage: tools/robustness_sweep.py [--B 8192] [--laps 2] [--seed 1] [--max-ticks 3000] [--model nominal|plant|noisy:REL] [--out FILE]"""
+--tyre selects the plants' tyre (lpvmpc_race_init_tyres, RaceFleet(tyre_params=...)): linear (default: today's run, same output:
+the plant rows' Cf, Cr) or pacejka (the launch file's Simulator.pacejka on every vehicle, the baseline race included: a tyre that
+saturates; the rows' Cf, Cr are then not read, so their bins show no trend of their own).  Every model keeps the linear tyre.
+Usage: tools/robustness_sweep.py [--B 8192] [--laps 2] [--seed 1] [--max-ticks 3000] [--model nominal|plant|noisy:REL]
+       [--tyre linear|pacejka] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -28,6 +32,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--max-ticks", type=int, default=3000)
     ap.add_argument("--model", default="nominal")
+    ap.add_argument("--tyre", default="linear", choices=("linear", "pacejka"))
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.model not in ("nominal", "plant") and not a.model.startswith("noisy:"):
@@ -52,8 +57,10 @@ def main():
         model_text = "take each vehicle's plant row times an independent uniform factor in [%g, %g] per field as its model (--model %s)" % (1 - rel, 1 + rel, a.model)
 
     def race(r, m=None):
-        f = lpvmpc.RaceFleet(mp, plant0, laps=a.laps, half_track0=1, plant_params=r, model_params=m)
+        f = lpvmpc.RaceFleet(mp, plant0, laps=a.laps, half_track0=1, plant_params=r, model_params=m,
+                             tyre_params="pacejka" if a.tyre == "pacejka" else None)
         assert np.array_equal(f.plant_params(), r)
+        assert a.tyre == "linear" or np.array_equal(f.tyre_params(), lpvmpc.tyre_params(B))
         assert m is None or np.array_equal(f.model_params(), m)
         f.record(1, 1 << 20)                                          # statistics of every tick; one record kept
         t0, n = time.perf_counter(), 0
@@ -73,8 +80,9 @@ def main():
     rmse = st["rmse_ey"][:, 1:a.laps + 1]
     fin, lost = ph == 2, ph == 3
     fin_nom = ph_nom == 2
-    lines = ["# tools/robustness_sweep.py --B %d --laps %d --seed %d on one MI355X: one race, rows from sample_plant_params(B, %d) with spreads %s"
-             % (B, a.laps, a.seed, a.seed, ", ".join("%s %+.0f %%" % (k, 100 * v) for k, v in spread.items())),
+    lines = ["# tools/robustness_sweep.py --B %d --laps %d --seed %d%s on one MI355X: one race, rows from sample_plant_params(B, %d) with spreads %s"
+             % (B, a.laps, a.seed, " --tyre pacejka" if a.tyre == "pacejka" else "", a.seed,
+                ", ".join("%s %+.0f %%" % (k, 100 * v) for k, v in spread.items())),
              "# the controllers and the planner %s." % model_text,
              "# %d ticks (%.1f s wall); all vehicles: %.1f %% finished, %.1f %% lost, %.1f %% still running; racing lap time median %.3f s, "
              "p90 %.3f s; RMSE_ey median %.4f m" % (ticks, wall, 100 * fin.mean(), 100 * lost.mean(), 100 * (ph < 2).mean(),
