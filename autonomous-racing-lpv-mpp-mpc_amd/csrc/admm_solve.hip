@@ -2528,12 +2528,6 @@ struct Solver {
         es_[0].wtd = ZTd[o.e0];
         if (two_elems()) es_[1].wtd = ZTd[o.e1c];
     }
-    // the state to the arrays (a loop that ends on a plain iteration; z_d = b behind any update)
-    __device__ __forceinline__ void state_flush() {
-        const Own o = own();
-        X[o.e0] = es_[0].x; Zd[o.e0] = dyn_bound(o.e0); Yd[o.e0] = es_[0].yd; Zb[o.e0] = es_[0].zb; Yb[o.e0] = es_[0].yb;
-        if (two_elems()) { X[o.e1c] = es_[1].x; Zd[o.e1c] = dyn_bound(o.e1c); Yd[o.e1c] = es_[1].yd; Zb[o.e1c] = es_[1].zb; Yb[o.e1c] = es_[1].yb; }
-    }
     // right-hand side of the thread's elements from the state (rhs_load without the loads of X[e] and ZTd[e])
     __device__ __forceinline__ RhsIn rhs_load_s(int e, const LaneC &lc, const ElState &st) const {
         RhsIn r;
@@ -2607,7 +2601,7 @@ struct Solver {
         q.wi = c_ == 0 ? rinv : (c_ == 1 ? rinv_eq : 1.0 / kRhoMin);
         return q;
     }
-    // want: a termination check or a rho update follows -- the state and the deltas go to the arrays as well
+    // want: a termination check or a rho update follows, or the loop ends -- the state and the deltas go to the arrays as well
     template <bool FIRST>
     __device__ __forceinline__ void update_s(double alpha, double oma, bool want) {
         const LaneC lc = lane_consts();
@@ -3387,10 +3381,14 @@ struct Solver {
         const int max_iter = cfg.max_iter, chk_every = cfg.check_termination > 0 ? cfg.check_termination : 0;
         const int adp_every = (cfg.adaptive_rho && cfg.adaptive_rho_interval > 0) ? cfg.adaptive_rho_interval : 0;
         const double rho_tol = cfg.rho_tol;
-        int to_chk = resuming ? to_chk0 : chk_every, to_adp = resuming ? to_adp0 : adp_every;
+        // OSQP's closing update_info / check_termination behind a loop that ends on an unchecked iteration (max_iter off the check grid,
+        // check_termination 0) is a check like the others here: the counter to the next check never reaches past max_iter, so the last
+        // iteration is always a checked one -- the element phase files delta_x / delta_y, which the infeasibility tests read, and the
+        // register state on checked iterations only.  (A rho update that falls on such a last iteration follows the check, as on the grid.)
+        const int chk_cap = chk_every > 0 ? chk_every : 0x7fffffff;
+        int to_chk = resuming ? to_chk0 : min(chk_cap, max_iter), to_adp = resuming ? to_adp0 : adp_every;
         const int defer_after = a.defer_after > 0 ? (resuming ? iter0 - 1 + a.defer_after : a.defer_after) : 0;     // park at the first check at or beyond this iteration
         constexpr bool reg_state = kRegState;
-        bool filed = true, ran = false;                           // (kRegState) the last iteration filed the state in the arrays; an iteration has run
         if constexpr (kRegState && !TAIL) { if (reg_state) state_load(); }
         if constexpr (TAIL) {
             // ---- the tail kernel's loop: dense product, fused element phase; checks evaluated beside the iterations (see tail_fused).
@@ -3417,9 +3415,9 @@ struct Solver {
             checked = true;
         } else
         for (iter = iter0; iter <= max_iter; ++iter) {
-            checked = chk_every > 0 && --to_chk == 0;
+            checked = --to_chk == 0;
             const bool adapt = adp_every > 0 && --to_adp == 0;
-            if (checked) to_chk = chk_every;
+            if (checked) to_chk = min(chk_cap, max_iter - iter);
             if (adapt) to_adp = adp_every;
 #if defined(LPVMPC_STAMPS) && LPVMPC_STAMPS != 5
             tlast = __builtin_amdgcn_s_memtime();
@@ -3445,7 +3443,6 @@ struct Solver {
                 STAMP(0);
                 kkt_solve_mf(m);
                 if (iter == iter0) update_s<true>(alpha, oma_u, checked || adapt); else update_s<false>(alpha, oma_u, checked || adapt);
-                filed = checked || adapt; ran = true;
             } else if constexpr (kMf) {
                 build_rhs<false>(sigma);
                 const MfLane m = mf_lane();     // (in front of the barrier: the sweeps' lane constants form while the stores drain)
@@ -3483,13 +3480,8 @@ struct Solver {
             }
         }
         STAMP5(4);
-        if constexpr (kRegState) { if (reg_state && ran && !filed) { state_flush(); sync(); } }      // (a loop that ends on a plain iteration: max_iter off the check grid)
         if constexpr (kUniScalars && !TAIL) launder_ids();      // (the post-loop code's addresses are formed behind the loop: see launder_ids)
         if (iter > max_iter) iter = max_iter;
-        if (!checked) {
-            R = residuals(X, Zd, Zb, Yd, Yb); pri_res = R.pri; dua_res = R.dua;
-            status = check_termination(R, false);
-        }
         const bool has_sol = !(status == LPVMPC_PRIMAL_INFEASIBLE_ || status == LPVMPC_PRIMAL_INFEASIBLE_INACC_ ||
                                status == LPVMPC_DUAL_INFEASIBLE_ || status == LPVMPC_DUAL_INFEASIBLE_INACC_ ||
                                status == LPVMPC_NON_CVX_);

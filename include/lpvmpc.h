@@ -90,7 +90,12 @@ typedef struct lpvmpc_config {
     double  plan_xmax[5];
     double  plan_umin[2];    /* [-0.249 -0.7] */
     double  plan_umax[2];    /* [ 0.249  2.0] */
-    /* OSQP settings (defaults of the 0.6.x series; the reference passes only polish=True) */
+    /* OSQP settings (defaults of the 0.6.x series; the reference passes only polish=True).  The loop schedule is OSQP's: an iteration
+     * that is a multiple of check_termination is checked (0: never inside the loop), one that is a multiple of adaptive_rho_interval
+     * may change rho, and a run that reaches max_iter on an unchecked iteration gets OSQP's closing update and check (here: the last
+     * iteration is always a checked one).  adaptive_rho_interval = 0 means NO ADAPTATION here, the same as adaptive_rho = 0: in OSQP 0
+     * asks for an interval chosen from the measured set-up time, the one default that cannot be reproduced (the default here is 25).
+     * polish = 0: the ADMM iterate is returned, polish flags 0. */
     double  rho, sigma, alpha, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf;
     double  polish_delta, adaptive_rho_tolerance;
     int32_t max_iter, check_termination, scaling, adaptive_rho, adaptive_rho_interval;

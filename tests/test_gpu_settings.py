@@ -37,6 +37,19 @@ SETTINGS = {
     "combined": dict(alpha=1.2, sigma=1e-5, scaling=5, polish_refine_iter=1, adaptive_rho_tolerance=3.0),
 }
 SWAPS = [("eps_a1e-4_r1e-2", "eps_a1e-2_r1e-4"), ("inf_p1e-6_d1e-2", "inf_p1e-2_d1e-6")]
+# the loop schedule (tests/test_gpu_schedule.py): when Solver::run checks, adapts rho, stops and polishes.  At the defaults (25 / 25 /
+# 4000 / on / on) the check grid, the rho grid and the cap coincide; each case here takes them apart another way.
+SCHEDULES = {
+    "chk1": dict(check_termination=1),
+    "chk7_adp10": dict(check_termination=7, adaptive_rho_interval=10),
+    "chk10_adp7": dict(check_termination=10, adaptive_rho_interval=7),
+    "adp40": dict(adaptive_rho_interval=40),
+    "chk40_adp15_max130": dict(check_termination=40, adaptive_rho_interval=15, max_iter=130),
+    "chk0_max90": dict(check_termination=0, max_iter=90),
+    "max60": dict(max_iter=60), "max100": dict(max_iter=100), "max1": dict(max_iter=1),
+    "adp0": dict(adaptive_rho_interval=0), "norho": dict(adaptive_rho=0), "nopolish": dict(polish=0),
+}
+SCHEDULE_SWAPS = [("chk7_adp10", "chk10_adp7")]
 
 # workload name -> (kind, builder); B ragged.  The planner N = 30 forms selected by batch size (two-wave MFMA at B >= 512, the
 # global-scalings kernel of variant 7 at B > 512) run "plan30" tiled 8 times (536 instances, the tiled oracle).
@@ -79,11 +92,18 @@ def workload(name):
     return WORKLOADS[name][0], _W[name]
 
 
+def settings_of(case):
+    """The settings dict of a case of SETTINGS or SCHEDULES (None: the defaults)."""
+    if case is None:
+        return None
+    return SETTINGS[case] if case in SETTINGS else SCHEDULES[case]
+
+
 def oracle(name, case):
     """tick_batch_qp of one workload under one settings case (None: defaults), computed once and shared by every route."""
     if (name, case) not in _ORC:
         kind, w = workload(name)
-        _ORC[(name, case)] = O.tick_batch_qp(w, kind, settings=SETTINGS.get(case), nthreads=NTHREADS, qps=_QPS[name])
+        _ORC[(name, case)] = O.tick_batch_qp(w, kind, settings=settings_of(case), nthreads=NTHREADS, qps=_QPS[name])
     return _ORC[(name, case)]
 
 
@@ -97,7 +117,7 @@ def tiled_ref(ref, n):
     return {k: np.concatenate([v] * n) for k, v in ref.items()}
 
 
-def device_solve(w, variant=0, defer_after=0, params=None, **settings):
+def device_solve(w, variant=0, defer_after=0, params=None, defer_pool=None, **settings):
     import lpvmpc
     d = int(np.asarray(w["u_old"]).reshape(w["x0"].shape[0], -1).shape[1] - 2) if w["kind"] == "controller" else 0
     eng = lpvmpc.BatchedSolver(w["kind"], w["N"], w["dt"], w["Q"], w["R"], w["dR"], L_cf=w["L_cf"], track=w["track"], params=params,
@@ -106,7 +126,7 @@ def device_solve(w, variant=0, defer_after=0, params=None, **settings):
     if defer_after:
         B = w["x0"].shape[0]
         eng.reserve(B)
-        eng.set_option("defer_after", defer_after); eng.set_option("defer_budget", -1); eng.set_option("defer_pool", B)
+        eng.set_option("defer_after", defer_after); eng.set_option("defer_budget", -1); eng.set_option("defer_pool", defer_pool or B)
     out = eng.solve(w["x0"], w["u_prev"], w["vel_ref"], w["curv_s"], w["u_old"], w["max_ey"], w["cf_new"], w["lap"])
     parked = eng.defer_stats()[0] if defer_after else 0
     eng.close()
@@ -134,7 +154,7 @@ BEYOND_BARS = {("rhotol2", "plan40"): ([23], "converged"), ("scaling0", "plan25"
 
 
 def _beyond_bars(case, name, kind, w, out, ref, js, rule):
-    st = SETTINGS[case]
+    st = settings_of(case)
     for j in js:
         assert int(out["status"][j]) == int(ref["status"][j]) and int(out["iters"][j]) == int(ref["iters"][j]), (case, name, j)
         du = float(np.max(np.abs(out["uPred"][j] - ref["uPred"][j])))
@@ -196,7 +216,7 @@ def test_polished_solutions_are_the_active_set_optimum(case):
     1e-5..1e-2 from it (so on both sides).  The rule: wherever the oracle's polished point is the optimum, the device's is too, on at
     least 30 instances per case; the others are counted.  Not run at polish_refine_iter = 0: there a polished point is the
     unrefined delta-regularised solve, never the optimum (none of 102 on the oracle side), and the matrix above covers it."""
-    st = SETTINGS[case]
+    st = settings_of(case)
     n = worst = off = 0
     for name in WORKLOADS:
         kind, w = workload(name)

@@ -97,9 +97,11 @@ def test_two_handles_on_two_host_threads():
         ins = dict(x0=t(w["x0"]), u_prev=t(w["u_prev"]), vel=t(w["vel_ref"]), curv=t(w["curv_s"]), u_old=t(w["u_old"]), mey=t(w["max_ey"]))
         outs = []
         for _ in range(rounds):
-            o = dict(xPred=torch.empty((B, N + 1, nx), dtype=torch.float64, device=dev), uPred=torch.empty((B, N, 2), dtype=torch.float64, device=dev),
-                     status=torch.zeros(B, dtype=torch.int32, device=dev), iters=torch.zeros(B, dtype=torch.int32, device=dev),
-                     resid=torch.zeros((B, 4), dtype=torch.float64, device=dev), polish=torch.zeros(B, dtype=torch.int32, device=dev))
+            with torch.cuda.stream(stream):      # the fills are ordered in front of the call on its own stream: on the thread's current (null) stream
+                                                 # they can be held up behind the other thread's work and land on the call's results
+                o = dict(xPred=torch.empty((B, N + 1, nx), dtype=torch.float64, device=dev), uPred=torch.empty((B, N, 2), dtype=torch.float64, device=dev),
+                         status=torch.zeros(B, dtype=torch.int32, device=dev), iters=torch.zeros(B, dtype=torch.int32, device=dev),
+                         resid=torch.zeros((B, 4), dtype=torch.float64, device=dev), polish=torch.zeros(B, dtype=torch.int32, device=dev))
             eng.solve_dev(B, ins["x0"], ins["u_prev"], ins["vel"], ins["curv"], ins["u_old"], ins["mey"], o["xPred"], o["uPred"], o["status"], o["iters"],
                           o["resid"], o["polish"], cf_new=w["cf_new"], lap=w["lap"], stream=stream.cuda_stream)
             outs.append(o)

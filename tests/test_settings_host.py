@@ -184,14 +184,16 @@ def test_osqp_settings_names():
         dict(delta=1e-8, alpha=1.2, scaling=3)
 
 
-# ---- non-vacuity of tests/test_gpu_settings.py, on the oracle side ---------------------------------------------------------------
+# ---- non-vacuity of tests/test_gpu_settings.py and tests/test_gpu_schedule.py, on the oracle side ------------------------------
 # share of the instances (over the GPU module's workloads) whose iteration count or solution words differ from the defaults'
 # (observed: sigma 24 %, the infeasibility tolerances 6 %, every other case 38-100 %; each bar is at most two thirds of the lowest
-# share observed for its cases)
-MIN_SHARE = {"sigma1e-4": 0.1, "inf_p1e-6_d1e-2": 0.025, "inf_p1e-2_d1e-6": 0.025}
+# share observed for its cases).  The schedule cases, of 623 instances: chk1 566 (91 %), chk7_adp10 611 (98 %), chk10_adp7 609 (98 %),
+# adp40 244 (39 %), chk40_adp15_max130, chk0_max90 and max1 623 (100 %), max60 265 (43 %), max100 214 (34 %), adp0 and norho 319
+# (51 %), nopolish 452 (73 %): the default bar holds for all but max100.
+MIN_SHARE = {"sigma1e-4": 0.1, "inf_p1e-6_d1e-2": 0.025, "inf_p1e-2_d1e-6": 0.025, "max100": 0.2}
 
 
-@pytest.mark.parametrize("case", list(G.SETTINGS))
+@pytest.mark.parametrize("case", list(G.SETTINGS) + list(G.SCHEDULES))
 def test_each_departure_changes_the_oracle(case):
     changed = total = 0
     for name in G.WORKLOADS:
@@ -204,13 +206,37 @@ def test_each_departure_changes_the_oracle(case):
     assert share >= MIN_SHARE.get(case, 0.25), (case, share)
 
 
-@pytest.mark.parametrize("a,b", G.SWAPS)
+@pytest.mark.parametrize("a,b", G.SWAPS + G.SCHEDULE_SWAPS)
 def test_swapped_pairs_are_told_apart(a, b):
     """eps_abs / eps_rel and eps_prim_inf / eps_dual_inf swapped change decisions: statuses or iteration counts.  The
-    infeasibility pair shows on the planner workloads' PRIMAL INFEASIBLE instances."""
+    infeasibility pair shows on the planner workloads' PRIMAL INFEASIBLE instances.  check_termination / adaptive_rho_interval
+    swapped (7 / 10 against 10 / 7): an instance stops on a multiple of its check interval."""
     n = 0
     for name in G.WORKLOADS:
         ra, rb = G.oracle(name, a), G.oracle(name, b)
         n += int(np.sum((ra["status"] != rb["status"]) | (ra["iters"] != rb["iters"])))
     print("%s vs %s: %d instances decide differently" % (a, b, n))
-    assert n >= {"eps_a1e-4_r1e-2": 250}.get(a, 20), n            # (observed: 544 and 42)
+    assert n >= {"eps_a1e-4_r1e-2": 250, "chk7_adp10": 300}.get(a, 20), n            # (observed: 544, 42 and 600)
+
+
+def test_interval_zero_is_adaptive_rho_off():
+    """adaptive_rho_interval = 0 means no adaptation here (include/lpvmpc.h; OSQP's time-based choice is not reproducible,
+    tests/test_oracle_osqp.py): the oracle's results under it equal those under adaptive_rho = 0 word for word, and differ from
+    the defaults' (test_each_departure_changes_the_oracle)."""
+    for name in G.WORKLOADS:
+        a, b = G.oracle(name, "adp0"), G.oracle(name, "norho")
+        assert set(a) == set(b)
+        for k in a:
+            assert np.array_equal(a[k], b[k], equal_nan=True), (name, k)
+
+
+def test_schedule_cases_are_settings():
+    """Every key of SCHEDULES is a setting of the handle and of the oracle, and each case departs from the defaults."""
+    from lpvmpc import _ffi
+    base = O.default_settings()
+    for case, st in G.SCHEDULES.items():
+        assert set(st) <= set(_ffi.SETTING_FIELDS) and O.osqp_settings(st) == st, case
+        assert any(getattr(base, k) != v for k, v in st.items()), case
+        assert G.settings_of(case) is st
+    assert G.settings_of(None) is None and G.settings_of("alpha1.0") is G.SETTINGS["alpha1.0"]
+    assert not set(G.SETTINGS) & set(G.SCHEDULES)
