@@ -2,7 +2,7 @@
 PathFollowingLPV_MPC / LPV_MPC_Planner classes).  Import as ``lpvmpc`` (alias package at the repo root)
 or via ``importlib.import_module("autonomous-racing-lpv-mpp-mpc_amd")``."""
 from .api import (BatchedSolver, LPV_MPC_Planner, PathFollowingLPV_MPC, PlannerHandoff, RaceFleet,  # noqa: F401
-                  body_frame_errors, handoff_operators)
+                  body_frame_errors, handoff_operators, observer_design_config)
 from ._ffi import LpvMpcError, STATUS_TEXT  # noqa: F401
 from .observer import GainScheduledLPVObserver, observer_config, observer_vertex_gains  # noqa: F401
 from .track import Map  # noqa: F401

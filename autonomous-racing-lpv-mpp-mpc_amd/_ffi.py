@@ -72,6 +72,11 @@ class ObserverConfig(C.Structure):
                 ("v_std", _d), ("n_bound", _d), ("gps_freq", _d), ("seed", C.c_uint64), ("vehicle_offset", C.c_int64)]
 
 
+class ObserverDesign(C.Structure):
+    """Mirror of ``struct lpvmpc_observer_design`` (include/lpvmpc.h)."""
+    _fields_ = [("lim_ls", _d * 12), ("lim_hs", _d * 12), ("Qo", _d * 36), ("Ro", _d * 25)]
+
+
 class RaceConfig(C.Structure):
     """Mirror of ``struct lpvmpc_race_config`` (include/lpvmpc.h)."""
     _fields_ = [("laps", _i), ("n_sub_lap0", _i), ("n_sub", _i * 3), ("q9_swap", _i), ("half_width", _d), ("slack", _d),
@@ -145,7 +150,9 @@ EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_d
            "lpvmpc_set_model_params", "lpvmpc_model_params_read",
            "lpvmpc_set_tunings", "lpvmpc_tunings_read", "lpvmpc_tuning_from_config", "lpvmpc_tuning_device_row",
            "lpvmpc_plant_step_tyres_batch", "lpvmpc_cl_init_tyres", "lpvmpc_race_init_tyres", "lpvmpc_tyre_params_read",
-           "lpvmpc_tyre_force_batch")
+           "lpvmpc_tyre_force_batch",
+           "lpvmpc_observer_default_design", "lpvmpc_observer_design_batch", "lpvmpc_set_observer_vehicles",
+           "lpvmpc_observer_vehicles_read", "lpvmpc_observer_step_vehicles_batch")
 
 _lib = None
 
@@ -301,7 +308,21 @@ def load():
         lib.lpvmpc_tyre_params_read.argtypes = [vp, vp]
         lib.lpvmpc_tyre_force_batch.argtypes = [vp, _i, vp, vp, vp, vp]
         for name in ("lpvmpc_plant_step_tyres_batch", "lpvmpc_cl_init_tyres", "lpvmpc_race_init_tyres", "lpvmpc_tyre_params_read",
-                     "lpvmpc_tyre_force_batch"):
+                     "lpvmpc_tyre_force_batch",
+           "lpvmpc_observer_default_design", "lpvmpc_observer_design_batch", "lpvmpc_set_observer_vehicles",
+           "lpvmpc_observer_vehicles_read", "lpvmpc_observer_step_vehicles_batch"):
+            getattr(lib, name).restype = C.c_int
+    except AttributeError:
+        pass
+    try:        # (nor the estimator's gain design)
+        lib.lpvmpc_observer_default_design.argtypes = [P(ObserverDesign)]
+        lib.lpvmpc_observer_default_design.restype = None
+        lib.lpvmpc_observer_design_batch.argtypes = [vp, _i, vp, P(ObserverDesign), vp, vp, vp]
+        lib.lpvmpc_observer_design_batch.restype = C.c_int
+        lib.lpvmpc_set_observer_vehicles.argtypes = [vp, _i, vp, vp, vp, P(ObserverDesign)]
+        lib.lpvmpc_observer_vehicles_read.argtypes = [vp, P(_i), vp, vp, vp]
+        lib.lpvmpc_observer_step_vehicles_batch.argtypes = [vp, _i, P(ObserverConfig), vp, vp, vp, vp, vp, vp, vp, vp]
+        for name in ("lpvmpc_set_observer_vehicles", "lpvmpc_observer_vehicles_read", "lpvmpc_observer_step_vehicles_batch"):
             getattr(lib, name).restype = C.c_int
     except AttributeError:
         pass
@@ -354,6 +375,12 @@ def default_observer_config():
     cfg = ObserverConfig()
     load().lpvmpc_observer_default_config(C.byref(cfg))
     return cfg
+
+
+def default_observer_design():
+    d = ObserverDesign()
+    load().lpvmpc_observer_default_design(C.byref(d))
+    return d
 
 
 def f64(a, shape=None, name="array"):

@@ -399,7 +399,9 @@ class BatchedSolver:
         "nominal": the nominal rows) selects lpvmpc_cl_init_vehicles: each vehicle's plant steps with its own row (lf, lr, m, Iz,
         Cf, Cr, mu; mu_sim is then ignored), the actuator all off unless ``actuator`` is given.  ``tyre_params`` [B, 4] = (kind, B,
         C, c_f) per vehicle, or "pacejka", selects lpvmpc_cl_init_tyres: the same fleet (plant_params None: nominal rows) whose kind
-        1 vehicles step with Simulator.pacejka on both axles."""
+        1 vehicles step with Simulator.pacejka on both axles.  With an estimator attached, a per-vehicle estimator bound to the
+        engine (``set_observer_vehicles``) runs in the fleets started with ``plant_params`` / ``tyre_params``; the other starts
+        refuse it."""
         p0 = f64(plant0).reshape(-1, 8)
         if plant_params is not None or tyre_params is not None:
             B = p0.shape[0]
@@ -492,6 +494,61 @@ class BatchedSolver:
             return e
         return e, (aux[:, :30].reshape(B, 6, 5), aux[:, 30:66].reshape(B, 6, 6), aux[:, 66:].reshape(B, 6, 2))
 
+    def observer_design(self, rows, lim_ls, lim_hs, Qo=None, Ro=None, want_iters=False, out=None):
+        """Vertex gains of the estimator designed on the device for each vehicle's model row: rows [B,7] = (lf, lr, m, Iz, Cf, Cr,
+        mu), the two SchedVars_Limits tables [6,2]; Qo [6,6] and Ro [5,5] default to ``observer.observer_vertex_gains``' weights.
+        Returns (L_ls [B,6,5,16], L_hs [B,6,5,16]) and with ``want_iters`` the Newton iterations [B,2,16] as well (-1 with NaN gains:
+        not converged).  ``out``: a pair of arrays to fill instead of new ones."""
+        rows = f64(rows).reshape(-1, _ffi.PLANT_WORDS)
+        B = rows.shape[0]
+        d = observer_design_config(lim_ls, lim_hs, Qo, Ro)
+        L_ls, L_hs = out if out is not None else (np.empty((B, 6, 5, 16)), np.empty((B, 6, 5, 16)))
+        iters = np.empty((B, 2, 16), np.int32) if want_iters else None
+        self._chk(self._lib.lpvmpc_observer_design_batch(self._h, B, ptr(rows), C.byref(d), ptr(L_ls), ptr(L_hs), ptr(iters)))
+        return (L_ls, L_hs, iters) if want_iters else (L_ls, L_hs)
+
+    def set_observer_vehicles(self, rows, L_ls=None, L_hs=None, design=None):
+        """Bind a per-vehicle estimator to this CONTROLLER engine (for a race: the path engine): model rows [B,7] and either the gain
+        tables ``L_ls``, ``L_hs`` [B,6,5,16] or ``design`` -- an ``observer_design_config`` result or a dict of its arguments
+        (lim_ls, lim_hs, Qo, Ro) -- for tables designed on the device straight into the binding.  The estimator of a fleet or race
+        started with per-vehicle rows (``cl_init(plant_params=...)``, ``race_init(plant_params=...)``) then runs each vehicle's
+        observer step on its own row and tables.  ``set_observer_vehicles(None)`` unbinds."""
+        if rows is None:
+            self._chk(self._lib.lpvmpc_set_observer_vehicles(self._h, 0, None, None, None, None))
+            return
+        rows = f64(rows).reshape(-1, _ffi.PLANT_WORDS)
+        B = rows.shape[0]
+        if isinstance(design, dict):
+            design = observer_design_config(**design)
+        L_ls = None if L_ls is None else f64(L_ls, (B, 6, 5, 16), "L_ls")
+        L_hs = None if L_hs is None else f64(L_hs, (B, 6, 5, 16), "L_hs")
+        self._chk(self._lib.lpvmpc_set_observer_vehicles(self._h, B, ptr(rows), ptr(L_ls), ptr(L_hs),
+                                                         None if design is None else C.byref(design)))
+
+    def observer_vehicles_read(self):
+        """The bound per-vehicle estimator as (rows [B,7], L_ls [B,6,5,16], L_hs [B,6,5,16]), or None when nothing is bound."""
+        n = C.c_int32(0)
+        self._chk(self._lib.lpvmpc_observer_vehicles_read(self._h, C.byref(n), None, None, None))
+        if n.value == 0:
+            return None
+        rows, L_ls, L_hs = np.empty((n.value, _ffi.PLANT_WORDS)), np.empty((n.value, 6, 5, 16)), np.empty((n.value, 6, 5, 16))
+        self._chk(self._lib.lpvmpc_observer_vehicles_read(self._h, C.byref(n), ptr(rows), ptr(L_ls), ptr(L_hs)))
+        return rows, L_ls, L_hs
+
+    def observer_step_vehicles(self, cfg, est, y, u, k, rows, L_ls, L_hs, want_aux=False):
+        """``observer_step`` with a model row [B,7] and gain tables [B,6,5,16] per instance (cfg's own tables are ignored)."""
+        e = f64(est).reshape(-1, 6).copy()
+        B = e.shape[0]
+        y = f64(y, (B, 5), "y"); u = f64(u, (B, 2), "u")
+        k = np.ascontiguousarray(np.broadcast_to(np.asarray(k, np.int32), (B,)))
+        rows = f64(rows, (B, _ffi.PLANT_WORDS), "rows"); L_ls = f64(L_ls, (B, 6, 5, 16), "L_ls"); L_hs = f64(L_hs, (B, 6, 5, 16), "L_hs")
+        aux = np.empty((B, _ffi.OBSERVER_AUX)) if want_aux else None
+        self._chk(self._lib.lpvmpc_observer_step_vehicles_batch(self._h, B, C.byref(cfg), ptr(e), ptr(y), ptr(u), ptr(k), ptr(aux),
+                                                                ptr(rows), ptr(L_ls), ptr(L_hs)))
+        if not want_aux:
+            return e
+        return e, (aux[:, :30].reshape(B, 6, 5), aux[:, 30:66].reshape(B, 6, 6), aux[:, 66:].reshape(B, 6, 2))
+
     # -- planner -> controller hand-off (SURVEY 8f row f2) ------------------------------------------------
     def handoff_setup(self, cfg=None):
         """Build the resampling / filtering operators for this PLANNER handle; returns M (samples per My_Planning array)."""
@@ -575,7 +632,9 @@ class BatchedSolver:
         ``plant_params`` [B, 7] (or "nominal") selects lpvmpc_race_init_vehicles: each vehicle's plant steps with its own row (lf,
         lr, m, Iz, Cf, Cr, mu; cfg mu_sim is then ignored), with or without ``estimator`` / ``actuator``.  ``tyre_params`` [B, 4] =
         (kind, B, C, c_f) per vehicle, or "pacejka", selects lpvmpc_race_init_tyres: the same race (plant_params None: nominal rows)
-        whose kind 1 vehicles step with Simulator.pacejka on both axles."""
+        whose kind 1 vehicles step with Simulator.pacejka on both axles.  With ``estimator``, a per-vehicle estimator bound to this
+        (path) engine (``set_observer_vehicles``) runs in the races started with ``plant_params`` / ``tyre_params``; the other
+        starts refuse it."""
         p0 = f64(plant0).reshape(-1, 8)
         B = p0.shape[0]
         c = _ffi.default_race_config()
@@ -715,6 +774,18 @@ class BatchedSolver:
                                                    dp(u_old), dp(max_ey), float(cf_new), int(lap), dp(xPred),
                                                    dp(uPred), dp(status), dp(iters), dp(resid), dp(polish),
                                                    C.c_void_p(int(stream))))
+
+
+def observer_design_config(lim_ls, lim_hs, Qo=None, Ro=None):
+    """An ``lpvmpc_observer_design``: the two limit tables [6,2] and the weights (None: the library's defaults)."""
+    d = _ffi.default_observer_design()
+    d.lim_ls[:] = f64(lim_ls, (6, 2), "lim_ls").ravel().tolist()
+    d.lim_hs[:] = f64(lim_hs, (6, 2), "lim_hs").ravel().tolist()
+    if Qo is not None:
+        d.Qo[:] = f64(Qo, (6, 6), "Qo").ravel().tolist()
+    if Ro is not None:
+        d.Ro[:] = f64(Ro, (5, 5), "Ro").ravel().tolist()
+    return d
 
 
 def _delay_array(v, B, name):
@@ -1060,11 +1131,15 @@ class RaceFleet(object):
     ``model_params`` is given: [B, 7] rows bound to the path, tt and planner engines (BatchedSolver.set_model_params), or the string
     "plant": each vehicle's model is its plant row (the matched experiment; the nominal plant rows where plant_params is None or
     "nominal").  ``path_tunings`` / ``tt_tunings`` / ``plan_tunings``: [B, 64] tuning rows (tuning.tuning_rows, tuning.sample_tunings)
-    bound to the path, tt and planner engine (BatchedSolver.set_tunings): vehicle b races with its own weights and limits."""
+    bound to the path, tt and planner engine (BatchedSolver.set_tunings): vehicle b races with its own weights and limits.
+    ``estimator_params`` (with ``estimator``): the estimator's model rows, [B, 7], "plant" (each vehicle's plant row) or "model" (the
+    rows ``model_params`` binds); the gain tables are designed on the device for each row, on the estimator configuration's limit
+    tables with ``estimator_design``'s weights (dict(Qo=, Ro=), default: observer_vertex_gains'), and bound to the path engine
+    (BatchedSolver.set_observer_vehicles).  None: the estimator keeps its own constants and the configuration's tables."""
 
     def __init__(self, track_map, plant0, laps=1, N=20, Np=40, half_track0=None, device=0, estimator=None, actuator=None,
                  steering_delay=0, delay_a=None, delay_df=None, plant_params=None, model_params=None, path_tunings=None,
-                 tt_tunings=None, plan_tunings=None, tyre_params=None, **options):
+                 tt_tunings=None, plan_tunings=None, tyre_params=None, estimator_params=None, estimator_design=None, **options):
         from .workloads import CTRL_TUNINGS, PLAN_L, PLAN_Q, PLAN_R, PLAN_dR
         race_keys = ("n_sub_lap0", "n_sub", "q9_swap", "plan_max_ey", "dt_sim", "mu_sim")
         race_opts = {k: v for k, v in options.items() if k in race_keys}
@@ -1098,6 +1173,25 @@ class RaceFleet(object):
             if rows is not None:
                 from .tuning import check_tuning_rows
                 e.set_tunings(check_tuning_rows(rows, f64(plant0).reshape(-1, 8).shape[0], e.kind))
+        if estimator_params is not None:
+            if estimator is None:
+                raise ValueError("estimator_params needs an estimator")
+            B = f64(plant0).reshape(-1, 8).shape[0]
+            if isinstance(estimator_params, str):
+                from .plant import plant_params as nominal_plant
+                if estimator_params == "plant":
+                    erows = (nominal_plant(B, self.path, race_opts.get("mu_sim", 0.05)) if plant_params is None or _is_nominal(plant_params)
+                             else _plant_rows(plant_params, B))
+                elif estimator_params == "model" and model_params is not None:
+                    erows = self.path.model_params_read()
+                else:
+                    raise ValueError("estimator_params must be [B, 7] rows, \"plant\" or (with model_params) \"model\", got %r" % (estimator_params,))
+            else:
+                erows = _plant_rows(estimator_params, B)
+            lim = np.array(estimator.lim_ls[:]).reshape(6, 2), np.array(estimator.lim_hs[:]).reshape(6, 2)
+            self.path.set_observer_vehicles(erows, design=observer_design_config(lim[0], lim[1], **(estimator_design or {})))
+            if plant_params is None and tyre_params is None:
+                plant_params = "nominal"                         # the starts that run the binding
         self.path.race_init(self.tt, self.planner, plant0, half_track0=half_track0, laps=laps, half_width=track_map.halfWidth,
                             slack=track_map.slack, estimator=estimator, actuator=actuator, delay_a=delay_a, delay_df=delay_df,
                             plant_params=plant_params, tyre_params=tyre_params, **race_opts)

@@ -143,6 +143,7 @@ extern "C" int lpvmpc_cascade_init(lpvmpc_handle *h, lpvmpc_handle *plan, int32_
     rc = lpvmpc_check_common(plan, B, "lpvmpc_cascade_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
     rc = lpvmpc_model_check(h, B, "lpvmpc_cascade_init"); if (rc) return rc;
     rc = lpvmpc_model_check(plan, B, "lpvmpc_cascade_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
+    if (h->obs_cfg) { rc = lpvmpc_observer_vehicles_check(h, B, h->obs_cfg.get(), false, "lpvmpc_cascade_init"); if (rc) return rc; }
     rc = lpvmpc_tuning_check(h, B, "lpvmpc_cascade_init"); if (rc) return rc;
     rc = lpvmpc_tuning_check(plan, B, "lpvmpc_cascade_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
     lpvmpc_cascade_free(h);

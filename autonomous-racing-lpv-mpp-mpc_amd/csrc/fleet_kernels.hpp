@@ -11,6 +11,10 @@
 // their code.  The same five have a tyre form (kTyre = true, always with kVeh = true): the argument is the plant table plus the
 // fleet's tyre table (TyrePlantCfg), and plant_step_at takes the vehicle's tyre row as well (linear or Pacejka, per vehicle).
 //
+// The two estimator kernels among them have a per-vehicle-estimator form on top (kObsVeh = true, always with kVeh = true): their
+// `gains` argument carries the binding's model rows and gain planes (ObsGainsArg<true>, observer_device.hpp), and each observer
+// step reads the vehicle's row and its own gain words; observer_vehicles.hip instantiates them, with and without the tyre table.
+//
 // One instantiation per translation unit: the .hip files above instantiate <false> only, actuator.hip <true> only, plant_params.hip
 // <true, true> only, tyre.hip <true, true, true> only.  With both
 // forms of a kernel in one translation unit LLVM compiles the plain form differently (other registers, other instructions); with
@@ -115,15 +119,16 @@ __global__ void __launch_bounds__(64) cl_command_plant_measure_kernel(const DevC
 // tick of a fleet; one kernel keeps local_position at a single call site, inlined).  mode 2 (the cascade, plain form only):
 // advance, then write the estimate in the plant's layout [x y vx vy 0 0 yaw psiDot] to local_next [B][8], which the cascade's
 // measurement kernels read in place of the plant; u_old is left to them
-template <bool kAct, bool kVeh = false, bool kTyre = false>
+template <bool kAct, bool kVeh = false, bool kTyre = false, bool kObsVeh = false>
 __global__ void __launch_bounds__(64) cl_command_plant_observe_kernel(const DevCfg *__restrict__ cp, int B, int N, const double *__restrict__ uPred,
                                                                       double *__restrict__ cmd, double *__restrict__ plant, PlantArg<kVeh, kTyre> pc,
                                                                       double hw, double slack, int q9_swap, double *__restrict__ local_next,
-                                                                      double *__restrict__ u_old, const double *__restrict__ gains,
+                                                                      double *__restrict__ u_old, typename ObsGainsArg<kObsVeh>::type gains,
                                                                       double *__restrict__ obs, ObsParams op, int mode, int sd, ActDev a) {
     static_assert((kAct || !kVeh) && (kVeh || !kTyre), "the per-vehicle forms are delayed forms, the tyre forms per-vehicle forms");
+    static_assert(kVeh || !kObsVeh, "the per-vehicle estimator runs in the per-vehicle forms");
     __shared__ double G[kObsGainWords];
-    if (mode != 0) obs_stage_gains(G, gains);
+    if (mode != 0) obs_stage_gains(G, obs_gain_words(gains));
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     double os[kObsStride];
@@ -151,7 +156,7 @@ __global__ void __launch_bounds__(64) cl_command_plant_observe_kernel(const DevC
             } else {
                 plant_step(pc, st, motor, servo);
             }
-            obs_substep(G, op, vid, os, st, servo, motor);
+            obs_substep<kObsVeh>(G, op, vid, os, st, servo, motor, obs_veh(gains), b);
         }
         if constexpr (kAct) { a.k[b] = k0 + pc.n_sub; a.servo[b] = sv; }
 #pragma unroll
@@ -275,12 +280,13 @@ __global__ void __launch_bounds__(64) race_command_plant_kernel(RaceDev r, Plant
 // race_command_plant_kernel with the estimator in the loop: per plant step, plant -> sensors -> observer (obs_substep, the schedule
 // of cl_command_plant_observe_kernel), then the estimate view that the next tick's measurements read.  A frozen vehicle (nstep 0)
 // advances neither the plant, its actuator nor its observer, so its noise keys (vid, step) depend on its own steps only.
-template <bool kAct, bool kVeh = false, bool kTyre = false>
-__global__ void __launch_bounds__(64) race_command_plant_observe_kernel(RaceDev r, PlantArg<kVeh, kTyre> pc, const double *__restrict__ gains,
+template <bool kAct, bool kVeh = false, bool kTyre = false, bool kObsVeh = false>
+__global__ void __launch_bounds__(64) race_command_plant_observe_kernel(RaceDev r, PlantArg<kVeh, kTyre> pc, typename ObsGainsArg<kObsVeh>::type gains,
                                                                         double *__restrict__ obs, ObsParams op, ActDev a) {
     static_assert((kAct || !kVeh) && (kVeh || !kTyre), "the per-vehicle forms are delayed forms, the tyre forms per-vehicle forms");
+    static_assert(kVeh || !kObsVeh, "the per-vehicle estimator runs in the per-vehicle forms");
     __shared__ double G[kObsGainWords];
-    obs_stage_gains(G, gains);
+    obs_stage_gains(G, obs_gain_words(gains));
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= r.B) return;
     const int src = r.src[b], n = r.nstep[b], N = r.N;
@@ -311,7 +317,7 @@ __global__ void __launch_bounds__(64) race_command_plant_observe_kernel(RaceDev 
         } else {
             plant_step(pc, st, motor, servo);
         }
-        obs_substep(G, op, vid, os, st, servo, motor);
+        obs_substep<kObsVeh>(G, op, vid, os, st, servo, motor, obs_veh(gains), b);
     }
     if constexpr (kAct) { a.k[b] = k0 + n; a.servo[b] = sv; }
 #pragma unroll

@@ -717,6 +717,7 @@ static int cl_init(lpvmpc_handle *h, int32_t B, const double *plant0, double hal
         return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: the fleet engines run the reference's steeringDelay = 0 (CMAIN:49); lpvmpc_cl_init_actuated runs delayed controllers");
     if (!plant0 || n_sub < 1 || !(dt_sim > 0)) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: bad argument");
     rc = lpvmpc_need_track(h, "lpvmpc_cl_init"); if (rc) return rc;
+    if (h->obs_cfg) { rc = lpvmpc_observer_vehicles_check(h, B, h->obs_cfg.get(), veh != nullptr, "lpvmpc_cl_init"); if (rc) return rc; }
     // the new fleet is built in f and installed after the last step that can fail: a failed call leaves no fleet (a refused
     // actuator configuration leaves the old one), never half of one
     Fleet f;
@@ -806,7 +807,15 @@ extern "C" int lpvmpc_cl_tick(lpvmpc_handle *h, int32_t n_ticks) {
         SolveArgs a{B, x0, h->d_AB, h->d_vel, h->d_uold, nullptr, h->d_xPred, h->d_uPred, h->d_status, h->d_iters, h->d_polish, h->d_resid,
                     nullptr, 0, x0_stride};
         int rc = lpvmpc_launch_solve_warm(h, a, st); if (rc) return rc;
-        if (h->cl_tyre.t && h->obs_state)
+        if (h->cl_tyre.t && h->obs_state && h->ov.L)
+            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_tyre_obsveh(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, tyre_plant(h->cl_veh, h->cl_tyre),
+                                                                            h->cl_hw, h->cl_slack, h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay,
+                                                                            lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, h->cl_act.d, st));
+        else if (h->cl_veh.d.p && h->obs_state && h->ov.L)
+            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_veh_obsveh(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_veh.d, h->cl_hw, h->cl_slack,
+                                                                           h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay,
+                                                                           lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, h->cl_act.d, st));
+        else if (h->cl_tyre.t && h->obs_state)
             HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_tyre(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, tyre_plant(h->cl_veh, h->cl_tyre),
                                                                      h->cl_hw, h->cl_slack, h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay,
                                                                      h->obs_gains, h->obs_state, h->obs_p, h->cl_act.d, st));

@@ -213,6 +213,11 @@ enum ObsSlot { OBS_EST = 0, OBS_Y = 6, OBS_GPS_X = 11, OBS_GPS_Y = 12, OBS_ENC_P
 constexpr int kObsStride = 18;
 // sensor std order = noise channel: psi, psiDot, x, y, v
 struct ObsParams { double dt, th_update, n_bound, std[5]; unsigned long long seed; long long voff; };
+// per-vehicle estimator (lpvmpc_set_observer_vehicles): the binding's model rows [kPlantWords][B] and gain planes [2][kObsTable][B]
+// (polytope, gain word, vehicle: the 64 lanes of a workgroup read consecutive words); with the gain words' pointer g, the `gains`
+// argument of the bound estimator kernels (observer_vehicles.hip)
+struct ObsVehDev { const double *rows = nullptr, *L = nullptr; int B = 0; };
+struct ObsVehGains : ObsVehDev { const double *g = nullptr; };
 hipError_t launch_observer_step(const double *gains, int B, double *est, const double *y, const double *u, const int32_t *k, double dt,
                                 double *aux, hipStream_t s);
 hipError_t launch_cl_observe_measure(const DevCfg *dcfg, int B, const double *obs, const double *cmd, double hw, double slack, int q9_swap,
@@ -287,5 +292,18 @@ hipError_t launch_race_command_plant_observe_veh(const RaceDev &r, const VehPlan
 hipError_t launch_race_command_plant_tyre(const RaceDev &r, const TyrePlantCfg &pc, const ActDev &a, hipStream_t s);
 hipError_t launch_race_command_plant_observe_tyre(const RaceDev &r, const TyrePlantCfg &pc, const double *gains, double *obs, const ObsParams &op,
                                                  const ActDev &a, hipStream_t s);
+// observer_vehicles.hip: the per-vehicle-estimator forms
+hipError_t launch_observer_step_vehicles(const ObsVehGains &v, int B, double *est, const double *y, const double *u, const int32_t *k, double dt,
+                                         double *aux, hipStream_t s);
+hipError_t launch_cl_command_plant_observe_veh_obsveh(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
+                                                      const VehPlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
+                                                      int sd, const ObsVehGains &gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s);
+hipError_t launch_cl_command_plant_observe_tyre_obsveh(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
+                                                       const TyrePlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
+                                                       int sd, const ObsVehGains &gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s);
+hipError_t launch_race_command_plant_observe_veh_obsveh(const RaceDev &r, const VehPlantCfg &pc, const ObsVehGains &gains, double *obs,
+                                                        const ObsParams &op, const ActDev &a, hipStream_t s);
+hipError_t launch_race_command_plant_observe_tyre_obsveh(const RaceDev &r, const TyrePlantCfg &pc, const ObsVehGains &gains, double *obs,
+                                                         const ObsParams &op, const ActDev &a, hipStream_t s);
 
 }  // namespace lpvmpc

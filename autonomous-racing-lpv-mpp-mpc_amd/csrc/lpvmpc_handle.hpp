@@ -111,8 +111,15 @@ struct TuneTable {                      // per-vehicle tunings (lpvmpc_set_tunin
     int tune_B = 0;
     std::vector<double> tune_rows;
 };
+struct ObsVehTable {                    // per-vehicle estimator (lpvmpc_set_observer_vehicles, observer_design_api.hip): the model rows [kPlantWords][ov_B] and
+    DevArena ov_mem;                    // the gain planes [2][kObsTable][ov_B] that the estimator kernels of a fleet or race started by the _vehicles / _tyres
+    lpvmpc::ObsVehDev ov{};             // calls take (ov.L null: the configuration's tables and the observer's own constants)
+    int ov_B = 0;
+    bool ov_designed = false;           // the tables were designed on the device, on the limit tables ov_lim (LS, HS)
+    double ov_lim[24] = {};
+};
 
-struct lpvmpc_handle : Workspace, Fleet, ObsState, ObsGains, ObsStage, DeferPools, Handoff, ModelTable, TuneTable {
+struct lpvmpc_handle : Workspace, Fleet, ObsState, ObsGains, ObsStage, DeferPools, Handoff, ModelTable, TuneTable, ObsVehTable {
     lpvmpc_config cfg{};
     DevCfg dev{};
     DevArena mem;                       // what lives as long as the handle: d_cfg, dstats, the device staging buffers
@@ -222,6 +229,12 @@ LPVMPC_HIDDEN int lpvmpc_model_check(lpvmpc_handle *h, int B, const char *who);
 // sets instances up (main launches, with or without riders; a resume pass reads no row) and refuses one the table does not cover
 LPVMPC_HIDDEN int lpvmpc_tuning_check(lpvmpc_handle *h, int B, const char *who);
 LPVMPC_HIDDEN int lpvmpc_solve_tune(lpvmpc_handle *h, lpvmpc::SolveArgs &a);
+// observer_design_api.hip: lpvmpc_observer_vehicles_check is called by every engine start with an estimator (obs non-null).  honoured: the
+// start runs the per-vehicle forms' kernels (the _vehicles / _tyres calls).  It refuses a bound handle on a start that does not honour
+// the binding, another B than the binding's, and a designed binding whose limit tables differ from the estimator configuration's.
+// lpvmpc_observer_vehicles_gains: the `gains` argument of the bound estimator kernels
+LPVMPC_HIDDEN int lpvmpc_observer_vehicles_check(lpvmpc_handle *h, int B, const lpvmpc_observer_config *obs, bool honoured, const char *who);
+inline lpvmpc::ObsVehGains lpvmpc_observer_vehicles_gains(const lpvmpc_handle *h) { lpvmpc::ObsVehGains g; static_cast<lpvmpc::ObsVehDev &>(g) = h->ov; g.g = h->obs_gains; return g; }
 namespace lpvmpc {
 // handoff.hip (host): interpolation operator W and interpolation + filtfilt operator FW, both [M][N] row-major
 bool handoff_operators(int N, double dt, double interp_dt, int padlen, int ord, const double *b, const double *a,

@@ -31,16 +31,37 @@ __device__ inline double obs_noise(const ObsParams &p, long long vid, long long 
     return n > lim ? lim : (n < -lim ? -lim : n);
 }
 
+// ---- per-vehicle estimator (lpvmpc_set_observer_vehicles) -----------------------------------------------------------------
+// The binding's device tables (ObsVehDev, lpvmpc_device.hpp).  ObsVeh<false> is empty: the forms without the flag take and read
+// nothing.  ObsGainsArg is the `gains` argument of the fused observe kernels: the gain words' pointer, with the flag the binding's
+// tables next to it (ObsVehGains)
+template <bool kObsVeh> struct ObsVeh {};
+template <> struct ObsVeh<true> : ObsVehDev {};
+template <bool kObsVeh> struct ObsGainsArg { using type = const double *__restrict__; };
+template <> struct ObsGainsArg<true> { using type = ObsVehGains; };
+__device__ inline const double *obs_gain_words(const double *g) { return g; }
+__device__ inline const double *obs_gain_words(const ObsVehGains &a) { return a.g; }
+__device__ inline ObsVeh<false> obs_veh(const double *) { return {}; }
+__device__ inline ObsVeh<true> obs_veh(const ObsVehGains &a) { ObsVeh<true> v; static_cast<ObsVehDev &>(v) = a; return v; }
+
 // ---- one GS_LPV_Est step (EST:349-398) ------------------------------------------------------------------------------------
 // G: the gain words (LDS); x [6] in/out; y [5]; t = k dt.  L [30], A [36], Bm [12] receive the step's matrices.
+// kObsVeh: the seven model words are vehicle b's row of ov.rows and the polytope's gain words come from ov.L (global memory);
+// limits, the polytope switch and the weights stay G's.  Every value is formed by the same operations in the same order.
+template <bool kObsVeh = false>
 __device__ inline void obs_step(const double *G, double x[6], const double y[5], double servo, double motor, double k, double dt,
-                                double L[30], double A[36], double Bm[12]) {
+                                double L[30], double A[36], double Bm[12], ObsVeh<kObsVeh> ov = {}, int b = 0) {
     const double t = k * dt;
     const bool run = t > 0.02;
     const double vx = run ? x[0] : y[0], vy = run ? x[1] : 0.0, th = run ? x[5] : y[4];
     const double steer = servo;
     // Continuous_AB_Comp (EST:402-436): the observer's own constants
-    const double lf = 0.125, lr = 0.125, m = 1.98, I = 0.03, Cf = 60, Cr = 60, mu = 0.05;
+    double lf = 0.125, lr = 0.125, m = 1.98, I = 0.03, Cf = 60, Cr = 60, mu = 0.05;
+    if constexpr (kObsVeh) {
+        const double *r = ov.rows + b;
+        const size_t n = ov.B;
+        lf = r[0]; lr = r[n]; m = r[2 * n]; I = r[3 * n]; Cf = r[4 * n]; Cr = r[5 * n]; mu = r[6 * n];
+    }
     double ss, cs, sth, cth;
     sincos(steer, &ss, &cs);
     sincos(th, &sth, &cth);
@@ -62,8 +83,11 @@ __device__ inline void obs_step(const double *G, double x[6], const double y[5],
     A[24] = sth; A[25] = cth;
     A[32] = 1.0;
     // L_Gain_Comp (EST:439-492): polytope choice, unclamped vertex weights, blend
-    const double *Lg = vx > G[kObsTable + 1] ? G + kObsTable + 12 : G;
+    const bool hs = vx > G[kObsTable + 1];
+    const double *Lg = hs ? G + kObsTable + 12 : G;
     const double *lim = Lg + kObsTable;
+    size_t gs = 1;                                                      // words between a polytope's consecutive gain words
+    if constexpr (kObsVeh) { gs = ov.B; Lg = ov.L + (hs ? (size_t)kObsTable * gs : 0) + b; }
     const double Mvx = (lim[1] - vx) / (lim[1] - lim[0]);
     const double Mvy = (lim[3] - vy) / (lim[3] - lim[2]);
     const double Mst = (lim[7] - steer) / (lim[7] - lim[6]);
@@ -78,7 +102,7 @@ __device__ inline void obs_step(const double *G, double x[6], const double y[5],
     for (int e = 0; e < 30; ++e) {
         double s = 0.0;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) s += w[i] * Lg[e * 16 + i];
+        for (int i = 0; i < 16; ++i) s += w[i] * Lg[(e * 16 + i) * gs];
         L[e] = s;
     }
     // x+ = x + (dt (A + L C) x + dt B u - dt L y), C = rows {0, 2, 3, 4, 5} of I6 (EST:248-252)
@@ -97,9 +121,10 @@ __device__ inline void obs_step(const double *G, double x[6], const double y[5],
 }
 
 // ---- sensors + one observer step after a plant step ------------------------------------------------------------------------
-// os [kObsStride]: see ObsSlot; st = plant state just advanced.
+// os [kObsStride]: see ObsSlot; st = plant state just advanced.  kObsVeh, ov, b: as obs_step.
+template <bool kObsVeh = false>
 __device__ inline void obs_substep(const double *G, const ObsParams &p, long long vid, double *os, const double st[8], double servo,
-                                   double motor) {
+                                   double motor, ObsVeh<kObsVeh> ov = {}, int b = 0) {
     const double k = os[OBS_K] + 1.0;
     os[OBS_K] = k;
     const long long step = (long long)k;
@@ -124,7 +149,7 @@ __device__ inline void obs_substep(const double *G, const ObsParams &p, long lon
     y[1] = imu_w; y[2] = os[OBS_GPS_X]; y[3] = os[OBS_GPS_Y];
     y[4] = run ? imu_yaw : st[6];
     double L[30], A[36], Bm[12];
-    obs_step(G, os, y, servo, motor, k, p.dt, L, A, Bm);
+    obs_step<kObsVeh>(G, os, y, servo, motor, k, p.dt, L, A, Bm, ov, b);
 #pragma unroll
     for (int i = 0; i < 5; ++i) os[OBS_Y + i] = y[i];
 }

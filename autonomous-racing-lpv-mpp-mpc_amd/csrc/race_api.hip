@@ -83,6 +83,7 @@ static int race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, i
         return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: bad configuration (laps >= 1, step counts >= 1, dt_sim > 0)");
     int rc;
     if (obs) { rc = lpvmpc_observer_check(h, obs, "lpvmpc_race_init_observed"); if (rc) return rc; }
+    if (obs) { rc = lpvmpc_observer_vehicles_check(h, B, obs, veh != nullptr, "lpvmpc_race_init"); if (rc) return rc; }
     rc = lpvmpc_need_track(h, "lpvmpc_race_init"); if (rc) return rc;
     rc = lpvmpc_need_track(plan, "lpvmpc_race_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
     rc = lpvmpc_check_common(h, B, "lpvmpc_race_init"); if (rc) return rc;
@@ -263,7 +264,11 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
                      tt->d_resid, nullptr, 0, 6};
         ta.active = d.m_tt;
         rc = lpvmpc_launch_solve_timed(tt, ta, st); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
-        if (r->tyre.t && d.estv)
+        if (r->tyre.t && d.estv && h->ov.L)
+            HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_tyre_obsveh(d, tyre_plant(r->veh, r->tyre), lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, r->act.d, st));
+        else if (r->veh.d.p && d.estv && h->ov.L)
+            HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_veh_obsveh(d, r->veh.d, lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, r->act.d, st));
+        else if (r->tyre.t && d.estv)
             HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_tyre(d, tyre_plant(r->veh, r->tyre), h->obs_gains, h->obs_state, h->obs_p, r->act.d, st));
         else if (r->tyre.t) HIP_TRY(h, lpvmpc::launch_race_command_plant_tyre(d, tyre_plant(r->veh, r->tyre), r->act.d, st));
         else if (r->veh.d.p && d.estv) HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_veh(d, r->veh.d, h->obs_gains, h->obs_state, h->obs_p, r->act.d, st));

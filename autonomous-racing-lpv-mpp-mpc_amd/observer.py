@@ -20,9 +20,20 @@ C_OBS = np.array([[1., 0., 0., 0., 0., 0.],     # vx        (EST:248-252)
                   [0., 0., 0., 0., 0., 1.]])    # yaw
 
 
-def observer_ab(vx, vy, theta, steer):
-    """Continuous_AB_Comp (EST:402-436): (A_obs [6,6], B_obs [6,2]) of the observer model."""
-    p = OBS_PARAMS
+def _obs_params(params):
+    """params None: OBS_PARAMS; a dict with OBS_PARAMS' keys; or a row [lf, lr, m, Iz, Cf, Cr, mu] (the plant rows' order)."""
+    if params is None:
+        return OBS_PARAMS
+    if isinstance(params, dict):
+        return params
+    lf, lr, m, I, Cf, Cr, mu = (float(v) for v in np.asarray(params, float).ravel())
+    return dict(lf=lf, lr=lr, m=m, I=I, Cf=Cf, Cr=Cr, mu=mu)
+
+
+def observer_ab(vx, vy, theta, steer, params=None):
+    """Continuous_AB_Comp (EST:402-436): (A_obs [6,6], B_obs [6,2]) of the observer model, with the observer's own constants or
+    a vehicle's ``params`` (see ``_obs_params``)."""
+    p = _obs_params(params)
     lf, lr, m, I, Cf, Cr, mu = p["lf"], p["lr"], p["m"], p["I"], p["Cf"], p["Cr"], p["mu"]
     B = np.array([[-(np.sin(steer) * Cf) / m, 1.], [(np.cos(steer) * Cf) / m, 0.], [(lf * Cf * np.cos(steer)) / I, 0.],
                   [0., 0.], [0., 0.], [0., 0.]])
@@ -54,21 +65,22 @@ def polytope_vertices(limits):
     return out
 
 
-def observer_vertex_gains(limits, Qo=None, Ro=None):
+def observer_vertex_gains(limits, Qo=None, Ro=None, params=None):
     """``Llmi`` [6, 5, 16] for a polytope with the given SchedVars_Limits [6, 2]: at each of the 16 vertices the steady-state
     Kalman gain of (A_obs, C) from scipy's ``solve_continuous_are``, with the reference's sign convention L = -P C^T Ro^-1
     (GS_LPV_Est adds L C, so A + L C = A - P C^T Ro^-1 C is Hurwitz at every vertex).
 
     These are per-vertex stabilising gains, NOT the reference's LMI design (its MATLAB synthesis and the .mat files it wrote
     are not available): they make the estimator usable for tests, tools and users without those files.  Between vertices the
-    blended gain is not guaranteed to stabilise; with the reference's own tables, pass those instead."""
+    blended gain is not guaranteed to stabilise; with the reference's own tables, pass those instead.  ``params``: the model
+    row the vertices are built on (``observer_ab``); ``BatchedSolver.observer_design`` is the device form for whole fleets."""
     from scipy.linalg import solve_continuous_are
     Qo = np.diag([1.0, 1.0, 1.0, 1.0, 1.0, 1.0]) if Qo is None else np.asarray(Qo, float)
     Ro = np.diag([0.1, 0.1, 0.01, 0.01, 0.01]) if Ro is None else np.asarray(Ro, float)
     Ri = np.linalg.inv(Ro)
     L = np.zeros((6, 5, 16))
     for i, (vx, vy, th, st) in enumerate(polytope_vertices(limits)):
-        A, _ = observer_ab(vx, vy, th, st)
+        A, _ = observer_ab(vx, vy, th, st, params)
         P = solve_continuous_are(A.T, C_OBS.T, Qo, Ro)
         L[:, :, i] = -P @ C_OBS.T @ Ri
     return L

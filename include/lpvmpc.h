@@ -507,7 +507,7 @@ int  lpvmpc_race_predictions(lpvmpc_handle *path, double *path_uPred, double *tt
  *   t = k dt with dt = 1 / loop_rate and k the number of observer steps including this one (k = 1 on the first step);
  *   scheduling variables (vx, vy, theta) = (x[0], x[1], x[5]) when t > 0.02, else (y[0], 0, y[4]) (EST:368-376);
  *   A_obs(vx, vy, theta, steer), B_obs(steer) with the observer's own constants lf = lr = 0.125, m = 1.98, I = 0.03,
- *   Cf = Cr = 60, mu = 0.05 (independent of lpvmpc_config);
+ *   Cf = Cr = 60, mu = 0.05 (independent of lpvmpc_config; a row per vehicle: "Per-vehicle state estimator" below);
  *   polytope HS when vx > lim_ls[0][1], else LS; 16 vertex weights from the limit rows 0, 1, 3, 5 (vx, vy, steer, theta) in
  *   EST:475-491's order (vertex i: bit 3 = vx, bit 2 = vy, bit 1 = steer, bit 0 = theta; a set bit takes 1 - M).  Like the
  *   reference the weights are NOT clamped: outside the polytope some are negative and the gain is extrapolated;
@@ -726,7 +726,7 @@ int  lpvmpc_race_lap_stats(lpvmpc_handle *path, double *f64, int32_t *i32, int32
 /* ---------------------------------------------------------------------------------------------------------------
  * Per-vehicle plant parameters: every vehicle of a lap-0 fleet or a race steps the simulated plant (Simulator.f, SIM:164-199)
  * with its own row of parameters, held on the device.  The controllers, the planner and the estimator keep the nominal model of
- * their handles (the mismatch is the point: a Monte-Carlo sweep of how the controller holds up when the car is not the model it
+ * their handles unless rows are bound to them ("Per-vehicle model parameters", "Per-vehicle state estimator" below; the mismatch is the point: a Monte-Carlo sweep of how the controller holds up when the car is not the model it
  * was tuned on).  All entry points here are new; the calls above keep their behaviour and refusals.
  *
  * Host layout: plant_params [B][LPVMPC_PLANT_WORDS] = {lf, lr, m, Iz, Cf, Cr, mu} per vehicle.  Cf and Cr are the linear tyre
@@ -783,8 +783,8 @@ int  lpvmpc_plant_params_read(lpvmpc_handle *h, double *plant_params);
  *     planner take the row's Cf and Cr, as they take the handle's without a binding.
  *   - Every value is formed by the same operations in the same order as without a binding: a row equal to the handle's words (and
  *     Cf equal to the call's cf_new, for the controller roll-out) gives the same words as the unbound handle.
- *   - lpvmpc_solve_batch_AB takes the caller's blocks and is unaffected (any B).  The estimator keeps the nominal model: its gain
- *     tables are designed on the nominal polytope's vertices.
+ *   - lpvmpc_solve_batch_AB takes the caller's blocks and is unaffected (any B).  The estimator does not read these rows: it has a
+ *     binding of its own, with gain tables designed for each row ("Per-vehicle state estimator" below).
  * lpvmpc_set_model_params copies the rows to the device (synchronises); B = 0 unbinds (model_params is then ignored).  Refused with
  * LPVMPC_E_ARG, the binding unchanged: a non-finite word, lf, lr, m or Iz <= 0, Cf, Cr or mu < 0 (the plant rows' rules), B < 0,
  * B > 0 with model_params NULL, and any call while the handle runs a fleet, cascade or race (as stand-alone batch calls are
@@ -881,6 +881,59 @@ int  lpvmpc_tyre_params_read(lpvmpc_handle *h, double *tyre_params);
  * fleet, cascade or race, like the other batch calls. */
 int  lpvmpc_tyre_force_batch(lpvmpc_handle *h, int32_t B, const double *tyre_params, const double *m, const double *alpha,
                              double *force);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Per-vehicle state estimator: gain tables designed on the device for each vehicle's own model row.  The gain-scheduled estimator
+ * above blends the gains of the 16 vertices of a polytope; those gains belong to the model they were designed on.  Here the
+ * design runs on the device, one problem per (vehicle b, polytope p in {LS, HS}, vertex i in 0..15, in the order of the
+ * estimator's vertex weights: bit 3 = vx, bit 2 = vy, bit 1 = steer, bit 0 = theta of i takes the maximum):
+ *   A = A_obs(vx, vy, theta, steer) at the vertex, formed as the observer step forms it, with the seven constants taken from the
+ *   vehicle's row {lf, lr, m, Iz, Cf, Cr, mu} (the plant rows' order);
+ *   P solves the filter equation A P + P A^T - P C^T Ro^-1 C P + Qo = 0;  L = -P C^T Ro^-1 [6][5], so that A + L C is Hurwitz.
+ * Method: matrix-sign Newton iteration on the Hamiltonian [[A^T, -C^T Ro^-1 C], [-Qo, -A]] with Frobenius-norm scaling, stopped
+ * when the step is <= 1e-13 of the iterate (cap: 40 iterations), P from the normal equations of the sign's stable subspace,
+ * symmetrised.  A vehicle's tables do not depend on the batch around it (no atomics, fixed summation order).
+ * A problem that does not meet the stop rule within the cap gets NaN gains and the iteration count -1.
+ *
+ * lpvmpc_observer_design_batch: rows [B][LPVMPC_PLANT_WORDS]; L_ls, L_hs [B][6][5][16] (the layout of lpvmpc_observer_config's tables
+ * per vehicle); iters [B][2][16] (may be NULL) the Newton iterations of each problem.  Refused with LPVMPC_E_ARG, the outputs
+ * untouched: a row the plant rows' rules refuse (non-finite word, lf, lr, m, Iz <= 0, Cf, Cr, mu < 0), Ro not symmetric positive
+ * definite, Qo not symmetric positive semidefinite or with a non-finite word, a limit row 0, 1, 3 or 5 with max <= min, a lower vx
+ * limit <= 0, B > LPVMPC_OBSERVER_DESIGN_MAX_B, and any call while the handle runs a fleet, cascade or race. */
+#define LPVMPC_OBSERVER_DESIGN_MAX_B (1 << 22)
+typedef struct lpvmpc_observer_design {
+    double lim_ls[6 * 2], lim_hs[6 * 2];    /* SchedVars_Limits of the two polytopes, as in lpvmpc_observer_config */
+    double Qo[6 * 6], Ro[5 * 5];            /* process and measurement weights of the filter equation */
+} lpvmpc_observer_design;
+/* Qo = I, Ro = diag(0.1, 0.1, 0.01, 0.01, 0.01); the limit tables are zeroed: the caller's */
+void lpvmpc_observer_default_design(lpvmpc_observer_design *d);
+int  lpvmpc_observer_design_batch(lpvmpc_handle *h, int32_t B, const double *rows, const lpvmpc_observer_design *d,
+                                  double *L_ls, double *L_hs, int32_t *iters);
+
+/* The binding: a model row and the two gain tables per vehicle on a controller handle (for a race: the path handle).  An estimator
+ * of a fleet or race started on the handle by lpvmpc_cl_init_vehicles, lpvmpc_cl_init_tyres, lpvmpc_race_init_vehicles or
+ * lpvmpc_race_init_tyres then runs vehicle b's observer step with row b's seven words in A_obs and B_obs and with vehicle b's
+ * tables; the tables of the estimator configuration are ignored, its limit tables, polytope switch, sensors and noise stay.  Every
+ * value is formed by the same operations in the same order as without a binding: the nominal row {0.125, 0.125, 1.98, 0.03, 60,
+ * 60, 0.05} with tables equal to the configuration's gives the unbound estimator's words.  A handle without a binding (the default)
+ * launches what it launched before.
+ *   lpvmpc_set_observer_vehicles: rows [B][LPVMPC_PLANT_WORDS], and exactly one of (L_ls and L_hs, [B][6][5][16] each: the caller's
+ *     tables, finite) or design (the tables are designed on the device straight into the binding, no host copy; a problem that does
+ *     not converge fails the call with LPVMPC_E_ARG and a message naming vehicle and vertex).  B = 0 unbinds.  Synchronises.
+ *     Refused with LPVMPC_E_ARG, the previous binding kept: what lpvmpc_observer_design_batch refuses, neither or both of tables
+ *     and design, a planner handle, and any call while the handle runs a fleet, cascade or race.  lpvmpc_cl_release keeps the
+ *     binding, lpvmpc_destroy frees it.
+ *   Starts: with an estimator configured, the four calls above refuse another B than the binding's and a designed binding whose limit
+ *     tables differ from the estimator configuration's; every other start of a fleet or race with an estimator and
+ *     lpvmpc_cascade_init with one refuse a bound handle.  Starts without an estimator ignore the binding.
+ *   lpvmpc_observer_vehicles_read: *B = the binding's batch size (0: unbound) and, where not NULL, the rows and tables as bound.
+ *   lpvmpc_observer_step_vehicles_batch: lpvmpc_observer_step_batch with a row and tables per instance (cfg's own tables are ignored). */
+int  lpvmpc_set_observer_vehicles(lpvmpc_handle *h, int32_t B, const double *rows, const double *L_ls, const double *L_hs,
+                                  const lpvmpc_observer_design *design);
+int  lpvmpc_observer_vehicles_read(lpvmpc_handle *h, int32_t *B, double *rows, double *L_ls, double *L_hs);
+int  lpvmpc_observer_step_vehicles_batch(lpvmpc_handle *h, int32_t B, const lpvmpc_observer_config *cfg, double *est, const double *y,
+                                         const double *u, const int32_t *k, double *aux, const double *rows, const double *L_ls,
+                                         const double *L_hs);
 
 #ifdef __cplusplus
 }

@@ -28,8 +28,12 @@ not a regression), and, with --parent-lib FILE, unbound on that build.
 lpvmpc_race_init_tyres race with kind 0 rows (the tyre forms of the kernels on the linear tyre) and with the launch file's Pacejka tyre on
 every vehicle (other trajectories, so its in-phase lines also carry the solvers' changed iteration counts), and, with --parent-lib FILE,
 the _vehicles race on that build.
+--observer-vehicles: the same protocol for the per-vehicle estimator: the lpvmpc_race_init_vehicles race with nominal rows and the
+estimator in the loop (the fixture's gain tables, noisy sensors), unbound (the baseline) and with a per-vehicle estimator bound to the
+path engine (lpvmpc_set_observer_vehicles: nominal rows, tables designed on the device -- 7.7 KB of gain words per vehicle and observer
+step from global memory instead of one table in LDS), and, with --parent-lib FILE, the unbound race on that build.
 Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator | --actuator | --record | --plant-params | --models | --tunings |
-       --tyres [--parent-lib FILE] [--reps R]] [--out FILE]"""
+       --tyres | --observer-vehicles [--parent-lib FILE] [--reps R]] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -61,8 +65,13 @@ def timed(tick, read, K):
 
 
 def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, record=False, plant_params=None, model_params=None, tunings=None,
-             tyre_params=None):
+             tyre_params=None, observer_vehicles=False):
     path, tt, plan = engines(mp, sd)
+    if observer_vehicles:                                             # nominal estimator rows, tables designed on the configuration's limits
+        from lpvmpc.observer import OBS_PARAMS
+        row = [OBS_PARAMS[k] for k in ("lf", "lr", "m", "I", "Cf", "Cr", "mu")]
+        path.set_observer_vehicles(np.tile(row, (plant0.shape[0], 1)),
+                                   design=dict(lim_ls=np.array(estimator.lim_ls[:]).reshape(6, 2), lim_hs=np.array(estimator.lim_hs[:]).reshape(6, 2)))
     if tunings is not None:                                           # "own": each handle's own row; "sampled": sample_tunings around it
         from lpvmpc import tuning
         for e in (path, tt, plan):
@@ -98,6 +107,7 @@ def main():
     ap.add_argument("--models", action="store_true")
     ap.add_argument("--tunings", action="store_true")
     ap.add_argument("--tyres", action="store_true")
+    ap.add_argument("--observer-vehicles", action="store_true")
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--models-child", nargs=4, default=None, help=argparse.SUPPRESS)      # lib regime B bind: one run of --models
     a = ap.parse_args()
@@ -110,6 +120,9 @@ def main():
     if a.tyres:
         return models_main(a, [("vehicles, nominal rows", "liblpvmpc.so", 4), ("tyres, kind 0 rows", "liblpvmpc.so", 5),
                                ("tyres, Pacejka", "liblpvmpc.so", 6)], parent=("parent, vehicles", 4))
+    if a.observer_vehicles:
+        return models_main(a, [("estimator, unbound", "liblpvmpc.so", 7), ("estimator, rows bound", "liblpvmpc.so", 8)],
+                           parent=("parent, estimator", 7))
     if a.plant_params:
         return plant_params_main(a)
     if a.record:
@@ -280,8 +293,15 @@ def models_child(a):
     plant0, half, warm = _models_starts(int(B))[regime]
     rows = lpvmpc.model_params(int(B)) if int(bind) == 1 else None                # bind: 0 nothing, 1 nominal model rows, 2 / 3 tuning rows,
     tyres = {5: lpvmpc.tyre_params(int(B), kind=0), 6: "pacejka"}.get(int(bind))   # 4 nominal plant rows (_vehicles), 5 / 6 tyre rows on top
+    obs = None                                                                     # 7 / 8: _vehicles with the estimator, unbound / rows bound
+    if int(bind) >= 7:
+        from lpvmpc.observer import observer_config
+        f = np.load(os.path.join(ROOT, "tests", "golden", "estimator", "estimator.npz"))
+        obs = observer_config(f["L_ls"], f["lim_ls"], f["L_hs"], f["lim_hs"], psi_std=0.01, psiDot_std=0.05, x_std=0.01, y_std=0.01,
+                              v_std=0.02, seed=7)
     ms, _vps, ph = race_run(mp, plant0, half, warm, a.ticks, model_params=rows, tunings={2: "own", 3: "sampled"}.get(int(bind)),
-                            plant_params="nominal" if int(bind) >= 4 else None, tyre_params=tyres)
+                            plant_params="nominal" if int(bind) >= 4 else None, tyre_params=tyres, estimator=obs,
+                            observer_vehicles=int(bind) == 8)
     print("MODELS_RUN %.6f %s" % (ms, ",".join(str(int(x)) for x in ph)), flush=True)
 
 

@@ -13,8 +13,12 @@ baseline race keeps the nominal model.
 --tyre selects the plants' tyre (lpvmpc_race_init_tyres, RaceFleet(tyre_params=...)): linear (default: today's run, same output:
 the plant rows' Cf, Cr) or pacejka (the launch file's Simulator.pacejka on every vehicle, the baseline race included: a tyre that
 saturates; the rows' Cf, Cr are then not read, so their bins show no trend of their own).  Every model keeps the linear tyre.
+--estimator puts the state estimator in the loop (the fixture's limit tables and nominal gain tables, the sensors without noise),
+in the baseline race as well: nominal (the estimator keeps its own constants and the nominal tables) or plant (each vehicle's
+estimator takes its plant row, with gain tables designed on the device for that row: RaceFleet(estimator_params="plant")).  Without
+the flag the race runs on ground truth: today's run, same output.
 Usage: tools/robustness_sweep.py [--B 8192] [--laps 2] [--seed 1] [--max-ticks 3000] [--model nominal|plant|noisy:REL]
-       [--tyre linear|pacejka] [--out FILE]"""
+       [--tyre linear|pacejka] [--estimator nominal|plant] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -33,6 +37,7 @@ def main():
     ap.add_argument("--max-ticks", type=int, default=3000)
     ap.add_argument("--model", default="nominal")
     ap.add_argument("--tyre", default="linear", choices=("linear", "pacejka"))
+    ap.add_argument("--estimator", default=None, choices=("nominal", "plant"))
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.model not in ("nominal", "plant") and not a.model.startswith("noisy:"):
@@ -56,9 +61,15 @@ def main():
         model_rows = model.perturb_rows(rows, a.seed, {k: rel for k in plant.WORDS})
         model_text = "take each vehicle's plant row times an independent uniform factor in [%g, %g] per field as its model (--model %s)" % (1 - rel, 1 + rel, a.model)
 
-    def race(r, m=None):
+    obs = None
+    if a.estimator:
+        from lpvmpc.observer import observer_config
+        g = np.load(os.path.join(ROOT, "tests", "golden", "estimator", "estimator.npz"))
+        obs = observer_config(g["L_ls"], g["lim_ls"], g["L_hs"], g["lim_hs"])
+
+    def race(r, m=None, est_rows=None):
         f = lpvmpc.RaceFleet(mp, plant0, laps=a.laps, half_track0=1, plant_params=r, model_params=m,
-                             tyre_params="pacejka" if a.tyre == "pacejka" else None)
+                             tyre_params="pacejka" if a.tyre == "pacejka" else None, estimator=obs, estimator_params=est_rows)
         assert np.array_equal(f.plant_params(), r)
         assert a.tyre == "linear" or np.array_equal(f.tyre_params(), lpvmpc.tyre_params(B))
         assert m is None or np.array_equal(f.model_params(), m)
@@ -73,7 +84,7 @@ def main():
     base, _n, _w = race(nom)                                          # the same starts with the nominal car: the baseline
     ph_nom = base.state()["phase"]
     base.close()
-    fleet, ticks, wall = race(rows, model_rows)
+    fleet, ticks, wall = race(rows, model_rows, "plant" if a.estimator == "plant" else None)
     ph = fleet.state()["phase"]
     lt = fleet.lap_times()[:, 1:a.laps + 1]                          # racing laps, seconds (NaN: not completed)
     st = fleet.lap_stats()
@@ -83,7 +94,9 @@ def main():
     lines = ["# tools/robustness_sweep.py --B %d --laps %d --seed %d%s on one MI355X: one race, rows from sample_plant_params(B, %d) with spreads %s"
              % (B, a.laps, a.seed, " --tyre pacejka" if a.tyre == "pacejka" else "", a.seed,
                 ", ".join("%s %+.0f %%" % (k, 100 * v) for k, v in spread.items())),
-             "# the controllers and the planner %s." % model_text,
+             "# the controllers and the planner %s." % model_text] + ([] if not a.estimator else [
+             "# the state estimator is in the loop (--estimator %s): %s." % (a.estimator, "each vehicle's estimator takes its plant row and gain tables "
+              "designed for it" if a.estimator == "plant" else "it keeps its own constants and the nominal gain tables")]) + [
              "# %d ticks (%.1f s wall); all vehicles: %.1f %% finished, %.1f %% lost, %.1f %% still running; racing lap time median %.3f s, "
              "p90 %.3f s; RMSE_ey median %.4f m" % (ticks, wall, 100 * fin.mean(), 100 * lost.mean(), 100 * (ph < 2).mean(),
                                                      np.nanmedian(lt), np.nanpercentile(lt, 90), np.nanmedian(rmse)),
