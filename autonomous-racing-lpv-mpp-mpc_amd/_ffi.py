@@ -129,6 +129,7 @@ PLANT_WORD_NAMES = ("lf", "lr", "m", "Iz", "Cf", "Cr", "mu")
 TYRE_WORDS = 4                           # LPVMPC_TYRE_WORDS: [kind, B, C, c_f] per vehicle (plant.py, "tyre rows")
 TYRE_WORD_NAMES = ("kind", "B", "C", "c_f")
 MODEL_WORDS = 7                          # LPVMPC_MODEL_WORDS: the same words, as a controller's / planner's model of the vehicle
+MAX_TRACKS = 64                          # LPVMPC_MAX_TRACKS: entries of a track palette (track.pack_tracks)
 TUNING_WORDS = 64                        # LPVMPC_TUNING_WORDS: Q[36] R[4] dR[2] L_cf[6] limits[16] per instance (tuning.py)
 
 OBSERVER_AUX = 30 + 36 + 12      # L_gain [6][5], A_obs [6][6], B_obs [6][2] per instance (lpvmpc_observer_step_batch)
@@ -152,7 +153,8 @@ EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_d
            "lpvmpc_plant_step_tyres_batch", "lpvmpc_cl_init_tyres", "lpvmpc_race_init_tyres", "lpvmpc_tyre_params_read",
            "lpvmpc_tyre_force_batch",
            "lpvmpc_observer_default_design", "lpvmpc_observer_design_batch", "lpvmpc_set_observer_vehicles",
-           "lpvmpc_observer_vehicles_read", "lpvmpc_observer_step_vehicles_batch")
+           "lpvmpc_observer_vehicles_read", "lpvmpc_observer_step_vehicles_batch",
+           "lpvmpc_set_tracks", "lpvmpc_tracks_read")
 
 _lib = None
 
@@ -323,6 +325,13 @@ def load():
         lib.lpvmpc_observer_vehicles_read.argtypes = [vp, P(_i), vp, vp, vp]
         lib.lpvmpc_observer_step_vehicles_batch.argtypes = [vp, _i, P(ObserverConfig), vp, vp, vp, vp, vp, vp, vp, vp]
         for name in ("lpvmpc_set_observer_vehicles", "lpvmpc_observer_vehicles_read", "lpvmpc_observer_step_vehicles_batch"):
+            getattr(lib, name).restype = C.c_int
+    except AttributeError:
+        pass
+    try:        # (nor the per-vehicle tracks)
+        lib.lpvmpc_set_tracks.argtypes = [vp, _i, vp, vp, vp, vp, _i, vp]
+        lib.lpvmpc_tracks_read.argtypes = [vp, P(_i), P(_i), vp, vp, vp, vp, vp]
+        for name in ("lpvmpc_set_tracks", "lpvmpc_tracks_read"):
             getattr(lib, name).restype = C.c_int
     except AttributeError:
         pass

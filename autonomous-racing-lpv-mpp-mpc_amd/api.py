@@ -366,6 +366,33 @@ class BatchedSolver:
         self._chk(self._lib.lpvmpc_model_params_read(self._h, C.byref(B), ptr(out)))
         return out
 
+    def set_tracks(self, maps, track_of):
+        """Bind per-vehicle tracks to this engine (lpvmpc_set_tracks): ``maps`` is a sequence (the palette, at most 64) of objects with
+        ``.PointAndTangent``, ``.halfWidth`` and ``.slack`` -- ``track.Map``, ``track.mirrored`` / ``track.scaled`` results, the
+        reference's own Map -- and ``track_of`` [B] the palette entry of each vehicle.  local_position, global_position, lpv,
+        estimate_abc, solve* and a lap-0 fleet started with ``cl_init(..., tyre_params=...)`` (``"linear"``: no tyre rows) then take
+        vehicle b's track, must have batch size B, and take each track's half width and slack instead of the call's.  ``None``
+        unbinds.  ``handoff`` and a race started with ``race_init(..., tyre_params=...)`` on three engines with equal bindings take
+        it too.  The other ``cl_init`` / ``race_init`` starts and the cascade refuse a bound engine."""
+        if maps is None:
+            self._chk(self._lib.lpvmpc_set_tracks(self._h, 0, None, None, None, None, 0, None))
+            return
+        from .track import pack_tracks
+        rows, tab, hw, sl, of = pack_tracks(maps, track_of)
+        self._chk(self._lib.lpvmpc_set_tracks(self._h, rows.shape[0], ptr(rows), ptr(tab), ptr(hw), ptr(sl), of.shape[0], ptr(of)))
+
+    def tracks_read(self):
+        """The bound tracks as they were set (lpvmpc_tracks_read): dict(tables = list of T PointAndTangent arrays [rows, 6],
+        half_width [T], slack [T], track_of [B]), or None while nothing is bound."""
+        T, B = C.c_int32(0), C.c_int32(0)
+        self._chk(self._lib.lpvmpc_tracks_read(self._h, C.byref(T), C.byref(B), None, None, None, None, None))
+        if T.value == 0:
+            return None
+        rows, of = np.empty(T.value, np.int32), np.empty(B.value, np.int32)
+        tab, hw, sl = np.empty((T.value, _ffi.MAX_TRACK_ROWS, 6)), np.empty(T.value), np.empty(T.value)
+        self._chk(self._lib.lpvmpc_tracks_read(self._h, C.byref(T), C.byref(B), ptr(rows), ptr(tab), ptr(hw), ptr(sl), ptr(of)))
+        return dict(tables=[tab[t, :rows[t]].copy() for t in range(T.value)], half_width=hw, slack=sl, track_of=of)
+
     def set_tunings(self, rows):
         """Bind per-instance tuning rows [B, 64] (tuning.py: Q, R, dR, L_cf and the limits) to this engine (lpvmpc_set_tunings): every
         call that solves -- solve, solve_AB, solve_batch_masked, solve_dev, and a fleet, cascade or race started afterwards -- then
@@ -1135,18 +1162,28 @@ class RaceFleet(object):
     ``estimator_params`` (with ``estimator``): the estimator's model rows, [B, 7], "plant" (each vehicle's plant row) or "model" (the
     rows ``model_params`` binds); the gain tables are designed on the device for each row, on the estimator configuration's limit
     tables with ``estimator_design``'s weights (dict(Qo=, Ro=), default: observer_vertex_gains'), and bound to the path engine
-    (BatchedSolver.set_observer_vehicles).  None: the estimator keeps its own constants and the configuration's tables."""
+    (BatchedSolver.set_observer_vehicles).  None: the estimator keeps its own constants and the configuration's tables.
+    ``track_map``: one map, or a sequence of maps (a palette, at most 64: track.Map, track.mirrored, track.scaled, ...) with
+    ``track_of`` [B], the palette entry of each vehicle: one race with vehicles on different circuits, each with its own lap length,
+    half width and slack (``tracks()`` reads the binding back; ``plan_max_ey`` stays one value per race)."""
 
     def __init__(self, track_map, plant0, laps=1, N=20, Np=40, half_track0=None, device=0, estimator=None, actuator=None,
                  steering_delay=0, delay_a=None, delay_df=None, plant_params=None, model_params=None, path_tunings=None,
-                 tt_tunings=None, plan_tunings=None, tyre_params=None, estimator_params=None, estimator_design=None, **options):
+                 tt_tunings=None, plan_tunings=None, tyre_params=None, estimator_params=None, estimator_design=None, track_of=None,
+                 **options):
         from .workloads import CTRL_TUNINGS, PLAN_L, PLAN_Q, PLAN_R, PLAN_dR
         race_keys = ("n_sub_lap0", "n_sub", "q9_swap", "plan_max_ey", "dt_sim", "mu_sim")
         race_opts = {k: v for k, v in options.items() if k in race_keys}
         engine_opts = {k: v for k, v in options.items() if k not in race_keys}
         Qp, Rp, dRp = CTRL_TUNINGS["path"]; Qr, Rr, dRr = CTRL_TUNINGS["race"]
+        # a sequence of maps with track_of: every vehicle on its own track (lpvmpc_set_tracks on the three engines, the start through
+        # the most general entry); a single map, or a sequence of one without track_of, keeps the unbound path
+        from .track import fleet_tracks
+        maps, of = fleet_tracks(track_map, track_of, f64(plant0).reshape(-1, 8).shape[0])
+        track_map = maps[0]
         tab = track_map.PointAndTangent
         self.map = track_map
+        self.maps = maps
         sd = {"steering_delay": int(steering_delay)} if steering_delay else {}
         self.path = BatchedSolver("controller", N, 1.0 / 30.0, Qp, Rp, dRp, track=tab, device=device, **sd)
         self.tt = BatchedSolver("controller", N, 1.0 / 30.0, Qr, Rr, dRr, track=tab, device=device, **sd)
@@ -1192,6 +1229,11 @@ class RaceFleet(object):
             self.path.set_observer_vehicles(erows, design=observer_design_config(lim[0], lim[1], **(estimator_design or {})))
             if plant_params is None and tyre_params is None:
                 plant_params = "nominal"                         # the starts that run the binding
+        if of is not None:
+            for e in (self.path, self.tt, self.planner):
+                e.set_tracks(maps, of)
+            if tyre_params is None:
+                tyre_params = "linear"                           # the start that runs the binding (each track's width and slack)
         self.path.race_init(self.tt, self.planner, plant0, half_track0=half_track0, laps=laps, half_width=track_map.halfWidth,
                             slack=track_map.slack, estimator=estimator, actuator=actuator, delay_a=delay_a, delay_df=delay_df,
                             plant_params=plant_params, tyre_params=tyre_params, **race_opts)
@@ -1223,6 +1265,11 @@ class RaceFleet(object):
     def model_params(self):
         """The model rows [B, 7] bound to the race's three engines by ``model_params`` (read from the path engine), or None."""
         return self.path.model_params_read()
+
+    def tracks(self):
+        """The tracks bound to the race's three engines by a sequence ``track_map`` with ``track_of`` (BatchedSolver.tracks_read on the
+        path engine), or None for a race on a single map."""
+        return self.path.tracks_read()
 
     def tunings(self):
         """The tuning rows bound to the (path, tt, planner) engines, each [B, 64] or None."""

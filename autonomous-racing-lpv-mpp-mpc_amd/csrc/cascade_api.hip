@@ -93,6 +93,7 @@ extern "C" int lpvmpc_handoff_setup(lpvmpc_handle *h, const lpvmpc_handoff_confi
 extern "C" int lpvmpc_handoff_batch(lpvmpc_handle *h, int32_t B, const double *xPred, double *SS, double *pose, double *sig, double *refs) {
     if (h && B == 0) return LPVMPC_OK;
     int rc = lpvmpc_check_batch(h, B, "lpvmpc_handoff_batch"); if (rc) return rc;
+    rc = lpvmpc_tracks_check(h, B, "lpvmpc_handoff_batch"); if (rc) return rc;
     if (!h->d_Wop) return fail(h, LPVMPC_E_ARG, "lpvmpc_handoff_batch: call lpvmpc_handoff_setup first");
     if (!xPred || !SS || !pose || !refs) return fail(h, LPVMPC_E_ARG, "lpvmpc_handoff_batch: NULL argument");
     const size_t N = h->cfg.N, M = h->ho_M, b = B;
@@ -103,7 +104,8 @@ extern "C" int lpvmpc_handoff_batch(lpvmpc_handle *h, int32_t B, const double *x
     double *d_refs = nullptr;
     HIP_TRY(h, tmp.alloc(d_refs, b * 5 * M * 8));
     H2D(h->d_xPred, xPred, b * (N + 1) * 5 * 8); H2D(h->d_curv, SS, b * (N + 1) * 8); H2D(h->d_resid, pose, b * 3 * 8);
-    HIP_TRY(h, lpvmpc::launch_plan_pose(h->d_cfg, B, h->d_xPred, h->d_curv, h->d_resid, h->d_states, st));
+    if (h->trk.tab) HIP_TRY(h, lpvmpc::launch_plan_pose_trk(h->d_cfg, h->trk, B, h->d_xPred, h->d_curv, h->d_resid, h->d_states, st));
+    else HIP_TRY(h, lpvmpc::launch_plan_pose(h->d_cfg, B, h->d_xPred, h->d_curv, h->d_resid, h->d_states, st));
     HIP_TRY(h, lpvmpc::launch_resample(B, (int)N, (int)M, h->d_Wop, h->d_FWop, h->d_states, d_refs, st));
     D2H(SS, h->d_curv, b * (N + 1) * 8); D2H(pose, h->d_resid, b * 3 * 8); D2H(refs, d_refs, b * 5 * M * 8);
     if (sig) D2H(sig, h->d_states, b * 5 * N * 8);
@@ -141,6 +143,7 @@ extern "C" int lpvmpc_cascade_init(lpvmpc_handle *h, lpvmpc_handle *plan, int32_
         return fail(h, LPVMPC_E_ARG, "lpvmpc_cascade_init: bad argument (lap0 must be >= 1: the cascade is the racing phase)");
     rc = lpvmpc_need_track(h, "lpvmpc_cascade_init"); if (rc) return rc;
     rc = lpvmpc_check_common(plan, B, "lpvmpc_cascade_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
+    for (const lpvmpc_handle *x : {h, plan}) { rc = lpvmpc_tracks_unbound(h, x, "lpvmpc_cascade_init"); if (rc) return rc; }
     rc = lpvmpc_model_check(h, B, "lpvmpc_cascade_init"); if (rc) return rc;
     rc = lpvmpc_model_check(plan, B, "lpvmpc_cascade_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
     if (h->obs_cfg) { rc = lpvmpc_observer_vehicles_check(h, B, h->obs_cfg.get(), false, "lpvmpc_cascade_init"); if (rc) return rc; }

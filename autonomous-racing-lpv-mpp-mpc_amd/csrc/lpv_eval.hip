@@ -309,16 +309,25 @@ __global__ void __launch_bounds__(64) plan_abc_kernel(const DevCfg *__restrict__
 
 // model: the handle's model table [kModelWords][B] (lpvmpc_set_model_params), null: the handle's own words.  With a table the kernels
 // that read vehicle words are replaced by their per-vehicle forms (veh_lpv_eval.hip), which take vehicle b's row and, in the
-// controller roll-out, its Cf for both axles instead of cf_new; ctrl_lpv_roll_kernel reads no vehicle word and is launched as it is
+// controller roll-out, its Cf for both axles instead of cf_new; ctrl_lpv_roll_kernel reads no vehicle word and is launched as it is.
+// trk: the handle's track binding (lpvmpc_set_tracks), null: the configuration's table.  With a binding the kernels that read the
+// track are replaced by their bound forms (track_lpv_eval.hip), per-vehicle-model forms all: they take model, or without one
+// own_model, the binding's table of the handle's own words.  ctrl_lpv_pre_kernel reads no track and is launched as it is
 hipError_t launch_lpv(const DevCfg &cfg, const DevCfg *dcfg, const double *model, int B, const double *x0, const double *u_prev,
                       const double *vel_ref, const double *curv_s, double cf_new, int lap, double *states, double *AB, hipStream_t stream,
-                      const int32_t *active) {
+                      const int32_t *active, const TrackDev *trk, const double *own_model) {
     const int blocks = (B + 63) / 64;
     if (cfg.kind == 0 && AB) {
         if (model) launch_ctrl_lpv_pre_veh(dcfg, model, B, cfg.N, u_prev, vel_ref, AB, stream, active);
         else hipLaunchKernelGGL(ctrl_lpv_pre_kernel, dim3((B * cfg.N + 63) / 64), dim3(64), 0, stream, dcfg, B, u_prev, vel_ref, cf_new, AB, active);
-        hipLaunchKernelGGL(ctrl_lpv_roll_kernel, dim3(blocks), dim3(64), 0, stream, dcfg, B, x0, u_prev, curv_s, lap, states, AB, active);
-    } else if (model)
+        if (trk) launch_ctrl_lpv_roll_trk(dcfg, *trk, B, x0, u_prev, curv_s, lap, states, AB, stream, active);
+        else hipLaunchKernelGGL(ctrl_lpv_roll_kernel, dim3(blocks), dim3(64), 0, stream, dcfg, B, x0, u_prev, curv_s, lap, states, AB, active);
+    } else if (trk) {
+        // the controller roll-out without [A | B] has no bound form (no caller of the library asks for it): an error, not another kernel
+        if (cfg.kind == 0) return hipErrorNotSupported;
+        launch_plan_lpv_trk(dcfg, *trk, model ? model : own_model, B, x0, u_prev, curv_s, states, AB, stream, active);
+    }
+    else if (model)
         launch_lpv_veh(cfg.kind, dcfg, model, B, x0, u_prev, vel_ref, curv_s, lap, states, AB, stream, active);
     else if (cfg.kind == 0)
         hipLaunchKernelGGL(ctrl_lpv_kernel, dim3(blocks), dim3(64), 0, stream, dcfg, B, x0, u_prev, vel_ref, curv_s, cf_new, lap, states, AB, active);
@@ -328,9 +337,11 @@ hipError_t launch_lpv(const DevCfg &cfg, const DevCfg *dcfg, const double *model
 }
 
 hipError_t launch_abc(const DevCfg &cfg, const DevCfg *dcfg, const double *model, int B, const double *xlast, const double *delta, double *AB,
-                      hipStream_t stream, const int32_t *active) {
+                      hipStream_t stream, const int32_t *active, const TrackDev *trk, const double *own_model) {
     const int blocks = (B * cfg.N + 63) / 64;
-    if (model)
+    if (trk)
+        launch_abc_trk(cfg.kind, dcfg, *trk, model ? model : own_model, B, cfg.N, xlast, delta, AB, stream, active);
+    else if (model)
         launch_abc_veh(cfg.kind, dcfg, model, B, cfg.N, xlast, delta, AB, stream, active);
     else if (cfg.kind == 0)
         hipLaunchKernelGGL(ctrl_abc_kernel, dim3(blocks), dim3(64), 0, stream, dcfg, B, xlast, delta, AB, active);

@@ -281,13 +281,18 @@ extern "C" double lpvmpc_last_kernel_ms(lpvmpc_handle *h) {
 
 // ------------------------------------------------------------------------------------------------
 int lpvmpc_need_track(lpvmpc_handle *h, const char *who) {
-    if (h->cfg.track_rows < 1) return fail(h, LPVMPC_E_ARG, "%s: the handle was created without a track table", who);
+    if (h->cfg.track_rows < 1 && !h->trk.tab) return fail(h, LPVMPC_E_ARG, "%s: the handle was created without a track table", who);
     return LPVMPC_OK;
 }
 
 static int launch_lpv(lpvmpc_handle *h, int B, const double *x0, const double *u_prev, const double *vel_ref,
                       const double *curv_s, double cf_new, int lap, double *states, double *AB, hipStream_t st) {
-    HIP_TRY(h, lpvmpc::launch_lpv(h->dev, h->d_cfg, h->d_model, B, x0, u_prev, vel_ref, curv_s, cf_new, lap, states, AB, st));
+    // (lpvmpc::launch_lpv has no bound form of the controller roll-out without [A | B]; every entry point passes the workspace's)
+    if (h->trk.tab && h->cfg.kind == LPVMPC_KIND_CONTROLLER && !AB)
+        return fail(h, LPVMPC_E_ARG, "lpvmpc_lpv_batch: the states-only controller roll-out is not available on a handle with per-vehicle tracks "
+                    "bound (lpvmpc_set_tracks)");
+    HIP_TRY(h, lpvmpc::launch_lpv(h->dev, h->d_cfg, h->d_model, B, x0, u_prev, vel_ref, curv_s, cf_new, lap, states, AB, st, nullptr,
+                                  lpvmpc_trk(h), h->d_trk_model));
     return LPVMPC_OK;
 }
 
@@ -401,6 +406,7 @@ extern "C" int lpvmpc_lpv_batch(lpvmpc_handle *h, int32_t B, const double *x0, c
     if (h && B == 0) return LPVMPC_OK;                                   // an empty batch is a no-op
     int rc = lpvmpc_check_batch(h, B, "lpvmpc_lpv_batch"); if (rc) return rc;
     rc = lpvmpc_model_check(h, B, "lpvmpc_lpv_batch"); if (rc) return rc;
+    rc = lpvmpc_tracks_check(h, B, "lpvmpc_lpv_batch"); if (rc) return rc;
     const bool ctrl = h->cfg.kind == LPVMPC_KIND_CONTROLLER;
     if (!x0 || !u_prev) return fail(h, LPVMPC_E_ARG, "lpvmpc_lpv_batch: x0 / u_prev is NULL");
     if (ctrl && !vel_ref) return fail(h, LPVMPC_E_ARG, "lpvmpc_lpv_batch: controller needs vel_ref");
@@ -434,12 +440,13 @@ extern "C" int lpvmpc_estimate_abc_batch(lpvmpc_handle *h, int32_t B, const doub
     if (h && B == 0) return LPVMPC_OK;                                   // an empty batch is a no-op
     int rc = lpvmpc_check_batch(h, B, "lpvmpc_estimate_abc_batch"); if (rc) return rc;
     rc = lpvmpc_model_check(h, B, "lpvmpc_estimate_abc_batch"); if (rc) return rc;
+    rc = lpvmpc_tracks_check(h, B, "lpvmpc_estimate_abc_batch"); if (rc) return rc;
     if (!xlast || !delta) return fail(h, LPVMPC_E_ARG, "lpvmpc_estimate_abc_batch: NULL input");
     rc = lpvmpc_need_track(h, "lpvmpc_estimate_abc_batch"); if (rc) return rc;
     const size_t N = h->cfg.N, nx = h->nx, nb = h->nb, b = B;
     hipStream_t st = h->stream;
     H2D(h->d_xlast, xlast, b * N * 6 * 8); H2D(h->d_delta, delta, b * N * 8);
-    HIP_TRY(h, lpvmpc::launch_abc(h->dev, h->d_cfg, h->d_model, B, h->d_xlast, h->d_delta, h->d_AB, st));
+    HIP_TRY(h, lpvmpc::launch_abc(h->dev, h->d_cfg, h->d_model, B, h->d_xlast, h->d_delta, h->d_AB, st, nullptr, lpvmpc_trk(h), h->d_trk_model));
     std::vector<double> ab(b * N * nx * nb);
     D2H(ab.data(), h->d_AB, ab.size() * 8);
     HIP_TRY(h, hipStreamSynchronize(st));
@@ -497,6 +504,7 @@ extern "C" int lpvmpc_solve_batch_dev(lpvmpc_handle *h, int32_t B, const double 
     if (h && B == 0) return LPVMPC_OK;                                   // an empty batch is a no-op
     int rc = lpvmpc_check_batch(h, B, "lpvmpc_solve_batch_dev"); if (rc) return rc;
     rc = lpvmpc_model_check(h, B, "lpvmpc_solve_batch_dev"); if (rc) return rc;
+    rc = lpvmpc_tracks_check(h, B, "lpvmpc_solve_batch_dev"); if (rc) return rc;
     rc = lpvmpc_tuning_check(h, B, "lpvmpc_solve_batch_dev"); if (rc) return rc;
     const bool ctrl = h->cfg.kind == LPVMPC_KIND_CONTROLLER;
     if (!x0 || !u_prev || !xPred || !uPred) return fail(h, LPVMPC_E_ARG, "lpvmpc_solve_batch_dev: NULL x0 / u_prev / xPred / uPred");
@@ -576,6 +584,7 @@ extern "C" int lpvmpc_solve_batch(lpvmpc_handle *h, int32_t B, const double *x0,
     if (h && B == 0) return LPVMPC_OK;                                   // an empty batch is a no-op
     int rc = lpvmpc_check_batch(h, B, "lpvmpc_solve_batch"); if (rc) return rc;
     rc = lpvmpc_model_check(h, B, "lpvmpc_solve_batch"); if (rc) return rc;
+    rc = lpvmpc_tracks_check(h, B, "lpvmpc_solve_batch"); if (rc) return rc;
     rc = lpvmpc_tuning_check(h, B, "lpvmpc_solve_batch"); if (rc) return rc;
     const bool ctrl = h->cfg.kind == LPVMPC_KIND_CONTROLLER;
     if (!x0 || !u_prev) return fail(h, LPVMPC_E_ARG, "lpvmpc_solve_batch: x0 / u_prev is NULL");
@@ -615,6 +624,7 @@ extern "C" int lpvmpc_solve_batch_masked(lpvmpc_handle *h, int32_t B, const doub
     if (h && B == 0) return LPVMPC_OK;                                   // an empty batch is a no-op
     int rc = lpvmpc_check_batch(h, B, "lpvmpc_solve_batch_masked"); if (rc) return rc;
     rc = lpvmpc_model_check(h, B, "lpvmpc_solve_batch_masked"); if (rc) return rc;
+    rc = lpvmpc_tracks_check(h, B, "lpvmpc_solve_batch_masked"); if (rc) return rc;
     rc = lpvmpc_tuning_check(h, B, "lpvmpc_solve_batch_masked"); if (rc) return rc;
     if (!active) return fail(h, LPVMPC_E_ARG, "lpvmpc_solve_batch_masked: active is NULL");
     std::vector<int32_t> rows;
@@ -650,10 +660,13 @@ extern "C" int lpvmpc_local_position_batch(lpvmpc_handle *h, int32_t B, const do
     int rc = lpvmpc_check_batch(h, B, "lpvmpc_local_position_batch"); if (rc) return rc;
     if (!xy_psi || !out) return fail(h, LPVMPC_E_ARG, "lpvmpc_local_position_batch: NULL argument");
     rc = lpvmpc_need_track(h, "lpvmpc_local_position_batch"); if (rc) return rc;
+    rc = lpvmpc_tracks_check(h, B, "lpvmpc_local_position_batch"); if (rc) return rc;
     hipStream_t st = h->stream;
     // workspace reuse: inputs in d_xlast ([cap][N][6] >= [B][3]), outputs in d_states ([cap][N][nx] >= [B][4])
     H2D(h->d_xlast, xy_psi, (size_t)B * 3 * 8);
-    HIP_TRY(h, lpvmpc::launch_local_position(h->d_cfg, B, h->d_xlast, half_width, slack, h->d_states, st));
+    // bound: every instance on its own track, with that track's half width and slack (the call's are ignored)
+    if (h->trk.tab) HIP_TRY(h, lpvmpc::launch_local_position_trk(h->trk, B, h->d_xlast, h->d_states, st));
+    else HIP_TRY(h, lpvmpc::launch_local_position(h->d_cfg, B, h->d_xlast, half_width, slack, h->d_states, st));
     D2H(out, h->d_states, (size_t)B * 4 * 8);
     HIP_TRY(h, hipStreamSynchronize(st));
     return LPVMPC_OK;
@@ -664,9 +677,11 @@ extern "C" int lpvmpc_global_position_batch(lpvmpc_handle *h, int32_t B, const d
     int rc = lpvmpc_check_batch(h, B, "lpvmpc_global_position_batch"); if (rc) return rc;
     if (!s_ey || !out) return fail(h, LPVMPC_E_ARG, "lpvmpc_global_position_batch: NULL argument");
     rc = lpvmpc_need_track(h, "lpvmpc_global_position_batch"); if (rc) return rc;
+    rc = lpvmpc_tracks_check(h, B, "lpvmpc_global_position_batch"); if (rc) return rc;
     hipStream_t st = h->stream;
     H2D(h->d_xlast, s_ey, (size_t)B * 2 * 8);
-    HIP_TRY(h, lpvmpc::launch_global_position(h->d_cfg, B, h->d_xlast, h->d_states, st));
+    if (h->trk.tab) HIP_TRY(h, lpvmpc::launch_global_position_trk(h->trk, B, h->d_xlast, h->d_states, st));
+    else HIP_TRY(h, lpvmpc::launch_global_position(h->d_cfg, B, h->d_xlast, h->d_states, st));
     D2H(out, h->d_states, (size_t)B * 3 * 8);
     HIP_TRY(h, hipStreamSynchronize(st));
     return LPVMPC_OK;
@@ -709,6 +724,10 @@ static int cl_init(lpvmpc_handle *h, int32_t B, const double *plant0, double hal
                    const std::vector<double> *veh = nullptr, const std::vector<double> *tyre = nullptr) {
     int rc = lpvmpc_check_common(h, B, "lpvmpc_cl_init"); if (rc) return rc;
     rc = lpvmpc_model_check(h, B, "lpvmpc_cl_init"); if (rc) return rc;
+    // a track binding acts on the start that takes every per-vehicle table (the tyre forms' kernels have the bound forms)
+    const char *entry = tyre ? "lpvmpc_cl_init_tyres" : veh ? "lpvmpc_cl_init_vehicles" : act ? "lpvmpc_cl_init_actuated" : "lpvmpc_cl_init";
+    if (!tyre) { rc = lpvmpc_tracks_unbound(h, h, entry, "lpvmpc_cl_init_tyres"); if (rc) return rc; }
+    rc = lpvmpc_tracks_check(h, B, "lpvmpc_cl_init"); if (rc) return rc;
     rc = lpvmpc_tuning_check(h, B, "lpvmpc_cl_init"); if (rc) return rc;
     if (h->cfg.kind != LPVMPC_KIND_CONTROLLER) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: controller handles only");
     if (h->race || h->race_owner) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_init: this handle takes part in a race (lpvmpc_cl_release on its path handle ends it)");
@@ -787,7 +806,11 @@ extern "C" int lpvmpc_cl_tick(lpvmpc_handle *h, int32_t n_ticks) {
     hipStream_t st = h->stream;
     for (int t = 0; t < n_ticks; ++t) {
         // the measurement of this tick: made by the launch that advanced the plant at the end of the previous tick, or here
+        const lpvmpc::TrackDev *trk = lpvmpc_trk(h);       // bound: the fleet was started by lpvmpc_cl_init_tyres, every vehicle on its own track
         if (h->cl_next_valid) { double *t_ = h->cl_local; h->cl_local = h->cl_local_next; h->cl_local_next = t_; }
+        else if (trk && h->obs_state) HIP_TRY(h, lpvmpc::launch_cl_observe_measure_trk(*trk, B, h->obs_state, h->cl_cmd, h->cl_q9, h->cl_local, h->d_uold,
+                                                                                        h->cfg.steering_delay, st));
+        else if (trk) HIP_TRY(h, lpvmpc::launch_cl_measure_trk(*trk, B, h->cl_plant, h->cl_cmd, h->cl_q9, h->cl_local, h->d_uold, h->cfg.steering_delay, st));
         else if (h->cl_actuated && h->obs_state) HIP_TRY(h, lpvmpc::launch_cl_observe_measure_act(h->d_cfg, B, h->obs_state, h->cl_cmd, h->cl_hw, h->cl_slack,
                                                                                                  h->cl_q9, h->cl_local, h->d_uold, h->cfg.steering_delay, st));
         else if (h->cl_actuated) HIP_TRY(h, lpvmpc::launch_cl_measure_act(h->d_cfg, B, h->cl_plant, h->cl_cmd, h->cl_hw, h->cl_slack, h->cl_q9, h->cl_local,
@@ -798,16 +821,28 @@ extern "C" int lpvmpc_cl_tick(lpvmpc_handle *h, int32_t n_ticks) {
         const double *x0 = h->cl_local; int x0_stride = 6;
         if (h->cl_first_it < 10) {                                           // CMAIN:310-315: seed mode
             HIP_TRY(h, lpvmpc::launch_cl_seed(B, N, h->cl_local, h->d_xlast, h->d_delta, st));
-            HIP_TRY(h, lpvmpc::launch_abc(h->dev, h->d_cfg, h->d_model, B, h->d_xlast, h->d_delta, h->d_AB, st));
+            HIP_TRY(h, lpvmpc::launch_abc(h->dev, h->d_cfg, h->d_model, B, h->d_xlast, h->d_delta, h->d_AB, st, nullptr, trk, h->d_trk_model));
             h->cl_first_it++;
         } else {                                                             // CMAIN:325-331: LPV prediction, x0 = first rolled-out state
-            HIP_TRY(h, lpvmpc::launch_lpv(h->dev, h->d_cfg, h->d_model, B, h->cl_local, h->d_uPred, h->d_vel, nullptr, 60.0, 0, h->d_states, h->d_AB, st));
+            HIP_TRY(h, lpvmpc::launch_lpv(h->dev, h->d_cfg, h->d_model, B, h->cl_local, h->d_uPred, h->d_vel, nullptr, 60.0, 0, h->d_states, h->d_AB, st,
+                                          nullptr, trk, h->d_trk_model));
             x0 = h->d_states; x0_stride = N * 6;
         }
         SolveArgs a{B, x0, h->d_AB, h->d_vel, h->d_uold, nullptr, h->d_xPred, h->d_uPred, h->d_status, h->d_iters, h->d_polish, h->d_resid,
                     nullptr, 0, x0_stride};
         int rc = lpvmpc_launch_solve_warm(h, a, st); if (rc) return rc;
-        if (h->cl_tyre.t && h->obs_state && h->ov.L)
+        if (trk && h->obs_state && h->ov.L)
+            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_trk_obsveh(*trk, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, tyre_plant(h->cl_veh, h->cl_tyre), h->cl_q9,
+                                                                          h->cl_local_next, h->d_uold, h->cfg.steering_delay,
+                                                                          lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, h->cl_act.d, st));
+        else if (trk && h->obs_state)
+            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_trk(*trk, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, tyre_plant(h->cl_veh, h->cl_tyre), h->cl_q9,
+                                                                   h->cl_local_next, h->d_uold, h->cfg.steering_delay, h->obs_gains, h->obs_state, h->obs_p,
+                                                                   h->cl_act.d, st));
+        else if (trk)
+            HIP_TRY(h, lpvmpc::launch_cl_command_plant_measure_trk(*trk, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, tyre_plant(h->cl_veh, h->cl_tyre), h->cl_q9,
+                                                                   h->cl_local_next, h->d_uold, h->cfg.steering_delay, h->cl_act.d, st));
+        else if (h->cl_tyre.t && h->obs_state && h->ov.L)
             HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_tyre_obsveh(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, tyre_plant(h->cl_veh, h->cl_tyre),
                                                                             h->cl_hw, h->cl_slack, h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay,
                                                                             lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, h->cl_act.d, st));

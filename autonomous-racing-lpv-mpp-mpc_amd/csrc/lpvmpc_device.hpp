@@ -120,11 +120,14 @@ size_t solve_lds_bytes(int kind, int N);
 hipError_t launch_solve(const DevCfg &cfg, const DevCfg *dcfg, const SolveArgs &a, hipStream_t stream, int force_generic);
 // active: optional [B] instance mask (null: every instance); a masked instance's rows of states / AB are not written.
 // model: the handle's per-vehicle model table (below), or null: the handle's own vehicle words
+// trk: the handle's track binding (below), or null: the configuration's own table; own_model: with trk, the binding's table of the
+// handle's own vehicle words, which the bound forms read where model is null
+struct TrackDev;
 hipError_t launch_lpv(const DevCfg &cfg, const DevCfg *dcfg, const double *model, int B, const double *x0, const double *u_prev,
                       const double *vel_ref, const double *curv_s, double cf_new, int lap, double *states, double *AB, hipStream_t stream,
-                      const int32_t *active = nullptr);
+                      const int32_t *active = nullptr, const TrackDev *trk = nullptr, const double *own_model = nullptr);
 hipError_t launch_abc(const DevCfg &cfg, const DevCfg *dcfg, const double *model, int B, const double *xlast, const double *delta, double *AB,
-                      hipStream_t stream, const int32_t *active = nullptr);
+                      hipStream_t stream, const int32_t *active = nullptr, const TrackDev *trk = nullptr, const double *own_model = nullptr);
 // per-vehicle model parameters (veh_lpv_eval.hip; lpvmpc_set_model_params, include/lpvmpc.h "Per-vehicle model parameters"): the
 // handle's table [kModelWords][B], parameter-major and vehicle-minor like the plant table below, indexed by vehicle (not by launch
 // slot: masked launches read the rows of the vehicles they run).  The launchers of the per-vehicle forms, called by the two above
@@ -135,6 +138,19 @@ void launch_lpv_veh(int kind, const DevCfg *dcfg, const double *model, int B, co
                     const double *curv_s, int lap, double *states, double *AB, hipStream_t stream, const int32_t *active);
 void launch_abc_veh(int kind, const DevCfg *dcfg, const double *model, int B, int N, const double *xlast, const double *delta, double *AB,
                     hipStream_t stream, const int32_t *active);
+
+// per-vehicle tracks (track_view.hpp; lpvmpc_set_tracks, include/lpvmpc.h "Per-vehicle tracks"): the launchers of the bound forms
+// (track_vehicles.hip: the stand-alone transforms; track_lpv_eval.hip: the LPV / ABC kernels that read the track, called by the two
+// launchers above).  model: a table [kModelWords][B], never null: the handle's bound model rows, or the binding's table of the handle's
+// own words
+hipError_t launch_local_position_trk(const TrackDev &trk, int B, const double *xypsi, double *out, hipStream_t s);
+hipError_t launch_global_position_trk(const TrackDev &trk, int B, const double *sey, double *out, hipStream_t s);
+void launch_ctrl_lpv_roll_trk(const DevCfg *dcfg, const TrackDev &trk, int B, const double *x0, const double *u_prev, const double *curv_ref,
+                              int lap, double *states, double *AB, hipStream_t stream, const int32_t *active);
+void launch_plan_lpv_trk(const DevCfg *dcfg, const TrackDev &trk, const double *model, int B, const double *x0, const double *u_prev,
+                         const double *SS, double *states, double *AB, hipStream_t stream, const int32_t *active);
+void launch_abc_trk(int kind, const DevCfg *dcfg, const TrackDev &trk, const double *model, int B, int N, const double *xlast,
+                    const double *delta, double *AB, hipStream_t stream, const int32_t *active);
 
 // closed-loop helpers (closed_loop.hip)
 struct PlantCfg { double lf, lr, m, Iz, mu, dt; int n_sub; };
@@ -305,5 +321,28 @@ hipError_t launch_race_command_plant_observe_veh_obsveh(const RaceDev &r, const 
                                                         const ObsParams &op, const ActDev &a, hipStream_t s);
 hipError_t launch_race_command_plant_observe_tyre_obsveh(const RaceDev &r, const TyrePlantCfg &pc, const ObsVehGains &gains, double *obs,
                                                          const ObsParams &op, const ActDev &a, hipStream_t s);
+// track_vehicles.hip: the bound forms of the lap-0 fleet's kernels that read the track (the tyre forms, lpvmpc_cl_init_tyres); half
+// width and slack are each vehicle's track's
+hipError_t launch_cl_measure_trk(const TrackDev &trk, int B, const double *plant, const double *cmd, int q9_swap, double *local_state,
+                                 double *u_old, int sd, hipStream_t s);
+hipError_t launch_cl_command_plant_measure_trk(const TrackDev &trk, int B, int N, const double *uPred, double *cmd, double *plant,
+                                               const TyrePlantCfg &pc, int q9_swap, double *local_next, double *u_old, int sd,
+                                               const ActDev &a, hipStream_t s);
+hipError_t launch_cl_observe_measure_trk(const TrackDev &trk, int B, const double *obs, const double *cmd, int q9_swap, double *local_state,
+                                         double *u_old, int sd, hipStream_t s);
+hipError_t launch_cl_command_plant_observe_trk(const TrackDev &trk, int B, int N, const double *uPred, double *cmd, double *plant,
+                                               const TyrePlantCfg &pc, int q9_swap, double *local_next, double *u_old, int sd,
+                                               const double *gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s);
+hipError_t launch_cl_command_plant_observe_trk_obsveh(const TrackDev &trk, int B, int N, const double *uPred, double *cmd, double *plant,
+                                                      const TyrePlantCfg &pc, int q9_swap, double *local_next, double *u_old, int sd,
+                                                      const ObsVehGains &gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s);
+
+// track_race.hip: the bound forms of the race's, the hand-off's and the recorder's kernels that read the track (RecDev: record.hpp)
+struct RecDev;
+hipError_t launch_race_plan_start_trk(const DevCfg *pcfg, const TrackDev &trk, const RaceDev &r, hipStream_t s);
+hipError_t launch_race_measure_trk(const DevCfg *ccfg, const TrackDev &trk, const RaceDev &r, int seed_tick, int sd, hipStream_t s);
+hipError_t launch_plan_pose_trk(const DevCfg *dcfg, const TrackDev &trk, int B, const double *xPred, double *SS, double *pose, double *sig,
+                                hipStream_t s, const int32_t *active = nullptr);
+hipError_t launch_race_record_trk(const TrackDev &trk, const RecDev &r, int t, int slot, hipStream_t s);
 
 }  // namespace lpvmpc

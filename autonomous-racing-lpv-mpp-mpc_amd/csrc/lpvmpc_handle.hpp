@@ -12,6 +12,7 @@
 
 #include "lpvmpc.h"
 #include "lpvmpc_device.hpp"
+#include "track_view.hpp"
 
 #define LPVMPC_HIDDEN __attribute__((visibility("hidden")))
 
@@ -118,8 +119,15 @@ struct ObsVehTable {                    // per-vehicle estimator (lpvmpc_set_obs
     bool ov_designed = false;           // the tables were designed on the device, on the limit tables ov_lim (LS, HS)
     double ov_lim[24] = {};
 };
+struct TrackTable {                     // per-vehicle tracks (lpvmpc_set_tracks, tracks_api.hip): the palette and the index per vehicle on the device (trk,
+    DevArena trk_mem;                   // the bound kernels' argument; trk.tab null: the configuration's own table), the table [kModelWords][trk.B] of the handle's
+    lpvmpc::TrackDev trk{};             // own vehicle words that the bound LPV / ABC kernels read on a handle without model rows, and the binding as it was
+    double *d_trk_model = nullptr;      // set, on the host, for the read-back and the comparison of a race's three bindings
+    std::vector<int32_t> trk_rows, trk_of;
+    std::vector<double> trk_tables, trk_hw, trk_slack;
+};
 
-struct lpvmpc_handle : Workspace, Fleet, ObsState, ObsGains, ObsStage, DeferPools, Handoff, ModelTable, TuneTable, ObsVehTable {
+struct lpvmpc_handle : Workspace, Fleet, ObsState, ObsGains, ObsStage, DeferPools, Handoff, ModelTable, TuneTable, ObsVehTable, TrackTable {
     lpvmpc_config cfg{};
     DevCfg dev{};
     DevArena mem;                       // what lives as long as the handle: d_cfg, dstats, the device staging buffers
@@ -224,6 +232,18 @@ LPVMPC_HIDDEN int lpvmpc_race_init_rows(lpvmpc_handle *h, lpvmpc_handle *tt, lpv
 // model_params_api.hip: lpvmpc_model_check refuses a batch size other than that of the handle's bound model rows (unbound: any);
 // called by every entry point that linearises, before anything is launched
 LPVMPC_HIDDEN int lpvmpc_model_check(lpvmpc_handle *h, int B, const char *who);
+// tracks_api.hip: lpvmpc_tracks_check refuses a batch size other than that of the handle's track binding (unbound: any); called by every
+// entry point the binding acts on, before anything is launched.  lpvmpc_tracks_unbound refuses a bound handle on an entry point the
+// binding does not act on; general: the entry point that starts the same engine on a bound handle (null: none does).  lpvmpc_trk:
+// the `trk` argument of lpvmpc::launch_lpv / launch_abc (null: unbound)
+LPVMPC_HIDDEN int lpvmpc_tracks_check(lpvmpc_handle *h, int B, const char *who);
+LPVMPC_HIDDEN int lpvmpc_tracks_unbound(lpvmpc_handle *h, const lpvmpc_handle *bound, const char *who, const char *general = nullptr);
+// the two handles carry the same binding (a race's three handles must)
+inline bool lpvmpc_tracks_equal(const lpvmpc_handle *a, const lpvmpc_handle *b) {
+    return a->trk.T == b->trk.T && a->trk.B == b->trk.B && a->trk_rows == b->trk_rows && a->trk_of == b->trk_of && a->trk_tables == b->trk_tables &&
+           a->trk_hw == b->trk_hw && a->trk_slack == b->trk_slack;
+}
+inline const lpvmpc::TrackDev *lpvmpc_trk(const lpvmpc_handle *h) { return h->trk.tab ? &h->trk : nullptr; }
 // tunings_api.hip: lpvmpc_tuning_check refuses a batch size other than that of the handle's bound tuning rows (unbound: any);
 // called by every entry point that solves, before anything is launched.  lpvmpc_solve_tune fills SolveArgs::tune of a launch that
 // sets instances up (main launches, with or without riders; a resume pass reads no row) and refuses one the table does not cover

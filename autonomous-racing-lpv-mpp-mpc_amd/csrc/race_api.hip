@@ -64,8 +64,20 @@ static int race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, i
         return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: needs two controller handles (path, tt) and a planner handle");
     if (h->cfg.device != tt->cfg.device || h->cfg.device != plan->cfg.device)
         return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: the three handles live on different devices");
-    if (h->cfg.N != tt->cfg.N || h->cfg.dt != tt->cfg.dt || h->cfg.track_rows != tt->cfg.track_rows ||
-        std::memcmp(h->cfg.track, tt->cfg.track, sizeof(double) * 6 * h->cfg.track_rows) != 0)
+    // per-vehicle tracks (lpvmpc_set_tracks): all three handles carry equal bindings, or none does; equal bindings replace the
+    // comparison of the handles' own tables
+    const int n_bound = (h->trk.tab != nullptr) + (tt->trk.tab != nullptr) + (plan->trk.tab != nullptr);
+    if (n_bound != 0 && n_bound != 3)
+        return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: %d of the three handles have per-vehicle tracks bound (lpvmpc_set_tracks); bind path, tt and "
+                    "planner with equal bindings, or none", n_bound);
+    if (n_bound == 3 && !tyre)
+        return lpvmpc_tracks_unbound(h, h, veh ? "lpvmpc_race_init_vehicles" : act ? "lpvmpc_race_init_actuated" : observed_call ? "lpvmpc_race_init_observed" : "lpvmpc_race_init",
+                                     "lpvmpc_race_init_tyres");
+    if (n_bound == 3 && (!lpvmpc_tracks_equal(h, tt) || !lpvmpc_tracks_equal(h, plan)))
+        return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init_tyres: the track bindings (lpvmpc_set_tracks) of path, tt and planner differ in T, B, tables, "
+                    "widths, slacks or track_of");
+    if (h->cfg.N != tt->cfg.N || h->cfg.dt != tt->cfg.dt ||
+        (n_bound == 0 && (h->cfg.track_rows != tt->cfg.track_rows || std::memcmp(h->cfg.track, tt->cfg.track, sizeof(double) * 6 * h->cfg.track_rows) != 0)))
         return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: path and tt handles differ in N, dt or track");
     if (h->cfg.N > 20) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_init: the reference's seed trajectories have 20 rows (N <= 20)");
     if ((h->cfg.steering_delay != 0 || tt->cfg.steering_delay != 0) && !act)
@@ -89,6 +101,7 @@ static int race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, i
     rc = lpvmpc_check_common(h, B, "lpvmpc_race_init"); if (rc) return rc;
     rc = lpvmpc_check_common(tt, B, "lpvmpc_race_init(tt)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
     rc = lpvmpc_check_common(plan, B, "lpvmpc_race_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
+    rc = lpvmpc_tracks_check(h, B, "lpvmpc_race_init_tyres"); if (rc) return rc;      // (equal bindings: one check covers the three)
     rc = lpvmpc_model_check(h, B, "lpvmpc_race_init"); if (rc) return rc;
     rc = lpvmpc_model_check(tt, B, "lpvmpc_race_init(tt)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
     rc = lpvmpc_model_check(plan, B, "lpvmpc_race_init(planner)"); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(plan));
@@ -232,26 +245,33 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
     hipStream_t st = h->stream;
     for (int t = 0; t < n_ticks; ++t) {
         // planner ticks of the racing vehicles whose controller tick reads a new message (PMAIN:126-224, 257-308)
-        HIP_TRY(h, lpvmpc::launch_race_plan_start(p->d_cfg, d, st));
-        HIP_TRY(h, lpvmpc::launch_lpv(p->dev, p->d_cfg, p->d_model, B, p->d_x0, p->d_uPred, nullptr, d.SSp, 60.0, 0, p->d_states, p->d_AB, st, d.m_pcont));
-        HIP_TRY(h, lpvmpc::launch_abc(p->dev, p->d_cfg, p->d_model, B, p->d_xlast, p->d_delta, p->d_AB, st, d.m_pfirst));
+        // bound (lpvmpc_set_tracks on all three handles, equal): every kernel that reads the track takes its bound form
+        const lpvmpc::TrackDev *trk = lpvmpc_trk(h), *ttrk = lpvmpc_trk(tt), *ptrk = lpvmpc_trk(p);
+        if (ptrk) HIP_TRY(h, lpvmpc::launch_race_plan_start_trk(p->d_cfg, *ptrk, d, st));
+        else HIP_TRY(h, lpvmpc::launch_race_plan_start(p->d_cfg, d, st));
+        HIP_TRY(h, lpvmpc::launch_lpv(p->dev, p->d_cfg, p->d_model, B, p->d_x0, p->d_uPred, nullptr, d.SSp, 60.0, 0, p->d_states, p->d_AB, st, d.m_pcont,
+                                      ptrk, p->d_trk_model));
+        HIP_TRY(h, lpvmpc::launch_abc(p->dev, p->d_cfg, p->d_model, B, p->d_xlast, p->d_delta, p->d_AB, st, d.m_pfirst, ptrk, p->d_trk_model));
         SolveArgs pa{B, p->d_x0, p->d_AB, nullptr, nullptr, p->d_maxey, p->d_xPred, p->d_uPred, p->d_status, p->d_iters, p->d_polish, p->d_resid,
                      nullptr, 0, 5};
         pa.active = d.m_plan;
         int rc = lpvmpc_launch_solve_timed(p, pa, st); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(p));
-        HIP_TRY(h, lpvmpc::launch_plan_pose(p->d_cfg, B, p->d_xPred, d.SSp, d.pose, d.sig, st, d.m_plan));
+        if (ptrk) HIP_TRY(h, lpvmpc::launch_plan_pose_trk(p->d_cfg, *ptrk, B, p->d_xPred, d.SSp, d.pose, d.sig, st, d.m_plan));
+        else HIP_TRY(h, lpvmpc::launch_plan_pose(p->d_cfg, B, p->d_xPred, d.SSp, d.pose, d.sig, st, d.m_plan));
         HIP_TRY(h, lpvmpc::launch_resample(B, d.Np, d.M, p->d_Wop, p->d_FWop, d.sig, d.refs, st, d.m_plan));
         // measurement, lap logic, masks of the two controllers
         const int seed = r->ticks < 9;
-        if (r->actuated) HIP_TRY(h, lpvmpc::launch_race_measure_act(h->d_cfg, d, seed, r->sd, st));
+        if (trk) HIP_TRY(h, lpvmpc::launch_race_measure_trk(h->d_cfg, *trk, d, seed, r->sd, st));
+        else if (r->actuated) HIP_TRY(h, lpvmpc::launch_race_measure_act(h->d_cfg, d, seed, r->sd, st));
         else HIP_TRY(h, lpvmpc::launch_race_measure(h->d_cfg, d, seed, st));
         // path controller (CMAIN:310-336)
         const double *x0 = d.local; int x0_stride = 6;
         if (seed) {                                                          // scratch only: unmasked
             HIP_TRY(h, lpvmpc::launch_cl_seed(B, N, d.local, h->d_xlast, h->d_delta, st));
-            HIP_TRY(h, lpvmpc::launch_abc(h->dev, h->d_cfg, h->d_model, B, h->d_xlast, h->d_delta, h->d_AB, st));
+            HIP_TRY(h, lpvmpc::launch_abc(h->dev, h->d_cfg, h->d_model, B, h->d_xlast, h->d_delta, h->d_AB, st, nullptr, trk, h->d_trk_model));
         } else {
-            HIP_TRY(h, lpvmpc::launch_lpv(h->dev, h->d_cfg, h->d_model, B, d.local, h->d_uPred, h->d_vel, nullptr, 60.0, 0, h->d_states, h->d_AB, st, d.m_path));
+            HIP_TRY(h, lpvmpc::launch_lpv(h->dev, h->d_cfg, h->d_model, B, d.local, h->d_uPred, h->d_vel, nullptr, 60.0, 0, h->d_states, h->d_AB, st, d.m_path,
+                                          trk, h->d_trk_model));
             x0 = h->d_states; x0_stride = N * 6;
         }
         SolveArgs ca{B, x0, h->d_AB, h->d_vel, h->d_uold, nullptr, h->d_xPred, h->d_uPred, h->d_status, h->d_iters, h->d_polish, h->d_resid,
@@ -259,7 +279,8 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
         ca.active = d.m_path;
         rc = lpvmpc_launch_solve_timed(h, ca, st); if (rc) return rc;
         // trajectory-tracking controller (CMAIN:361-363)
-        HIP_TRY(h, lpvmpc::launch_lpv(tt->dev, tt->d_cfg, tt->d_model, B, d.local, tt->d_uPred, tt->d_vel, tt->d_curv, 60.0, 1, tt->d_states, tt->d_AB, st, d.m_tt));
+        HIP_TRY(h, lpvmpc::launch_lpv(tt->dev, tt->d_cfg, tt->d_model, B, d.local, tt->d_uPred, tt->d_vel, tt->d_curv, 60.0, 1, tt->d_states, tt->d_AB, st, d.m_tt,
+                                      ttrk, tt->d_trk_model));
         SolveArgs ta{B, d.local, tt->d_AB, tt->d_vel, tt->d_uold, nullptr, tt->d_xPred, tt->d_uPred, tt->d_status, tt->d_iters, tt->d_polish,
                      tt->d_resid, nullptr, 0, 6};
         ta.active = d.m_tt;
@@ -280,7 +301,8 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
         if (lpvmpc_race_recorder *q = r->rec.get()) {                               // the recorder (record.hip)
             int slot = -1;
             if ((r->ticks - q->t_start) % q->stride == 0) { slot = q->total % q->capacity; q->total++; }
-            HIP_TRY(h, lpvmpc::launch_race_record(h->d_cfg, q->d, r->ticks, slot, st));
+            if (trk) HIP_TRY(h, lpvmpc::launch_race_record_trk(*trk, q->d, r->ticks, slot, st));
+            else HIP_TRY(h, lpvmpc::launch_race_record(h->d_cfg, q->d, r->ticks, slot, st));
         }
         r->ticks++;
     }

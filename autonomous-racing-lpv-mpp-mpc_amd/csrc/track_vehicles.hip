@@ -1,0 +1,162 @@
+// track_vehicles.hip -- the bound forms of the stand-alone track transforms and of the lap-0 fleet's kernels that read the track
+// (include/lpvmpc.h, "Per-vehicle tracks"): vehicle b is measured on its own entry of the handle's track palette, with that entry's
+// half width and slack (lpvmpc_set_tracks).  The transforms themselves are the view forms of track_view.hpp.
+//   local_position_trk_kernel, global_position_trk_kernel   local_position_kernel, global_position_kernel of closed_loop.hip
+//   cl_measure_trk_kernel                                   cl_measure_kernel<true> of fleet_kernels.hpp
+//   cl_command_plant_measure_trk_kernel                     cl_command_plant_measure_kernel<true, true, true>
+//   cl_command_plant_observe_trk_kernel<kObsVeh>            cl_command_plant_observe_kernel<true, true, true, kObsVeh>
+// The fleet forms exist for the most general start only (lpvmpc_cl_init_tyres: delayed forms with the plant and tyre tables), so
+// each restates that one form of its template with the vehicle's track view where the template passes the configuration -- the
+// same statements in the same order, compiled as tyre.o and observer_vehicles.o are, so that a palette entry equal to a handle's
+// table gives that handle's words.  Restated and not added to fleet_kernels.hpp as one more template flag: every object that
+// includes the header would have to be shown unchanged again, and a track argument in the shared signature changes the kernel
+// arguments of every form.  Their own object, so that closed_loop.o, tyre.o and observer_vehicles.o keep the code they have alone.
+#include "observer_device.hpp"
+#include "track_view.hpp"
+
+namespace lpvmpc {
+
+__global__ void __launch_bounds__(64) local_position_trk_kernel(TrackDev trk, int B, const double *__restrict__ in, double *__restrict__ out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double hw, slack;
+    const TrackView v = track_view(trk, b, hw, slack);
+    double s, ey, epsi; int inside;
+    local_position(v, hw, slack, in[b * 3 + 0], in[b * 3 + 1], in[b * 3 + 2], s, ey, epsi, inside);
+    out[b * 4 + 0] = s; out[b * 4 + 1] = ey; out[b * 4 + 2] = epsi; out[b * 4 + 3] = inside;
+}
+__global__ void __launch_bounds__(64) global_position_trk_kernel(TrackDev trk, int B, const double *__restrict__ in, double *__restrict__ out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double x, y, th;
+    global_position(track_view(trk, b), in[b * 2 + 0], in[b * 2 + 1], x, y, th);
+    out[b * 3 + 0] = x; out[b * 3 + 1] = y; out[b * 3 + 2] = th;
+}
+
+// first tick of a fleet without an estimator: the measurement of the start state and the controller's history
+__global__ void __launch_bounds__(64) cl_measure_trk_kernel(TrackDev trk, int B, const double *__restrict__ plant, const double *__restrict__ cmd,
+                                                            int q9_swap, double *__restrict__ local_state, double *__restrict__ u_old, int sd) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double hw, slack;
+    const TrackView v = track_view(trk, b, hw, slack);
+    cl_local(v, hw, slack, q9_swap, plant + (size_t)b * 8, local_state + (size_t)b * 6);
+    uold_push(u_old + (size_t)b * (2 + sd), sd, cmd[b * 2 + 0], cmd[b * 2 + 1]);
+}
+
+// command, n_sub simulator steps through the actuator stage with the vehicle's plant and tyre rows, then the next tick's measurement
+__global__ void __launch_bounds__(64) cl_command_plant_measure_trk_kernel(TrackDev trk, int B, int N, const double *__restrict__ uPred,
+                                                                          double *__restrict__ cmd, double *__restrict__ plant, TyrePlantCfg pc,
+                                                                          int q9_swap, double *__restrict__ local_next,
+                                                                          double *__restrict__ u_old, int sd, ActDev a) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double servo = uPred[(size_t)b * N * 2 + 0], motor = uPred[(size_t)b * N * 2 + 1];
+    cmd[b * 2 + 0] = servo; cmd[b * 2 + 1] = motor;
+    double st[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) st[i] = plant[(size_t)b * 8 + i];
+    const int k0 = a.k[b], La = a.La[b], Ld = a.Ld[b];
+    double sv = a.servo[b];
+    for (int k = 0; k < pc.n_sub; ++k) {
+        double ua, ud;
+        act_stage(a, b, k0 + k, La, Ld, motor, servo, sv, ua, ud);
+        plant_step_at(pc, b, st, ua, ud);
+    }
+    a.k[b] = k0 + pc.n_sub; a.servo[b] = sv;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) plant[(size_t)b * 8 + i] = st[i];
+    double hw, slack;
+    const TrackView v = track_view(trk, b, hw, slack);
+    cl_local(v, hw, slack, q9_swap, st, local_next + (size_t)b * 6);
+    uold_push(u_old + (size_t)b * (2 + sd), sd, servo, motor);
+}
+
+// the same with the estimator in the loop: per plant step, plant -> sensors -> observer; the next tick's measurement is made from
+// the estimate.  mode 0: only the measurement of the current estimate with u_old = cmd (the first tick of a fleet)
+template <bool kObsVeh>
+__global__ void __launch_bounds__(64) cl_command_plant_observe_trk_kernel(TrackDev trk, int B, int N, const double *__restrict__ uPred,
+                                                                          double *__restrict__ cmd, double *__restrict__ plant, TyrePlantCfg pc,
+                                                                          int q9_swap, double *__restrict__ local_next, double *__restrict__ u_old,
+                                                                          typename ObsGainsArg<kObsVeh>::type gains, double *__restrict__ obs,
+                                                                          ObsParams op, int mode, int sd, ActDev a) {
+    __shared__ double G[kObsGainWords];
+    if (mode != 0) obs_stage_gains(G, obs_gain_words(gains));
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double os[kObsStride];
+#pragma unroll
+    for (int i = 0; i < kObsStride; ++i) os[i] = obs[(size_t)b * kObsStride + i];
+    double servo = cmd[b * 2 + 0], motor = cmd[b * 2 + 1];
+    if (mode != 0) {
+        servo = uPred[(size_t)b * N * 2 + 0]; motor = uPred[(size_t)b * N * 2 + 1];
+        cmd[b * 2 + 0] = servo; cmd[b * 2 + 1] = motor;
+        double st[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) st[i] = plant[(size_t)b * 8 + i];
+        const long long vid = op.voff + b;
+        const int k0 = a.k[b], La = a.La[b], Ld = a.Ld[b];
+        double sv = a.servo[b];
+        for (int k = 0; k < pc.n_sub; ++k) {
+            // compiler-only barrier, as in the template: keeps the gain words' LDS loads inside the loop
+            asm volatile("" ::: "memory");
+            double ua, ud;
+            act_stage(a, b, k0 + k, La, Ld, motor, servo, sv, ua, ud);
+            plant_step_at(pc, b, st, ua, ud);
+            obs_substep<kObsVeh>(G, op, vid, os, st, servo, motor, obs_veh(gains), b);
+        }
+        a.k[b] = k0 + pc.n_sub; a.servo[b] = sv;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) plant[(size_t)b * 8 + i] = st[i];
+#pragma unroll
+        for (int i = 0; i < kObsStride; ++i) obs[(size_t)b * kObsStride + i] = os[i];
+    }
+    double hw, slack;
+    const TrackView v = track_view(trk, b, hw, slack);
+    obs_local_state(v, hw, slack, q9_swap, os, local_next + (size_t)b * 6);
+    uold_push(u_old + (size_t)b * (2 + sd), sd, servo, motor);
+}
+
+#define LPVMPC_GRID(n) dim3(((n) + 63) / 64), dim3(64)
+hipError_t launch_cl_measure_trk(const TrackDev &trk, int B, const double *plant, const double *cmd, int q9_swap, double *local_state,
+                                 double *u_old, int sd, hipStream_t s) {
+    hipLaunchKernelGGL(cl_measure_trk_kernel, LPVMPC_GRID(B), 0, s, trk, B, plant, cmd, q9_swap, local_state, u_old, sd);
+    return hipGetLastError();
+}
+hipError_t launch_cl_command_plant_measure_trk(const TrackDev &trk, int B, int N, const double *uPred, double *cmd, double *plant,
+                                               const TyrePlantCfg &pc, int q9_swap, double *local_next, double *u_old, int sd,
+                                               const ActDev &a, hipStream_t s) {
+    hipLaunchKernelGGL(cl_command_plant_measure_trk_kernel, LPVMPC_GRID(B), 0, s, trk, B, N, uPred, cmd, plant, pc, q9_swap, local_next, u_old, sd, a);
+    return hipGetLastError();
+}
+hipError_t launch_cl_observe_measure_trk(const TrackDev &trk, int B, const double *obs, const double *cmd, int q9_swap, double *local_state,
+                                         double *u_old, int sd, hipStream_t s) {
+    hipLaunchKernelGGL(cl_command_plant_observe_trk_kernel<false>, LPVMPC_GRID(B), 0, s, trk, B, 1, (const double *)nullptr, const_cast<double *>(cmd),
+                       (double *)nullptr, TyrePlantCfg{}, q9_swap, local_state, u_old, (const double *)nullptr, const_cast<double *>(obs),
+                       ObsParams{}, 0, sd, ActDev{});
+    return hipGetLastError();
+}
+hipError_t launch_cl_command_plant_observe_trk(const TrackDev &trk, int B, int N, const double *uPred, double *cmd, double *plant,
+                                               const TyrePlantCfg &pc, int q9_swap, double *local_next, double *u_old, int sd,
+                                               const double *gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s) {
+    hipLaunchKernelGGL(cl_command_plant_observe_trk_kernel<false>, LPVMPC_GRID(B), 0, s, trk, B, N, uPred, cmd, plant, pc, q9_swap, local_next, u_old,
+                       gains, obs, op, 1, sd, a);
+    return hipGetLastError();
+}
+hipError_t launch_cl_command_plant_observe_trk_obsveh(const TrackDev &trk, int B, int N, const double *uPred, double *cmd, double *plant,
+                                                      const TyrePlantCfg &pc, int q9_swap, double *local_next, double *u_old, int sd,
+                                                      const ObsVehGains &gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s) {
+    hipLaunchKernelGGL(cl_command_plant_observe_trk_kernel<true>, LPVMPC_GRID(B), 0, s, trk, B, N, uPred, cmd, plant, pc, q9_swap, local_next, u_old,
+                       gains, obs, op, 1, sd, a);
+    return hipGetLastError();
+}
+hipError_t launch_local_position_trk(const TrackDev &trk, int B, const double *xypsi, double *out, hipStream_t s) {
+    hipLaunchKernelGGL(local_position_trk_kernel, LPVMPC_GRID(B), 0, s, trk, B, xypsi, out);
+    return hipGetLastError();
+}
+hipError_t launch_global_position_trk(const TrackDev &trk, int B, const double *sey, double *out, hipStream_t s) {
+    hipLaunchKernelGGL(global_position_trk_kernel, LPVMPC_GRID(B), 0, s, trk, B, sey, out);
+    return hipGetLastError();
+}
+
+}  // namespace lpvmpc

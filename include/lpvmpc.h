@@ -935,6 +935,57 @@ int  lpvmpc_observer_step_vehicles_batch(lpvmpc_handle *h, int32_t B, const lpvm
                                          const double *u, const int32_t *k, double *aux, const double *rows, const double *L_ls,
                                          const double *L_hs);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Per-vehicle tracks: every instance of a batch is transformed and linearised on a track of its own instead of the one table of
+ * the handle's configuration: one batch on several circuits, mirrored or scaled variants of one, a tuning sweep crossed with a track
+ * sweep.  The binding is a palette of T tracks plus one palette index per vehicle, not B tables: a batch uses a handful of
+ * circuits, and a palette of at most LPVMPC_MAX_TRACKS * 768 bytes stays in the cache.  dt, N, the vehicle words, limits, weights
+ * and the OSQP settings stay the handle's.  Both entry points are new; a handle without a binding (the default) launches what it
+ * launched before.
+ *
+ * Host layout: track_rows [T] the rows of each track in use (2 .. LPVMPC_MAX_TRACK_ROWS); tables [T][LPVMPC_MAX_TRACK_ROWS * 6],
+ * the PointAndTangent rows [x, y, psi, cum_s, seg_len, curvature] of lpvmpc_config::track per track (rows beyond track_rows are
+ * ignored and read back as zero); half_width [T], slack [T]; track_of [B] the palette entry of each vehicle, 0 .. T-1.
+ *
+ * The binding belongs to the handle and acts on: lpvmpc_local_position_batch and lpvmpc_global_position_batch; wherever the
+ * handle linearises in a batch call: lpvmpc_lpv_batch, lpvmpc_estimate_abc_batch, lpvmpc_solve_batch, _masked and _dev (the
+ * curvature look-ups of the controller at lap 0, of its seed mode and of the planner); lpvmpc_handoff_batch on a bound planner
+ * handle (curvature and centre-line pose from each vehicle's track); the lap-0 fleet started through lpvmpc_cl_init_tyres and the
+ * race started through lpvmpc_race_init_tyres, the most general entry points (measurement from the plant or from the estimate, seed
+ * mode, the LPV roll-outs and the planner of every tick; with or without an estimator, per-vehicle estimator included).  Vehicle b
+ * takes track track_of[b]: indexed by vehicle, not by launch slot, so masked launches work unchanged.
+ *   - In a race path, tt and planner are bound separately and must carry equal bindings (T, B, track_rows, tables, half_width,
+ *     slack, track_of): all three, or none; anything else is refused.  Equal bindings replace the comparison of the handles' own
+ *     tables.  The lap-event rules take the vehicle's own lap length L: HalfTrack at s >= 3L/4, the event at s <= L/4, the racing
+ *     rule s >= L - L/10.  The recorder's track frame is the vehicle's own track, width and slack.  plan_max_ey stays one value per
+ *     race, max_ey the per-instance argument it is.
+ *   - Bound, every such call must have the binding's B: another B is refused with LPVMPC_E_ARG before anything is launched.
+ *   - lpvmpc_local_position_batch, lpvmpc_cl_init_tyres and lpvmpc_race_init_tyres (lpvmpc_race_config) take each track's half_width
+ *     and slack; the call's own are ignored, as mu_sim is ignored when plant rows are given.
+ *   - Every value is formed by the same operations in the same order as without a binding: an instance computes, word for word,
+ *     what a handle created with its track computes (called with that track's half width and slack), with or without model rows
+ *     bound beside the tracks.  A handle without model rows linearises on a table of its own vehicle words and takes the call's
+ *     cf_new as without a binding.
+ *   - lpvmpc_solve_batch_AB reads no track and is unaffected (any B).  A bound handle needs no track table of its own.
+ *   - The controller roll-out without its [A | B] blocks (states only) has no bound form: no entry point asks for it, and the
+ *     library refuses it by name (LPVMPC_E_ARG) rather than run another kernel.
+ *   - lpvmpc_cl_init, _actuated and _vehicles refuse a bound handle with LPVMPC_E_ARG and a message that names lpvmpc_cl_init_tyres
+ *     (with NULL rows it computes what they compute, word for word).  A vehicle of a bound fleet computes, bit for bit, what it
+ *     computes in a fleet on a handle created with its track.  lpvmpc_race_init, _observed, _actuated and _vehicles refuse bound
+ *     handles likewise and name lpvmpc_race_init_tyres.
+ *   - lpvmpc_cascade_init refuses a bound handle (controller or planner) with LPVMPC_E_ARG: the cascade runs on the handle's own
+ *     track.
+ * lpvmpc_set_tracks copies the binding to the device (synchronises); T = 0 or B = 0 unbinds (the arrays are then ignored).  Refused
+ * with LPVMPC_E_ARG, the binding unchanged: T outside 1 .. LPVMPC_MAX_TRACKS, a track_rows outside 2 .. LPVMPC_MAX_TRACK_ROWS, a
+ * non-finite table word in the rows in use, a segment length <= 0, a non-finite or negative half_width or slack, a track_of[b]
+ * outside 0 .. T-1, B < 0, a NULL array, and any call while the handle runs a fleet, cascade or race.  lpvmpc_destroy frees it.
+ * lpvmpc_tracks_read: *T and *B of the binding (0, 0: unbound) and, where not NULL, the arrays as they were set. */
+#define LPVMPC_MAX_TRACKS 64
+int  lpvmpc_set_tracks(lpvmpc_handle *h, int32_t T, const int32_t *track_rows, const double *tables, const double *half_width,
+                       const double *slack, int32_t B, const int32_t *track_of);
+int  lpvmpc_tracks_read(lpvmpc_handle *h, int32_t *T, int32_t *B, int32_t *track_rows, double *tables, double *half_width,
+                        double *slack, int32_t *track_of);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,8 +32,15 @@ the _vehicles race on that build.
 estimator in the loop (the fixture's gain tables, noisy sensors), unbound (the baseline) and with a per-vehicle estimator bound to the
 path engine (lpvmpc_set_observer_vehicles: nominal rows, tables designed on the device -- 7.7 KB of gain words per vehicle and observer
 step from global memory instead of one table in LDS), and, with --parent-lib FILE, the unbound race on that build.
+--tracks: the same protocol for the per-vehicle tracks (lpvmpc_set_tracks): the lpvmpc_race_init_tyres race with kind 0 rows, unbound
+(the baseline), with a one-entry palette of the handles' own track bound to the three engines (the bound forms of every kernel that reads
+the track, all lanes on one table), with the six-entry palette of track.palette(), track_of cycling (lap 0 from each track's grid; in
+phase: every vehicle as far before the end of its own lap as the fixture's start is on the L shape -- other circuits, so other QPs and
+other survivors), the same six tracks as six homogeneous sub-fleets of B / 6 vehicles ticked in turn in one process (the engines have
+no stream of their own to run side by side on), and, with --parent-lib FILE, the unbound race on that build.  Every line carries
+alive vehicle-ticks per second.
 Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator | --actuator | --record | --plant-params | --models | --tunings |
-       --tyres | --observer-vehicles [--parent-lib FILE] [--reps R]] [--out FILE]"""
+       --tyres | --observer-vehicles | --tracks [--parent-lib FILE] [--reps R]] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -65,8 +72,11 @@ def timed(tick, read, K):
 
 
 def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, record=False, plant_params=None, model_params=None, tunings=None,
-             tyre_params=None, observer_vehicles=False):
+             tyre_params=None, observer_vehicles=False, tracks=None):
     path, tt, plan = engines(mp, sd)
+    if tracks is not None:                                            # (maps, track_of) bound to the three engines
+        for e in (path, tt, plan):
+            e.set_tracks(*tracks)
     if observer_vehicles:                                             # nominal estimator rows, tables designed on the configuration's limits
         from lpvmpc.observer import OBS_PARAMS
         row = [OBS_PARAMS[k] for k in ("lf", "lr", "m", "I", "Cf", "Cr", "mu")]
@@ -108,6 +118,7 @@ def main():
     ap.add_argument("--tunings", action="store_true")
     ap.add_argument("--tyres", action="store_true")
     ap.add_argument("--observer-vehicles", action="store_true")
+    ap.add_argument("--tracks", action="store_true")
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--models-child", nargs=4, default=None, help=argparse.SUPPRESS)      # lib regime B bind: one run of --models
     a = ap.parse_args()
@@ -123,6 +134,9 @@ def main():
     if a.observer_vehicles:
         return models_main(a, [("estimator, unbound", "liblpvmpc.so", 7), ("estimator, rows bound", "liblpvmpc.so", 8)],
                            parent=("parent, estimator", 7))
+    if a.tracks:
+        return models_main(a, [("tyres, unbound", "liblpvmpc.so", 9), ("own track bound", "liblpvmpc.so", 10), ("six tracks bound", "liblpvmpc.so", 11),
+                               ("six sub-fleets", "liblpvmpc.so", 12)], parent=("parent, tyres", 9))
     if a.plant_params:
         return plant_params_main(a)
     if a.record:
@@ -284,25 +298,84 @@ def _models_starts(B):
     return {"lap0": (grid, 0, 10), "inphase": (np.tile(c["pre_plant"][0], (B, 1)), 1, int(c["pre_ticks"]) + 3)}
 
 
+def _tracks_starts(B, regime, maps, of, plant0):
+    """The starts of _models_starts on each vehicle's own track: lap 0 from the grid (every table starts at the origin, heading 0);
+    in phase: as far before the end of its own lap, and as far off the centre line and the tangent, as the fixture's start is on the
+    L shape."""
+    if regime == "lap0":
+        return plant0
+    from oracle import plant_ref as PR
+    import lpvmpc
+    ls = lpvmpc.Map("L_shape", 0.2)
+    s, ey, epsi, _ = PR.get_local_position(ls.PointAndTangent, ls.halfWidth, ls.slack, plant0[0, 0], plant0[0, 1], plant0[0, 6])
+    out = plant0.copy()
+    for t, m in enumerate(maps):
+        x, y, th = PR.get_global_position(m.PointAndTangent, m.TrackLength - (ls.TrackLength - s), ey)
+        out[of == t, 0], out[of == t, 1], out[of == t, 6] = x, y, th + epsi
+    return out
+
+
+def tracks_child(a, regime, B, bind):
+    """bind 10: the own track bound; 11: the six-entry palette; 12: the palette's tracks as six homogeneous sub-fleets ticked in turn."""
+    import lpvmpc
+    from lpvmpc import track as TK
+    mp = lpvmpc.Map("L_shape", 0.2)
+    plant0, half, warm = _models_starts(B)[regime]
+    tyres = lpvmpc.tyre_params(B, kind=0)
+    if bind == 10:
+        return race_run(mp, plant0, half, warm, a.ticks, tyre_params=tyres, tracks=([mp], np.zeros(B, np.int32)))
+    maps, of = TK.palette(), TK.cycle(B)
+    plant0 = _tracks_starts(B, regime, maps, of, plant0)
+    if bind == 11:
+        return race_run(mp, plant0, half, warm, a.ticks, tyre_params=tyres, tracks=(maps, of))
+    fleets = []
+    for t, m in enumerate(maps):
+        path, tt, plan = engines(m)
+        path.race_init(tt, plan, plant0[of == t], half_track0=half, laps=5, half_width=m.halfWidth, slack=m.slack,
+                       tyre_params=tyres[of == t])
+        fleets.append((path, tt, plan))
+    for _ in range(warm):
+        for f in fleets:
+            f[0].race_tick(1)
+    a0 = sum(f[0].race_laps()[1].sum() for f in fleets)
+    t0 = time.perf_counter()
+    for _ in range(a.ticks):
+        for f in fleets:
+            f[0].race_tick(1)
+    for f in fleets:
+        f[0].race_read()
+    ms = (time.perf_counter() - t0) * 1e3 / a.ticks
+    alive = sum(f[0].race_laps()[1].sum() for f in fleets) - a0
+    ph = sum(np.bincount(f[0].race_read()["phase"], minlength=4) for f in fleets)
+    for f in fleets:
+        for e in f:
+            e.close()
+    return ms, alive / (ms * a.ticks * 1e-3), ph
+
+
 def models_child(a):
     lib, regime, B, bind = a.models_child
     from lpvmpc import _ffi
     _ffi.LIB_PATH = os.path.join(os.path.dirname(_ffi.LIB_PATH), lib)
     import lpvmpc
+    if int(bind) >= 10:
+        ms, vps, ph = tracks_child(a, regime, int(B), int(bind))
+        print("MODELS_RUN %.6f %s %.4g" % (ms, ",".join(str(int(x)) for x in ph), vps), flush=True)
+        return
     mp = lpvmpc.Map("L_shape", 0.2)
     plant0, half, warm = _models_starts(int(B))[regime]
     rows = lpvmpc.model_params(int(B)) if int(bind) == 1 else None                # bind: 0 nothing, 1 nominal model rows, 2 / 3 tuning rows,
-    tyres = {5: lpvmpc.tyre_params(int(B), kind=0), 6: "pacejka"}.get(int(bind))   # 4 nominal plant rows (_vehicles), 5 / 6 tyre rows on top
+    tyres = {5: lpvmpc.tyre_params(int(B), kind=0), 6: "pacejka", 9: lpvmpc.tyre_params(int(B), kind=0)}.get(int(bind))   # 4 nominal plant rows (_vehicles), 5 / 6 tyre rows on top
     obs = None                                                                     # 7 / 8: _vehicles with the estimator, unbound / rows bound
-    if int(bind) >= 7:
+    if int(bind) in (7, 8):
         from lpvmpc.observer import observer_config
         f = np.load(os.path.join(ROOT, "tests", "golden", "estimator", "estimator.npz"))
         obs = observer_config(f["L_ls"], f["lim_ls"], f["L_hs"], f["lim_hs"], psi_std=0.01, psiDot_std=0.05, x_std=0.01, y_std=0.01,
                               v_std=0.02, seed=7)
-    ms, _vps, ph = race_run(mp, plant0, half, warm, a.ticks, model_params=rows, tunings={2: "own", 3: "sampled"}.get(int(bind)),
-                            plant_params="nominal" if int(bind) >= 4 else None, tyre_params=tyres, estimator=obs,
+    ms, vps, ph = race_run(mp, plant0, half, warm, a.ticks, model_params=rows, tunings={2: "own", 3: "sampled"}.get(int(bind)),
+                            plant_params="nominal" if int(bind) in (4, 5, 6, 7, 8) else None, tyre_params=tyres, estimator=obs,
                             observer_vehicles=int(bind) == 8)
-    print("MODELS_RUN %.6f %s" % (ms, ",".join(str(int(x)) for x in ph)), flush=True)
+    print("MODELS_RUN %.6f %s %.4g" % (ms, ",".join(str(int(x)) for x in ph), vps), flush=True)
 
 
 def models_main(a, cfgs=None, parent=("parent, unbound", 0)):
@@ -315,18 +388,19 @@ def models_main(a, cfgs=None, parent=("parent, unbound", 0)):
     for B in [int(x) for x in a.sizes.split(",")]:
         for regime in ("lap0", "inphase"):
             ms = {k: [] for k, _, _ in cfgs}
-            ph = {}
+            ph, vps = {}, {}
             for _ in range(a.reps):
                 for k, lib, bind in cfgs:
                     out = subprocess.run([sys.executable, os.path.abspath(__file__), "--ticks", str(a.ticks), "--models-child", lib, regime, str(B),
                                           str(bind)], check=True, capture_output=True, text=True, timeout=600).stdout
                     f = [l for l in out.splitlines() if l.startswith("MODELS_RUN")][-1].split()
-                    ms[k].append(float(f[1])); ph[k] = f[2]
+                    ms[k].append(float(f[1])); ph[k] = f[2]; vps.setdefault(k, []).append(float(f[3]))
             m0 = float(np.median(ms[base]))
             for k, _, _ in cfgs:
                 m = float(np.median(ms[k]))
-                lines.append("%-8s B=%5d  %-22s %.3f ms/tick (runs %s, spread %.3f, phases [%s])  vs %s %+.3f ms/tick"
-                             % (regime, B, k, m, " ".join("%.3f" % x for x in ms[k]), max(ms[k]) - min(ms[k]), ph[k], base.split(",")[0], m - m0))
+                lines.append("%-8s B=%5d  %-22s %.3f ms/tick (runs %s, spread %.3f, phases [%s], %.4g alive vehicle-ticks/s)  vs %s %+.3f ms/tick"
+                             % (regime, B, k, m, " ".join("%.3f" % x for x in ms[k]), max(ms[k]) - min(ms[k]), ph[k], float(np.median(vps[k])),
+                                base.split(",")[0], m - m0))
                 print(lines[-1], flush=True)
     if a.out:
         with open(a.out, "w") as f:

@@ -6,6 +6,8 @@ lap (HalfTrack = 1), so lap 0 is short.  The race runs until every vehicle has f
 Reports, binned by each sampled parameter (quartiles of its factor against the nominal row): vehicles, the fractions finished and
 lost, the median and p90 racing lap time (laps 1 .. laps of the finished vehicles' laps) and the median per-lap RMSE_ey of the
 racing laps (RaceFleet.lap_stats, CMAIN:101-106).
+--tracks oval,L_shape,... puts vehicle b on track b mod their number (lpvmpc_set_tracks, RaceFleet(track_map=<sequence>, track_of=...)):
+one race, one launch sequence, every vehicle with its own lap length, half width and slack; the report is the same.
 --model selects the controllers' and the planner's model of each vehicle (lpvmpc_set_model_params, RaceFleet(model_params=...)):
 nominal (default: today's run, same output), plant (each vehicle's model is its plant row: the matched experiment) or noisy:REL
 (the plant row times an independent uniform factor in [1 - REL, 1 + REL] per field: an identification error).  The nominal-car
@@ -38,6 +40,7 @@ def main():
     ap.add_argument("--model", default="nominal")
     ap.add_argument("--tyre", default="linear", choices=("linear", "pacejka"))
     ap.add_argument("--estimator", default=None, choices=("nominal", "plant"))
+    ap.add_argument("--tracks", default=None, help="comma-separated track shapes (oval, L_shape, 3110, Euge_Track): vehicle b races on track b mod their number")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.model not in ("nominal", "plant") and not a.model.startswith("noisy:"):
@@ -51,6 +54,12 @@ def main():
     rows = lpvmpc.sample_plant_params(B, a.seed, spread)
     nom = lpvmpc.plant_params(B)
     plant0 = start_line_fleet(mp.PointAndTangent, B, a.seed, 0.8, 0.97)
+    maps = track_of = None
+    if a.tracks:                                # the track axis: the same starts (same seed), each on the last quarter of the vehicle's own lap
+        maps = [lpvmpc.Map(t, 0.2) for t in a.tracks.split(",")]
+        track_of = (np.arange(B) % len(maps)).astype(np.int32)
+        for t, m in enumerate(maps):
+            plant0[track_of == t] = start_line_fleet(m.PointAndTangent, B, a.seed, 0.8, 0.97)[track_of == t]
 
     if a.model == "nominal":
         model_rows, model_text = None, "keep the nominal model (lf = lr = 0.125, m = 1.98, Iz = 0.03, Cf = Cr = 60, mu = 0.05)"
@@ -68,7 +77,7 @@ def main():
         obs = observer_config(g["L_ls"], g["lim_ls"], g["L_hs"], g["lim_hs"])
 
     def race(r, m=None, est_rows=None):
-        f = lpvmpc.RaceFleet(mp, plant0, laps=a.laps, half_track0=1, plant_params=r, model_params=m,
+        f = lpvmpc.RaceFleet(mp if maps is None else maps, plant0, laps=a.laps, half_track0=1, plant_params=r, model_params=m, track_of=track_of,
                              tyre_params="pacejka" if a.tyre == "pacejka" else None, estimator=obs, estimator_params=est_rows)
         assert np.array_equal(f.plant_params(), r)
         assert a.tyre == "linear" or np.array_equal(f.tyre_params(), lpvmpc.tyre_params(B))
