@@ -88,6 +88,11 @@ class ActuatorConfig(C.Structure):
     _fields_ = [("delay_a", _i), ("delay_df", _i), ("low_level_dyn", _i), ("reserved", _i), ("servo_tf", _d)]
 
 
+class DisturbanceConfig(C.Structure):
+    """Mirror of ``struct lpvmpc_disturbance_config`` (include/lpvmpc.h)."""
+    _fields_ = [("seed", C.c_uint64), ("vehicle_offset", C.c_int64), ("n_bound", _d)]
+
+
 class RaceRecordConfig(C.Structure):
     """Mirror of ``struct lpvmpc_race_record_config`` (include/lpvmpc.h)."""
     _fields_ = [("capacity", _i), ("stride", _i)]
@@ -128,6 +133,8 @@ PLANT_WORDS = 7                          # LPVMPC_PLANT_WORDS: [lf, lr, m, Iz, C
 PLANT_WORD_NAMES = ("lf", "lr", "m", "Iz", "Cf", "Cr", "mu")
 TYRE_WORDS = 4                           # LPVMPC_TYRE_WORDS: [kind, B, C, c_f] per vehicle (plant.py, "tyre rows")
 TYRE_WORD_NAMES = ("kind", "B", "C", "c_f")
+DIST_WORDS, DIST_STATE = 13, 5           # LPVMPC_DIST_WORDS, LPVMPC_DIST_STATE (disturbance.py)
+DIST_STREAM = 0xD157A2B3C4D5E6F7         # LPVMPC_DIST_STREAM
 MODEL_WORDS = 7                          # LPVMPC_MODEL_WORDS: the same words, as a controller's / planner's model of the vehicle
 MAX_TRACKS = 64                          # LPVMPC_MAX_TRACKS: entries of a track palette (track.pack_tracks)
 TUNING_WORDS = 64                        # LPVMPC_TUNING_WORDS: Q[36] R[4] dR[2] L_cf[6] limits[16] per instance (tuning.py)
@@ -154,7 +161,9 @@ EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_d
            "lpvmpc_tyre_force_batch",
            "lpvmpc_observer_default_design", "lpvmpc_observer_design_batch", "lpvmpc_set_observer_vehicles",
            "lpvmpc_observer_vehicles_read", "lpvmpc_observer_step_vehicles_batch",
-           "lpvmpc_set_tracks", "lpvmpc_tracks_read")
+           "lpvmpc_set_tracks", "lpvmpc_tracks_read",
+           "lpvmpc_disturbance_default_config", "lpvmpc_set_disturbances", "lpvmpc_disturbances_read",
+           "lpvmpc_plant_step_disturbed_batch")
 
 _lib = None
 
@@ -335,6 +344,17 @@ def load():
             getattr(lib, name).restype = C.c_int
     except AttributeError:
         pass
+    try:        # (nor the plant disturbances)
+        lib.lpvmpc_disturbance_default_config.argtypes = [P(DisturbanceConfig)]
+        lib.lpvmpc_disturbance_default_config.restype = None
+        lib.lpvmpc_set_disturbances.argtypes = [vp, _i, P(DisturbanceConfig), vp]
+        lib.lpvmpc_disturbances_read.argtypes = [vp, vp, vp]
+        lib.lpvmpc_plant_step_disturbed_batch.argtypes = [vp, _i, vp, vp, vp, _i, _d, _d, P(ActuatorConfig), vp, vp, vp, vp,
+                                                          P(DisturbanceConfig), vp, vp]
+        for name in ("lpvmpc_set_disturbances", "lpvmpc_disturbances_read", "lpvmpc_plant_step_disturbed_batch"):
+            getattr(lib, name).restype = C.c_int
+    except AttributeError:
+        pass
     try:        # (nor the race recorder)
         lib.lpvmpc_race_record.argtypes = [vp, P(RaceRecordConfig)]
         lib.lpvmpc_race_record_read.argtypes = [vp, _i, vp, vp, vp, vp]
@@ -383,6 +403,12 @@ def default_actuator_config():
 def default_observer_config():
     cfg = ObserverConfig()
     load().lpvmpc_observer_default_config(C.byref(cfg))
+    return cfg
+
+
+def default_disturbance_config():
+    cfg = DisturbanceConfig()
+    load().lpvmpc_disturbance_default_config(C.byref(cfg))
     return cfg
 
 

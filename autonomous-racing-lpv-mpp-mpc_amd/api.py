@@ -316,6 +316,53 @@ class BatchedSolver:
                                                              C.byref(cfg), ptr(la), ptr(ld), ptr(rows)))
         return st, act
 
+    def plant_step_disturbed(self, state, u, rows, dist_state=None, seed=0, vehicle_offset=0, n_bound=None, plant_params=None,
+                             tyre_params=None, act_state=None, n_sub=1, dt_sim=0.005, mu_sim=0.05, actuator=None, delay_a=None,
+                             delay_df=None):
+        """plant_step_vehicles as one control tick of n_sub steps with the plant disturbances in front of it
+        (lpvmpc_plant_step_disturbed_batch): ``rows`` [B, 13] (disturbance.disturbance_rows), ``dist_state`` [B, 5] = (d_ax, d_ay,
+        d_aw, ticks, gamma) carried between calls (None: fresh).  The grip patches are placed on this engine's track, or on its
+        track binding.  Returns (state, act_state, dist_state)."""
+        from .disturbance import check_disturbance_rows, disturbance_config
+        st = f64(state).reshape(-1, 8).copy(); B = st.shape[0]
+        u = f64(u, (B, 2), "u")
+        prow = _plant_rows(plant_params, B)
+        act = np.zeros((B, _ffi.ACT_WORDS)) if act_state is None else f64(act_state, (B, _ffi.ACT_WORDS), "act_state").copy()
+        ds = np.zeros((B, _ffi.DIST_STATE)) if dist_state is None else f64(dist_state, (B, _ffi.DIST_STATE), "dist_state").copy()
+        if dist_state is None:
+            ds[:, 4] = 1.0
+        cfg = _ffi.default_actuator_config() if actuator is None else _actuator_cfg(actuator)
+        la, ld = _delay_array(delay_a, B, "delay_a"), _delay_array(delay_df, B, "delay_df")
+        dc = disturbance_config(seed, vehicle_offset, n_bound)
+        r = check_disturbance_rows(rows, B)
+        self._chk(self._lib.lpvmpc_plant_step_disturbed_batch(self._h, B, ptr(st), ptr(act), ptr(u), int(n_sub), float(dt_sim), float(mu_sim),
+                                                              C.byref(cfg), ptr(la), ptr(ld), ptr(prow),
+                                                              ptr(None if tyre_params is None else _tyre_rows(tyre_params, B)),
+                                                              C.byref(dc), ptr(r), ptr(ds)))
+        return st, act, ds
+
+    def set_disturbances(self, rows, seed=0, vehicle_offset=0, n_bound=None):
+        """Attach plant disturbances to the lap-0 fleet or race this engine runs (lpvmpc_set_disturbances; the path engine, for a
+        race), from the next tick on: ``rows`` [B, 13] (disturbance.disturbance_rows / sample_disturbances).  The fleet or race must
+        have been started with ``tyre_params`` ("linear": kind 0 rows).  ``None`` detaches and restores the base plant / tyre rows."""
+        from .disturbance import check_disturbance_rows, disturbance_config
+        race = getattr(self, "_race", None) is not None
+        B = self._race[0] if race else getattr(self, "_cl_B", 0)
+        if rows is None:
+            self._chk(self._lib.lpvmpc_set_disturbances(self._h, B, None, None))
+            return
+        r = check_disturbance_rows(rows, np.asarray(rows).shape[0] if np.asarray(rows).ndim == 2 else B)
+        dc = disturbance_config(seed, vehicle_offset, n_bound)
+        self._chk(self._lib.lpvmpc_set_disturbances(self._h, r.shape[0], C.byref(dc), ptr(r)))
+
+    def disturbances_read(self):
+        """The attached rows [B, 13] and the model's state [B, 5] = (d_ax, d_ay, d_aw, ticks, gamma) (lpvmpc_disturbances_read)."""
+        race = getattr(self, "_race", None) is not None
+        B = self._race[0] if race else getattr(self, "_cl_B", 0)
+        rows, state = np.empty((B, _ffi.DIST_WORDS)), np.empty((B, _ffi.DIST_STATE))
+        self._chk(self._lib.lpvmpc_disturbances_read(self._h, ptr(rows), ptr(state)))
+        return rows, state
+
     def tyre_force(self, tyre_params, m, alpha):
         """The tyre curve on the device (lpvmpc_tyre_force_batch): force [B] of tyre row b at slip angle alpha [B] for mass m
         (scalar or [B]); tyre_params [B, 4] or "pacejka"."""
@@ -1165,12 +1212,15 @@ class RaceFleet(object):
     (BatchedSolver.set_observer_vehicles).  None: the estimator keeps its own constants and the configuration's tables.
     ``track_map``: one map, or a sequence of maps (a palette, at most 64: track.Map, track.mirrored, track.scaled, ...) with
     ``track_of`` [B], the palette entry of each vehicle: one race with vehicles on different circuits, each with its own lap length,
-    half width and slack (``tracks()`` reads the binding back; ``plan_max_ey`` stays one value per race)."""
+    half width and slack (``tracks()`` reads the binding back; ``plan_max_ey`` stays one value per race).
+    ``disturbance``: [B, 13] rows (disturbance.disturbance_rows, disturbance.sample_disturbances) or dict(rows=, seed=,
+    vehicle_offset=, n_bound=): gusts, a kick and grip patches on the plant from the first tick on (``disturb`` attaches or detaches
+    mid-race, ``disturbance()`` reads rows and state back); it selects ``tyre_params="linear"`` when none is given."""
 
     def __init__(self, track_map, plant0, laps=1, N=20, Np=40, half_track0=None, device=0, estimator=None, actuator=None,
                  steering_delay=0, delay_a=None, delay_df=None, plant_params=None, model_params=None, path_tunings=None,
                  tt_tunings=None, plan_tunings=None, tyre_params=None, estimator_params=None, estimator_design=None, track_of=None,
-                 **options):
+                 disturbance=None, **options):
         from .workloads import CTRL_TUNINGS, PLAN_L, PLAN_Q, PLAN_R, PLAN_dR
         race_keys = ("n_sub_lap0", "n_sub", "q9_swap", "plan_max_ey", "dt_sim", "mu_sim")
         race_opts = {k: v for k, v in options.items() if k in race_keys}
@@ -1234,9 +1284,21 @@ class RaceFleet(object):
                 e.set_tracks(maps, of)
             if tyre_params is None:
                 tyre_params = "linear"                           # the start that runs the binding (each track's width and slack)
+        if disturbance is not None and tyre_params is None:
+            tyre_params = "linear"                               # the start whose tables the disturbances scale
         self.path.race_init(self.tt, self.planner, plant0, half_track0=half_track0, laps=laps, half_width=track_map.halfWidth,
                             slack=track_map.slack, estimator=estimator, actuator=actuator, delay_a=delay_a, delay_df=delay_df,
                             plant_params=plant_params, tyre_params=tyre_params, **race_opts)
+        if disturbance is not None:
+            self.disturb(**disturbance) if isinstance(disturbance, dict) else self.disturb(disturbance)
+
+    def disturb(self, rows, seed=0, vehicle_offset=0, n_bound=None):
+        """Attach plant disturbances from the next tick on (BatchedSolver.set_disturbances on the path engine); ``None`` detaches."""
+        self.path.set_disturbances(rows, seed=seed, vehicle_offset=vehicle_offset, n_bound=n_bound)
+
+    def disturbance(self):
+        """The attached disturbance rows [B, 13] and the model's state [B, 5] (BatchedSolver.disturbances_read)."""
+        return self.path.disturbances_read()
 
     def run(self, n_ticks):
         """Enqueue n_ticks controller ticks (no synchronisation)."""

@@ -831,6 +831,7 @@ extern "C" int lpvmpc_cl_tick(lpvmpc_handle *h, int32_t n_ticks) {
         SolveArgs a{B, x0, h->d_AB, h->d_vel, h->d_uold, nullptr, h->d_xPred, h->d_uPred, h->d_status, h->d_iters, h->d_polish, h->d_resid,
                     nullptr, 0, x0_stride};
         int rc = lpvmpc_launch_solve_warm(h, a, st); if (rc) return rc;
+        if (h->cl_dist.d.rows) HIP_TRY(h, lpvmpc::launch_disturbance(h->d_cfg, trk, h->cl_dist.d, st));   // lpvmpc_set_disturbances
         if (trk && h->obs_state && h->ov.L)
             HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_trk_obsveh(*trk, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, tyre_plant(h->cl_veh, h->cl_tyre), h->cl_q9,
                                                                           h->cl_local_next, h->d_uold, h->cfg.steering_delay,

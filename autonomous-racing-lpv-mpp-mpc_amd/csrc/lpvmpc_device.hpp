@@ -345,4 +345,24 @@ hipError_t launch_plan_pose_trk(const DevCfg *dcfg, const TrackDev &trk, int B, 
                                 hipStream_t s, const int32_t *active = nullptr);
 hipError_t launch_race_record_trk(const TrackDev &trk, const RecDev &r, int t, int slot, hipStream_t s);
 
+// plant disturbances (disturbance.hip; lpvmpc_set_disturbances, include/lpvmpc.h "Plant disturbances"): the binding on the device,
+// passed by value to the one kernel that runs in front of a tick's command / plant kernel.  Every table is word-major [word][B]
+constexpr int kDistWords = 13;               // = LPVMPC_DIST_WORDS
+constexpr int kDistState = 5;                // = LPVMPC_DIST_STATE: d_ax, d_ay, d_aw, ticks, gamma
+struct DistDev {
+    const double *rows;                      // [kDistWords + 1][B]: the public words, then q = sqrt(1 - rho^2)
+    double *state;                           // [kDistState][B]
+    const double *base;                      // [3][B]: Cf, Cr of the base plant rows, c_f of the base tyre rows
+    double *live_p, *live_t;                 // the fleet's plant table [kPlantWords][B] and tyre table [kTyreWords][B]
+    double *plant;                           // [B][8]
+    const int32_t *k;                        // [B] ActDev::k, the vehicle's plant-step counter
+    const int32_t *nstep;                    // [B] plant steps of this tick (a race's), or null: n_fixed for every vehicle
+    int B, n_fixed;
+    double dt, n_bound, hw, slack;           // dt_sim; the clip in standard deviations; the unbound form's map width
+    unsigned long long seed;                 // the configuration's seed ^ LPVMPC_DIST_STREAM
+    long long voff;
+};
+// trk null: the handle's own track (dcfg, d.hw, d.slack); else every vehicle on its palette entry
+hipError_t launch_disturbance(const DevCfg *dcfg, const TrackDev *trk, const DistDev &d, hipStream_t s);
+
 }  // namespace lpvmpc

@@ -18,6 +18,7 @@
 
 struct lpvmpc_cascade;       // cascade_api.hip
 struct lpvmpc_race;          // race_api.hip
+struct DistStep;             // below: the stand-alone step's disturbance arguments
 
 using lpvmpc::DevCfg;
 using lpvmpc::SolveArgs;
@@ -50,6 +51,16 @@ struct TyreTable { const double *t = nullptr; DevArena mem; };   // tyre table [
 // the tyre forms' kernel argument: the plant table with its tyre table
 inline lpvmpc::TyrePlantCfg tyre_plant(const PlantTable &v, const TyreTable &y) { lpvmpc::TyrePlantCfg c; static_cast<lpvmpc::VehPlantCfg &>(c) = v.d; c.t = y.t; return c; }
 
+// plant disturbances of a fleet or race (lpvmpc_set_disturbances, disturbance_api.hip; d.rows null: none attached): the kernel
+// argument with its device memory, and on the host the rows as they were set and the base plant / tyre tables [word][B] that the
+// read-backs return and a detach restores
+struct DistBinding {
+    lpvmpc::DistDev d{};
+    DevArena mem;
+    lpvmpc_disturbance_config cfg{};
+    std::vector<double> rows, base_p, base_t;
+};
+
 struct EventRing {                      // ring of event pairs around launches (lpvmpc_set_timing)
     std::vector<hipEvent_t> e0, e1;
     int count = 0;                      // pairs recorded since timing was (re)enabled
@@ -81,6 +92,7 @@ struct Fleet {                          // closed-loop fleet (lpvmpc_cl_*): plan
     ActState cl_act;
     PlantTable cl_veh;                  // the fleet was started by lpvmpc_cl_init_vehicles: its plant table
     TyreTable cl_tyre;                  // the fleet was started by lpvmpc_cl_init_tyres: its tyre table as well
+    DistBinding cl_dist;                // lpvmpc_set_disturbances on that fleet (freed with it)
 };
 struct ObsState {                       // the fleet's / cascade's / race's estimator state [obs_B][kObsStride] (null: it runs on ground truth;
     DevArena obs_mem;                   // a race's is set by lpvmpc_race_init_observed without obs_cfg and freed with the race)
@@ -214,7 +226,8 @@ LPVMPC_HIDDEN const lpvmpc::VehPlantCfg *lpvmpc_race_plant(const lpvmpc_handle *
 // lpvmpc_plant_step_vehicles_batch with the checked tyre table [4][B] of tyre_api.hip (null: the per-vehicle forms' kernel)
 LPVMPC_HIDDEN int lpvmpc_plant_step_rows(lpvmpc_handle *h, int32_t B, double *state, double *act_state, const double *u, int32_t n_sub, double dt_sim,
                                          double mu_sim, const lpvmpc_actuator_config *act, const int32_t *delay_a, const int32_t *delay_df,
-                                         const double *plant_params, const std::vector<double> *tyre, const char *who);
+                                         const double *plant_params, const std::vector<double> *tyre, const char *who,
+                                         const DistStep *dist = nullptr);
 // tyre_api.hip: tyre rows (lpvmpc_*_tyres).  lpvmpc_tyre_rows checks the host rows [B][4] (null: kind 0 for every vehicle) and returns
 // the device layout [4][B] in t; nothing is allocated.  lpvmpc_tyre_upload allocates and fills the table in y, released first (synchronises)
 LPVMPC_HIDDEN int lpvmpc_tyre_rows(lpvmpc_handle *h, int B, const double *rows, const char *who, std::vector<double> &t);
@@ -229,6 +242,19 @@ LPVMPC_HIDDEN int lpvmpc_race_init_rows(lpvmpc_handle *h, lpvmpc_handle *tt, lpv
                                         const int32_t *half_track0, const lpvmpc_race_config *cfg, const lpvmpc_observer_config *obs,
                                         const lpvmpc_actuator_config *act, const int32_t *delay_a, const int32_t *delay_df,
                                         const double *plant_params, bool tyres, const double *tyre_params);
+// disturbance_api.hip: plant disturbances.  lpvmpc_race_dist (race_api.hip): the race's binding and what it acts on -- filled into t:
+// plant, step counters, this tick's step counts, dt_sim, the map's width and the live tables (false: the race has no tyre table).
+// lpvmpc_dist_rows checks cfg and the host rows [B][LPVMPC_DIST_WORDS] against each vehicle's lap length and returns the device
+// layout [LPVMPC_DIST_WORDS + 1][B] in t.  lpvmpc_dist_step: the stand-alone step's launch in front of its plant kernel, on tables
+// that live in mem; dist_state [B][LPVMPC_DIST_STATE] in (null: fresh), lpvmpc_dist_step_read copies it out after the step
+struct DistStep { const lpvmpc_disturbance_config *cfg; const double *rows; double *dist_state; };
+LPVMPC_HIDDEN DistBinding *lpvmpc_race_dist(lpvmpc_handle *h, lpvmpc::DistDev *t);
+LPVMPC_HIDDEN int lpvmpc_dist_rows(lpvmpc_handle *h, int B, const lpvmpc_disturbance_config *cfg, const double *rows, const char *who,
+                                   std::vector<double> &t);
+LPVMPC_HIDDEN int lpvmpc_dist_step(lpvmpc_handle *h, int B, const DistStep &ds, const std::vector<double> &rows_dev, const std::vector<double> &plant_tab,
+                                   const std::vector<double> &tyre_tab, double *d_plant, const int32_t *d_k, int n_sub, double dt_sim,
+                                   double *live_p, double *live_t, DistBinding &tmp, hipStream_t st);
+LPVMPC_HIDDEN int lpvmpc_dist_step_read(lpvmpc_handle *h, int B, const DistStep &ds, const DistBinding &tmp, hipStream_t st);
 // model_params_api.hip: lpvmpc_model_check refuses a batch size other than that of the handle's bound model rows (unbound: any);
 // called by every entry point that linearises, before anything is launched
 LPVMPC_HIDDEN int lpvmpc_model_check(lpvmpc_handle *h, int B, const char *who);

@@ -40,12 +40,14 @@ int lpvmpc_plant_upload(lpvmpc_handle *h, int B, const std::vector<double> &t, d
 
 int lpvmpc_plant_step_rows(lpvmpc_handle *h, int32_t B, double *state, double *act_state, const double *u, int32_t n_sub, double dt_sim,
                            double mu_sim, const lpvmpc_actuator_config *act, const int32_t *delay_a, const int32_t *delay_df,
-                           const double *plant_params, const std::vector<double> *tyre, const char *who) {
+                           const double *plant_params, const std::vector<double> *tyre, const char *who, const DistStep *dist) {
     if (h && B == 0) return LPVMPC_OK;
     int rc = lpvmpc_check_batch(h, B, who); if (rc) return rc;
     if (!state || !u || n_sub < 1 || !(dt_sim > 0) || (act && !act_state)) return fail(h, LPVMPC_E_ARG, "%s: bad argument", who);
     std::vector<double> tab;
     rc = lpvmpc_plant_rows(h, B, plant_params, h->cfg, mu_sim, who, tab); if (rc) return rc;
+    std::vector<double> dist_rows;                                  // lpvmpc_plant_step_disturbed_batch: the model in front of the step
+    if (dist) { rc = lpvmpc_dist_rows(h, B, dist->cfg, dist->rows, who, dist_rows); if (rc) return rc; }
     lpvmpc_actuator_config off;
     lpvmpc_actuator_default_config(&off);
     if (!act) { act = &off; delay_a = delay_df = nullptr; }
@@ -64,6 +66,7 @@ int lpvmpc_plant_step_rows(lpvmpc_handle *h, int32_t B, double *state, double *a
     ActState as;                                                    // (all freed when the call returns)
     PlantTable v;
     TyreTable y;
+    DistBinding dtmp;
     rc = lpvmpc_act_alloc(h, B, act, delay_a, delay_df, dt_sim, who, as); if (rc) return rc;
     const lpvmpc::ActDev &a = as.d;
     rc = lpvmpc_plant_upload(h, B, tab, dt_sim, n_sub, v);
@@ -72,9 +75,15 @@ int lpvmpc_plant_step_rows(lpvmpc_handle *h, int32_t B, double *state, double *a
     auto run = [&]() -> int {
         H2D(a.ring, ring.data(), ring.size() * 8); H2D(a.servo, sv.data(), b * 8); H2D(a.k, k.data(), b * 4);
         H2D(h->d_xlast, state, b * 8 * 8); H2D(h->d_states, u, b * 2 * 8);
+        if (dist) {
+            int rd = lpvmpc_dist_step(h, B, *dist, dist_rows, tab, *tyre, h->d_xlast, a.k, n_sub, dt_sim, const_cast<double *>(v.d.p),
+                                      const_cast<double *>(y.t), dtmp, st);
+            if (rd) return rd;
+        }
         if (y.t) HIP_TRY(h, lpvmpc::launch_plant_tyre(B, h->d_xlast, h->d_states, tyre_plant(v, y), a, st));
         else HIP_TRY(h, lpvmpc::launch_plant_veh(B, h->d_xlast, h->d_states, v.d, a, st));
         D2H(state, h->d_xlast, b * 8 * 8);
+        if (dist) { int rd = lpvmpc_dist_step_read(h, B, *dist, dtmp, st); if (rd) return rd; }
         if (act_state) return lpvmpc_act_download(h, a, act_state, st);   // (synchronises)
         HIP_TRY(h, hipStreamSynchronize(st));
         return LPVMPC_OK;
@@ -103,7 +112,9 @@ extern "C" int lpvmpc_plant_params_read(lpvmpc_handle *h, double *plant_params) 
     hipStream_t st = h->stream;
     const size_t B = v->B;
     std::vector<double> t(B * LPVMPC_PLANT_WORDS);
-    D2H(t.data(), v->p, t.size() * 8);
+    const DistBinding *dist = h->race ? lpvmpc_race_dist(h, nullptr) : &h->cl_dist;
+    if (dist && dist->d.rows) t = dist->base_p;                      // disturbances attached: the base rows, not the scaled live words
+    else D2H(t.data(), v->p, t.size() * 8);
     HIP_TRY(h, hipStreamSynchronize(st));
     for (size_t b = 0; b < B; ++b)
         for (size_t i = 0; i < LPVMPC_PLANT_WORDS; ++i) plant_params[b * LPVMPC_PLANT_WORDS + i] = t[i * B + b];

@@ -30,6 +30,7 @@ struct lpvmpc_race {
     PlantTable veh;               // lpvmpc_race_init_vehicles: the plant table (veh.d.p; null: one PlantCfg), with the delayed kernels' actuator
     TyreTable tyre;               // lpvmpc_race_init_tyres: the tyre table next to veh (tyre.t; null: the linear tyre's kernels)
     std::unique_ptr<lpvmpc_race_recorder> rec;   // lpvmpc_race_record (null: not recording)
+    DistBinding dist;             // lpvmpc_set_disturbances (dist.d.rows null: none attached), freed with the race
 };
 
 void lpvmpc_race_free(lpvmpc_handle *h) {
@@ -214,6 +215,19 @@ extern "C" int lpvmpc_race_init_vehicles(lpvmpc_handle *h, lpvmpc_handle *tt, lp
 const lpvmpc::VehPlantCfg *lpvmpc_race_plant(const lpvmpc_handle *h) { return h->race ? &h->race->veh.d : nullptr; }
 const double *lpvmpc_race_tyre(const lpvmpc_handle *h) { return h->race ? h->race->tyre.t : nullptr; }
 
+// the race's disturbance binding and, in t, what it acts on (null: no race, or one without plant and tyre tables)
+DistBinding *lpvmpc_race_dist(lpvmpc_handle *h, lpvmpc::DistDev *t) {
+    lpvmpc_race *r = h->race;
+    if (!r || !r->veh.d.p || !r->tyre.t) return nullptr;
+    if (t) {
+        *t = lpvmpc::DistDev{};
+        t->B = r->d.B; t->plant = r->d.plant; t->k = r->act.d.k; t->nstep = r->d.nstep; t->n_fixed = 0; t->dt = r->pc.dt;
+        t->hw = r->d.hw; t->slack = r->d.slack;
+        t->live_p = const_cast<double *>(r->veh.d.p); t->live_t = const_cast<double *>(r->tyre.t);
+    }
+    return &r->dist;
+}
+
 // the race's actuator state and its two controllers' histories (lpvmpc_actuator_read)
 int lpvmpc_race_act_read(lpvmpc_handle *h, double *act_state, double *path_hist, double *tt_hist) {
     lpvmpc_race *r = h->race;
@@ -285,6 +299,7 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
                      tt->d_resid, nullptr, 0, 6};
         ta.active = d.m_tt;
         rc = lpvmpc_launch_solve_timed(tt, ta, st); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
+        if (r->dist.d.rows) HIP_TRY(h, lpvmpc::launch_disturbance(h->d_cfg, trk, r->dist.d, st));   // lpvmpc_set_disturbances
         if (r->tyre.t && d.estv && h->ov.L)
             HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_tyre_obsveh(d, tyre_plant(r->veh, r->tyre), lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, r->act.d, st));
         else if (r->veh.d.p && d.estv && h->ov.L)

@@ -72,7 +72,9 @@ extern "C" int lpvmpc_tyre_params_read(lpvmpc_handle *h, double *tyre_params) {
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t st = h->stream;
     std::vector<double> v(B * LPVMPC_TYRE_WORDS);
-    D2H(v.data(), t, v.size() * 8);
+    const DistBinding *dist = h->race ? lpvmpc_race_dist(h, nullptr) : &h->cl_dist;
+    if (dist && dist->d.rows) v = dist->base_t;                      // disturbances attached: the base rows, not the scaled live words
+    else D2H(v.data(), t, v.size() * 8);
     HIP_TRY(h, hipStreamSynchronize(st));
     for (size_t b = 0; b < B; ++b)
         for (size_t i = 0; i < LPVMPC_TYRE_WORDS; ++i) tyre_params[b * LPVMPC_TYRE_WORDS + i] = v[i * B + b];

@@ -986,6 +986,64 @@ int  lpvmpc_set_tracks(lpvmpc_handle *h, int32_t T, const int32_t *track_rows, c
 int  lpvmpc_tracks_read(lpvmpc_handle *h, int32_t *T, int32_t *B, int32_t *track_rows, double *tables, double *half_width,
                         double *slack, int32_t *track_of);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Plant disturbances: gusts, a kick and low-grip patches for the vehicles of a lap-0 fleet or a race.  The reference's simulator has
+ * sensor noise only; its dynamics are deterministic and uniform along the lap.  The model here acts at the control tick, on every
+ * tick on which a vehicle's plant advances n > 0 simulator steps, after that tick's solve and immediately before its command / plant
+ * kernel (one more launch per tick; with nothing attached a tick issues the launches it always did).  k0 is the vehicle's own
+ * plant-step counter, j its own count of disturbed ticks since the binding was attached, vid = vehicle_offset + b.  In order:
+ *   1. grip: (s, ey, epsi, inside) = Map.getLocalPosition of the ground-truth plant pose on the vehicle's own track (the handle's
+ *      table, or the vehicle's palette entry where tracks are bound; with an estimator in the loop it still reads the plant).
+ *      gamma = the product of gamma_p over the patches p in {0, 1} that contain s, 1 when inside == 0 or no patch does.  A patch
+ *      contains s when d < len, d = s - s0 and d += L when d < 0 (L: the lap length of the vehicle's track, so a patch may span the
+ *      start line).  The live tables' words become Cf = gamma * Cf_base, Cr = gamma * Cr_base (plant row) and c_f = gamma * c_f_base
+ *      (tyre row): the linear tyre's stiffnesses and the Pacejka peak D.  gamma == 1 leaves the base words bit for bit.
+ *   2. gusts: for each channel c in {0: ax, 1: ay, 2: yaw acceleration} with sigma_c != 0,
+ *      g = clip(gauss(seed ^ LPVMPC_DIST_STREAM, vid, j, c), +-n_bound) on the estimator's counter-based generator;
+ *      d_c = sigma_c * g on j == 0, else d_c = rho * d_c + sigma_c * q * g with q = sqrt(1 - rho^2) formed once on the host: a
+ *      stationary first-order Gauss-Markov process of variance sigma_c^2 on every tick.  With T = n * dt_sim it is applied as an
+ *      impulse: vx = |vx + d_0 T|, vy += d_1 T, psiDot += d_2 T.  A channel with sigma_c == 0 draws nothing and adds nothing.
+ *   3. kick: if k0 <= kick_step < k0 + n: vy += kick_vy, psiDot += kick_w.  Once; kick_step < 0: never.
+ *   4. j += 1.
+ * Frozen vehicles (finished, lost) are not touched and their j stays put, so a vehicle's draws depend on (seed, vid, j) only: not on
+ * B, the other vehicles or how a fleet is sharded.  An all-off row (sigma = 0, kick_step = -1, len = 0 or gamma = 1) changes no word
+ * of plant or tables.
+ *
+ * Host layouts: rows [B][LPVMPC_DIST_WORDS] = {sigma_ax, sigma_ay, sigma_aw, rho, kick_step, kick_vy, kick_w, p0_s0, p0_len,
+ * p0_gamma, p1_s0, p1_len, p1_gamma}; state [B][LPVMPC_DIST_STATE] = {d_ax, d_ay, d_aw, ticks (= j), gamma (of the last disturbed
+ * tick; 1 before the first)}.
+ *
+ * lpvmpc_set_disturbances attaches rows to the lap-0 fleet or race that h runs (the path handle, for a race), from the next tick on;
+ * cfg NULL: the defaults.  The fleet or race must have plant and tyre tables (lpvmpc_cl_init_tyres / lpvmpc_race_init_tyres): there is
+ * nothing to scale otherwise.  Attaching again replaces the binding (state and j start over, the base rows stay).  rows == NULL
+ * detaches: the live words are restored from the base copy and the state is freed.  lpvmpc_cl_release frees the binding; a new fleet
+ * starts undisturbed.  While a binding is attached lpvmpc_plant_params_read and lpvmpc_tyre_params_read return the base rows.
+ * Refused with LPVMPC_E_ARG, a running fleet left exactly as it is: no fleet or race on the handle or one without the tables, another
+ * B than the fleet's, a non-finite word, sigma < 0, rho outside [0, 1), kick_step not integer-valued or >= 2^31, s0 < 0 or >= the
+ * vehicle's lap length, len < 0 or > the lap length, gamma < 0, n_bound <= 0.  lpvmpc_disturbances_read: the rows as they were set
+ * and the state (synchronises); either pointer may be NULL.  lpvmpc_cascade_init is not extended.
+ *
+ * lpvmpc_plant_step_disturbed_batch: lpvmpc_plant_step_tyres_batch as one tick of n_sub steps with the model in front of it, on the
+ * handle's track or its track binding (an unbound handle takes lpvmpc_race_default_config's half_width and slack for the
+ * transform); dist_state [B][LPVMPC_DIST_STATE] is read and written (NULL: fresh, nothing returned; refused: a non-finite d word, a
+ * tick count that is not an integer >= 0). */
+#define LPVMPC_DIST_WORDS 13
+#define LPVMPC_DIST_STATE 5
+#define LPVMPC_DIST_STREAM 0xD157A2B3C4D5E6F7ull   /* keeps the gusts' draws apart from the sensors' under one seed */
+typedef struct lpvmpc_disturbance_config {
+    uint64_t seed;             /* 0 */
+    int64_t  vehicle_offset;   /* 0: global index of vehicle 0 of this fleet (shards of one fleet draw the same numbers) */
+    double   n_bound;          /* 3.0: the gusts' clip, in standard deviations */
+} lpvmpc_disturbance_config;
+void lpvmpc_disturbance_default_config(lpvmpc_disturbance_config *cfg);
+int  lpvmpc_set_disturbances(lpvmpc_handle *h, int32_t B, const lpvmpc_disturbance_config *cfg, const double *rows);
+int  lpvmpc_disturbances_read(lpvmpc_handle *h, double *rows, double *state);
+int  lpvmpc_plant_step_disturbed_batch(lpvmpc_handle *h, int32_t B, double *state, double *act_state, const double *u,
+                                       int32_t n_sub, double dt_sim, double mu_sim, const lpvmpc_actuator_config *act,
+                                       const int32_t *delay_a, const int32_t *delay_df, const double *plant_params,
+                                       const double *tyre_params, const lpvmpc_disturbance_config *cfg, const double *rows,
+                                       double *dist_state);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,8 +39,13 @@ phase: every vehicle as far before the end of its own lap as the fixture's start
 other survivors), the same six tracks as six homogeneous sub-fleets of B / 6 vehicles ticked in turn in one process (the engines have
 no stream of their own to run side by side on), and, with --parent-lib FILE, the unbound race on that build.  Every line carries
 alive vehicle-ticks per second.
+--disturbance: the same protocol for the plant disturbances (lpvmpc_set_disturbances): the lpvmpc_race_init_tyres race with kind 0 rows and
+nothing attached (the baseline: the launches of the parent's tick), the same race with all three disturbances attached to every vehicle
+(gusts of 0.3 on the three channels, a grip patch of 0.7 over the first 3 m of the lap, a kick at plant step 400: one more launch per
+tick, and other trajectories, so the lines also carry the solvers' changed iteration counts), and, with --parent-lib FILE, the
+nothing-attached race on that build.
 Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator | --actuator | --record | --plant-params | --models | --tunings |
-       --tyres | --observer-vehicles | --tracks [--parent-lib FILE] [--reps R]] [--out FILE]"""
+       --tyres | --observer-vehicles | --tracks | --disturbance [--parent-lib FILE] [--reps R]] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -72,7 +77,7 @@ def timed(tick, read, K):
 
 
 def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, record=False, plant_params=None, model_params=None, tunings=None,
-             tyre_params=None, observer_vehicles=False, tracks=None):
+             tyre_params=None, observer_vehicles=False, tracks=None, disturbance=None):
     path, tt, plan = engines(mp, sd)
     if tracks is not None:                                            # (maps, track_of) bound to the three engines
         for e in (path, tt, plan):
@@ -92,6 +97,8 @@ def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, rec
             e.set_model_params(model_params)
     path.race_init(tt, plan, plant0, half_track0=half, laps=5, half_width=mp.halfWidth, slack=mp.slack, estimator=estimator,
                    actuator=actuator, plant_params=plant_params, **({} if tyre_params is None else {"tyre_params": tyre_params}))
+    if disturbance is not None:                                       # rows attached before the first tick
+        path.set_disturbances(disturbance, seed=1)
     path.race_tick(warm)
     if record:
         path.race_record(K, 1)
@@ -119,6 +126,7 @@ def main():
     ap.add_argument("--tyres", action="store_true")
     ap.add_argument("--observer-vehicles", action="store_true")
     ap.add_argument("--tracks", action="store_true")
+    ap.add_argument("--disturbance", action="store_true")
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--models-child", nargs=4, default=None, help=argparse.SUPPRESS)      # lib regime B bind: one run of --models
     a = ap.parse_args()
@@ -137,6 +145,9 @@ def main():
     if a.tracks:
         return models_main(a, [("tyres, unbound", "liblpvmpc.so", 9), ("own track bound", "liblpvmpc.so", 10), ("six tracks bound", "liblpvmpc.so", 11),
                                ("six sub-fleets", "liblpvmpc.so", 12)], parent=("parent, tyres", 9))
+    if a.disturbance:
+        return models_main(a, [("tyres, nothing attached", "liblpvmpc.so", 9), ("disturbances attached", "liblpvmpc.so", 13)],
+                           parent=("parent, tyres", 9))
     if a.plant_params:
         return plant_params_main(a)
     if a.record:
@@ -353,19 +364,29 @@ def tracks_child(a, regime, B, bind):
     return ms, alive / (ms * a.ticks * 1e-3), ph
 
 
+def mp_length():
+    import lpvmpc
+    return float(lpvmpc.Map("L_shape", 0.2).TrackLength)
+
+
 def models_child(a):
     lib, regime, B, bind = a.models_child
     from lpvmpc import _ffi
     _ffi.LIB_PATH = os.path.join(os.path.dirname(_ffi.LIB_PATH), lib)
     import lpvmpc
-    if int(bind) >= 10:
+    if int(bind) in (10, 11, 12):
         ms, vps, ph = tracks_child(a, regime, int(B), int(bind))
         print("MODELS_RUN %.6f %s %.4g" % (ms, ",".join(str(int(x)) for x in ph), vps), flush=True)
         return
     mp = lpvmpc.Map("L_shape", 0.2)
     plant0, half, warm = _models_starts(int(B))[regime]
     rows = lpvmpc.model_params(int(B)) if int(bind) == 1 else None                # bind: 0 nothing, 1 nominal model rows, 2 / 3 tuning rows,
-    tyres = {5: lpvmpc.tyre_params(int(B), kind=0), 6: "pacejka", 9: lpvmpc.tyre_params(int(B), kind=0)}.get(int(bind))   # 4 nominal plant rows (_vehicles), 5 / 6 tyre rows on top
+    tyres = {5: lpvmpc.tyre_params(int(B), kind=0), 6: "pacejka", 9: lpvmpc.tyre_params(int(B), kind=0),
+             13: lpvmpc.tyre_params(int(B), kind=0)}.get(int(bind))               # 4 nominal plant rows (_vehicles), 5 / 6 tyre rows on top
+    dist = None                                                                    # 13: 9 with gusts, a patch and a kick on every vehicle
+    if int(bind) == 13:
+        from lpvmpc.disturbance import parse_disturbance
+        dist = parse_disturbance("gusts:0.3+patch:0,3,0.7+kick:400,0.1,0.3", int(B), mp_length())
     obs = None                                                                     # 7 / 8: _vehicles with the estimator, unbound / rows bound
     if int(bind) in (7, 8):
         from lpvmpc.observer import observer_config
@@ -374,7 +395,7 @@ def models_child(a):
                               v_std=0.02, seed=7)
     ms, vps, ph = race_run(mp, plant0, half, warm, a.ticks, model_params=rows, tunings={2: "own", 3: "sampled"}.get(int(bind)),
                             plant_params="nominal" if int(bind) in (4, 5, 6, 7, 8) else None, tyre_params=tyres, estimator=obs,
-                            observer_vehicles=int(bind) == 8)
+                            observer_vehicles=int(bind) == 8, disturbance=dist)
     print("MODELS_RUN %.6f %s %.4g" % (ms, ",".join(str(int(x)) for x in ph), vps), flush=True)
 
 

@@ -19,8 +19,13 @@ saturates; the rows' Cf, Cr are then not read, so their bins show no trend of th
 in the baseline race as well: nominal (the estimator keeps its own constants and the nominal tables) or plant (each vehicle's
 estimator takes its plant row, with gain tables designed on the device for that row: RaceFleet(estimator_params="plant")).  Without
 the flag the race runs on ground truth: today's run, same output.
+--disturbance pushes back on the swept race (lpvmpc_set_disturbances, RaceFleet(disturbance=...)), the same rows for every vehicle:
+gusts:SIGMA (a Gauss-Markov gust of that standard deviation on ax, ay and the yaw acceleration, per-tick correlation 0.8, seeded with
+--seed), patch:S0,LEN,GAMMA (grip times GAMMA from S0 m on, LEN m long, on every vehicle's own track) or kick:STEP,VY,W (a side push
+at plant step STEP); several joined with +.  The nominal-car baseline race stays undisturbed.  Without the flag the race is today's
+run, same output.
 Usage: tools/robustness_sweep.py [--B 8192] [--laps 2] [--seed 1] [--max-ticks 3000] [--model nominal|plant|noisy:REL]
-       [--tyre linear|pacejka] [--estimator nominal|plant] [--out FILE]"""
+       [--tyre linear|pacejka] [--estimator nominal|plant] [--disturbance SPEC] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -41,6 +46,7 @@ def main():
     ap.add_argument("--tyre", default="linear", choices=("linear", "pacejka"))
     ap.add_argument("--estimator", default=None, choices=("nominal", "plant"))
     ap.add_argument("--tracks", default=None, help="comma-separated track shapes (oval, L_shape, 3110, Euge_Track): vehicle b races on track b mod their number")
+    ap.add_argument("--disturbance", default=None, help="gusts:SIGMA | patch:S0,LEN,GAMMA | kick:STEP,VY,W (joined with +)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.model not in ("nominal", "plant") and not a.model.startswith("noisy:"):
@@ -76,9 +82,16 @@ def main():
         g = np.load(os.path.join(ROOT, "tests", "golden", "estimator", "estimator.npz"))
         obs = observer_config(g["L_ls"], g["lim_ls"], g["L_hs"], g["lim_hs"])
 
-    def race(r, m=None, est_rows=None):
+    dist = None
+    if a.disturbance:
+        from lpvmpc.disturbance import parse_disturbance
+        lap = [float(m.PointAndTangent[-1, 3] + m.PointAndTangent[-1, 4]) for m in (maps or [mp])]
+        dist = dict(rows=parse_disturbance(a.disturbance, B, np.array(lap)[track_of] if maps else lap[0]), seed=a.seed)
+
+    def race(r, m=None, est_rows=None, disturbance=None):
         f = lpvmpc.RaceFleet(mp if maps is None else maps, plant0, laps=a.laps, half_track0=1, plant_params=r, model_params=m, track_of=track_of,
-                             tyre_params="pacejka" if a.tyre == "pacejka" else None, estimator=obs, estimator_params=est_rows)
+                             tyre_params="pacejka" if a.tyre == "pacejka" else None, estimator=obs, estimator_params=est_rows,
+                             disturbance=disturbance)
         assert np.array_equal(f.plant_params(), r)
         assert a.tyre == "linear" or np.array_equal(f.tyre_params(), lpvmpc.tyre_params(B))
         assert m is None or np.array_equal(f.model_params(), m)
@@ -93,7 +106,7 @@ def main():
     base, _n, _w = race(nom)                                          # the same starts with the nominal car: the baseline
     ph_nom = base.state()["phase"]
     base.close()
-    fleet, ticks, wall = race(rows, model_rows, "plant" if a.estimator == "plant" else None)
+    fleet, ticks, wall = race(rows, model_rows, "plant" if a.estimator == "plant" else None, dist)
     ph = fleet.state()["phase"]
     lt = fleet.lap_times()[:, 1:a.laps + 1]                          # racing laps, seconds (NaN: not completed)
     st = fleet.lap_stats()
@@ -105,7 +118,9 @@ def main():
                 ", ".join("%s %+.0f %%" % (k, 100 * v) for k, v in spread.items())),
              "# the controllers and the planner %s." % model_text] + ([] if not a.estimator else [
              "# the state estimator is in the loop (--estimator %s): %s." % (a.estimator, "each vehicle's estimator takes its plant row and gain tables "
-              "designed for it" if a.estimator == "plant" else "it keeps its own constants and the nominal gain tables")]) + [
+              "designed for it" if a.estimator == "plant" else "it keeps its own constants and the nominal gain tables")]) + ([] if not dist else [
+             "# the swept race is disturbed (--disturbance %s): the same rows for every vehicle, gusts seeded with --seed; the baseline race is not."
+             % a.disturbance]) + [
              "# %d ticks (%.1f s wall); all vehicles: %.1f %% finished, %.1f %% lost, %.1f %% still running; racing lap time median %.3f s, "
              "p90 %.3f s; RMSE_ey median %.4f m" % (ticks, wall, 100 * fin.mean(), 100 * lost.mean(), 100 * (ph < 2).mean(),
                                                      np.nanmedian(lt), np.nanpercentile(lt, 90), np.nanmedian(rmse)),
