@@ -163,7 +163,8 @@ EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_d
            "lpvmpc_observer_vehicles_read", "lpvmpc_observer_step_vehicles_batch",
            "lpvmpc_set_tracks", "lpvmpc_tracks_read",
            "lpvmpc_disturbance_default_config", "lpvmpc_set_disturbances", "lpvmpc_disturbances_read",
-           "lpvmpc_plant_step_disturbed_batch")
+           "lpvmpc_plant_step_disturbed_batch",
+           "lpvmpc_race_snapshot_size", "lpvmpc_race_snapshot", "lpvmpc_race_restore", "lpvmpc_race_clone")
 
 _lib = None
 
@@ -360,6 +361,15 @@ def load():
         lib.lpvmpc_race_record_read.argtypes = [vp, _i, vp, vp, vp, vp]
         lib.lpvmpc_race_lap_stats.argtypes = [vp, vp, vp, vp]
         for name in ("lpvmpc_race_record", "lpvmpc_race_record_read", "lpvmpc_race_lap_stats"):
+            getattr(lib, name).restype = C.c_int
+    except AttributeError:
+        pass
+    try:        # (nor the race's snapshot, restore and clone)
+        lib.lpvmpc_race_snapshot_size.argtypes = [vp, P(C.c_int64)]
+        lib.lpvmpc_race_snapshot.argtypes = [vp, vp, C.c_int64]
+        lib.lpvmpc_race_restore.argtypes = [vp, vp, C.c_int64]
+        lib.lpvmpc_race_clone.argtypes = [vp, vp, P(_i)]
+        for name in ("lpvmpc_race_snapshot_size", "lpvmpc_race_snapshot", "lpvmpc_race_restore", "lpvmpc_race_clone"):
             getattr(lib, name).restype = C.c_int
     except AttributeError:
         pass

@@ -836,6 +836,41 @@ class BatchedSolver:
         self._chk(self._lib.lpvmpc_race_lap_stats(self._h, ptr(f), ptr(i), ptr(e)))
         return _ffi.lap_stats_dict(f, i, e)
 
+    # -- race snapshot, restore and clone (lpvmpc_race_snapshot / _restore / _clone; snapshot.py) -----------------
+    def race_snapshot(self, raw=False):
+        """Synchronise and return the race's whole per-vehicle state and tick counter as a ``snapshot.RaceSnapshot`` (``raw``: the
+        blob's bytes).  It carries state only: bindings (plant, tyre, model, tuning, track, gain and disturbance rows) are the
+        caller's business.  Changes nothing; allowed while recording."""
+        from .snapshot import RaceSnapshot
+        self._race_B("race_snapshot")
+        n = C.c_int64(0)
+        self._chk(self._lib.lpvmpc_race_snapshot_size(self._h, C.byref(n)))
+        buf = np.empty(n.value, np.uint8)
+        self._chk(self._lib.lpvmpc_race_snapshot(self._h, ptr(buf), n.value))
+        blob = buf.tobytes()
+        return blob if raw else RaceSnapshot.from_bytes(blob)
+
+    def race_restore(self, snap):
+        """Put a snapshot (a ``RaceSnapshot`` or a blob's bytes) back into this race: the one it came from, or a freshly initialised
+        one of the same shape and features with the same bindings.  Refused (LpvMpcError, the race untouched) where header or
+        directory differ from the live race's, and while a recorder is attached."""
+        self._race_B("race_restore")
+        blob = snap.to_bytes() if hasattr(snap, "to_bytes") else bytes(snap)
+        buf = np.frombuffer(blob, np.uint8)
+        self._chk(self._lib.lpvmpc_race_restore(self._h, ptr(buf), len(blob)))
+
+    def race_clone(self, src):
+        """Vehicle b takes the whole state of vehicle src[b] and keeps its own bindings (src [B]; duplicates, swaps and cycles read
+        the state before the call).  Returns the number of vehicles moved.  Refused, with nothing changed: an index outside [0, B),
+        a source on another track of a track-bound race, a recorder attached."""
+        B = self._race_B("race_clone")
+        s = np.ascontiguousarray(np.asarray(src).reshape(-1), np.int32)
+        if s.shape[0] != B:
+            raise ValueError("race_clone: src must have one entry per vehicle (%d), got %d" % (B, s.shape[0]))
+        moved = _ffi._i(0)
+        self._chk(self._lib.lpvmpc_race_clone(self._h, ptr(s), C.byref(moved)))
+        return int(moved.value)
+
     # -- device-pointer entry point (torch tensors or raw integers) -----------------------------------
     def solve_dev(self, B, x0, u_prev, vel_ref, curv_s, u_old, max_ey, xPred, uPred, status=None, iters=None,
                   resid=None, polish=None, cf_new=60.0, lap=1, stream=0):
@@ -1358,6 +1393,34 @@ class RaceFleet(object):
         (RMSE_ve / RMSE_ye / RMSE_thetae of CMAIN:101-106; NaN where the lap has no counted tick)."""
         from .telemetry import add_rmse
         return add_rmse(self.path.race_lap_stats())
+
+    def snapshot(self):
+        """The race's whole per-vehicle state and tick counter (BatchedSolver.race_snapshot): a ``snapshot.RaceSnapshot`` with
+        ``to_bytes`` / ``save`` for a checkpoint.  State only: a race restored elsewhere is first built with the same arguments."""
+        return self.path.race_snapshot()
+
+    def restore(self, snap):
+        """Continue from a snapshot of this race or of one built alike (BatchedSolver.race_restore): rewind, or resume a checkpoint."""
+        self.path.race_restore(snap)
+
+    def clone(self, src):
+        """Vehicle b takes the state of vehicle src[b] and keeps its own bindings (BatchedSolver.race_clone); returns the number moved.
+        Sensor noise and gusts are keyed by the vehicle's slot, so a clone draws its own future."""
+        return self.path.race_clone(src)
+
+    def respawn(self, seed):
+        """Fill every lost slot (non-finite plant) with a clone of a vehicle that is still driving, on a track-bound race one of the
+        slot's own track, chosen by ``numpy.random.default_rng(seed)`` (snapshot.respawn_sources): importance splitting's
+        resampling step.  Finished vehicles are frozen, not lost, and are neither filled nor cloned.  Returns the ``src`` map; any
+        weights of a splitting estimator are the caller's to keep."""
+        from .snapshot import respawn_sources
+        st = self.path.race_read()
+        finite = np.isfinite(st["plant"]).all(axis=1)
+        tr = self.tracks()
+        src = respawn_sources(finite & (st["phase"] < 2), None if tr is None else tr["track_of"], seed, lost=~finite)
+        if (src != np.arange(src.shape[0])).any():
+            self.path.race_clone(src)
+        return src
 
     def close(self):
         for e in (self.path, self.tt, self.planner):

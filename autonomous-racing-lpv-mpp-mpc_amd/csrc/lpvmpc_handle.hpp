@@ -1,6 +1,6 @@
 // lpvmpc_handle.hpp -- private host-side definitions shared by the translation units that implement the C ABI
 // (lpvmpc_api.hip: solver entry points and the lap-0 fleet; cascade_api.hip: hand-off and planner + controller cascade;
-// race_api.hip: the race engine).
+// race_api.hip: the race engine; race_state_api.hip: its snapshot, restore and clone).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -208,6 +208,20 @@ LPVMPC_HIDDEN int lpvmpc_launch_solve_warm(lpvmpc_handle *h, lpvmpc::SolveArgs a
 LPVMPC_HIDDEN lpvmpc::PlantCfg lpvmpc_plant_cfg(const lpvmpc_handle *h, int n_sub, double dt_sim, double mu_sim);
 LPVMPC_HIDDEN void lpvmpc_cascade_free(lpvmpc_handle *h);
 LPVMPC_HIDDEN void lpvmpc_race_free(lpvmpc_handle *h);                                  // race_api.hip
+// race_api.hip: the inventory of the running race's per-vehicle state (include/lpvmpc.h, "Race snapshot, restore and clone"), the one
+// table that lpvmpc_race_snapshot / _restore / _clone (race_state_api.hip) walk.  An array is in it if a tick can read a word of it
+// that an earlier tick, or the init, wrote; bindings and tables, scratch that a tick writes before it reads, and the recorder are not.
+// type / layout: lpvmpc::StateType / StateLayout (race_state.hpp).  false: the handle owns no race
+struct RaceStateDesc { char name[16]; void *ptr; int32_t type, W, layout; };
+struct RaceState {
+    int32_t shape[8] = {};                      // B, N, Np, M, sd, lap_cols, laps, ticks
+    uint32_t features = 0;                      // LPVMPC_SNAP_HAS_*
+    bool recording = false;                     // a recorder is attached (lpvmpc_race_record)
+    const std::vector<int32_t> *track_of = nullptr;   // [B] with tracks bound, else null
+    std::vector<RaceStateDesc> tab;
+};
+LPVMPC_HIDDEN bool lpvmpc_race_state(lpvmpc_handle *h, RaceState &s);
+LPVMPC_HIDDEN void lpvmpc_race_set_ticks(lpvmpc_handle *h, int ticks);
 LPVMPC_HIDDEN int lpvmpc_observer_start(lpvmpc_handle *h, const lpvmpc_observer_config &o, int B, const double *plant0, double dt_sim,
                                         int from_plant);                                // lpvmpc_api.hip
 // actuator_api.hip: checks cfg / per-vehicle delays and allocates a zeroed actuator state for B vehicles in a (released first)

@@ -10,6 +10,7 @@
 #include <new>
 
 #include "lpvmpc_handle.hpp"
+#include "race_state.hpp"
 #include "record.hpp"
 
 struct lpvmpc_race_recorder {
@@ -227,6 +228,69 @@ DistBinding *lpvmpc_race_dist(lpvmpc_handle *h, lpvmpc::DistDev *t) {
     }
     return &r->dist;
 }
+
+// The inventory of the race's per-vehicle state (lpvmpc_handle.hpp: RaceState; include/lpvmpc.h, "Race snapshot, restore and clone").
+// Worked out from the kernels of a tick (race.hip, fleet_kernels.hpp, track_race.hip, handoff.hip, disturbance.hip and the masked LPV /
+// solve launches): an array is listed if a tick can read a word of it that an earlier tick, or the init, wrote.  A masked launch
+// leaves the rows of the vehicles it does not run as they are, so every per-vehicle output that a later tick or a read-back can see
+// is state (the handles' uPred, iters, status, polish, the planner's xPred ...).  Not listed, because every word a tick reads of them
+// is written earlier in the same tick under the same mask: sig, the handles' d_AB / d_states / d_resid, the controllers' d_xPred /
+// d_xlast / d_delta, and the path handle's d_curv, which no kernel of a race dereferences.  The planner's x0 / xlast / delta are
+// written by race_plan_start_kernel before their readers too; they are carried so that a blob holds the planner's whole recursion.
+// Bindings and tables (plant, tyre, model, tuning, track, gain and disturbance rows, La / Ld, d_maxey, the hand-off operators, the
+// live Cf / Cr / c_f words that the disturbances' kernel rewrites on every tick that steps the vehicle) are the caller's business
+bool lpvmpc_race_state(lpvmpc_handle *h, RaceState &s) {
+    lpvmpc_race *r = h->race;
+    if (!r) return false;
+    using namespace lpvmpc;
+    const RaceDev &d = r->d;
+    const lpvmpc_handle *tt = r->tt, *p = r->plan;
+    const int N = d.N, Np = d.Np;
+    s = RaceState{};
+    const int32_t shape[8] = {d.B, N, Np, d.M, r->sd, d.lap_cols, d.laps, r->ticks};
+    std::memcpy(s.shape, shape, sizeof(shape));
+    s.recording = r->rec != nullptr;
+    if (h->trk.tab) s.track_of = &h->trk_of;
+    s.features = (d.estv ? LPVMPC_SNAP_HAS_ESTIMATOR : 0u) | (r->act.d.ring ? LPVMPC_SNAP_HAS_ACTUATOR : 0u) |
+                 (r->dist.d.rows ? LPVMPC_SNAP_HAS_DISTURBANCES : 0u) | (h->trk.tab ? LPVMPC_SNAP_HAS_TRACKS : 0u);
+    auto add = [&s](const char *name, void *ptr, int type, int W, int layout = STATE_VEHICLE_MAJOR) {
+        RaceStateDesc e{};
+        std::strncpy(e.name, name, 15);
+        e.ptr = ptr; e.type = type; e.W = W; e.layout = layout;
+        s.tab.push_back(e);
+    };
+    // RaceDev
+    add("plant", d.plant, STATE_F64, 8); add("cmd", d.cmd, STATE_F64, 2); add("local", d.local, STATE_F64, 6);
+    if (d.estv) add("estv", d.estv, STATE_F64, 8);
+    add("phase", d.phase, STATE_I32, 1); add("lap", d.lap, STATE_I32, 1); add("half", d.half, STATE_I32, 1); add("rk", d.rk, STATE_I32, 1);
+    add("plan_done", d.plan_done, STATE_I32, 1); add("idx", d.idx, STATE_I32, 1); add("nstep", d.nstep, STATE_I32, 1);
+    add("src", d.src, STATE_I32, 1); add("step", d.step, STATE_I32, 1); add("alive", d.alive, STATE_I32, 1);
+    add("iters", d.iters, STATE_I32, 1); add("status", d.status, STATE_I32, 1);
+    add("lap_step", d.lap_step, STATE_I32, d.lap_cols);
+    add("m_path", d.m_path, STATE_I32, 1); add("m_tt", d.m_tt, STATE_I32, 1); add("m_plan", d.m_plan, STATE_I32, 1);
+    add("m_pfirst", d.m_pfirst, STATE_I32, 1); add("m_pcont", d.m_pcont, STATE_I32, 1);
+    add("SSc", d.SSc, STATE_F64, 1); add("ref0", d.ref0, STATE_F64, 3); add("refs", d.refs, STATE_F64, 5 * d.M);
+    add("SSp", d.SSp, STATE_F64, Np + 1); add("pose", d.pose, STATE_F64, 3);
+    // path and trajectory-tracking handles: the carried rows of their workspaces (d_curv [B][N]: race_measure_kernel's stride)
+    add("path.uold", h->d_uold, STATE_F64, 2 + r->sd); add("path.uPred", h->d_uPred, STATE_F64, N * 2); add("path.vel", h->d_vel, STATE_F64, N + 1);
+    add("path.iters", h->d_iters, STATE_I32, 1); add("path.status", h->d_status, STATE_I32, 1); add("path.polish", h->d_polish, STATE_I32, 1);
+    add("tt.uold", tt->d_uold, STATE_F64, 2 + r->sd); add("tt.uPred", tt->d_uPred, STATE_F64, N * 2); add("tt.vel", tt->d_vel, STATE_F64, N + 1);
+    add("tt.curv", tt->d_curv, STATE_F64, N);
+    add("tt.iters", tt->d_iters, STATE_I32, 1); add("tt.status", tt->d_status, STATE_I32, 1); add("tt.polish", tt->d_polish, STATE_I32, 1);
+    // planner handle
+    add("plan.x0", p->d_x0, STATE_F64, 5); add("plan.xPred", p->d_xPred, STATE_F64, (Np + 1) * 5); add("plan.uPred", p->d_uPred, STATE_F64, Np * 2);
+    add("plan.xlast", p->d_xlast, STATE_F64, Np * 6); add("plan.delta", p->d_delta, STATE_F64, Np);
+    add("plan.iters", p->d_iters, STATE_I32, 1); add("plan.status", p->d_status, STATE_I32, 1); add("plan.polish", p->d_polish, STATE_I32, 1);
+    // actuator, estimator, disturbances
+    if (r->act.d.ring) {
+        add("act.ring", r->act.d.ring, STATE_F64, 2 * kActRing, STATE_WORD_MAJOR);
+        add("act.servo", r->act.d.servo, STATE_F64, 1); add("act.k", r->act.d.k, STATE_I32, 1);
+    }
+    if (d.estv) add("obs.state", h->obs_state, STATE_F64, kObsStride);
+    if (r->dist.d.rows) add("dist.state", r->dist.d.state, STATE_F64, kDistState, STATE_WORD_MAJOR);
+    return true;
+}
+void lpvmpc_race_set_ticks(lpvmpc_handle *h, int ticks) { if (h->race) h->race->ticks = ticks; }
 
 // the race's actuator state and its two controllers' histories (lpvmpc_actuator_read)
 int lpvmpc_race_act_read(lpvmpc_handle *h, double *act_state, double *path_hist, double *tt_hist) {

@@ -1044,6 +1044,66 @@ int  lpvmpc_plant_step_disturbed_batch(lpvmpc_handle *h, int32_t B, double *stat
                                        const double *tyre_params, const lpvmpc_disturbance_config *cfg, const double *rows,
                                        double *dist_state);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Race snapshot, restore and clone: checkpoint a running race, continue it later (in the same race, or in a freshly initialised
+ * one of the same shape, even in another process), and branch it: vehicles take the whole dynamic state of other vehicles.  All
+ * calls take the race's path handle and fail with LPVMPC_E_ARG ("call lpvmpc_race_init first") on a handle without a race.  None of
+ * them is on the path of a tick: a race that calls none of them issues the launches it always did.
+ *
+ * State and bindings.  The three calls act on the race's per-vehicle STATE: every device array of which a tick can read a word that an
+ * earlier tick, or the init, wrote -- plant, command, measurement, phase and lap bookkeeping, this tick's masks, the planner message
+ * and recursion, the carried rows of the three handles' workspaces (u_old, uPred, vel, curv, xPred, iters, status, polish), and
+ * where present the estimate view and estimator state, the actuator's ring / servo / step counter and the disturbances' process
+ * state -- plus the host's tick counter.  BINDINGS are the caller's business and are never touched: plant, tyre, model, tuning, track,
+ * estimator-gain and disturbance rows, actuator delays, the planner's max_ey, the hand-off operators, the live Cf / Cr / c_f words
+ * (the disturbance kernel rewrites them on every tick that steps the vehicle), the seeds.  A blob carries state only: to continue a
+ * race elsewhere, initialise one with the same bindings first, then restore.  The recorder's ring and statistics are neither.
+ *
+ * Blob format, version 1.  Little-endian, no pointers, self-describing:
+ *   header     LPVMPC_SNAP_HEADER_BYTES = 64 B: char magic[8] = "LPVRACE\0"; then int32 words: version; B, N, Np, M (samples of the
+ *              planner message), sd (steeringDelay), lap_cols (= laps + 2), laps, ticks; features (LPVMPC_SNAP_HAS_*: one bit each for
+ *              the estimator in the loop, actuator state present, disturbances attached, tracks bound); count (arrays); 3 words zero
+ *   directory  count entries of LPVMPC_SNAP_ENTRY_BYTES = 40 B: char name[16] (NUL-padded, at most 15 characters); int32 type
+ *              (LPVMPC_SNAP_F64 / _I32), W (words per vehicle), layout (LPVMPC_SNAP_VEHICLE_MAJOR [B][W] / _WORD_MAJOR [W][B]), zero;
+ *              int64 offset of the array from the start of the blob
+ *   arrays     each exactly as it lies on the device, B * W elements, each starting on a multiple of 8 B (zero padding)
+ * lpvmpc_race_snapshot_size returns the blob's size for the race as it is now (attaching or detaching disturbances changes it).
+ *
+ * lpvmpc_race_snapshot synchronises the path handle's stream and copies the state into buf (bytes >= the size).  It changes no
+ * state and is allowed while a recorder is attached.
+ *
+ * lpvmpc_race_restore accepts a blob only if the live race matches it: magic and version; the shape words B, N, Np, M, sd, lap_cols,
+ * laps; the feature word; the directory equal to the live table in count, names, types, W, layouts and offsets; bytes covering all of
+ * it.  Otherwise LPVMPC_E_ARG, lpvmpc_last_error names the first mismatch, and the race is untouched.  On success the arrays are copied
+ * to the device on the handle's stream, ticks is set to the blob's, and the call synchronises: the next lpvmpc_race_tick continues the
+ * snapshotted race word for word, noise and gust draws included (their counters are state).
+ *
+ * lpvmpc_race_clone: vehicle b takes the whole state of vehicle src[b] (src [B]; src[b] == b: untouched) and keeps its own bindings.
+ * src may hold duplicates, cycles and swaps: every read sees the state before the call (the words are staged in a buffer that lives
+ * for the call, which synchronises before it returns).  moved (may be NULL) returns the number of b with src[b] != b.  The sensors'
+ * and gusts' generators are keyed by (seed, vehicle slot, the vehicle's own counter), so a clone in another slot draws another stream
+ * from the next tick on: importance splitting needs nothing more.  Refused with nothing changed: an index outside [0, B); on a
+ * track-bound race, track_of[src[b]] != track_of[b] (a pose and a lap table mean nothing on another track).
+ *
+ * Recorder: restore and clone are refused while a recorder is attached (stop it with lpvmpc_race_record, capacity 0, and start it
+ * again afterwards); its ring and per-lap statistics are not carried.  The lap-0 fleet (lpvmpc_cl_*) and the cascade have no
+ * snapshot. */
+#define LPVMPC_SNAP_VERSION 1
+#define LPVMPC_SNAP_HEADER_BYTES 64
+#define LPVMPC_SNAP_ENTRY_BYTES 40
+#define LPVMPC_SNAP_F64 0
+#define LPVMPC_SNAP_I32 1
+#define LPVMPC_SNAP_VEHICLE_MAJOR 0
+#define LPVMPC_SNAP_WORD_MAJOR 1
+#define LPVMPC_SNAP_HAS_ESTIMATOR 1u
+#define LPVMPC_SNAP_HAS_ACTUATOR 2u
+#define LPVMPC_SNAP_HAS_DISTURBANCES 4u
+#define LPVMPC_SNAP_HAS_TRACKS 8u
+int  lpvmpc_race_snapshot_size(lpvmpc_handle *path, int64_t *bytes);
+int  lpvmpc_race_snapshot(lpvmpc_handle *path, void *buf, int64_t bytes);
+int  lpvmpc_race_restore(lpvmpc_handle *path, const void *buf, int64_t bytes);
+int  lpvmpc_race_clone(lpvmpc_handle *path, const int32_t *src /* [B] */, int32_t *moved /* out, may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

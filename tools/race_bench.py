@@ -44,8 +44,15 @@ nothing attached (the baseline: the launches of the parent's tick), the same rac
 (gusts of 0.3 on the three channels, a grip patch of 0.7 over the first 3 m of the lap, a kick at plant step 400: one more launch per
 tick, and other trajectories, so the lines also carry the solvers' changed iteration counts), and, with --parent-lib FILE, the
 nothing-attached race on that build.
+--fork: the race's snapshot, restore and clone (lpvmpc_race_snapshot / _restore / _clone).  First the same protocol with one
+configuration, the lpvmpc_race_init_tyres race with kind 0 rows that calls none of them, and, with --parent-lib FILE, the same race on
+that build: nothing called, nothing paid.  Then, per B, in the in-phase regime at the first timed tick (every vehicle racing): the
+median over --reps calls, in ms, of a snapshot (device to host, the blob's bytes), a restore of that blob, a clone with every vehicle
+moved (a rotation by one) and a clone with 10 % of the vehicles moved (random slots from random sources), beside the ms per race tick
+of the same regime as the scale (the parent's where --parent-lib is given); the blob's bytes per vehicle; and for the full clone
+the GB/s over the bytes its two kernels read plus write (the state goes through the staging buffer: four times its size).
 Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator | --actuator | --record | --plant-params | --models | --tunings |
-       --tyres | --observer-vehicles | --tracks | --disturbance [--parent-lib FILE] [--reps R]] [--out FILE]"""
+       --tyres | --observer-vehicles | --tracks | --disturbance | --fork [--parent-lib FILE] [--reps R]] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -127,11 +134,17 @@ def main():
     ap.add_argument("--observer-vehicles", action="store_true")
     ap.add_argument("--tracks", action="store_true")
     ap.add_argument("--disturbance", action="store_true")
+    ap.add_argument("--fork", action="store_true")
+    ap.add_argument("--fork-child", default=None, help=argparse.SUPPRESS)                  # B: the fork measurements of one fleet size
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--models-child", nargs=4, default=None, help=argparse.SUPPRESS)      # lib regime B bind: one run of --models
     a = ap.parse_args()
     if a.models_child:
         return models_child(a)
+    if a.fork_child:
+        return fork_child(a)
+    if a.fork:
+        return fork_main(a)
     if a.models:
         return models_main(a)
     if a.tunings:
@@ -399,7 +412,62 @@ def models_child(a):
     print("MODELS_RUN %.6f %s %.4g" % (ms, ",".join(str(int(x)) for x in ph), vps), flush=True)
 
 
-def models_main(a, cfgs=None, parent=("parent, unbound", 0)):
+def fork_child(a):
+    """One fleet size: the in-phase race of bind 9 at its first timed tick; medians of --reps calls each."""
+    import lpvmpc
+    B = int(a.fork_child)
+    mp = lpvmpc.Map("L_shape", 0.2)
+    plant0, half, warm = _models_starts(B)["inphase"]
+    path, tt, plan = engines(mp)
+    path.race_init(tt, plan, plant0, half_track0=half, laps=5, half_width=mp.halfWidth, slack=mp.slack,
+                   tyre_params=lpvmpc.tyre_params(B, kind=0))
+    path.race_tick(warm)
+    ph = np.bincount(path.race_read()["phase"], minlength=4)
+    rng = np.random.default_rng(1)
+    rot = ((np.arange(B) + 1) % B).astype(np.int32)
+    tenth = np.arange(B, dtype=np.int32)
+    slots = rng.choice(B, max(B // 10, 1), replace=False)
+    tenth[slots] = rng.integers(0, B, slots.size)
+    blob = path.race_snapshot(raw=True)
+
+    def med(call):
+        call()                                                            # (the first call pays for code loading)
+        t = []
+        for _ in range(max(a.reps, 3)):
+            t0 = time.perf_counter(); call(); t.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(t))
+    ms = [med(lambda: path.race_snapshot(raw=True)), med(lambda: path.race_restore(blob)), med(lambda: path.race_clone(rot)),
+          med(lambda: path.race_clone(tenth))]
+    path.race_restore(blob)
+    state = len(blob) - 64 - 40 * lpvmpc.RaceSnapshot.from_bytes(blob).header["count"]
+    path.race_tick(2); path.race_read()                                   # the race goes on
+    for e in (path, tt, plan):
+        e.close()
+    print("FORK_RUN %d %s %d %d %s %d" % (B, ",".join(str(int(x)) for x in ph), len(blob), state, " ".join("%.4f" % m for m in ms),
+                                          int(np.sum(tenth != np.arange(B)))), flush=True)
+
+
+def fork_main(a):
+    import subprocess
+    lines = models_main(a, [("tyres, unforked", "liblpvmpc.so", 9)], parent=("parent, tyres", 9), write=False)
+    scale_of = "parent, tyres" if a.parent_lib else "tyres, unforked"
+    for B in [int(x) for x in a.sizes.split(",")]:
+        tick = [float(l.split("ms/tick")[0].split()[-1]) for l in lines if l.startswith("inphase  B=%5d  %-22s" % (B, scale_of))][0]
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--reps", str(a.reps), "--fork-child", str(B)], check=True,
+                             capture_output=True, text=True, timeout=600).stdout
+        f = [l for l in out.splitlines() if l.startswith("FORK_RUN")][-1].split()
+        size, state = int(f[3]), int(f[4])
+        snap, rest, full, part = (float(x) for x in f[5:9])
+        lines.append("fork     B=%5d  phases [%s]  blob %d B = %.0f B/vehicle  snapshot %.3f ms  restore %.3f ms  clone, all moved %.3f ms "
+                     "(%.1f GB/s over 4 x %.2f MB read + written)  clone, %d moved %.3f ms  scale: %s %.3f ms per race tick"
+                     % (B, f[2], size, size / B, snap, rest, full, 4 * state / (full * 1e-3) / 1e9, state / 1e6, int(f[9]), part, scale_of, tick))
+        print(lines[-1], flush=True)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+def models_main(a, cfgs=None, parent=("parent, unbound", 0), write=True):
     import subprocess
     cfgs = list(cfgs or [("unbound", "liblpvmpc.so", 0), ("nominal rows bound", "liblpvmpc.so", 1)])
     base = cfgs[0][0]                                                                 # the differences are against the first configuration
@@ -423,9 +491,10 @@ def models_main(a, cfgs=None, parent=("parent, unbound", 0)):
                              % (regime, B, k, m, " ".join("%.3f" % x for x in ms[k]), max(ms[k]) - min(ms[k]), ph[k], float(np.median(vps[k])),
                                 base.split(",")[0], m - m0))
                 print(lines[-1], flush=True)
-    if a.out:
+    if a.out and write:
         with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")
+    return lines
 
 
 def record_main(a):

@@ -24,8 +24,15 @@ gusts:SIGMA (a Gauss-Markov gust of that standard deviation on ax, ay and the ya
 --seed), patch:S0,LEN,GAMMA (grip times GAMMA from S0 m on, LEN m long, on every vehicle's own track) or kick:STEP,VY,W (a side push
 at plant step STEP); several joined with +.  The nominal-car baseline race stays undisturbed.  Without the flag the race is today's
 run, same output.
+--respawn K refills the swept race every K ticks (RaceFleet.respawn, lpvmpc_race_clone): every lost slot takes the state of a vehicle
+that is still driving (of the slot's own track), drawn with --seed + the tick, keeps its own plant row and, where gusts are attached,
+draws its own future -- the resampling step of importance splitting; the weights are the caller's and this report keeps none, so
+its bins then describe the slots' rows, not independent vehicles.  The recorder cannot follow a clone, so the run records nothing and
+RMSE_ey is not reported.  The report gains one line: slots respawned, alive vehicle-ticks and alive vehicle-ticks per second of the
+swept race.  --respawn 0 adds the same line to an unchanged run (recorder on, nothing respawned), for the comparison.  The baseline
+race is never refilled.  Without the flag the output is today's.
 Usage: tools/robustness_sweep.py [--B 8192] [--laps 2] [--seed 1] [--max-ticks 3000] [--model nominal|plant|noisy:REL]
-       [--tyre linear|pacejka] [--estimator nominal|plant] [--disturbance SPEC] [--out FILE]"""
+       [--tyre linear|pacejka] [--estimator nominal|plant] [--disturbance SPEC] [--respawn K] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -47,8 +54,11 @@ def main():
     ap.add_argument("--estimator", default=None, choices=("nominal", "plant"))
     ap.add_argument("--tracks", default=None, help="comma-separated track shapes (oval, L_shape, 3110, Euge_Track): vehicle b races on track b mod their number")
     ap.add_argument("--disturbance", default=None, help="gusts:SIGMA | patch:S0,LEN,GAMMA | kick:STEP,VY,W (joined with +)")
+    ap.add_argument("--respawn", type=int, default=None, help="refill the lost slots every K ticks (0: never, but report the alive vehicle-ticks)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.respawn is not None and a.respawn < 0:
+        ap.error("--respawn must be >= 0")
     if a.model not in ("nominal", "plant") and not a.model.startswith("noisy:"):
         ap.error("--model must be nominal, plant or noisy:REL")
     import lpvmpc
@@ -88,29 +98,38 @@ def main():
         lap = [float(m.PointAndTangent[-1, 3] + m.PointAndTangent[-1, 4]) for m in (maps or [mp])]
         dist = dict(rows=parse_disturbance(a.disturbance, B, np.array(lap)[track_of] if maps else lap[0]), seed=a.seed)
 
-    def race(r, m=None, est_rows=None, disturbance=None):
+    fork = dict(slots=0, alive=0)                                     # of the swept race, with --respawn
+
+    def race(r, m=None, est_rows=None, disturbance=None, respawn=None):
         f = lpvmpc.RaceFleet(mp if maps is None else maps, plant0, laps=a.laps, half_track0=1, plant_params=r, model_params=m, track_of=track_of,
                              tyre_params="pacejka" if a.tyre == "pacejka" else None, estimator=obs, estimator_params=est_rows,
                              disturbance=disturbance)
         assert np.array_equal(f.plant_params(), r)
         assert a.tyre == "linear" or np.array_equal(f.tyre_params(), lpvmpc.tyre_params(B))
         assert m is None or np.array_equal(f.model_params(), m)
-        f.record(1, 1 << 20)                                          # statistics of every tick; one record kept
+        if not respawn:
+            f.record(1, 1 << 20)                                      # statistics of every tick; one record kept
+        step = respawn if respawn else 100
         t0, n = time.perf_counter(), 0
         while n < a.max_ticks:
-            f.run(100); n += 100
+            before = int(f.path.race_laps()[1].sum()) if respawn is not None else 0
+            f.run(step); n += step
+            if respawn is not None:                                   # (alive ticks are state: a clone carries its source's count)
+                fork["alive"] += int(f.path.race_laps()[1].sum()) - before
             if np.all(f.state()["phase"] >= 2):
                 break
+            if respawn and n < a.max_ticks:                             # (nothing after the last tick: the report shows the slots as they ended)
+                src = f.respawn(a.seed + n)
+                fork["slots"] += int(np.sum(src != np.arange(B)))
         return f, n, time.perf_counter() - t0
 
     base, _n, _w = race(nom)                                          # the same starts with the nominal car: the baseline
     ph_nom = base.state()["phase"]
     base.close()
-    fleet, ticks, wall = race(rows, model_rows, "plant" if a.estimator == "plant" else None, dist)
+    fleet, ticks, wall = race(rows, model_rows, "plant" if a.estimator == "plant" else None, dist, a.respawn)
     ph = fleet.state()["phase"]
     lt = fleet.lap_times()[:, 1:a.laps + 1]                          # racing laps, seconds (NaN: not completed)
-    st = fleet.lap_stats()
-    rmse = st["rmse_ey"][:, 1:a.laps + 1]
+    rmse = fleet.lap_stats()["rmse_ey"][:, 1:a.laps + 1] if not a.respawn else np.full(lt.shape, np.nan)
     fin, lost = ph == 2, ph == 3
     fin_nom = ph_nom == 2
     lines = ["# tools/robustness_sweep.py --B %d --laps %d --seed %d%s on one MI355X: one race, rows from sample_plant_params(B, %d) with spreads %s"
@@ -124,6 +143,10 @@ def main():
              "# %d ticks (%.1f s wall); all vehicles: %.1f %% finished, %.1f %% lost, %.1f %% still running; racing lap time median %.3f s, "
              "p90 %.3f s; RMSE_ey median %.4f m" % (ticks, wall, 100 * fin.mean(), 100 * lost.mean(), 100 * (ph < 2).mean(),
                                                      np.nanmedian(lt), np.nanpercentile(lt, 90), np.nanmedian(rmse)),
+             ] + ([] if a.respawn is None else [
+             "# --respawn %d: %d slots respawned, %d alive vehicle-ticks, %.4g alive vehicle-ticks/s over the %d ticks%s"
+             % (a.respawn, fork["slots"], fork["alive"], fork["alive"] / wall, ticks,
+                " (lost slots refilled every %d ticks: a different experiment, not a faster one; nothing recorded)" % a.respawn if a.respawn else "")]) + [
              "# the same starts with the nominal car: %.1f %% finished, %.1f %% lost (the starts near the end of the lap lose vehicles in "
              "lap 0 and on the first racing laps whatever the car); of the vehicles that finish with the nominal car, %.1f %% are lost "
              "with their own" % (100 * fin_nom.mean(), 100 * (ph_nom == 3).mean(), 100 * lost[fin_nom].mean()),
