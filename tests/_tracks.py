@@ -81,11 +81,19 @@ def groups(of):
 
 def transform_points(B, seed, maps, of):
     """(s, ey) [B, 2] and (x, y, psi) [B, 3] per vehicle on its own track: four of five points inside the track (|ey| below the half
-    width, heading off the tangent), every fifth beyond half width + slack (the 10000 sentinels); every seventh s beyond the lap end."""
+    width, heading off the tangent), every fifth beyond half width + slack (the 10000 sentinels); every seventh s beyond the lap end,
+    every eleventh inside the closing row."""
     rng = np.random.default_rng(seed)
     L = lengths(maps)[of]
     hw = np.array([m.halfWidth for m in maps])[of]; sl = np.array([m.slack for m in maps])[of]
     s = rng.uniform(0.02, 0.98, B) * L
+    # every eleventh s inside its track's closing row (the last 0.4 % of the lap on 3110 and Euge_Track), from a stream of its own so
+    # that every other point stays what it was; a closing row that is empty in float64 (the oval's 6e-16 m) cannot be entered
+    u = np.random.default_rng(seed + 77).uniform(0.05, 0.95, B)
+    for b in range(10, B, 11):
+        last = maps[of[b]].PointAndTangent[-1]
+        if last[3] + last[4] > last[3]:
+            s[b] = last[3] + u[b] * last[4]
     ey = rng.uniform(-0.9, 0.9, B) * hw
     off = np.arange(B) % 5 == 4
     ey[off] = (hw[off] + sl[off]) * rng.uniform(1.5, 3.0, int(off.sum())) * rng.choice([-1.0, 1.0], int(off.sum()))
