@@ -98,6 +98,21 @@ class RaceRecordConfig(C.Structure):
     _fields_ = [("capacity", _i), ("stride", _i)]
 
 
+class HeatsConfig(C.Structure):
+    """Mirror of ``struct lpvmpc_heats_config`` (include/lpvmpc.h)."""
+    _fields_ = [("half_length", _d), ("half_width_car", _d)]
+
+
+# heats (LPVMPC_HEAT_*): standings f64 [HEAT_F64][B] / i32 [HEAT_I32][B] and the carried state of the batch form, named in channel order
+HEAT_MAX = 256
+HEAT_F64, HEAT_I32, HEAT_CARRY_F64, HEAT_CARRY_I32 = 5, 10, 3, 10
+HEAT_F64_NAMES = ("progress", "gap_ahead", "gap_leader", "clearance", "min_clearance")
+HEAT_I32_NAMES = ("position", "ahead", "nearest", "contact", "contact_ticks", "first_contact_tick", "passes", "passed", "turns", "class")
+HEAT_CARRY_F64_NAMES = ("s", "progress", "min_clearance")
+HEAT_CARRY_I32_NAMES = ("flags", "turns", "turns0", "crossings", "phase", "finish_tick", "contact_ticks", "first_contact_tick", "passes",
+                        "passed")
+
+
 # race recorder channels (LPVMPC_REC_*): f64 [REC_F64][B] and i32 [REC_I32][B] per record, named in channel order
 REC_F64, REC_I32 = 29, 8
 REC_PLANT, REC_LOCAL, REC_CMD, REC_REF, REC_TRACK, REC_EST = 0, 8, 14, 16, 20, 23
@@ -164,7 +179,8 @@ EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_d
            "lpvmpc_set_tracks", "lpvmpc_tracks_read",
            "lpvmpc_disturbance_default_config", "lpvmpc_set_disturbances", "lpvmpc_disturbances_read",
            "lpvmpc_plant_step_disturbed_batch",
-           "lpvmpc_race_snapshot_size", "lpvmpc_race_snapshot", "lpvmpc_race_restore", "lpvmpc_race_clone")
+           "lpvmpc_race_snapshot_size", "lpvmpc_race_snapshot", "lpvmpc_race_restore", "lpvmpc_race_clone",
+           "lpvmpc_heats_default_config", "lpvmpc_race_heats", "lpvmpc_race_standings", "lpvmpc_heat_step_batch")
 
 _lib = None
 
@@ -370,6 +386,16 @@ def load():
         lib.lpvmpc_race_restore.argtypes = [vp, vp, C.c_int64]
         lib.lpvmpc_race_clone.argtypes = [vp, vp, P(_i)]
         for name in ("lpvmpc_race_snapshot_size", "lpvmpc_race_snapshot", "lpvmpc_race_restore", "lpvmpc_race_clone"):
+            getattr(lib, name).restype = C.c_int
+    except AttributeError:
+        pass
+    try:        # (nor the heats)
+        lib.lpvmpc_heats_default_config.argtypes = [P(HeatsConfig)]
+        lib.lpvmpc_heats_default_config.restype = None
+        lib.lpvmpc_race_heats.argtypes = [vp, P(HeatsConfig), vp, vp]
+        lib.lpvmpc_race_standings.argtypes = [vp, vp, vp, vp, vp]
+        lib.lpvmpc_heat_step_batch.argtypes = [vp, _i, _i, vp, vp, P(HeatsConfig), _i, vp, vp, vp, vp, vp, vp, vp, vp]
+        for name in ("lpvmpc_race_heats", "lpvmpc_race_standings", "lpvmpc_heat_step_batch"):
             getattr(lib, name).restype = C.c_int
     except AttributeError:
         pass

@@ -871,6 +871,82 @@ class BatchedSolver:
         self._chk(self._lib.lpvmpc_race_clone(self._h, ptr(s), C.byref(moved)))
         return int(moved.value)
 
+    # -- heats: standings, gaps, passes and contacts (lpvmpc_race_heats / _standings, lpvmpc_heat_step_batch; heats.py) ----
+    def race_heats(self, heat, turns0=None, half_length=0.4, half_width=0.2):
+        """Attach heats from the next tick on (lpvmpc_race_heats): ``heat`` [B], the heat of each vehicle (-1: none; at most 256
+        members each; with tracks bound, one track per heat), ``turns0`` [B] the starting turn count (default 0; -1 for a car gridded
+        behind the line), ``half_length`` / ``half_width`` the half extents of a car's footprint.  Re-attaching resets the standings;
+        ``heat=None`` detaches.  Heats only observe: no output of the race changes."""
+        from . import heats as H
+        B = self._race_B("race_heats")
+        if heat is None:
+            self._chk(self._lib.lpvmpc_race_heats(self._h, None, None, None))
+            return
+        hl, hw = H.check_extents(half_length, half_width)
+        cfg = _ffi.HeatsConfig(hl, hw)
+        h = H.check_heats(heat, B)
+        t0 = None if turns0 is None else np.ascontiguousarray(np.asarray(turns0).reshape(-1), np.int32)
+        if t0 is not None and t0.shape[0] != B:
+            raise ValueError("race_heats: turns0 must have one entry per vehicle (%d), got %d" % (B, t0.shape[0]))
+        self._chk(self._lib.lpvmpc_race_heats(self._h, C.byref(cfg), ptr(h), ptr(t0)))
+
+    def race_standings(self):
+        """Synchronise and return the standings (lpvmpc_race_standings): a dict of [B] arrays named as _ffi.HEAT_F64_NAMES /
+        HEAT_I32_NAMES (progress, gap_ahead, gap_leader, clearance, min_clearance; position, ahead, nearest, contact, contact_ticks,
+        first_contact_tick, passes, passed, turns, class), the planes f64 [5, B] / i32 [10, B], and line_tick / line_pos
+        [B, laps + 2].  A vehicle in no heat reads position -1 and NaN gaps."""
+        from . import heats as H
+        B = self._race_B("race_standings")
+        K = self._race[1] + 2
+        f = np.empty((_ffi.HEAT_F64, B)); i = np.empty((_ffi.HEAT_I32, B), np.int32)
+        lt = np.empty((B, K), np.int32); lp = np.empty((B, K), np.int32)
+        self._chk(self._lib.lpvmpc_race_standings(self._h, ptr(f), ptr(i), ptr(lt), ptr(lp)))
+        return H.standings_dict(f, i, lt, lp)
+
+    def heat_step(self, heat, L, pose, s, inside, phase, t, carry=None, n_heats=None, half_length=0.4, half_width=0.2):
+        """One tick of the heats' device function on the caller's data (lpvmpc_heat_step_batch): ``heat`` [B] (-1: none), ``L`` [B]
+        (or one value) each vehicle's track length, ``pose`` [B, 3] = x y yaw, ``s`` / ``inside`` [B] the track frame, ``phase`` [B],
+        ``t`` the tick number.  ``carry``: the state returned by the previous call (None: ``heats.new_carry(B)``, just attached).
+        Returns (standings, carry): the dict of ``race_standings`` (with the carry's line tables, if it has any) and the new carry.
+        The batch form keeps no line tables on the device: the kernel carries the count of lines crossed, and the tables of a carry made
+        with ``heats.new_carry(..., lines=K)`` are filled HERE, on the host, from that count and this tick's position -- a convenience
+        that mirrors what the race's kernel writes on the device (``race_standings``), not a read-back of it."""
+        from . import heats as H
+        pose = f64(pose)
+        if pose.ndim != 2 or pose.shape[1] != 3:
+            raise ValueError("heat_step: pose must be [B, 3], got %s" % (pose.shape,))
+        B = pose.shape[0]
+        hl, hw = H.check_extents(half_length, half_width)
+        cfg = _ffi.HeatsConfig(hl, hw)
+        h = H.check_heats(heat, B)
+        n = int(h.max()) + 1 if n_heats is None else int(n_heats)
+        Lb = f64(np.broadcast_to(np.asarray(L, float), (B,)), (B,), "L")
+        s = f64(s, (B,), "s")
+        ins = np.ascontiguousarray(np.asarray(inside).reshape(-1), np.int32)
+        ph = np.ascontiguousarray(np.asarray(phase).reshape(-1), np.int32)
+        if ins.shape[0] != B or ph.shape[0] != B:
+            raise ValueError("heat_step: inside and phase must have one entry per vehicle (%d)" % B)
+        c = H.new_carry(B) if carry is None else carry
+        cf = f64(c["f64"], (_ffi.HEAT_CARRY_F64, B), "carry f64").copy()
+        ci = np.ascontiguousarray(c["i32"], np.int32).copy()
+        if ci.shape != (_ffi.HEAT_CARRY_I32, B):
+            raise ValueError("heat_step: carry i32 has shape %s, expected %s" % (ci.shape, (_ffi.HEAT_CARRY_I32, B)))
+        f = np.empty((_ffi.HEAT_F64, B)); i = np.empty((_ffi.HEAT_I32, B), np.int32)
+        was = ci[_ffi.HEAT_CARRY_I32_NAMES.index("crossings")].copy() * (ci[0] & 1)
+        self._chk(self._lib.lpvmpc_heat_step_batch(self._h, B, n, ptr(h), ptr(Lb), C.byref(cfg), int(t), ptr(pose), ptr(s), ptr(ins), ptr(ph),
+                                                   ptr(cf), ptr(ci), ptr(f), ptr(i)))
+        out = dict(f64=cf, i32=ci)
+        lt = lp = None
+        if "line_tick" in c:                                   # the line tables, filled as the race's kernel fills them on the device
+            lt, lp = c["line_tick"].copy(), c["line_pos"].copy()
+            if not (c["i32"][0] & 1).any():
+                lt[h >= 0] = -1; lp[h >= 0] = -1
+            now = ci[_ffi.HEAT_CARRY_I32_NAMES.index("crossings")]
+            for b in np.nonzero((h >= 0) & (now > was) & (was < lt.shape[1]))[0]:
+                lt[b, was[b]] = int(t); lp[b, was[b]] = i[_ffi.HEAT_I32_NAMES.index("position"), b]
+            out.update(line_tick=lt, line_pos=lp)
+        return H.standings_dict(f, i, lt, lp), out
+
     # -- device-pointer entry point (torch tensors or raw integers) -----------------------------------
     def solve_dev(self, B, x0, u_prev, vel_ref, curv_s, u_old, max_ey, xPred, uPred, status=None, iters=None,
                   resid=None, polish=None, cf_new=60.0, lap=1, stream=0):
@@ -1393,6 +1469,15 @@ class RaceFleet(object):
         (RMSE_ve / RMSE_ye / RMSE_thetae of CMAIN:101-106; NaN where the lap has no counted tick)."""
         from .telemetry import add_rmse
         return add_rmse(self.path.race_lap_stats())
+
+    def heats(self, heat, turns0=None, half_length=0.4, half_width=0.2):
+        """Attach heats from the next tick on (BatchedSolver.race_heats): ``heat`` [B], the heat of each vehicle (-1: none); the
+        device then keeps each heat's order, gaps, passes, line crossings and footprint clearances.  ``heats(None)`` detaches."""
+        self.path.race_heats(heat, turns0=turns0, half_length=half_length, half_width=half_width)
+
+    def standings(self):
+        """The standings of the attached heats (BatchedSolver.race_standings); ``telemetry.standings_table`` prints them."""
+        return self.path.race_standings()
 
     def snapshot(self):
         """The race's whole per-vehicle state and tick counter (BatchedSolver.race_snapshot): a ``snapshot.RaceSnapshot`` with

@@ -19,6 +19,7 @@
 struct lpvmpc_cascade;       // cascade_api.hip
 struct lpvmpc_race;          // race_api.hip
 struct DistStep;             // below: the stand-alone step's disturbance arguments
+struct HeatsBinding;         // heats_host.hpp: heats attached to a race (race_api.hip, heats_api.hip)
 
 using lpvmpc::DevCfg;
 using lpvmpc::SolveArgs;
@@ -217,11 +218,22 @@ struct RaceState {
     int32_t shape[8] = {};                      // B, N, Np, M, sd, lap_cols, laps, ticks
     uint32_t features = 0;                      // LPVMPC_SNAP_HAS_*
     bool recording = false;                     // a recorder is attached (lpvmpc_race_record)
+    bool heats = false;                         // heats are attached (lpvmpc_race_heats)
     const std::vector<int32_t> *track_of = nullptr;   // [B] with tracks bound, else null
     std::vector<RaceStateDesc> tab;
 };
 LPVMPC_HIDDEN bool lpvmpc_race_state(lpvmpc_handle *h, RaceState &s);
 LPVMPC_HIDDEN void lpvmpc_race_set_ticks(lpvmpc_handle *h, int ticks);
+// race_api.hip: what lpvmpc_race_heats / lpvmpc_race_standings (heats_api.hip) need of the running race: its shape, the state a heat
+// tick reads, and the slot that owns the attachment (false: the handle owns no race)
+struct RaceHeatsView {
+    int B = 0, laps = 0;
+    double hw = 0, slack = 0;
+    const double *plant = nullptr;
+    const int32_t *phase = nullptr;
+    std::unique_ptr<HeatsBinding> *slot = nullptr;
+};
+LPVMPC_HIDDEN bool lpvmpc_race_heats_view(lpvmpc_handle *h, RaceHeatsView &v);
 LPVMPC_HIDDEN int lpvmpc_observer_start(lpvmpc_handle *h, const lpvmpc_observer_config &o, int B, const double *plant0, double dt_sim,
                                         int from_plant);                                // lpvmpc_api.hip
 // actuator_api.hip: checks cfg / per-vehicle delays and allocates a zeroed actuator state for B vehicles in a (released first)

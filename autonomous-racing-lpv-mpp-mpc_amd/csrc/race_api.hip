@@ -3,12 +3,13 @@
 // admm_solve.hip and handoff.hip (masked launches).  A race with the estimator in the loop (lpvmpc_race_init_observed) keeps
 // the estimator state, gains and parameters in the path handle's obs_state / obs_gains / obs_p (obs_cfg stays null, so the
 // handle's next lpvmpc_cl_init runs on ground truth); lpvmpc_race_free releases them.  The recorder (lpvmpc_race_record,
-// record.hip) belongs to the race as well.
+// record.hip) and the heats (lpvmpc_race_heats, heats_api.hip / heats.hip) belong to the race as well.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <new>
 
+#include "heats_host.hpp"
 #include "lpvmpc_handle.hpp"
 #include "race_state.hpp"
 #include "record.hpp"
@@ -31,6 +32,7 @@ struct lpvmpc_race {
     PlantTable veh;               // lpvmpc_race_init_vehicles: the plant table (veh.d.p; null: one PlantCfg), with the delayed kernels' actuator
     TyreTable tyre;               // lpvmpc_race_init_tyres: the tyre table next to veh (tyre.t; null: the linear tyre's kernels)
     std::unique_ptr<lpvmpc_race_recorder> rec;   // lpvmpc_race_record (null: not recording)
+    std::unique_ptr<HeatsBinding> heats;         // lpvmpc_race_heats (heats_api.hip; null: none attached)
     DistBinding dist;             // lpvmpc_set_disturbances (dist.d.rows null: none attached), freed with the race
 };
 
@@ -159,6 +161,10 @@ static int race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, i
     HIP_TRY(h, hipMemsetAsync(h->d_uPred, 0, b * N * 2 * 8, st)); HIP_TRY(h, hipMemsetAsync(tt->d_uPred, 0, b * N * 2 * 8, st));
     HIP_TRY(h, hipMemsetAsync(plan->d_uPred, 0, b * Np * 2 * 8, st));
     HIP_TRY(h, hipMemsetAsync(tt->d_curv, 0, b * (N + 1) * 8, st));
+    // the solves' iteration counts, statuses and polish flags are carried rows too (a masked launch leaves the rows of the vehicles it
+    // does not run): 0 until a vehicle's controller or planner has solved, whatever the workspace held when it was allocated
+    for (lpvmpc_handle *e : {h, tt, plan})
+        for (int32_t *p : {e->d_iters, e->d_status, e->d_polish}) HIP_TRY(h, hipMemsetAsync(p, 0, b * 4, st));
     std::vector<double> ones(b * (N + 1), 1.0), mey(b, cfg->plan_max_ey);
     H2D(h->d_vel, ones.data(), ones.size() * 8); H2D(tt->d_vel, ones.data(), ones.size() * 8);
     H2D(plan->d_maxey, mey.data(), b * 8);                                                 // Planner.solve(..., HW)  (PMAIN:162,176)
@@ -250,6 +256,7 @@ bool lpvmpc_race_state(lpvmpc_handle *h, RaceState &s) {
     const int32_t shape[8] = {d.B, N, Np, d.M, r->sd, d.lap_cols, d.laps, r->ticks};
     std::memcpy(s.shape, shape, sizeof(shape));
     s.recording = r->rec != nullptr;
+    s.heats = r->heats != nullptr;
     if (h->trk.tab) s.track_of = &h->trk_of;
     s.features = (d.estv ? LPVMPC_SNAP_HAS_ESTIMATOR : 0u) | (r->act.d.ring ? LPVMPC_SNAP_HAS_ACTUATOR : 0u) |
                  (r->dist.d.rows ? LPVMPC_SNAP_HAS_DISTURBANCES : 0u) | (h->trk.tab ? LPVMPC_SNAP_HAS_TRACKS : 0u);
@@ -291,6 +298,14 @@ bool lpvmpc_race_state(lpvmpc_handle *h, RaceState &s) {
     return true;
 }
 void lpvmpc_race_set_ticks(lpvmpc_handle *h, int ticks) { if (h->race) h->race->ticks = ticks; }
+
+bool lpvmpc_race_heats_view(lpvmpc_handle *h, RaceHeatsView &v) {
+    lpvmpc_race *r = h->race;
+    if (!r) return false;
+    v.B = r->d.B; v.laps = r->d.laps; v.hw = r->d.hw; v.slack = r->d.slack; v.plant = r->d.plant; v.phase = r->d.phase;
+    v.slot = &r->heats;
+    return true;
+}
 
 // the race's actuator state and its two controllers' histories (lpvmpc_actuator_read)
 int lpvmpc_race_act_read(lpvmpc_handle *h, double *act_state, double *path_hist, double *tt_hist) {
@@ -383,6 +398,8 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
             if (trk) HIP_TRY(h, lpvmpc::launch_race_record_trk(*trk, q->d, r->ticks, slot, st));
             else HIP_TRY(h, lpvmpc::launch_race_record(h->d_cfg, q->d, r->ticks, slot, st));
         }
+        if (const HeatsBinding *q = r->heats.get())                                 // the heats (heats.hip)
+            HIP_TRY(h, lpvmpc::launch_heat_tick(h->d_cfg, trk, q->d, q->block, r->ticks, st));
         r->ticks++;
     }
     return LPVMPC_OK;

@@ -84,6 +84,9 @@ extern "C" int lpvmpc_race_restore(lpvmpc_handle *h, const void *buf, int64_t by
     if (s.recording)
         return fail(h, LPVMPC_E_ARG, "%s: a recorder is attached, and its ring and statistics do not travel with the state; stop it first "
                     "(lpvmpc_race_record with capacity 0)", who);
+    if (s.heats)
+        return fail(h, LPVMPC_E_ARG, "%s: heats are attached, and a position history means nothing after a restore; detach them first "
+                    "(lpvmpc_race_heats(path, cfg, NULL, NULL))", who);
     if (!buf || bytes < kHeaderBytes) return fail(h, LPVMPC_E_ARG, "%s: the buffer is NULL or shorter than the %d B header (%lld B)", who, kHeaderBytes, (long long)bytes);
     const char *in = (const char *)buf;
     if (std::memcmp(in, kMagic, 8) != 0) return fail(h, LPVMPC_E_ARG, "%s: not a race snapshot (magic)", who);
@@ -129,6 +132,9 @@ extern "C" int lpvmpc_race_clone(lpvmpc_handle *h, const int32_t *src, int32_t *
     if (s.recording)
         return fail(h, LPVMPC_E_ARG, "%s: a recorder is attached, and its per-vehicle statistics do not move with the state; stop it first "
                     "(lpvmpc_race_record with capacity 0)", who);
+    if (s.heats)
+        return fail(h, LPVMPC_E_ARG, "%s: heats are attached, and their standings do not move with the state; detach them first "
+                    "(lpvmpc_race_heats(path, cfg, NULL, NULL))", who);
     if (!src) return fail(h, LPVMPC_E_ARG, "%s: src is NULL", who);
     const int B = s.shape[0];
     std::vector<int32_t> srcv, dstv;

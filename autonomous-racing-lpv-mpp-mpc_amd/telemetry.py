@@ -2,7 +2,8 @@
 include/lpvmpc.h "Race recorder").  ``lap_stats`` replays a trace in tick order with the recorder's operations -- s = s + x * x,
 each product and sum rounded, and max only when |x| exceeds it -- so on a stride-1 trace of a recorded race it reproduces
 ``BatchedSolver.race_lap_stats`` word for word.  It applies as well to host replays laid out as a trace (dict of [n, B] arrays named
-as ``_ffi.REC_F64_NAMES`` / ``REC_I32_NAMES`` plus ``tick`` [n]); on a trace with gaps only the ticks in it count."""
+as ``_ffi.REC_F64_NAMES`` / ``REC_I32_NAMES`` plus ``tick`` [n]); on a trace with gaps only the ticks in it count.
+``standings_table`` turns the standings of a race's heats (``BatchedSolver.race_standings``) into the table a user prints."""
 from __future__ import annotations
 
 import numpy as np
@@ -67,6 +68,28 @@ def lap_stats(trace, laps, phase0=None, q9_swap=True):
         I[:, _ffi.LAPSTAT_OFF_TRACK] += np.asarray(trace["inside"][t])[c] == 0
         i[b, l] = I
     return _ffi.lap_stats_dict(f, i, end)
+
+
+def standings_table(standings, heat):
+    """Per heat, the vehicles in finishing / running order with their gaps: ``standings`` a ``BatchedSolver.race_standings`` /
+    ``heat_step`` dict, ``heat`` [B] the heats as they were attached (-1: none).  Returns {heat index: dict(vehicle, position, cls,
+    progress, gap_ahead, gap_leader, passes, passed, contact_ticks, min_clearance)} with every array in position order.  Host only.
+    Raises ValueError when the positions of a heat are not 0 .. n-1 (standings of another attachment, or read before the first tick)."""
+    from .heats import check_heats
+    pos = np.asarray(standings["position"])
+    h = check_heats(heat, pos.shape[0])
+    out = {}
+    for g in np.unique(h[h >= 0]):
+        veh = np.nonzero(h == g)[0]
+        p = pos[veh]
+        if not np.array_equal(np.sort(p), np.arange(veh.shape[0])):
+            raise ValueError("standings_table: the positions of heat %d are not a permutation of 0 .. %d" % (int(g), veh.shape[0] - 1))
+        v = veh[np.argsort(p)]
+        row = dict(vehicle=v, position=pos[v], cls=np.asarray(standings["class"])[v])
+        for k in ("progress", "gap_ahead", "gap_leader", "passes", "passed", "contact_ticks", "min_clearance"):
+            row[k] = np.asarray(standings[k])[v]
+        out[int(g)] = row
+    return out
 
 
 def add_rmse(stats):

@@ -488,8 +488,8 @@ int  lpvmpc_race_init_observed(lpvmpc_handle *path, lpvmpc_handle *tt, lpvmpc_ha
 int  lpvmpc_race_tick(lpvmpc_handle *path, int32_t n_ticks);
 /* synchronises and copies (any pointer may be NULL): plant [B][8], local_state [B][6] (the last measurement), cmd [B][2],
  * phase / lap [B]; iters / status [B]: the controller solve of the vehicle's phase on the last tick (iters 0 and status
- * unchanged when it did not solve: frozen, lost); plan_iters / plan_status [B] of the vehicle's last planner tick;
- * ticks [1] = ticks run. */
+ * unchanged when it did not solve: frozen, lost); plan_iters / plan_status [B] of the vehicle's last planner tick (0 before
+ * its first: the race's start zeroes the three handles' iteration, status and polish rows); ticks [1] = ticks run. */
 int  lpvmpc_race_read(lpvmpc_handle *path, double *plant, double *local_state, double *cmd, int32_t *phase,
                       int32_t *lap, int32_t *iters, int32_t *status, int32_t *plan_iters, int32_t *plan_status,
                       int32_t *ticks);
@@ -1103,6 +1103,116 @@ int  lpvmpc_race_snapshot_size(lpvmpc_handle *path, int64_t *bytes);
 int  lpvmpc_race_snapshot(lpvmpc_handle *path, void *buf, int64_t bytes);
 int  lpvmpc_race_restore(lpvmpc_handle *path, const void *buf, int64_t bytes);
 int  lpvmpc_race_clone(lpvmpc_handle *path, const int32_t *src /* [B] */, int32_t *moved /* out, may be NULL */);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Heats: standings, gaps, passes and contacts of the vehicles of a race that share a track, kept on the device.  A heat is a set of
+ * vehicles of one race that are taken to be on one track together; each vehicle belongs to one heat or to none, a heat has at most
+ * LPVMPC_HEAT_MAX members.  While heats are attached, lpvmpc_race_tick launches one more kernel per tick, after the command / plant
+ * kernel (one workgroup per heat, the members staged in LDS); with none attached a tick issues the launches it always did.  Heats
+ * only observe: no output of the race changes.  Everything below is per vehicle b of heat g, on tick t (the race's tick number
+ * counted before the tick, as the recorder's).
+ *
+ * Track frame.  (s, ey, epsi, inside) = Map.getLocalPosition of the ground-truth plant (x, y, yaw) with the race's half_width /
+ * slack (each track's own, with tracks bound): the recorder's LPVMPC_REC_TRACK function, sentinels included.
+ * Located: inside == 1 and s finite.  A vehicle that is not located keeps the s and turns of the last tick on which it was; one
+ * never located since the attach has progress NaN.
+ * Turns and progress.  turns starts at turns0[b] (NULL: 0; -1 for a car gridded behind the line).  Between two located ticks
+ * turns += 1 when s_now - s_last < -L / 2 and turns -= 1 when s_now - s_last > L / 2, L the length of the vehicle's track.
+ * progress = (double)turns * L + s, product and sum each rounded (no fused multiply-add).  turns has nothing to do with the race's
+ * lap counter: the lap events fire ahead of the line (CMAIN:254-272), turns counts crossings of s = 0 itself.
+ * Class, from the race's phase: 0 finished (phase 2), 1 running and located at least once, 2 running and never located, 3 lost
+ * (phase 3).
+ * Order within a heat -- a total order, so positions are a permutation of 0 .. n-1: by class ascending; within class 0 by finish
+ * tick ascending (the tick on which phase became 2 while heats were attached; -1, sorting first, for a vehicle that had finished
+ * before the attach), then progress descending, then vehicle index ascending; within classes 1 and 3 by progress descending (a
+ * lost vehicle keeps its last progress; NaN sorts last), then index; within class 2 by index.
+ * position = the number of members ordered before b; ahead = the member one place in front (-1 for the leader);
+ * gap_ahead = progress[ahead] - progress[b], gap_leader = progress[leader] - progress[b], one subtraction each, NaN when either
+ * vehicle is outside class 1 or b leads.
+ * Passes.  For an unordered pair (i, j) of members that are both class 1 on the previous tick and on this one: when i was ordered
+ * behind j on the previous tick and is in front of j on this one, passes[i] += 1 and passed[j] += 1.  The first tick after the
+ * attach counts nothing.
+ * Line crossings, K = laps + 2.  When turns reaches turns0 + k + 1 for the first time, 0 <= k < K, line_tick[b][k] = t and
+ * line_pos[b][k] = position of that tick; untouched entries are -1.
+ * Footprint and clearance.  A footprint is the rectangle centred at (x, y) with heading yaw and half extents half_length /
+ * half_width_car (defaults 0.4 / 0.2, the reference's drawn car, plotCarTrajectory.py:115,161-166).  For a pair, sep is the largest
+ * of the four separating-axis gaps |d . a| - (r_own(a) + r_other(a)) over the two axes a of each rectangle: d the difference of the
+ * centres, r_own the rectangle's own half extent along its axis, r_other the other rectangle's projected half extent,
+ * half_length |u . a| + half_width_car |v . a| with u / v its axes.  The rectangles overlap exactly when sep < 0.  Both vehicles
+ * evaluate sep with the lower index as the first rectangle, so it is the same word on both sides.  Only pairs of vehicles that are
+ * both class 1 or 2 with a finite pose take part (finished and lost cars have left the track).  Per tick: clearance = the smallest
+ * sep over the vehicle's partners (+inf without one), nearest = that partner (lowest index on a tie, -1 without one), contact =
+ * clearance < 0.  Since the attach: min_clearance, contact_ticks, first_contact_tick (-1: none).
+ *
+ * lpvmpc_race_heats attaches heats from the next tick: heat [B], the heat of each vehicle, -1 for none (indices need not be dense,
+ * empty heats are allowed); turns0 [B] or NULL.  It frees a previous attachment first; heat == NULL detaches.  The member lists are
+ * built on the host and the attachment is installed only when it is whole.  Refused with LPVMPC_E_ARG: no race on the handle, a heat
+ * index below -1, a heat of more than LPVMPC_HEAT_MAX members, extents that are not finite and positive, and, with tracks bound, a
+ * heat whose members are on different palette entries; a refused argument leaves a previous attachment as it was.  A failed
+ * allocation or copy (LPVMPC_E_NOMEM, LPVMPC_E_HIP) comes after the previous attachment was freed and leaves the race without heats.
+ * The attachment belongs to the race, as the recorder does:
+ * lpvmpc_cl_release(path) or destroying a handle frees it, a new race starts without heats.  lpvmpc_race_snapshot works with heats
+ * attached and does not contain them; lpvmpc_race_restore and lpvmpc_race_clone are refused while heats are attached (detach with
+ * lpvmpc_race_heats(path, cfg, NULL, NULL)): a position history means nothing after a restore.
+ *
+ * lpvmpc_race_standings synchronises and copies (any pointer may be NULL) two planes, channel-major and vehicle-minor as the
+ * recorder's, f64 [LPVMPC_HEAT_F64][B] and i32 [LPVMPC_HEAT_I32][B], and line_tick / line_pos [B][laps + 2].  A vehicle in no heat
+ * reads NaN in every f64 channel, -1 in position, ahead, nearest, first_contact_tick and class, 0 in contact, contact_ticks, passes,
+ * passed and turns, -1 in its line tables; so does every vehicle before the first tick after the attach (a member's turns reads turns0).
+ * Refused with LPVMPC_E_ARG while no heats are attached.
+ *
+ * lpvmpc_heat_step_batch is one tick of the same device function on caller-supplied data (as lpvmpc_plant_step_*_batch): heat [B]
+ * with indices in [-1, n_heats), L [B] each vehicle's track length, pose [B][3] = x y yaw, s [B] / inside [B] the track frame,
+ * phase [B].  The caller owns the state carried from tick to tick and passes it in and gets it back: carry_f64
+ * [LPVMPC_HEAT_CARRY_F64][B] and carry_i32 [LPVMPC_HEAT_CARRY_I32][B], channel-major.  A carry with flag word 0 is the state "just
+ * attached": its TURNS word is turns0, its PHASE word the phase before the attach (0: running), every other word is ignored and
+ * written; so an all-zero carry is a fresh attachment with turns0 = 0.  CROSSINGS counts the lines crossed since the attach: on the
+ * tick it becomes k + 1 the race writes line_tick[b][k] / line_pos[b][k].  Outputs f64 / i32 as lpvmpc_race_standings.  It needs a
+ * handle (device and stream) that runs no fleet, cascade or race. */
+#define LPVMPC_HEAT_MAX                 256
+#define LPVMPC_HEAT_F64                   5
+#define LPVMPC_HEAT_PROGRESS              0
+#define LPVMPC_HEAT_GAP_AHEAD             1
+#define LPVMPC_HEAT_GAP_LEADER            2
+#define LPVMPC_HEAT_CLEARANCE             3
+#define LPVMPC_HEAT_MIN_CLEARANCE         4
+#define LPVMPC_HEAT_I32                  10
+#define LPVMPC_HEAT_POSITION              0
+#define LPVMPC_HEAT_AHEAD                 1
+#define LPVMPC_HEAT_NEAREST               2
+#define LPVMPC_HEAT_CONTACT               3
+#define LPVMPC_HEAT_CONTACT_TICKS         4
+#define LPVMPC_HEAT_FIRST_CONTACT_TICK    5
+#define LPVMPC_HEAT_PASSES                6
+#define LPVMPC_HEAT_PASSED                7
+#define LPVMPC_HEAT_TURNS                 8
+#define LPVMPC_HEAT_CLASS                 9
+#define LPVMPC_HEAT_CARRY_F64             3
+#define LPVMPC_HEAT_CARRY_S               0  /* s of the last located tick */
+#define LPVMPC_HEAT_CARRY_PROGRESS        1  /* progress of the previous tick */
+#define LPVMPC_HEAT_CARRY_MIN_CLEARANCE   2
+#define LPVMPC_HEAT_CARRY_I32            10
+#define LPVMPC_HEAT_CARRY_FLAGS           0  /* bit 0: a tick has run since the attach; bit 1: located at least once */
+#define LPVMPC_HEAT_CARRY_TURNS           1
+#define LPVMPC_HEAT_CARRY_TURNS0          2
+#define LPVMPC_HEAT_CARRY_CROSSINGS       3
+#define LPVMPC_HEAT_CARRY_PHASE           4  /* phase of the previous tick */
+#define LPVMPC_HEAT_CARRY_FINISH_TICK     5
+#define LPVMPC_HEAT_CARRY_CONTACT_TICKS   6
+#define LPVMPC_HEAT_CARRY_FIRST_CONTACT   7
+#define LPVMPC_HEAT_CARRY_PASSES          8
+#define LPVMPC_HEAT_CARRY_PASSED          9
+typedef struct lpvmpc_heats_config {
+    double half_length;       /* half extents of a vehicle's footprint, along and across its heading */
+    double half_width_car;
+} lpvmpc_heats_config;
+void lpvmpc_heats_default_config(lpvmpc_heats_config *cfg);
+int  lpvmpc_race_heats(lpvmpc_handle *path, const lpvmpc_heats_config *cfg, const int32_t *heat /* [B], -1: none */,
+                       const int32_t *turns0 /* [B] or NULL */);
+int  lpvmpc_race_standings(lpvmpc_handle *path, double *f64, int32_t *i32, int32_t *line_tick, int32_t *line_pos);
+int  lpvmpc_heat_step_batch(lpvmpc_handle *h, int32_t B, int32_t n_heats, const int32_t *heat, const double *L,
+                            const lpvmpc_heats_config *cfg, int32_t t, const double *pose, const double *s, const int32_t *inside,
+                            const int32_t *phase, double *carry_f64, int32_t *carry_i32, double *f64, int32_t *i32);
 
 #ifdef __cplusplus
 }

@@ -51,8 +51,12 @@ median over --reps calls, in ms, of a snapshot (device to host, the blob's bytes
 moved (a rotation by one) and a clone with 10 % of the vehicles moved (random slots from random sources), beside the ms per race tick
 of the same regime as the scale (the parent's where --parent-lib is given); the blob's bytes per vehicle; and for the full clone
 the GB/s over the bytes its two kernels read plus write (the state goes through the staging buffer: four times its size).
-Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator | --actuator | --record | --plant-params | --models | --tunings |
-       --tyres | --observer-vehicles | --tracks | --disturbance | --fork [--parent-lib FILE] [--reps R]] [--out FILE]"""
+--heats SIZE: instead, the lap0 and inphase races run with heats detached and with heats of SIZE consecutive vehicles attached
+(lpvmpc_race_heats: one more launch per tick, one workgroup per heat), alternated --reps times per (regime, B) in one process; medians, each
+configuration's spread over the alternations and the added ms per controller tick; and, with --parent-lib FILE, the detached race on that
+build, one child process per run: the launches are identical, so it must lie within the alternation's spread.
+Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator | --actuator | --record | --heats SIZE | --plant-params | --models |
+       --tunings | --tyres | --observer-vehicles | --tracks | --disturbance | --fork [--parent-lib FILE] [--reps R]] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -84,7 +88,7 @@ def timed(tick, read, K):
 
 
 def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, record=False, plant_params=None, model_params=None, tunings=None,
-             tyre_params=None, observer_vehicles=False, tracks=None, disturbance=None):
+             tyre_params=None, observer_vehicles=False, tracks=None, disturbance=None, heats=0):
     path, tt, plan = engines(mp, sd)
     if tracks is not None:                                            # (maps, track_of) bound to the three engines
         for e in (path, tt, plan):
@@ -109,6 +113,8 @@ def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, rec
     path.race_tick(warm)
     if record:
         path.race_record(K, 1)
+    if heats:                                                         # heats of `heats` consecutive vehicles
+        path.race_heats(np.arange(plant0.shape[0]) // int(heats))
     a0 = path.race_laps()[1].sum()
     ms = timed(path.race_tick, path.race_read, K)
     alive = path.race_laps()[1].sum() - a0
@@ -127,6 +133,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--actuator", action="store_true")
     ap.add_argument("--record", action="store_true")
+    ap.add_argument("--heats", type=int, default=0, metavar="SIZE")
     ap.add_argument("--plant-params", action="store_true")
     ap.add_argument("--models", action="store_true")
     ap.add_argument("--tunings", action="store_true")
@@ -165,6 +172,8 @@ def main():
         return plant_params_main(a)
     if a.record:
         return record_main(a)
+    if a.heats:
+        return heats_main(a)
     if a.estimator:
         return estimator_main(a)
     if a.actuator:
@@ -520,6 +529,38 @@ def record_main(a):
                          "added %+.3f ms/tick" % (name, B, m0, " ".join("%.3f" % x for x in ms[False]), ph[False].tolist(), m1,
                                                   " ".join("%.3f" % x for x in ms[True]), ph[True].tolist(), m1 - m0))
             print(lines[-1], flush=True)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+def heats_main(a):
+    import subprocess
+    import lpvmpc
+    mp = lpvmpc.Map("L_shape", 0.2)
+    lines = []
+    for B in [int(x) for x in a.sizes.split(",")]:
+        for name, (plant0, half, warm) in _models_starts(B).items():
+            ms = {"detached": [], "attached": [], "parent": []}
+            ph = {}
+            for _ in range(a.reps):
+                for k in ("detached", "attached"):
+                    m, _vps, ph[k] = race_run(mp, plant0, half, warm, a.ticks, heats=a.heats if k == "attached" else 0)
+                    ms[k].append(m)
+                if a.parent_lib:
+                    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--ticks", str(a.ticks), "--models-child", a.parent_lib, name,
+                                          str(B), "0"], check=True, capture_output=True, text=True, timeout=600).stdout
+                    ms["parent"].append(float([l for l in out.splitlines() if l.startswith("MODELS_RUN")][-1].split()[1]))
+            m0, m1 = float(np.median(ms["detached"])), float(np.median(ms["attached"]))
+            line = ("%-8s B=%5d  heats of %d  detached %.3f ms/tick (runs %s, spread %.3f, phases %s)  attached %.3f ms/tick (runs %s, spread %.3f)  "
+                    "added %+.3f ms/tick" % (name, B, a.heats, m0, " ".join("%.3f" % x for x in ms["detached"]), max(ms["detached"]) - min(ms["detached"]),
+                                             ph["detached"].tolist(), m1, " ".join("%.3f" % x for x in ms["attached"]),
+                                             max(ms["attached"]) - min(ms["attached"]), m1 - m0))
+            if a.parent_lib:
+                mp_ = float(np.median(ms["parent"]))
+                line += "  parent, detached %.3f ms/tick (runs %s)  vs detached %+.3f ms/tick" % (mp_, " ".join("%.3f" % x for x in ms["parent"]), mp_ - m0)
+            lines.append(line)
+            print(line, flush=True)
     if a.out:
         with open(a.out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
