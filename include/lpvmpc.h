@@ -267,7 +267,22 @@ int lpvmpc_estimate_abc_batch(lpvmpc_handle *h, int32_t B, const double *xlast, 
  * outputs:
  *   xPred [B][N+1][nx], uPred [B][N][2]  (NaN for instances without a solution, as OSQP returns)
  *   status [B], iters [B]  (may be NULL)
- *   resid  [B][4] = {pri_res, dua_res, obj_val, rho_final}  (may be NULL)
+ *   resid  [B][4] = {pri_res, dua_res, obj_val, rho_final}  (may be NULL): OSQP's info words, in the unscaled problem.
+ *                   pri_res = |Ax - z|_inf and dua_res = |Px + q + A'y|_inf of the point the status refers to; obj_val = 1/2 x'Px + q'x
+ *                   of the returned point; rho_final = the rho of the last ADMM iteration (the configured rho when adaptive_rho = 0,
+ *                   adaptive_rho_interval = 0 or max_iter < adaptive_rho_interval).  By status:
+ *                     SOLVED, polish accepted (polish = 1)   the polished point's residuals and objective; rho_final stays the ADMM's
+ *                     SOLVED, polish rejected (-1) or off (0), SOLVED_INACCURATE, MAX_ITER_REACHED
+ *                                                            the last ADMM iterate's residuals and objective (the point returned)
+ *                     PRIMAL_INFEASIBLE (exact / inaccurate) obj_val = +1e30; pri_res / dua_res of the last iterate; xPred / uPred NaN
+ *                     DUAL_INFEASIBLE (exact / inaccurate)   obj_val = -1e30; likewise
+ *                     UNSOLVED (non-finite inputs: no iteration is run)   four NaN
+ *                     LPVMPC_PENDING (parked by the straggler deferral)   not written yet: the caller's words stay until the
+ *                                                            instance's results arrive with its final status
+ *                   One difference from OSQP, in rho_final alone: when max_iter is off the check_termination grid and on the
+ *                   adaptive_rho_interval grid, a run that the closing check of iteration max_iter ends as SOLVED or (PRIMAL / DUAL)
+ *                   INFEASIBLE reports the rho of iteration max_iter - 1 -- OSQP updates rho once more in front of that check
+ *                   (tests/_tolerance.py late_rho; the iterate, the status and the other words are OSQP's).
  *   polish [B]    = OSQP status_polish (1 accepted, -1 rejected, 0 not run)  (may be NULL)
  */
 int lpvmpc_solve_batch_AB(lpvmpc_handle *h, int32_t B, const double *x0, const double *A, const double *Bm,

@@ -234,15 +234,18 @@ def instance_qp(w, kind, j, params=None, limits=None):
                            p["min_vel"], **lim)
 
 
-def tick_batch_qp(w, kind, settings=None, params=None, limits=None, nthreads=16, qps=None):
+def tick_batch_qp(w, kind, settings=None, params=None, limits=None, nthreads=16, qps=None, order="stage"):
     """One tick of a batch, instance by instance: the LPV roll-out and the reference's QP (instance_qp: vehicle ``params``,
     QP ``limits``) solved by the OSQP restatement under ``settings`` (a BatchedSolver settings dict, see osqp_settings).
     ``kind`` "controller" (``u_old`` (B, 2 + d): d = steeringDelay pinned-steering rows) or "planner".  Elimination order:
     the stage-wise one of the C ticks (ctrl_delay_ordering, plan_ordering): at default arguments the statuses and iteration
     counts equal ctrl_tick_batch / plan_tick_batch's; the solutions differ by the round-off of the C ticks' own LPV / QP assembly
-    (polished within 1e-10, tests/test_settings_host.py).  Returns dict(xPred, uPred, status, iters, polish, z, y); ``nthreads``
-    (<= 16) solves run at a time (the solver releases the GIL).  ``qps``: the instances' QPs (a list of instance_qp results
-    or None entries for a roll-out that left the track) when the caller solves the same batch under several settings."""
+    (polished within 1e-10, tests/test_settings_host.py).  Returns dict(xPred, uPred, status, iters, polish, z, y, resid);
+    ``resid`` (B, 4) holds the solver's own (pri_res, dua_res, obj_val, rho_final) in the order of the device's resid words, NaN
+    for an instance without an answer (-10).  ``nthreads`` (<= 16) solves run at a time (the solver releases the GIL).  ``qps``: the instances' QPs (a list of instance_qp results
+    or None entries for a roll-out that left the track) when the caller solves the same batch under several settings.
+    ``order`` "rcm": solve_qp's default elimination order instead of the stage-wise one (the same KKT matrix: the two results
+    differ by round-off alone, the yardstick of tests/_tolerance.py check_resid)."""
     from concurrent.futures import ThreadPoolExecutor
     N = int(w["N"])
     x0 = np.asarray(w["x0"], np.float64); B = x0.shape[0]
@@ -255,6 +258,10 @@ def tick_batch_qp(w, kind, settings=None, params=None, limits=None, nthreads=16,
     else:
         perm, m = plan_ordering(N), (N + 1) * nx + nz
     kw = osqp_settings(settings)
+    if order == "rcm":
+        perm = "rcm"
+    elif order != "stage":
+        raise ValueError(order)
 
     def one(j):
         # no answer (NaN, UNSOLVED -10): a roll-out that leaves the track table (the reference raises, UTIL:44-48) or a KKT
@@ -265,15 +272,16 @@ def tick_batch_qp(w, kind, settings=None, params=None, limits=None, nthreads=16,
                 raise ValueError("no QP")
             r = solve_qp(qp.P, qp.q, qp.A, qp.l, qp.u, perm=perm, **kw)
         except (ValueError, RuntimeError):
-            return np.full(nz, np.nan), np.full(m, np.nan), -10, 0, 0
-        return r.x, r.y, r.info.status_val, r.info.iter, r.info.status_polish
+            return np.full(nz, np.nan), np.full(m, np.nan), -10, 0, 0, (np.nan,) * 4
+        return r.x, r.y, r.info.status_val, r.info.iter, r.info.status_polish, (r.info.pri_res, r.info.dua_res, r.info.obj_val, r.info.rho_final)
 
     with ThreadPoolExecutor(max_workers=max(1, min(16, int(nthreads)))) as ex:
         res = list(ex.map(one, range(B)))
     z = np.array([r[0] for r in res]).reshape(B, nz)
     return dict(xPred=z[:, :(N + 1) * nx].reshape(B, N + 1, nx).copy(), uPred=z[:, (N + 1) * nx:].reshape(B, N, 2).copy(), z=z,
                 y=np.array([r[1] for r in res]).reshape(B, m), status=np.array([r[2] for r in res], np.int32).reshape(B),
-                iters=np.array([r[3] for r in res], np.int32).reshape(B), polish=np.array([r[4] for r in res], np.int32).reshape(B))
+                iters=np.array([r[3] for r in res], np.int32).reshape(B), polish=np.array([r[4] for r in res], np.int32).reshape(B),
+                resid=np.array([r[5] for r in res], np.float64).reshape(B, 4))
 
 
 def ctrl_tick_batch_delay(w, nthreads=1, params=None):
