@@ -93,6 +93,11 @@ class DisturbanceConfig(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("vehicle_offset", C.c_int64), ("n_bound", _d)]
 
 
+class SensorFaultConfig(C.Structure):
+    """Mirror of ``struct lpvmpc_sensor_fault_config`` (include/lpvmpc.h)."""
+    _fields_ = [("seed", C.c_uint64), ("vehicle_offset", C.c_int64)]
+
+
 class RaceRecordConfig(C.Structure):
     """Mirror of ``struct lpvmpc_race_record_config`` (include/lpvmpc.h)."""
     _fields_ = [("capacity", _i), ("stride", _i)]
@@ -150,6 +155,8 @@ TYRE_WORDS = 4                           # LPVMPC_TYRE_WORDS: [kind, B, C, c_f] 
 TYRE_WORD_NAMES = ("kind", "B", "C", "c_f")
 DIST_WORDS, DIST_STATE = 13, 5           # LPVMPC_DIST_WORDS, LPVMPC_DIST_STATE (disturbance.py)
 DIST_STREAM = 0xD157A2B3C4D5E6F7         # LPVMPC_DIST_STREAM
+FAULT_WORDS, OBS_STATE_WORDS = 12, 18    # LPVMPC_FAULT_WORDS, LPVMPC_OBS_STATE_WORDS (sensor_faults.py)
+FAULT_STREAM = 0x5E4507FA17C0FFEE        # LPVMPC_FAULT_STREAM
 MODEL_WORDS = 7                          # LPVMPC_MODEL_WORDS: the same words, as a controller's / planner's model of the vehicle
 MAX_TRACKS = 64                          # LPVMPC_MAX_TRACKS: entries of a track palette (track.pack_tracks)
 TUNING_WORDS = 64                        # LPVMPC_TUNING_WORDS: Q[36] R[4] dR[2] L_cf[6] limits[16] per instance (tuning.py)
@@ -180,7 +187,8 @@ EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_d
            "lpvmpc_disturbance_default_config", "lpvmpc_set_disturbances", "lpvmpc_disturbances_read",
            "lpvmpc_plant_step_disturbed_batch",
            "lpvmpc_race_snapshot_size", "lpvmpc_race_snapshot", "lpvmpc_race_restore", "lpvmpc_race_clone",
-           "lpvmpc_heats_default_config", "lpvmpc_race_heats", "lpvmpc_race_standings", "lpvmpc_heat_step_batch")
+           "lpvmpc_heats_default_config", "lpvmpc_race_heats", "lpvmpc_race_standings", "lpvmpc_heat_step_batch",
+           "lpvmpc_sensor_fault_default_config", "lpvmpc_set_sensor_faults", "lpvmpc_sensor_faults_read", "lpvmpc_sensor_step_batch")
 
 _lib = None
 
@@ -372,6 +380,16 @@ def load():
             getattr(lib, name).restype = C.c_int
     except AttributeError:
         pass
+    try:        # (nor the sensor faults)
+        lib.lpvmpc_sensor_fault_default_config.argtypes = [P(SensorFaultConfig)]
+        lib.lpvmpc_sensor_fault_default_config.restype = None
+        lib.lpvmpc_set_sensor_faults.argtypes = [vp, _i, P(SensorFaultConfig), vp]
+        lib.lpvmpc_sensor_faults_read.argtypes = [vp, P(_i), vp]
+        lib.lpvmpc_sensor_step_batch.argtypes = [vp, _i, P(ObserverConfig), _d, P(SensorFaultConfig), vp, vp, vp, vp, vp]
+        for name in ("lpvmpc_set_sensor_faults", "lpvmpc_sensor_faults_read", "lpvmpc_sensor_step_batch"):
+            getattr(lib, name).restype = C.c_int
+    except AttributeError:
+        pass
     try:        # (nor the race recorder)
         lib.lpvmpc_race_record.argtypes = [vp, P(RaceRecordConfig)]
         lib.lpvmpc_race_record_read.argtypes = [vp, _i, vp, vp, vp, vp]
@@ -445,6 +463,12 @@ def default_observer_config():
 def default_disturbance_config():
     cfg = DisturbanceConfig()
     load().lpvmpc_disturbance_default_config(C.byref(cfg))
+    return cfg
+
+
+def default_sensor_fault_config():
+    cfg = SensorFaultConfig()
+    load().lpvmpc_sensor_fault_default_config(C.byref(cfg))
     return cfg
 
 

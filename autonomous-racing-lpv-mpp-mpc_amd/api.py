@@ -363,6 +363,47 @@ class BatchedSolver:
         self._chk(self._lib.lpvmpc_disturbances_read(self._h, ptr(rows), ptr(state)))
         return rows, state
 
+    def set_sensor_faults(self, rows, seed=0, vehicle_offset=0):
+        """Attach sensor faults to the lap-0 fleet or race this engine runs (lpvmpc_set_sensor_faults; the path engine, for a race),
+        from the next tick on: ``rows`` [B, 12] (sensor_faults.fault_rows / sample_faults).  The fleet or race must have the estimator
+        in the loop and have been started with ``tyre_params`` ("linear": kind 0 rows).  ``None`` detaches."""
+        from .sensor_faults import check_fault_rows, sensor_fault_config
+        race = getattr(self, "_race", None) is not None
+        B = self._race[0] if race else getattr(self, "_cl_B", 0)
+        if rows is None:
+            self._chk(self._lib.lpvmpc_set_sensor_faults(self._h, B, None, None))
+            return
+        r = check_fault_rows(rows, np.asarray(rows).shape[0] if np.asarray(rows).ndim == 2 else B)
+        fc = sensor_fault_config(seed, vehicle_offset)
+        self._chk(self._lib.lpvmpc_set_sensor_faults(self._h, r.shape[0], C.byref(fc), ptr(r)))
+
+    def sensor_faults(self):
+        """The attached sensor fault rows [B, 12], or None with none attached (lpvmpc_sensor_faults_read)."""
+        n = C.c_int32(0)
+        self._chk(self._lib.lpvmpc_sensor_faults_read(self._h, C.byref(n), None))
+        if n.value == 0:
+            return None
+        rows = np.empty((n.value, _ffi.FAULT_WORDS))
+        self._chk(self._lib.lpvmpc_sensor_faults_read(self._h, C.byref(n), ptr(rows)))
+        return rows
+
+    def sensor_step(self, cfg, obs_state, plant, servo, motor, rows=None, seed=0, vehicle_offset=0, dt_sim=0.005):
+        """One sensors + observer sub-step per vehicle on caller arrays (lpvmpc_sensor_step_batch), as the fused fleet kernels run it
+        once per plant step: ``obs_state`` [B, 18] (sensor_faults.OBS_STATE_NAMES), ``plant`` [B, 8] the plant state just advanced,
+        ``servo`` / ``motor`` [B] the commanded input, ``cfg`` the estimator configuration.  ``rows`` [B, 12]: the faulted sensor stage
+        (None: the healthy one).  An engine with per-vehicle estimator rows bound runs the bound form.  Returns the new state."""
+        from .sensor_faults import check_fault_rows, sensor_fault_config
+        os_ = f64(obs_state).reshape(-1, _ffi.OBS_STATE_WORDS).copy()
+        B = os_.shape[0]
+        p = f64(plant, (B, 8), "plant")
+        sv = np.ascontiguousarray(np.broadcast_to(np.asarray(servo, float), (B,)))
+        mo = np.ascontiguousarray(np.broadcast_to(np.asarray(motor, float), (B,)))
+        r = None if rows is None else check_fault_rows(rows, B)
+        fc = sensor_fault_config(seed, vehicle_offset)
+        self._chk(self._lib.lpvmpc_sensor_step_batch(self._h, B, C.byref(cfg), float(dt_sim), C.byref(fc), ptr(r), ptr(os_), ptr(p), ptr(sv),
+                                                     ptr(mo)))
+        return os_
+
     def tyre_force(self, tyre_params, m, alpha):
         """The tyre curve on the device (lpvmpc_tyre_force_batch): force [B] of tyre row b at slip angle alpha [B] for mass m
         (scalar or [B]); tyre_params [B, 4] or "pacejka"."""
@@ -1326,12 +1367,15 @@ class RaceFleet(object):
     half width and slack (``tracks()`` reads the binding back; ``plan_max_ey`` stays one value per race).
     ``disturbance``: [B, 13] rows (disturbance.disturbance_rows, disturbance.sample_disturbances) or dict(rows=, seed=,
     vehicle_offset=, n_bound=): gusts, a kick and grip patches on the plant from the first tick on (``disturb`` attaches or detaches
-    mid-race, ``disturbance()`` reads rows and state back); it selects ``tyre_params="linear"`` when none is given."""
+    mid-race, ``disturbance()`` reads rows and state back); it selects ``tyre_params="linear"`` when none is given.
+    ``sensor_faults`` (with ``estimator``): [B, 12] rows (sensor_faults.fault_rows, sensor_faults.sample_faults) or dict(rows=, seed=,
+    vehicle_offset=): GPS loss and jumps, IMU bias and drift, a slipping or stuck encoder from the first tick on (``fault`` attaches or
+    detaches mid-race, ``faults()`` reads the rows back); it selects ``tyre_params="linear"`` when none is given."""
 
     def __init__(self, track_map, plant0, laps=1, N=20, Np=40, half_track0=None, device=0, estimator=None, actuator=None,
                  steering_delay=0, delay_a=None, delay_df=None, plant_params=None, model_params=None, path_tunings=None,
                  tt_tunings=None, plan_tunings=None, tyre_params=None, estimator_params=None, estimator_design=None, track_of=None,
-                 disturbance=None, **options):
+                 disturbance=None, sensor_faults=None, **options):
         from .workloads import CTRL_TUNINGS, PLAN_L, PLAN_Q, PLAN_R, PLAN_dR
         race_keys = ("n_sub_lap0", "n_sub", "q9_swap", "plan_max_ey", "dt_sim", "mu_sim")
         race_opts = {k: v for k, v in options.items() if k in race_keys}
@@ -1397,11 +1441,23 @@ class RaceFleet(object):
                 tyre_params = "linear"                           # the start that runs the binding (each track's width and slack)
         if disturbance is not None and tyre_params is None:
             tyre_params = "linear"                               # the start whose tables the disturbances scale
+        if sensor_faults is not None and tyre_params is None:
+            tyre_params = "linear"                               # the start whose fused kernel has a faulted form
         self.path.race_init(self.tt, self.planner, plant0, half_track0=half_track0, laps=laps, half_width=track_map.halfWidth,
                             slack=track_map.slack, estimator=estimator, actuator=actuator, delay_a=delay_a, delay_df=delay_df,
                             plant_params=plant_params, tyre_params=tyre_params, **race_opts)
         if disturbance is not None:
             self.disturb(**disturbance) if isinstance(disturbance, dict) else self.disturb(disturbance)
+        if sensor_faults is not None:
+            self.fault(**sensor_faults) if isinstance(sensor_faults, dict) else self.fault(sensor_faults)
+
+    def fault(self, rows, seed=0, vehicle_offset=0):
+        """Attach sensor faults from the next tick on (BatchedSolver.set_sensor_faults on the path engine); ``None`` detaches."""
+        self.path.set_sensor_faults(rows, seed=seed, vehicle_offset=vehicle_offset)
+
+    def faults(self):
+        """The attached sensor fault rows [B, 12], or None (BatchedSolver.sensor_faults)."""
+        return self.path.sensor_faults()
 
     def disturb(self, rows, seed=0, vehicle_offset=0, n_bound=None):
         """Attach plant disturbances from the next tick on (BatchedSolver.set_disturbances on the path engine); ``None`` detaches."""

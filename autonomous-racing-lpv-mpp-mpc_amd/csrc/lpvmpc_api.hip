@@ -843,6 +843,15 @@ extern "C" int lpvmpc_cl_tick(lpvmpc_handle *h, int32_t n_ticks) {
         else if (trk)
             HIP_TRY(h, lpvmpc::launch_cl_command_plant_measure_trk(*trk, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, tyre_plant(h->cl_veh, h->cl_tyre), h->cl_q9,
                                                                    h->cl_local_next, h->d_uold, h->cfg.steering_delay, h->cl_act.d, st));
+        else if (h->cl_fault.d.rows && h->ov.L)                              // lpvmpc_set_sensor_faults: in place of the tyre forms' kernel
+            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_faulted_obsveh(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, tyre_plant(h->cl_veh, h->cl_tyre),
+                                                                               h->cl_hw, h->cl_slack, h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay,
+                                                                               lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, h->cl_act.d,
+                                                                               h->cl_fault.d, st));
+        else if (h->cl_fault.d.rows)
+            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_faulted(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, tyre_plant(h->cl_veh, h->cl_tyre),
+                                                                        h->cl_hw, h->cl_slack, h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay,
+                                                                        h->obs_gains, h->obs_state, h->obs_p, h->cl_act.d, h->cl_fault.d, st));
         else if (h->cl_tyre.t && h->obs_state && h->ov.L)
             HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_tyre_obsveh(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, tyre_plant(h->cl_veh, h->cl_tyre),
                                                                             h->cl_hw, h->cl_slack, h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay,

@@ -365,4 +365,31 @@ struct DistDev {
 // trk null: the handle's own track (dcfg, d.hw, d.slack); else every vehicle on its palette entry
 hipError_t launch_disturbance(const DevCfg *dcfg, const TrackDev *trk, const DistDev &d, hipStream_t s);
 
+// sensor faults (sensor_faults.hip; lpvmpc_set_sensor_faults, include/lpvmpc.h "Sensor faults"): the binding on the device, passed
+// by value to the faulted fused kernels, which a tick launches in place of its command / plant / observe kernel
+constexpr int kFaultWords = 12;              // = LPVMPC_FAULT_WORDS
+struct FaultDev {
+    const double *rows;                      // [kFaultWords][B], word-major
+    int B;                                   // the table's row stride (vehicles)
+    unsigned long long seed;                 // the configuration's seed ^ LPVMPC_FAULT_STREAM
+    long long voff;
+};
+// the general forms only: actuated, per-vehicle plant, tyre (the _tyres starts); gains as the forms they stand in for
+hipError_t launch_cl_command_plant_observe_faulted(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
+                                                   const TyrePlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
+                                                   int sd, const double *gains, double *obs, const ObsParams &op, const ActDev &a,
+                                                   const FaultDev &f, hipStream_t s);
+hipError_t launch_cl_command_plant_observe_faulted_obsveh(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
+                                                          const TyrePlantCfg &pc, double hw, double slack, int q9_swap, double *local_next,
+                                                          double *u_old, int sd, const ObsVehGains &gains, double *obs, const ObsParams &op,
+                                                          const ActDev &a, const FaultDev &f, hipStream_t s);
+hipError_t launch_race_command_plant_observe_faulted(const RaceDev &r, const TyrePlantCfg &pc, const double *gains, double *obs,
+                                                     const ObsParams &op, const ActDev &a, const FaultDev &f, hipStream_t s);
+hipError_t launch_race_command_plant_observe_faulted_obsveh(const RaceDev &r, const TyrePlantCfg &pc, const ObsVehGains &gains, double *obs,
+                                                            const ObsParams &op, const ActDev &a, const FaultDev &f, hipStream_t s);
+// lpvmpc_sensor_step_batch: one sensors + observer sub-step on caller arrays; f.rows null: the healthy stage; v.L null: the
+// configuration's tables and the observer's own constants
+hipError_t launch_sensor_step(const ObsVehGains &v, int B, double *obs, const double *plant, const double *servo, const double *motor,
+                              const ObsParams &op, const FaultDev &f, hipStream_t s);
+
 }  // namespace lpvmpc

@@ -62,6 +62,15 @@ struct DistBinding {
     std::vector<double> rows, base_p, base_t;
 };
 
+// sensor faults of a fleet or race (lpvmpc_set_sensor_faults, sensor_faults_api.hip; d.rows null: none attached): the faulted kernels'
+// argument with its device memory, and on the host the configuration and the rows as they were set, for the read-back
+struct FaultBinding {
+    lpvmpc::FaultDev d{};
+    DevArena mem;
+    lpvmpc_sensor_fault_config cfg{};
+    std::vector<double> rows;
+};
+
 struct EventRing {                      // ring of event pairs around launches (lpvmpc_set_timing)
     std::vector<hipEvent_t> e0, e1;
     int count = 0;                      // pairs recorded since timing was (re)enabled
@@ -94,6 +103,7 @@ struct Fleet {                          // closed-loop fleet (lpvmpc_cl_*): plan
     PlantTable cl_veh;                  // the fleet was started by lpvmpc_cl_init_vehicles: its plant table
     TyreTable cl_tyre;                  // the fleet was started by lpvmpc_cl_init_tyres: its tyre table as well
     DistBinding cl_dist;                // lpvmpc_set_disturbances on that fleet (freed with it)
+    FaultBinding cl_fault;              // lpvmpc_set_sensor_faults on that fleet (freed with it)
 };
 struct ObsState {                       // the fleet's / cascade's / race's estimator state [obs_B][kObsStride] (null: it runs on ground truth;
     DevArena obs_mem;                   // a race's is set by lpvmpc_race_init_observed without obs_cfg and freed with the race)
@@ -281,6 +291,9 @@ LPVMPC_HIDDEN int lpvmpc_dist_step(lpvmpc_handle *h, int B, const DistStep &ds, 
                                    const std::vector<double> &tyre_tab, double *d_plant, const int32_t *d_k, int n_sub, double dt_sim,
                                    double *live_p, double *live_t, DistBinding &tmp, hipStream_t st);
 LPVMPC_HIDDEN int lpvmpc_dist_step_read(lpvmpc_handle *h, int B, const DistStep &ds, const DistBinding &tmp, hipStream_t st);
+// sensor_faults_api.hip: sensor faults.  lpvmpc_race_fault (race_api.hip): the race's binding, *B its fleet size, *served whether the race
+// has an estimator in the loop and plant and tyre tables (null: the handle owns no race)
+LPVMPC_HIDDEN FaultBinding *lpvmpc_race_fault(lpvmpc_handle *h, int *B, bool *served);
 // model_params_api.hip: lpvmpc_model_check refuses a batch size other than that of the handle's bound model rows (unbound: any);
 // called by every entry point that linearises, before anything is launched
 LPVMPC_HIDDEN int lpvmpc_model_check(lpvmpc_handle *h, int B, const char *who);

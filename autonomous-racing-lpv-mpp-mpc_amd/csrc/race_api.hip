@@ -34,6 +34,7 @@ struct lpvmpc_race {
     std::unique_ptr<lpvmpc_race_recorder> rec;   // lpvmpc_race_record (null: not recording)
     std::unique_ptr<HeatsBinding> heats;         // lpvmpc_race_heats (heats_api.hip; null: none attached)
     DistBinding dist;             // lpvmpc_set_disturbances (dist.d.rows null: none attached), freed with the race
+    FaultBinding fault;           // lpvmpc_set_sensor_faults (fault.d.rows null: none attached), freed with the race
 };
 
 void lpvmpc_race_free(lpvmpc_handle *h) {
@@ -235,6 +236,15 @@ DistBinding *lpvmpc_race_dist(lpvmpc_handle *h, lpvmpc::DistDev *t) {
     return &r->dist;
 }
 
+// the race's sensor-fault binding (a binding, not state: the inventory below does not list it)
+FaultBinding *lpvmpc_race_fault(lpvmpc_handle *h, int *B, bool *served) {
+    lpvmpc_race *r = h->race;
+    if (!r) return nullptr;
+    *B = r->d.B;
+    *served = r->d.estv && r->veh.d.p && r->tyre.t;
+    return &r->fault;
+}
+
 // The inventory of the race's per-vehicle state (lpvmpc_handle.hpp: RaceState; include/lpvmpc.h, "Race snapshot, restore and clone").
 // Worked out from the kernels of a tick (race.hip, fleet_kernels.hpp, track_race.hip, handoff.hip, disturbance.hip and the masked LPV /
 // solve launches): an array is listed if a tick can read a word of it that an earlier tick, or the init, wrote.  A masked launch
@@ -379,7 +389,11 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
         ta.active = d.m_tt;
         rc = lpvmpc_launch_solve_timed(tt, ta, st); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
         if (r->dist.d.rows) HIP_TRY(h, lpvmpc::launch_disturbance(h->d_cfg, trk, r->dist.d, st));   // lpvmpc_set_disturbances
-        if (r->tyre.t && d.estv && h->ov.L)
+        if (r->fault.d.rows && h->ov.L)                                      // lpvmpc_set_sensor_faults: in place of the tyre forms' kernel
+            HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_faulted_obsveh(d, tyre_plant(r->veh, r->tyre), lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, r->act.d, r->fault.d, st));
+        else if (r->fault.d.rows)
+            HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_faulted(d, tyre_plant(r->veh, r->tyre), h->obs_gains, h->obs_state, h->obs_p, r->act.d, r->fault.d, st));
+        else if (r->tyre.t && d.estv && h->ov.L)
             HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_tyre_obsveh(d, tyre_plant(r->veh, r->tyre), lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, r->act.d, st));
         else if (r->veh.d.p && d.estv && h->ov.L)
             HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_veh_obsveh(d, r->veh.d, lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, r->act.d, st));

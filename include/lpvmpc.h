@@ -1229,6 +1229,65 @@ int  lpvmpc_heat_step_batch(lpvmpc_handle *h, int32_t B, int32_t n_heats, const 
                             const lpvmpc_heats_config *cfg, int32_t t, const double *pose, const double *s, const int32_t *inside,
                             const int32_t *phase, double *carry_f64, int32_t *carry_i32, double *f64, int32_t *i32);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Sensor faults: GPS loss and jumps, IMU bias and drift, a slipping or stuck encoder for the vehicles of a lap-0 fleet or a race with
+ * the estimator in the loop.  The simulated sensors above are healthy: white noise, a GPS that publishes on its cadence, an encoder
+ * that always delivers.  The model here is stateless and keyed on the vehicle's own observer step k (the step counter after its
+ * increment: the first step is k = 1) and its global index vid = vehicle_offset + b.  One row per vehicle:
+ *   rows [B][LPVMPC_FAULT_WORDS] = {gps_out_k0, gps_out_len, gps_loss_z, gps_jump_k0, gps_jump_len, gps_jump_dx, gps_jump_dy,
+ *                                   imu_w_bias, imu_yaw_drift, enc_scale, enc_out_k0, enc_out_len}
+ * A window (k0, len) contains k when k0 <= k < k0 + len; len = 0: never.  With noise_c the sensors' draw of channel c on step k
+ * (channel = std order: psi, psiDot, x, y, v), st the plant state just advanced and dt = 1 / loop_rate, the sensor stage of one
+ * observer sub-step becomes, in this order (everything not named is the healthy stage, word for word):
+ *   1. IMU:      imu_yaw = st[6] + noise_0 + imu_yaw_drift * (k * dt);  imu_w = st[7] + noise_1 + imu_w_bias.
+ *   2. GPS:      gx = st[0] + noise_2, inside the jump window gx = (st[0] + noise_2) + gps_jump_dx; gy likewise with noise_3 and
+ *                gps_jump_dy.  pub and the publish counter follow the healthy cadence rule unchanged (the beacon keeps its rhythm).  A
+ *                publication is LOST when k is inside the outage window, or when gps_loss_z < 9 and
+ *                gauss(seed ^ LPVMPC_FAULT_STREAM, vid, k, 5) > gps_loss_z on the estimator's counter-based generator (channel 5;
+ *                drawn only on steps with pub).  The held reading is updated only when pub && !lost.  z >= 9 draws nothing: the
+ *                generator cannot exceed sqrt(-2 ln 2^-53) = 8.57.  (A loss probability p is z = the standard normal's inverse CDF
+ *                at 1 - p; the Python helper converts.)
+ *   3. Encoder:  v = enc_scale * (|v_xy| + noise_4); inside the encoder window the delivered value is the previous one (the
+ *                stored previous reading), a stuck reading: it counts as unchanged, so the healthy rule "more than 40 unchanged readings
+ *                in a row read 0" fires by itself on the 41st stuck step, and the first step after the window reads v again.
+ *   4. The start-up branch (k dt <= 0.02) and the observer step are untouched.
+ * An all-off row (every len = 0, gps_loss_z >= 9, dx = dy = 0, bias = drift = 0, enc_scale = 1) changes no word of any output.
+ *
+ * lpvmpc_set_sensor_faults attaches rows to the lap-0 fleet or race that h runs (the path handle, for a race), from the next tick
+ * on; cfg NULL: the defaults.  Attaching again replaces the binding; rows == NULL detaches; lpvmpc_cl_release (and the end of the
+ * race) frees it.  With nothing attached a tick issues exactly the launches it always did; with a binding attached the tick launches
+ * the faulted kernel IN PLACE of its fused command / plant / observe kernel: no extra launch.  Refused with LPVMPC_E_ARG, the running
+ * fleet left exactly as it was: a non-finite word; k0 or len not integer-valued, negative or >= 2^31; enc_scale <= 0; another B than
+ * the fleet's; no fleet or race on the handle; one without an estimator; one without plant and tyre tables (only the
+ * lpvmpc_cl_init_tyres / lpvmpc_race_init_tyres starts are served: one general kernel form); a lap-0 fleet with a track binding (a
+ * race with tracks is served: its fused kernel reads no track).  lpvmpc_cascade_init is not extended.
+ * The rows are a binding, not state: the race's snapshot blob and its version do not change, and snapshot, restore and clone work
+ * while faults are attached.  A clone keeps its slot's own row and, keyed on vid, draws its own losses.
+ * lpvmpc_sensor_faults_read: the rows as they were set ([B][LPVMPC_FAULT_WORDS]); *B returns the binding's size, 0 with none
+ * attached (rows is then untouched); either pointer may be NULL.
+ *
+ * lpvmpc_sensor_step_batch: ONE sensors + observer sub-step for B vehicles on caller arrays, as the fused kernels run it once per
+ * plant step: obs_state [B][LPVMPC_OBS_STATE_WORDS] is read and written -- the estimator's whole per-vehicle state {estimate [6],
+ * last measurement y [5], held GPS x, y, previous encoder reading, encoder measurement, GPS publish counter, unchanged-encoder
+ * counter, step counter k} -- plant [B][8] is the plant state just advanced, servo [B] / motor [B] the commanded input.  rows ==
+ * NULL: the healthy stage.  obs is the estimator configuration (gains, limits, noise, seed, vehicle_offset), dt_sim the simulator
+ * step that sets the GPS cadence (thUpdate = (1 / gps_freq) / dt_sim).  A handle with per-vehicle estimator rows bound
+ * (lpvmpc_set_observer_vehicles) runs the bound form (B must be the binding's).  Refused: the row rules above, a counter word that is
+ * not an integer >= 0, and a handle that runs a fleet, cascade or race. */
+#define LPVMPC_FAULT_WORDS 12
+#define LPVMPC_OBS_STATE_WORDS 18
+#define LPVMPC_FAULT_STREAM 0x5E4507FA17C0FFEEull   /* keeps the loss draws apart from the sensors' and the gusts' under one seed */
+typedef struct lpvmpc_sensor_fault_config {
+    uint64_t seed;             /* 0 */
+    int64_t  vehicle_offset;   /* 0: global index of vehicle 0 of this fleet (shards of one fleet draw the same losses) */
+} lpvmpc_sensor_fault_config;
+void lpvmpc_sensor_fault_default_config(lpvmpc_sensor_fault_config *cfg);
+int  lpvmpc_set_sensor_faults(lpvmpc_handle *h, int32_t B, const lpvmpc_sensor_fault_config *cfg, const double *rows);
+int  lpvmpc_sensor_faults_read(lpvmpc_handle *h, int32_t *B, double *rows);
+int  lpvmpc_sensor_step_batch(lpvmpc_handle *h, int32_t B, const lpvmpc_observer_config *obs, double dt_sim,
+                              const lpvmpc_sensor_fault_config *cfg, const double *rows, double *obs_state, const double *plant,
+                              const double *servo, const double *motor);
+
 #ifdef __cplusplus
 }
 #endif

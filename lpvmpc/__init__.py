@@ -15,6 +15,7 @@ from .plant import plant_params, sample_plant_params, sample_tyre_params, tyre_p
 from .model import model_params, sample_model_params  # noqa: E402,F401
 from .tuning import check_tuning_rows, sample_tunings, tuning_rows  # noqa: E402,F401
 from .disturbance import check_disturbance_rows, disturbance_rows, rho_from_tau, sample_disturbances  # noqa: E402,F401
+from .sensor_faults import check_fault_rows, fault_rows, sample_faults  # noqa: E402,F401
 from .snapshot import RaceSnapshot, respawn_sources  # noqa: E402,F401
 
 __all__ = ["BatchedSolver", "PathFollowingLPV_MPC", "LPV_MPC_Planner", "PlannerHandoff", "body_frame_errors", "handoff_operators",
@@ -22,4 +23,5 @@ __all__ = ["BatchedSolver", "PathFollowingLPV_MPC", "LPV_MPC_Planner", "PlannerH
            "actuator_config", "controller_delay", "delay_steps", "plant_params", "sample_plant_params", "tyre_params", "sample_tyre_params",
            "model_params", "sample_model_params", "tuning_rows", "sample_tunings", "check_tuning_rows",
            "disturbance_rows", "sample_disturbances", "check_disturbance_rows", "rho_from_tau",
+           "fault_rows", "sample_faults", "check_fault_rows",
            "RaceSnapshot", "respawn_sources"]

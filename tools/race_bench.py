@@ -56,7 +56,14 @@ the GB/s over the bytes its two kernels read plus write (the state goes through 
 configuration's spread over the alternations and the added ms per controller tick; and, with --parent-lib FILE, the detached race on that
 build, one child process per run: the launches are identical, so it must lie within the alternation's spread.
 Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator | --actuator | --record | --heats SIZE | --plant-params | --models |
-       --tunings | --tyres | --observer-vehicles | --tracks | --disturbance | --fork [--parent-lib FILE] [--reps R]] [--out FILE]"""
+       --tunings | --tyres | --observer-vehicles | --tracks | --disturbance | --sensor-faults | --fork [--parent-lib FILE] [--reps R]]
+       [--out FILE]
+--sensor-faults: the same protocol for the sensor faults (lpvmpc_set_sensor_faults): the lpvmpc_race_init_tyres race with kind 0 rows and the
+estimator in the loop with nothing attached (the baseline: the launches of the parent's tick), with all-off rows attached (the faulted
+kernel in place of the fused observe kernel on the same trajectories: the kernel's own cost), the same race with every fault attached to
+every vehicle (a GPS outage, a random loss, a jump, a gyro bias, a yaw drift, a slipping and a stuck encoder: the faulted kernel in place
+of the fused observe kernel, no extra launch; other trajectories, so the lines also carry the solvers' changed iteration counts), and,
+with --parent-lib FILE, the race with nothing attached on that build."""
 import argparse
 import os
 import sys
@@ -88,7 +95,7 @@ def timed(tick, read, K):
 
 
 def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, record=False, plant_params=None, model_params=None, tunings=None,
-             tyre_params=None, observer_vehicles=False, tracks=None, disturbance=None, heats=0):
+             tyre_params=None, observer_vehicles=False, tracks=None, disturbance=None, heats=0, sensor_faults=None):
     path, tt, plan = engines(mp, sd)
     if tracks is not None:                                            # (maps, track_of) bound to the three engines
         for e in (path, tt, plan):
@@ -110,6 +117,8 @@ def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, rec
                    actuator=actuator, plant_params=plant_params, **({} if tyre_params is None else {"tyre_params": tyre_params}))
     if disturbance is not None:                                       # rows attached before the first tick
         path.set_disturbances(disturbance, seed=1)
+    if sensor_faults is not None:                                     # rows attached before the first tick
+        path.set_sensor_faults(sensor_faults, seed=1)
     path.race_tick(warm)
     if record:
         path.race_record(K, 1)
@@ -141,6 +150,7 @@ def main():
     ap.add_argument("--observer-vehicles", action="store_true")
     ap.add_argument("--tracks", action="store_true")
     ap.add_argument("--disturbance", action="store_true")
+    ap.add_argument("--sensor-faults", action="store_true")
     ap.add_argument("--fork", action="store_true")
     ap.add_argument("--fork-child", default=None, help=argparse.SUPPRESS)                  # B: the fork measurements of one fleet size
     ap.add_argument("--parent-lib", default=None)
@@ -168,6 +178,10 @@ def main():
     if a.disturbance:
         return models_main(a, [("tyres, nothing attached", "liblpvmpc.so", 9), ("disturbances attached", "liblpvmpc.so", 13)],
                            parent=("parent, tyres", 9))
+    if a.sensor_faults:
+        return models_main(a, [("estimator, nothing attached", "liblpvmpc.so", 14), ("off rows attached", "liblpvmpc.so", 16),
+                               ("sensor faults attached", "liblpvmpc.so", 15)],
+                           parent=("parent, estimator", 14))
     if a.plant_params:
         return plant_params_main(a)
     if a.record:
@@ -404,20 +418,29 @@ def models_child(a):
     plant0, half, warm = _models_starts(int(B))[regime]
     rows = lpvmpc.model_params(int(B)) if int(bind) == 1 else None                # bind: 0 nothing, 1 nominal model rows, 2 / 3 tuning rows,
     tyres = {5: lpvmpc.tyre_params(int(B), kind=0), 6: "pacejka", 9: lpvmpc.tyre_params(int(B), kind=0),
-             13: lpvmpc.tyre_params(int(B), kind=0)}.get(int(bind))               # 4 nominal plant rows (_vehicles), 5 / 6 tyre rows on top
+             13: lpvmpc.tyre_params(int(B), kind=0), 14: lpvmpc.tyre_params(int(B), kind=0),
+             15: lpvmpc.tyre_params(int(B), kind=0), 16: lpvmpc.tyre_params(int(B), kind=0)}.get(int(bind))               # 4 nominal plant rows (_vehicles), 5 / 6 tyre rows on top
     dist = None                                                                    # 13: 9 with gusts, a patch and a kick on every vehicle
     if int(bind) == 13:
         from lpvmpc.disturbance import parse_disturbance
         dist = parse_disturbance("gusts:0.3+patch:0,3,0.7+kick:400,0.1,0.3", int(B), mp_length())
     obs = None                                                                     # 7 / 8: _vehicles with the estimator, unbound / rows bound
-    if int(bind) in (7, 8):
+    faults = None                                                                  # 14 / 16 / 15: _tyres with the estimator; nothing, all-off rows
+    if int(bind) == 16:                                                            # (the faulted kernel on the healthy race's trajectories), every fault
+        from lpvmpc.sensor_faults import fault_rows
+        faults = fault_rows(int(B), 0.005)
+    if int(bind) == 15:
+        from lpvmpc.sensor_faults import fault_rows
+        faults = fault_rows(int(B), 0.005, gps_outage=(1.0, 1.0), gps_loss_p=0.2, gps_jump=(3.0, 0.5, 0.05, -0.05), imu_w_bias=0.02,
+                            imu_yaw_drift=0.001, enc_scale=0.98, enc_outage=(4.0, 0.1))
+    if int(bind) in (7, 8, 14, 15, 16):
         from lpvmpc.observer import observer_config
         f = np.load(os.path.join(ROOT, "tests", "golden", "estimator", "estimator.npz"))
         obs = observer_config(f["L_ls"], f["lim_ls"], f["L_hs"], f["lim_hs"], psi_std=0.01, psiDot_std=0.05, x_std=0.01, y_std=0.01,
                               v_std=0.02, seed=7)
     ms, vps, ph = race_run(mp, plant0, half, warm, a.ticks, model_params=rows, tunings={2: "own", 3: "sampled"}.get(int(bind)),
                             plant_params="nominal" if int(bind) in (4, 5, 6, 7, 8) else None, tyre_params=tyres, estimator=obs,
-                            observer_vehicles=int(bind) == 8, disturbance=dist)
+                            observer_vehicles=int(bind) == 8, disturbance=dist, sensor_faults=faults)
     print("MODELS_RUN %.6f %s %.4g" % (ms, ",".join(str(int(x)) for x in ph), vps), flush=True)
 
 

@@ -31,8 +31,14 @@ its bins then describe the slots' rows, not independent vehicles.  The recorder 
 RMSE_ey is not reported.  The report gains one line: slots respawned, alive vehicle-ticks and alive vehicle-ticks per second of the
 swept race.  --respawn 0 adds the same line to an unchanged run (recorder on, nothing respawned), for the comparison.  The baseline
 race is never refilled.  Without the flag the output is today's.
+--sensor-faults breaks the swept race's sensors (lpvmpc_set_sensor_faults, RaceFleet(sensor_faults=...)), the same rows for every
+vehicle: gps_outage:LEN_S and enc_outage:LEN_S (a GPS without publications / a stuck encoder for LEN_S seconds, from one second
+into the race), gps_loss:P (each publication lost with probability P, seeded with --seed), imu_bias:W (a rate-gyro bias, rad/s),
+imu_drift:W, enc_scale:S; several joined with +.  It needs --estimator (the sensors feed the estimator); the baseline race keeps
+healthy sensors.  The answer it is for: does estimator + controller survive one second without GPS?  Without the flag the output is
+today's.
 Usage: tools/robustness_sweep.py [--B 8192] [--laps 2] [--seed 1] [--max-ticks 3000] [--model nominal|plant|noisy:REL]
-       [--tyre linear|pacejka] [--estimator nominal|plant] [--disturbance SPEC] [--respawn K] [--out FILE]"""
+       [--tyre linear|pacejka] [--estimator nominal|plant] [--disturbance SPEC] [--sensor-faults SPEC] [--respawn K] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -54,11 +60,14 @@ def main():
     ap.add_argument("--estimator", default=None, choices=("nominal", "plant"))
     ap.add_argument("--tracks", default=None, help="comma-separated track shapes (oval, L_shape, 3110, Euge_Track): vehicle b races on track b mod their number")
     ap.add_argument("--disturbance", default=None, help="gusts:SIGMA | patch:S0,LEN,GAMMA | kick:STEP,VY,W (joined with +)")
+    ap.add_argument("--sensor-faults", default=None, help="gps_outage:LEN_S | enc_outage:LEN_S | gps_loss:P | imu_bias:W | imu_drift:W | enc_scale:S (joined with +)")
     ap.add_argument("--respawn", type=int, default=None, help="refill the lost slots every K ticks (0: never, but report the alive vehicle-ticks)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.respawn is not None and a.respawn < 0:
         ap.error("--respawn must be >= 0")
+    if a.sensor_faults and not a.estimator:
+        ap.error("--sensor-faults needs --estimator: the sensors feed the estimator")
     if a.model not in ("nominal", "plant") and not a.model.startswith("noisy:"):
         ap.error("--model must be nominal, plant or noisy:REL")
     import lpvmpc
@@ -98,12 +107,17 @@ def main():
         lap = [float(m.PointAndTangent[-1, 3] + m.PointAndTangent[-1, 4]) for m in (maps or [mp])]
         dist = dict(rows=parse_disturbance(a.disturbance, B, np.array(lap)[track_of] if maps else lap[0]), seed=a.seed)
 
+    faults = None
+    if a.sensor_faults:
+        from lpvmpc.sensor_faults import parse_sensor_faults
+        faults = dict(rows=parse_sensor_faults(a.sensor_faults, B), seed=a.seed)
+
     fork = dict(slots=0, alive=0)                                     # of the swept race, with --respawn
 
-    def race(r, m=None, est_rows=None, disturbance=None, respawn=None):
+    def race(r, m=None, est_rows=None, disturbance=None, respawn=None, sensor_faults=None):
         f = lpvmpc.RaceFleet(mp if maps is None else maps, plant0, laps=a.laps, half_track0=1, plant_params=r, model_params=m, track_of=track_of,
                              tyre_params="pacejka" if a.tyre == "pacejka" else None, estimator=obs, estimator_params=est_rows,
-                             disturbance=disturbance)
+                             disturbance=disturbance, sensor_faults=sensor_faults)
         assert np.array_equal(f.plant_params(), r)
         assert a.tyre == "linear" or np.array_equal(f.tyre_params(), lpvmpc.tyre_params(B))
         assert m is None or np.array_equal(f.model_params(), m)
@@ -126,7 +140,7 @@ def main():
     base, _n, _w = race(nom)                                          # the same starts with the nominal car: the baseline
     ph_nom = base.state()["phase"]
     base.close()
-    fleet, ticks, wall = race(rows, model_rows, "plant" if a.estimator == "plant" else None, dist, a.respawn)
+    fleet, ticks, wall = race(rows, model_rows, "plant" if a.estimator == "plant" else None, dist, a.respawn, faults)
     ph = fleet.state()["phase"]
     lt = fleet.lap_times()[:, 1:a.laps + 1]                          # racing laps, seconds (NaN: not completed)
     rmse = fleet.lap_stats()["rmse_ey"][:, 1:a.laps + 1] if not a.respawn else np.full(lt.shape, np.nan)
@@ -139,7 +153,9 @@ def main():
              "# the state estimator is in the loop (--estimator %s): %s." % (a.estimator, "each vehicle's estimator takes its plant row and gain tables "
               "designed for it" if a.estimator == "plant" else "it keeps its own constants and the nominal gain tables")]) + ([] if not dist else [
              "# the swept race is disturbed (--disturbance %s): the same rows for every vehicle, gusts seeded with --seed; the baseline race is not."
-             % a.disturbance]) + [
+             % a.disturbance]) + ([] if not faults else [
+             "# the swept race's sensors are faulted (--sensor-faults %s): the same rows for every vehicle, losses seeded with --seed; the "
+             "baseline race's are healthy." % a.sensor_faults]) + [
              "# %d ticks (%.1f s wall); all vehicles: %.1f %% finished, %.1f %% lost, %.1f %% still running; racing lap time median %.3f s, "
              "p90 %.3f s; RMSE_ey median %.4f m" % (ticks, wall, 100 * fin.mean(), 100 * lost.mean(), 100 * (ph < 2).mean(),
                                                      np.nanmedian(lt), np.nanpercentile(lt, 90), np.nanmedian(rmse)),
