@@ -6,50 +6,42 @@
 
 namespace lpvmpc {
 
-#define LPVMPC_GRID(n) dim3(((n) + 63) / 64), dim3(64)
-hipError_t launch_plant_actuated(int B, double *plant, const double *u, PlantCfg pc, const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL(plant_kernel<true>, LPVMPC_GRID(B), 0, s, B, plant, u, pc, a);
+hipError_t launch_plant_actuated(const PlantStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(plant_kernel<true>, LPVMPC_GRID(a.B), 0, s, a.B, a.plant, a.u, a.pc, a.act);
     return hipGetLastError();
 }
-hipError_t launch_cl_measure_act(const DevCfg *dcfg, int B, const double *plant, const double *cmd, double hw, double slack, int q9_swap,
-                                 double *local_state, double *u_old, int sd, hipStream_t s) {
-    hipLaunchKernelGGL(cl_measure_kernel<true>, LPVMPC_GRID(B), 0, s, dcfg, B, plant, cmd, hw, slack, q9_swap, local_state, u_old, sd);
+hipError_t launch_cl_measure_act(const FleetMeasureArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(cl_measure_kernel<true>, LPVMPC_GRID(a.B), 0, s, a.dcfg, a.B, a.plant, a.cmd, a.hw, a.slack, a.q9, a.local_state, a.u_old, a.sd);
     return hipGetLastError();
 }
-hipError_t launch_cl_command_plant_measure_act(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant, PlantCfg pc,
-                                               double hw, double slack, int q9_swap, double *local_next, double *u_old, int sd,
-                                               const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL(cl_command_plant_measure_kernel<true>, LPVMPC_GRID(B), 0, s, dcfg, B, N, uPred, cmd, plant, pc, hw, slack, q9_swap,
-                       local_next, u_old, sd, a);
+hipError_t launch_cl_command_plant_measure_act(const FleetStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(cl_command_plant_measure_kernel<true>, LPVMPC_GRID(a.B), 0, s, a.dcfg, a.B, a.N, a.uPred, a.cmd, a.plant, a.pc, a.hw, a.slack, a.q9,
+                       a.local_next, a.u_old, a.sd, a.act);
     return hipGetLastError();
 }
 
-hipError_t launch_cl_observe_measure_act(const DevCfg *dcfg, int B, const double *obs, const double *cmd, double hw, double slack, int q9_swap,
-                                         double *local_state, double *u_old, int sd, hipStream_t s) {
-    hipLaunchKernelGGL(cl_command_plant_observe_kernel<true>, LPVMPC_GRID(B), 0, s, dcfg, B, 1, (const double *)nullptr, const_cast<double *>(cmd),
-                       (double *)nullptr, PlantCfg{}, hw, slack, q9_swap, local_state, u_old, (const double *)nullptr, const_cast<double *>(obs),
-                       ObsParams{}, 0, sd, ActDev{});
+hipError_t launch_cl_observe_measure_act(const FleetMeasureArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(cl_command_plant_observe_kernel<true>, LPVMPC_GRID(a.B), 0, s, a.dcfg, a.B, 1, (const double *)nullptr, const_cast<double *>(a.cmd),
+                       (double *)nullptr, PlantCfg{}, a.hw, a.slack, a.q9, a.local_state, a.u_old, (const double *)nullptr, const_cast<double *>(a.obs),
+                       ObsParams{}, 0, a.sd, ActDev{});
     return hipGetLastError();
 }
-hipError_t launch_cl_command_plant_observe_act(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant, PlantCfg pc,
-                                              double hw, double slack, int q9_swap, double *local_next, double *u_old, int sd,
-                                              const double *gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL(cl_command_plant_observe_kernel<true>, LPVMPC_GRID(B), 0, s, dcfg, B, N, uPred, cmd, plant, pc, hw, slack, q9_swap,
-                       local_next, u_old, gains, obs, op, 1, sd, a);
+hipError_t launch_cl_command_plant_observe_act(const FleetStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(cl_command_plant_observe_kernel<true>, LPVMPC_GRID(a.B), 0, s, a.dcfg, a.B, a.N, a.uPred, a.cmd, a.plant, a.pc, a.hw, a.slack, a.q9,
+                       a.local_next, a.u_old, a.gains.g, a.obs, a.op, 1, a.sd, a.act);
     return hipGetLastError();
 }
 
-hipError_t launch_race_measure_act(const DevCfg *ccfg, const RaceDev &r, int seed_tick, int sd, hipStream_t s) {
-    hipLaunchKernelGGL(race_measure_kernel<true>, LPVMPC_GRID(r.B), 0, s, ccfg, r, seed_tick, sd);
+hipError_t launch_race_measure_act(const RaceMeasureArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(race_measure_kernel<true>, LPVMPC_GRID(a.r.B), 0, s, a.ccfg, a.r, a.seed_tick, a.sd);
     return hipGetLastError();
 }
-hipError_t launch_race_command_plant_act(const RaceDev &r, PlantCfg pc, const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL(race_command_plant_kernel<true>, LPVMPC_GRID(r.B), 0, s, r, pc, a);
+hipError_t launch_race_command_plant_act(const RaceStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(race_command_plant_kernel<true>, LPVMPC_GRID(a.r.B), 0, s, a.r, a.pc, a.act);
     return hipGetLastError();
 }
-hipError_t launch_race_command_plant_observe_act(const RaceDev &r, PlantCfg pc, const double *gains, double *obs, const ObsParams &op,
-                                                const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL(race_command_plant_observe_kernel<true>, LPVMPC_GRID(r.B), 0, s, r, pc, gains, obs, op, a);
+hipError_t launch_race_command_plant_observe_act(const RaceStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(race_command_plant_observe_kernel<true>, LPVMPC_GRID(a.r.B), 0, s, a.r, a.pc, a.gains.g, a.obs, a.op, a.act);
     return hipGetLastError();
 }
 

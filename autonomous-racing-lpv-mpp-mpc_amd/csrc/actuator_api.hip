@@ -91,20 +91,26 @@ extern "C" int lpvmpc_plant_step_actuated_batch(lpvmpc_handle *h, int32_t B, dou
     hipStream_t st = h->stream;
     H2D(a.ring, ring.data(), ring.size() * 8); H2D(a.servo, sv.data(), b * 8); H2D(a.k, k.data(), b * 4);
     H2D(h->d_xlast, state, b * 8 * 8); H2D(h->d_states, u, b * 2 * 8);
-    HIP_TRY(h, lpvmpc::launch_plant_actuated(B, h->d_xlast, h->d_states, lpvmpc_plant_cfg(h, n_sub, dt_sim, mu_sim), a, st));
+    lpvmpc::PlantStepArgs pa{};
+    pa.B = B; pa.plant = h->d_xlast; pa.u = h->d_states; pa.pc = lpvmpc_plant_cfg(h, n_sub, dt_sim, mu_sim); pa.act = a;
+    HIP_TRY(h, lpvmpc::plant_step_launcher(lpvmpc::SF_ACT)(pa, st));
     D2H(state, h->d_xlast, b * 8 * 8);
     return lpvmpc_act_download(h, a, act_state, st);                // (synchronises)
 }
 
 extern "C" int lpvmpc_actuator_read(lpvmpc_handle *h, double *act_state, double *path_hist, double *tt_hist) {
-    if (h && h->race) return lpvmpc_race_act_read(h, act_state, path_hist, tt_hist);
-    if (!h || !h->cl_plant || !h->cl_actuated)
+    const lpvmpc::RaceDev *race = nullptr;
+    const PlantSide *p = lpvmpc_plant_side(h, &race);
+    if (race && !p->actuated) return fail(h, LPVMPC_E_ARG, "lpvmpc_actuator_read: the race was not started by lpvmpc_race_init_actuated");
+    if (!p || !p->actuated)
         return fail(h, LPVMPC_E_ARG, "lpvmpc_actuator_read: no fleet or race started by lpvmpc_cl_init_actuated / lpvmpc_race_init_actuated");
-    if (tt_hist) return fail(h, LPVMPC_E_ARG, "lpvmpc_actuator_read: a lap-0 fleet has one controller (tt_hist must be NULL)");
+    if (tt_hist && !race) return fail(h, LPVMPC_E_ARG, "lpvmpc_actuator_read: a lap-0 fleet has one controller (tt_hist must be NULL)");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t st = h->stream;
-    if (path_hist) D2H(path_hist, h->d_uold, (size_t)h->cl_B * (2 + h->cfg.steering_delay) * 8);
-    if (act_state) { int rc = lpvmpc_act_download(h, h->cl_act.d, act_state, st); if (rc) return rc; }
+    const size_t n = (size_t)p->B * (2 + h->cfg.steering_delay) * 8;      // (a race's two controllers have one steering delay)
+    if (path_hist) D2H(path_hist, h->d_uold, n);
+    if (tt_hist) D2H(tt_hist, race->t_uold, n);
+    if (act_state) { int rc = lpvmpc_act_download(h, p->act.d, act_state, st); if (rc) return rc; }
     HIP_TRY(h, hipStreamSynchronize(st));
     return LPVMPC_OK;
 }

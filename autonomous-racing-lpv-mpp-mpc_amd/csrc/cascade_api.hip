@@ -249,11 +249,11 @@ extern "C" int lpvmpc_cascade_tick(lpvmpc_handle *h, int32_t n_ticks) {
         SolveArgs a{B, c->local, h->d_AB, h->d_vel, h->d_uold, nullptr, h->d_xPred, h->d_uPred, h->d_status, h->d_iters, h->d_polish, h->d_resid,
                     nullptr, 0, 6};
         int rc = lpvmpc_launch_solve_warm(h, a, st); if (rc) return rc;
-        if (c->estv)
-            HIP_TRY(h, lpvmpc::launch_cascade_plant_observe(B, N, h->d_uPred, c->cmd, c->plant, lpvmpc_plant_cfg(h, c->n_sub[k % 3], c->dt_sim, c->mu_sim),
-                                                             c->estv, h->obs_gains, h->obs_state, h->obs_p, st));
-        else
-            HIP_TRY(h, lpvmpc::launch_cl_command_plant(B, N, h->d_uPred, c->cmd, c->plant, lpvmpc_plant_cfg(h, c->n_sub[k % 3], c->dt_sim, c->mu_sim), st));
+        // command and plant; with the estimator the estimate's view as well (the cascade has the plain forms only: no table)
+        lpvmpc::FleetStepArgs sa{};
+        sa.B = B; sa.N = N; sa.uPred = h->d_uPred; sa.cmd = c->cmd; sa.plant = c->plant; sa.pc = lpvmpc_plant_cfg(h, c->n_sub[k % 3], c->dt_sim, c->mu_sim);
+        sa.local_next = c->estv; sa.gains.g = h->obs_gains; sa.obs = h->obs_state; sa.op = h->obs_p;
+        HIP_TRY(h, (c->estv ? lpvmpc::launch_cascade_plant_observe : lpvmpc::launch_cl_command_plant)(sa, st));
         c->ctrl_ticks++;
     }
     return LPVMPC_OK;

@@ -63,7 +63,6 @@ __global__ void __launch_bounds__(64) cl_command_plant_kernel(int B, int N, cons
     for (int i = 0; i < 8; ++i) plant[(size_t)b * 8 + i] = st[i];
 }
 
-#define LPVMPC_GRID(n) dim3(((n) + 63) / 64), dim3(64)
 hipError_t launch_local_position(const DevCfg *dcfg, int B, const double *xypsi, double hw, double slack, double *out, hipStream_t s) {
     hipLaunchKernelGGL(local_position_kernel, LPVMPC_GRID(B), 0, s, dcfg, B, xypsi, hw, slack, out);
     return hipGetLastError();
@@ -72,28 +71,26 @@ hipError_t launch_global_position(const DevCfg *dcfg, int B, const double *sey, 
     hipLaunchKernelGGL(global_position_kernel, LPVMPC_GRID(B), 0, s, dcfg, B, sey, out);
     return hipGetLastError();
 }
-hipError_t launch_plant(int B, double *plant, const double *u, PlantCfg pc, hipStream_t s) {
-    hipLaunchKernelGGL(plant_kernel<false>, LPVMPC_GRID(B), 0, s, B, plant, u, pc, ActDev{});
+hipError_t launch_plant(const PlantStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(plant_kernel<false>, LPVMPC_GRID(a.B), 0, s, a.B, a.plant, a.u, a.pc, ActDev{});
     return hipGetLastError();
 }
-hipError_t launch_cl_measure(const DevCfg *dcfg, int B, const double *plant, const double *cmd, double hw, double slack, int q9_swap,
-                             double *local_state, double *u_old, hipStream_t s) {
-    hipLaunchKernelGGL(cl_measure_kernel<false>, LPVMPC_GRID(B), 0, s, dcfg, B, plant, cmd, hw, slack, q9_swap, local_state, u_old, 0);
+hipError_t launch_cl_measure(const FleetMeasureArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(cl_measure_kernel<false>, LPVMPC_GRID(a.B), 0, s, a.dcfg, a.B, a.plant, a.cmd, a.hw, a.slack, a.q9, a.local_state, a.u_old, 0);
     return hipGetLastError();
 }
 hipError_t launch_cl_seed(int B, int N, const double *local_state, double *xlast, double *delta, hipStream_t s) {
     hipLaunchKernelGGL(cl_seed_kernel, LPVMPC_GRID(B * N), 0, s, B, N, local_state, xlast, delta);
     return hipGetLastError();
 }
-hipError_t launch_cl_command_plant(int B, int N, const double *uPred, double *cmd, double *plant, PlantCfg pc, hipStream_t s) {
-    hipLaunchKernelGGL(cl_command_plant_kernel, LPVMPC_GRID(B), 0, s, B, N, uPred, cmd, plant, pc);
+hipError_t launch_cl_command_plant(const FleetStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(cl_command_plant_kernel, LPVMPC_GRID(a.B), 0, s, a.B, a.N, a.uPred, a.cmd, a.plant, a.pc);
     return hipGetLastError();
 }
 
-hipError_t launch_cl_command_plant_measure(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant, PlantCfg pc,
-                                           double hw, double slack, int q9_swap, double *local_next, double *u_old, hipStream_t s) {
-    hipLaunchKernelGGL(cl_command_plant_measure_kernel<false>, LPVMPC_GRID(B), 0, s, dcfg, B, N, uPred, cmd, plant, pc, hw, slack, q9_swap, local_next,
-                       u_old, 0, ActDev{});
+hipError_t launch_cl_command_plant_measure(const FleetStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(cl_command_plant_measure_kernel<false>, LPVMPC_GRID(a.B), 0, s, a.dcfg, a.B, a.N, a.uPred, a.cmd, a.plant, a.pc, a.hw, a.slack, a.q9,
+                       a.local_next, a.u_old, 0, ActDev{});
     return hipGetLastError();
 }
 

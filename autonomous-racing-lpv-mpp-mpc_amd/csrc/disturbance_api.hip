@@ -1,5 +1,5 @@
 // disturbance_api.hip -- C ABI of the plant disturbances (include/lpvmpc.h, "Plant disturbances"): the checks, the binding of a lap-0
-// fleet (Fleet::cl_dist) or a race (lpvmpc_race_dist, race_api.hip), the read-back and the stand-alone step's launch.  Kernel:
+// fleet or a race (PlantSide::dist of the running engine, lpvmpc_plant_side), the read-back and the stand-alone step's launch.  Kernel:
 // disturbance.hip, launched in front of the command / plant launch of lpvmpc_cl_tick, lpvmpc_race_tick and lpvmpc_plant_step_rows.
 #include <cmath>
 #include <vector>
@@ -77,13 +77,15 @@ static void dist_cfg(const lpvmpc_disturbance_config &c, lpvmpc::DistDev &d) {
 
 // the binding of the fleet or race that h runs and, in t, what it acts on (null: none with plant and tyre tables)
 static DistBinding *dist_target(lpvmpc_handle *h, lpvmpc::DistDev &t) {
-    if (h->race) return lpvmpc_race_dist(h, &t);
-    if (!h->cl_plant || !h->cl_veh.d.p || !h->cl_tyre.t) return nullptr;
+    const lpvmpc::RaceDev *race = nullptr;
+    PlantSide *p = lpvmpc_plant_side(h, &race);
+    if (!p || !p->veh.d.p || !p->tyre.t) return nullptr;
+    if (race) { t = lpvmpc_race_dist(*p, *race); return &p->dist; }
     t = lpvmpc::DistDev{};
-    t.B = h->cl_B; t.plant = h->cl_plant; t.k = h->cl_act.d.k; t.nstep = nullptr; t.n_fixed = h->cl_pc.n_sub; t.dt = h->cl_pc.dt;
+    t.B = p->B; t.plant = h->cl_plant; t.k = p->act.d.k; t.nstep = nullptr; t.n_fixed = p->pc.n_sub; t.dt = p->pc.dt;
     t.hw = h->cl_hw; t.slack = h->cl_slack;
-    t.live_p = const_cast<double *>(h->cl_veh.d.p); t.live_t = const_cast<double *>(h->cl_tyre.t);
-    return &h->cl_dist;
+    t.live_p = const_cast<double *>(p->veh.d.p); t.live_t = const_cast<double *>(p->tyre.t);
+    return &p->dist;
 }
 
 // the live tables' scaled words back from the base copy (the other words never change)

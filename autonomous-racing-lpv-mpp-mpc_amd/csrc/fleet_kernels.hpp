@@ -20,6 +20,10 @@
 // forms of a kernel in one translation unit LLVM compiles the plain form differently (other registers, other instructions); with
 // one per translation unit each form compiles to the code it has alone (docs/HISTORY.md, "Fleet kernels as templates").
 // tests/test_fleet_kernel_instances.py guards the rule.
+//
+// Each launcher stands next to its instantiation and takes its family's argument struct (lpvmpc_device.hpp: FleetStepArgs ...).
+// Which form serves an engine is decided away from the kernels: step_form.hpp maps the engine's form to a kernel enumerator, and
+// fleet_launch.hip binds the enumerators to the launchers.
 #pragma once
 #include "lpvmpc_device.hpp"
 #include "observer_device.hpp"

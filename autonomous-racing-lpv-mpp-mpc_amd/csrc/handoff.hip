@@ -245,7 +245,6 @@ __global__ void __launch_bounds__(64) tt_measure_kernel(const DevCfg *__restrict
     u_old[b * 2 + 0] = cmd[b * 2 + 0]; u_old[b * 2 + 1] = cmd[b * 2 + 1];
 }
 
-#define LPVMPC_GRID(n) dim3(((n) + 63) / 64), dim3(64)
 hipError_t launch_plan_pose(const DevCfg *dcfg, int B, const double *xPred, double *SS, double *pose, double *sig, hipStream_t s,
                             const int32_t *active) {
     hipLaunchKernelGGL(plan_pose_kernel, LPVMPC_GRID(B), 0, s, dcfg, B, xPred, SS, pose, sig, active);

@@ -698,7 +698,9 @@ extern "C" int lpvmpc_plant_step_batch(lpvmpc_handle *h, int32_t B, double *stat
     if (!state || !u || n_sub < 1 || !(dt_sim > 0)) return fail(h, LPVMPC_E_ARG, "lpvmpc_plant_step_batch: bad argument");
     hipStream_t st = h->stream;
     H2D(h->d_xlast, state, (size_t)B * 8 * 8); H2D(h->d_states, u, (size_t)B * 2 * 8);
-    HIP_TRY(h, lpvmpc::launch_plant(B, h->d_xlast, h->d_states, lpvmpc_plant_cfg(h, n_sub, dt_sim, mu_sim), st));
+    lpvmpc::PlantStepArgs a{};
+    a.B = B; a.plant = h->d_xlast; a.u = h->d_states; a.pc = lpvmpc_plant_cfg(h, n_sub, dt_sim, mu_sim);
+    HIP_TRY(h, lpvmpc::plant_step_launcher(0)(a, st));
     D2H(state, h->d_xlast, (size_t)B * 8 * 8);
     HIP_TRY(h, hipStreamSynchronize(st));
     return LPVMPC_OK;
@@ -740,12 +742,12 @@ static int cl_init(lpvmpc_handle *h, int32_t B, const double *plant0, double hal
     // the new fleet is built in f and installed after the last step that can fail: a failed call leaves no fleet (a refused
     // actuator configuration leaves the old one), never half of one
     Fleet f;
-    if (act) { rc = lpvmpc_act_alloc(h, B, act, delay_a, delay_df, dt_sim, veh ? "lpvmpc_cl_init_vehicles" : "lpvmpc_cl_init_actuated", f.cl_act); if (rc) return rc; }
+    if (act) { rc = lpvmpc_act_alloc(h, B, act, delay_a, delay_df, dt_sim, veh ? "lpvmpc_cl_init_vehicles" : "lpvmpc_cl_init_actuated", f.cl_side.act); if (rc) return rc; }
     release<Fleet>(*h);                                          // the old fleet first: never two at once
     release<ObsState>(*h);
-    if (veh) { rc = lpvmpc_plant_upload(h, B, *veh, dt_sim, n_sub, f.cl_veh); if (rc) return rc; }
-    if (tyre) { rc = lpvmpc_tyre_upload(h, *tyre, f.cl_tyre); if (rc) return rc; }
-    f.cl_actuated = act != nullptr;
+    if (veh) { rc = lpvmpc_plant_upload(h, B, *veh, dt_sim, n_sub, f.cl_side.veh); if (rc) return rc; }
+    if (tyre) { rc = lpvmpc_tyre_upload(h, *tyre, f.cl_side.tyre); if (rc) return rc; }
+    f.cl_side.actuated = act != nullptr;
     HIP_TRY(h, f.cl_mem.alloc(f.cl_local_next, (size_t)B * 6 * 8));
     HIP_TRY(h, f.cl_mem.alloc(f.cl_plant, (size_t)B * 8 * 8));
     HIP_TRY(h, f.cl_mem.alloc(f.cl_local, (size_t)B * 6 * 8));
@@ -758,8 +760,8 @@ static int cl_init(lpvmpc_handle *h, int32_t B, const double *plant0, double hal
     // the controller's OldSteering / OldAccelera start at zero (CTRL:71-73)
     if (act) HIP_TRY(h, hipMemsetAsync(h->d_uold, 0, (size_t)B * (2 + h->cfg.steering_delay) * 8, st));
     HIP_TRY(h, hipStreamSynchronize(st));
-    f.cl_B = B; f.cl_q9 = q9_swap != 0; f.cl_hw = half_width; f.cl_slack = slack;
-    f.cl_pc = lpvmpc_plant_cfg(h, n_sub, dt_sim, mu_sim);
+    f.cl_side.B = B; f.cl_q9 = q9_swap != 0; f.cl_hw = half_width; f.cl_slack = slack;
+    f.cl_side.pc = lpvmpc_plant_cfg(h, n_sub, dt_sim, mu_sim);
     h->state_valid_B = 0;
     if (h->obs_cfg) { rc = lpvmpc_observer_start(h, *h->obs_cfg, B, plant0, dt_sim, 0); if (rc) return rc; }   // the estimator in the loop
     static_cast<Fleet &>(*h) = std::move(f);
@@ -802,22 +804,20 @@ extern "C" int lpvmpc_cl_init_vehicles(lpvmpc_handle *h, int32_t B, const double
 extern "C" int lpvmpc_cl_tick(lpvmpc_handle *h, int32_t n_ticks) {
     if (!h || !h->cl_plant || n_ticks < 1) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_tick: call lpvmpc_cl_init first");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const int B = h->cl_B, N = h->cfg.N;
+    const int B = h->cl_side.B, N = h->cfg.N;
     hipStream_t st = h->stream;
+    // the kernels of the fleet's form (step_form.hpp)
+    const PlantSide &side = h->cl_side;
+    const lpvmpc::TrackDev *trk = lpvmpc_trk(h);           // bound: the fleet was started by lpvmpc_cl_init_tyres, every vehicle on its own track
+    const lpvmpc::StepForm form = lpvmpc_step_form(h, side, nullptr);
+    lpvmpc::FleetMeasureFn *measure = lpvmpc::fleet_measure_launcher(form);
+    lpvmpc::FleetStepFn *step = lpvmpc::fleet_step_launcher(form);
+    if (!measure || !step) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_tick: internal error: no kernel for step form 0x%x", form);
     for (int t = 0; t < n_ticks; ++t) {
         // the measurement of this tick: made by the launch that advanced the plant at the end of the previous tick, or here
-        const lpvmpc::TrackDev *trk = lpvmpc_trk(h);       // bound: the fleet was started by lpvmpc_cl_init_tyres, every vehicle on its own track
         if (h->cl_next_valid) { double *t_ = h->cl_local; h->cl_local = h->cl_local_next; h->cl_local_next = t_; }
-        else if (trk && h->obs_state) HIP_TRY(h, lpvmpc::launch_cl_observe_measure_trk(*trk, B, h->obs_state, h->cl_cmd, h->cl_q9, h->cl_local, h->d_uold,
-                                                                                        h->cfg.steering_delay, st));
-        else if (trk) HIP_TRY(h, lpvmpc::launch_cl_measure_trk(*trk, B, h->cl_plant, h->cl_cmd, h->cl_q9, h->cl_local, h->d_uold, h->cfg.steering_delay, st));
-        else if (h->cl_actuated && h->obs_state) HIP_TRY(h, lpvmpc::launch_cl_observe_measure_act(h->d_cfg, B, h->obs_state, h->cl_cmd, h->cl_hw, h->cl_slack,
-                                                                                                 h->cl_q9, h->cl_local, h->d_uold, h->cfg.steering_delay, st));
-        else if (h->cl_actuated) HIP_TRY(h, lpvmpc::launch_cl_measure_act(h->d_cfg, B, h->cl_plant, h->cl_cmd, h->cl_hw, h->cl_slack, h->cl_q9, h->cl_local,
-                                                                          h->d_uold, h->cfg.steering_delay, st));
-        else if (h->obs_state) HIP_TRY(h, lpvmpc::launch_cl_observe_measure(h->d_cfg, B, h->obs_state, h->cl_cmd, h->cl_hw, h->cl_slack, h->cl_q9,
-                                                                           h->cl_local, h->d_uold, st));
-        else HIP_TRY(h, lpvmpc::launch_cl_measure(h->d_cfg, B, h->cl_plant, h->cl_cmd, h->cl_hw, h->cl_slack, h->cl_q9, h->cl_local, h->d_uold, st));
+        else HIP_TRY(h, measure(lpvmpc::FleetMeasureArgs{h->d_cfg, trk, B, h->cl_plant, h->obs_state, h->cl_cmd, h->cl_hw, h->cl_slack, h->cl_q9, h->cl_local,
+                                                         h->d_uold, h->cfg.steering_delay}, st));
         const double *x0 = h->cl_local; int x0_stride = 6;
         if (h->cl_first_it < 10) {                                           // CMAIN:310-315: seed mode
             HIP_TRY(h, lpvmpc::launch_cl_seed(B, N, h->cl_local, h->d_xlast, h->d_delta, st));
@@ -831,63 +831,10 @@ extern "C" int lpvmpc_cl_tick(lpvmpc_handle *h, int32_t n_ticks) {
         SolveArgs a{B, x0, h->d_AB, h->d_vel, h->d_uold, nullptr, h->d_xPred, h->d_uPred, h->d_status, h->d_iters, h->d_polish, h->d_resid,
                     nullptr, 0, x0_stride};
         int rc = lpvmpc_launch_solve_warm(h, a, st); if (rc) return rc;
-        if (h->cl_dist.d.rows) HIP_TRY(h, lpvmpc::launch_disturbance(h->d_cfg, trk, h->cl_dist.d, st));   // lpvmpc_set_disturbances
-        if (trk && h->obs_state && h->ov.L)
-            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_trk_obsveh(*trk, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, tyre_plant(h->cl_veh, h->cl_tyre), h->cl_q9,
-                                                                          h->cl_local_next, h->d_uold, h->cfg.steering_delay,
-                                                                          lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, h->cl_act.d, st));
-        else if (trk && h->obs_state)
-            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_trk(*trk, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, tyre_plant(h->cl_veh, h->cl_tyre), h->cl_q9,
-                                                                   h->cl_local_next, h->d_uold, h->cfg.steering_delay, h->obs_gains, h->obs_state, h->obs_p,
-                                                                   h->cl_act.d, st));
-        else if (trk)
-            HIP_TRY(h, lpvmpc::launch_cl_command_plant_measure_trk(*trk, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, tyre_plant(h->cl_veh, h->cl_tyre), h->cl_q9,
-                                                                   h->cl_local_next, h->d_uold, h->cfg.steering_delay, h->cl_act.d, st));
-        else if (h->cl_fault.d.rows && h->ov.L)                              // lpvmpc_set_sensor_faults: in place of the tyre forms' kernel
-            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_faulted_obsveh(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, tyre_plant(h->cl_veh, h->cl_tyre),
-                                                                               h->cl_hw, h->cl_slack, h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay,
-                                                                               lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, h->cl_act.d,
-                                                                               h->cl_fault.d, st));
-        else if (h->cl_fault.d.rows)
-            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_faulted(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, tyre_plant(h->cl_veh, h->cl_tyre),
-                                                                        h->cl_hw, h->cl_slack, h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay,
-                                                                        h->obs_gains, h->obs_state, h->obs_p, h->cl_act.d, h->cl_fault.d, st));
-        else if (h->cl_tyre.t && h->obs_state && h->ov.L)
-            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_tyre_obsveh(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, tyre_plant(h->cl_veh, h->cl_tyre),
-                                                                            h->cl_hw, h->cl_slack, h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay,
-                                                                            lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, h->cl_act.d, st));
-        else if (h->cl_veh.d.p && h->obs_state && h->ov.L)
-            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_veh_obsveh(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_veh.d, h->cl_hw, h->cl_slack,
-                                                                           h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay,
-                                                                           lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, h->cl_act.d, st));
-        else if (h->cl_tyre.t && h->obs_state)
-            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_tyre(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, tyre_plant(h->cl_veh, h->cl_tyre),
-                                                                     h->cl_hw, h->cl_slack, h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay,
-                                                                     h->obs_gains, h->obs_state, h->obs_p, h->cl_act.d, st));
-        else if (h->cl_tyre.t)
-            HIP_TRY(h, lpvmpc::launch_cl_command_plant_measure_tyre(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, tyre_plant(h->cl_veh, h->cl_tyre),
-                                                                     h->cl_hw, h->cl_slack, h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay,
-                                                                     h->cl_act.d, st));
-        else if (h->cl_veh.d.p && h->obs_state)
-            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_veh(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_veh.d, h->cl_hw, h->cl_slack,
-                                                                    h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay, h->obs_gains,
-                                                                    h->obs_state, h->obs_p, h->cl_act.d, st));
-        else if (h->cl_veh.d.p)
-            HIP_TRY(h, lpvmpc::launch_cl_command_plant_measure_veh(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_veh.d, h->cl_hw, h->cl_slack,
-                                                                    h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay, h->cl_act.d, st));
-        else if (h->cl_actuated && h->obs_state)
-            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe_act(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_pc, h->cl_hw, h->cl_slack,
-                                                                    h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay, h->obs_gains,
-                                                                    h->obs_state, h->obs_p, h->cl_act.d, st));
-        else if (h->cl_actuated)
-            HIP_TRY(h, lpvmpc::launch_cl_command_plant_measure_act(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_pc, h->cl_hw, h->cl_slack,
-                                                                    h->cl_q9, h->cl_local_next, h->d_uold, h->cfg.steering_delay, h->cl_act.d, st));
-        else if (h->obs_state)
-            HIP_TRY(h, lpvmpc::launch_cl_command_plant_observe(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_pc, h->cl_hw, h->cl_slack,
-                                                                h->cl_q9, h->cl_local_next, h->d_uold, h->obs_gains, h->obs_state, h->obs_p, st));
-        else
-            HIP_TRY(h, lpvmpc::launch_cl_command_plant_measure(h->d_cfg, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, h->cl_pc, h->cl_hw, h->cl_slack, h->cl_q9,
-                                                                h->cl_local_next, h->d_uold, st));
+        if (side.dist.d.rows) HIP_TRY(h, lpvmpc::launch_disturbance(h->d_cfg, trk, side.dist.d, st));   // lpvmpc_set_disturbances
+        HIP_TRY(h, step(lpvmpc::FleetStepArgs{h->d_cfg, trk, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, side.pc, side.tpc(), h->cl_hw, h->cl_slack, h->cl_q9,
+                                              h->cl_local_next, h->d_uold, h->cfg.steering_delay, lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p,
+                                              side.act.d, side.fault.d}, st));
         h->cl_next_valid = 1;
         h->cl_ticks++;
     }
@@ -897,7 +844,7 @@ extern "C" int lpvmpc_cl_tick(lpvmpc_handle *h, int32_t n_ticks) {
 extern "C" int lpvmpc_cl_read(lpvmpc_handle *h, double *plant, double *local_state, double *cmd, int32_t *iters, int32_t *status) {
     if (!h || !h->cl_plant) return fail(h, LPVMPC_E_ARG, "lpvmpc_cl_read: call lpvmpc_cl_init first");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const size_t B = h->cl_B;
+    const size_t B = h->cl_side.B;
     hipStream_t st = h->stream;
     if (plant) D2H(plant, h->cl_plant, B * 8 * 8);
     if (local_state) D2H(local_state, h->cl_local, B * 6 * 8);

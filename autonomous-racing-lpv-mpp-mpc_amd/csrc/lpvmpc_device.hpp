@@ -156,13 +156,7 @@ void launch_abc_trk(int kind, const DevCfg *dcfg, const TrackDev &trk, const dou
 struct PlantCfg { double lf, lr, m, Iz, mu, dt; int n_sub; };
 hipError_t launch_local_position(const DevCfg *dcfg, int B, const double *xypsi, double half_width, double slack, double *out, hipStream_t s);
 hipError_t launch_global_position(const DevCfg *dcfg, int B, const double *sey, double *out, hipStream_t s);
-hipError_t launch_plant(int B, double *plant, const double *u_a_delta, PlantCfg pc, hipStream_t s);
-hipError_t launch_cl_measure(const DevCfg *dcfg, int B, const double *plant, const double *cmd, double half_width, double slack,
-                             int q9_swap, double *local_state, double *u_old, hipStream_t s);
 hipError_t launch_cl_seed(int B, int N, const double *local_state, double *xlast, double *delta, hipStream_t s);
-hipError_t launch_cl_command_plant(int B, int N, const double *uPred, double *cmd, double *plant, PlantCfg pc, hipStream_t s);
-hipError_t launch_cl_command_plant_measure(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant, PlantCfg pc,
-                                           double hw, double slack, int q9_swap, double *local_next, double *u_old, hipStream_t s);
 
 // actuator stage of the simulator (fleet_kernels.hpp, actuator.hip; vehicleSimulator.py:53-78; lpvmpc_*_actuated, include/lpvmpc.h "Actuator delay and servo lag"):
 // per vehicle a ring of its last kActRing commands in global memory (a runtime-indexed per-lane array would live in scratch), the
@@ -176,14 +170,6 @@ struct ActDev {
     int B, lld;                              // lld: lowLevelDyn
     double c, c1;                            // T / Tf and 1 - T / Tf
 };
-hipError_t launch_plant_actuated(int B, double *plant, const double *u_a_delta, PlantCfg pc, const ActDev &a, hipStream_t s);
-// the delayed forms of the lap-0 fleet's kernels: the plant steps through the actuator stage, u_old [B][2 + sd] is the controller's
-// OldSteering / OldAccelera history (append the last command, drop the oldest entry, CMAIN:289-298) instead of the last command
-hipError_t launch_cl_measure_act(const DevCfg *dcfg, int B, const double *plant, const double *cmd, double half_width, double slack,
-                                 int q9_swap, double *local_state, double *u_old, int sd, hipStream_t s);
-hipError_t launch_cl_command_plant_measure_act(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant, PlantCfg pc,
-                                               double hw, double slack, int q9_swap, double *local_next, double *u_old, int sd,
-                                               const ActDev &a, hipStream_t s);
 
 // per-vehicle plant parameters (plant_params.hip; lpvmpc_*_vehicles, include/lpvmpc.h "Per-vehicle plant parameters"): the fleet's
 // table [kPlantWords][B], parameter-major and vehicle-minor like the actuator ring, so that a wavefront's loads of one word coalesce.
@@ -206,16 +192,6 @@ template <bool kVeh, bool kTyre = false> struct PlantArgT { using type = PlantCf
 template <> struct PlantArgT<true, false> { using type = VehPlantCfg; };
 template <> struct PlantArgT<true, true> { using type = TyrePlantCfg; };
 template <bool kVeh, bool kTyre = false> using PlantArg = typename PlantArgT<kVeh, kTyre>::type;
-// the per-vehicle forms of the kernels that step the plant: always the delayed forms (an all-off actuator is a pass-through)
-hipError_t launch_plant_veh(int B, double *plant, const double *u_a_delta, const VehPlantCfg &pc, const ActDev &a, hipStream_t s);
-hipError_t launch_cl_command_plant_measure_veh(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
-                                               const VehPlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
-                                               int sd, const ActDev &a, hipStream_t s);
-// the tyre forms of the same kernels (tyre.hip): the per-vehicle forms whose simulator step takes the vehicle's tyre row
-hipError_t launch_plant_tyre(int B, double *plant, const double *u_a_delta, const TyrePlantCfg &pc, const ActDev &a, hipStream_t s);
-hipError_t launch_cl_command_plant_measure_tyre(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
-                                                const TyrePlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
-                                                int sd, const ActDev &a, hipStream_t s);
 // force [B] = the tyre curve of row b of tyre [kTyreWords][B] at slip angle alpha [B] for a vehicle of mass m [B]
 hipError_t launch_tyre_force(int B, const double *tyre, const double *m, const double *alpha, double *force, hipStream_t s);
 
@@ -236,24 +212,6 @@ struct ObsVehDev { const double *rows = nullptr, *L = nullptr; int B = 0; };
 struct ObsVehGains : ObsVehDev { const double *g = nullptr; };
 hipError_t launch_observer_step(const double *gains, int B, double *est, const double *y, const double *u, const int32_t *k, double dt,
                                 double *aux, hipStream_t s);
-hipError_t launch_cl_observe_measure(const DevCfg *dcfg, int B, const double *obs, const double *cmd, double hw, double slack, int q9_swap,
-                                     double *local_state, double *u_old, hipStream_t s);
-hipError_t launch_cascade_plant_observe(int B, int N, const double *uPred, double *cmd, double *plant, PlantCfg pc, double *est_view,
-                                        const double *gains, double *obs, const ObsParams &op, hipStream_t s);
-hipError_t launch_cl_command_plant_observe(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant, PlantCfg pc,
-                                          double hw, double slack, int q9_swap, double *local_next, double *u_old, const double *gains,
-                                          double *obs, const ObsParams &op, hipStream_t s);
-hipError_t launch_cl_observe_measure_act(const DevCfg *dcfg, int B, const double *obs, const double *cmd, double hw, double slack, int q9_swap,
-                                         double *local_state, double *u_old, int sd, hipStream_t s);
-hipError_t launch_cl_command_plant_observe_act(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant, PlantCfg pc,
-                                              double hw, double slack, int q9_swap, double *local_next, double *u_old, int sd,
-                                              const double *gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s);
-hipError_t launch_cl_command_plant_observe_veh(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
-                                               const VehPlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
-                                               int sd, const double *gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s);
-hipError_t launch_cl_command_plant_observe_tyre(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
-                                                const TyrePlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
-                                                int sd, const double *gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s);
 
 
 // planner -> controller hand-off and trajectory-tracking measurement (handoff.hip)
@@ -291,56 +249,13 @@ struct RaceDev {              // device pointers and constants of one race (lpvm
     double *q_x0, *q_xPred, *q_xlast, *q_delta; // planner
 };
 hipError_t launch_race_plan_start(const DevCfg *pcfg, const RaceDev &r, hipStream_t s);
-hipError_t launch_race_measure(const DevCfg *ccfg, const RaceDev &r, int seed_tick, hipStream_t s);
-hipError_t launch_race_command_plant(const RaceDev &r, PlantCfg pc, hipStream_t s);
-hipError_t launch_race_command_plant_observe(const RaceDev &r, PlantCfg pc, const double *gains, double *obs, const ObsParams &op,
-                                            hipStream_t s);
-// the delayed forms (lpvmpc_race_init_actuated): u_old histories of path and TT (steering delay sd), actuator stage in the plant
-hipError_t launch_race_measure_act(const DevCfg *ccfg, const RaceDev &r, int seed_tick, int sd, hipStream_t s);
-hipError_t launch_race_command_plant_act(const RaceDev &r, PlantCfg pc, const ActDev &a, hipStream_t s);
-hipError_t launch_race_command_plant_observe_act(const RaceDev &r, PlantCfg pc, const double *gains, double *obs, const ObsParams &op,
-                                                const ActDev &a, hipStream_t s);
-// the per-vehicle forms (lpvmpc_race_init_vehicles, plant_params.hip): the delayed forms with the fleet's plant table
-hipError_t launch_race_command_plant_veh(const RaceDev &r, const VehPlantCfg &pc, const ActDev &a, hipStream_t s);
-hipError_t launch_race_command_plant_observe_veh(const RaceDev &r, const VehPlantCfg &pc, const double *gains, double *obs, const ObsParams &op,
-                                                const ActDev &a, hipStream_t s);
-// the tyre forms (lpvmpc_race_init_tyres, tyre.hip)
-hipError_t launch_race_command_plant_tyre(const RaceDev &r, const TyrePlantCfg &pc, const ActDev &a, hipStream_t s);
-hipError_t launch_race_command_plant_observe_tyre(const RaceDev &r, const TyrePlantCfg &pc, const double *gains, double *obs, const ObsParams &op,
-                                                 const ActDev &a, hipStream_t s);
 // observer_vehicles.hip: the per-vehicle-estimator forms
 hipError_t launch_observer_step_vehicles(const ObsVehGains &v, int B, double *est, const double *y, const double *u, const int32_t *k, double dt,
                                          double *aux, hipStream_t s);
-hipError_t launch_cl_command_plant_observe_veh_obsveh(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
-                                                      const VehPlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
-                                                      int sd, const ObsVehGains &gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s);
-hipError_t launch_cl_command_plant_observe_tyre_obsveh(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
-                                                       const TyrePlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
-                                                       int sd, const ObsVehGains &gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s);
-hipError_t launch_race_command_plant_observe_veh_obsveh(const RaceDev &r, const VehPlantCfg &pc, const ObsVehGains &gains, double *obs,
-                                                        const ObsParams &op, const ActDev &a, hipStream_t s);
-hipError_t launch_race_command_plant_observe_tyre_obsveh(const RaceDev &r, const TyrePlantCfg &pc, const ObsVehGains &gains, double *obs,
-                                                         const ObsParams &op, const ActDev &a, hipStream_t s);
-// track_vehicles.hip: the bound forms of the lap-0 fleet's kernels that read the track (the tyre forms, lpvmpc_cl_init_tyres); half
-// width and slack are each vehicle's track's
-hipError_t launch_cl_measure_trk(const TrackDev &trk, int B, const double *plant, const double *cmd, int q9_swap, double *local_state,
-                                 double *u_old, int sd, hipStream_t s);
-hipError_t launch_cl_command_plant_measure_trk(const TrackDev &trk, int B, int N, const double *uPred, double *cmd, double *plant,
-                                               const TyrePlantCfg &pc, int q9_swap, double *local_next, double *u_old, int sd,
-                                               const ActDev &a, hipStream_t s);
-hipError_t launch_cl_observe_measure_trk(const TrackDev &trk, int B, const double *obs, const double *cmd, int q9_swap, double *local_state,
-                                         double *u_old, int sd, hipStream_t s);
-hipError_t launch_cl_command_plant_observe_trk(const TrackDev &trk, int B, int N, const double *uPred, double *cmd, double *plant,
-                                               const TyrePlantCfg &pc, int q9_swap, double *local_next, double *u_old, int sd,
-                                               const double *gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s);
-hipError_t launch_cl_command_plant_observe_trk_obsveh(const TrackDev &trk, int B, int N, const double *uPred, double *cmd, double *plant,
-                                                      const TyrePlantCfg &pc, int q9_swap, double *local_next, double *u_old, int sd,
-                                                      const ObsVehGains &gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s);
 
 // track_race.hip: the bound forms of the race's, the hand-off's and the recorder's kernels that read the track (RecDev: record.hpp)
 struct RecDev;
 hipError_t launch_race_plan_start_trk(const DevCfg *pcfg, const TrackDev &trk, const RaceDev &r, hipStream_t s);
-hipError_t launch_race_measure_trk(const DevCfg *ccfg, const TrackDev &trk, const RaceDev &r, int seed_tick, int sd, hipStream_t s);
 hipError_t launch_plan_pose_trk(const DevCfg *dcfg, const TrackDev &trk, int B, const double *xPred, double *SS, double *pose, double *sig,
                                 hipStream_t s, const int32_t *active = nullptr);
 hipError_t launch_race_record_trk(const TrackDev &trk, const RecDev &r, int t, int slot, hipStream_t s);
@@ -374,22 +289,66 @@ struct FaultDev {
     unsigned long long seed;                 // the configuration's seed ^ LPVMPC_FAULT_STREAM
     long long voff;
 };
-// the general forms only: actuated, per-vehicle plant, tyre (the _tyres starts); gains as the forms they stand in for
-hipError_t launch_cl_command_plant_observe_faulted(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
-                                                   const TyrePlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
-                                                   int sd, const double *gains, double *obs, const ObsParams &op, const ActDev &a,
-                                                   const FaultDev &f, hipStream_t s);
-hipError_t launch_cl_command_plant_observe_faulted_obsveh(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
-                                                          const TyrePlantCfg &pc, double hw, double slack, int q9_swap, double *local_next,
-                                                          double *u_old, int sd, const ObsVehGains &gains, double *obs, const ObsParams &op,
-                                                          const ActDev &a, const FaultDev &f, hipStream_t s);
-hipError_t launch_race_command_plant_observe_faulted(const RaceDev &r, const TyrePlantCfg &pc, const double *gains, double *obs,
-                                                     const ObsParams &op, const ActDev &a, const FaultDev &f, hipStream_t s);
-hipError_t launch_race_command_plant_observe_faulted_obsveh(const RaceDev &r, const TyrePlantCfg &pc, const ObsVehGains &gains, double *obs,
-                                                            const ObsParams &op, const ActDev &a, const FaultDev &f, hipStream_t s);
 // lpvmpc_sensor_step_batch: one sensors + observer sub-step on caller arrays; f.rows null: the healthy stage; v.L null: the
 // configuration's tables and the observer's own constants
 hipError_t launch_sensor_step(const ObsVehGains &v, int B, double *obs, const double *plant, const double *servo, const double *motor,
                               const ObsParams &op, const FaultDev &f, hipStream_t s);
+
+// The kernels that advance a plant come in forms (fleet_kernels.hpp: delayed, per-vehicle plant, tyre, estimator, per-vehicle gains;
+// track_vehicles.hip / track_race.hip: bound tracks; sensor_faults.hip: faults), one form per translation unit.  Each family has one
+// argument struct, the union of what its kernels take, and every launcher of the family has the one signature below; it stands next
+// to its kernel and reads what that kernel takes.  Which launcher serves an engine is decided in one place: step_form.hpp maps the
+// engine's form to a kernel enumerator, fleet_launch.hip binds the enumerators to the launchers (null: the form has no kernel).
+// tpc slices to the per-vehicle forms' VehPlantCfg; gains.g is the plain forms' `gains`.
+#define LPVMPC_GRID(n) dim3(((n) + 63) / 64), dim3(64)
+struct FleetStepArgs {        // lpvmpc_cl_tick: command, plant and the coming tick's measurement (hw, slack: the unbound forms' map)
+    const DevCfg *dcfg; const TrackDev *trk;
+    int B, N;
+    const double *uPred; double *cmd, *plant;
+    PlantCfg pc; TyrePlantCfg tpc;
+    double hw, slack; int q9;
+    double *local_next, *u_old; int sd;
+    ObsVehGains gains; double *obs; ObsParams op;
+    ActDev act; FaultDev fault;
+};
+struct FleetMeasureArgs {     // the first tick's measurement: of the plant, or with an estimator of obs
+    const DevCfg *dcfg; const TrackDev *trk;
+    int B;
+    const double *plant, *obs, *cmd;
+    double hw, slack; int q9;
+    double *local_state, *u_old; int sd;
+};
+struct RaceStepArgs { RaceDev r; PlantCfg pc; TyrePlantCfg tpc; ObsVehGains gains; double *obs; ObsParams op; ActDev act; FaultDev fault; };
+struct RaceMeasureArgs { const DevCfg *ccfg; const TrackDev *trk; RaceDev r; int seed_tick, sd; };
+struct PlantStepArgs { int B; double *plant; const double *u; PlantCfg pc; TyrePlantCfg tpc; ActDev act; };
+using FleetStepFn = hipError_t(const FleetStepArgs &, hipStream_t);
+using FleetMeasureFn = hipError_t(const FleetMeasureArgs &, hipStream_t);
+using RaceStepFn = hipError_t(const RaceStepArgs &, hipStream_t);
+using RaceMeasureFn = hipError_t(const RaceMeasureArgs &, hipStream_t);
+using PlantStepFn = hipError_t(const PlantStepArgs &, hipStream_t);
+// closed_loop.hip, observer.hip, race.hip: the plain forms; actuator.hip: the delayed forms; plant_params.hip: the per-vehicle forms;
+// tyre.hip: the tyre forms; observer_vehicles.hip: the per-vehicle-estimator forms; track_vehicles.hip, track_race.hip: the bound forms;
+// sensor_faults.hip: the faulted forms
+FleetStepFn launch_cl_command_plant_measure, launch_cl_command_plant_observe, launch_cl_command_plant_measure_act, launch_cl_command_plant_observe_act,
+    launch_cl_command_plant_measure_veh, launch_cl_command_plant_observe_veh, launch_cl_command_plant_measure_tyre, launch_cl_command_plant_observe_tyre,
+    launch_cl_command_plant_observe_veh_obsveh, launch_cl_command_plant_observe_tyre_obsveh, launch_cl_command_plant_measure_trk,
+    launch_cl_command_plant_observe_trk, launch_cl_command_plant_observe_trk_obsveh, launch_cl_command_plant_observe_faulted,
+    launch_cl_command_plant_observe_faulted_obsveh;
+// the cascade's step (no table: it has the plain forms only): command and plant, and with its estimator the estimate's view in local_next
+FleetStepFn launch_cl_command_plant, launch_cascade_plant_observe;
+FleetMeasureFn launch_cl_measure, launch_cl_observe_measure, launch_cl_measure_act, launch_cl_observe_measure_act, launch_cl_measure_trk,
+    launch_cl_observe_measure_trk;
+RaceStepFn launch_race_command_plant, launch_race_command_plant_observe, launch_race_command_plant_act, launch_race_command_plant_observe_act,
+    launch_race_command_plant_veh, launch_race_command_plant_observe_veh, launch_race_command_plant_tyre, launch_race_command_plant_observe_tyre,
+    launch_race_command_plant_observe_veh_obsveh, launch_race_command_plant_observe_tyre_obsveh, launch_race_command_plant_observe_faulted,
+    launch_race_command_plant_observe_faulted_obsveh;
+RaceMeasureFn launch_race_measure, launch_race_measure_act, launch_race_measure_trk;
+PlantStepFn launch_plant, launch_plant_actuated, launch_plant_veh, launch_plant_tyre;
+// fleet_launch.hip: the launcher of a form (step_form.hpp: step_form), null: the family has no kernel for it
+FleetStepFn *fleet_step_launcher(unsigned form);
+FleetMeasureFn *fleet_measure_launcher(unsigned form);
+RaceStepFn *race_step_launcher(unsigned form);
+RaceMeasureFn *race_measure_launcher(unsigned form);
+PlantStepFn *plant_step_launcher(unsigned form);
 
 }  // namespace lpvmpc

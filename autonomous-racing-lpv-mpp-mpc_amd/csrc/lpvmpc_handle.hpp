@@ -12,6 +12,7 @@
 
 #include "lpvmpc.h"
 #include "lpvmpc_device.hpp"
+#include "step_form.hpp"
 #include "track_view.hpp"
 
 #define LPVMPC_HIDDEN __attribute__((visibility("hidden")))
@@ -71,6 +72,21 @@ struct FaultBinding {
     std::vector<double> rows;
 };
 
+// The plant an engine drives, stored once: a lap-0 fleet (Fleet::cl_side) and a race (lpvmpc_race::side) each hold one, and the
+// bindings and read-backs reach the running engine's through lpvmpc_plant_side.  Built in a local with the engine that owns it and
+// moved in after the last step that can fail
+struct PlantSide {
+    int B = 0;                          // fleet size
+    lpvmpc::PlantCfg pc{};              // the fleet-wide plant (a race's: n_sub = 1, each vehicle's steps of a tick are RaceDev::nstep)
+    int actuated = 0;                   // started by an _actuated call (or _vehicles / _tyres, which take the delayed kernels): actuator state act
+    ActState act;
+    PlantTable veh;                     // started by a _vehicles call: the plant table
+    TyreTable tyre;                     // started by a _tyres call: the tyre table as well
+    DistBinding dist;                   // lpvmpc_set_disturbances on that engine (freed with it)
+    FaultBinding fault;                 // lpvmpc_set_sensor_faults on that engine (freed with it)
+    lpvmpc::TyrePlantCfg tpc() const { return tyre_plant(veh, tyre); }
+};
+
 struct EventRing {                      // ring of event pairs around launches (lpvmpc_set_timing)
     std::vector<hipEvent_t> e0, e1;
     int count = 0;                      // pairs recorded since timing was (re)enabled
@@ -95,15 +111,9 @@ struct Fleet {                          // closed-loop fleet (lpvmpc_cl_*): plan
     double *cl_plant = nullptr, *cl_local = nullptr, *cl_cmd = nullptr;
     double *cl_local_next = nullptr;    // measurement of the coming tick, made by the launch that advanced the plant (valid: cl_next_valid)
     int cl_next_valid = 0;
-    int cl_B = 0, cl_first_it = 1, cl_q9 = 1, cl_ticks = 0;
+    int cl_first_it = 1, cl_q9 = 1, cl_ticks = 0;
     double cl_hw = 0, cl_slack = 0;
-    lpvmpc::PlantCfg cl_pc{};
-    int cl_actuated = 0;                // the fleet was started by lpvmpc_cl_init_actuated: delayed kernels, actuator state cl_act
-    ActState cl_act;
-    PlantTable cl_veh;                  // the fleet was started by lpvmpc_cl_init_vehicles: its plant table
-    TyreTable cl_tyre;                  // the fleet was started by lpvmpc_cl_init_tyres: its tyre table as well
-    DistBinding cl_dist;                // lpvmpc_set_disturbances on that fleet (freed with it)
-    FaultBinding cl_fault;              // lpvmpc_set_sensor_faults on that fleet (freed with it)
+    PlantSide cl_side;                  // the plant it drives
 };
 struct ObsState {                       // the fleet's / cascade's / race's estimator state [obs_B][kObsStride] (null: it runs on ground truth;
     DevArena obs_mem;                   // a race's is set by lpvmpc_race_init_observed without obs_cfg and freed with the race)
@@ -250,7 +260,6 @@ LPVMPC_HIDDEN int lpvmpc_observer_start(lpvmpc_handle *h, const lpvmpc_observer_
 LPVMPC_HIDDEN int lpvmpc_act_alloc(lpvmpc_handle *h, int B, const lpvmpc_actuator_config *cfg, const int32_t *delay_a, const int32_t *delay_df,
                                    double dt_sim, const char *who, ActState &a);
 LPVMPC_HIDDEN int lpvmpc_act_download(lpvmpc_handle *h, const lpvmpc::ActDev &a, double *act_state, hipStream_t st);   // device -> host layout
-LPVMPC_HIDDEN int lpvmpc_race_act_read(lpvmpc_handle *h, double *act_state, double *path_hist, double *tt_hist);        // race_api.hip
 LPVMPC_HIDDEN int lpvmpc_observer_check(lpvmpc_handle *h, const lpvmpc_observer_config *c, const char *who);   // lpvmpc_api.hip
 // plant_params_api.hip: per-vehicle plant parameters (lpvmpc_*_vehicles).  lpvmpc_plant_rows checks the host rows [B][7] (null: the
 // nominal row lf, lr, m, Iz, 60, 60, mu for every vehicle) and returns the device layout [7][B] in t; nothing is allocated.
@@ -258,7 +267,13 @@ LPVMPC_HIDDEN int lpvmpc_observer_check(lpvmpc_handle *h, const lpvmpc_observer_
 LPVMPC_HIDDEN int lpvmpc_plant_rows(lpvmpc_handle *h, int B, const double *rows, const lpvmpc_config &nominal, double mu, const char *who,
                                     std::vector<double> &t);
 LPVMPC_HIDDEN int lpvmpc_plant_upload(lpvmpc_handle *h, int B, const std::vector<double> &t, double dt_sim, int n_sub, PlantTable &v);
-LPVMPC_HIDDEN const lpvmpc::VehPlantCfg *lpvmpc_race_plant(const lpvmpc_handle *h);                     // race_api.hip: the race's table
+// race_api.hip: the plant side of the engine that h runs -- the race's (*race: its RaceDev), else the lap-0 fleet's (*race null), else
+// null -- and the engine's step form (step_form.hpp); lpvmpc_race_dist: what a race's disturbances act on
+LPVMPC_HIDDEN PlantSide *lpvmpc_plant_side(lpvmpc_handle *h, const lpvmpc::RaceDev **race = nullptr);
+LPVMPC_HIDDEN lpvmpc::DistDev lpvmpc_race_dist(const PlantSide &p, const lpvmpc::RaceDev &d);
+inline lpvmpc::StepForm lpvmpc_step_form(const lpvmpc_handle *h, const PlantSide &p, const lpvmpc::RaceDev *race) {
+    return lpvmpc::step_form(p.actuated, p.veh.d.p, p.tyre.t, race ? race->estv != nullptr : h->obs_state != nullptr, h->ov.L, h->trk.tab, p.fault.d.rows);
+}
 // lpvmpc_plant_step_vehicles_batch with the checked tyre table [4][B] of tyre_api.hip (null: the per-vehicle forms' kernel)
 LPVMPC_HIDDEN int lpvmpc_plant_step_rows(lpvmpc_handle *h, int32_t B, double *state, double *act_state, const double *u, int32_t n_sub, double dt_sim,
                                          double mu_sim, const lpvmpc_actuator_config *act, const int32_t *delay_a, const int32_t *delay_df,
@@ -268,7 +283,6 @@ LPVMPC_HIDDEN int lpvmpc_plant_step_rows(lpvmpc_handle *h, int32_t B, double *st
 // the device layout [4][B] in t; nothing is allocated.  lpvmpc_tyre_upload allocates and fills the table in y, released first (synchronises)
 LPVMPC_HIDDEN int lpvmpc_tyre_rows(lpvmpc_handle *h, int B, const double *rows, const char *who, std::vector<double> &t);
 LPVMPC_HIDDEN int lpvmpc_tyre_upload(lpvmpc_handle *h, const std::vector<double> &t, TyreTable &y);
-LPVMPC_HIDDEN const double *lpvmpc_race_tyre(const lpvmpc_handle *h);                                  // race_api.hip: the race's tyre table (null: none)
 // the fleet / race starts shared by the _vehicles and _tyres entry points (lpvmpc_api.hip, race_api.hip); tyre_params: see lpvmpc_tyre_rows,
 // tyres false: the _vehicles call
 LPVMPC_HIDDEN int lpvmpc_cl_init_rows(lpvmpc_handle *h, int32_t B, const double *plant0, double half_width, double slack, int32_t q9_swap,
@@ -278,22 +292,16 @@ LPVMPC_HIDDEN int lpvmpc_race_init_rows(lpvmpc_handle *h, lpvmpc_handle *tt, lpv
                                         const int32_t *half_track0, const lpvmpc_race_config *cfg, const lpvmpc_observer_config *obs,
                                         const lpvmpc_actuator_config *act, const int32_t *delay_a, const int32_t *delay_df,
                                         const double *plant_params, bool tyres, const double *tyre_params);
-// disturbance_api.hip: plant disturbances.  lpvmpc_race_dist (race_api.hip): the race's binding and what it acts on -- filled into t:
-// plant, step counters, this tick's step counts, dt_sim, the map's width and the live tables (false: the race has no tyre table).
-// lpvmpc_dist_rows checks cfg and the host rows [B][LPVMPC_DIST_WORDS] against each vehicle's lap length and returns the device
+// disturbance_api.hip: plant disturbances.  lpvmpc_dist_rows checks cfg and the host rows [B][LPVMPC_DIST_WORDS] against each vehicle's lap length and returns the device
 // layout [LPVMPC_DIST_WORDS + 1][B] in t.  lpvmpc_dist_step: the stand-alone step's launch in front of its plant kernel, on tables
 // that live in mem; dist_state [B][LPVMPC_DIST_STATE] in (null: fresh), lpvmpc_dist_step_read copies it out after the step
 struct DistStep { const lpvmpc_disturbance_config *cfg; const double *rows; double *dist_state; };
-LPVMPC_HIDDEN DistBinding *lpvmpc_race_dist(lpvmpc_handle *h, lpvmpc::DistDev *t);
 LPVMPC_HIDDEN int lpvmpc_dist_rows(lpvmpc_handle *h, int B, const lpvmpc_disturbance_config *cfg, const double *rows, const char *who,
                                    std::vector<double> &t);
 LPVMPC_HIDDEN int lpvmpc_dist_step(lpvmpc_handle *h, int B, const DistStep &ds, const std::vector<double> &rows_dev, const std::vector<double> &plant_tab,
                                    const std::vector<double> &tyre_tab, double *d_plant, const int32_t *d_k, int n_sub, double dt_sim,
                                    double *live_p, double *live_t, DistBinding &tmp, hipStream_t st);
 LPVMPC_HIDDEN int lpvmpc_dist_step_read(lpvmpc_handle *h, int B, const DistStep &ds, const DistBinding &tmp, hipStream_t st);
-// sensor_faults_api.hip: sensor faults.  lpvmpc_race_fault (race_api.hip): the race's binding, *B its fleet size, *served whether the race
-// has an estimator in the loop and plant and tyre tables (null: the handle owns no race)
-LPVMPC_HIDDEN FaultBinding *lpvmpc_race_fault(lpvmpc_handle *h, int *B, bool *served);
 // model_params_api.hip: lpvmpc_model_check refuses a batch size other than that of the handle's bound model rows (unbound: any);
 // called by every entry point that linearises, before anything is launched
 LPVMPC_HIDDEN int lpvmpc_model_check(lpvmpc_handle *h, int B, const char *who);

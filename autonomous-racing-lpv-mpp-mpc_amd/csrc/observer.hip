@@ -41,30 +41,25 @@ __global__ void __launch_bounds__(64) observer_step_kernel(const double *__restr
     }
 }
 
-#define LPVMPC_GRID(n) dim3(((n) + 63) / 64), dim3(64)
 hipError_t launch_observer_step(const double *gains, int B, double *est, const double *y, const double *u, const int32_t *k, double dt,
                                 double *aux, hipStream_t s) {
     hipLaunchKernelGGL(observer_step_kernel, LPVMPC_GRID(B), 0, s, gains, B, est, y, u, k, dt, aux);
     return hipGetLastError();
 }
-hipError_t launch_cl_observe_measure(const DevCfg *dcfg, int B, const double *obs, const double *cmd, double hw, double slack, int q9_swap,
-                                     double *local_state, double *u_old, hipStream_t s) {
-    hipLaunchKernelGGL(cl_command_plant_observe_kernel<false>, LPVMPC_GRID(B), 0, s, dcfg, B, 1, (const double *)nullptr, const_cast<double *>(cmd),
-                       (double *)nullptr, PlantCfg{}, hw, slack, q9_swap, local_state, u_old, (const double *)nullptr, const_cast<double *>(obs),
+hipError_t launch_cl_observe_measure(const FleetMeasureArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(cl_command_plant_observe_kernel<false>, LPVMPC_GRID(a.B), 0, s, a.dcfg, a.B, 1, (const double *)nullptr, const_cast<double *>(a.cmd),
+                       (double *)nullptr, PlantCfg{}, a.hw, a.slack, a.q9, a.local_state, a.u_old, (const double *)nullptr, const_cast<double *>(a.obs),
                        ObsParams{}, 0, 0, ActDev{});
     return hipGetLastError();
 }
-hipError_t launch_cl_command_plant_observe(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant, PlantCfg pc,
-                                          double hw, double slack, int q9_swap, double *local_next, double *u_old, const double *gains,
-                                          double *obs, const ObsParams &op, hipStream_t s) {
-    hipLaunchKernelGGL(cl_command_plant_observe_kernel<false>, LPVMPC_GRID(B), 0, s, dcfg, B, N, uPred, cmd, plant, pc, hw, slack, q9_swap,
-                       local_next, u_old, gains, obs, op, 1, 0, ActDev{});
+hipError_t launch_cl_command_plant_observe(const FleetStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(cl_command_plant_observe_kernel<false>, LPVMPC_GRID(a.B), 0, s, a.dcfg, a.B, a.N, a.uPred, a.cmd, a.plant, a.pc, a.hw, a.slack, a.q9,
+                       a.local_next, a.u_old, a.gains.g, a.obs, a.op, 1, 0, ActDev{});
     return hipGetLastError();
 }
-hipError_t launch_cascade_plant_observe(int B, int N, const double *uPred, double *cmd, double *plant, PlantCfg pc, double *est_view,
-                                        const double *gains, double *obs, const ObsParams &op, hipStream_t s) {
-    hipLaunchKernelGGL(cl_command_plant_observe_kernel<false>, LPVMPC_GRID(B), 0, s, (const DevCfg *)nullptr, B, N, uPred, cmd, plant, pc, 0.0, 0.0, 0,
-                       est_view, (double *)nullptr, gains, obs, op, 2, 0, ActDev{});
+hipError_t launch_cascade_plant_observe(const FleetStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(cl_command_plant_observe_kernel<false>, LPVMPC_GRID(a.B), 0, s, (const DevCfg *)nullptr, a.B, a.N, a.uPred, a.cmd, a.plant, a.pc, 0.0, 0.0,
+                       0, a.local_next, (double *)nullptr, a.gains.g, a.obs, a.op, 2, 0, ActDev{});
     return hipGetLastError();
 }
 

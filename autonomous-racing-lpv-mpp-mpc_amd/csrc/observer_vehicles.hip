@@ -32,34 +32,28 @@ __global__ void __launch_bounds__(64) observer_step_vehicles_kernel(ObsVehGains 
     }
 }
 
-#define LPVMPC_GRID(n) dim3(((n) + 63) / 64), dim3(64)
 hipError_t launch_observer_step_vehicles(const ObsVehGains &v, int B, double *est, const double *y, const double *u, const int32_t *k, double dt,
                                          double *aux, hipStream_t s) {
     hipLaunchKernelGGL(observer_step_vehicles_kernel, LPVMPC_GRID(B), 0, s, v, B, est, y, u, k, dt, aux);
     return hipGetLastError();
 }
-hipError_t launch_cl_command_plant_observe_veh_obsveh(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
-                                                      const VehPlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
-                                                      int sd, const ObsVehGains &gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL((cl_command_plant_observe_kernel<true, true, false, true>), LPVMPC_GRID(B), 0, s, dcfg, B, N, uPred, cmd, plant, pc, hw, slack,
-                       q9_swap, local_next, u_old, gains, obs, op, 1, sd, a);
+hipError_t launch_cl_command_plant_observe_veh_obsveh(const FleetStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((cl_command_plant_observe_kernel<true, true, false, true>), LPVMPC_GRID(a.B), 0, s, a.dcfg, a.B, a.N, a.uPred, a.cmd, a.plant,
+                       static_cast<const VehPlantCfg &>(a.tpc), a.hw, a.slack, a.q9, a.local_next, a.u_old, a.gains, a.obs, a.op, 1, a.sd, a.act);
     return hipGetLastError();
 }
-hipError_t launch_cl_command_plant_observe_tyre_obsveh(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
-                                                       const TyrePlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
-                                                       int sd, const ObsVehGains &gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL((cl_command_plant_observe_kernel<true, true, true, true>), LPVMPC_GRID(B), 0, s, dcfg, B, N, uPred, cmd, plant, pc, hw, slack,
-                       q9_swap, local_next, u_old, gains, obs, op, 1, sd, a);
+hipError_t launch_cl_command_plant_observe_tyre_obsveh(const FleetStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((cl_command_plant_observe_kernel<true, true, true, true>), LPVMPC_GRID(a.B), 0, s, a.dcfg, a.B, a.N, a.uPred, a.cmd, a.plant, a.tpc, a.hw,
+                       a.slack, a.q9, a.local_next, a.u_old, a.gains, a.obs, a.op, 1, a.sd, a.act);
     return hipGetLastError();
 }
-hipError_t launch_race_command_plant_observe_veh_obsveh(const RaceDev &r, const VehPlantCfg &pc, const ObsVehGains &gains, double *obs,
-                                                        const ObsParams &op, const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL((race_command_plant_observe_kernel<true, true, false, true>), LPVMPC_GRID(r.B), 0, s, r, pc, gains, obs, op, a);
+hipError_t launch_race_command_plant_observe_veh_obsveh(const RaceStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((race_command_plant_observe_kernel<true, true, false, true>), LPVMPC_GRID(a.r.B), 0, s, a.r, static_cast<const VehPlantCfg &>(a.tpc),
+                       a.gains, a.obs, a.op, a.act);
     return hipGetLastError();
 }
-hipError_t launch_race_command_plant_observe_tyre_obsveh(const RaceDev &r, const TyrePlantCfg &pc, const ObsVehGains &gains, double *obs,
-                                                         const ObsParams &op, const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL((race_command_plant_observe_kernel<true, true, true, true>), LPVMPC_GRID(r.B), 0, s, r, pc, gains, obs, op, a);
+hipError_t launch_race_command_plant_observe_tyre_obsveh(const RaceStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((race_command_plant_observe_kernel<true, true, true, true>), LPVMPC_GRID(a.r.B), 0, s, a.r, a.tpc, a.gains, a.obs, a.op, a.act);
     return hipGetLastError();
 }
 

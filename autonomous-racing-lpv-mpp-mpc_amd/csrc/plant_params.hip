@@ -8,33 +8,27 @@
 
 namespace lpvmpc {
 
-#define LPVMPC_GRID(n) dim3(((n) + 63) / 64), dim3(64)
-hipError_t launch_plant_veh(int B, double *plant, const double *u, const VehPlantCfg &pc, const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL((plant_kernel<true, true>), LPVMPC_GRID(B), 0, s, B, plant, u, pc, a);
+hipError_t launch_plant_veh(const PlantStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((plant_kernel<true, true>), LPVMPC_GRID(a.B), 0, s, a.B, a.plant, a.u, static_cast<const VehPlantCfg &>(a.tpc), a.act);
     return hipGetLastError();
 }
-hipError_t launch_cl_command_plant_measure_veh(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
-                                               const VehPlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
-                                               int sd, const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL((cl_command_plant_measure_kernel<true, true>), LPVMPC_GRID(B), 0, s, dcfg, B, N, uPred, cmd, plant, pc, hw, slack,
-                       q9_swap, local_next, u_old, sd, a);
+hipError_t launch_cl_command_plant_measure_veh(const FleetStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((cl_command_plant_measure_kernel<true, true>), LPVMPC_GRID(a.B), 0, s, a.dcfg, a.B, a.N, a.uPred, a.cmd, a.plant, static_cast<const VehPlantCfg &>(a.tpc), a.hw, a.slack,
+                       a.q9, a.local_next, a.u_old, a.sd, a.act);
     return hipGetLastError();
 }
-hipError_t launch_cl_command_plant_observe_veh(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
-                                               const VehPlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
-                                               int sd, const double *gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL((cl_command_plant_observe_kernel<true, true>), LPVMPC_GRID(B), 0, s, dcfg, B, N, uPred, cmd, plant, pc, hw, slack,
-                       q9_swap, local_next, u_old, gains, obs, op, 1, sd, a);
+hipError_t launch_cl_command_plant_observe_veh(const FleetStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((cl_command_plant_observe_kernel<true, true>), LPVMPC_GRID(a.B), 0, s, a.dcfg, a.B, a.N, a.uPred, a.cmd, a.plant, static_cast<const VehPlantCfg &>(a.tpc), a.hw, a.slack,
+                       a.q9, a.local_next, a.u_old, a.gains.g, a.obs, a.op, 1, a.sd, a.act);
     return hipGetLastError();
 }
 
-hipError_t launch_race_command_plant_veh(const RaceDev &r, const VehPlantCfg &pc, const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL((race_command_plant_kernel<true, true>), LPVMPC_GRID(r.B), 0, s, r, pc, a);
+hipError_t launch_race_command_plant_veh(const RaceStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((race_command_plant_kernel<true, true>), LPVMPC_GRID(a.r.B), 0, s, a.r, static_cast<const VehPlantCfg &>(a.tpc), a.act);
     return hipGetLastError();
 }
-hipError_t launch_race_command_plant_observe_veh(const RaceDev &r, const VehPlantCfg &pc, const double *gains, double *obs, const ObsParams &op,
-                                                const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL((race_command_plant_observe_kernel<true, true>), LPVMPC_GRID(r.B), 0, s, r, pc, gains, obs, op, a);
+hipError_t launch_race_command_plant_observe_veh(const RaceStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((race_command_plant_observe_kernel<true, true>), LPVMPC_GRID(a.r.B), 0, s, a.r, static_cast<const VehPlantCfg &>(a.tpc), a.gains.g, a.obs, a.op, a.act);
     return hipGetLastError();
 }
 

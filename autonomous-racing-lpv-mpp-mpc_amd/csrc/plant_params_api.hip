@@ -80,8 +80,8 @@ int lpvmpc_plant_step_rows(lpvmpc_handle *h, int32_t B, double *state, double *a
                                       const_cast<double *>(y.t), dtmp, st);
             if (rd) return rd;
         }
-        if (y.t) HIP_TRY(h, lpvmpc::launch_plant_tyre(B, h->d_xlast, h->d_states, tyre_plant(v, y), a, st));
-        else HIP_TRY(h, lpvmpc::launch_plant_veh(B, h->d_xlast, h->d_states, v.d, a, st));
+        const lpvmpc::PlantStepArgs pa{B, h->d_xlast, h->d_states, lpvmpc::PlantCfg{}, tyre_plant(v, y), a};
+        HIP_TRY(h, lpvmpc::plant_step_launcher(lpvmpc::step_form(true, true, y.t, false, false, false, false))(pa, st));
         D2H(state, h->d_xlast, b * 8 * 8);
         if (dist) { int rd = lpvmpc_dist_step_read(h, B, *dist, dtmp, st); if (rd) return rd; }
         if (act_state) return lpvmpc_act_download(h, a, act_state, st);   // (synchronises)
@@ -103,17 +103,15 @@ extern "C" int lpvmpc_plant_step_vehicles_batch(lpvmpc_handle *h, int32_t B, dou
 // device [7][B] -> host [B][7]
 extern "C" int lpvmpc_plant_params_read(lpvmpc_handle *h, double *plant_params) {
     const char *who = "lpvmpc_plant_params_read";
-    const lpvmpc::VehPlantCfg *v = nullptr;
-    if (h && h->race) v = lpvmpc_race_plant(h);
-    else if (h && h->cl_plant && h->cl_veh.d.p) v = &h->cl_veh.d;
+    const PlantSide *side = lpvmpc_plant_side(h);
+    const lpvmpc::VehPlantCfg *v = side ? &side->veh.d : nullptr;
     if (!v || !v->p) return fail(h, LPVMPC_E_ARG, "%s: no fleet or race started by lpvmpc_cl_init_vehicles / lpvmpc_race_init_vehicles", who);
     if (!plant_params) return fail(h, LPVMPC_E_ARG, "%s: plant_params is NULL", who);
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t st = h->stream;
     const size_t B = v->B;
     std::vector<double> t(B * LPVMPC_PLANT_WORDS);
-    const DistBinding *dist = h->race ? lpvmpc_race_dist(h, nullptr) : &h->cl_dist;
-    if (dist && dist->d.rows) t = dist->base_p;                      // disturbances attached: the base rows, not the scaled live words
+    if (side->dist.d.rows) t = side->dist.base_p;                        // disturbances attached: the base rows, not the scaled live words
     else D2H(t.data(), v->p, t.size() * 8);
     HIP_TRY(h, hipStreamSynchronize(st));
     for (size_t b = 0; b < B; ++b)

@@ -53,22 +53,20 @@ __global__ void __launch_bounds__(64) race_plan_start_kernel(const DevCfg *__res
     r.m_pfirst[b] = first; r.m_pcont[b] = cont; r.m_plan[b] = first | cont;
 }
 
-#define LPVMPC_GRID(n) dim3(((n) + 63) / 64), dim3(64)
 hipError_t launch_race_plan_start(const DevCfg *pcfg, const RaceDev &r, hipStream_t s) {
     hipLaunchKernelGGL(race_plan_start_kernel, LPVMPC_GRID(r.B), 0, s, pcfg, r);
     return hipGetLastError();
 }
-hipError_t launch_race_measure(const DevCfg *ccfg, const RaceDev &r, int seed_tick, hipStream_t s) {
-    hipLaunchKernelGGL(race_measure_kernel<false>, LPVMPC_GRID(r.B), 0, s, ccfg, r, seed_tick, 0);
+hipError_t launch_race_measure(const RaceMeasureArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(race_measure_kernel<false>, LPVMPC_GRID(a.r.B), 0, s, a.ccfg, a.r, a.seed_tick, 0);
     return hipGetLastError();
 }
-hipError_t launch_race_command_plant(const RaceDev &r, PlantCfg pc, hipStream_t s) {
-    hipLaunchKernelGGL(race_command_plant_kernel<false>, LPVMPC_GRID(r.B), 0, s, r, pc, ActDev{});
+hipError_t launch_race_command_plant(const RaceStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(race_command_plant_kernel<false>, LPVMPC_GRID(a.r.B), 0, s, a.r, a.pc, ActDev{});
     return hipGetLastError();
 }
-hipError_t launch_race_command_plant_observe(const RaceDev &r, PlantCfg pc, const double *gains, double *obs, const ObsParams &op,
-                                            hipStream_t s) {
-    hipLaunchKernelGGL(race_command_plant_observe_kernel<false>, LPVMPC_GRID(r.B), 0, s, r, pc, gains, obs, op, ActDev{});
+hipError_t launch_race_command_plant_observe(const RaceStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(race_command_plant_observe_kernel<false>, LPVMPC_GRID(a.r.B), 0, s, a.r, a.pc, a.gains.g, a.obs, a.op, ActDev{});
     return hipGetLastError();
 }
 

@@ -25,16 +25,10 @@ struct lpvmpc_race {
     lpvmpc::RaceDev d{};          // device pointers and constants (kernel argument)
     DevArena mem;                 // the race's own buffers of d (the p_ / t_ / q_ pointers are the three handles' workspaces)
     int ticks = 0;
-    lpvmpc::PlantCfg pc{};
-    bool actuated = false;        // lpvmpc_race_init_actuated: delayed kernels, actuator state act, controller histories of steering delay sd
-    ActState act;
+    PlantSide side;               // the plant it drives (side.actuated: the controllers keep histories of steering delay sd)
     int sd = 0;
-    PlantTable veh;               // lpvmpc_race_init_vehicles: the plant table (veh.d.p; null: one PlantCfg), with the delayed kernels' actuator
-    TyreTable tyre;               // lpvmpc_race_init_tyres: the tyre table next to veh (tyre.t; null: the linear tyre's kernels)
     std::unique_ptr<lpvmpc_race_recorder> rec;   // lpvmpc_race_record (null: not recording)
     std::unique_ptr<HeatsBinding> heats;         // lpvmpc_race_heats (heats_api.hip; null: none attached)
-    DistBinding dist;             // lpvmpc_set_disturbances (dist.d.rows null: none attached), freed with the race
-    FaultBinding fault;           // lpvmpc_set_sensor_faults (fault.d.rows null: none attached), freed with the race
 };
 
 void lpvmpc_race_free(lpvmpc_handle *h) {
@@ -116,12 +110,12 @@ static int race_init(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, i
     // the race is built in r and installed in the three handles after the last step that can fail: a failed call leaves them idle
     std::unique_ptr<lpvmpc_race> r(new (std::nothrow) lpvmpc_race());
     if (!r) return fail(h, LPVMPC_E_NOMEM, "out of host memory");
-    if (act) { rc = lpvmpc_act_alloc(h, B, act, delay_a, delay_df, cfg->dt_sim, veh ? "lpvmpc_race_init_vehicles" : "lpvmpc_race_init_actuated", r->act); if (rc) return rc; }
-    if (veh) { rc = lpvmpc_plant_upload(h, B, *veh, cfg->dt_sim, 1, r->veh); if (rc) return rc; }
-    if (tyre) { rc = lpvmpc_tyre_upload(h, *tyre, r->tyre); if (rc) return rc; }
+    if (act) { rc = lpvmpc_act_alloc(h, B, act, delay_a, delay_df, cfg->dt_sim, veh ? "lpvmpc_race_init_vehicles" : "lpvmpc_race_init_actuated", r->side.act); if (rc) return rc; }
+    if (veh) { rc = lpvmpc_plant_upload(h, B, *veh, cfg->dt_sim, 1, r->side.veh); if (rc) return rc; }
+    if (tyre) { rc = lpvmpc_tyre_upload(h, *tyre, r->side.tyre); if (rc) return rc; }
     r->tt = tt; r->plan = plan;
-    r->actuated = act != nullptr; r->sd = h->cfg.steering_delay;
-    r->pc = lpvmpc_plant_cfg(h, 1, cfg->dt_sim, cfg->mu_sim);
+    r->side.B = B; r->side.actuated = act != nullptr; r->sd = h->cfg.steering_delay;
+    r->side.pc = lpvmpc_plant_cfg(h, 1, cfg->dt_sim, cfg->mu_sim);
     lpvmpc::RaceDev &d = r->d;
     const size_t b = B, N = h->cfg.N, Np = plan->cfg.N, M = plan->ho_M;
     d.B = B; d.N = (int)N; d.Np = (int)Np; d.M = (int)M; d.laps = cfg->laps; d.q9 = cfg->q9_swap != 0; d.n_sub_lap0 = cfg->n_sub_lap0;
@@ -220,29 +214,18 @@ extern "C" int lpvmpc_race_init_vehicles(lpvmpc_handle *h, lpvmpc_handle *tt, lp
     return lpvmpc_race_init_rows(h, tt, plan, B, plant0, half_track0, cfg, obs, act, delay_a, delay_df, plant_params, false, nullptr);
 }
 
-const lpvmpc::VehPlantCfg *lpvmpc_race_plant(const lpvmpc_handle *h) { return h->race ? &h->race->veh.d : nullptr; }
-const double *lpvmpc_race_tyre(const lpvmpc_handle *h) { return h->race ? h->race->tyre.t : nullptr; }
-
-// the race's disturbance binding and, in t, what it acts on (null: no race, or one without plant and tyre tables)
-DistBinding *lpvmpc_race_dist(lpvmpc_handle *h, lpvmpc::DistDev *t) {
-    lpvmpc_race *r = h->race;
-    if (!r || !r->veh.d.p || !r->tyre.t) return nullptr;
-    if (t) {
-        *t = lpvmpc::DistDev{};
-        t->B = r->d.B; t->plant = r->d.plant; t->k = r->act.d.k; t->nstep = r->d.nstep; t->n_fixed = 0; t->dt = r->pc.dt;
-        t->hw = r->d.hw; t->slack = r->d.slack;
-        t->live_p = const_cast<double *>(r->veh.d.p); t->live_t = const_cast<double *>(r->tyre.t);
-    }
-    return &r->dist;
+PlantSide *lpvmpc_plant_side(lpvmpc_handle *h, const lpvmpc::RaceDev **race) {
+    if (race) *race = h && h->race ? &h->race->d : nullptr;
+    return !h ? nullptr : h->race ? &h->race->side : h->cl_plant ? &h->cl_side : nullptr;
 }
 
-// the race's sensor-fault binding (a binding, not state: the inventory below does not list it)
-FaultBinding *lpvmpc_race_fault(lpvmpc_handle *h, int *B, bool *served) {
-    lpvmpc_race *r = h->race;
-    if (!r) return nullptr;
-    *B = r->d.B;
-    *served = r->d.estv && r->veh.d.p && r->tyre.t;
-    return &r->fault;
+// what a race's disturbances act on (lpvmpc_set_disturbances): each vehicle steps RaceDev::nstep times in a tick
+lpvmpc::DistDev lpvmpc_race_dist(const PlantSide &p, const lpvmpc::RaceDev &d) {
+    lpvmpc::DistDev t{};
+    t.B = d.B; t.plant = d.plant; t.k = p.act.d.k; t.nstep = d.nstep; t.n_fixed = 0; t.dt = p.pc.dt;
+    t.hw = d.hw; t.slack = d.slack;
+    t.live_p = const_cast<double *>(p.veh.d.p); t.live_t = const_cast<double *>(p.tyre.t);
+    return t;
 }
 
 // The inventory of the race's per-vehicle state (lpvmpc_handle.hpp: RaceState; include/lpvmpc.h, "Race snapshot, restore and clone").
@@ -268,8 +251,8 @@ bool lpvmpc_race_state(lpvmpc_handle *h, RaceState &s) {
     s.recording = r->rec != nullptr;
     s.heats = r->heats != nullptr;
     if (h->trk.tab) s.track_of = &h->trk_of;
-    s.features = (d.estv ? LPVMPC_SNAP_HAS_ESTIMATOR : 0u) | (r->act.d.ring ? LPVMPC_SNAP_HAS_ACTUATOR : 0u) |
-                 (r->dist.d.rows ? LPVMPC_SNAP_HAS_DISTURBANCES : 0u) | (h->trk.tab ? LPVMPC_SNAP_HAS_TRACKS : 0u);
+    s.features = (d.estv ? LPVMPC_SNAP_HAS_ESTIMATOR : 0u) | (r->side.act.d.ring ? LPVMPC_SNAP_HAS_ACTUATOR : 0u) |
+                 (r->side.dist.d.rows ? LPVMPC_SNAP_HAS_DISTURBANCES : 0u) | (h->trk.tab ? LPVMPC_SNAP_HAS_TRACKS : 0u);
     auto add = [&s](const char *name, void *ptr, int type, int W, int layout = STATE_VEHICLE_MAJOR) {
         RaceStateDesc e{};
         std::strncpy(e.name, name, 15);
@@ -299,12 +282,12 @@ bool lpvmpc_race_state(lpvmpc_handle *h, RaceState &s) {
     add("plan.xlast", p->d_xlast, STATE_F64, Np * 6); add("plan.delta", p->d_delta, STATE_F64, Np);
     add("plan.iters", p->d_iters, STATE_I32, 1); add("plan.status", p->d_status, STATE_I32, 1); add("plan.polish", p->d_polish, STATE_I32, 1);
     // actuator, estimator, disturbances
-    if (r->act.d.ring) {
-        add("act.ring", r->act.d.ring, STATE_F64, 2 * kActRing, STATE_WORD_MAJOR);
-        add("act.servo", r->act.d.servo, STATE_F64, 1); add("act.k", r->act.d.k, STATE_I32, 1);
+    if (r->side.act.d.ring) {
+        add("act.ring", r->side.act.d.ring, STATE_F64, 2 * kActRing, STATE_WORD_MAJOR);
+        add("act.servo", r->side.act.d.servo, STATE_F64, 1); add("act.k", r->side.act.d.k, STATE_I32, 1);
     }
     if (d.estv) add("obs.state", h->obs_state, STATE_F64, kObsStride);
-    if (r->dist.d.rows) add("dist.state", r->dist.d.state, STATE_F64, kDistState, STATE_WORD_MAJOR);
+    if (r->side.dist.d.rows) add("dist.state", r->side.dist.d.state, STATE_F64, kDistState, STATE_WORD_MAJOR);
     return true;
 }
 void lpvmpc_race_set_ticks(lpvmpc_handle *h, int ticks) { if (h->race) h->race->ticks = ticks; }
@@ -315,20 +298,6 @@ bool lpvmpc_race_heats_view(lpvmpc_handle *h, RaceHeatsView &v) {
     v.B = r->d.B; v.laps = r->d.laps; v.hw = r->d.hw; v.slack = r->d.slack; v.plant = r->d.plant; v.phase = r->d.phase;
     v.slot = &r->heats;
     return true;
-}
-
-// the race's actuator state and its two controllers' histories (lpvmpc_actuator_read)
-int lpvmpc_race_act_read(lpvmpc_handle *h, double *act_state, double *path_hist, double *tt_hist) {
-    lpvmpc_race *r = h->race;
-    if (!r->actuated) return fail(h, LPVMPC_E_ARG, "lpvmpc_actuator_read: the race was not started by lpvmpc_race_init_actuated");
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = h->stream;
-    const size_t n = (size_t)r->d.B * (2 + r->sd) * 8;
-    if (path_hist) D2H(path_hist, r->d.p_uold, n);
-    if (tt_hist) D2H(tt_hist, r->d.t_uold, n);
-    if (act_state) { int rc = lpvmpc_act_download(h, r->act.d, act_state, st); if (rc) return rc; }
-    HIP_TRY(h, hipStreamSynchronize(st));
-    return LPVMPC_OK;
 }
 
 extern "C" int lpvmpc_race_init_observed(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, int32_t B, const double *plant0,
@@ -346,6 +315,12 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
     const lpvmpc::RaceDev &d = r->d;
     const int B = d.B, N = d.N;
     hipStream_t st = h->stream;
+    // the kernels of the race's form (step_form.hpp)
+    const PlantSide &side = r->side;
+    const lpvmpc::StepForm form = lpvmpc_step_form(h, side, &d);
+    lpvmpc::RaceMeasureFn *measure = lpvmpc::race_measure_launcher(form);
+    lpvmpc::RaceStepFn *step = lpvmpc::race_step_launcher(form);
+    if (!measure || !step) return fail(h, LPVMPC_E_ARG, "lpvmpc_race_tick: internal error: no kernel for step form 0x%x", form);
     for (int t = 0; t < n_ticks; ++t) {
         // planner ticks of the racing vehicles whose controller tick reads a new message (PMAIN:126-224, 257-308)
         // bound (lpvmpc_set_tracks on all three handles, equal): every kernel that reads the track takes its bound form
@@ -364,9 +339,7 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
         HIP_TRY(h, lpvmpc::launch_resample(B, d.Np, d.M, p->d_Wop, p->d_FWop, d.sig, d.refs, st, d.m_plan));
         // measurement, lap logic, masks of the two controllers
         const int seed = r->ticks < 9;
-        if (trk) HIP_TRY(h, lpvmpc::launch_race_measure_trk(h->d_cfg, *trk, d, seed, r->sd, st));
-        else if (r->actuated) HIP_TRY(h, lpvmpc::launch_race_measure_act(h->d_cfg, d, seed, r->sd, st));
-        else HIP_TRY(h, lpvmpc::launch_race_measure(h->d_cfg, d, seed, st));
+        HIP_TRY(h, measure(lpvmpc::RaceMeasureArgs{h->d_cfg, trk, d, seed, r->sd}, st));
         // path controller (CMAIN:310-336)
         const double *x0 = d.local; int x0_stride = 6;
         if (seed) {                                                          // scratch only: unmasked
@@ -388,24 +361,8 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
                      tt->d_resid, nullptr, 0, 6};
         ta.active = d.m_tt;
         rc = lpvmpc_launch_solve_timed(tt, ta, st); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
-        if (r->dist.d.rows) HIP_TRY(h, lpvmpc::launch_disturbance(h->d_cfg, trk, r->dist.d, st));   // lpvmpc_set_disturbances
-        if (r->fault.d.rows && h->ov.L)                                      // lpvmpc_set_sensor_faults: in place of the tyre forms' kernel
-            HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_faulted_obsveh(d, tyre_plant(r->veh, r->tyre), lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, r->act.d, r->fault.d, st));
-        else if (r->fault.d.rows)
-            HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_faulted(d, tyre_plant(r->veh, r->tyre), h->obs_gains, h->obs_state, h->obs_p, r->act.d, r->fault.d, st));
-        else if (r->tyre.t && d.estv && h->ov.L)
-            HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_tyre_obsveh(d, tyre_plant(r->veh, r->tyre), lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, r->act.d, st));
-        else if (r->veh.d.p && d.estv && h->ov.L)
-            HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_veh_obsveh(d, r->veh.d, lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, r->act.d, st));
-        else if (r->tyre.t && d.estv)
-            HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_tyre(d, tyre_plant(r->veh, r->tyre), h->obs_gains, h->obs_state, h->obs_p, r->act.d, st));
-        else if (r->tyre.t) HIP_TRY(h, lpvmpc::launch_race_command_plant_tyre(d, tyre_plant(r->veh, r->tyre), r->act.d, st));
-        else if (r->veh.d.p && d.estv) HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_veh(d, r->veh.d, h->obs_gains, h->obs_state, h->obs_p, r->act.d, st));
-        else if (r->veh.d.p) HIP_TRY(h, lpvmpc::launch_race_command_plant_veh(d, r->veh.d, r->act.d, st));
-        else if (r->actuated && d.estv) HIP_TRY(h, lpvmpc::launch_race_command_plant_observe_act(d, r->pc, h->obs_gains, h->obs_state, h->obs_p, r->act.d, st));
-        else if (r->actuated) HIP_TRY(h, lpvmpc::launch_race_command_plant_act(d, r->pc, r->act.d, st));
-        else if (d.estv) HIP_TRY(h, lpvmpc::launch_race_command_plant_observe(d, r->pc, h->obs_gains, h->obs_state, h->obs_p, st));
-        else HIP_TRY(h, lpvmpc::launch_race_command_plant(d, r->pc, st));
+        if (side.dist.d.rows) HIP_TRY(h, lpvmpc::launch_disturbance(h->d_cfg, trk, side.dist.d, st));   // lpvmpc_set_disturbances
+        HIP_TRY(h, step(lpvmpc::RaceStepArgs{d, side.pc, side.tpc(), lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, side.act.d, side.fault.d}, st));
         if (lpvmpc_race_recorder *q = r->rec.get()) {                               // the recorder (record.hip)
             int slot = -1;
             if ((r->ticks - q->t_start) % q->stride == 0) { slot = q->total % q->capacity; q->total++; }

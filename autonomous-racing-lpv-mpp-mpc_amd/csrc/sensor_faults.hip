@@ -121,31 +121,22 @@ __global__ void __launch_bounds__(64) sensor_step_kernel(typename ObsGainsArg<kO
     for (int i = 0; i < kObsStride; ++i) obs[(size_t)b * kObsStride + i] = os[i];
 }
 
-#define LPVMPC_GRID(n) dim3(((n) + 63) / 64), dim3(64)
-hipError_t launch_cl_command_plant_observe_faulted(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
-                                                   const TyrePlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
-                                                   int sd, const double *gains, double *obs, const ObsParams &op, const ActDev &a,
-                                                   const FaultDev &f, hipStream_t s) {
-    hipLaunchKernelGGL((cl_command_plant_observe_faulted_kernel<false>), LPVMPC_GRID(B), 0, s, dcfg, B, N, uPred, cmd, plant, pc, hw, slack, q9_swap,
-                       local_next, u_old, gains, obs, op, sd, a, f);
+hipError_t launch_cl_command_plant_observe_faulted(const FleetStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((cl_command_plant_observe_faulted_kernel<false>), LPVMPC_GRID(a.B), 0, s, a.dcfg, a.B, a.N, a.uPred, a.cmd, a.plant, a.tpc, a.hw, a.slack,
+                       a.q9, a.local_next, a.u_old, a.gains.g, a.obs, a.op, a.sd, a.act, a.fault);
     return hipGetLastError();
 }
-hipError_t launch_cl_command_plant_observe_faulted_obsveh(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
-                                                          const TyrePlantCfg &pc, double hw, double slack, int q9_swap, double *local_next,
-                                                          double *u_old, int sd, const ObsVehGains &gains, double *obs, const ObsParams &op,
-                                                          const ActDev &a, const FaultDev &f, hipStream_t s) {
-    hipLaunchKernelGGL((cl_command_plant_observe_faulted_kernel<true>), LPVMPC_GRID(B), 0, s, dcfg, B, N, uPred, cmd, plant, pc, hw, slack, q9_swap,
-                       local_next, u_old, gains, obs, op, sd, a, f);
+hipError_t launch_cl_command_plant_observe_faulted_obsveh(const FleetStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((cl_command_plant_observe_faulted_kernel<true>), LPVMPC_GRID(a.B), 0, s, a.dcfg, a.B, a.N, a.uPred, a.cmd, a.plant, a.tpc, a.hw, a.slack,
+                       a.q9, a.local_next, a.u_old, a.gains, a.obs, a.op, a.sd, a.act, a.fault);
     return hipGetLastError();
 }
-hipError_t launch_race_command_plant_observe_faulted(const RaceDev &r, const TyrePlantCfg &pc, const double *gains, double *obs,
-                                                     const ObsParams &op, const ActDev &a, const FaultDev &f, hipStream_t s) {
-    hipLaunchKernelGGL((race_command_plant_observe_faulted_kernel<false>), LPVMPC_GRID(r.B), 0, s, r, pc, gains, obs, op, a, f);
+hipError_t launch_race_command_plant_observe_faulted(const RaceStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((race_command_plant_observe_faulted_kernel<false>), LPVMPC_GRID(a.r.B), 0, s, a.r, a.tpc, a.gains.g, a.obs, a.op, a.act, a.fault);
     return hipGetLastError();
 }
-hipError_t launch_race_command_plant_observe_faulted_obsveh(const RaceDev &r, const TyrePlantCfg &pc, const ObsVehGains &gains, double *obs,
-                                                            const ObsParams &op, const ActDev &a, const FaultDev &f, hipStream_t s) {
-    hipLaunchKernelGGL((race_command_plant_observe_faulted_kernel<true>), LPVMPC_GRID(r.B), 0, s, r, pc, gains, obs, op, a, f);
+hipError_t launch_race_command_plant_observe_faulted_obsveh(const RaceStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((race_command_plant_observe_faulted_kernel<true>), LPVMPC_GRID(a.r.B), 0, s, a.r, a.tpc, a.gains, a.obs, a.op, a.act, a.fault);
     return hipGetLastError();
 }
 hipError_t launch_sensor_step(const ObsVehGains &v, int B, double *obs, const double *plant, const double *servo, const double *motor,

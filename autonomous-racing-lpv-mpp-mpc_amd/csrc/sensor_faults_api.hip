@@ -1,5 +1,5 @@
 // sensor_faults_api.hip -- C ABI of the sensor faults (include/lpvmpc.h, "Sensor faults"): the checks, the binding of a lap-0 fleet
-// (Fleet::cl_fault) or a race (lpvmpc_race_fault, race_api.hip), the read-back and the stand-alone sensor step.  Kernels:
+// or a race (PlantSide::fault of the running engine, lpvmpc_plant_side), the read-back and the stand-alone sensor step.  Kernels:
 // sensor_faults.hip; lpvmpc_cl_tick and lpvmpc_race_tick launch the faulted kernel in place of their fused observe kernel.
 #include <cmath>
 #include <vector>
@@ -37,19 +37,22 @@ static void fault_cfg(const lpvmpc_sensor_fault_config &c, lpvmpc::FaultDev &d) 
 
 // the binding of the fleet or race that h runs; B its size; why: what keeps it from being served (null: served)
 static FaultBinding *fault_target(lpvmpc_handle *h, int &B, const char *&why) {
+    using namespace lpvmpc;
     why = nullptr;
-    if (h->race) {
-        bool served = false;
-        FaultBinding *x = lpvmpc_race_fault(h, &B, &served);
-        if (!served) why = "the race has no estimator in the loop or no plant and tyre tables (start it through lpvmpc_race_init_tyres with an estimator configuration)";
-        return x;
+    const RaceDev *race = nullptr;
+    PlantSide *p = lpvmpc_plant_side(h, &race);
+    if (!p) return nullptr;
+    B = p->B;
+    // the faulted kernels have the general form only: the _tyres starts with an estimator (step_form.hpp: their rows)
+    const StepForm form = lpvmpc_step_form(h, *p, race);
+    const bool tables = (form & SF_TYRES) == SF_TYRES;
+    if (race) {
+        if (!(form & SF_OBS) || !tables) why = "the race has no estimator in the loop or no plant and tyre tables (start it through lpvmpc_race_init_tyres with an estimator configuration)";
     }
-    if (!h->cl_plant) return nullptr;
-    B = h->cl_B;
-    if (!h->obs_state) why = "the fleet runs on ground truth: there are no sensors (lpvmpc_observer_setup before lpvmpc_cl_init_tyres)";
-    else if (!h->cl_veh.d.p || !h->cl_tyre.t) why = "the fleet has no plant and tyre tables (start it through lpvmpc_cl_init_tyres: the faulted kernel has the general form only)";
-    else if (h->trk.tab) why = "the fleet has per-vehicle tracks bound (lpvmpc_set_tracks): the faulted kernel has no track form (a race with tracks is served)";
-    return &h->cl_fault;
+    else if (!(form & SF_OBS)) why = "the fleet runs on ground truth: there are no sensors (lpvmpc_observer_setup before lpvmpc_cl_init_tyres)";
+    else if (!tables) why = "the fleet has no plant and tyre tables (start it through lpvmpc_cl_init_tyres: the faulted kernel has the general form only)";
+    else if (form & SF_TRK) why = "the fleet has per-vehicle tracks bound (lpvmpc_set_tracks): the faulted kernel has no track form (a race with tracks is served)";
+    return &p->fault;
 }
 
 extern "C" int lpvmpc_set_sensor_faults(lpvmpc_handle *h, int32_t B, const lpvmpc_sensor_fault_config *cfg, const double *rows) {

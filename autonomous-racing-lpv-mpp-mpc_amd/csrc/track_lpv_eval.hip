@@ -234,7 +234,6 @@ __global__ void __launch_bounds__(64) plan_abc_trk_kernel(const DevCfg *__restri
     plan_abc_body(c, track_view(trk, t / N), load_model(model, B, t / N), t, xlast, delta, AB);
 }
 
-#define LPVMPC_GRID(n) dim3(((n) + 63) / 64), dim3(64)
 void launch_ctrl_lpv_roll_trk(const DevCfg *dcfg, const TrackDev &trk, int B, const double *x0, const double *u_prev, const double *curv_ref,
                               int lap, double *states, double *AB, hipStream_t stream, const int32_t *active) {
     hipLaunchKernelGGL(ctrl_lpv_roll_trk_kernel, LPVMPC_GRID(B), 0, stream, dcfg, trk, B, x0, u_prev, curv_ref, lap, states, AB, active);

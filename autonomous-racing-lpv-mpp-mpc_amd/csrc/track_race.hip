@@ -209,13 +209,12 @@ __global__ void __launch_bounds__(64) race_record_trk_kernel(TrackDev trk, RecDe
     si[LPVMPC_LAPSTAT_OFF_TRACK] += inside == 0;
 }
 
-#define LPVMPC_GRID(n) dim3(((n) + 63) / 64), dim3(64)
 hipError_t launch_race_plan_start_trk(const DevCfg *pcfg, const TrackDev &trk, const RaceDev &r, hipStream_t s) {
     hipLaunchKernelGGL(race_plan_start_trk_kernel, LPVMPC_GRID(r.B), 0, s, pcfg, trk, r);
     return hipGetLastError();
 }
-hipError_t launch_race_measure_trk(const DevCfg *ccfg, const TrackDev &trk, const RaceDev &r, int seed_tick, int sd, hipStream_t s) {
-    hipLaunchKernelGGL(race_measure_trk_kernel, LPVMPC_GRID(r.B), 0, s, ccfg, trk, r, seed_tick, sd);
+hipError_t launch_race_measure_trk(const RaceMeasureArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(race_measure_trk_kernel, LPVMPC_GRID(a.r.B), 0, s, a.ccfg, *a.trk, a.r, a.seed_tick, a.sd);
     return hipGetLastError();
 }
 hipError_t launch_plan_pose_trk(const DevCfg *dcfg, const TrackDev &trk, int B, const double *xPred, double *SS, double *pose, double *sig,

@@ -117,37 +117,29 @@ __global__ void __launch_bounds__(64) cl_command_plant_observe_trk_kernel(TrackD
     uold_push(u_old + (size_t)b * (2 + sd), sd, servo, motor);
 }
 
-#define LPVMPC_GRID(n) dim3(((n) + 63) / 64), dim3(64)
-hipError_t launch_cl_measure_trk(const TrackDev &trk, int B, const double *plant, const double *cmd, int q9_swap, double *local_state,
-                                 double *u_old, int sd, hipStream_t s) {
-    hipLaunchKernelGGL(cl_measure_trk_kernel, LPVMPC_GRID(B), 0, s, trk, B, plant, cmd, q9_swap, local_state, u_old, sd);
+hipError_t launch_cl_measure_trk(const FleetMeasureArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(cl_measure_trk_kernel, LPVMPC_GRID(a.B), 0, s, *a.trk, a.B, a.plant, a.cmd, a.q9, a.local_state, a.u_old, a.sd);
     return hipGetLastError();
 }
-hipError_t launch_cl_command_plant_measure_trk(const TrackDev &trk, int B, int N, const double *uPred, double *cmd, double *plant,
-                                               const TyrePlantCfg &pc, int q9_swap, double *local_next, double *u_old, int sd,
-                                               const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL(cl_command_plant_measure_trk_kernel, LPVMPC_GRID(B), 0, s, trk, B, N, uPred, cmd, plant, pc, q9_swap, local_next, u_old, sd, a);
+hipError_t launch_cl_command_plant_measure_trk(const FleetStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(cl_command_plant_measure_trk_kernel, LPVMPC_GRID(a.B), 0, s, *a.trk, a.B, a.N, a.uPred, a.cmd, a.plant, a.tpc, a.q9, a.local_next,
+                       a.u_old, a.sd, a.act);
     return hipGetLastError();
 }
-hipError_t launch_cl_observe_measure_trk(const TrackDev &trk, int B, const double *obs, const double *cmd, int q9_swap, double *local_state,
-                                         double *u_old, int sd, hipStream_t s) {
-    hipLaunchKernelGGL(cl_command_plant_observe_trk_kernel<false>, LPVMPC_GRID(B), 0, s, trk, B, 1, (const double *)nullptr, const_cast<double *>(cmd),
-                       (double *)nullptr, TyrePlantCfg{}, q9_swap, local_state, u_old, (const double *)nullptr, const_cast<double *>(obs),
-                       ObsParams{}, 0, sd, ActDev{});
+hipError_t launch_cl_observe_measure_trk(const FleetMeasureArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(cl_command_plant_observe_trk_kernel<false>, LPVMPC_GRID(a.B), 0, s, *a.trk, a.B, 1, (const double *)nullptr, const_cast<double *>(a.cmd),
+                       (double *)nullptr, TyrePlantCfg{}, a.q9, a.local_state, a.u_old, (const double *)nullptr, const_cast<double *>(a.obs),
+                       ObsParams{}, 0, a.sd, ActDev{});
     return hipGetLastError();
 }
-hipError_t launch_cl_command_plant_observe_trk(const TrackDev &trk, int B, int N, const double *uPred, double *cmd, double *plant,
-                                               const TyrePlantCfg &pc, int q9_swap, double *local_next, double *u_old, int sd,
-                                               const double *gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL(cl_command_plant_observe_trk_kernel<false>, LPVMPC_GRID(B), 0, s, trk, B, N, uPred, cmd, plant, pc, q9_swap, local_next, u_old,
-                       gains, obs, op, 1, sd, a);
+hipError_t launch_cl_command_plant_observe_trk(const FleetStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(cl_command_plant_observe_trk_kernel<false>, LPVMPC_GRID(a.B), 0, s, *a.trk, a.B, a.N, a.uPred, a.cmd, a.plant, a.tpc, a.q9, a.local_next,
+                       a.u_old, a.gains.g, a.obs, a.op, 1, a.sd, a.act);
     return hipGetLastError();
 }
-hipError_t launch_cl_command_plant_observe_trk_obsveh(const TrackDev &trk, int B, int N, const double *uPred, double *cmd, double *plant,
-                                                      const TyrePlantCfg &pc, int q9_swap, double *local_next, double *u_old, int sd,
-                                                      const ObsVehGains &gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL(cl_command_plant_observe_trk_kernel<true>, LPVMPC_GRID(B), 0, s, trk, B, N, uPred, cmd, plant, pc, q9_swap, local_next, u_old,
-                       gains, obs, op, 1, sd, a);
+hipError_t launch_cl_command_plant_observe_trk_obsveh(const FleetStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(cl_command_plant_observe_trk_kernel<true>, LPVMPC_GRID(a.B), 0, s, *a.trk, a.B, a.N, a.uPred, a.cmd, a.plant, a.tpc, a.q9, a.local_next,
+                       a.u_old, a.gains, a.obs, a.op, 1, a.sd, a.act);
     return hipGetLastError();
 }
 hipError_t launch_local_position_trk(const TrackDev &trk, int B, const double *xypsi, double *out, hipStream_t s) {

@@ -7,33 +7,27 @@
 
 namespace lpvmpc {
 
-#define LPVMPC_GRID(n) dim3(((n) + 63) / 64), dim3(64)
-hipError_t launch_plant_tyre(int B, double *plant, const double *u, const TyrePlantCfg &pc, const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL((plant_kernel<true, true, true>), LPVMPC_GRID(B), 0, s, B, plant, u, pc, a);
+hipError_t launch_plant_tyre(const PlantStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((plant_kernel<true, true, true>), LPVMPC_GRID(a.B), 0, s, a.B, a.plant, a.u, a.tpc, a.act);
     return hipGetLastError();
 }
-hipError_t launch_cl_command_plant_measure_tyre(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
-                                                const TyrePlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
-                                                int sd, const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL((cl_command_plant_measure_kernel<true, true, true>), LPVMPC_GRID(B), 0, s, dcfg, B, N, uPred, cmd, plant, pc, hw, slack,
-                       q9_swap, local_next, u_old, sd, a);
+hipError_t launch_cl_command_plant_measure_tyre(const FleetStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((cl_command_plant_measure_kernel<true, true, true>), LPVMPC_GRID(a.B), 0, s, a.dcfg, a.B, a.N, a.uPred, a.cmd, a.plant, a.tpc, a.hw, a.slack,
+                       a.q9, a.local_next, a.u_old, a.sd, a.act);
     return hipGetLastError();
 }
-hipError_t launch_cl_command_plant_observe_tyre(const DevCfg *dcfg, int B, int N, const double *uPred, double *cmd, double *plant,
-                                                const TyrePlantCfg &pc, double hw, double slack, int q9_swap, double *local_next, double *u_old,
-                                                int sd, const double *gains, double *obs, const ObsParams &op, const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL((cl_command_plant_observe_kernel<true, true, true>), LPVMPC_GRID(B), 0, s, dcfg, B, N, uPred, cmd, plant, pc, hw, slack,
-                       q9_swap, local_next, u_old, gains, obs, op, 1, sd, a);
+hipError_t launch_cl_command_plant_observe_tyre(const FleetStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((cl_command_plant_observe_kernel<true, true, true>), LPVMPC_GRID(a.B), 0, s, a.dcfg, a.B, a.N, a.uPred, a.cmd, a.plant, a.tpc, a.hw, a.slack,
+                       a.q9, a.local_next, a.u_old, a.gains.g, a.obs, a.op, 1, a.sd, a.act);
     return hipGetLastError();
 }
 
-hipError_t launch_race_command_plant_tyre(const RaceDev &r, const TyrePlantCfg &pc, const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL((race_command_plant_kernel<true, true, true>), LPVMPC_GRID(r.B), 0, s, r, pc, a);
+hipError_t launch_race_command_plant_tyre(const RaceStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((race_command_plant_kernel<true, true, true>), LPVMPC_GRID(a.r.B), 0, s, a.r, a.tpc, a.act);
     return hipGetLastError();
 }
-hipError_t launch_race_command_plant_observe_tyre(const RaceDev &r, const TyrePlantCfg &pc, const double *gains, double *obs, const ObsParams &op,
-                                                 const ActDev &a, hipStream_t s) {
-    hipLaunchKernelGGL((race_command_plant_observe_kernel<true, true, true>), LPVMPC_GRID(r.B), 0, s, r, pc, gains, obs, op, a);
+hipError_t launch_race_command_plant_observe_tyre(const RaceStepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((race_command_plant_observe_kernel<true, true, true>), LPVMPC_GRID(a.r.B), 0, s, a.r, a.tpc, a.gains.g, a.obs, a.op, a.act);
     return hipGetLastError();
 }
 

@@ -63,17 +63,15 @@ extern "C" int lpvmpc_race_init_tyres(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmp
 // device [4][B] -> host [B][4]
 extern "C" int lpvmpc_tyre_params_read(lpvmpc_handle *h, double *tyre_params) {
     const char *who = "lpvmpc_tyre_params_read";
-    const double *t = nullptr;
-    size_t B = 0;
-    if (h && h->race) { t = lpvmpc_race_tyre(h); B = lpvmpc_race_plant(h)->B; }
-    else if (h && h->cl_plant) { t = h->cl_tyre.t; B = h->cl_B; }
+    const PlantSide *side = lpvmpc_plant_side(h);
+    const double *t = side ? side->tyre.t : nullptr;
     if (!t) return fail(h, LPVMPC_E_ARG, "%s: no fleet or race started by lpvmpc_cl_init_tyres / lpvmpc_race_init_tyres", who);
     if (!tyre_params) return fail(h, LPVMPC_E_ARG, "%s: tyre_params is NULL", who);
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t st = h->stream;
+    const size_t B = side->B;
     std::vector<double> v(B * LPVMPC_TYRE_WORDS);
-    const DistBinding *dist = h->race ? lpvmpc_race_dist(h, nullptr) : &h->cl_dist;
-    if (dist && dist->d.rows) v = dist->base_t;                      // disturbances attached: the base rows, not the scaled live words
+    if (side->dist.d.rows) v = side->dist.base_t;                        // disturbances attached: the base rows, not the scaled live words
     else D2H(v.data(), t, v.size() * 8);
     HIP_TRY(h, hipStreamSynchronize(st));
     for (size_t b = 0; b < B; ++b)

@@ -284,7 +284,6 @@ __global__ void __launch_bounds__(64) plan_abc_veh_kernel(const DevCfg *__restri
     plan_abc_body(c, load_model(model, B, t / N), t, xlast, delta, AB);
 }
 
-#define LPVMPC_GRID(n) dim3(((n) + 63) / 64), dim3(64)
 void launch_ctrl_lpv_pre_veh(const DevCfg *dcfg, const double *model, int B, int N, const double *u_prev, const double *vel_ref, double *AB,
                              hipStream_t stream, const int32_t *active) {
     hipLaunchKernelGGL(ctrl_lpv_pre_veh_kernel, LPVMPC_GRID(B * N), 0, stream, dcfg, model, B, u_prev, vel_ref, AB, active);
