@@ -118,6 +118,20 @@ HEAT_CARRY_I32_NAMES = ("flags", "turns", "turns0", "crossings", "phase", "finis
                         "passed")
 
 
+class InteractionConfig(C.Structure):
+    """Mirror of ``struct lpvmpc_interaction_config`` (include/lpvmpc.h)."""
+    _fields_ = [("draft_gain", _d), ("wake_length", _d), ("wake_half_width", _d), ("contact", _i), ("reserved", _i), ("restitution", _d),
+                ("push", _d)]
+
+
+# interactions (LPVMPC_INTER_*): outputs f64 [INTER_F64][B] / i32 [INTER_I32][B] and the carried state of the batch form, in channel order
+INTER_F64, INTER_I32, INTER_CARRY_F64, INTER_CARRY_I32 = 4, 5, 1, 3
+INTER_F64_NAMES = ("shelter", "mu", "impulse", "impulse_total")
+INTER_I32_NAMES = ("leader", "hit", "hit_ticks", "first_hit_tick", "draft_ticks")
+INTER_CARRY_F64_NAMES = ("impulse_total",)
+INTER_CARRY_I32_NAMES = ("hit_ticks", "first_hit_tick", "draft_ticks")
+
+
 # race recorder channels (LPVMPC_REC_*): f64 [REC_F64][B] and i32 [REC_I32][B] per record, named in channel order
 REC_F64, REC_I32 = 29, 8
 REC_PLANT, REC_LOCAL, REC_CMD, REC_REF, REC_TRACK, REC_EST = 0, 8, 14, 16, 20, 23
@@ -188,7 +202,8 @@ EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_d
            "lpvmpc_plant_step_disturbed_batch",
            "lpvmpc_race_snapshot_size", "lpvmpc_race_snapshot", "lpvmpc_race_restore", "lpvmpc_race_clone",
            "lpvmpc_heats_default_config", "lpvmpc_race_heats", "lpvmpc_race_standings", "lpvmpc_heat_step_batch",
-           "lpvmpc_sensor_fault_default_config", "lpvmpc_set_sensor_faults", "lpvmpc_sensor_faults_read", "lpvmpc_sensor_step_batch")
+           "lpvmpc_sensor_fault_default_config", "lpvmpc_set_sensor_faults", "lpvmpc_sensor_faults_read", "lpvmpc_sensor_step_batch",
+           "lpvmpc_interaction_default_config", "lpvmpc_race_interactions", "lpvmpc_race_interactions_read", "lpvmpc_interaction_step_batch")
 
 _lib = None
 
@@ -417,6 +432,16 @@ def load():
             getattr(lib, name).restype = C.c_int
     except AttributeError:
         pass
+    try:        # (nor the interactions)
+        lib.lpvmpc_interaction_default_config.argtypes = [P(InteractionConfig)]
+        lib.lpvmpc_interaction_default_config.restype = None
+        lib.lpvmpc_race_interactions.argtypes = [vp, P(InteractionConfig)]
+        lib.lpvmpc_race_interactions_read.argtypes = [vp, vp, vp]
+        lib.lpvmpc_interaction_step_batch.argtypes = [vp, _i, _i, vp, P(HeatsConfig), P(InteractionConfig), _i, vp, vp, vp, vp, vp, vp, vp, vp]
+        for name in ("lpvmpc_race_interactions", "lpvmpc_race_interactions_read", "lpvmpc_interaction_step_batch"):
+            getattr(lib, name).restype = C.c_int
+    except AttributeError:
+        pass
     for name in ("lpvmpc_handoff_length", "lpvmpc_handoff_operators", "lpvmpc_handoff_setup", "lpvmpc_handoff_batch",
                  "lpvmpc_cascade_init", "lpvmpc_cascade_tick", "lpvmpc_cascade_read"):
         getattr(lib, name).restype = C.c_int
@@ -469,6 +494,12 @@ def default_disturbance_config():
 def default_sensor_fault_config():
     cfg = SensorFaultConfig()
     load().lpvmpc_sensor_fault_default_config(C.byref(cfg))
+    return cfg
+
+
+def default_interaction_config():
+    cfg = InteractionConfig()
+    load().lpvmpc_interaction_default_config(C.byref(cfg))
     return cfg
 
 

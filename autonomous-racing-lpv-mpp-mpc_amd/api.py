@@ -988,6 +988,61 @@ class BatchedSolver:
             out.update(line_tick=lt, line_pos=lp)
         return H.standings_dict(f, i, lt, lp), out
 
+    # -- interactions: slipstream and contact response within a heat (lpvmpc_race_interactions / _read, lpvmpc_interaction_step_batch;
+    # interactions.py) --------------------------------------------------------------------------------------------------------
+    def race_interactions(self, cfg=None, detach=False):
+        """Attach the interactions from the next tick on (lpvmpc_race_interactions): ``cfg`` an ``interactions.interaction_config(...)``
+        result, a dict of its words, or None for the defaults.  Needs heats attached (``race_heats``) and a race started with
+        ``plant_params`` / ``tyre_params``.  Attaching again replaces the binding; ``detach=True`` detaches and puts the base mu words
+        back into the live plant table.  ``race_heats`` detaches the interactions, whether it re-attaches or detaches the heats."""
+        from . import interactions as I
+        self._race_B("race_interactions")
+        if detach:
+            self._chk(self._lib.lpvmpc_race_interactions(self._h, None))
+            return
+        c = I.as_config(cfg)
+        self._chk(self._lib.lpvmpc_race_interactions(self._h, C.byref(c)))
+
+    def race_interactions_read(self):
+        """Synchronise and return the interactions' outputs (lpvmpc_race_interactions_read): a dict of [B] arrays named as
+        _ffi.INTER_F64_NAMES / INTER_I32_NAMES (shelter, mu, impulse, impulse_total; leader, hit, hit_ticks, first_hit_tick,
+        draft_ticks) and the planes f64 [4, B] / i32 [5, B].  A vehicle in no heat reads NaN and leader -1."""
+        from . import interactions as I
+        B = self._race_B("race_interactions_read")
+        f = np.empty((_ffi.INTER_F64, B)); i = np.empty((_ffi.INTER_I32, B), np.int32)
+        self._chk(self._lib.lpvmpc_race_interactions_read(self._h, ptr(f), ptr(i)))
+        return I.interactions_dict(f, i)
+
+    def interaction_step(self, heat, plant, plant_params, t, cfg=None, nstep=None, carry=None, n_heats=None, half_length=0.4, half_width=0.2):
+        """One tick of the interactions' kernel on the caller's data (lpvmpc_interaction_step_batch): ``heat`` [B] (-1: none), ``plant``
+        [B, 8], ``plant_params`` [B, 7] (m and mu are read), ``t`` the tick number, ``cfg`` as ``race_interactions``, ``nstep`` [B] the
+        simulator steps of this tick (None: every vehicle steps; 0: frozen), ``carry`` the state returned by the previous call (None:
+        ``interactions.new_carry(B)``), ``half_length`` / ``half_width`` the heats' footprint.  Returns (plant [B, 8] after the tick,
+        mu_live [B], outputs dict, carry)."""
+        from . import heats as H, interactions as I
+        plant = f64(plant).copy()
+        if plant.ndim != 2 or plant.shape[1] != 8:
+            raise ValueError("interaction_step: plant must be [B, 8], got %s" % (plant.shape,))
+        B = plant.shape[0]
+        rows = f64(plant_params, (B, _ffi.PLANT_WORDS), "plant_params")
+        hl, hw = H.check_extents(half_length, half_width)
+        hcfg = _ffi.HeatsConfig(hl, hw)
+        c = I.as_config(cfg)
+        h = H.check_heats(heat, B)
+        n = int(h.max()) + 1 if n_heats is None else int(n_heats)
+        ns = None if nstep is None else np.ascontiguousarray(np.asarray(nstep).reshape(-1), np.int32)
+        if ns is not None and ns.shape[0] != B:
+            raise ValueError("interaction_step: nstep must have one entry per vehicle (%d)" % B)
+        k = I.new_carry(B) if carry is None else carry
+        cf = f64(k["f64"], (_ffi.INTER_CARRY_F64, B), "carry f64").copy()
+        ci = np.ascontiguousarray(k["i32"], np.int32).copy()
+        if ci.shape != (_ffi.INTER_CARRY_I32, B):
+            raise ValueError("interaction_step: carry i32 has shape %s, expected %s" % (ci.shape, (_ffi.INTER_CARRY_I32, B)))
+        f = np.empty((_ffi.INTER_F64, B)); i = np.empty((_ffi.INTER_I32, B), np.int32); mu = np.empty(B)
+        self._chk(self._lib.lpvmpc_interaction_step_batch(self._h, B, n, ptr(h), C.byref(hcfg), C.byref(c), int(t), ptr(plant), ptr(rows), ptr(ns),
+                                                          ptr(cf), ptr(ci), ptr(mu), ptr(f), ptr(i)))
+        return plant, mu, I.interactions_dict(f, i), dict(f64=cf, i32=ci)
+
     # -- device-pointer entry point (torch tensors or raw integers) -----------------------------------
     def solve_dev(self, B, x0, u_prev, vel_ref, curv_s, u_old, max_ey, xPred, uPred, status=None, iters=None,
                   resid=None, polish=None, cf_new=60.0, lap=1, stream=0):
@@ -1370,13 +1425,20 @@ class RaceFleet(object):
     mid-race, ``disturbance()`` reads rows and state back); it selects ``tyre_params="linear"`` when none is given.
     ``sensor_faults`` (with ``estimator``): [B, 12] rows (sensor_faults.fault_rows, sensor_faults.sample_faults) or dict(rows=, seed=,
     vehicle_offset=): GPS loss and jumps, IMU bias and drift, a slipping or stuck encoder from the first tick on (``fault`` attaches or
-    detaches mid-race, ``faults()`` reads the rows back); it selects ``tyre_params="linear"`` when none is given."""
+    detaches mid-race, ``faults()`` reads the rows back); it selects ``tyre_params="linear"`` when none is given.
+    ``heats``: heat [B] (-1: none) or dict(heat=, turns0=, half_length=, half_width=): heats attached from the first tick on (``heats``
+    attaches or detaches mid-race, ``standings()`` reads them).  ``interactions`` (with ``heats``): True for the defaults, an
+    ``interactions.interaction_config(...)`` result or a dict of its words: slipstream and contact response between the members of a
+    heat from the first tick on (``interact`` attaches or detaches mid-race, ``interactions()`` reads the outputs back); it selects
+    ``tyre_params="linear"`` when none is given."""
 
     def __init__(self, track_map, plant0, laps=1, N=20, Np=40, half_track0=None, device=0, estimator=None, actuator=None,
                  steering_delay=0, delay_a=None, delay_df=None, plant_params=None, model_params=None, path_tunings=None,
                  tt_tunings=None, plan_tunings=None, tyre_params=None, estimator_params=None, estimator_design=None, track_of=None,
-                 disturbance=None, sensor_faults=None, **options):
+                 disturbance=None, sensor_faults=None, heats=None, interactions=None, **options):
         from .workloads import CTRL_TUNINGS, PLAN_L, PLAN_Q, PLAN_R, PLAN_dR
+        if interactions is not None and interactions is not False and heats is None:
+            raise ValueError("interactions needs heats: the vehicles of a heat act on each other")
         race_keys = ("n_sub_lap0", "n_sub", "q9_swap", "plan_max_ey", "dt_sim", "mu_sim")
         race_opts = {k: v for k, v in options.items() if k in race_keys}
         engine_opts = {k: v for k, v in options.items() if k not in race_keys}
@@ -1443,6 +1505,9 @@ class RaceFleet(object):
             tyre_params = "linear"                               # the start whose tables the disturbances scale
         if sensor_faults is not None and tyre_params is None:
             tyre_params = "linear"                               # the start whose fused kernel has a faulted form
+        if interactions is not None and interactions is not False:
+            if tyre_params is None:
+                tyre_params = "linear"                           # the start whose plant table holds the masses and the drag words
         self.path.race_init(self.tt, self.planner, plant0, half_track0=half_track0, laps=laps, half_width=track_map.halfWidth,
                             slack=track_map.slack, estimator=estimator, actuator=actuator, delay_a=delay_a, delay_df=delay_df,
                             plant_params=plant_params, tyre_params=tyre_params, **race_opts)
@@ -1450,6 +1515,10 @@ class RaceFleet(object):
             self.disturb(**disturbance) if isinstance(disturbance, dict) else self.disturb(disturbance)
         if sensor_faults is not None:
             self.fault(**sensor_faults) if isinstance(sensor_faults, dict) else self.fault(sensor_faults)
+        if heats is not None:
+            self.heats(**heats) if isinstance(heats, dict) else self.heats(heats)
+        if interactions is not None and interactions is not False:
+            self.interact(None if interactions is True else interactions)
 
     def fault(self, rows, seed=0, vehicle_offset=0):
         """Attach sensor faults from the next tick on (BatchedSolver.set_sensor_faults on the path engine); ``None`` detaches."""
@@ -1534,6 +1603,16 @@ class RaceFleet(object):
     def standings(self):
         """The standings of the attached heats (BatchedSolver.race_standings); ``telemetry.standings_table`` prints them."""
         return self.path.race_standings()
+
+    def interact(self, cfg=None, detach=False):
+        """Attach the interactions from the next tick on (BatchedSolver.race_interactions): slipstream and contact response between the
+        members of the attached heats.  ``cfg``: None (the defaults), a dict of words or an ``interactions.interaction_config(...)``
+        result; ``interact(detach=True)`` detaches.  ``heats(...)`` detaches them too."""
+        self.path.race_interactions(cfg, detach=detach)
+
+    def interactions(self):
+        """The outputs of the attached interactions (BatchedSolver.race_interactions_read): shelter, live mu, impulses, leader, hits."""
+        return self.path.race_interactions_read()
 
     def snapshot(self):
         """The race's whole per-vehicle state and tick counter (BatchedSolver.race_snapshot): a ``snapshot.RaceSnapshot`` with

@@ -131,6 +131,8 @@ extern "C" int lpvmpc_set_disturbances(lpvmpc_handle *h, int32_t B, const lpvmpc
         D2H(x.base_p.data(), t.live_p, x.base_p.size() * 8);
         D2H(x.base_t.data(), t.live_t, x.base_t.size() * 8);
         HIP_TRY(h, hipStreamSynchronize(st));
+        if (const std::vector<double> *mu = lpvmpc_race_mu_base(h))        // interactions attached: the live mu words are theirs
+            for (size_t b = 0; b < n; ++b) x.base_p[6 * n + b] = (*mu)[b];
     }
     x.d = t;
     dist_cfg(c, x.d);

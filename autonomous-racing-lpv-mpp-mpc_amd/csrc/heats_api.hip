@@ -9,10 +9,8 @@
 
 #include "heats_host.hpp"
 
-namespace {
-
 // member lists of the heats: off [n_heats + 1], members in ascending vehicle index within each heat (a counting sort keeps the order)
-int heat_members(lpvmpc_handle *h, const char *who, int B, int n_heats, const int32_t *heat, std::vector<int32_t> &off, std::vector<int32_t> &members,
+int lpvmpc_heat_members(lpvmpc_handle *h, const char *who, int B, int n_heats, const int32_t *heat, std::vector<int32_t> &off, std::vector<int32_t> &members,
                  int &largest) {
     off.assign((size_t)n_heats + 1, 0);
     for (int b = 0; b < B; ++b) {
@@ -33,12 +31,14 @@ int heat_members(lpvmpc_handle *h, const char *who, int B, int n_heats, const in
     return LPVMPC_OK;
 }
 
-int check_extents(lpvmpc_handle *h, const char *who, const lpvmpc_heats_config *cfg) {
+int lpvmpc_heat_extents(lpvmpc_handle *h, const char *who, const lpvmpc_heats_config *cfg) {
     if (!cfg) return fail(h, LPVMPC_E_ARG, "%s: the heats configuration is NULL", who);
     if (!(std::isfinite(cfg->half_length) && cfg->half_length > 0 && std::isfinite(cfg->half_width_car) && cfg->half_width_car > 0))
         return fail(h, LPVMPC_E_ARG, "%s: half_length = %g, half_width_car = %g must be finite and > 0", who, cfg->half_length, cfg->half_width_car);
     return LPVMPC_OK;
 }
+
+namespace {
 
 // what a vehicle in no heat reads, and every vehicle before the first tick (a member's turns then reads its turns0)
 void blank_standings(size_t B, const int32_t *heat, const int32_t *turns0, std::vector<double> &f, std::vector<int32_t> &i) {
@@ -63,7 +63,7 @@ extern "C" int lpvmpc_race_heats(lpvmpc_handle *h, const lpvmpc_heats_config *cf
     std::vector<int32_t> off, members;
     int largest = 0, n_heats = 0;
     if (heat) {                                                                 // every check before the old attachment goes
-        int rc = check_extents(h, who, cfg); if (rc) return rc;
+        int rc = lpvmpc_heat_extents(h, who, cfg); if (rc) return rc;
         // indices need not be dense: the heats in use, in ascending order, take the workgroups of the launch (an empty heat takes none)
         std::vector<int32_t> ids;
         for (int b = 0; b < v.B; ++b) {
@@ -80,7 +80,7 @@ extern "C" int lpvmpc_race_heats(lpvmpc_handle *h, const lpvmpc_heats_config *cf
         std::vector<int32_t> dense(v.B, -1);
         for (int b = 0; b < v.B; ++b)
             if (heat[b] >= 0) dense[b] = (int32_t)(std::lower_bound(ids.begin(), ids.end(), heat[b]) - ids.begin());
-        rc = heat_members(h, who, v.B, n_heats, dense.data(), off, members, largest); if (rc) return rc;
+        rc = lpvmpc_heat_members(h, who, v.B, n_heats, dense.data(), off, members, largest); if (rc) return rc;
         if (h->trk.tab)
             for (int g = 0; g < n_heats; ++g)
                 for (int k = off[g] + 1; k < off[g + 1]; ++k)
@@ -91,6 +91,7 @@ extern "C" int lpvmpc_race_heats(lpvmpc_handle *h, const lpvmpc_heats_config *cf
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t st = h->stream;
     HIP_TRY(h, hipStreamSynchronize(st));                                       // no tick in flight reads the old attachment
+    { const int rd = lpvmpc_race_interactions_detach(h); if (rd) return rd; }   // the interactions read this attachment's lists and extents
     v.slot->reset();
     if (!heat) return LPVMPC_OK;
     std::unique_ptr<HeatsBinding> q(new (std::nothrow) HeatsBinding());         // installed once it is complete
@@ -159,10 +160,10 @@ extern "C" int lpvmpc_heat_step_batch(lpvmpc_handle *h, int32_t B, int32_t n_hea
     if (busy(h)) return fail(h, LPVMPC_E_ARG, "%s: this handle runs a fleet, cascade or race; use another handle for batch calls", who);
     if (B < 0 || n_heats < 0 || !heat || !L || !pose || !s || !inside || !phase || !carry_f64 || !carry_i32 || !f64 || !i32)
         return fail(h, LPVMPC_E_ARG, "%s: B < 0, n_heats < 0 or NULL argument", who);
-    int rc = check_extents(h, who, cfg); if (rc) return rc;
+    int rc = lpvmpc_heat_extents(h, who, cfg); if (rc) return rc;
     std::vector<int32_t> off, members;
     int largest = 0;
-    rc = heat_members(h, who, B, n_heats, heat, off, members, largest); if (rc) return rc;
+    rc = lpvmpc_heat_members(h, who, B, n_heats, heat, off, members, largest); if (rc) return rc;
     const size_t n = B;
     for (size_t b = 0; b < n; ++b)
         if (heat[b] >= 0 && !(std::isfinite(L[b]) && L[b] > 0)) return fail(h, LPVMPC_E_ARG, "%s: vehicle %zu: L = %g must be finite and > 0", who, b, L[b]);

@@ -1,0 +1,28 @@
+// interactions_host.hpp -- host side of the interactions (lpvmpc_race_interactions), shared by race_api.hip, which owns the binding
+// and launches the tick's kernel, and interactions_api.hip, which builds and reads it.  No other translation unit includes it.
+#pragma once
+#include "heats_host.hpp"
+#include "interactions.hpp"
+
+// interactions attached to a race: the kernel argument with its device memory (the base mu words, carried state and outputs; the
+// member lists are the heats'), the heats' block size, the configuration as it was set and, on the host, the base mu words [B] that
+// the read-backs return and a detach restores.  Owned by the race next to the heats
+struct InterBinding {
+    lpvmpc::InterDev d{};
+    DevArena mem;
+    int block = 64;
+    lpvmpc_interaction_config cfg{};
+    std::vector<double> mu_base;
+};
+
+// race_api.hip: what lpvmpc_race_interactions needs of the running race: the state a tick reads and writes, the plant side whose live
+// table it rewrites, the heats it reads and the slot that owns the binding (false: the handle owns no race)
+struct RaceInterView {
+    int B = 0;
+    double *plant = nullptr;
+    const int32_t *nstep = nullptr;
+    PlantSide *side = nullptr;
+    const HeatsBinding *heats = nullptr;
+    std::unique_ptr<InterBinding> *slot = nullptr;
+};
+LPVMPC_HIDDEN bool lpvmpc_race_inter_view(lpvmpc_handle *h, RaceInterView &v);

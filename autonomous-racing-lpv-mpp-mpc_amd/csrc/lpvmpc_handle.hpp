@@ -254,6 +254,9 @@ struct RaceHeatsView {
     std::unique_ptr<HeatsBinding> *slot = nullptr;
 };
 LPVMPC_HIDDEN bool lpvmpc_race_heats_view(lpvmpc_handle *h, RaceHeatsView &v);
+// race_api.hip: the caller's mu words [B] (plant row word 6) while interactions are attached to the race that h owns
+// (lpvmpc_race_interactions rewrites the live words), else null: what a base copy of the live plant table takes in their place
+LPVMPC_HIDDEN const std::vector<double> *lpvmpc_race_mu_base(lpvmpc_handle *h);
 LPVMPC_HIDDEN int lpvmpc_observer_start(lpvmpc_handle *h, const lpvmpc_observer_config &o, int B, const double *plant0, double dt_sim,
                                         int from_plant);                                // lpvmpc_api.hip
 // actuator_api.hip: checks cfg / per-vehicle delays and allocates a zeroed actuator state for B vehicles in a (released first)

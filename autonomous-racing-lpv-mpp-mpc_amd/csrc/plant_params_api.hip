@@ -114,6 +114,8 @@ extern "C" int lpvmpc_plant_params_read(lpvmpc_handle *h, double *plant_params) 
     if (side->dist.d.rows) t = side->dist.base_p;                        // disturbances attached: the base rows, not the scaled live words
     else D2H(t.data(), v->p, t.size() * 8);
     HIP_TRY(h, hipStreamSynchronize(st));
+    if (const std::vector<double> *mu = lpvmpc_race_mu_base(h))          // interactions attached: the base mu, not the sheltered live word
+        for (size_t b = 0; b < B; ++b) t[6 * B + b] = (*mu)[b];
     for (size_t b = 0; b < B; ++b)
         for (size_t i = 0; i < LPVMPC_PLANT_WORDS; ++i) plant_params[b * LPVMPC_PLANT_WORDS + i] = t[i * B + b];
     return LPVMPC_OK;

@@ -3,13 +3,15 @@
 // admm_solve.hip and handoff.hip (masked launches).  A race with the estimator in the loop (lpvmpc_race_init_observed) keeps
 // the estimator state, gains and parameters in the path handle's obs_state / obs_gains / obs_p (obs_cfg stays null, so the
 // handle's next lpvmpc_cl_init runs on ground truth); lpvmpc_race_free releases them.  The recorder (lpvmpc_race_record,
-// record.hip) and the heats (lpvmpc_race_heats, heats_api.hip / heats.hip) belong to the race as well.
+// record.hip), the heats (lpvmpc_race_heats, heats_api.hip / heats.hip) and the interactions (lpvmpc_race_interactions,
+// interactions_api.hip / interactions.hip) belong to the race as well.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <new>
 
 #include "heats_host.hpp"
+#include "interactions_host.hpp"
 #include "lpvmpc_handle.hpp"
 #include "race_state.hpp"
 #include "record.hpp"
@@ -29,6 +31,7 @@ struct lpvmpc_race {
     int sd = 0;
     std::unique_ptr<lpvmpc_race_recorder> rec;   // lpvmpc_race_record (null: not recording)
     std::unique_ptr<HeatsBinding> heats;         // lpvmpc_race_heats (heats_api.hip; null: none attached)
+    std::unique_ptr<InterBinding> inter;         // lpvmpc_race_interactions (interactions_api.hip; null: none attached; reads the heats' lists)
 };
 
 void lpvmpc_race_free(lpvmpc_handle *h) {
@@ -300,6 +303,16 @@ bool lpvmpc_race_heats_view(lpvmpc_handle *h, RaceHeatsView &v) {
     return true;
 }
 
+bool lpvmpc_race_inter_view(lpvmpc_handle *h, RaceInterView &v) {
+    lpvmpc_race *r = h->race;
+    if (!r) return false;
+    v.B = r->d.B; v.plant = r->d.plant; v.nstep = r->d.nstep; v.side = &r->side; v.heats = r->heats.get(); v.slot = &r->inter;
+    return true;
+}
+const std::vector<double> *lpvmpc_race_mu_base(lpvmpc_handle *h) {
+    return h && h->race && h->race->inter ? &h->race->inter->mu_base : nullptr;
+}
+
 extern "C" int lpvmpc_race_init_observed(lpvmpc_handle *h, lpvmpc_handle *tt, lpvmpc_handle *plan, int32_t B, const double *plant0,
                                          const int32_t *half_track0, const lpvmpc_race_config *cfg, const lpvmpc_observer_config *obs) {
     return race_init(h, tt, plan, B, plant0, half_track0, cfg, obs, true);
@@ -362,6 +375,8 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
         ta.active = d.m_tt;
         rc = lpvmpc_launch_solve_timed(tt, ta, st); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
         if (side.dist.d.rows) HIP_TRY(h, lpvmpc::launch_disturbance(h->d_cfg, trk, side.dist.d, st));   // lpvmpc_set_disturbances
+        if (const InterBinding *q = r->inter.get())                                 // lpvmpc_race_interactions: a kick comes before a contact
+            HIP_TRY(h, lpvmpc::launch_interaction_tick(q->d, q->block, r->ticks, st));
         HIP_TRY(h, step(lpvmpc::RaceStepArgs{d, side.pc, side.tpc(), lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, side.act.d, side.fault.d}, st));
         if (lpvmpc_race_recorder *q = r->rec.get()) {                               // the recorder (record.hip)
             int slot = -1;

@@ -1288,6 +1288,115 @@ int  lpvmpc_sensor_step_batch(lpvmpc_handle *h, int32_t B, const lpvmpc_observer
                               const lpvmpc_sensor_fault_config *cfg, const double *rows, double *obs_state, const double *plant,
                               const double *servo, const double *motor);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Interactions: slipstream and contact response between the vehicles of a heat.  Heats observe; interactions let the members of a heat
+ * act on each other's PLANTS: a car in another's wake has less drag, and overlapping footprints exchange an impulse and are pushed
+ * apart.  Plant side only: one more kernel in front of the tick's command / plant kernel, behind the disturbances' (a kick comes
+ * before a contact of the same tick); no controller, planner or estimator knows about an opponent.  The reference's simulator drives
+ * one car, so nothing here has a counterpart in it: this text is the definition, and the defaults are invented values of the right
+ * order for a 1:10 car.  The contact is frictionless and acts through the centres: it changes the velocity along the contact normal
+ * and the position, never yaw, psiDot, ax or ay.
+ *
+ * Participants.  A vehicle takes part on a tick when it is a member of an attached heat, its plant advances this tick (nstep[b] > 0,
+ * the disturbances' rule: a frozen vehicle is neither touched nor seen) and its x, y, yaw, vx, vy are finite.  Everything below is
+ * per heat, over its participants, in member (= ascending vehicle index) order.
+ * Staged per participant, before anything is written: x, y; c = cos(yaw), s = sin(yaw); the world velocity ux = c*vx - s*vy,
+ * uy = s*vx + c*vy; m (plant row word 2) and the base mu (plant row word 6).  Every product and sum here and below is rounded on its
+ * own (no fused multiply-add), in the order written, a unary minus applying to the factor it stands in front of.
+ *
+ * Slipstream of vehicle i, over every other participant j:
+ *   dx = x_i - x_j, dy = y_i - y_j;  lon = -(dx*c_j + dy*s_j), the distance behind j's centre along j's heading;
+ *   lat = -dx*s_j + dy*c_j;  align = c_i*c_j + s_i*s_j.
+ *   i is in j's wake when 0 < lon < wake_length, |lat| < wake_half_width and align > 0; then
+ *   w_ij = (1 - lon/wake_length) * (1 - |lat|/wake_half_width), else w_ij = 0.
+ *   w_i = max_j w_ij (the shelter); leader_i = the lowest j attaining the max, -1 when w_i == 0.
+ * The live plant table's drag word of vehicle i becomes mu_i * (1 - draft_gain * w_i), mu_i the base word; it is rewritten on every
+ * tick on which the vehicle takes part, as the grip patches rewrite Cf, Cr, c_f.  A max does not depend on the order of evaluation:
+ * no atomics, and reruns are bit-identical.
+ *
+ * Contact (contact != 0), for every unordered pair a < b of participants whose footprints overlap: sep < 0 by the heats' own
+ * definition ("Heats", footprint and clearance), with the heats' configured half extents and a, the lower index, as the first
+ * rectangle, so both sides hold the same word.  With d = centre_b - centre_a, the projections p0 = d . u_a, p1 = d . v_a,
+ * p2 = d . u_b, p3 = d . v_b on the axes u = (c, s), v = (-s, c) of each rectangle (p1 = dy*c_a - dx*s_a, p3 likewise) and the four gaps
+ * g_k = |p_k| - r_k of that definition:
+ *   the contact axis is the first of (u_a, v_a, u_b, v_b) whose gap attains the max, sep = that gap;
+ *   n = axis * sign(p_k), sign(0) = +1: the normal, from a to b;
+ *   vn = (u_b - u_a) . n;   J = vn < 0 ? -(1 + restitution) * vn / (1/m_a + 1/m_b) : 0   (a separating pair gets no impulse);
+ *   du_a = -(J/m_a) n,  du_b = +(J/m_b) n;
+ *   depth = -sep;  dc_a = -push * depth * (m_b/(m_a + m_b)) n,  dc_b = +push * depth * (m_a/(m_a + m_b)) n.
+ * Each vehicle sums the du and dc of its own contacts over its partners in ascending order, starting from 0; all of them come from
+ * the staged (pre-tick) words, a Jacobi step: the result does not depend on which pair is handled first.
+ * A vehicle WITHOUT an overlapping partner keeps every state word as it is (no round trip through the world frame).  One with an
+ * overlapping partner or more writes u' = u + sum du, vx = max(c*u'_x + s*u'_y, 0), vy = -s*u'_x + c*u'_y, x += sum dc_x,
+ * y += sum dc_y.
+ *
+ * Outputs per vehicle, channel-major and vehicle-minor as the standings: f64 [LPVMPC_INTER_F64][B] = SHELTER (w_i), MU (the live word
+ * written), IMPULSE (the sum of |J| over its contacts of this tick), IMPULSE_TOTAL (since the attach); i32 [LPVMPC_INTER_I32][B] =
+ * LEADER (vehicle index), HIT (0 / 1 this tick), HIT_TICKS, FIRST_HIT_TICK (-1: none), DRAFT_TICKS (ticks with w_i > 0).  The three
+ * counters and the total are carried.  A member that does not take part on a tick reads SHELTER 0, IMPULSE 0, LEADER -1, HIT 0; its
+ * carried words and its MU word stay put (before its first tick MU reads the base word).  A vehicle in no heat reads NaN in every f64
+ * channel, -1 in LEADER and FIRST_HIT_TICK, 0 in HIT, HIT_TICKS and DRAFT_TICKS, as in lpvmpc_race_standings.
+ *
+ * Configuration (lpvmpc_interaction_default_config: draft_gain 0.3, wake_length 3.0 m, wake_half_width 0.3 m, contact 1,
+ * restitution 0.2, push 0.5): draft_gain in [0, 1] (0: no slipstream), wake_length > 0, wake_half_width > 0, contact 0 / 1,
+ * restitution in [0, 1], push in [0, 1].  With draft_gain = 0 and contact = 0 no word of any plant changes and the live mu word is the
+ * base word.
+ *
+ * lpvmpc_race_interactions attaches the interactions to the race of the path handle from the next tick on; attaching again replaces
+ * the binding (counters start anew), cfg == NULL detaches.  It needs a race with heats attached (it reads their member lists and
+ * extents) and a plant table (the lpvmpc_race_init_vehicles / _tyres starts).  Refused with LPVMPC_E_ARG, the race left as it was: no
+ * race on the handle, no heats, no plant table, a config word that is not finite or outside its range.  The binding is built whole
+ * and then installed; the race owns it next to the heats and frees it with them.  lpvmpc_race_heats, whether it re-attaches or
+ * detaches, detaches the interactions first.  A detach writes the base mu words back to the live plant table.  While attached
+ * lpvmpc_race_tick issues one more launch, behind the disturbances' and in front of the command / plant kernel; with nothing attached
+ * a tick issues exactly the launches it always did.  lpvmpc_plant_params_read returns the caller's rows (the base mu) while attached,
+ * as it does for the disturbances' words; disturbances and interactions may be attached and detached in either order: each keeps the
+ * caller's words as its base, and with both detached the live tables are word for word what the race started with.
+ * lpvmpc_race_snapshot works while attached and does not contain the binding (the live mu word is a table word, the counters belong
+ * to the binding); restore and clone are refused while heats are attached.
+ * lpvmpc_race_interactions_read synchronises and copies the two output planes (either pointer may be NULL); refused with LPVMPC_E_ARG
+ * while nothing is attached.
+ *
+ * lpvmpc_interaction_step_batch is one tick of the same kernel on caller-supplied data: heat [B] with indices in [-1, n_heats) and the
+ * heats' extents heats_cfg, plant [B][8] in / out, plant_params [B][LPVMPC_PLANT_WORDS] (words 2 and 6 are read), nstep [B] or NULL
+ * (every vehicle steps), the carried state carry_f64 [LPVMPC_INTER_CARRY_F64][B] / carry_i32 [LPVMPC_INTER_CARRY_I32][B] in / out (just
+ * attached: zeros, FIRST_HIT_TICK -1), mu_live [B] out (the base word for a vehicle that does not take part) and the output planes.  It
+ * needs a handle (device and stream) that runs no fleet, cascade or race. */
+#define LPVMPC_INTER_F64                  4
+#define LPVMPC_INTER_SHELTER              0
+#define LPVMPC_INTER_MU                   1
+#define LPVMPC_INTER_IMPULSE              2
+#define LPVMPC_INTER_IMPULSE_TOTAL        3
+#define LPVMPC_INTER_I32                  5
+#define LPVMPC_INTER_LEADER               0
+#define LPVMPC_INTER_HIT                  1
+#define LPVMPC_INTER_HIT_TICKS            2
+#define LPVMPC_INTER_FIRST_HIT_TICK       3
+#define LPVMPC_INTER_DRAFT_TICKS          4
+#define LPVMPC_INTER_CARRY_F64            1
+#define LPVMPC_INTER_CARRY_IMPULSE_TOTAL  0
+#define LPVMPC_INTER_CARRY_I32            3
+#define LPVMPC_INTER_CARRY_HIT_TICKS      0
+#define LPVMPC_INTER_CARRY_FIRST_HIT_TICK 1
+#define LPVMPC_INTER_CARRY_DRAFT_TICKS    2
+typedef struct lpvmpc_interaction_config {
+    double  draft_gain;        /* [0, 1]: the share of the drag word a full shelter takes away; 0: no slipstream */
+    double  wake_length;       /* > 0, metres behind the leader's centre */
+    double  wake_half_width;   /* > 0, metres to either side of the leader's axis */
+    int32_t contact;           /* 0 / 1 */
+    int32_t reserved;          /* 0 */
+    double  restitution;       /* [0, 1] */
+    double  push;              /* [0, 1]: the share of the overlap depth removed per tick */
+} lpvmpc_interaction_config;
+void lpvmpc_interaction_default_config(lpvmpc_interaction_config *cfg);
+int  lpvmpc_race_interactions(lpvmpc_handle *path, const lpvmpc_interaction_config *cfg /* NULL: detach */);
+int  lpvmpc_race_interactions_read(lpvmpc_handle *path, double *f64, int32_t *i32);
+int  lpvmpc_interaction_step_batch(lpvmpc_handle *h, int32_t B, int32_t n_heats, const int32_t *heat,
+                                   const lpvmpc_heats_config *heats_cfg, const lpvmpc_interaction_config *cfg, int32_t t,
+                                   double *plant /* [B][8] in/out */, const double *plant_params /* [B][7] */,
+                                   const int32_t *nstep /* [B] or NULL: all step */, double *carry_f64, int32_t *carry_i32,
+                                   double *mu_live /* [B] out */, double *f64, int32_t *i32);
+
 #ifdef __cplusplus
 }
 #endif

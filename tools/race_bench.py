@@ -55,8 +55,14 @@ the GB/s over the bytes its two kernels read plus write (the state goes through 
 (lpvmpc_race_heats: one more launch per tick, one workgroup per heat), alternated --reps times per (regime, B) in one process; medians, each
 configuration's spread over the alternations and the added ms per controller tick; and, with --parent-lib FILE, the detached race on that
 build, one child process per run: the launches are identical, so it must lie within the alternation's spread.
+--interactions [--heats SIZE]: the --disturbance protocol for the interactions (lpvmpc_race_interactions): the lpvmpc_race_init_tyres race with
+kind 0 rows and heats of SIZE (default 16) consecutive vehicles attached (the baseline: the launches of the parent's tick), the same race
+with the all-off interactions attached (draft_gain 0, contact off: the same race word for word, so the difference is the launch), and
+with the default interactions attached (another race: other trajectories, other QPs), alternated --reps times per (regime, B), each run in
+a fresh process; with --parent-lib FILE the parent's library on the baseline as well.
+
 Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator | --actuator | --record | --heats SIZE | --plant-params | --models |
-       --tunings | --tyres | --observer-vehicles | --tracks | --disturbance | --sensor-faults | --fork [--parent-lib FILE] [--reps R]]
+       --tunings | --tyres | --observer-vehicles | --tracks | --disturbance | --sensor-faults | --interactions | --fork [--parent-lib FILE] [--reps R]]
        [--out FILE]
 --sensor-faults: the same protocol for the sensor faults (lpvmpc_set_sensor_faults): the lpvmpc_race_init_tyres race with kind 0 rows and the
 estimator in the loop with nothing attached (the baseline: the launches of the parent's tick), with all-off rows attached (the faulted
@@ -95,7 +101,7 @@ def timed(tick, read, K):
 
 
 def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, record=False, plant_params=None, model_params=None, tunings=None,
-             tyre_params=None, observer_vehicles=False, tracks=None, disturbance=None, heats=0, sensor_faults=None):
+             tyre_params=None, observer_vehicles=False, tracks=None, disturbance=None, heats=0, sensor_faults=None, interactions=None):
     path, tt, plan = engines(mp, sd)
     if tracks is not None:                                            # (maps, track_of) bound to the three engines
         for e in (path, tt, plan):
@@ -124,6 +130,8 @@ def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, rec
         path.race_record(K, 1)
     if heats:                                                         # heats of `heats` consecutive vehicles
         path.race_heats(np.arange(plant0.shape[0]) // int(heats))
+    if interactions is not None:                                      # a dict of configuration words, on the heats just attached
+        path.race_interactions(interactions)
     a0 = path.race_laps()[1].sum()
     ms = timed(path.race_tick, path.race_read, K)
     alive = path.race_laps()[1].sum() - a0
@@ -151,6 +159,7 @@ def main():
     ap.add_argument("--tracks", action="store_true")
     ap.add_argument("--disturbance", action="store_true")
     ap.add_argument("--sensor-faults", action="store_true")
+    ap.add_argument("--interactions", action="store_true")
     ap.add_argument("--fork", action="store_true")
     ap.add_argument("--fork-child", default=None, help=argparse.SUPPRESS)                  # B: the fork measurements of one fleet size
     ap.add_argument("--parent-lib", default=None)
@@ -182,6 +191,10 @@ def main():
         return models_main(a, [("estimator, nothing attached", "liblpvmpc.so", 14), ("off rows attached", "liblpvmpc.so", 16),
                                ("sensor faults attached", "liblpvmpc.so", 15)],
                            parent=("parent, estimator", 14))
+    if a.interactions:
+        a.heats = a.heats or 16
+        return models_main(a, [("tyres + heats of %d" % a.heats, "liblpvmpc.so", 17), ("all-off interactions", "liblpvmpc.so", 18),
+                               ("interactions attached", "liblpvmpc.so", 19)], parent=("parent, tyres + heats", 17))
     if a.plant_params:
         return plant_params_main(a)
     if a.record:
@@ -419,7 +432,8 @@ def models_child(a):
     rows = lpvmpc.model_params(int(B)) if int(bind) == 1 else None                # bind: 0 nothing, 1 nominal model rows, 2 / 3 tuning rows,
     tyres = {5: lpvmpc.tyre_params(int(B), kind=0), 6: "pacejka", 9: lpvmpc.tyre_params(int(B), kind=0),
              13: lpvmpc.tyre_params(int(B), kind=0), 14: lpvmpc.tyre_params(int(B), kind=0),
-             15: lpvmpc.tyre_params(int(B), kind=0), 16: lpvmpc.tyre_params(int(B), kind=0)}.get(int(bind))               # 4 nominal plant rows (_vehicles), 5 / 6 tyre rows on top
+             15: lpvmpc.tyre_params(int(B), kind=0), 16: lpvmpc.tyre_params(int(B), kind=0), 17: lpvmpc.tyre_params(int(B), kind=0),
+             18: lpvmpc.tyre_params(int(B), kind=0), 19: lpvmpc.tyre_params(int(B), kind=0)}.get(int(bind))               # 4 nominal plant rows (_vehicles), 5 / 6 tyre rows on top
     dist = None                                                                    # 13: 9 with gusts, a patch and a kick on every vehicle
     if int(bind) == 13:
         from lpvmpc.disturbance import parse_disturbance
@@ -440,7 +454,9 @@ def models_child(a):
                               v_std=0.02, seed=7)
     ms, vps, ph = race_run(mp, plant0, half, warm, a.ticks, model_params=rows, tunings={2: "own", 3: "sampled"}.get(int(bind)),
                             plant_params="nominal" if int(bind) in (4, 5, 6, 7, 8) else None, tyre_params=tyres, estimator=obs,
-                            observer_vehicles=int(bind) == 8, disturbance=dist, sensor_faults=faults)
+                            observer_vehicles=int(bind) == 8, disturbance=dist, sensor_faults=faults,
+                            heats=(a.heats or 16) if int(bind) in (17, 18, 19) else 0,       # 17: 9 with heats; 18 / 19: the interactions on top, all off / defaults
+                            interactions={18: dict(draft_gain=0.0, contact=0), 19: {}}.get(int(bind)))
     print("MODELS_RUN %.6f %s %.4g" % (ms, ",".join(str(int(x)) for x in ph), vps), flush=True)
 
 
@@ -513,7 +529,7 @@ def models_main(a, cfgs=None, parent=("parent, unbound", 0), write=True):
             for _ in range(a.reps):
                 for k, lib, bind in cfgs:
                     out = subprocess.run([sys.executable, os.path.abspath(__file__), "--ticks", str(a.ticks), "--models-child", lib, regime, str(B),
-                                          str(bind)], check=True, capture_output=True, text=True, timeout=600).stdout
+                                          str(bind)] + (["--heats", str(a.heats)] if a.heats else []), check=True, capture_output=True, text=True, timeout=600).stdout
                     f = [l for l in out.splitlines() if l.startswith("MODELS_RUN")][-1].split()
                     ms[k].append(float(f[1])); ph[k] = f[2]; vps.setdefault(k, []).append(float(f[3]))
             m0 = float(np.median(ms[base]))

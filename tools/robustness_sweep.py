@@ -37,8 +37,13 @@ into the race), gps_loss:P (each publication lost with probability P, seeded wit
 imu_drift:W, enc_scale:S; several joined with +.  It needs --estimator (the sensors feed the estimator); the baseline race keeps
 healthy sensors.  The answer it is for: does estimator + controller survive one second without GPS?  Without the flag the output is
 today's.
+--interactions SIZE[:WORD=VALUE,...] lets the vehicles of the swept race act on each other (lpvmpc_race_heats + lpvmpc_race_interactions,
+RaceFleet(heats=..., interactions=...)): heats of SIZE consecutive vehicles (on one track each; with --tracks, consecutive vehicles of
+one track) whose members take drag off each other in the wake and exchange impulses where their footprints overlap; WORD=VALUE sets
+configuration words (draft_gain, wake_length, wake_half_width, contact, restitution, push).  The baseline race keeps to itself.  The
+report gains one line: vehicles hit, total hit ticks, drafting ticks.  Without the flag the output is today's.
 Usage: tools/robustness_sweep.py [--B 8192] [--laps 2] [--seed 1] [--max-ticks 3000] [--model nominal|plant|noisy:REL]
-       [--tyre linear|pacejka] [--estimator nominal|plant] [--disturbance SPEC] [--sensor-faults SPEC] [--respawn K] [--out FILE]"""
+       [--tyre linear|pacejka] [--estimator nominal|plant] [--disturbance SPEC] [--sensor-faults SPEC] [--interactions SPEC] [--respawn K] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -61,9 +66,13 @@ def main():
     ap.add_argument("--tracks", default=None, help="comma-separated track shapes (oval, L_shape, 3110, Euge_Track): vehicle b races on track b mod their number")
     ap.add_argument("--disturbance", default=None, help="gusts:SIGMA | patch:S0,LEN,GAMMA | kick:STEP,VY,W (joined with +)")
     ap.add_argument("--sensor-faults", default=None, help="gps_outage:LEN_S | enc_outage:LEN_S | gps_loss:P | imu_bias:W | imu_drift:W | enc_scale:S (joined with +)")
+    ap.add_argument("--interactions", default=None, metavar="SIZE[:WORD=VALUE,...]",
+                    help="heats of SIZE consecutive vehicles whose members draft and hit each other, e.g. 16 or 16:draft_gain=0.5,contact=0")
     ap.add_argument("--respawn", type=int, default=None, help="refill the lost slots every K ticks (0: never, but report the alive vehicle-ticks)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.interactions and a.respawn:
+        ap.error("--respawn clones vehicles, which a race refuses while heats are attached: not with --interactions")
     if a.respawn is not None and a.respawn < 0:
         ap.error("--respawn must be >= 0")
     if a.sensor_faults and not a.estimator:
@@ -112,12 +121,23 @@ def main():
         from lpvmpc.sensor_faults import parse_sensor_faults
         faults = dict(rows=parse_sensor_faults(a.sensor_faults, B), seed=a.seed)
 
+    inter = None
+    if a.interactions:
+        size, _, words = a.interactions.partition(":")
+        cfg = {k: (int(v) if k == "contact" else float(v)) for k, v in (w.split("=") for w in words.split(",") if w)}
+        heat = np.zeros(B, np.int32)
+        for t in (np.unique(track_of) if maps else [0]):               # consecutive vehicles of one track
+            on = np.nonzero(track_of == t)[0] if maps else np.arange(B)
+            heat[on] = (heat.max() + 1 if t else 0) + np.arange(on.shape[0]) // int(size)
+        inter = dict(heats=dict(heat=heat), interactions=cfg or True)
+    contacts = {}
+
     fork = dict(slots=0, alive=0)                                     # of the swept race, with --respawn
 
-    def race(r, m=None, est_rows=None, disturbance=None, respawn=None, sensor_faults=None):
+    def race(r, m=None, est_rows=None, disturbance=None, respawn=None, sensor_faults=None, interact=None):
         f = lpvmpc.RaceFleet(mp if maps is None else maps, plant0, laps=a.laps, half_track0=1, plant_params=r, model_params=m, track_of=track_of,
                              tyre_params="pacejka" if a.tyre == "pacejka" else None, estimator=obs, estimator_params=est_rows,
-                             disturbance=disturbance, sensor_faults=sensor_faults)
+                             disturbance=disturbance, sensor_faults=sensor_faults, **(interact or {}))
         assert np.array_equal(f.plant_params(), r)
         assert a.tyre == "linear" or np.array_equal(f.tyre_params(), lpvmpc.tyre_params(B))
         assert m is None or np.array_equal(f.model_params(), m)
@@ -140,7 +160,10 @@ def main():
     base, _n, _w = race(nom)                                          # the same starts with the nominal car: the baseline
     ph_nom = base.state()["phase"]
     base.close()
-    fleet, ticks, wall = race(rows, model_rows, "plant" if a.estimator == "plant" else None, dist, a.respawn, faults)
+    fleet, ticks, wall = race(rows, model_rows, "plant" if a.estimator == "plant" else None, dist, a.respawn, faults, inter)
+    if inter:
+        io = fleet.interactions()
+        contacts.update(hit=int((io["hit_ticks"] > 0).sum()), hit_ticks=int(io["hit_ticks"].sum()), draft_ticks=int(io["draft_ticks"].sum()))
     ph = fleet.state()["phase"]
     lt = fleet.lap_times()[:, 1:a.laps + 1]                          # racing laps, seconds (NaN: not completed)
     rmse = fleet.lap_stats()["rmse_ey"][:, 1:a.laps + 1] if not a.respawn else np.full(lt.shape, np.nan)
@@ -159,7 +182,9 @@ def main():
              "# %d ticks (%.1f s wall); all vehicles: %.1f %% finished, %.1f %% lost, %.1f %% still running; racing lap time median %.3f s, "
              "p90 %.3f s; RMSE_ey median %.4f m" % (ticks, wall, 100 * fin.mean(), 100 * lost.mean(), 100 * (ph < 2).mean(),
                                                      np.nanmedian(lt), np.nanpercentile(lt, 90), np.nanmedian(rmse)),
-             ] + ([] if a.respawn is None else [
+             ] + ([] if not inter else [
+             "# the swept race's vehicles act on each other (--interactions %s): %d vehicles hit, %d hit ticks, %d drafting ticks; the baseline "
+             "race's do not." % (a.interactions, contacts["hit"], contacts["hit_ticks"], contacts["draft_ticks"])]) + ([] if a.respawn is None else [
              "# --respawn %d: %d slots respawned, %d alive vehicle-ticks, %.4g alive vehicle-ticks/s over the %d ticks%s"
              % (a.respawn, fork["slots"], fork["alive"], fork["alive"] / wall, ticks,
                 " (lost slots refilled every %d ticks: a different experiment, not a faster one; nothing recorded)" % a.respawn if a.respawn else "")]) + [
