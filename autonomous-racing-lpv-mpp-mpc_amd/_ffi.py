@@ -132,6 +132,20 @@ INTER_CARRY_F64_NAMES = ("impulse_total",)
 INTER_CARRY_I32_NAMES = ("hit_ticks", "first_hit_tick", "draft_ticks")
 
 
+class WallConfig(C.Structure):
+    """Mirror of ``struct lpvmpc_wall_config`` (include/lpvmpc.h)."""
+    _fields_ = [("margin", _d), ("reach", _d), ("half_length", _d), ("half_width_car", _d), ("restitution", _d), ("friction", _d), ("push", _d),
+                ("yaw_response", _i), ("reserved", _i)]
+
+
+# walls (LPVMPC_WALL_*): outputs f64 [WALL_F64][B] / i32 [WALL_I32][B] and the carried state of the batch form, in channel order
+WALL_F64, WALL_I32, WALL_CARRY_F64, WALL_CARRY_I32 = 4, 6, 2, 2
+WALL_F64_NAMES = ("depth", "impulse", "impulse_total", "max_impulse")
+WALL_I32_NAMES = ("hit", "side", "corner", "hit_ticks", "first_hit_tick", "outside")
+WALL_CARRY_F64_NAMES = ("impulse_total", "max_impulse")
+WALL_CARRY_I32_NAMES = ("hit_ticks", "first_hit_tick")
+
+
 # race recorder channels (LPVMPC_REC_*): f64 [REC_F64][B] and i32 [REC_I32][B] per record, named in channel order
 REC_F64, REC_I32 = 29, 8
 REC_PLANT, REC_LOCAL, REC_CMD, REC_REF, REC_TRACK, REC_EST = 0, 8, 14, 16, 20, 23
@@ -203,7 +217,8 @@ EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_d
            "lpvmpc_race_snapshot_size", "lpvmpc_race_snapshot", "lpvmpc_race_restore", "lpvmpc_race_clone",
            "lpvmpc_heats_default_config", "lpvmpc_race_heats", "lpvmpc_race_standings", "lpvmpc_heat_step_batch",
            "lpvmpc_sensor_fault_default_config", "lpvmpc_set_sensor_faults", "lpvmpc_sensor_faults_read", "lpvmpc_sensor_step_batch",
-           "lpvmpc_interaction_default_config", "lpvmpc_race_interactions", "lpvmpc_race_interactions_read", "lpvmpc_interaction_step_batch")
+           "lpvmpc_interaction_default_config", "lpvmpc_race_interactions", "lpvmpc_race_interactions_read", "lpvmpc_interaction_step_batch",
+           "lpvmpc_wall_default_config", "lpvmpc_race_walls", "lpvmpc_race_walls_read", "lpvmpc_wall_step_batch")
 
 _lib = None
 
@@ -442,6 +457,16 @@ def load():
             getattr(lib, name).restype = C.c_int
     except AttributeError:
         pass
+    try:        # (nor the walls)
+        lib.lpvmpc_wall_default_config.argtypes = [P(WallConfig)]
+        lib.lpvmpc_wall_default_config.restype = None
+        lib.lpvmpc_race_walls.argtypes = [vp, P(WallConfig)]
+        lib.lpvmpc_race_walls_read.argtypes = [vp, vp, vp]
+        lib.lpvmpc_wall_step_batch.argtypes = [vp, _i, P(WallConfig), _d, _i, vp, vp, vp, vp, vp, vp, vp]
+        for name in ("lpvmpc_race_walls", "lpvmpc_race_walls_read", "lpvmpc_wall_step_batch"):
+            getattr(lib, name).restype = C.c_int
+    except AttributeError:
+        pass
     for name in ("lpvmpc_handoff_length", "lpvmpc_handoff_operators", "lpvmpc_handoff_setup", "lpvmpc_handoff_batch",
                  "lpvmpc_cascade_init", "lpvmpc_cascade_tick", "lpvmpc_cascade_read"):
         getattr(lib, name).restype = C.c_int
@@ -500,6 +525,12 @@ def default_sensor_fault_config():
 def default_interaction_config():
     cfg = InteractionConfig()
     load().lpvmpc_interaction_default_config(C.byref(cfg))
+    return cfg
+
+
+def default_wall_config():
+    cfg = WallConfig()
+    load().lpvmpc_wall_default_config(C.byref(cfg))
     return cfg
 
 

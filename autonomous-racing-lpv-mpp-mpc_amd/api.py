@@ -1043,6 +1043,55 @@ class BatchedSolver:
                                                           ptr(cf), ptr(ci), ptr(mu), ptr(f), ptr(i)))
         return plant, mu, I.interactions_dict(f, i), dict(f64=cf, i32=ci)
 
+    # -- walls: barrier contact at the track's edges (lpvmpc_race_walls / _read, lpvmpc_wall_step_batch; walls.py) ------------------
+    def race_walls(self, cfg=None, detach=False):
+        """Attach the walls from the next tick on (lpvmpc_race_walls): ``cfg`` a ``walls.wall_config(...)`` result, a dict of its words,
+        or None for the defaults.  Needs a race started with ``plant_params`` / ``tyre_params``; independent of heats, interactions and
+        disturbances.  Attaching again replaces the binding (counters start anew); ``detach=True`` detaches."""
+        from . import walls as W
+        self._race_B("race_walls")
+        if detach:
+            self._chk(self._lib.lpvmpc_race_walls(self._h, None))
+            return
+        c = W.as_config(cfg)
+        self._chk(self._lib.lpvmpc_race_walls(self._h, C.byref(c)))
+
+    def race_walls_read(self):
+        """Synchronise and return the walls' outputs (lpvmpc_race_walls_read): a dict of [B] arrays named as _ffi.WALL_F64_NAMES /
+        WALL_I32_NAMES (depth, impulse, impulse_total, max_impulse; hit, side, corner, hit_ticks, first_hit_tick, outside) and the
+        planes f64 [4, B] / i32 [6, B]."""
+        from . import walls as W
+        B = self._race_B("race_walls_read")
+        f = np.empty((_ffi.WALL_F64, B)); i = np.empty((_ffi.WALL_I32, B), np.int32)
+        self._chk(self._lib.lpvmpc_race_walls_read(self._h, ptr(f), ptr(i)))
+        return W.walls_dict(f, i)
+
+    def wall_step(self, plant, plant_params, t, cfg=None, nstep=None, carry=None, half_width=0.3):
+        """One tick of the walls' kernel on the caller's data (lpvmpc_wall_step_batch): ``plant`` [B, 8], ``plant_params`` [B, 7] (m and
+        Iz are read), ``t`` the tick number, ``cfg`` as ``race_walls``, ``nstep`` [B] the simulator steps of this tick (None: every
+        vehicle steps; 0: frozen), ``carry`` the state returned by the previous call (None: ``walls.new_carry(B)``), ``half_width`` the
+        track's (ignored when tracks are bound to the engine: each vehicle's palette entry has its own).  Returns (plant [B, 8] after
+        the tick, outputs dict, carry)."""
+        from . import walls as W
+        plant = f64(plant).copy()
+        if plant.ndim != 2 or plant.shape[1] != 8:
+            raise ValueError("wall_step: plant must be [B, 8], got %s" % (plant.shape,))
+        B = plant.shape[0]
+        rows = f64(plant_params, (B, _ffi.PLANT_WORDS), "plant_params")
+        c = W.as_config(cfg)
+        ns = None if nstep is None else np.ascontiguousarray(np.asarray(nstep).reshape(-1), np.int32)
+        if ns is not None and ns.shape[0] != B:
+            raise ValueError("wall_step: nstep must have one entry per vehicle (%d)" % B)
+        k = W.new_carry(B) if carry is None else carry
+        cf = f64(k["f64"], (_ffi.WALL_CARRY_F64, B), "carry f64").copy()
+        ci = np.ascontiguousarray(k["i32"], np.int32).copy()
+        if ci.shape != (_ffi.WALL_CARRY_I32, B):
+            raise ValueError("wall_step: carry i32 has shape %s, expected %s" % (ci.shape, (_ffi.WALL_CARRY_I32, B)))
+        f = np.empty((_ffi.WALL_F64, B)); i = np.empty((_ffi.WALL_I32, B), np.int32)
+        self._chk(self._lib.lpvmpc_wall_step_batch(self._h, B, C.byref(c), float(half_width), int(t), ptr(plant), ptr(rows), ptr(ns), ptr(cf),
+                                                   ptr(ci), ptr(f), ptr(i)))
+        return plant, W.walls_dict(f, i), dict(f64=cf, i32=ci)
+
     # -- device-pointer entry point (torch tensors or raw integers) -----------------------------------
     def solve_dev(self, B, x0, u_prev, vel_ref, curv_s, u_old, max_ey, xPred, uPred, status=None, iters=None,
                   resid=None, polish=None, cf_new=60.0, lap=1, stream=0):
@@ -1430,12 +1479,15 @@ class RaceFleet(object):
     attaches or detaches mid-race, ``standings()`` reads them).  ``interactions`` (with ``heats``): True for the defaults, an
     ``interactions.interaction_config(...)`` result or a dict of its words: slipstream and contact response between the members of a
     heat from the first tick on (``interact`` attaches or detaches mid-race, ``interactions()`` reads the outputs back); it selects
+    ``tyre_params="linear"`` when none is given.
+    ``walls``: True for the defaults, a ``walls.wall_config(...)`` result or a dict of its words: barrier contact at the track's edges
+    from the first tick on (``wall`` attaches or detaches mid-race, ``walls()`` reads the outputs back); it selects
     ``tyre_params="linear"`` when none is given."""
 
     def __init__(self, track_map, plant0, laps=1, N=20, Np=40, half_track0=None, device=0, estimator=None, actuator=None,
                  steering_delay=0, delay_a=None, delay_df=None, plant_params=None, model_params=None, path_tunings=None,
                  tt_tunings=None, plan_tunings=None, tyre_params=None, estimator_params=None, estimator_design=None, track_of=None,
-                 disturbance=None, sensor_faults=None, heats=None, interactions=None, **options):
+                 disturbance=None, sensor_faults=None, heats=None, interactions=None, walls=None, **options):
         from .workloads import CTRL_TUNINGS, PLAN_L, PLAN_Q, PLAN_R, PLAN_dR
         if interactions is not None and interactions is not False and heats is None:
             raise ValueError("interactions needs heats: the vehicles of a heat act on each other")
@@ -1508,6 +1560,8 @@ class RaceFleet(object):
         if interactions is not None and interactions is not False:
             if tyre_params is None:
                 tyre_params = "linear"                           # the start whose plant table holds the masses and the drag words
+        if walls is not None and walls is not False and tyre_params is None:
+            tyre_params = "linear"                               # the start whose plant table holds m and Iz
         self.path.race_init(self.tt, self.planner, plant0, half_track0=half_track0, laps=laps, half_width=track_map.halfWidth,
                             slack=track_map.slack, estimator=estimator, actuator=actuator, delay_a=delay_a, delay_df=delay_df,
                             plant_params=plant_params, tyre_params=tyre_params, **race_opts)
@@ -1519,6 +1573,8 @@ class RaceFleet(object):
             self.heats(**heats) if isinstance(heats, dict) else self.heats(heats)
         if interactions is not None and interactions is not False:
             self.interact(None if interactions is True else interactions)
+        if walls is not None and walls is not False:
+            self.wall(None if walls is True else walls)
 
     def fault(self, rows, seed=0, vehicle_offset=0):
         """Attach sensor faults from the next tick on (BatchedSolver.set_sensor_faults on the path engine); ``None`` detaches."""
@@ -1613,6 +1669,15 @@ class RaceFleet(object):
     def interactions(self):
         """The outputs of the attached interactions (BatchedSolver.race_interactions_read): shelter, live mu, impulses, leader, hits."""
         return self.path.race_interactions_read()
+
+    def wall(self, cfg=None, detach=False):
+        """Attach the walls from the next tick on (BatchedSolver.race_walls): ``cfg`` None (the defaults), a dict of words or a
+        ``walls.wall_config(...)`` result; ``wall(detach=True)`` detaches."""
+        self.path.race_walls(cfg, detach=detach)
+
+    def walls(self):
+        """The outputs of the attached walls (BatchedSolver.race_walls_read): depth, impulses, hit, side, corner, counters, outside."""
+        return self.path.race_walls_read()
 
     def snapshot(self):
         """The race's whole per-vehicle state and tick counter (BatchedSolver.race_snapshot): a ``snapshot.RaceSnapshot`` with

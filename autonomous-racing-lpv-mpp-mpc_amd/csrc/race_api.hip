@@ -3,8 +3,8 @@
 // admm_solve.hip and handoff.hip (masked launches).  A race with the estimator in the loop (lpvmpc_race_init_observed) keeps
 // the estimator state, gains and parameters in the path handle's obs_state / obs_gains / obs_p (obs_cfg stays null, so the
 // handle's next lpvmpc_cl_init runs on ground truth); lpvmpc_race_free releases them.  The recorder (lpvmpc_race_record,
-// record.hip), the heats (lpvmpc_race_heats, heats_api.hip / heats.hip) and the interactions (lpvmpc_race_interactions,
-// interactions_api.hip / interactions.hip) belong to the race as well.
+// record.hip), the heats (lpvmpc_race_heats, heats_api.hip / heats.hip), the interactions (lpvmpc_race_interactions,
+// interactions_api.hip / interactions.hip) and the walls (lpvmpc_race_walls, walls_api.hip / walls.hip) belong to the race as well.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -15,6 +15,7 @@
 #include "lpvmpc_handle.hpp"
 #include "race_state.hpp"
 #include "record.hpp"
+#include "walls_host.hpp"
 
 struct lpvmpc_race_recorder {
     lpvmpc::RecDev d{};           // kernel argument: race state pointers and the recorder's buffers
@@ -32,6 +33,7 @@ struct lpvmpc_race {
     std::unique_ptr<lpvmpc_race_recorder> rec;   // lpvmpc_race_record (null: not recording)
     std::unique_ptr<HeatsBinding> heats;         // lpvmpc_race_heats (heats_api.hip; null: none attached)
     std::unique_ptr<InterBinding> inter;         // lpvmpc_race_interactions (interactions_api.hip; null: none attached; reads the heats' lists)
+    std::unique_ptr<WallBinding> walls;          // lpvmpc_race_walls (walls_api.hip; null: none attached)
 };
 
 void lpvmpc_race_free(lpvmpc_handle *h) {
@@ -309,6 +311,12 @@ bool lpvmpc_race_inter_view(lpvmpc_handle *h, RaceInterView &v) {
     v.B = r->d.B; v.plant = r->d.plant; v.nstep = r->d.nstep; v.side = &r->side; v.heats = r->heats.get(); v.slot = &r->inter;
     return true;
 }
+bool lpvmpc_race_wall_view(lpvmpc_handle *h, RaceWallView &v) {
+    lpvmpc_race *r = h->race;
+    if (!r) return false;
+    v.B = r->d.B; v.hw = r->d.hw; v.plant = r->d.plant; v.nstep = r->d.nstep; v.side = &r->side; v.slot = &r->walls;
+    return true;
+}
 const std::vector<double> *lpvmpc_race_mu_base(lpvmpc_handle *h) {
     return h && h->race && h->race->inter ? &h->race->inter->mu_base : nullptr;
 }
@@ -377,6 +385,8 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
         if (side.dist.d.rows) HIP_TRY(h, lpvmpc::launch_disturbance(h->d_cfg, trk, side.dist.d, st));   // lpvmpc_set_disturbances
         if (const InterBinding *q = r->inter.get())                                 // lpvmpc_race_interactions: a kick comes before a contact
             HIP_TRY(h, lpvmpc::launch_interaction_tick(q->d, q->block, r->ticks, st));
+        if (const WallBinding *q = r->walls.get())                                  // lpvmpc_race_walls: a shove into a wall is answered on this tick
+            HIP_TRY(h, lpvmpc::launch_wall_tick(q->d, r->ticks, st));
         HIP_TRY(h, step(lpvmpc::RaceStepArgs{d, side.pc, side.tpc(), lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, side.act.d, side.fault.d}, st));
         if (lpvmpc_race_recorder *q = r->rec.get()) {                               // the recorder (record.hip)
             int slot = -1;

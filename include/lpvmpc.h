@@ -1397,6 +1397,125 @@ int  lpvmpc_interaction_step_batch(lpvmpc_handle *h, int32_t B, int32_t n_heats,
                                    const int32_t *nstep /* [B] or NULL: all step */, double *carry_f64, int32_t *carry_i32,
                                    double *mu_live /* [B] out */, double *f64, int32_t *i32);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Walls: barrier contact at the track's edges.  The interactions let cars act on each other; the walls let the TRACK act on a car:
+ * a corner of a footprint that passes the wall gets an impulse there and the car is pushed back, so a shoved or kicked car is turned
+ * and stopped instead of leaving a world without edges.  Plant side only: one more kernel in front of the tick's command / plant
+ * kernel, behind the disturbances' and the interactions' (a shove into a wall is answered on the same tick); no controller, planner or
+ * estimator knows about a wall.  The reference simulates one car on an open plane, so nothing here has a counterpart in it: this text
+ * is the definition, and the defaults are invented values of the right order for a 1:10 car.  Every product and sum below is rounded
+ * on its own (no fused multiply-add), in the order written, a unary minus applying to the factor it stands in front of.
+ *
+ * Participants.  A vehicle takes part on a tick when its plant advances this tick (nstep[b] > 0: a frozen vehicle is neither touched
+ * nor counted) and its x, y, yaw, vx, vy, psiDot are finite.  Heats play no part: a race without heats can have walls.
+ *
+ * Geometry.  The wall stands at |ey| = wall_ey = half_width + margin, half_width the race's, or the vehicle's track's when tracks are
+ * bound (lpvmpc_set_tracks).  The footprint is the rectangle half_length x half_width_car of this configuration around (x, y), turned
+ * by yaw; with c = cos(yaw), s = sin(yaw) its corners k = 0 .. 3 are taken in the order
+ *   (a, b) = (+half_length, +half_width_car), (+half_length, -half_width_car), (-half_length, +half_width_car),
+ *            (-half_length, -half_width_car):   r_k = (c*a - s*b, s*a + c*b),   corner_k = (x + r_kx, y + r_ky).
+ * A point p is located by a search over ALL rows i of the track table (PointAndTangent; ip the row before, the last for i = 0;
+ * S = (x, y) of row ip, F = (x, y) of row i, cv = word 5 of row i).  A row is Map.getLocalPosition's arithmetic for that row
+ * (lpvmpc_local_position_batch; computeAngle(a, o, b) = atan2 of the cross and dot products of a - o and b - o, |.| the norm
+ * sqrt(dx*dx + dy*dy)), giving (ey, th) where that function gives (s, ey, epsi); s and epsi are not computed:
+ *   cv == 0 (straight): |S - p| == 0 or |F - p| == 0: ey = 0.  Else, when |computeAngle(p, S, F)| <= pi/2 and
+ *     |computeAngle(p, F, S)| <= pi/2: ey = |p - S| * sin(computeAngle(F, S, p)); else the row does not see p.  th = word 2 of row ip.
+ *   cv != 0 (arc): r = 1/cv, d = r >= 0 ? 1 : -1, ang = word 2 of row ip, C = S + |r| * (cos(ang + d*pi/2), sin(ang + d*pi/2)).
+ *     |S - p| == 0: ey = 0, th = ang.  |F - p| == 0: ey = 0, th = word 2 of row i.  Else arc1 = word 4 * word 5 of row i,
+ *     arc2 = computeAngle(S, C, p): when sign(arc1) == sign(arc2) and |arc1| >= |arc2|: ey = -d * (|p - C| - |r|), th = ang + arc2;
+ *     else the row does not see p.
+ *   A row that sees p accepts it when |ey| <= wall_ey + reach (the function's own bound is half_width + slack).
+ * Among the rows that accept p the one with the smallest |ey| wins, the first of them on a tie: the wall is the nearest stretch of
+ * track, not whichever row comes first where two stretches run close.  A point that no row accepts is not located.
+ * A corner that is not located is not in contact on that tick.  A located corner penetrates when |ey_k| > wall_ey, with
+ * depth_k = |ey_k| - wall_ey.  The contact corner is the first corner that attains the largest depth: at most one contact per vehicle
+ * and tick.  With side = ey_k > 0 ? +1 : -1 and th of the winning row, the inward normal is n = (side * sin(th), -(side * cos(th)))
+ * (= -side * (-sin th, cos th)) and the tangent t = (-n_y, n_x).
+ *
+ * Response at the contact corner.  Staged before anything is written: c, s; the world velocity u_x = c*vx - s*vy, u_y = s*vx + c*vy;
+ * w = psiDot; m and Iz (plant row words 2 and 3); r = r_k.  With yaw_response == 0, r is taken as (0, 0) in everything below and psiDot
+ * is never written: the interactions' "through the centres" form.
+ *   Normal impulse:  v_c = (u_x + w * -r_y, u_y + w * r_x);  vn = v_cx*n_x + v_cy*n_y;  rn = r_x*n_y - r_y*n_x;
+ *     kn = 1/m + (rn*rn)/Iz;  Jn = vn < 0 ? (-(1 + restitution) * vn) / kn : 0.
+ *     u' = (u_x + (Jn/m)*n_x, u_y + (Jn/m)*n_y);  w' = w + (rn*Jn)/Iz.
+ *   Friction impulse, from the velocity after the normal impulse:  v_c' = (u'_x + w' * -r_y, u'_y + w' * r_x);
+ *     vt = v_c'x*t_x + v_c'y*t_y;  rt = r_x*t_y - r_y*t_x;  kt = 1/m + (rt*rt)/Iz;  lim = friction * Jn;
+ *     Jt = -vt / kt, then lim where Jt > lim, then -lim where Jt < -lim.
+ *     u'' = (u'_x + (Jt/m)*t_x, u'_y + (Jt/m)*t_y);  w'' = w' + (rt*Jt)/Iz.
+ * One pass, normal then friction.  Each step moves along its own impulse towards that direction's energy minimum and never beyond
+ * it, so the pair cannot add kinetic energy; a decoupled one-shot friction formula could.
+ * Written for a vehicle with a penetrating corner:  vx = max(c*u''_x + s*u''_y, 0) (the plant's vx is never negative),
+ * vy = -s*u''_x + c*u''_y,  psiDot = w'' when yaw_response != 0,  x += (push*depth)*n_x,  y += (push*depth)*n_y.  A penetrating but
+ * separating corner (vn >= 0) gets the push and no impulse (Jn = Jt = 0).  yaw, ax, ay are never written.  A vehicle without a
+ * penetrating corner keeps every state word bit for bit.
+ *
+ * Outputs per vehicle, channel-major and vehicle-minor as the standings: f64 [LPVMPC_WALL_F64][B] = DEPTH (of the contact corner, 0
+ * without one), IMPULSE (|Jn| of this tick), IMPULSE_TOTAL, MAX_IMPULSE (since the attach); i32 [LPVMPC_WALL_I32][B] = HIT (0 / 1: a
+ * penetrating corner this tick), SIDE (+1 / -1, 0 without a hit), CORNER (0 .. 3, -1: none), HIT_TICKS, FIRST_HIT_TICK (-1: none),
+ * OUTSIDE (1: the vehicle takes part and no row accepts its centre (x, y) within wall_ey + reach).  IMPULSE_TOTAL, MAX_IMPULSE,
+ * HIT_TICKS and FIRST_HIT_TICK are carried.  A vehicle that does not take part on a tick reads 0 in DEPTH, IMPULSE, HIT, SIDE and
+ * OUTSIDE and -1 in CORNER, and keeps its carried words.
+ *
+ * Configuration (lpvmpc_wall_default_config: margin 0.25, reach 0.5, half_length 0.4, half_width_car 0.2 (the heats' footprint),
+ * restitution 0.2, friction 0.3, push 0.5, yaw_response 1; invented values of the right order): margin >= 0, reach > 0,
+ * half_length > 0, half_width_car > 0, restitution in [0, 1], friction >= 0, push in [0, 1], yaw_response 0 / 1, reserved 0.  The
+ * margin is the caller's trade: with the race's half_width 0.3 / slack 0.15 the default leaves the centre of a car that runs along
+ * the wall at |ey| <= 0.35, inside what the controller's measurement locates; a larger margin lets a car slide to where
+ * Map.getLocalPosition loses it before the wall stops it, a smaller one makes the walls touch cars that merely run wide.
+ *
+ * lpvmpc_race_walls attaches the walls to the race of the path handle from the next tick on; attaching again replaces the binding
+ * (counters start anew), cfg == NULL detaches.  It needs a race with a plant table (the lpvmpc_race_init_vehicles / _tyres starts: m
+ * and Iz).  Refused with LPVMPC_E_ARG, the race left as it was: no race on the handle, no plant table, a config word that is not finite
+ * or outside its range, reserved != 0.  The binding is built whole and then installed; the race owns it and frees it.  Attach and
+ * detach are independent of heats, interactions and disturbances, in any order.  While attached lpvmpc_race_tick issues one more
+ * launch, behind the disturbances' and the interactions' and in front of the command / plant kernel; with nothing attached a tick
+ * issues exactly the launches it always did.  lpvmpc_race_snapshot, _restore and _clone work while attached: the blob and its version
+ * do not change, and the counters and outputs belong to the binding's slots (a restore or a clone leaves them as they are).
+ * lpvmpc_race_walls_read synchronises and copies the two output planes (either pointer may be NULL); refused with LPVMPC_E_ARG while
+ * nothing is attached.
+ *
+ * lpvmpc_wall_step_batch is one tick of the same kernel on caller-supplied data: plant [B][8] in / out, plant_params
+ * [B][LPVMPC_PLANT_WORDS] (words 2 and 3 are read), nstep [B] or NULL (every vehicle steps), the carried state carry_f64
+ * [LPVMPC_WALL_CARRY_F64][B] / carry_i32 [LPVMPC_WALL_CARRY_I32][B] in / out (just attached: zeros, FIRST_HIT_TICK -1) and the output
+ * planes.  The track is the handle's own with half_width, or, when tracks are bound to the handle (B vehicles), each vehicle's palette
+ * entry and its half width (half_width is then ignored).  It needs a handle that runs no fleet, cascade or race. */
+#define LPVMPC_WALL_F64                  4
+#define LPVMPC_WALL_DEPTH                0
+#define LPVMPC_WALL_IMPULSE              1
+#define LPVMPC_WALL_IMPULSE_TOTAL        2
+#define LPVMPC_WALL_MAX_IMPULSE          3
+#define LPVMPC_WALL_I32                  6
+#define LPVMPC_WALL_HIT                  0
+#define LPVMPC_WALL_SIDE                 1
+#define LPVMPC_WALL_CORNER               2
+#define LPVMPC_WALL_HIT_TICKS            3
+#define LPVMPC_WALL_FIRST_HIT_TICK       4
+#define LPVMPC_WALL_OUTSIDE              5
+#define LPVMPC_WALL_CARRY_F64            2
+#define LPVMPC_WALL_CARRY_IMPULSE_TOTAL  0
+#define LPVMPC_WALL_CARRY_MAX_IMPULSE    1
+#define LPVMPC_WALL_CARRY_I32            2
+#define LPVMPC_WALL_CARRY_HIT_TICKS      0
+#define LPVMPC_WALL_CARRY_FIRST_HIT_TICK 1
+typedef struct lpvmpc_wall_config {
+    double  margin;            /* >= 0, metres: the wall's offset beyond half_width */
+    double  reach;             /* > 0, metres: how far beyond the wall a corner is still located */
+    double  half_length;       /* > 0: footprint half length */
+    double  half_width_car;    /* > 0: footprint half width */
+    double  restitution;       /* [0, 1] */
+    double  friction;          /* >= 0 */
+    double  push;              /* [0, 1]: the share of the depth removed per tick */
+    int32_t yaw_response;      /* 0 / 1: 0 applies the impulses through the centre and leaves psiDot alone */
+    int32_t reserved;          /* 0 */
+} lpvmpc_wall_config;
+void lpvmpc_wall_default_config(lpvmpc_wall_config *cfg);
+int  lpvmpc_race_walls(lpvmpc_handle *path, const lpvmpc_wall_config *cfg /* NULL: detach */);
+int  lpvmpc_race_walls_read(lpvmpc_handle *path, double *f64, int32_t *i32);
+int  lpvmpc_wall_step_batch(lpvmpc_handle *h, int32_t B, const lpvmpc_wall_config *cfg, double half_width, int32_t t,
+                            double *plant /* [B][8] in/out */, const double *plant_params /* [B][7] */,
+                            const int32_t *nstep /* [B] or NULL: all step */, double *carry_f64, int32_t *carry_i32, double *f64,
+                            int32_t *i32);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,8 +42,12 @@ RaceFleet(heats=..., interactions=...)): heats of SIZE consecutive vehicles (on 
 one track) whose members take drag off each other in the wake and exchange impulses where their footprints overlap; WORD=VALUE sets
 configuration words (draft_gain, wake_length, wake_half_width, contact, restitution, push).  The baseline race keeps to itself.  The
 report gains one line: vehicles hit, total hit ticks, drafting ticks.  Without the flag the output is today's.
+--walls [WORD=VALUE,...] puts walls at the edges of the swept race's tracks (lpvmpc_race_walls, RaceFleet(walls=...)): a corner of a
+footprint beyond half_width + margin gets an impulse there and the car is pushed back; WORD=VALUE sets configuration words (margin, reach,
+half_length, half_width_car, restitution, friction, push, yaw_response).  The baseline race has none.  The report gains one line:
+vehicles that hit a wall, total hit ticks, the largest impulse, vehicles outside at the end.  Without the flag the output is today's.
 Usage: tools/robustness_sweep.py [--B 8192] [--laps 2] [--seed 1] [--max-ticks 3000] [--model nominal|plant|noisy:REL]
-       [--tyre linear|pacejka] [--estimator nominal|plant] [--disturbance SPEC] [--sensor-faults SPEC] [--interactions SPEC] [--respawn K] [--out FILE]"""
+       [--tyre linear|pacejka] [--estimator nominal|plant] [--disturbance SPEC] [--sensor-faults SPEC] [--interactions SPEC] [--walls [SPEC]] [--respawn K] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -68,6 +72,8 @@ def main():
     ap.add_argument("--sensor-faults", default=None, help="gps_outage:LEN_S | enc_outage:LEN_S | gps_loss:P | imu_bias:W | imu_drift:W | enc_scale:S (joined with +)")
     ap.add_argument("--interactions", default=None, metavar="SIZE[:WORD=VALUE,...]",
                     help="heats of SIZE consecutive vehicles whose members draft and hit each other, e.g. 16 or 16:draft_gain=0.5,contact=0")
+    ap.add_argument("--walls", default=None, nargs="?", const="", metavar="WORD=VALUE,...",
+                    help="walls at the track's edges with the default configuration, or e.g. margin=0.2,restitution=0.5")
     ap.add_argument("--respawn", type=int, default=None, help="refill the lost slots every K ticks (0: never, but report the alive vehicle-ticks)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -131,6 +137,10 @@ def main():
             heat[on] = (heat.max() + 1 if t else 0) + np.arange(on.shape[0]) // int(size)
         inter = dict(heats=dict(heat=heat), interactions=cfg or True)
     contacts = {}
+    if a.walls is not None:
+        wcfg = {k: (int(v) if k == "yaw_response" else float(v)) for k, v in (w.split("=") for w in a.walls.split(",") if w)}
+        inter = dict(inter or {}, walls=wcfg or True)
+    walled = {}
 
     fork = dict(slots=0, alive=0)                                     # of the swept race, with --respawn
 
@@ -161,9 +171,13 @@ def main():
     ph_nom = base.state()["phase"]
     base.close()
     fleet, ticks, wall = race(rows, model_rows, "plant" if a.estimator == "plant" else None, dist, a.respawn, faults, inter)
-    if inter:
+    if a.interactions:
         io = fleet.interactions()
         contacts.update(hit=int((io["hit_ticks"] > 0).sum()), hit_ticks=int(io["hit_ticks"].sum()), draft_ticks=int(io["draft_ticks"].sum()))
+    if a.walls is not None:
+        wo = fleet.walls()
+        walled.update(hit=int((wo["hit_ticks"] > 0).sum()), hit_ticks=int(wo["hit_ticks"].sum()), most=float(wo["max_impulse"].max()),
+                      outside=int(wo["outside"].sum()))
     ph = fleet.state()["phase"]
     lt = fleet.lap_times()[:, 1:a.laps + 1]                          # racing laps, seconds (NaN: not completed)
     rmse = fleet.lap_stats()["rmse_ey"][:, 1:a.laps + 1] if not a.respawn else np.full(lt.shape, np.nan)
@@ -182,7 +196,10 @@ def main():
              "# %d ticks (%.1f s wall); all vehicles: %.1f %% finished, %.1f %% lost, %.1f %% still running; racing lap time median %.3f s, "
              "p90 %.3f s; RMSE_ey median %.4f m" % (ticks, wall, 100 * fin.mean(), 100 * lost.mean(), 100 * (ph < 2).mean(),
                                                      np.nanmedian(lt), np.nanpercentile(lt, 90), np.nanmedian(rmse)),
-             ] + ([] if not inter else [
+             ] + ([] if a.walls is None else [
+             "# the swept race's tracks have walls (--walls %s): %d vehicles hit one, %d hit ticks, largest impulse %.3g N s, %d vehicles "
+             "outside at the end; the baseline race's tracks have none." % (a.walls, walled["hit"], walled["hit_ticks"], walled["most"], walled["outside"])]) + (
+             [] if not a.interactions else [
              "# the swept race's vehicles act on each other (--interactions %s): %d vehicles hit, %d hit ticks, %d drafting ticks; the baseline "
              "race's do not." % (a.interactions, contacts["hit"], contacts["hit_ticks"], contacts["draft_ticks"])]) + ([] if a.respawn is None else [
              "# --respawn %d: %d slots respawned, %d alive vehicle-ticks, %.4g alive vehicle-ticks/s over the %d ticks%s"
