@@ -20,17 +20,13 @@ __global__ void __launch_bounds__(64) local_position_kernel(const DevCfg *__rest
                                                             double hw, double slack, double *__restrict__ out) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    double s, ey, epsi; int inside;
-    local_position(*cp, hw, slack, in[b * 3 + 0], in[b * 3 + 1], in[b * 3 + 2], s, ey, epsi, inside);
-    out[b * 4 + 0] = s; out[b * 4 + 1] = ey; out[b * 4 + 2] = epsi; out[b * 4 + 3] = inside;
+    local_position_body(*cp, hw, slack, b, in, out);
 }
 __global__ void __launch_bounds__(64) global_position_kernel(const DevCfg *__restrict__ cp, int B, const double *__restrict__ in,
                                                              double *__restrict__ out) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    double x, y, th;
-    global_position(*cp, in[b * 2 + 0], in[b * 2 + 1], x, y, th);
-    out[b * 3 + 0] = x; out[b * 3 + 1] = y; out[b * 3 + 2] = th;
+    global_position_body(*cp, b, in, out);
 }
 // predicted_vectors_generation (CMAIN:510-553): 20 fixed rows built on the local state; delta seeds are zero
 __constant__ double kSeedDvx[20] = {0.05, 0.2, 0.4, 0.6, 0.7, 0.8, 0.9, 0.9, 0.9, 0.9, 0.9, 0.9, 0.9, 0.9, 0.9, 0.9, 0.9, 0.9, 0.9, 0.9};

@@ -31,6 +31,27 @@
 
 namespace lpvmpc {
 
+// Some of the kernels that read the track share their body with a bound form on per-vehicle tracks (track_vehicles.hip).  Kernel
+// arguments differ between the two, so the kernels stay apart; the body is a function template over the track source `src`
+// (track_geometry.hpp, track_view), forced inline and instantiated once per object.  Which pairs share is decided by the device code:
+// a pair whose kernels do not all keep their instruction stream stays restated, with the measurement in its comment ("One
+// source, one form per object").
+
+// the stand-alone transforms of vehicle b (closed_loop.hip, track_vehicles.hip): in [B][3] -> out [B][4], in [B][2] -> out [B][3]
+template <class Src>
+__device__ __forceinline__ void local_position_body(const Src &src, double hw, double slack, int b, const double *in, double *out) {
+    const auto &v = track_view(src, b, hw, slack);
+    double s, ey, epsi; int inside;
+    local_position(v, hw, slack, in[b * 3 + 0], in[b * 3 + 1], in[b * 3 + 2], s, ey, epsi, inside);
+    out[b * 4 + 0] = s; out[b * 4 + 1] = ey; out[b * 4 + 2] = epsi; out[b * 4 + 3] = inside;
+}
+template <class Src>
+__device__ __forceinline__ void global_position_body(const Src &src, int b, const double *in, double *out) {
+    double x, y, th;
+    global_position(track_view(src, b), in[b * 2 + 0], in[b * 2 + 1], x, y, th);
+    out[b * 3 + 0] = x; out[b * 3 + 1] = y; out[b * 3 + 2] = th;
+}
+
 // n_sub simulator steps under u = [motor, servo] per vehicle (lpvmpc_plant_step_batch / _actuated_batch)
 template <bool kAct, bool kVeh = false, bool kTyre = false>
 __global__ void __launch_bounds__(64) plant_kernel(int B, double *__restrict__ plant, const double *__restrict__ u, PlantArg<kVeh, kTyre> pc, ActDev a) {
@@ -62,15 +83,26 @@ __global__ void __launch_bounds__(64) plant_kernel(int B, double *__restrict__ p
 // (s, ey, epsi) as LocalState[4], LocalState[3], LocalState[5], i.e. ey lands in the epsi slot and vice versa
 // (SURVEY quirk Q9); with q9_swap = 0 the slots are filled as the state definition says.
 // u_old = last command [servo, motor] (CMAIN:289-298 leaves exactly that in OldSteering[0] / OldAccelera[0]).
+// The delayed form's body, shared with cl_measure_trk_kernel.  The plain form keeps its two statements in the kernel: through this body
+// (with kAct as a flag) cl_measure_kernel<false> of closed_loop.o kept its 1638 instructions but had three of them scheduled elsewhere
+template <class Src>
+__device__ __forceinline__ void cl_measure_body(const Src &src, int b, const double *plant, const double *cmd, double hw, double slack, int q9_swap,
+                                                double *local_state, double *u_old, int sd) {
+    const auto &v = track_view(src, b, hw, slack);
+    cl_local(v, hw, slack, q9_swap, plant + (size_t)b * 8, local_state + (size_t)b * 6);
+    uold_push(u_old + (size_t)b * (2 + sd), sd, cmd[b * 2 + 0], cmd[b * 2 + 1]);
+}
 template <bool kAct>
 __global__ void __launch_bounds__(64) cl_measure_kernel(const DevCfg *__restrict__ cp, int B, const double *__restrict__ plant,
                                                         const double *__restrict__ cmd, double hw, double slack, int q9_swap,
                                                         double *__restrict__ local_state, double *__restrict__ u_old, int sd) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    cl_local(*cp, hw, slack, q9_swap, plant + (size_t)b * 8, local_state + (size_t)b * 6);
-    if constexpr (kAct) uold_push(u_old + (size_t)b * (2 + sd), sd, cmd[b * 2 + 0], cmd[b * 2 + 1]);
-    else { u_old[b * 2 + 0] = cmd[b * 2 + 0]; u_old[b * 2 + 1] = cmd[b * 2 + 1]; }
+    if constexpr (kAct) cl_measure_body(*cp, b, plant, cmd, hw, slack, q9_swap, local_state, u_old, sd);
+    else {
+        cl_local(*cp, hw, slack, q9_swap, plant + (size_t)b * 8, local_state + (size_t)b * 6);
+        u_old[b * 2 + 0] = cmd[b * 2 + 0]; u_old[b * 2 + 1] = cmd[b * 2 + 1];
+    }
 }
 
 // command = first predicted input (CMAIN:381-386: servo = uPred[0,0], motor = uPred[0,1]), n_sub simulator steps under it

@@ -72,7 +72,9 @@ __device__ __forceinline__ void interaction_tick(const InterDev &h, InterLds<BS>
                 if (w > best) { best = w; leader = wj; }                    // ascending j: the lowest index attaining the max
             }
             // contact: footprint_sep of heats.hip restated (the lower index is the first rectangle, a), keeping which gap is the
-            // largest and the signed projection behind it
+            // largest and the signed projection behind it.  One function that returns the four gaps and projections to both files
+            // was tried: interaction_tick_kernel<64> 1190 -> 1214 and <256> 1191 -> 1215 instructions, and in heats.o the six kernels
+            // (heat_tick_kernel, heat_tick_trk_kernel, heat_step_kernel, each <64> and <256>) gained one or two each
             const bool lo = j < i;
             const double xa = lo ? xj : x, ya = lo ? yj : y, ca = lo ? cj : cs, sa = lo ? sj : sn;
             const double xb = lo ? x : xj, yb = lo ? y : yj, cb = lo ? cs : cj, sb = lo ? sn : sj;

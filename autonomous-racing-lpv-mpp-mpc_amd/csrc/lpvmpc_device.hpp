@@ -39,16 +39,18 @@ __device__ inline double wrap_track_s(double s, double L) {
     for (int it = 0; it < kMaxWrapLaps && s > L; ++it) s -= L;
     return s;
 }
-__device__ inline double track_curvature(const DevCfg &c, double s) {
-    const int rows = c.track_rows;
-    const double L = c.track[(rows - 1) * 6 + 3] + c.track[(rows - 1) * 6 + 4];
+// The track functions are written once, on a table T [rows][6] of PointAndTangent rows; the configuration's own table (here) and a
+// palette entry (track_view.hpp) forward to them.
+__device__ inline double track_curvature(const double *T, int rows, double s) {
+    const double L = T[(rows - 1) * 6 + 3] + T[(rows - 1) * 6 + 4];
     s = wrap_track_s(s, L);
     for (int i = 0; i < rows; ++i) {
-        const double st = c.track[i * 6 + 3], ln = c.track[i * 6 + 4];
-        if (s >= st && s < st + ln) return c.track[i * 6 + 5];
+        const double st = T[i * 6 + 3], ln = T[i * 6 + 4];
+        if (s >= st && s < st + ln) return T[i * 6 + 5];
     }
     return __builtin_nan("");
 }
+__device__ __forceinline__ double track_curvature(const DevCfg &c, double s) { return track_curvature(c.track, c.track_rows, s); }
 
 // offsets of the tuning words within their block (DevCfg::Q onward) and within a device row of the tuning table
 constexpr int kTuneWords = 64;               // = LPVMPC_TUNING_WORDS

@@ -161,11 +161,14 @@ __device__ inline void obs_stage_gains(double *lds, const double *__restrict__ g
 
 // controller measurement from the estimate (the estimator path's cl_measure_kernel): [max(vx, 0.01), vy, psiDot] and the map's
 // local frame of (x, y, yaw) with quirk Q9 as in cl_local
-__device__ inline void obs_local_state(const DevCfg &c, double hw, double slack, int q9_swap, const double *e, double *ls) {
+__device__ inline void obs_local_state(const double *T, int rows, double hw, double slack, int q9_swap, const double *e, double *ls) {
     double s, ey, epsi; int inside;
-    local_position(c, hw, slack, e[3], e[4], e[5], s, ey, epsi, inside);
+    local_position(T, rows, hw, slack, e[3], e[4], e[5], s, ey, epsi, inside);
     ls[0] = e[0] < 0.01 ? 0.01 : e[0]; ls[1] = e[1]; ls[2] = e[2];
     ls[3] = q9_swap ? ey : epsi; ls[4] = s; ls[5] = q9_swap ? epsi : ey;
+}
+__device__ __forceinline__ void obs_local_state(const DevCfg &c, double hw, double slack, int q9_swap, const double *e, double *ls) {
+    obs_local_state(c.track, c.track_rows, hw, slack, q9_swap, e, ls);
 }
 
 }  // namespace lpvmpc

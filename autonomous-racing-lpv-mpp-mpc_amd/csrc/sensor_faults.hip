@@ -7,7 +7,13 @@
 // actuated, per-vehicle plant row, tyre row (the _tyres starts), with the configuration's estimator or the per-vehicle one.  The
 // bodies are restated here, not shared with fleet_kernels.hpp through a device function: the objects that instantiate those
 // templates keep the code they have alone ("Sensor faults"), and tests/test_gpu_sensor_faults.py holds the two
-// together word for word through an all-off row.  One lane per vehicle, 64-lane blocks; the fault rows are word-major [word][B], so a
+// together word for word through an all-off row.  That was measured (tools/isa_equal.py): with the race kernel's body as a
+// forced-inline function template over the sensor stage, called by both kernels, every form moved -- race_command_plant_observe_kernel
+// <false> 6371 -> 6378 instructions and 24 B of scratch, which the build's gate refuses, <true> 5720 -> 5730, <true, true> 5732 -> 5740,
+// <true, true, true> 6358 -> 6347, <true, true, false, true> 6747 -> 6750, <true, true, true, true> 7361 -> 7383, and here
+// race_command_plant_observe_faulted_kernel<false> 6778 -> 6788, <true> 7805 -> 7816.  The fleet kernel's body moved every form of
+// cl_command_plant_observe_kernel as a function already, without a stage parameter (track_vehicles.hip has the counts), so the fleet
+// pair was not taken further.  One lane per vehicle, 64-lane blocks; the fault rows are word-major [word][B], so a
 // wavefront's loads of one word coalesce, and a vehicle's 12 words are loaded once, in front of the sub-step loop.  The gain words
 // are staged in LDS as in the kernels restated, behind the same compiler barrier.  Gated: no scratch.
 #include "sensor_faults.hpp"

@@ -35,11 +35,19 @@ __device__ inline double compute_angle(double p1x, double p1y, double ox, double
 }
 __device__ inline double norm2(double x, double y) { return sqrt(x * x + y * y); }
 
+// The functions that read the track are written once, on a table T [rows][6] of PointAndTangent rows; the forms on the configuration's
+// own table (DevCfg::track) follow each, the forms on a palette entry are in track_view.hpp.  All of them forward, but for
+// plan_first_one (see there).
+//
+// A kernel body shared by a form on the handle's own track and a form on per-vehicle tracks is a template over its track source `src`,
+// the configuration or the binding (TrackDev, track_view.hpp), and looks the vehicle's track up with track_view(src, b, hw, slack)
+// where the bound form does.  The configuration is its own view, and hw and slack stay the caller's.
+__device__ __forceinline__ const DevCfg &track_view(const DevCfg &c, int, double &, double &) { return c; }
+__device__ __forceinline__ const DevCfg &track_view(const DevCfg &c, int) { return c; }
+
 // Map.getLocalPosition: (x, y, psi) -> (s, ey, epsi, inside); 10000 sentinels when off the track (TRACK:376-379)
-__device__ __forceinline__ void local_position(const DevCfg &c, double hw, double slack, double x, double y, double psi,
-                                      double &s, double &ey, double &epsi, int &inside) {
-    const double *T = c.track;
-    const int rows = c.track_rows;
+__device__ __forceinline__ void local_position(const double *T, int rows, double hw, double slack, double x, double y, double psi,
+                                               double &s, double &ey, double &epsi, int &inside) {
     int done = 0;
     s = ey = epsi = 0.0;
     for (int i = 0; i < rows && !done; ++i) {
@@ -80,11 +88,13 @@ __device__ __forceinline__ void local_position(const DevCfg &c, double hw, doubl
     inside = done;
     if (!done) { s = 10000; ey = 10000; epsi = 10000; }
 }
+__device__ __forceinline__ void local_position(const DevCfg &c, double hw, double slack, double x, double y, double psi,
+                                               double &s, double &ey, double &epsi, int &inside) {
+    local_position(c.track, c.track_rows, hw, slack, x, y, psi, s, ey, epsi, inside);
+}
 
 // Map.getGlobalPosition: (s, ey) -> (x, y, theta).  Where the reference fails (no segment contains s) NaNs are returned.
-__device__ inline void global_position(const DevCfg &c, double s, double ey, double &x, double &y, double &th) {
-    const double *T = c.track;
-    const int rows = c.track_rows;
+__device__ inline void global_position(const double *T, int rows, double s, double ey, double &x, double &y, double &th) {
     const double L = T[(rows - 1) * 6 + 3] + T[(rows - 1) * 6 + 4];
     s = wrap_track_s(s, L);      // NaN beyond kMaxWrapLaps laps / non-finite s: no segment below, NaNs returned
     int i = -1;
@@ -108,6 +118,9 @@ __device__ inline void global_position(const DevCfg &c, double s, double ey, dou
         y = cy + (fabs(r) - d * ey) * sin(a0 + d * span);
         th = ang + d * span;
     }
+}
+__device__ __forceinline__ void global_position(const DevCfg &c, double s, double ey, double &x, double &y, double &th) {
+    global_position(c.track, c.track_rows, s, ey, x, y, th);
 }
 
 // Simulator.f: st = [x y vx vy ax ay yaw psiDot], u = [a, delta]
@@ -235,11 +248,14 @@ __device__ inline bool plant_finite(const double *p) {
 
 // ---- per-vehicle measurement recipes shared by the fleet engines (closed_loop.hip, handoff.hip, race.hip) ----
 // lap-0 measurement (CMAIN:183-188): local state from the plant's ground truth, vx clamped at 0.01; q9_swap = SURVEY quirk Q9
-__device__ __forceinline__ void cl_local(const DevCfg &c, double hw, double slack, int q9_swap, const double *p, double *ls) {
+__device__ __forceinline__ void cl_local(const double *T, int rows, double hw, double slack, int q9_swap, const double *p, double *ls) {
     double s, ey, epsi; int inside;
-    local_position(c, hw, slack, p[0], p[1], p[6], s, ey, epsi, inside);
+    local_position(T, rows, hw, slack, p[0], p[1], p[6], s, ey, epsi, inside);
     ls[0] = p[2] < 0.01 ? 0.01 : p[2]; ls[1] = p[3]; ls[2] = p[7];
     ls[3] = q9_swap ? ey : epsi; ls[4] = s; ls[5] = q9_swap ? epsi : ey;
+}
+__device__ __forceinline__ void cl_local(const DevCfg &c, double hw, double slack, int q9_swap, const double *p, double *ls) {
+    cl_local(c.track, c.track_rows, hw, slack, q9_swap, p, ls);
 }
 
 // LapNumber >= 1 measurement (CMAIN:198-248): yaw unwound by the lap counter, Body_Frame_Errors against the first sample of
@@ -255,7 +271,11 @@ __device__ __forceinline__ void tt_local(const DevCfg &c, const double *p, int l
 }
 
 // planner's first tick (PMAIN:137-141, :152-162, seed of PMAIN:465-505); c is the planner's configuration.  x0 [5],
-// xlast [N][6], delta [N] of one vehicle
+// xlast [N][6], delta [N] of one vehicle.  track_view.hpp restates it on a view.  One source was tried (this body forced inline into two
+// `inline` forwards of these signatures, on a table pointer and as a template over the track source): race.o and track_race.o call
+// plan_first_one as a function of its own, and in both attempts that function kept its instruction count (1896 in race.o, 1901 in
+// track_race.o) but had one instruction, the seed loop's v_lshl_add_u64 of the xlast row pointer, scheduled one place later; no kernel
+// moved, handoff.o (where it is inlined) stayed identical
 __device__ inline void plan_first_one(const DevCfg &c, const double *p, double hw, double slack, int q9_swap, double accel_rate,
                                       double *x, double *xlast, double *delta) {
     const int N = c.N;

@@ -10,6 +10,18 @@
 // same order, compiled as race.o, handoff.o and record.o are, so that a palette entry equal to a handle's table gives that handle's
 // words.  race_command_plant* and tt_measure_kernel read no track and have no form here.  Their own object, so that race.o,
 // actuator.o, handoff.o and record.o keep the code they have alone.
+//
+// One source for each pair was tried, the body as a forced-inline function template over the track source (the configuration, or the
+// binding) that both kernels call, and measured on the device code (tools/isa_equal.py; DESIGN.md, "One source, one form per object").
+// None of the four pairs kept its instruction streams, so all four stay restated (instructions before -> after):
+//   race_measure          race_measure_kernel<false> 3254 -> 3365 (race.o), <true> 3279 -> 3390 (actuator.o), race_measure_trk_kernel
+//                         3218 -> 3311
+//   race_plan_start       plan_first_one, which both objects call as a function, was inlined instead: race_plan_start_kernel
+//                         370 -> 2215, race_plan_start_trk_kernel 388 -> 2174
+//   plan_pose             plan_pose_kernel 1901 -> 1901 (handoff.o) and plan_pose_trk_kernel 1894 -> 1894, both with the entry's address
+//                         arithmetic scheduled elsewhere and a loop's compare inverted
+//   race_record           race_record_kernel 2048 -> 2046 (record.o), race_record_trk_kernel 2024 -> 2022 (other registers), with the
+//                         recorder's argument by reference or by value
 #include "record.hpp"
 #include "track_view.hpp"
 

@@ -5,13 +5,22 @@
 //   cl_measure_trk_kernel                                   cl_measure_kernel<true> of fleet_kernels.hpp
 //   cl_command_plant_measure_trk_kernel                     cl_command_plant_measure_kernel<true, true, true>
 //   cl_command_plant_observe_trk_kernel<kObsVeh>            cl_command_plant_observe_kernel<true, true, true, kObsVeh>
-// The fleet forms exist for the most general start only (lpvmpc_cl_init_tyres: delayed forms with the plant and tyre tables), so
-// each restates that one form of its template with the vehicle's track view where the template passes the configuration -- the
-// same statements in the same order, compiled as tyre.o and observer_vehicles.o are, so that a palette entry equal to a handle's
-// table gives that handle's words.  Restated and not added to fleet_kernels.hpp as one more template flag: every object that
-// includes the header would have to be shown unchanged again, and a track argument in the shared signature changes the kernel
-// arguments of every form.  Their own object, so that closed_loop.o, tyre.o and observer_vehicles.o keep the code they have alone.
-#include "observer_device.hpp"
+// The fleet forms exist for the most general start only (lpvmpc_cl_init_tyres: delayed forms with the plant and tyre tables).  They are
+// kernels of their own and no further template flag of fleet_kernels.hpp: a track argument in the shared signature changes the
+// kernel arguments of every form.  Their own object, so that closed_loop.o, tyre.o and observer_vehicles.o keep the code they have
+// alone, compiled as those are, so that a palette entry equal to a handle's table gives that handle's words.
+//
+// The two transforms and cl_measure_trk_kernel share their body with the original (fleet_kernels.hpp: a function template over the
+// track source, here the binding).  The two command / plant kernels restate their one form of the template with the vehicle's track
+// view where the template passes the configuration, the same statements in the same order: with one body for both, every delayed
+// form of the template moved (tools/isa_equal.py; DESIGN.md, "One source, one form per object"; instructions before -> after):
+//   cl_command_plant_measure   <true> 3085 -> 3088 (actuator.o), <true, true> 3098 -> 3100 (plant_params.o), <true, true, true>
+//                              3623 -> 3625 (tyre.o), cl_command_plant_measure_trk_kernel 3603 -> 3605; with the plant and actuator
+//                              arguments by value 3086, 3099, 3624 and 3601
+//   cl_command_plant_observe   <false> 6807 -> 6806 (observer.o), <true> 7345 -> 7333, <true, true> 7288 -> 7297, <true, true, true>
+//                              7889 -> 7893, <true, true, false, true> 8294 -> 8317 and <true, true, true, true> 8921 -> 8891
+//                              (observer_vehicles.o), cl_command_plant_observe_trk_kernel<false> 9148 -> 9140, <true> 8936 -> 8934
+#include "fleet_kernels.hpp"
 #include "track_view.hpp"
 
 namespace lpvmpc {
@@ -19,18 +28,12 @@ namespace lpvmpc {
 __global__ void __launch_bounds__(64) local_position_trk_kernel(TrackDev trk, int B, const double *__restrict__ in, double *__restrict__ out) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    double hw, slack;
-    const TrackView v = track_view(trk, b, hw, slack);
-    double s, ey, epsi; int inside;
-    local_position(v, hw, slack, in[b * 3 + 0], in[b * 3 + 1], in[b * 3 + 2], s, ey, epsi, inside);
-    out[b * 4 + 0] = s; out[b * 4 + 1] = ey; out[b * 4 + 2] = epsi; out[b * 4 + 3] = inside;
+    local_position_body(trk, 0.0, 0.0, b, in, out);
 }
 __global__ void __launch_bounds__(64) global_position_trk_kernel(TrackDev trk, int B, const double *__restrict__ in, double *__restrict__ out) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    double x, y, th;
-    global_position(track_view(trk, b), in[b * 2 + 0], in[b * 2 + 1], x, y, th);
-    out[b * 3 + 0] = x; out[b * 3 + 1] = y; out[b * 3 + 2] = th;
+    global_position_body(trk, b, in, out);
 }
 
 // first tick of a fleet without an estimator: the measurement of the start state and the controller's history
@@ -38,10 +41,7 @@ __global__ void __launch_bounds__(64) cl_measure_trk_kernel(TrackDev trk, int B,
                                                             int q9_swap, double *__restrict__ local_state, double *__restrict__ u_old, int sd) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    double hw, slack;
-    const TrackView v = track_view(trk, b, hw, slack);
-    cl_local(v, hw, slack, q9_swap, plant + (size_t)b * 8, local_state + (size_t)b * 6);
-    uold_push(u_old + (size_t)b * (2 + sd), sd, cmd[b * 2 + 0], cmd[b * 2 + 1]);
+    cl_measure_body(trk, b, plant, cmd, 0.0, 0.0, q9_swap, local_state, u_old, sd);
 }
 
 // command, n_sub simulator steps through the actuator stage with the vehicle's plant and tyre rows, then the next tick's measurement

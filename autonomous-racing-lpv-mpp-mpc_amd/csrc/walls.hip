@@ -17,6 +17,9 @@
 // Its own translation unit, compiled with -ffp-contract=off as interactions.o: every product and sum of the model is rounded on its
 // own.  row_locate restates the row arithmetic of local_position (track_geometry.hpp / track_view.hpp) -- the straight and arc
 // branches with compute_angle and norm2 of that header -- with (ey, th) as results, no s / epsi, the caller's bound and no early exit.
+// One row function for both (local_position as a loop over it, epsi from its th) was tried: it moved all fifteen objects that inline
+// local_position, each kernel by about 1100 instructions (local_position_kernel 1612 -> 2741, race_record_kernel 2048 -> 3158), and
+// wall_tick_kernel 4271 -> 4321.
 #include "walls.hpp"
 #include "wave_ops.hpp"
 
