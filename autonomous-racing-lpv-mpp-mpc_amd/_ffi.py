@@ -146,6 +146,19 @@ WALL_CARRY_F64_NAMES = ("impulse_total", "max_impulse")
 WALL_CARRY_I32_NAMES = ("hit_ticks", "first_hit_tick")
 
 
+class ContactConfig(C.Structure):
+    """Mirror of ``struct lpvmpc_contact_config`` (include/lpvmpc.h)."""
+    _fields_ = [("friction", _d), ("yaw_response", _i), ("reserved", _i)]
+
+
+# contact model (LPVMPC_CONTACT_*): planes f64 [CONTACT_F64][B] / i32 [CONTACT_I32][B] and the carried state of the batch form
+CONTACT_F64, CONTACT_I32, CONTACT_CARRY_F64, CONTACT_CARRY_I32 = 3, 2, 1, 1
+CONTACT_F64_NAMES = ("friction_impulse", "yaw_kick", "yaw_kick_total")
+CONTACT_I32_NAMES = ("partners", "max_partners")
+CONTACT_CARRY_F64_NAMES = ("yaw_kick_total",)
+CONTACT_CARRY_I32_NAMES = ("max_partners",)
+
+
 # race recorder channels (LPVMPC_REC_*): f64 [REC_F64][B] and i32 [REC_I32][B] per record, named in channel order
 REC_F64, REC_I32 = 29, 8
 REC_PLANT, REC_LOCAL, REC_CMD, REC_REF, REC_TRACK, REC_EST = 0, 8, 14, 16, 20, 23
@@ -218,7 +231,8 @@ EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_d
            "lpvmpc_heats_default_config", "lpvmpc_race_heats", "lpvmpc_race_standings", "lpvmpc_heat_step_batch",
            "lpvmpc_sensor_fault_default_config", "lpvmpc_set_sensor_faults", "lpvmpc_sensor_faults_read", "lpvmpc_sensor_step_batch",
            "lpvmpc_interaction_default_config", "lpvmpc_race_interactions", "lpvmpc_race_interactions_read", "lpvmpc_interaction_step_batch",
-           "lpvmpc_wall_default_config", "lpvmpc_race_walls", "lpvmpc_race_walls_read", "lpvmpc_wall_step_batch")
+           "lpvmpc_wall_default_config", "lpvmpc_race_walls", "lpvmpc_race_walls_read", "lpvmpc_wall_step_batch",
+           "lpvmpc_contact_default_config", "lpvmpc_race_contact", "lpvmpc_race_contact_read", "lpvmpc_contact_step_batch")
 
 _lib = None
 
@@ -467,6 +481,16 @@ def load():
             getattr(lib, name).restype = C.c_int
     except AttributeError:
         pass
+    try:        # (nor the contact model)
+        lib.lpvmpc_contact_default_config.argtypes = [P(ContactConfig)]
+        lib.lpvmpc_contact_default_config.restype = None
+        lib.lpvmpc_race_contact.argtypes = [vp, P(ContactConfig)]
+        lib.lpvmpc_race_contact_read.argtypes = [vp, vp, vp]
+        lib.lpvmpc_contact_step_batch.argtypes = [vp, _i, _i, vp, P(HeatsConfig), P(InteractionConfig), P(ContactConfig), _i] + [vp] * 12
+        for name in ("lpvmpc_race_contact", "lpvmpc_race_contact_read", "lpvmpc_contact_step_batch"):
+            getattr(lib, name).restype = C.c_int
+    except AttributeError:
+        pass
     for name in ("lpvmpc_handoff_length", "lpvmpc_handoff_operators", "lpvmpc_handoff_setup", "lpvmpc_handoff_batch",
                  "lpvmpc_cascade_init", "lpvmpc_cascade_tick", "lpvmpc_cascade_read"):
         getattr(lib, name).restype = C.c_int
@@ -531,6 +555,12 @@ def default_interaction_config():
 def default_wall_config():
     cfg = WallConfig()
     load().lpvmpc_wall_default_config(C.byref(cfg))
+    return cfg
+
+
+def default_contact_config():
+    cfg = ContactConfig()
+    load().lpvmpc_contact_default_config(C.byref(cfg))
     return cfg
 
 

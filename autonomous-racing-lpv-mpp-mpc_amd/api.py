@@ -1043,6 +1043,67 @@ class BatchedSolver:
                                                           ptr(cf), ptr(ci), ptr(mu), ptr(f), ptr(i)))
         return plant, mu, I.interactions_dict(f, i), dict(f64=cf, i32=ci)
 
+    # -- contact model: the corner form of the car-to-car contact (lpvmpc_race_contact / _read, lpvmpc_contact_step_batch; contact.py) --
+    def race_contact(self, cfg=None, detach=False):
+        """Attach the contact model on top of the interactions from the next tick on (lpvmpc_race_contact): ``cfg`` a
+        ``contact.contact_config(...)`` result, a dict of its words, or None for the defaults.  Needs interactions attached with
+        ``contact=1``.  Attaching again replaces the binding; ``detach=True`` goes back to the centres form.  ``race_interactions`` and
+        ``race_heats`` detach the contact model."""
+        from . import contact as K
+        self._race_B("race_contact")
+        if detach:
+            self._chk(self._lib.lpvmpc_race_contact(self._h, None))
+            return
+        c = K.as_config(cfg)
+        self._chk(self._lib.lpvmpc_race_contact(self._h, C.byref(c)))
+
+    def race_contact_read(self):
+        """Synchronise and return the contact model's planes (lpvmpc_race_contact_read): a dict of [B] arrays named as
+        _ffi.CONTACT_F64_NAMES / CONTACT_I32_NAMES (friction_impulse, yaw_kick, yaw_kick_total; partners, max_partners) and the planes
+        f64 [3, B] / i32 [2, B].  A vehicle in no heat reads NaN and 0."""
+        from . import contact as K
+        B = self._race_B("race_contact_read")
+        f = np.empty((_ffi.CONTACT_F64, B)); i = np.empty((_ffi.CONTACT_I32, B), np.int32)
+        self._chk(self._lib.lpvmpc_race_contact_read(self._h, ptr(f), ptr(i)))
+        return K.contact_dict(f, i)
+
+    def contact_step(self, heat, plant, plant_params, t, cfg=None, contact=None, nstep=None, carry=None, contact_carry=None, n_heats=None,
+                     half_length=0.4, half_width=0.2):
+        """One tick of the contact model's kernel on the caller's data (lpvmpc_contact_step_batch): the arguments of
+        ``interaction_step`` (``plant_params``: m, Iz and mu are read; ``cfg`` needs contact = 1) plus ``contact`` as ``race_contact``
+        and ``contact_carry`` the contact model's state returned by the previous call (None: ``contact.new_contact_carry(B)``).  Returns
+        (plant [B, 8] after the tick, mu_live [B], the interactions' outputs dict, their carry, the contact model's dict, its carry)."""
+        from . import contact as K, heats as H, interactions as I
+        plant = f64(plant).copy()
+        if plant.ndim != 2 or plant.shape[1] != 8:
+            raise ValueError("contact_step: plant must be [B, 8], got %s" % (plant.shape,))
+        B = plant.shape[0]
+        rows = f64(plant_params, (B, _ffi.PLANT_WORDS), "plant_params")
+        hl, hw = H.check_extents(half_length, half_width)
+        hcfg = _ffi.HeatsConfig(hl, hw)
+        c = I.as_config(cfg)
+        kc = K.as_config(contact)
+        h = H.check_heats(heat, B)
+        n = int(h.max()) + 1 if n_heats is None else int(n_heats)
+        ns = None if nstep is None else np.ascontiguousarray(np.asarray(nstep).reshape(-1), np.int32)
+        if ns is not None and ns.shape[0] != B:
+            raise ValueError("contact_step: nstep must have one entry per vehicle (%d)" % B)
+        k = I.new_carry(B) if carry is None else carry
+        cf = f64(k["f64"], (_ffi.INTER_CARRY_F64, B), "carry f64").copy()
+        ci = np.ascontiguousarray(k["i32"], np.int32).copy()
+        if ci.shape != (_ffi.INTER_CARRY_I32, B):
+            raise ValueError("contact_step: carry i32 has shape %s, expected %s" % (ci.shape, (_ffi.INTER_CARRY_I32, B)))
+        kk = K.new_contact_carry(B) if contact_carry is None else contact_carry
+        kf = f64(kk["f64"], (_ffi.CONTACT_CARRY_F64, B), "contact carry f64").copy()
+        ki = np.ascontiguousarray(kk["i32"], np.int32).copy()
+        if ki.shape != (_ffi.CONTACT_CARRY_I32, B):
+            raise ValueError("contact_step: contact carry i32 has shape %s, expected %s" % (ki.shape, (_ffi.CONTACT_CARRY_I32, B)))
+        f = np.empty((_ffi.INTER_F64, B)); i = np.empty((_ffi.INTER_I32, B), np.int32); mu = np.empty(B)
+        qf = np.empty((_ffi.CONTACT_F64, B)); qi = np.empty((_ffi.CONTACT_I32, B), np.int32)
+        self._chk(self._lib.lpvmpc_contact_step_batch(self._h, B, n, ptr(h), C.byref(hcfg), C.byref(c), C.byref(kc), int(t), ptr(plant), ptr(rows),
+                                                      ptr(ns), ptr(cf), ptr(ci), ptr(kf), ptr(ki), ptr(mu), ptr(f), ptr(i), ptr(qf), ptr(qi)))
+        return plant, mu, I.interactions_dict(f, i), dict(f64=cf, i32=ci), K.contact_dict(qf, qi), dict(f64=kf, i32=ki)
+
     # -- walls: barrier contact at the track's edges (lpvmpc_race_walls / _read, lpvmpc_wall_step_batch; walls.py) ------------------
     def race_walls(self, cfg=None, detach=False):
         """Attach the walls from the next tick on (lpvmpc_race_walls): ``cfg`` a ``walls.wall_config(...)`` result, a dict of its words,
@@ -1479,7 +1540,9 @@ class RaceFleet(object):
     attaches or detaches mid-race, ``standings()`` reads them).  ``interactions`` (with ``heats``): True for the defaults, an
     ``interactions.interaction_config(...)`` result or a dict of its words: slipstream and contact response between the members of a
     heat from the first tick on (``interact`` attaches or detaches mid-race, ``interactions()`` reads the outputs back); it selects
-    ``tyre_params="linear"`` when none is given.
+    ``tyre_params="linear"`` when none is given.  ``contact`` (with ``interactions``): True for the defaults, a
+    ``contact.contact_config(...)`` result or a dict of its words: the corner form of the car-to-car contact, with friction and a yaw
+    response, from the first tick on (``contact`` attaches or detaches mid-race, ``contacts()`` reads its planes back).
     ``walls``: True for the defaults, a ``walls.wall_config(...)`` result or a dict of its words: barrier contact at the track's edges
     from the first tick on (``wall`` attaches or detaches mid-race, ``walls()`` reads the outputs back); it selects
     ``tyre_params="linear"`` when none is given."""
@@ -1487,10 +1550,12 @@ class RaceFleet(object):
     def __init__(self, track_map, plant0, laps=1, N=20, Np=40, half_track0=None, device=0, estimator=None, actuator=None,
                  steering_delay=0, delay_a=None, delay_df=None, plant_params=None, model_params=None, path_tunings=None,
                  tt_tunings=None, plan_tunings=None, tyre_params=None, estimator_params=None, estimator_design=None, track_of=None,
-                 disturbance=None, sensor_faults=None, heats=None, interactions=None, walls=None, **options):
+                 disturbance=None, sensor_faults=None, heats=None, interactions=None, walls=None, contact=None, **options):
         from .workloads import CTRL_TUNINGS, PLAN_L, PLAN_Q, PLAN_R, PLAN_dR
         if interactions is not None and interactions is not False and heats is None:
             raise ValueError("interactions needs heats: the vehicles of a heat act on each other")
+        if contact is not None and contact is not False and (interactions is None or interactions is False):
+            raise ValueError("contact needs interactions: the contact model is a form of their contact")
         race_keys = ("n_sub_lap0", "n_sub", "q9_swap", "plan_max_ey", "dt_sim", "mu_sim")
         race_opts = {k: v for k, v in options.items() if k in race_keys}
         engine_opts = {k: v for k, v in options.items() if k not in race_keys}
@@ -1573,6 +1638,8 @@ class RaceFleet(object):
             self.heats(**heats) if isinstance(heats, dict) else self.heats(heats)
         if interactions is not None and interactions is not False:
             self.interact(None if interactions is True else interactions)
+        if contact is not None and contact is not False:
+            self.contact(None if contact is True else contact)
         if walls is not None and walls is not False:
             self.wall(None if walls is True else walls)
 
@@ -1669,6 +1736,16 @@ class RaceFleet(object):
     def interactions(self):
         """The outputs of the attached interactions (BatchedSolver.race_interactions_read): shelter, live mu, impulses, leader, hits."""
         return self.path.race_interactions_read()
+
+    def contact(self, cfg=None, detach=False):
+        """Attach the contact model on top of the interactions from the next tick on (BatchedSolver.race_contact): ``cfg`` None (the
+        defaults), a dict of words or a ``contact.contact_config(...)`` result; ``contact(detach=True)`` goes back to the centres form.
+        ``interact(...)`` and ``heats(...)`` detach it too."""
+        self.path.race_contact(cfg, detach=detach)
+
+    def contacts(self):
+        """The planes of the attached contact model (BatchedSolver.race_contact_read): friction impulse, yaw kicks, partners."""
+        return self.path.race_contact_read()
 
     def wall(self, cfg=None, detach=False):
         """Attach the walls from the next tick on (BatchedSolver.race_walls): ``cfg`` None (the defaults), a dict of words or a

@@ -6,6 +6,7 @@
 #include <new>
 #include <vector>
 
+#include "contact_host.hpp"
 #include "interactions_host.hpp"
 
 namespace {
@@ -41,6 +42,13 @@ void blank_outputs(size_t B, const int32_t *heat_of, const double *mu, std::vect
 
 }  // namespace
 
+// the three above for contact_api.hip (interactions_host.hpp)
+int lpvmpc_interaction_check_config(lpvmpc_handle *h, const char *who, const lpvmpc_interaction_config *c) { return check_config(h, who, c); }
+void lpvmpc_interaction_set_config(const lpvmpc_interaction_config &c, lpvmpc::InterDev &d) { set_config(c, d); }
+void lpvmpc_interaction_blank_outputs(size_t B, const int32_t *heat_of, const double *mu, std::vector<double> &f, std::vector<int32_t> &i) {
+    blank_outputs(B, heat_of, mu, f, i);
+}
+
 extern "C" void lpvmpc_interaction_default_config(lpvmpc_interaction_config *c) {
     if (!c) return;
     // invented values of the right order for a 1:10 car (0.8 m long): nothing in the reference fixes them
@@ -50,6 +58,7 @@ extern "C" void lpvmpc_interaction_default_config(lpvmpc_interaction_config *c) 
 int lpvmpc_race_interactions_detach(lpvmpc_handle *h) {
     RaceInterView v;
     if (!h || !lpvmpc_race_inter_view(h, v) || !v.slot->get()) return LPVMPC_OK;
+    { const int rd = lpvmpc_race_contact_detach(h); if (rd) return rd; }        // the contact model reads this binding
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t st = h->stream;
     HIP_TRY(h, hipStreamSynchronize(st));                                       // no tick in flight reads the binding
@@ -70,6 +79,7 @@ extern "C" int lpvmpc_race_interactions(lpvmpc_handle *h, const lpvmpc_interacti
         return fail(h, LPVMPC_E_ARG, "%s: the race has no plant table (start it through lpvmpc_race_init_vehicles / lpvmpc_race_init_tyres): there is "
                     "no mass to exchange an impulse with and no drag word to scale", who);
     int rc = check_config(h, who, cfg); if (rc) return rc;
+    rc = lpvmpc_race_contact_detach(h); if (rc) return rc;                      // the contact model reads the binding that is replaced
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t st = h->stream;
     HIP_TRY(h, hipStreamSynchronize(st));                                       // no tick in flight writes the table read below

@@ -26,3 +26,8 @@ struct RaceInterView {
     std::unique_ptr<InterBinding> *slot = nullptr;
 };
 LPVMPC_HIDDEN bool lpvmpc_race_inter_view(lpvmpc_handle *h, RaceInterView &v);
+// interactions_api.hip: the interactions' configuration check, its words into the kernel argument, and the planes a vehicle reads
+// before its first tick, for contact_api.hip, whose batch form takes the interactions' configuration and writes their planes
+LPVMPC_HIDDEN int lpvmpc_interaction_check_config(lpvmpc_handle *h, const char *who, const lpvmpc_interaction_config *c);
+LPVMPC_HIDDEN void lpvmpc_interaction_set_config(const lpvmpc_interaction_config &c, lpvmpc::InterDev &d);
+LPVMPC_HIDDEN void lpvmpc_interaction_blank_outputs(size_t B, const int32_t *heat_of, const double *mu, std::vector<double> &f, std::vector<int32_t> &i);

@@ -4,13 +4,15 @@
 // the estimator state, gains and parameters in the path handle's obs_state / obs_gains / obs_p (obs_cfg stays null, so the
 // handle's next lpvmpc_cl_init runs on ground truth); lpvmpc_race_free releases them.  The recorder (lpvmpc_race_record,
 // record.hip), the heats (lpvmpc_race_heats, heats_api.hip / heats.hip), the interactions (lpvmpc_race_interactions,
-// interactions_api.hip / interactions.hip) and the walls (lpvmpc_race_walls, walls_api.hip / walls.hip) belong to the race as well.
+// interactions_api.hip / interactions.hip), the contact model (lpvmpc_race_contact, contact_api.hip / contact.hip) and the walls
+// (lpvmpc_race_walls, walls_api.hip / walls.hip) belong to the race as well.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <new>
 
 #include "heats_host.hpp"
+#include "contact_host.hpp"
 #include "interactions_host.hpp"
 #include "lpvmpc_handle.hpp"
 #include "race_state.hpp"
@@ -33,6 +35,7 @@ struct lpvmpc_race {
     std::unique_ptr<lpvmpc_race_recorder> rec;   // lpvmpc_race_record (null: not recording)
     std::unique_ptr<HeatsBinding> heats;         // lpvmpc_race_heats (heats_api.hip; null: none attached)
     std::unique_ptr<InterBinding> inter;         // lpvmpc_race_interactions (interactions_api.hip; null: none attached; reads the heats' lists)
+    std::unique_ptr<ContactBinding> contact;     // lpvmpc_race_contact (contact_api.hip; null: the centres form; reads the interactions' binding)
     std::unique_ptr<WallBinding> walls;          // lpvmpc_race_walls (walls_api.hip; null: none attached)
 };
 
@@ -311,6 +314,12 @@ bool lpvmpc_race_inter_view(lpvmpc_handle *h, RaceInterView &v) {
     v.B = r->d.B; v.plant = r->d.plant; v.nstep = r->d.nstep; v.side = &r->side; v.heats = r->heats.get(); v.slot = &r->inter;
     return true;
 }
+bool lpvmpc_race_contact_view(lpvmpc_handle *h, RaceContactView &v) {
+    lpvmpc_race *r = h->race;
+    if (!r) return false;
+    v.B = r->d.B; v.side = &r->side; v.heats = r->heats.get(); v.inter = r->inter.get(); v.slot = &r->contact;
+    return true;
+}
 bool lpvmpc_race_wall_view(lpvmpc_handle *h, RaceWallView &v) {
     lpvmpc_race *r = h->race;
     if (!r) return false;
@@ -383,7 +392,9 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
         ta.active = d.m_tt;
         rc = lpvmpc_launch_solve_timed(tt, ta, st); if (rc) return fail(h, rc, "%s", lpvmpc_last_error(tt));
         if (side.dist.d.rows) HIP_TRY(h, lpvmpc::launch_disturbance(h->d_cfg, trk, side.dist.d, st));   // lpvmpc_set_disturbances
-        if (const InterBinding *q = r->inter.get())                                 // lpvmpc_race_interactions: a kick comes before a contact
+        if (const ContactBinding *q = r->contact.get())                             // lpvmpc_race_contact: in place of the interactions' launch
+            HIP_TRY(h, lpvmpc::launch_contact_tick(q->d, q->block, r->ticks, st));
+        else if (const InterBinding *q = r->inter.get())                            // lpvmpc_race_interactions: a kick comes before a contact
             HIP_TRY(h, lpvmpc::launch_interaction_tick(q->d, q->block, r->ticks, st));
         if (const WallBinding *q = r->walls.get())                                  // lpvmpc_race_walls: a shove into a wall is answered on this tick
             HIP_TRY(h, lpvmpc::launch_wall_tick(q->d, r->ticks, st));

@@ -1516,6 +1516,110 @@ int  lpvmpc_wall_step_batch(lpvmpc_handle *h, int32_t B, const lpvmpc_wall_confi
                             const int32_t *nstep /* [B] or NULL: all step */, double *carry_f64, int32_t *carry_i32, double *f64,
                             int32_t *i32);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Contact model: the corner form of the car-to-car contact.  The interactions' contact is frictionless and acts through both centres;
+ * the walls' acts at a corner, with friction, and turns the car.  The contact model gives a pair of cars the walls' response: one
+ * contact point per overlapping pair, a normal and a clamped friction impulse there, and the yaw rates that follow from the lever
+ * arms.  It is attached ON TOP of the interactions (contact = 1) and replaces their kernel's launch on the ticks on which it is
+ * attached; slipstream, push, the interactions' configuration, planes and counters keep their meaning and are written by the same
+ * launch.  Nothing here has a counterpart in the reference; this text is the definition.  Every product and sum below is rounded on
+ * its own (no fused multiply-add), in the order written, a unary minus applying to the factor it stands in front of; a / 2 is exact.
+ *
+ * Participants.  The interactions' rule, and psiDot finite as well (the walls' rule).  Staged per participant before anything is
+ * written, in addition to the interactions' words: w = psiDot and Iz (plant row word 3).
+ * Decision.  For every unordered pair a < b of participants the overlap decision is the interactions' own, word for word: the four
+ * projections p_k and gaps g_k, k the first axis of (u_a, v_a, u_b, v_b) attaining the max, sep = g_k, n = axis * sign(p_k) from a to b.
+ * A pair with sep >= 0 is untouched.  The half extents hl (along u) and hw (along v) are the heats' footprint.
+ *
+ * Reference and incident body.  R owns the contact axis: a for k in {0, 1}, b for k in {2, 3}; I is the other one.  n_R = n when R = a,
+ * else (-n_x, -n_y); t_R = (-n_Ry, n_Rx).  r_n = hl and r_t = hw for k in {0, 2} (a u axis), r_n = hw and r_t = hl for k in {1, 3}.
+ * Incident face.  With (c, s) of I: d_0 = c*n_Rx + s*n_Ry (face +u_I), d_1 = -d_0 (-u_I), d_2 = -s*n_Rx + c*n_Ry (+v_I), d_3 = -d_2
+ * (-v_I); the face is the first that attains the min.  Its end points are I's corners on it in the walls' corner order,
+ *   (a_0, b_0), (a_1, b_1) = face 0: (+hl, +hw), (+hl, -hw);  1: (-hl, +hw), (-hl, -hw);  2: (+hl, +hw), (-hl, +hw);
+ *   3: (+hl, -hw), (-hl, -hw);      E_j = (x_I + (c*a_j - s*b_j), y_I + (s*a_j + c*b_j)),
+ *   q_j = (E_jx - x_R, E_jy - y_R);  tau_j = q_jx*t_Rx + q_jy*t_Ry;  delta_j = r_n - (q_jx*n_Rx + q_jy*n_Ry)   (depth below R's face).
+ * Contact point.  The face is E_0 + s (E_1 - E_0), s in [0, 1]; tau and delta are linear in s.  dt = tau_1 - tau_0 (never 0 for the
+ * chosen face);  s1 = (r_t - tau_0)/dt,  s2 = (-r_t - tau_0)/dt;  s_lo = max(0, min(s1, s2)),  s_hi = min(1, max(s1, s2)).
+ * When delta_0 < 0 and delta_1 < 0 the interval is empty.  Else, when delta_0 < 0: s_lo = max(s_lo, -delta_0/(delta_1 - delta_0)); else,
+ * when delta_1 < 0: s_hi = min(s_hi, -delta_0/(delta_1 - delta_0)).  The interval is empty as well when s_lo > s_hi.
+ *   s* = (s_lo + s_hi)/2, or, of an empty interval, 0 when delta_0 >= delta_1 and 1 otherwise (no overlapping pair is known to
+ *   reach this; the rule makes the text total);   P = (E_0x + s* * (E_1x - E_0x), E_0y + s* * (E_1y - E_0y)).
+ * A flat nose-to-tail hit gets the middle of the shared width; a corner driven into a side gets a point next to the corner.
+ * Between parallel cars two axes tie and the lower index owns the axis: with the labels swapped P moves by the depth along n, which
+ * changes the friction's lever arms and nothing else.
+ *
+ * Response at P.  r_a = (P_x - x_a, P_y - y_a), r_b likewise; with yaw_response == 0 both are (0, 0) in everything below and psiDot is
+ * never written: the interactions' through-the-centres form, with friction.  For a direction d (n, then t = (-n_y, n_x)) and the
+ * velocities (u_a, w_a, u_b, w_b) of the pair:
+ *   v_b = (u_bx + w_b * -r_by, u_by + w_b * r_bx),  v_a likewise;   vd = (v_bx - v_ax)*d_x + (v_by - v_ay)*d_y;
+ *   ka = r_ax*d_y - r_ay*d_x,  kb = r_bx*d_y - r_by*d_x;   kd = ((1/m_a + 1/m_b) + (ka*ka)/Iz_a) + (kb*kb)/Iz_b.
+ *   Normal impulse (d = n, the staged velocities):  Jn = vn < 0 ? (-(1 + restitution) * vn) / kn : 0, restitution the interactions'.
+ *     u_a' = u_a - (Jn/m_a) n,  w_a' = w_a - (ka*Jn)/Iz_a;   u_b' = u_b + (Jn/m_b) n,  w_b' = w_b + (kb*Jn)/Iz_b.
+ *   Friction impulse (d = t, the primed velocities):  lim = friction * Jn;  Jt = -vt / kt, then lim where Jt > lim, then -lim where
+ *     Jt < -lim.  With ka, kb of d = t named la, lb:
+ *   du_a = (-((Jn/m_a)*n_x) + -((Jt/m_a)*t_x), same in y),   dw_a = -((ka*Jn)/Iz_a) + -((la*Jt)/Iz_a);
+ *   du_b = ((Jn/m_b)*n_x + (Jt/m_b)*t_x, same in y),         dw_b = (kb*Jn)/Iz_b + (lb*Jt)/Iz_b.
+ * One pass, normal then friction, as the walls': neither step passes its direction's energy minimum, so an isolated pair on which
+ * no vx clamp acts keeps its linear momentum and its angular momentum about the origin (sum m (c x u) + Iz w, at the positions before
+ * the push) to rounding and never gains kinetic energy, rotation included.  NOTHING of that kind is claimed for a vehicle with
+ * several partners on one tick: their contributions are summed from the same staged words (below), and the sum of two admissible
+ * impulses can add energy.
+ * Push.  The interactions' own: dc_a, dc_b of that section, unchanged.
+ * Several partners.  du, dw, dc of every partner come from the staged (pre-tick) words and are summed in ascending partner order,
+ * starting from 0: the interactions' Jacobi step.
+ * Written for a vehicle with at least one overlapping partner: u' = u + sum du;  vx = max(c*u'_x + s*u'_y, 0),  vy = -s*u'_x + c*u'_y,
+ * psiDot = w + sum dw when yaw_response != 0,  x += sum dc_x,  y += sum dc_y.  yaw, ax, ay are never written; a vehicle without an
+ * overlapping partner keeps every state word bit for bit.  Slipstream: unchanged, computed by the same launch in the same words.
+ * With friction = 0 and yaw_response = 0 every plant word and every plane of the interactions is the word the interactions alone
+ * give (when every psiDot is finite).
+ *
+ * Outputs.  The interactions' planes as they are (IMPULSE sums |Jn|).  f64 [LPVMPC_CONTACT_F64][B] = FRICTION_IMPULSE (the sum of |Jt|
+ * over its partners of this tick), YAW_KICK (sum dw of this tick), YAW_KICK_TOTAL (the sum of |dw| over every partner and tick since
+ * the attach, carried); i32 [LPVMPC_CONTACT_I32][B] = PARTNERS (overlapping partners this tick), MAX_PARTNERS (carried).  A member that
+ * does not take part on a tick reads 0 in FRICTION_IMPULSE, YAW_KICK and PARTNERS and keeps its carried words; a vehicle in no heat reads
+ * NaN in every f64 channel and 0 in both i32 channels.
+ *
+ * Configuration (lpvmpc_contact_default_config: friction 0.3, yaw_response 1, the walls' values): friction >= 0 and finite,
+ * yaw_response 0 / 1, reserved 0.  Restitution and push are read from the attached interactions.
+ *
+ * lpvmpc_race_contact attaches the contact model to the race of the path handle from the next tick on; attaching again replaces the
+ * binding (its counters start anew; the interactions' go on), cfg == NULL goes back to the centres form.  It needs interactions attached
+ * with contact = 1.  Refused with LPVMPC_E_ARG, the race left as it was: no race on the handle, no interactions attached, contact == 0,
+ * a word that is not finite or out of range, reserved != 0.  The binding is built whole and then installed; the race owns it.
+ * lpvmpc_race_interactions, whether it re-attaches or detaches, detaches the contact model first, and so does lpvmpc_race_heats.  While
+ * attached lpvmpc_race_tick launches the contact model's kernel IN PLACE OF the interactions': one launch in the same position, behind
+ * the disturbances' and in front of the walls'.  lpvmpc_race_contact_read synchronises and copies the two planes (either pointer may be
+ * NULL); refused while nothing is attached.
+ *
+ * lpvmpc_contact_step_batch is one tick of the same kernel on caller-supplied data: lpvmpc_interaction_step_batch's arguments (of
+ * plant_params word 3 is read as well) plus the contact configuration, the carried state ccarry_f64 [LPVMPC_CONTACT_CARRY_F64][B] /
+ * ccarry_i32 [LPVMPC_CONTACT_CARRY_I32][B] in / out (just attached: zeros) and the two planes. */
+#define LPVMPC_CONTACT_F64                  3
+#define LPVMPC_CONTACT_FRICTION_IMPULSE     0
+#define LPVMPC_CONTACT_YAW_KICK             1
+#define LPVMPC_CONTACT_YAW_KICK_TOTAL       2
+#define LPVMPC_CONTACT_I32                  2
+#define LPVMPC_CONTACT_PARTNERS             0
+#define LPVMPC_CONTACT_MAX_PARTNERS         1
+#define LPVMPC_CONTACT_CARRY_F64            1
+#define LPVMPC_CONTACT_CARRY_YAW_KICK_TOTAL 0
+#define LPVMPC_CONTACT_CARRY_I32            1
+#define LPVMPC_CONTACT_CARRY_MAX_PARTNERS   0
+typedef struct lpvmpc_contact_config {
+    double  friction;          /* >= 0 */
+    int32_t yaw_response;      /* 0 / 1: 0 applies the impulses through the centres and leaves psiDot alone */
+    int32_t reserved;          /* 0 */
+} lpvmpc_contact_config;
+void lpvmpc_contact_default_config(lpvmpc_contact_config *cfg);
+int  lpvmpc_race_contact(lpvmpc_handle *path, const lpvmpc_contact_config *cfg /* NULL: back to the centres form */);
+int  lpvmpc_race_contact_read(lpvmpc_handle *path, double *f64, int32_t *i32);
+int  lpvmpc_contact_step_batch(lpvmpc_handle *h, int32_t B, int32_t n_heats, const int32_t *heat,
+                               const lpvmpc_heats_config *heats_cfg, const lpvmpc_interaction_config *cfg,
+                               const lpvmpc_contact_config *contact_cfg, int32_t t, double *plant /* [B][8] in/out */,
+                               const double *plant_params /* [B][7] */, const int32_t *nstep /* [B] or NULL: all step */,
+                               double *carry_f64, int32_t *carry_i32, double *ccarry_f64, int32_t *ccarry_i32,
+                               double *mu_live /* [B] out */, double *f64, int32_t *i32, double *cf64, int32_t *ci32);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,9 +64,14 @@ a fresh process; with --parent-lib FILE the parent's library on the baseline as 
 (the baseline: the launches of the parent's tick), the same race with walls attached whose margin is so large that nothing touches (margin
 50: the same race word for word, so the difference is the launch), and with the default walls attached (another race where a car meets a
 wall); with --parent-lib FILE the parent's library on the baseline as well.
+--contact [--heats SIZE]: the same protocol for the contact model (lpvmpc_race_contact): the --interactions race with the default interactions
+attached (the baseline: the interactions' own launch; the bench's starts put a heat on one pose, so this is the pile-up start), the same
+race with the contact model attached with friction 0 and yaw_response 0 (the same race word for word, so the difference is the new kernel
+in place of the interactions'), and with the default contact model attached (another race); with --parent-lib FILE the parent's library
+on the baseline as well.
 
 Usage: tools/race_bench.py [--ticks K] [--sizes 1024,8192] [--estimator | --actuator | --record | --heats SIZE | --plant-params | --models |
-       --tunings | --tyres | --observer-vehicles | --tracks | --disturbance | --sensor-faults | --interactions | --walls | --fork [--parent-lib FILE] [--reps R]]
+       --tunings | --tyres | --observer-vehicles | --tracks | --disturbance | --sensor-faults | --interactions | --walls | --contact | --fork [--parent-lib FILE] [--reps R]]
        [--out FILE]
 --sensor-faults: the same protocol for the sensor faults (lpvmpc_set_sensor_faults): the lpvmpc_race_init_tyres race with kind 0 rows and the
 estimator in the loop with nothing attached (the baseline: the launches of the parent's tick), with all-off rows attached (the faulted
@@ -105,7 +110,8 @@ def timed(tick, read, K):
 
 
 def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, record=False, plant_params=None, model_params=None, tunings=None,
-             tyre_params=None, observer_vehicles=False, tracks=None, disturbance=None, heats=0, sensor_faults=None, interactions=None, walls=None):
+             tyre_params=None, observer_vehicles=False, tracks=None, disturbance=None, heats=0, sensor_faults=None, interactions=None, walls=None,
+             contact=None):
     path, tt, plan = engines(mp, sd)
     if tracks is not None:                                            # (maps, track_of) bound to the three engines
         for e in (path, tt, plan):
@@ -136,6 +142,8 @@ def race_run(mp, plant0, half, warm, K, estimator=None, actuator=None, sd=0, rec
         path.race_heats(np.arange(plant0.shape[0]) // int(heats))
     if interactions is not None:                                      # a dict of configuration words, on the heats just attached
         path.race_interactions(interactions)
+    if contact is not None:                                           # a dict of configuration words, on the interactions just attached
+        path.race_contact(contact)
     if walls is not None:                                             # a dict of configuration words
         path.race_walls(walls)
     a0 = path.race_laps()[1].sum()
@@ -167,6 +175,7 @@ def main():
     ap.add_argument("--sensor-faults", action="store_true")
     ap.add_argument("--interactions", action="store_true")
     ap.add_argument("--walls", action="store_true")
+    ap.add_argument("--contact", action="store_true")
     ap.add_argument("--fork", action="store_true")
     ap.add_argument("--fork-child", default=None, help=argparse.SUPPRESS)                  # B: the fork measurements of one fleet size
     ap.add_argument("--parent-lib", default=None)
@@ -202,6 +211,10 @@ def main():
         a.heats = a.heats or 16
         return models_main(a, [("tyres + heats of %d" % a.heats, "liblpvmpc.so", 17), ("all-off interactions", "liblpvmpc.so", 18),
                                ("interactions attached", "liblpvmpc.so", 19)], parent=("parent, tyres + heats", 17))
+    if a.contact:
+        a.heats = a.heats or 16
+        return models_main(a, [("interactions attached", "liblpvmpc.so", 19), ("contact, no friction/yaw", "liblpvmpc.so", 24),
+                               ("contact attached", "liblpvmpc.so", 25)], parent=("parent, interactions", 19))
     if a.walls:
         return models_main(a, [("tyres, nothing attached", "liblpvmpc.so", 20), ("far-margin walls", "liblpvmpc.so", 21),
                                ("walls attached", "liblpvmpc.so", 22)], parent=("parent, tyres", 20))
@@ -444,7 +457,8 @@ def models_child(a):
              13: lpvmpc.tyre_params(int(B), kind=0), 14: lpvmpc.tyre_params(int(B), kind=0),
              15: lpvmpc.tyre_params(int(B), kind=0), 16: lpvmpc.tyre_params(int(B), kind=0), 17: lpvmpc.tyre_params(int(B), kind=0),
              18: lpvmpc.tyre_params(int(B), kind=0), 19: lpvmpc.tyre_params(int(B), kind=0), 20: lpvmpc.tyre_params(int(B), kind=0),
-             21: lpvmpc.tyre_params(int(B), kind=0), 22: lpvmpc.tyre_params(int(B), kind=0), 23: lpvmpc.tyre_params(int(B), kind=0)}.get(int(bind))               # 4 nominal plant rows (_vehicles), 5 / 6 tyre rows on top
+             21: lpvmpc.tyre_params(int(B), kind=0), 22: lpvmpc.tyre_params(int(B), kind=0), 23: lpvmpc.tyre_params(int(B), kind=0),
+             24: lpvmpc.tyre_params(int(B), kind=0), 25: lpvmpc.tyre_params(int(B), kind=0)}.get(int(bind))               # 4 nominal plant rows (_vehicles), 5 / 6 tyre rows on top
     dist = None                                                                    # 13: 9 with gusts, a patch and a kick on every vehicle
     if int(bind) == 13:
         from lpvmpc.disturbance import parse_disturbance
@@ -466,8 +480,9 @@ def models_child(a):
     ms, vps, ph = race_run(mp, plant0, half, warm, a.ticks, model_params=rows, tunings={2: "own", 3: "sampled"}.get(int(bind)),
                             plant_params="nominal" if int(bind) in (4, 5, 6, 7, 8) else None, tyre_params=tyres, estimator=obs,
                             observer_vehicles=int(bind) == 8, disturbance=dist, sensor_faults=faults,
-                            heats=(a.heats or 16) if int(bind) in (17, 18, 19, 23) else 0,       # 17: 9 with heats; 18 / 19: the interactions on top, all off / defaults
-                            interactions={18: dict(draft_gain=0.0, contact=0), 19: {}, 23: {}}.get(int(bind)),
+                            heats=(a.heats or 16) if int(bind) in (17, 18, 19, 23, 24, 25) else 0,       # 17: 9 with heats; 18 / 19: the interactions on top, all off / defaults
+                            interactions={18: dict(draft_gain=0.0, contact=0), 19: {}, 23: {}, 24: {}, 25: {}}.get(int(bind)),
+                            contact={24: dict(friction=0.0, yaw_response=0), 25: {}}.get(int(bind)),   # 24 / 25: 19 with the contact model, centres-form words / defaults
                             walls={21: dict(margin=50.0), 22: {}, 23: {}}.get(int(bind)))   # 20: 9 again; 21 / 22: walls on top, out of reach / defaults; 23: 19 with walls
     print("MODELS_RUN %.6f %s %.4g" % (ms, ",".join(str(int(x)) for x in ph), vps), flush=True)
 
