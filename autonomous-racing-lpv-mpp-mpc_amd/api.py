@@ -918,14 +918,11 @@ class BatchedSolver:
         members each; with tracks bound, one track per heat), ``turns0`` [B] the starting turn count (default 0; -1 for a car gridded
         behind the line), ``half_length`` / ``half_width`` the half extents of a car's footprint.  Re-attaching resets the standings;
         ``heat=None`` detaches.  Heats only observe: no output of the race changes."""
-        from . import heats as H
         B = self._race_B("race_heats")
         if heat is None:
             self._chk(self._lib.lpvmpc_race_heats(self._h, None, None, None))
             return
-        hl, hw = H.check_extents(half_length, half_width)
-        cfg = _ffi.HeatsConfig(hl, hw)
-        h = H.check_heats(heat, B)
+        cfg, h, _ = _heats_args(heat, B, None, half_length, half_width)
         t0 = None if turns0 is None else np.ascontiguousarray(np.asarray(turns0).reshape(-1), np.int32)
         if t0 is not None and t0.shape[0] != B:
             raise ValueError("race_heats: turns0 must have one entry per vehicle (%d), got %d" % (B, t0.shape[0]))
@@ -939,9 +936,8 @@ class BatchedSolver:
         from . import heats as H
         B = self._race_B("race_standings")
         K = self._race[1] + 2
-        f = np.empty((_ffi.HEAT_F64, B)); i = np.empty((_ffi.HEAT_I32, B), np.int32)
         lt = np.empty((B, K), np.int32); lp = np.empty((B, K), np.int32)
-        self._chk(self._lib.lpvmpc_race_standings(self._h, ptr(f), ptr(i), ptr(lt), ptr(lp)))
+        f, i = _read_planes(self, self._lib.lpvmpc_race_standings, B, _ffi.HEAT_F64, _ffi.HEAT_I32, lt, lp)
         return H.standings_dict(f, i, lt, lp)
 
     def heat_step(self, heat, L, pose, s, inside, phase, t, carry=None, n_heats=None, half_length=0.4, half_width=0.2):
@@ -957,10 +953,7 @@ class BatchedSolver:
         if pose.ndim != 2 or pose.shape[1] != 3:
             raise ValueError("heat_step: pose must be [B, 3], got %s" % (pose.shape,))
         B = pose.shape[0]
-        hl, hw = H.check_extents(half_length, half_width)
-        cfg = _ffi.HeatsConfig(hl, hw)
-        h = H.check_heats(heat, B)
-        n = int(h.max()) + 1 if n_heats is None else int(n_heats)
+        cfg, h, n = _heats_args(heat, B, n_heats, half_length, half_width)
         Lb = f64(np.broadcast_to(np.asarray(L, float), (B,)), (B,), "L")
         s = f64(s, (B,), "s")
         ins = np.ascontiguousarray(np.asarray(inside).reshape(-1), np.int32)
@@ -968,10 +961,7 @@ class BatchedSolver:
         if ins.shape[0] != B or ph.shape[0] != B:
             raise ValueError("heat_step: inside and phase must have one entry per vehicle (%d)" % B)
         c = H.new_carry(B) if carry is None else carry
-        cf = f64(c["f64"], (_ffi.HEAT_CARRY_F64, B), "carry f64").copy()
-        ci = np.ascontiguousarray(c["i32"], np.int32).copy()
-        if ci.shape != (_ffi.HEAT_CARRY_I32, B):
-            raise ValueError("heat_step: carry i32 has shape %s, expected %s" % (ci.shape, (_ffi.HEAT_CARRY_I32, B)))
+        cf, ci = _carry_in("heat_step", c, _ffi.HEAT_CARRY_F64, _ffi.HEAT_CARRY_I32, B)
         f = np.empty((_ffi.HEAT_F64, B)); i = np.empty((_ffi.HEAT_I32, B), np.int32)
         was = ci[_ffi.HEAT_CARRY_I32_NAMES.index("crossings")].copy() * (ci[0] & 1)
         self._chk(self._lib.lpvmpc_heat_step_batch(self._h, B, n, ptr(h), ptr(Lb), C.byref(cfg), int(t), ptr(pose), ptr(s), ptr(ins), ptr(ph),
@@ -997,11 +987,7 @@ class BatchedSolver:
         back into the live plant table.  ``race_heats`` detaches the interactions, whether it re-attaches or detaches the heats."""
         from . import interactions as I
         self._race_B("race_interactions")
-        if detach:
-            self._chk(self._lib.lpvmpc_race_interactions(self._h, None))
-            return
-        c = I.as_config(cfg)
-        self._chk(self._lib.lpvmpc_race_interactions(self._h, C.byref(c)))
+        _race_attach(self, self._lib.lpvmpc_race_interactions, None if detach else I.as_config(cfg))
 
     def race_interactions_read(self):
         """Synchronise and return the interactions' outputs (lpvmpc_race_interactions_read): a dict of [B] arrays named as
@@ -1009,9 +995,7 @@ class BatchedSolver:
         draft_ticks) and the planes f64 [4, B] / i32 [5, B].  A vehicle in no heat reads NaN and leader -1."""
         from . import interactions as I
         B = self._race_B("race_interactions_read")
-        f = np.empty((_ffi.INTER_F64, B)); i = np.empty((_ffi.INTER_I32, B), np.int32)
-        self._chk(self._lib.lpvmpc_race_interactions_read(self._h, ptr(f), ptr(i)))
-        return I.interactions_dict(f, i)
+        return I.interactions_dict(*_read_planes(self, self._lib.lpvmpc_race_interactions_read, B, _ffi.INTER_F64, _ffi.INTER_I32))
 
     def interaction_step(self, heat, plant, plant_params, t, cfg=None, nstep=None, carry=None, n_heats=None, half_length=0.4, half_width=0.2):
         """One tick of the interactions' kernel on the caller's data (lpvmpc_interaction_step_batch): ``heat`` [B] (-1: none), ``plant``
@@ -1019,25 +1003,13 @@ class BatchedSolver:
         simulator steps of this tick (None: every vehicle steps; 0: frozen), ``carry`` the state returned by the previous call (None:
         ``interactions.new_carry(B)``), ``half_length`` / ``half_width`` the heats' footprint.  Returns (plant [B, 8] after the tick,
         mu_live [B], outputs dict, carry)."""
-        from . import heats as H, interactions as I
-        plant = f64(plant).copy()
-        if plant.ndim != 2 or plant.shape[1] != 8:
-            raise ValueError("interaction_step: plant must be [B, 8], got %s" % (plant.shape,))
-        B = plant.shape[0]
-        rows = f64(plant_params, (B, _ffi.PLANT_WORDS), "plant_params")
-        hl, hw = H.check_extents(half_length, half_width)
-        hcfg = _ffi.HeatsConfig(hl, hw)
+        from . import interactions as I
+        plant, B, rows = _step_plant("interaction_step", plant, plant_params)
+        hcfg, h, n = _heats_args(heat, B, n_heats, half_length, half_width)
         c = I.as_config(cfg)
-        h = H.check_heats(heat, B)
-        n = int(h.max()) + 1 if n_heats is None else int(n_heats)
-        ns = None if nstep is None else np.ascontiguousarray(np.asarray(nstep).reshape(-1), np.int32)
-        if ns is not None and ns.shape[0] != B:
-            raise ValueError("interaction_step: nstep must have one entry per vehicle (%d)" % B)
+        ns = _step_nstep("interaction_step", nstep, B)
         k = I.new_carry(B) if carry is None else carry
-        cf = f64(k["f64"], (_ffi.INTER_CARRY_F64, B), "carry f64").copy()
-        ci = np.ascontiguousarray(k["i32"], np.int32).copy()
-        if ci.shape != (_ffi.INTER_CARRY_I32, B):
-            raise ValueError("interaction_step: carry i32 has shape %s, expected %s" % (ci.shape, (_ffi.INTER_CARRY_I32, B)))
+        cf, ci = _carry_in("interaction_step", k, _ffi.INTER_CARRY_F64, _ffi.INTER_CARRY_I32, B)
         f = np.empty((_ffi.INTER_F64, B)); i = np.empty((_ffi.INTER_I32, B), np.int32); mu = np.empty(B)
         self._chk(self._lib.lpvmpc_interaction_step_batch(self._h, B, n, ptr(h), C.byref(hcfg), C.byref(c), int(t), ptr(plant), ptr(rows), ptr(ns),
                                                           ptr(cf), ptr(ci), ptr(mu), ptr(f), ptr(i)))
@@ -1051,11 +1023,7 @@ class BatchedSolver:
         ``race_heats`` detach the contact model."""
         from . import contact as K
         self._race_B("race_contact")
-        if detach:
-            self._chk(self._lib.lpvmpc_race_contact(self._h, None))
-            return
-        c = K.as_config(cfg)
-        self._chk(self._lib.lpvmpc_race_contact(self._h, C.byref(c)))
+        _race_attach(self, self._lib.lpvmpc_race_contact, None if detach else K.as_config(cfg))
 
     def race_contact_read(self):
         """Synchronise and return the contact model's planes (lpvmpc_race_contact_read): a dict of [B] arrays named as
@@ -1063,9 +1031,7 @@ class BatchedSolver:
         f64 [3, B] / i32 [2, B].  A vehicle in no heat reads NaN and 0."""
         from . import contact as K
         B = self._race_B("race_contact_read")
-        f = np.empty((_ffi.CONTACT_F64, B)); i = np.empty((_ffi.CONTACT_I32, B), np.int32)
-        self._chk(self._lib.lpvmpc_race_contact_read(self._h, ptr(f), ptr(i)))
-        return K.contact_dict(f, i)
+        return K.contact_dict(*_read_planes(self, self._lib.lpvmpc_race_contact_read, B, _ffi.CONTACT_F64, _ffi.CONTACT_I32))
 
     def contact_step(self, heat, plant, plant_params, t, cfg=None, contact=None, nstep=None, carry=None, contact_carry=None, n_heats=None,
                      half_length=0.4, half_width=0.2):
@@ -1073,31 +1039,16 @@ class BatchedSolver:
         ``interaction_step`` (``plant_params``: m, Iz and mu are read; ``cfg`` needs contact = 1) plus ``contact`` as ``race_contact``
         and ``contact_carry`` the contact model's state returned by the previous call (None: ``contact.new_contact_carry(B)``).  Returns
         (plant [B, 8] after the tick, mu_live [B], the interactions' outputs dict, their carry, the contact model's dict, its carry)."""
-        from . import contact as K, heats as H, interactions as I
-        plant = f64(plant).copy()
-        if plant.ndim != 2 or plant.shape[1] != 8:
-            raise ValueError("contact_step: plant must be [B, 8], got %s" % (plant.shape,))
-        B = plant.shape[0]
-        rows = f64(plant_params, (B, _ffi.PLANT_WORDS), "plant_params")
-        hl, hw = H.check_extents(half_length, half_width)
-        hcfg = _ffi.HeatsConfig(hl, hw)
+        from . import contact as K, interactions as I
+        plant, B, rows = _step_plant("contact_step", plant, plant_params)
+        hcfg, h, n = _heats_args(heat, B, n_heats, half_length, half_width)
         c = I.as_config(cfg)
         kc = K.as_config(contact)
-        h = H.check_heats(heat, B)
-        n = int(h.max()) + 1 if n_heats is None else int(n_heats)
-        ns = None if nstep is None else np.ascontiguousarray(np.asarray(nstep).reshape(-1), np.int32)
-        if ns is not None and ns.shape[0] != B:
-            raise ValueError("contact_step: nstep must have one entry per vehicle (%d)" % B)
+        ns = _step_nstep("contact_step", nstep, B)
         k = I.new_carry(B) if carry is None else carry
-        cf = f64(k["f64"], (_ffi.INTER_CARRY_F64, B), "carry f64").copy()
-        ci = np.ascontiguousarray(k["i32"], np.int32).copy()
-        if ci.shape != (_ffi.INTER_CARRY_I32, B):
-            raise ValueError("contact_step: carry i32 has shape %s, expected %s" % (ci.shape, (_ffi.INTER_CARRY_I32, B)))
+        cf, ci = _carry_in("contact_step", k, _ffi.INTER_CARRY_F64, _ffi.INTER_CARRY_I32, B)
         kk = K.new_contact_carry(B) if contact_carry is None else contact_carry
-        kf = f64(kk["f64"], (_ffi.CONTACT_CARRY_F64, B), "contact carry f64").copy()
-        ki = np.ascontiguousarray(kk["i32"], np.int32).copy()
-        if ki.shape != (_ffi.CONTACT_CARRY_I32, B):
-            raise ValueError("contact_step: contact carry i32 has shape %s, expected %s" % (ki.shape, (_ffi.CONTACT_CARRY_I32, B)))
+        kf, ki = _carry_in("contact_step", kk, _ffi.CONTACT_CARRY_F64, _ffi.CONTACT_CARRY_I32, B, "contact carry")
         f = np.empty((_ffi.INTER_F64, B)); i = np.empty((_ffi.INTER_I32, B), np.int32); mu = np.empty(B)
         qf = np.empty((_ffi.CONTACT_F64, B)); qi = np.empty((_ffi.CONTACT_I32, B), np.int32)
         self._chk(self._lib.lpvmpc_contact_step_batch(self._h, B, n, ptr(h), C.byref(hcfg), C.byref(c), C.byref(kc), int(t), ptr(plant), ptr(rows),
@@ -1111,11 +1062,7 @@ class BatchedSolver:
         disturbances.  Attaching again replaces the binding (counters start anew); ``detach=True`` detaches."""
         from . import walls as W
         self._race_B("race_walls")
-        if detach:
-            self._chk(self._lib.lpvmpc_race_walls(self._h, None))
-            return
-        c = W.as_config(cfg)
-        self._chk(self._lib.lpvmpc_race_walls(self._h, C.byref(c)))
+        _race_attach(self, self._lib.lpvmpc_race_walls, None if detach else W.as_config(cfg))
 
     def race_walls_read(self):
         """Synchronise and return the walls' outputs (lpvmpc_race_walls_read): a dict of [B] arrays named as _ffi.WALL_F64_NAMES /
@@ -1123,9 +1070,7 @@ class BatchedSolver:
         planes f64 [4, B] / i32 [6, B]."""
         from . import walls as W
         B = self._race_B("race_walls_read")
-        f = np.empty((_ffi.WALL_F64, B)); i = np.empty((_ffi.WALL_I32, B), np.int32)
-        self._chk(self._lib.lpvmpc_race_walls_read(self._h, ptr(f), ptr(i)))
-        return W.walls_dict(f, i)
+        return W.walls_dict(*_read_planes(self, self._lib.lpvmpc_race_walls_read, B, _ffi.WALL_F64, _ffi.WALL_I32))
 
     def wall_step(self, plant, plant_params, t, cfg=None, nstep=None, carry=None, half_width=0.3):
         """One tick of the walls' kernel on the caller's data (lpvmpc_wall_step_batch): ``plant`` [B, 8], ``plant_params`` [B, 7] (m and
@@ -1134,20 +1079,11 @@ class BatchedSolver:
         track's (ignored when tracks are bound to the engine: each vehicle's palette entry has its own).  Returns (plant [B, 8] after
         the tick, outputs dict, carry)."""
         from . import walls as W
-        plant = f64(plant).copy()
-        if plant.ndim != 2 or plant.shape[1] != 8:
-            raise ValueError("wall_step: plant must be [B, 8], got %s" % (plant.shape,))
-        B = plant.shape[0]
-        rows = f64(plant_params, (B, _ffi.PLANT_WORDS), "plant_params")
+        plant, B, rows = _step_plant("wall_step", plant, plant_params)
         c = W.as_config(cfg)
-        ns = None if nstep is None else np.ascontiguousarray(np.asarray(nstep).reshape(-1), np.int32)
-        if ns is not None and ns.shape[0] != B:
-            raise ValueError("wall_step: nstep must have one entry per vehicle (%d)" % B)
+        ns = _step_nstep("wall_step", nstep, B)
         k = W.new_carry(B) if carry is None else carry
-        cf = f64(k["f64"], (_ffi.WALL_CARRY_F64, B), "carry f64").copy()
-        ci = np.ascontiguousarray(k["i32"], np.int32).copy()
-        if ci.shape != (_ffi.WALL_CARRY_I32, B):
-            raise ValueError("wall_step: carry i32 has shape %s, expected %s" % (ci.shape, (_ffi.WALL_CARRY_I32, B)))
+        cf, ci = _carry_in("wall_step", k, _ffi.WALL_CARRY_F64, _ffi.WALL_CARRY_I32, B)
         f = np.empty((_ffi.WALL_F64, B)); i = np.empty((_ffi.WALL_I32, B), np.int32)
         self._chk(self._lib.lpvmpc_wall_step_batch(self._h, B, C.byref(c), float(half_width), int(t), ptr(plant), ptr(rows), ptr(ns), ptr(cf),
                                                    ptr(ci), ptr(f), ptr(i)))
@@ -1201,6 +1137,53 @@ def _plant_rows(v, B):
         return None
     from .plant import check_plant_params
     return check_plant_params(v, B)
+
+
+# -- what the race's attachments share (heats, interactions, contact model, walls): attach / detach, read, and the step forms' inputs --
+def _race_attach(solver, call, cfg):
+    """Attach the checked configuration ``cfg`` through the C call, or detach (None)."""
+    solver._chk(call(solver._h, None if cfg is None else C.byref(cfg)))
+
+
+def _read_planes(solver, call, B, wf, wi, *more):
+    """Read a layer's output planes f64 [wf, B] / i32 [wi, B] through the C call (``more``: further arrays it fills)."""
+    f = np.empty((wf, B)); i = np.empty((wi, B), np.int32)
+    solver._chk(call(solver._h, ptr(f), ptr(i), *[ptr(m) for m in more]))
+    return f, i
+
+
+def _step_plant(who, plant, plant_params):
+    """A step form's plant [B, 8], copied, its B and the plant rows [B, 7]."""
+    plant = f64(plant).copy()
+    if plant.ndim != 2 or plant.shape[1] != 8:
+        raise ValueError("%s: plant must be [B, 8], got %s" % (who, plant.shape,))
+    B = plant.shape[0]
+    return plant, B, f64(plant_params, (B, _ffi.PLANT_WORDS), "plant_params")
+
+
+def _step_nstep(who, nstep, B):
+    """A step form's simulator steps per vehicle: None, or [B] integers."""
+    ns = None if nstep is None else np.ascontiguousarray(np.asarray(nstep).reshape(-1), np.int32)
+    if ns is not None and ns.shape[0] != B:
+        raise ValueError("%s: nstep must have one entry per vehicle (%d)" % (who, B))
+    return ns
+
+
+def _carry_in(who, carry, wf, wi, B, label="carry"):
+    """Copies of a carried state's planes f64 [wf, B] / i32 [wi, B], shape-checked."""
+    cf = f64(carry["f64"], (wf, B), label + " f64").copy()
+    ci = np.ascontiguousarray(carry["i32"], np.int32).copy()
+    if ci.shape != (wi, B):
+        raise ValueError("%s: %s i32 has shape %s, expected %s" % (who, label, ci.shape, (wi, B)))
+    return cf, ci
+
+
+def _heats_args(heat, B, n_heats, half_length, half_width):
+    """The heats' arguments of a C call: the checked footprint, ``heat`` [B] and the number of heats (None: the largest index + 1)."""
+    from . import heats as H
+    cfg = _ffi.HeatsConfig(*H.check_extents(half_length, half_width))
+    h = H.check_heats(heat, B)
+    return cfg, h, int(h.max()) + 1 if n_heats is None else int(n_heats)
 
 
 def _tyre_rows(v, B):

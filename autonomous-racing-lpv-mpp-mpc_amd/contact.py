@@ -8,6 +8,7 @@ import math
 import numpy as np
 
 from . import _ffi
+from ._planes import blank_carry, planes_dict
 
 # lpvmpc_contact_default_config: the walls' values
 DEFAULTS = dict(friction=0.3, yaw_response=1)
@@ -45,13 +46,10 @@ def as_config(cfg):
 
 def new_contact_carry(B):
     """The carried state "just attached" of ``BatchedSolver.contact_step`` for B vehicles: no yaw kick, no partner."""
-    return dict(f64=np.zeros((_ffi.CONTACT_CARRY_F64, B)), i32=np.zeros((_ffi.CONTACT_CARRY_I32, B), np.int32))
+    return blank_carry(B, _ffi.CONTACT_CARRY_F64, _ffi.CONTACT_CARRY_I32_NAMES)
 
 
 def contact_dict(f, i):
     """Planes f [CONTACT_F64, B], i [CONTACT_I32, B] -> dict of [B] arrays named as _ffi.CONTACT_F64_NAMES / CONTACT_I32_NAMES and the
     planes themselves (f64, i32)."""
-    out = {k: f[c] for c, k in enumerate(_ffi.CONTACT_F64_NAMES)}
-    out.update({k: i[c] for c, k in enumerate(_ffi.CONTACT_I32_NAMES)})
-    out.update(f64=f, i32=i)
-    return out
+    return planes_dict(f, i, _ffi.CONTACT_F64_NAMES, _ffi.CONTACT_I32_NAMES)

@@ -1,6 +1,6 @@
 // contact_host.hpp -- host side of the contact model (lpvmpc_race_contact), shared by race_api.hip, which owns the binding and chooses
-// the tick's launch, contact_api.hip, which builds and reads it, and interactions_api.hip, which detaches it before the interactions
-// change.  No other translation unit includes it.
+// the tick's launch and detaches it before the interactions change, and contact_api.hip, which builds and reads it.  No other
+// translation unit includes it.
 #pragma once
 #include "contact.hpp"
 #include "interactions_host.hpp"
@@ -14,15 +14,6 @@ struct ContactBinding {
     int block = 64;
     lpvmpc_contact_config cfg{};
 };
-
-// race_api.hip: what lpvmpc_race_contact needs of the running race (false: the handle owns no race)
-struct RaceContactView {
-    int B = 0;
-    PlantSide *side = nullptr;
-    const HeatsBinding *heats = nullptr;
-    const InterBinding *inter = nullptr;
-    std::unique_ptr<ContactBinding> *slot = nullptr;
-};
-LPVMPC_HIDDEN bool lpvmpc_race_contact_view(lpvmpc_handle *h, RaceContactView &v);
-// contact_api.hip: back to the centres form (no race or nothing attached: nothing to do)
-LPVMPC_HIDDEN int lpvmpc_race_contact_detach(lpvmpc_handle *h);
+inline Planes lpvmpc_contact_planes(lpvmpc::ContactDev &d, size_t B) {
+    return lpvmpc_planes(d, B, LPVMPC_CONTACT_CARRY_F64, LPVMPC_CONTACT_CARRY_I32, LPVMPC_CONTACT_F64, LPVMPC_CONTACT_I32);
+}

@@ -58,12 +58,14 @@ extern "C" void lpvmpc_heats_default_config(lpvmpc_heats_config *c) {
 
 extern "C" int lpvmpc_race_heats(lpvmpc_handle *h, const lpvmpc_heats_config *cfg, const int32_t *heat, const int32_t *turns0) {
     const char *who = "lpvmpc_race_heats";
-    RaceHeatsView v;
-    if (!h || !lpvmpc_race_heats_view(h, v)) return fail(h, LPVMPC_E_ARG, "%s: call lpvmpc_race_init first", who);
+    RaceAttach a;
+    RC_TRY(a.begin(h, who));
+    const RaceAttachView &v = a.v;
+    hipStream_t st = a.st;
     std::vector<int32_t> off, members;
     int largest = 0, n_heats = 0;
     if (heat) {                                                                 // every check before the old attachment goes
-        int rc = lpvmpc_heat_extents(h, who, cfg); if (rc) return rc;
+        RC_TRY(lpvmpc_heat_extents(h, who, cfg));
         // indices need not be dense: the heats in use, in ascending order, take the workgroups of the launch (an empty heat takes none)
         std::vector<int32_t> ids;
         for (int b = 0; b < v.B; ++b) {
@@ -80,7 +82,7 @@ extern "C" int lpvmpc_race_heats(lpvmpc_handle *h, const lpvmpc_heats_config *cf
         std::vector<int32_t> dense(v.B, -1);
         for (int b = 0; b < v.B; ++b)
             if (heat[b] >= 0) dense[b] = (int32_t)(std::lower_bound(ids.begin(), ids.end(), heat[b]) - ids.begin());
-        rc = lpvmpc_heat_members(h, who, v.B, n_heats, dense.data(), off, members, largest); if (rc) return rc;
+        RC_TRY(lpvmpc_heat_members(h, who, v.B, n_heats, dense.data(), off, members, largest));
         if (h->trk.tab)
             for (int g = 0; g < n_heats; ++g)
                 for (int k = off[g] + 1; k < off[g + 1]; ++k)
@@ -88,66 +90,46 @@ extern "C" int lpvmpc_race_heats(lpvmpc_handle *h, const lpvmpc_heats_config *cf
                         return fail(h, LPVMPC_E_ARG, "%s: heat %d: vehicle %d is on track %d, vehicle %d on track %d: a heat shares one track", who, ids[g],
                                     members[k], h->trk_of[members[k]], members[off[g]], h->trk_of[members[off[g]]]);
     }
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = h->stream;
-    HIP_TRY(h, hipStreamSynchronize(st));                                       // no tick in flight reads the old attachment
-    { const int rd = lpvmpc_race_interactions_detach(h); if (rd) return rd; }   // the interactions read this attachment's lists and extents
-    v.slot->reset();
+    RC_TRY(lpvmpc_race_detach(h, RACE_HEATS));                                  // the old attachment goes first, and with it what reads it
     if (!heat) return LPVMPC_OK;
     std::unique_ptr<HeatsBinding> q(new (std::nothrow) HeatsBinding());         // installed once it is complete
     if (!q) return fail(h, LPVMPC_E_NOMEM, "out of host memory");
     lpvmpc::HeatDev &e = q->d;
     const size_t B = v.B, K = (size_t)v.laps + 2;
-    int32_t *d_off = nullptr, *d_members = nullptr;
-    hipError_t err = hipSuccess;
-    size_t want = 0;
-    auto take = [&](auto *&p, size_t n) { if (err == hipSuccess) { want = n; err = q->mem.alloc(p, n ? n : 8); } };
-    take(d_off, off.size() * 4); take(d_members, members.size() * 4);
-    take(e.carry_f, B * LPVMPC_HEAT_CARRY_F64 * 8); take(e.carry_i, B * LPVMPC_HEAT_CARRY_I32 * 4);
-    take(e.out_f, B * LPVMPC_HEAT_F64 * 8); take(e.out_i, B * LPVMPC_HEAT_I32 * 4);
+    const Planes pl = lpvmpc_heat_planes(e, B);
+    HeatLists lists;
+    DevTake take{q->mem};
+    lists.alloc(take, off, members); pl.alloc(take);
     take(e.line_tick, B * K * 4); take(e.line_pos, B * K * 4);
-    if (err != hipSuccess) return fail(h, LPVMPC_E_NOMEM, "%s: hipMalloc of %zu B failed: %s", who, want, hipGetErrorString(err));
+    RC_TRY(take.check(h, who, true));
     e.B = v.B; e.n_heats = n_heats; e.K = (int)K; e.hl = cfg->half_length; e.hwc = cfg->half_width_car;
-    e.off = d_off; e.members = d_members; e.plant = v.plant; e.hw = v.hw; e.slack = v.slack; e.phase = v.phase;
+    e.off = lists.off; e.members = lists.members; e.plant = v.plant; e.hw = v.hw; e.slack = v.slack; e.phase = v.phase;
     q->block = largest <= 64 ? 64 : 256;
     std::vector<double> f;
     std::vector<int32_t> i;
     blank_standings(B, heat, turns0, f, i);
-    auto run = [&]() -> int {
-        H2D(d_off, off.data(), off.size() * 4);
-        if (!members.empty()) H2D(d_members, members.data(), members.size() * 4);
-        HIP_TRY(h, hipMemsetAsync(e.carry_f, 0, B * LPVMPC_HEAT_CARRY_F64 * 8, st));
-        HIP_TRY(h, hipMemsetAsync(e.carry_i, 0, B * LPVMPC_HEAT_CARRY_I32 * 4, st));
+    return lpvmpc_race_install(h, st, *v.heats, q, [&]() -> int {
+        RC_TRY(lists.upload(h, st, off, members));
+        RC_TRY(pl.blank_carry(h, st, nullptr));
         if (turns0) H2D(e.carry_i + (size_t)LPVMPC_HEAT_CARRY_TURNS * B, turns0, B * 4);
         HIP_TRY(h, hipMemcpyAsync(e.carry_i + (size_t)LPVMPC_HEAT_CARRY_PHASE * B, v.phase, B * 4, hipMemcpyDeviceToDevice, st));
-        H2D(e.out_f, f.data(), f.size() * 8);
-        H2D(e.out_i, i.data(), i.size() * 4);
+        RC_TRY(pl.blank_out(h, st, f, i));
         HIP_TRY(h, hipMemsetAsync(e.line_tick, 0xff, B * K * 4, st));
         HIP_TRY(h, hipMemsetAsync(e.line_pos, 0xff, B * K * 4, st));
-        HIP_TRY(h, hipStreamSynchronize(st));
         return LPVMPC_OK;
-    };
-    const int rc = run();
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }                      // the host vectors outlive the copies; nothing installed
-    *v.slot = std::move(q);
-    return LPVMPC_OK;
+    });
 }
 
+static Planes standings_planes(HeatsBinding &q) { return lpvmpc_heat_planes(q.d, q.d.B); }
+
 extern "C" int lpvmpc_race_standings(lpvmpc_handle *h, double *f64, int32_t *i32, int32_t *line_tick, int32_t *line_pos) {
-    const char *who = "lpvmpc_race_standings";
-    RaceHeatsView v;
-    if (!h || !lpvmpc_race_heats_view(h, v)) return fail(h, LPVMPC_E_ARG, "%s: call lpvmpc_race_init first", who);
-    const HeatsBinding *q = v.slot->get();
-    if (!q) return fail(h, LPVMPC_E_ARG, "%s: no heats are attached (lpvmpc_race_heats)", who);
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = h->stream;
-    const size_t B = q->d.B, K = q->d.K;
-    if (f64) D2H(f64, q->d.out_f, B * LPVMPC_HEAT_F64 * 8);
-    if (i32) D2H(i32, q->d.out_i, B * LPVMPC_HEAT_I32 * 4);
-    if (line_tick) D2H(line_tick, q->d.line_tick, B * K * 4);
-    if (line_pos) D2H(line_pos, q->d.line_pos, B * K * 4);
-    HIP_TRY(h, hipStreamSynchronize(st));
-    return LPVMPC_OK;
+    return lpvmpc_race_read_planes(h, "lpvmpc_race_standings", &RaceAttachView::heats, "no heats are attached (lpvmpc_race_heats)", standings_planes,
+                                   f64, i32, [&](HeatsBinding &q, hipStream_t st) -> int {
+        const size_t B = q.d.B, K = q.d.K;
+        if (line_tick) D2H(line_tick, q.d.line_tick, B * K * 4);
+        if (line_pos) D2H(line_pos, q.d.line_pos, B * K * 4);
+        return LPVMPC_OK;
+    });
 }
 
 // one tick on caller-supplied data; one-off device buffers, freed when the call returns
@@ -155,49 +137,41 @@ extern "C" int lpvmpc_heat_step_batch(lpvmpc_handle *h, int32_t B, int32_t n_hea
                                       int32_t t, const double *pose, const double *s, const int32_t *inside, const int32_t *phase, double *carry_f64,
                                       int32_t *carry_i32, double *f64, int32_t *i32) {
     const char *who = "lpvmpc_heat_step_batch";
-    if (h && B == 0) return LPVMPC_OK;
-    if (!h) return fail(nullptr, LPVMPC_E_ARG, "%s: handle is NULL", who);
-    if (busy(h)) return fail(h, LPVMPC_E_ARG, "%s: this handle runs a fleet, cascade or race; use another handle for batch calls", who);
+    int rc;
+    if (lpvmpc_batch_done(h, B, who, rc)) return rc;
     if (B < 0 || n_heats < 0 || !heat || !L || !pose || !s || !inside || !phase || !carry_f64 || !carry_i32 || !f64 || !i32)
         return fail(h, LPVMPC_E_ARG, "%s: B < 0, n_heats < 0 or NULL argument", who);
-    int rc = lpvmpc_heat_extents(h, who, cfg); if (rc) return rc;
+    RC_TRY(lpvmpc_heat_extents(h, who, cfg));
     std::vector<int32_t> off, members;
     int largest = 0;
-    rc = lpvmpc_heat_members(h, who, B, n_heats, heat, off, members, largest); if (rc) return rc;
+    RC_TRY(lpvmpc_heat_members(h, who, B, n_heats, heat, off, members, largest));
     const size_t n = B;
     for (size_t b = 0; b < n; ++b)
         if (heat[b] >= 0 && !(std::isfinite(L[b]) && L[b] > 0)) return fail(h, LPVMPC_E_ARG, "%s: vehicle %zu: L = %g must be finite and > 0", who, b, L[b]);
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     DevArena mem;
     lpvmpc::HeatDev e{};
+    const Planes pl = lpvmpc_heat_planes(e, n);
+    HeatLists lists;
     double *d_pose = nullptr, *d_s = nullptr, *d_L = nullptr;
-    int32_t *d_off = nullptr, *d_members = nullptr, *d_inside = nullptr, *d_phase = nullptr;
-    hipError_t err = hipSuccess;
-    auto take = [&](auto *&p, size_t bytes) { if (err == hipSuccess) err = mem.alloc(p, bytes ? bytes : 8); };
-    take(d_off, off.size() * 4); take(d_members, members.size() * 4); take(d_pose, n * 3 * 8); take(d_s, n * 8); take(d_L, n * 8);
+    int32_t *d_inside = nullptr, *d_phase = nullptr;
+    DevTake take{mem};
+    lists.alloc(take, off, members); take(d_pose, n * 3 * 8); take(d_s, n * 8); take(d_L, n * 8);
     take(d_inside, n * 4); take(d_phase, n * 4);
-    take(e.carry_f, n * LPVMPC_HEAT_CARRY_F64 * 8); take(e.carry_i, n * LPVMPC_HEAT_CARRY_I32 * 4);
-    take(e.out_f, n * LPVMPC_HEAT_F64 * 8); take(e.out_i, n * LPVMPC_HEAT_I32 * 4);
-    if (err != hipSuccess) return fail(h, LPVMPC_E_NOMEM, "%s: hipMalloc failed: %s", who, hipGetErrorString(err));
+    pl.alloc(take);
+    RC_TRY(take.check(h, who, false));
     e.B = B; e.n_heats = n_heats; e.K = 0; e.hl = cfg->half_length; e.hwc = cfg->half_width_car;
-    e.off = d_off; e.members = d_members; e.pose = d_pose; e.s = d_s; e.L = d_L; e.inside = d_inside; e.phase = d_phase;
+    e.off = lists.off; e.members = lists.members; e.pose = d_pose; e.s = d_s; e.L = d_L; e.inside = d_inside; e.phase = d_phase;
     std::vector<double> f;
     std::vector<int32_t> i;
     blank_standings(n, heat, nullptr, f, i);
     hipStream_t st = h->stream;
-    auto run = [&]() -> int {
-        H2D(d_off, off.data(), off.size() * 4);
-        if (!members.empty()) H2D(d_members, members.data(), members.size() * 4);
+    return lpvmpc_run_synced(h, st, [&]() -> int {                              // nothing in flight reads the buffers when they are freed
+        RC_TRY(lists.upload(h, st, off, members));
         H2D(d_pose, pose, n * 3 * 8); H2D(d_s, s, n * 8); H2D(d_L, L, n * 8); H2D(d_inside, inside, n * 4); H2D(d_phase, phase, n * 4);
-        H2D(e.carry_f, carry_f64, n * LPVMPC_HEAT_CARRY_F64 * 8); H2D(e.carry_i, carry_i32, n * LPVMPC_HEAT_CARRY_I32 * 4);
-        H2D(e.out_f, f.data(), f.size() * 8); H2D(e.out_i, i.data(), i.size() * 4);
+        RC_TRY(pl.carry_in(h, st, carry_f64, carry_i32));
+        RC_TRY(pl.blank_out(h, st, f, i));
         HIP_TRY(h, lpvmpc::launch_heat_step(e, largest <= 64 ? 64 : 256, t, st));
-        D2H(carry_f64, e.carry_f, n * LPVMPC_HEAT_CARRY_F64 * 8); D2H(carry_i32, e.carry_i, n * LPVMPC_HEAT_CARRY_I32 * 4);
-        D2H(f64, e.out_f, f.size() * 8); D2H(i32, e.out_i, i.size() * 4);
-        HIP_TRY(h, hipStreamSynchronize(st));
-        return LPVMPC_OK;
-    };
-    rc = run();
-    (void)hipStreamSynchronize(st);                                             // nothing in flight reads the buffers when they are freed
-    return rc;
+        return pl.copy_out(h, st, carry_f64, carry_i32, f64, i32);
+    });
 }

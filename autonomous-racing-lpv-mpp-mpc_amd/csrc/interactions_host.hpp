@@ -14,18 +14,10 @@ struct InterBinding {
     lpvmpc_interaction_config cfg{};
     std::vector<double> mu_base;
 };
+inline Planes lpvmpc_interaction_planes(lpvmpc::InterDev &d, size_t B) {
+    return lpvmpc_planes(d, B, LPVMPC_INTER_CARRY_F64, LPVMPC_INTER_CARRY_I32, LPVMPC_INTER_F64, LPVMPC_INTER_I32);
+}
 
-// race_api.hip: what lpvmpc_race_interactions needs of the running race: the state a tick reads and writes, the plant side whose live
-// table it rewrites, the heats it reads and the slot that owns the binding (false: the handle owns no race)
-struct RaceInterView {
-    int B = 0;
-    double *plant = nullptr;
-    const int32_t *nstep = nullptr;
-    PlantSide *side = nullptr;
-    const HeatsBinding *heats = nullptr;
-    std::unique_ptr<InterBinding> *slot = nullptr;
-};
-LPVMPC_HIDDEN bool lpvmpc_race_inter_view(lpvmpc_handle *h, RaceInterView &v);
 // interactions_api.hip: the interactions' configuration check, its words into the kernel argument, and the planes a vehicle reads
 // before its first tick, for contact_api.hip, whose batch form takes the interactions' configuration and writes their planes
 LPVMPC_HIDDEN int lpvmpc_interaction_check_config(lpvmpc_handle *h, const char *who, const lpvmpc_interaction_config *c);

@@ -1,6 +1,9 @@
-// lpvmpc_handle.hpp -- private host-side definitions shared by the translation units that implement the C ABI
-// (lpvmpc_api.hip: solver entry points and the lap-0 fleet; cascade_api.hip: hand-off and planner + controller cascade;
-// race_api.hip: the race engine; race_state_api.hip: its snapshot, restore and clone).
+// lpvmpc_handle.hpp -- private host-side definitions shared by every translation unit that implements the C ABI, the *_api.hip files:
+// lpvmpc_api.hip (solver entry points and the lap-0 fleet), cascade_api.hip (hand-off and planner + controller cascade), race_api.hip
+// (the race engine) and race_state_api.hip (its snapshot, restore and clone); the bindings of a handle or of its engine's plant side
+// (actuator_, plant_params_, tyre_, model_params_, tunings_, observer_design_, tracks_, disturbance_, sensor_faults_api.hip); and,
+// through race_attach.hpp, what attaches to a running race (heats_, interactions_, contact_, walls_api.hip).  No kernel translation
+// unit includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,7 +23,6 @@
 struct lpvmpc_cascade;       // cascade_api.hip
 struct lpvmpc_race;          // race_api.hip
 struct DistStep;             // below: the stand-alone step's disturbance arguments
-struct HeatsBinding;         // heats_host.hpp: heats attached to a race (race_api.hip, heats_api.hip)
 
 using lpvmpc::DevCfg;
 using lpvmpc::SolveArgs;
@@ -244,16 +246,6 @@ struct RaceState {
 };
 LPVMPC_HIDDEN bool lpvmpc_race_state(lpvmpc_handle *h, RaceState &s);
 LPVMPC_HIDDEN void lpvmpc_race_set_ticks(lpvmpc_handle *h, int ticks);
-// race_api.hip: what lpvmpc_race_heats / lpvmpc_race_standings (heats_api.hip) need of the running race: its shape, the state a heat
-// tick reads, and the slot that owns the attachment (false: the handle owns no race)
-struct RaceHeatsView {
-    int B = 0, laps = 0;
-    double hw = 0, slack = 0;
-    const double *plant = nullptr;
-    const int32_t *phase = nullptr;
-    std::unique_ptr<HeatsBinding> *slot = nullptr;
-};
-LPVMPC_HIDDEN bool lpvmpc_race_heats_view(lpvmpc_handle *h, RaceHeatsView &v);
 // race_api.hip: the caller's mu words [B] (plant row word 6) while interactions are attached to the race that h owns
 // (lpvmpc_race_interactions rewrites the live words), else null: what a base copy of the live plant table takes in their place
 LPVMPC_HIDDEN const std::vector<double> *lpvmpc_race_mu_base(lpvmpc_handle *h);

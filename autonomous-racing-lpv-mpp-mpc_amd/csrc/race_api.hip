@@ -11,10 +11,7 @@
 #include <cstring>
 #include <new>
 
-#include "heats_host.hpp"
 #include "contact_host.hpp"
-#include "interactions_host.hpp"
-#include "lpvmpc_handle.hpp"
 #include "race_state.hpp"
 #include "record.hpp"
 #include "walls_host.hpp"
@@ -300,31 +297,44 @@ bool lpvmpc_race_state(lpvmpc_handle *h, RaceState &s) {
 }
 void lpvmpc_race_set_ticks(lpvmpc_handle *h, int ticks) { if (h->race) h->race->ticks = ticks; }
 
-bool lpvmpc_race_heats_view(lpvmpc_handle *h, RaceHeatsView &v) {
+bool lpvmpc_race_attach_view(lpvmpc_handle *h, RaceAttachView &v) {
     lpvmpc_race *r = h->race;
     if (!r) return false;
-    v.B = r->d.B; v.laps = r->d.laps; v.hw = r->d.hw; v.slack = r->d.slack; v.plant = r->d.plant; v.phase = r->d.phase;
-    v.slot = &r->heats;
+    v.B = r->d.B; v.laps = r->d.laps; v.hw = r->d.hw; v.slack = r->d.slack; v.plant = r->d.plant; v.nstep = r->d.nstep; v.phase = r->d.phase;
+    v.side = &r->side;
+    v.heats = &r->heats; v.inter = &r->inter; v.contact = &r->contact; v.walls = &r->walls;
     return true;
 }
 
-bool lpvmpc_race_inter_view(lpvmpc_handle *h, RaceInterView &v) {
-    lpvmpc_race *r = h->race;
-    if (!r) return false;
-    v.B = r->d.B; v.plant = r->d.plant; v.nstep = r->d.nstep; v.side = &r->side; v.heats = r->heats.get(); v.slot = &r->inter;
-    return true;
+// the detach chain (race_attach.hpp): heats -> interactions -> contact model, readers first; the walls stand alone
+int lpvmpc_race_detach_readers(lpvmpc_handle *h, RaceLayer layer) {
+    if (layer == RACE_HEATS) return lpvmpc_race_detach(h, RACE_INTERACTIONS);   // the interactions read the heats' lists and extents
+    if (layer == RACE_INTERACTIONS) return lpvmpc_race_detach(h, RACE_CONTACT); // the contact model reads the interactions' binding
+    return LPVMPC_OK;
 }
-bool lpvmpc_race_contact_view(lpvmpc_handle *h, RaceContactView &v) {
-    lpvmpc_race *r = h->race;
-    if (!r) return false;
-    v.B = r->d.B; v.side = &r->side; v.heats = r->heats.get(); v.inter = r->inter.get(); v.slot = &r->contact;
-    return true;
-}
-bool lpvmpc_race_wall_view(lpvmpc_handle *h, RaceWallView &v) {
-    lpvmpc_race *r = h->race;
-    if (!r) return false;
-    v.B = r->d.B; v.hw = r->d.hw; v.plant = r->d.plant; v.nstep = r->d.nstep; v.side = &r->side; v.slot = &r->walls;
-    return true;
+int lpvmpc_race_detach(lpvmpc_handle *h, RaceLayer layer) {
+    lpvmpc_race *r = h ? h->race : nullptr;
+    if (!r) return LPVMPC_OK;
+    RC_TRY(lpvmpc_race_detach_readers(h, layer));
+    const bool attached = layer == RACE_HEATS ? r->heats != nullptr : layer == RACE_INTERACTIONS ? r->inter != nullptr :
+                          layer == RACE_CONTACT ? r->contact != nullptr : r->walls != nullptr;
+    if (!attached) return LPVMPC_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = h->stream;
+    HIP_TRY(h, hipStreamSynchronize(st));                                       // no tick in flight reads the binding
+    switch (layer) {
+    case RACE_HEATS: r->heats.reset(); break;
+    case RACE_INTERACTIONS: {
+        const InterBinding &q = *r->inter;
+        H2D(q.d.mu_live, q.mu_base.data(), q.mu_base.size() * 8);               // the base words back to the live table
+        HIP_TRY(h, hipStreamSynchronize(st));
+        r->inter.reset();
+        break;
+    }
+    case RACE_CONTACT: r->contact.reset(); break;                               // back to the centres form
+    case RACE_WALLS: r->walls.reset(); break;
+    }
+    return LPVMPC_OK;
 }
 const std::vector<double> *lpvmpc_race_mu_base(lpvmpc_handle *h) {
     return h && h->race && h->race->inter ? &h->race->inter->mu_base : nullptr;

@@ -57,30 +57,24 @@ extern "C" void lpvmpc_wall_default_config(lpvmpc_wall_config *c) {
 
 extern "C" int lpvmpc_race_walls(lpvmpc_handle *h, const lpvmpc_wall_config *cfg) {
     const char *who = "lpvmpc_race_walls";
-    RaceWallView v;
-    if (!h || !lpvmpc_race_wall_view(h, v)) return fail(h, LPVMPC_E_ARG, "%s: call lpvmpc_race_init first", who);
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = h->stream;
-    if (!cfg) {
-        HIP_TRY(h, hipStreamSynchronize(st));                                   // no tick in flight reads the binding
-        v.slot->reset();
-        return LPVMPC_OK;
-    }
+    RaceAttach a;
+    RC_TRY(a.begin(h, who));
+    const RaceAttachView &v = a.v;
+    hipStream_t st = a.st;
+    if (!cfg) return lpvmpc_race_detach(h, RACE_WALLS);
     if (!v.side->veh.d.p)
         return fail(h, LPVMPC_E_ARG, "%s: the race has no plant table (start it through lpvmpc_race_init_vehicles / lpvmpc_race_init_tyres): there is "
                     "no mass and no yaw inertia to answer an impulse with", who);
-    int rc = check_config(h, who, cfg); if (rc) return rc;
+    RC_TRY(check_config(h, who, cfg));
     std::unique_ptr<WallBinding> q(new (std::nothrow) WallBinding());           // installed once it is complete
     if (!q) return fail(h, LPVMPC_E_NOMEM, "out of host memory");
     const size_t B = v.B;
     const double *live = v.side->veh.d.p;                                       // [7][B]
     lpvmpc::WallDev &e = q->d;
-    hipError_t err = hipSuccess;
-    size_t want = 0;
-    auto take = [&](auto *&p, size_t n) { if (err == hipSuccess) { want = n; err = q->mem.alloc(p, n ? n : 8); } };
-    take(e.carry_f, B * LPVMPC_WALL_CARRY_F64 * 8); take(e.carry_i, B * LPVMPC_WALL_CARRY_I32 * 4);
-    take(e.out_f, B * LPVMPC_WALL_F64 * 8); take(e.out_i, B * LPVMPC_WALL_I32 * 4);
-    if (err != hipSuccess) return fail(h, LPVMPC_E_NOMEM, "%s: hipMalloc of %zu B failed: %s", who, want, hipGetErrorString(err));
+    const Planes pl = lpvmpc_wall_planes(e, B);
+    DevTake take{q->mem};
+    pl.alloc(take);
+    RC_TRY(take.check(h, who, true));
     e.B = v.B;
     set_track(h, v.hw, e);
     set_config(*cfg, e);
@@ -89,33 +83,17 @@ extern "C" int lpvmpc_race_walls(lpvmpc_handle *h, const lpvmpc_wall_config *cfg
     std::vector<double> f;
     std::vector<int32_t> i, ci;
     blank_outputs(B, f, i, ci);
-    auto run = [&]() -> int {
-        HIP_TRY(h, hipMemsetAsync(e.carry_f, 0, B * LPVMPC_WALL_CARRY_F64 * 8, st));
-        H2D(e.carry_i, ci.data(), ci.size() * 4);
-        H2D(e.out_f, f.data(), f.size() * 8);
-        H2D(e.out_i, i.data(), i.size() * 4);
-        HIP_TRY(h, hipStreamSynchronize(st));                                   // (and no tick in flight reads the old binding)
-        return LPVMPC_OK;
-    };
-    rc = run();
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }                      // the host vectors outlive the copies; nothing installed
-    *v.slot = std::move(q);
-    return LPVMPC_OK;
+    return lpvmpc_race_install(h, st, *v.walls, q, [&]() -> int {              // (its synchronisation: no tick in flight reads the old binding)
+        RC_TRY(pl.blank_carry(h, st, ci.data()));
+        return pl.blank_out(h, st, f, i);
+    });
 }
 
+static Planes read_planes(WallBinding &q) { return lpvmpc_wall_planes(q.d, q.d.B); }
+
 extern "C" int lpvmpc_race_walls_read(lpvmpc_handle *h, double *f64, int32_t *i32) {
-    const char *who = "lpvmpc_race_walls_read";
-    RaceWallView v;
-    if (!h || !lpvmpc_race_wall_view(h, v)) return fail(h, LPVMPC_E_ARG, "%s: call lpvmpc_race_init first", who);
-    const WallBinding *q = v.slot->get();
-    if (!q) return fail(h, LPVMPC_E_ARG, "%s: no walls are attached (lpvmpc_race_walls)", who);
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = h->stream;
-    const size_t B = q->d.B;
-    if (f64) D2H(f64, q->d.out_f, B * LPVMPC_WALL_F64 * 8);
-    if (i32) D2H(i32, q->d.out_i, B * LPVMPC_WALL_I32 * 4);
-    HIP_TRY(h, hipStreamSynchronize(st));
-    return LPVMPC_OK;
+    return lpvmpc_race_read_planes(h, "lpvmpc_race_walls_read", &RaceAttachView::walls, "no walls are attached (lpvmpc_race_walls)", read_planes, f64,
+                                   i32);
 }
 
 // one tick on caller-supplied data; one-off device buffers, freed when the call returns
@@ -123,47 +101,39 @@ extern "C" int lpvmpc_wall_step_batch(lpvmpc_handle *h, int32_t B, const lpvmpc_
                                       const double *plant_params, const int32_t *nstep, double *carry_f64, int32_t *carry_i32, double *f64,
                                       int32_t *i32) {
     const char *who = "lpvmpc_wall_step_batch";
-    if (h && B == 0) return LPVMPC_OK;
-    if (!h) return fail(nullptr, LPVMPC_E_ARG, "%s: handle is NULL", who);
-    if (busy(h)) return fail(h, LPVMPC_E_ARG, "%s: this handle runs a fleet, cascade or race; use another handle for batch calls", who);
+    int rc;
+    if (lpvmpc_batch_done(h, B, who, rc)) return rc;
     if (B < 0 || !cfg || !plant || !plant_params || !carry_f64 || !carry_i32 || !f64 || !i32)
         return fail(h, LPVMPC_E_ARG, "%s: B < 0 or NULL argument", who);
-    int rc = lpvmpc_need_track(h, who); if (rc) return rc;
-    rc = lpvmpc_tracks_check(h, B, who); if (rc) return rc;
+    RC_TRY(lpvmpc_need_track(h, who));
+    RC_TRY(lpvmpc_tracks_check(h, B, who));
     if (!h->trk.tab && !(std::isfinite(half_width) && half_width >= 0))
         return fail(h, LPVMPC_E_ARG, "%s: half_width = %g must be finite and >= 0", who, half_width);
-    rc = check_config(h, who, cfg); if (rc) return rc;
+    RC_TRY(check_config(h, who, cfg));
     std::vector<double> tab;                                                    // [7][B], checked (m > 0, Iz > 0)
-    rc = lpvmpc_plant_rows(h, B, plant_params, h->cfg, 0.0, who, tab); if (rc) return rc;
+    RC_TRY(lpvmpc_plant_rows(h, B, plant_params, h->cfg, 0.0, who, tab));
     const size_t n = B;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     DevArena mem;
     lpvmpc::WallDev e{};
+    const Planes pl = lpvmpc_wall_planes(e, n);
     double *d_m = nullptr, *d_Iz = nullptr;
     int32_t *d_nstep = nullptr;
-    hipError_t err = hipSuccess;
-    auto take = [&](auto *&p, size_t bytes) { if (err == hipSuccess) err = mem.alloc(p, bytes ? bytes : 8); };
+    DevTake take{mem};
     take(e.plant, n * 8 * 8); take(d_m, n * 8); take(d_Iz, n * 8);
     if (nstep) take(d_nstep, n * 4);
-    take(e.carry_f, n * LPVMPC_WALL_CARRY_F64 * 8); take(e.carry_i, n * LPVMPC_WALL_CARRY_I32 * 4);
-    take(e.out_f, n * LPVMPC_WALL_F64 * 8); take(e.out_i, n * LPVMPC_WALL_I32 * 4);
-    if (err != hipSuccess) return fail(h, LPVMPC_E_NOMEM, "%s: hipMalloc failed: %s", who, hipGetErrorString(err));
+    pl.alloc(take);
+    RC_TRY(take.check(h, who, false));
     e.B = B; e.nstep = d_nstep; e.m = d_m; e.Iz = d_Iz;
     set_track(h, half_width, e);
     set_config(*cfg, e);
     hipStream_t st = h->stream;
-    auto run = [&]() -> int {
+    return lpvmpc_run_synced(h, st, [&]() -> int {                              // nothing in flight reads the buffers when they are freed
         H2D(e.plant, plant, n * 8 * 8); H2D(d_m, tab.data() + 2 * n, n * 8); H2D(d_Iz, tab.data() + 3 * n, n * 8);
         if (nstep) H2D(d_nstep, nstep, n * 4);
-        H2D(e.carry_f, carry_f64, n * LPVMPC_WALL_CARRY_F64 * 8); H2D(e.carry_i, carry_i32, n * LPVMPC_WALL_CARRY_I32 * 4);
+        RC_TRY(pl.carry_in(h, st, carry_f64, carry_i32));
         HIP_TRY(h, lpvmpc::launch_wall_tick(e, t, st));                        // (every vehicle's output words are written by its quad)
         D2H(plant, e.plant, n * 8 * 8);
-        D2H(carry_f64, e.carry_f, n * LPVMPC_WALL_CARRY_F64 * 8); D2H(carry_i32, e.carry_i, n * LPVMPC_WALL_CARRY_I32 * 4);
-        D2H(f64, e.out_f, n * LPVMPC_WALL_F64 * 8); D2H(i32, e.out_i, n * LPVMPC_WALL_I32 * 4);
-        HIP_TRY(h, hipStreamSynchronize(st));
-        return LPVMPC_OK;
-    };
-    rc = run();
-    (void)hipStreamSynchronize(st);                                             // nothing in flight reads the buffers when they are freed
-    return rc;
+        return pl.copy_out(h, st, carry_f64, carry_i32, f64, i32);
+    });
 }

@@ -5,6 +5,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _ffi
+from ._planes import blank_carry, planes_dict
 
 
 def check_heats(heat, B, track_of=None):
@@ -43,7 +44,7 @@ def new_carry(B, turns0=None, phase0=None, lines=0):
     """The carried state "just attached" of ``BatchedSolver.heat_step`` for B vehicles: flag word 0, TURNS = ``turns0`` (default 0),
     PHASE = ``phase0`` (the phases before the attach, default 0: running).  ``lines`` > 0 adds the line tables line_tick / line_pos
     [B, lines] (-1), which heat_step fills from the carried crossing count as the race's kernel does on the device."""
-    c = dict(f64=np.zeros((_ffi.HEAT_CARRY_F64, B)), i32=np.zeros((_ffi.HEAT_CARRY_I32, B), np.int32))
+    c = blank_carry(B, _ffi.HEAT_CARRY_F64, _ffi.HEAT_CARRY_I32_NAMES)
     if turns0 is not None:
         c["i32"][_ffi.HEAT_CARRY_I32_NAMES.index("turns")] = np.asarray(turns0, np.int32).reshape(B)
     if phase0 is not None:
@@ -57,9 +58,7 @@ def new_carry(B, turns0=None, phase0=None, lines=0):
 def standings_dict(f, i, line_tick=None, line_pos=None):
     """Standings planes f [HEAT_F64, B], i [HEAT_I32, B] -> dict of [B] arrays named as _ffi.HEAT_F64_NAMES / HEAT_I32_NAMES, the
     planes themselves (f64, i32) and the line tables."""
-    out = {k: f[c] for c, k in enumerate(_ffi.HEAT_F64_NAMES)}
-    out.update({k: i[c] for c, k in enumerate(_ffi.HEAT_I32_NAMES)})
-    out.update(f64=f, i32=i)
+    out = planes_dict(f, i, _ffi.HEAT_F64_NAMES, _ffi.HEAT_I32_NAMES)
     if line_tick is not None:
         out.update(line_tick=line_tick, line_pos=line_pos)
     return out

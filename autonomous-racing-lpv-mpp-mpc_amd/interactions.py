@@ -8,6 +8,7 @@ import math
 import numpy as np
 
 from . import _ffi
+from ._planes import blank_carry, planes_dict
 
 # lpvmpc_interaction_default_config: invented values of the right order for a 1:10 car, nothing in the reference fixes them
 DEFAULTS = dict(draft_gain=0.3, wake_length=3.0, wake_half_width=0.3, contact=1, restitution=0.2, push=0.5)
@@ -52,18 +53,13 @@ def as_config(cfg):
 def new_carry(B):
     """The carried state "just attached" of ``BatchedSolver.interaction_step`` for B vehicles: no impulse, no hit (first_hit_tick -1),
     no drafting tick."""
-    c = dict(f64=np.zeros((_ffi.INTER_CARRY_F64, B)), i32=np.zeros((_ffi.INTER_CARRY_I32, B), np.int32))
-    c["i32"][_ffi.INTER_CARRY_I32_NAMES.index("first_hit_tick")] = -1
-    return c
+    return blank_carry(B, _ffi.INTER_CARRY_F64, _ffi.INTER_CARRY_I32_NAMES, ("first_hit_tick",))
 
 
 def interactions_dict(f, i):
     """Output planes f [INTER_F64, B], i [INTER_I32, B] -> dict of [B] arrays named as _ffi.INTER_F64_NAMES / INTER_I32_NAMES and the
     planes themselves (f64, i32)."""
-    out = {k: f[c] for c, k in enumerate(_ffi.INTER_F64_NAMES)}
-    out.update({k: i[c] for c, k in enumerate(_ffi.INTER_I32_NAMES)})
-    out.update(f64=f, i32=i)
-    return out
+    return planes_dict(f, i, _ffi.INTER_F64_NAMES, _ffi.INTER_I32_NAMES)
 
 
 def grid(track, n, gap, stagger=0.0, vx=1.0, position=None):

@@ -8,6 +8,7 @@ import math
 import numpy as np
 
 from . import _ffi
+from ._planes import blank_carry, planes_dict
 
 # lpvmpc_wall_default_config: invented values of the right order for a 1:10 car, nothing in the reference fixes them
 DEFAULTS = dict(margin=0.25, reach=0.5, half_length=0.4, half_width_car=0.2, restitution=0.2, friction=0.3, push=0.5, yaw_response=1)
@@ -61,18 +62,13 @@ def as_config(cfg):
 
 def new_carry(B):
     """The carried state "just attached" of ``BatchedSolver.wall_step`` for B vehicles: no impulse, no hit (first_hit_tick -1)."""
-    c = dict(f64=np.zeros((_ffi.WALL_CARRY_F64, B)), i32=np.zeros((_ffi.WALL_CARRY_I32, B), np.int32))
-    c["i32"][CARRY_I32_NAMES.index("first_hit_tick")] = -1
-    return c
+    return blank_carry(B, _ffi.WALL_CARRY_F64, CARRY_I32_NAMES, ("first_hit_tick",))
 
 
 def walls_dict(f, i):
     """Output planes f [WALL_F64, B], i [WALL_I32, B] -> dict of [B] arrays named as _ffi.WALL_F64_NAMES / WALL_I32_NAMES and the planes
     themselves (f64, i32)."""
-    out = {k: f[c] for c, k in enumerate(F64_NAMES)}
-    out.update({k: i[c] for c, k in enumerate(I32_NAMES)})
-    out.update(f64=f, i32=i)
-    return out
+    return planes_dict(f, i, F64_NAMES, I32_NAMES)
 
 
 def corners(plant, cfg=None):

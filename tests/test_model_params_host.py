@@ -141,4 +141,9 @@ def test_per_vehicle_kernels_have_their_own_translation_unit():
     mk = open(os.path.join(CSRC, "Makefile")).read()
     rule = re.search(r"^veh_lpv_eval\.o:.*\n\t(.*)$", mk, flags=re.M).group(1)
     assert "-ffp-contract=off" in rule and "$(RESCHK)" in rule and all(k in rule for k in five)
-    assert mk.count("veh_lpv_eval.o") >= 4 and mk.count("model_params_api.o") >= 4
+    # both objects are linked into the library and into the stamps build, which take the one list, and the host object has a rule
+    objs = re.search(r"^OBJS\s*:=((?:.*\\\n)*.*)$", mk, flags=re.M).group(1).replace("\\\n", " ").split()
+    assert "veh_lpv_eval.o" in objs and "model_params_api.o" in objs
+    assert re.search(r"^\$\(OUT\): \$\(OBJS\)\n\t.* -o \$@ \$\(OBJS\)$", mk, flags=re.M)
+    assert "STAMPOBJS := $(OBJS:admm_solve.o=admm_solve_stamps.o)" in mk and re.search(r"^\t.* -o \$@ \$\(STAMPOBJS\)$", mk, flags=re.M)
+    assert "HOSTOBJS := $(filter %_api.o fleet_launch.o,$(OBJS))" in mk and re.search(r"^\$\(HOSTOBJS\): %\.o: %\.hip\b", mk, flags=re.M)
