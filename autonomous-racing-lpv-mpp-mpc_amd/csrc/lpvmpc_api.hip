@@ -311,6 +311,10 @@ int lpvmpc_launch_solve_timed(lpvmpc_handle *h, const SolveArgs &a, hipStream_t 
 int lpvmpc_launch_solve_warm(lpvmpc_handle *h, SolveArgs a, hipStream_t st) {
     a.state = h->warm_mode ? h->d_state : nullptr;
     a.warm = (h->warm_mode && h->state_valid_B == a.B) ? h->warm_mode : 0;
+    // a cold launch with the option on: what the state holds (uninitialised memory, solves from before the option was set again or of
+    // another batch size) must not reach the next call through an instance this launch does not write (lpvmpc_solve_batch_masked).
+    // Zeros are a cold start: the kernel stores them itself for an instance without a solution.
+    if (h->warm_mode && !a.warm) HIP_TRY(h, hipMemsetAsync(h->d_state, 0, (size_t)a.B * 3 * (h->cfg.N + 1) * 8 * 8, st));
     int rc = lpvmpc_launch_solve_timed(h, a, st); if (rc) return rc;
     if (h->warm_mode) h->state_valid_B = a.B;
     return LPVMPC_OK;

@@ -130,6 +130,19 @@ int lpvmpc_last_error_code(void);
  * "warm_start": 0 = every solve starts from x = z = y = 0 like the reference (fresh OSQP object per call,
  * CTRL:302,316 / PLAN:204-208; default); 1 = start from the previous solve's (x, y) of the same handle and
  * batch size; 2 = the same shifted by one stage (receding horizon).  Opt-in, changes iteration counts, not optima.
+ * Applied as osqp_warm_start does (x, y as given, z = A x).  The shift of mode 2: stage k takes the previous solve's stage k + 1 and
+ * the last stage that exists for a variable or row is kept -- states, dynamics rows and the planner's state-box rows run to stage N,
+ * inputs, the planner's input-box rows and the controller's box rows to stage N - 1; of the steeringDelay pinned-steering rows, the row
+ * of stage k takes the row of stage k + 1 and the last one (stage steeringDelay - 1) starts at 0, stage steeringDelay having none.
+ * What is kept of a solve: the returned point with its duals -- the polished ones after an accepted polish, the ADMM iterate's otherwise
+ * (rejected polish, SOLVED_INACCURATE, MAX_ITER_REACHED); zeros, a cold start, for an instance without a solution (PRIMAL / DUAL
+ * INFEASIBLE, exact or inaccurate, UNSOLVED).  Whose state is valid: an instance warm-starts from ITS OWN most recent solve since the
+ * option was last set (setting it again, to the same value too, is a fresh start), the workspace was (re)allocated or a fleet, cascade or
+ * race was initialised on the handle; otherwise it starts cold.  A call of another batch size than the previous one starts cold, and an
+ * instance that lpvmpc_solve_batch_masked leaves inactive keeps the state (or the cold start) it had.  Against the oracle's warm-started
+ * run (tests/test_gpu_warm_start.py, every solve route, both modes, two warm ticks): status, iteration count and polish flag equal on
+ * every instance the oracle itself decides robustly (all controller instances, 88 % .. 98 % of the planners':
+ * tests/golden/warm_start/make_robust.py).
  * "cascade_prefetch" (0/1, default 1): read by lpvmpc_cascade_init on the controller handle, see there.
  * "kernel_variant" 3 = the DPP two-wavefront kernels of round 1 for the controller at N = 20 and the planner at N = 20 / 30 / 40 (their
  * defaults run the KKT sweeps and the factorisation on the matrix cores; the planner at N = 30 / 40 with FOUR wavefronts per instance, the

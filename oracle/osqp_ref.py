@@ -59,6 +59,7 @@ def lib():
         _lib = C.CDLL(build())
         _lib.osqp_ref_default_settings.argtypes = [C.POINTER(Settings)]
         _lib.osqp_ref_solve.restype = C.c_int
+        _lib.osqp_ref_solve_ws.restype = C.c_int
     return _lib
 
 
@@ -88,12 +89,14 @@ def _ptr(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
 
-def solve_qp(P, q, A, l, u, perm="rcm", **settings):
+def solve_qp(P, q, A, l, u, perm="rcm", x_ws=None, y_ws=None, **settings):
     """Solve min 1/2 x'Px + q'x s.t. l <= Ax <= u with the OSQP restatement.
 
     ``P`` (n,n) symmetric, ``A`` (m,n): dense arrays or scipy sparse.  Returns a
     namespace ``x, y, info`` where ``info`` carries iter / status_val / status /
-    status_polish / obj_val / pri_res / dua_res / rho_updates / rho_estimate."""
+    status_polish / obj_val / pri_res / dua_res / rho_updates / rho_estimate.
+    ``x_ws`` (n,), ``y_ws`` (m,): an unscaled warm start as osqp_warm_start takes it
+    (osqp_ref_solve_ws: x <- D^-1 x_ws, y <- c E^-1 y_ws, z <- A x); None: cold."""
     P = sp.csc_matrix(P)
     A = sp.csc_matrix(A)
     n, m = P.shape[0], A.shape[0]
@@ -108,13 +111,18 @@ def solve_qp(P, q, A, l, u, perm="rcm", **settings):
     s = settings.pop("settings", None) or default_settings(**settings)
     x = np.empty(n); y = np.empty(m)
     info = Info()
+    if x_ws is not None:
+        x_ws = np.ascontiguousarray(x_ws, dtype=np.float64).reshape(n)
+    if y_ws is not None:
+        y_ws = np.ascontiguousarray(y_ws, dtype=np.float64).reshape(m)
     Pp = Pu.indptr.astype(np.int32); Pi = Pu.indices.astype(np.int32); Px = Pu.data.astype(np.float64)
     Ap = A.indptr.astype(np.int32); Ai = A.indices.astype(np.int32); Ax = A.data.astype(np.float64)
-    rc = lib().osqp_ref_solve(
+    rc = lib().osqp_ref_solve_ws(
         C.c_int(n), C.c_int(m), _ptr(Pp, C.c_int), _ptr(Pi, C.c_int), _ptr(Px, C.c_double), _ptr(q, C.c_double),
         _ptr(Ap, C.c_int), _ptr(Ai, C.c_int), _ptr(Ax, C.c_double), _ptr(l, C.c_double), _ptr(u, C.c_double),
-        _ptr(perm, C.c_int) if perm is not None else None, C.byref(s), _ptr(x, C.c_double), _ptr(y, C.c_double),
-        C.byref(info))
+        _ptr(perm, C.c_int) if perm is not None else None, C.byref(s),
+        _ptr(x_ws, C.c_double) if x_ws is not None else None, _ptr(y_ws, C.c_double) if y_ws is not None else None,
+        _ptr(x, C.c_double), _ptr(y, C.c_double), C.byref(info))
     if rc != 0:
         raise RuntimeError("osqp_ref_solve failed (KKT factorisation), rc=%d" % rc)
     return SimpleNamespace(
@@ -234,7 +242,7 @@ def instance_qp(w, kind, j, params=None, limits=None):
                            p["min_vel"], **lim)
 
 
-def tick_batch_qp(w, kind, settings=None, params=None, limits=None, nthreads=16, qps=None, order="stage"):
+def tick_batch_qp(w, kind, settings=None, params=None, limits=None, nthreads=16, qps=None, order="stage", warm=None):
     """One tick of a batch, instance by instance: the LPV roll-out and the reference's QP (instance_qp: vehicle ``params``,
     QP ``limits``) solved by the OSQP restatement under ``settings`` (a BatchedSolver settings dict, see osqp_settings).
     ``kind`` "controller" (``u_old`` (B, 2 + d): d = steeringDelay pinned-steering rows) or "planner".  Elimination order:
@@ -245,7 +253,9 @@ def tick_batch_qp(w, kind, settings=None, params=None, limits=None, nthreads=16,
     for an instance without an answer (-10).  ``nthreads`` (<= 16) solves run at a time (the solver releases the GIL).  ``qps``: the instances' QPs (a list of instance_qp results
     or None entries for a roll-out that left the track) when the caller solves the same batch under several settings.
     ``order`` "rcm": solve_qp's default elimination order instead of the stage-wise one (the same KKT matrix: the two results
-    differ by round-off alone, the yardstick of tests/_tolerance.py check_resid)."""
+    differ by round-off alone, the yardstick of tests/_tolerance.py check_resid).  ``warm``: (z, y) of shapes (B, nz) and (B, m), the
+    warm start of every instance as solve_qp takes it, already shifted by the caller (tests/_warm_ref.py shift_state); a row of
+    zeros is a cold start."""
     from concurrent.futures import ThreadPoolExecutor
     N = int(w["N"])
     x0 = np.asarray(w["x0"], np.float64); B = x0.shape[0]
@@ -270,7 +280,8 @@ def tick_batch_qp(w, kind, settings=None, params=None, limits=None, nthreads=16,
             qp = instance_qp(w, kind, j, params, limits) if qps is None else qps[j]
             if qp is None:
                 raise ValueError("no QP")
-            r = solve_qp(qp.P, qp.q, qp.A, qp.l, qp.u, perm=perm, **kw)
+            ws = {} if warm is None else dict(x_ws=warm[0][j], y_ws=warm[1][j])
+            r = solve_qp(qp.P, qp.q, qp.A, qp.l, qp.u, perm=perm, **ws, **kw)
         except (ValueError, RuntimeError):
             return np.full(nz, np.nan), np.full(m, np.nan), -10, 0, 0, (np.nan,) * 4
         return r.x, r.y, r.info.status_val, r.info.iter, r.info.status_polish, (r.info.pri_res, r.info.dua_res, r.info.obj_val, r.info.rho_final)
