@@ -159,6 +159,23 @@ CONTACT_CARRY_F64_NAMES = ("yaw_kick_total",)
 CONTACT_CARRY_I32_NAMES = ("max_partners",)
 
 
+class EventConfig(C.Structure):
+    """Mirror of ``struct lpvmpc_event_config`` (include/lpvmpc.h)."""
+    _fields_ = [("capacity", _i), ("kinds", C.c_uint32), ("reserved", _i * 2)]
+
+
+# race event log (LPVMPC_EVENT_*): an event's words i32 [EVENT_I32] / f64 [EVENT_F64], the kinds, the per-vehicle outputs and the carried
+# state of the batch form, in channel order
+EVENT_I32, EVENT_F64, EVENT_OUT_I32, EVENT_CARRY_F64, EVENT_CARRY_I32 = 6, 2, 2, 2, 11
+EVENT_I32_NAMES = ("tick", "kind", "vehicle", "other", "a", "b")
+EVENT_F64_NAMES = ("v0", "v1")
+EVENT_KIND_NAMES = ("lap", "finish", "lost", "pass", "contact_begin", "contact_end", "wall_hit", "wall_clear")     # kinds 1 .. 8
+EVENT_ALL_KINDS = 0x1FE
+EVENT_OUT_I32_NAMES = ("count", "count_total")
+EVENT_CARRY_F64_NAMES = ("min_clearance", "max_impulse")
+EVENT_CARRY_I32_NAMES = ("flags", "phase", "lap", "position", "class", "contact", "nearest", "contact_start", "hit", "hit_start", "count_total")
+
+
 # race recorder channels (LPVMPC_REC_*): f64 [REC_F64][B] and i32 [REC_I32][B] per record, named in channel order
 REC_F64, REC_I32 = 29, 8
 REC_PLANT, REC_LOCAL, REC_CMD, REC_REF, REC_TRACK, REC_EST = 0, 8, 14, 16, 20, 23
@@ -232,7 +249,8 @@ EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_d
            "lpvmpc_sensor_fault_default_config", "lpvmpc_set_sensor_faults", "lpvmpc_sensor_faults_read", "lpvmpc_sensor_step_batch",
            "lpvmpc_interaction_default_config", "lpvmpc_race_interactions", "lpvmpc_race_interactions_read", "lpvmpc_interaction_step_batch",
            "lpvmpc_wall_default_config", "lpvmpc_race_walls", "lpvmpc_race_walls_read", "lpvmpc_wall_step_batch",
-           "lpvmpc_contact_default_config", "lpvmpc_race_contact", "lpvmpc_race_contact_read", "lpvmpc_contact_step_batch")
+           "lpvmpc_contact_default_config", "lpvmpc_race_contact", "lpvmpc_race_contact_read", "lpvmpc_contact_step_batch",
+           "lpvmpc_event_default_config", "lpvmpc_race_events", "lpvmpc_race_events_read", "lpvmpc_event_step_batch")
 
 _lib = None
 
@@ -491,6 +509,17 @@ def load():
             getattr(lib, name).restype = C.c_int
     except AttributeError:
         pass
+    try:        # (nor the race event log)
+        lib.lpvmpc_event_default_config.argtypes = [P(EventConfig)]
+        lib.lpvmpc_event_default_config.restype = None
+        lib.lpvmpc_race_events.argtypes = [vp, P(EventConfig)]
+        lib.lpvmpc_race_events_read.argtypes = [vp, _i, P(C.c_int64), P(_i), vp, vp, vp]
+        lib.lpvmpc_event_step_batch.argtypes = [vp, _i, _i, vp, vp, vp, _i, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, P(C.c_int64), _i, vp, vp,
+                                                P(_i), vp]
+        for name in ("lpvmpc_race_events", "lpvmpc_race_events_read", "lpvmpc_event_step_batch"):
+            getattr(lib, name).restype = C.c_int
+    except AttributeError:
+        pass
     for name in ("lpvmpc_handoff_length", "lpvmpc_handoff_operators", "lpvmpc_handoff_setup", "lpvmpc_handoff_batch",
                  "lpvmpc_cascade_init", "lpvmpc_cascade_tick", "lpvmpc_cascade_read"):
         getattr(lib, name).restype = C.c_int
@@ -561,6 +590,12 @@ def default_wall_config():
 def default_contact_config():
     cfg = ContactConfig()
     load().lpvmpc_contact_default_config(C.byref(cfg))
+    return cfg
+
+
+def default_event_config():
+    cfg = EventConfig()
+    load().lpvmpc_event_default_config(C.byref(cfg))
     return cfg
 
 

@@ -1,4 +1,4 @@
-"""The planes of a race attachment (heats, interactions, contact model, walls), [W, B] each, on the host: the named view of the output
+"""The planes of a race attachment (heats, interactions, contact model, walls, event log), [W, B] each, on the host: the named view of the output
 planes and the carried state "just attached"."""
 from __future__ import annotations
 

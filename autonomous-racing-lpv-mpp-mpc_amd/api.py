@@ -1089,6 +1089,83 @@ class BatchedSolver:
                                                    ptr(ci), ptr(f), ptr(i)))
         return plant, W.walls_dict(f, i), dict(f64=cf, i32=ci)
 
+    # -- race event log: an ordered device-side record of what happened (lpvmpc_race_events / _read, lpvmpc_event_step_batch; events.py) --
+    def race_events(self, cfg=None, detach=False):
+        """Attach the event log from the next tick on (lpvmpc_race_events): ``cfg`` an ``events.event_config(...)`` result, a dict of
+        its arguments (capacity, kinds), or None for the defaults (65536 events, every kind).  Attaching again replaces the binding
+        and its count starts at 0; ``detach=True`` detaches.  Independent of heats, interactions, contact model and walls, in any
+        order: it only observes, and it meets a heats or walls attachment at "first sight" (no event from that source on that tick)."""
+        from . import events as E
+        self._race_B("race_events")
+        _race_attach(self, self._lib.lpvmpc_race_events, None if detach else E.as_config(cfg))
+
+    def race_events_read(self, n=None):
+        """Synchronise and return the last ``n`` kept events, oldest first (lpvmpc_race_events_read; None: all that are kept): a dict
+        with ``events`` (an ``events.events_table``), ``total`` (events since the attach), ``kept`` (= min(total, capacity)) and the
+        per-vehicle planes ``count`` / ``count_total`` [B] (``i32`` [2, B])."""
+        from . import events as E
+        B = self._race_B("race_events_read")
+        if n is not None and int(n) < 0:
+            raise ValueError("race_events_read: n = %r must be >= 0" % (n,))
+        total = C.c_int64(0); kept = _ffi._i(0)
+        out = np.zeros((_ffi.EVENT_OUT_I32, B), np.int32)
+        self._chk(self._lib.lpvmpc_race_events_read(self._h, 0, C.byref(total), C.byref(kept), None, None, ptr(out)))
+        m = kept.value if n is None else min(int(n), kept.value)
+        i = np.empty((m, _ffi.EVENT_I32), np.int32); f = np.empty((m, _ffi.EVENT_F64))
+        if m:                                   # (no tick runs between the two calls: both synchronise the engine's stream)
+            self._chk(self._lib.lpvmpc_race_events_read(self._h, m, C.byref(total), C.byref(kept), ptr(i), ptr(f), None))
+        return dict(events=E.events_table(i, f), total=int(total.value), kept=int(kept.value), count=out[0], count_total=out[1], i32=out)
+
+    def event_step(self, t, phase, lap, lap_value, heats=None, heat=None, walls=None, kinds=None, carry=None, max_events=None, n_heats=None):
+        """One tick of the log's device function on the caller's data (lpvmpc_event_step_batch): ``t`` the tick number, ``phase`` /
+        ``lap`` [B] the race's rows after the tick, ``lap_value`` [B] the V0 of a LAP event; ``heats`` the heats' two output planes
+        (a dict with ``f64`` [5, B] / ``i32`` [10, B], as ``race_standings`` / ``heat_step`` return; None: no heats) with ``heat`` [B]
+        the heat of each vehicle; ``walls`` the walls' planes alike (None: no walls); ``kinds`` as ``events.kinds_mask``; ``carry`` the
+        state returned by the previous call (None: ``events.new_carry(B)``, just attached); ``max_events`` the rows of the returned
+        table at most (None: as many as a tick can produce).  Returns (table of this tick's events in order, cut to ``max_events``;
+        n_events the tick produced; the planes dict with count / count_total; the new carry)."""
+        from . import events as E
+        ph = np.ascontiguousarray(np.asarray(phase).reshape(-1), np.int32)
+        B = ph.shape[0]
+        lp = np.ascontiguousarray(np.asarray(lap).reshape(-1), np.int32)
+        lv = f64(np.broadcast_to(np.asarray(lap_value, float), (B,)), (B,), "lap_value")
+        if lp.shape[0] != B:
+            raise ValueError("event_step: phase and lap must have one entry per vehicle (%d)" % B)
+        mask = E.kinds_mask(kinds)
+        if (heats is None) != (heat is None):
+            raise ValueError("event_step: heats (the two planes) and heat (the heat of each vehicle) come together")
+        hf = hi = h = wf = wi = None
+        nh = 0
+        if heats is not None:
+            from . import heats as H
+            h = H.check_heats(heat, B)
+            nh = int(h.max()) + 1 if n_heats is None else int(n_heats)
+            hf = f64(heats["f64"], (_ffi.HEAT_F64, B), "heats f64")
+            hi = np.ascontiguousarray(heats["i32"], np.int32)
+            if hi.shape != (_ffi.HEAT_I32, B):
+                raise ValueError("event_step: heats i32 has shape %s, expected %s" % (hi.shape, (_ffi.HEAT_I32, B)))
+        if walls is not None:
+            wf = f64(walls["f64"], (_ffi.WALL_F64, B), "walls f64")
+            wi = np.ascontiguousarray(walls["i32"], np.int32)
+            if wi.shape != (_ffi.WALL_I32, B):
+                raise ValueError("event_step: walls i32 has shape %s, expected %s" % (wi.shape, (_ffi.WALL_I32, B)))
+        c = E.new_carry(B) if carry is None else carry
+        cf, ci = _carry_in("event_step", c, _ffi.EVENT_CARRY_F64, _ffi.EVENT_CARRY_I32, B)
+        total = C.c_int64(int(c.get("total", 0)))
+        if max_events is None:                   # LAP, FINISH or LOST, a PASS per other member, one contact and one wall event
+            max_events = B * 4 + (int(np.sum(np.bincount(h[h >= 0]) ** 2)) if h is not None and (h >= 0).any() else 0)
+        M = int(max_events)
+        if M < 0:
+            raise ValueError("event_step: max_events = %r must be >= 0" % (max_events,))
+        ei = np.empty((M, _ffi.EVENT_I32), np.int32); ef = np.empty((M, _ffi.EVENT_F64))
+        n = _ffi._i(0)
+        out = np.empty((_ffi.EVENT_OUT_I32, B), np.int32)
+        self._chk(self._lib.lpvmpc_event_step_batch(self._h, B, int(t), ptr(ph), ptr(lp), ptr(lv), nh, ptr(h), ptr(hf), ptr(hi), ptr(wf), ptr(wi),
+                                                    mask, ptr(cf), ptr(ci), C.byref(total), M, ptr(ei), ptr(ef), C.byref(n), ptr(out)))
+        m = min(M, n.value)
+        return (E.events_table(ei[:m], ef[:m]), int(n.value), dict(count=out[0], count_total=out[1], i32=out),
+                dict(f64=cf, i32=ci, total=int(total.value)))
+
     # -- device-pointer entry point (torch tensors or raw integers) -----------------------------------
     def solve_dev(self, B, x0, u_prev, vel_ref, curv_s, u_old, max_ey, xPred, uPred, status=None, iters=None,
                   resid=None, polish=None, cf_new=60.0, lap=1, stream=0):
@@ -1139,7 +1216,7 @@ def _plant_rows(v, B):
     return check_plant_params(v, B)
 
 
-# -- what the race's attachments share (heats, interactions, contact model, walls): attach / detach, read, and the step forms' inputs --
+# -- what the race's attachments share (heats, interactions, contact model, walls, event log): attach / detach, read, and the step forms' inputs --
 def _race_attach(solver, call, cfg):
     """Attach the checked configuration ``cfg`` through the C call, or detach (None)."""
     solver._chk(call(solver._h, None if cfg is None else C.byref(cfg)))
@@ -1528,12 +1605,15 @@ class RaceFleet(object):
     response, from the first tick on (``contact`` attaches or detaches mid-race, ``contacts()`` reads its planes back).
     ``walls``: True for the defaults, a ``walls.wall_config(...)`` result or a dict of its words: barrier contact at the track's edges
     from the first tick on (``wall`` attaches or detaches mid-race, ``walls()`` reads the outputs back); it selects
-    ``tyre_params="linear"`` when none is given."""
+    ``tyre_params="linear"`` when none is given.
+    ``events``: True for the defaults, an ``events.event_config(...)`` result or a dict of its arguments (capacity, kinds): the event
+    log from the first tick on, attached last (``log`` attaches or detaches mid-race, ``events()`` reads the ordered record back)."""
 
     def __init__(self, track_map, plant0, laps=1, N=20, Np=40, half_track0=None, device=0, estimator=None, actuator=None,
                  steering_delay=0, delay_a=None, delay_df=None, plant_params=None, model_params=None, path_tunings=None,
                  tt_tunings=None, plan_tunings=None, tyre_params=None, estimator_params=None, estimator_design=None, track_of=None,
-                 disturbance=None, sensor_faults=None, heats=None, interactions=None, walls=None, contact=None, **options):
+                 disturbance=None, sensor_faults=None, heats=None, interactions=None, walls=None, contact=None, events=None,
+                 **options):
         from .workloads import CTRL_TUNINGS, PLAN_L, PLAN_Q, PLAN_R, PLAN_dR
         if interactions is not None and interactions is not False and heats is None:
             raise ValueError("interactions needs heats: the vehicles of a heat act on each other")
@@ -1625,6 +1705,8 @@ class RaceFleet(object):
             self.contact(None if contact is True else contact)
         if walls is not None and walls is not False:
             self.wall(None if walls is True else walls)
+        if events is not None and events is not False:
+            self.log(None if events is True else events)
 
     def fault(self, rows, seed=0, vehicle_offset=0):
         """Attach sensor faults from the next tick on (BatchedSolver.set_sensor_faults on the path engine); ``None`` detaches."""
@@ -1738,6 +1820,17 @@ class RaceFleet(object):
     def walls(self):
         """The outputs of the attached walls (BatchedSolver.race_walls_read): depth, impulses, hit, side, corner, counters, outside."""
         return self.path.race_walls_read()
+
+    def log(self, cfg=None, detach=False):
+        """Attach the event log from the next tick on (BatchedSolver.race_events): ``cfg`` None (the defaults), a dict of arguments
+        or an ``events.event_config(...)`` result; ``log(detach=True)`` detaches."""
+        self.path.race_events(cfg, detach=detach)
+
+    def events(self, n=None):
+        """The last ``n`` kept events of the attached log, oldest first, in the log's order (tick, vehicle, kind, other), and the
+        count of every event since the attach: (``events.events_table``, total) (BatchedSolver.race_events_read)."""
+        r = self.path.race_events_read(n)
+        return r["events"], r["total"]
 
     def snapshot(self):
         """The race's whole per-vehicle state and tick counter (BatchedSolver.race_snapshot): a ``snapshot.RaceSnapshot`` with

@@ -117,7 +117,7 @@ extern "C" int lpvmpc_race_heats(lpvmpc_handle *h, const lpvmpc_heats_config *cf
         HIP_TRY(h, hipMemsetAsync(e.line_tick, 0xff, B * K * 4, st));
         HIP_TRY(h, hipMemsetAsync(e.line_pos, 0xff, B * K * 4, st));
         return LPVMPC_OK;
-    });
+    }, v.heats_serial);
 }
 
 static Planes standings_planes(HeatsBinding &q) { return lpvmpc_heat_planes(q.d, q.d.B); }

@@ -241,6 +241,7 @@ struct RaceState {
     uint32_t features = 0;                      // LPVMPC_SNAP_HAS_*
     bool recording = false;                     // a recorder is attached (lpvmpc_race_record)
     bool heats = false;                         // heats are attached (lpvmpc_race_heats)
+    bool events = false;                        // an event log is attached (lpvmpc_race_events)
     const std::vector<int32_t> *track_of = nullptr;   // [B] with tracks bound, else null
     std::vector<RaceStateDesc> tab;
 };

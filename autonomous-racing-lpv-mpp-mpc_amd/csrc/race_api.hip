@@ -4,14 +4,16 @@
 // the estimator state, gains and parameters in the path handle's obs_state / obs_gains / obs_p (obs_cfg stays null, so the
 // handle's next lpvmpc_cl_init runs on ground truth); lpvmpc_race_free releases them.  The recorder (lpvmpc_race_record,
 // record.hip), the heats (lpvmpc_race_heats, heats_api.hip / heats.hip), the interactions (lpvmpc_race_interactions,
-// interactions_api.hip / interactions.hip), the contact model (lpvmpc_race_contact, contact_api.hip / contact.hip) and the walls
-// (lpvmpc_race_walls, walls_api.hip / walls.hip) belong to the race as well.
+// interactions_api.hip / interactions.hip), the contact model (lpvmpc_race_contact, contact_api.hip / contact.hip), the walls
+// (lpvmpc_race_walls, walls_api.hip / walls.hip) and the event log (lpvmpc_race_events, events_api.hip / events.hip) belong to the
+// race as well.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <new>
 
 #include "contact_host.hpp"
+#include "events_host.hpp"
 #include "race_state.hpp"
 #include "record.hpp"
 #include "walls_host.hpp"
@@ -34,6 +36,8 @@ struct lpvmpc_race {
     std::unique_ptr<InterBinding> inter;         // lpvmpc_race_interactions (interactions_api.hip; null: none attached; reads the heats' lists)
     std::unique_ptr<ContactBinding> contact;     // lpvmpc_race_contact (contact_api.hip; null: the centres form; reads the interactions' binding)
     std::unique_ptr<WallBinding> walls;          // lpvmpc_race_walls (walls_api.hip; null: none attached)
+    std::unique_ptr<EventBinding> events;        // lpvmpc_race_events (events_api.hip; null: none attached; reads no binding)
+    uint32_t heats_serial = 0, walls_serial = 0; // bumped wherever that slot's binding is installed or detached: the log's first sight
 };
 
 void lpvmpc_race_free(lpvmpc_handle *h) {
@@ -255,6 +259,7 @@ bool lpvmpc_race_state(lpvmpc_handle *h, RaceState &s) {
     std::memcpy(s.shape, shape, sizeof(shape));
     s.recording = r->rec != nullptr;
     s.heats = r->heats != nullptr;
+    s.events = r->events != nullptr;
     if (h->trk.tab) s.track_of = &h->trk_of;
     s.features = (d.estv ? LPVMPC_SNAP_HAS_ESTIMATOR : 0u) | (r->side.act.d.ring ? LPVMPC_SNAP_HAS_ACTUATOR : 0u) |
                  (r->side.dist.d.rows ? LPVMPC_SNAP_HAS_DISTURBANCES : 0u) | (h->trk.tab ? LPVMPC_SNAP_HAS_TRACKS : 0u);
@@ -302,11 +307,12 @@ bool lpvmpc_race_attach_view(lpvmpc_handle *h, RaceAttachView &v) {
     if (!r) return false;
     v.B = r->d.B; v.laps = r->d.laps; v.hw = r->d.hw; v.slack = r->d.slack; v.plant = r->d.plant; v.nstep = r->d.nstep; v.phase = r->d.phase;
     v.side = &r->side;
-    v.heats = &r->heats; v.inter = &r->inter; v.contact = &r->contact; v.walls = &r->walls;
+    v.heats = &r->heats; v.inter = &r->inter; v.contact = &r->contact; v.walls = &r->walls; v.events = &r->events;
+    v.heats_serial = &r->heats_serial; v.walls_serial = &r->walls_serial;
     return true;
 }
 
-// the detach chain (race_attach.hpp): heats -> interactions -> contact model, readers first; the walls stand alone
+// the detach chain (race_attach.hpp): heats -> interactions -> contact model, readers first; the walls and the event log stand alone
 int lpvmpc_race_detach_readers(lpvmpc_handle *h, RaceLayer layer) {
     if (layer == RACE_HEATS) return lpvmpc_race_detach(h, RACE_INTERACTIONS);   // the interactions read the heats' lists and extents
     if (layer == RACE_INTERACTIONS) return lpvmpc_race_detach(h, RACE_CONTACT); // the contact model reads the interactions' binding
@@ -317,13 +323,13 @@ int lpvmpc_race_detach(lpvmpc_handle *h, RaceLayer layer) {
     if (!r) return LPVMPC_OK;
     RC_TRY(lpvmpc_race_detach_readers(h, layer));
     const bool attached = layer == RACE_HEATS ? r->heats != nullptr : layer == RACE_INTERACTIONS ? r->inter != nullptr :
-                          layer == RACE_CONTACT ? r->contact != nullptr : r->walls != nullptr;
+                          layer == RACE_CONTACT ? r->contact != nullptr : layer == RACE_WALLS ? r->walls != nullptr : r->events != nullptr;
     if (!attached) return LPVMPC_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t st = h->stream;
     HIP_TRY(h, hipStreamSynchronize(st));                                       // no tick in flight reads the binding
     switch (layer) {
-    case RACE_HEATS: r->heats.reset(); break;
+    case RACE_HEATS: r->heats.reset(); r->heats_serial++; break;
     case RACE_INTERACTIONS: {
         const InterBinding &q = *r->inter;
         H2D(q.d.mu_live, q.mu_base.data(), q.mu_base.size() * 8);               // the base words back to the live table
@@ -332,7 +338,8 @@ int lpvmpc_race_detach(lpvmpc_handle *h, RaceLayer layer) {
         break;
     }
     case RACE_CONTACT: r->contact.reset(); break;                               // back to the centres form
-    case RACE_WALLS: r->walls.reset(); break;
+    case RACE_WALLS: r->walls.reset(); r->walls_serial++; break;
+    case RACE_EVENTS: r->events.reset(); break;
     }
     return LPVMPC_OK;
 }
@@ -417,6 +424,24 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
         }
         if (const HeatsBinding *q = r->heats.get())                                 // the heats (heats.hip)
             HIP_TRY(h, lpvmpc::launch_heat_tick(h->d_cfg, trk, q->d, q->block, r->ticks, st));
+        if (EventBinding *q = r->events.get()) {                                    // the event log (events.hip): last, every plane is final
+            lpvmpc::EventSrc s{};                                                   // the bindings of THIS tick: the log keeps no pointer of theirs
+            s.phase = d.phase; s.lap = d.lap; s.lap_step = d.lap_step; s.lap_cols = d.lap_cols;
+            if (const HeatsBinding *hb = r->heats.get()) {
+                s.heat_f = hb->d.out_f; s.heat_i = hb->d.out_i; s.off = hb->d.off; s.members = hb->d.members; s.n_heats = hb->d.n_heats;
+                s.heat_of = q->heat_of;
+                s.heats_fresh = !q->heats_known || q->heats_serial != r->heats_serial;
+                if (s.heats_fresh) HIP_TRY(h, lpvmpc::launch_event_heat_of(B, s.n_heats, s.off, s.members, q->heat_of, st));
+            }
+            if (const WallBinding *wb = r->walls.get()) {
+                s.wall_f = wb->d.out_f; s.wall_i = wb->d.out_i;
+                s.walls_fresh = !q->walls_known || q->walls_serial != r->walls_serial;
+            }
+            HIP_TRY(h, lpvmpc::launch_event_tick(q->d, s, r->ticks, st));
+            // seen only once the tick that stores its words is launched: a failed launch leaves the source at first sight
+            if (s.heat_f) { q->heats_known = true; q->heats_serial = r->heats_serial; }
+            if (s.wall_f) { q->walls_known = true; q->walls_serial = r->walls_serial; }
+        }
         r->ticks++;
     }
     return LPVMPC_OK;

@@ -1,6 +1,6 @@
-// race_attach.hpp -- the host scaffold of what attaches to a running race: the heats, the interactions, the contact model and the
-// walls (heats_api.hip, interactions_api.hip, contact_api.hip, walls_api.hip) and race_api.hip, which owns the four slots.  Host code
-// only: no kernel translation unit includes it.  A layer supplies its configuration check, its blank-output rule, the fields of its
+// race_attach.hpp -- the host scaffold of what attaches to a running race: the heats, the interactions, the contact model, the walls
+// and the event log (heats_api.hip, interactions_api.hip, contact_api.hip, walls_api.hip, events_api.hip) and race_api.hip, which owns
+// the five slots.  Host code only: no kernel translation unit includes it.  A layer supplies its configuration check, its blank-output rule, the fields of its
 // kernel argument and its launch; the allocation, the four planes, the entry points' prologues, the whole-or-nothing install, the read
 // entry point and the detach chain are here ("Race attachments").
 #pragma once
@@ -15,9 +15,11 @@ struct HeatsBinding;         // heats_host.hpp
 struct InterBinding;         // interactions_host.hpp
 struct ContactBinding;       // contact_host.hpp
 struct WallBinding;          // walls_host.hpp
+struct EventBinding;         // events_host.hpp
 
 // race_api.hip: what an attachment needs of the running race: its shape, the state a tick reads and writes, the plant side whose live
-// table the layers read and rewrite, and the four slots that own the bindings (false: the handle owns no race)
+// table the layers read and rewrite, and the five slots that own the bindings, with the serials of the two slots that the event log
+// observes (false: the handle owns no race)
 struct RaceAttachView {
     int B = 0, laps = 0;
     double hw = 0, slack = 0;
@@ -28,14 +30,16 @@ struct RaceAttachView {
     std::unique_ptr<InterBinding> *inter = nullptr;
     std::unique_ptr<ContactBinding> *contact = nullptr;
     std::unique_ptr<WallBinding> *walls = nullptr;
+    std::unique_ptr<EventBinding> *events = nullptr;
+    uint32_t *heats_serial = nullptr, *walls_serial = nullptr;                  // bumped wherever that slot's binding is installed or detached
 };
 LPVMPC_HIDDEN bool lpvmpc_race_attach_view(lpvmpc_handle *h, RaceAttachView &v);
 
 // race_api.hip: detaches one layer of h's race with the layers that read it, readers first: the heats take the interactions with them
 // (their binding reads the heats' lists and extents), the interactions the contact model (its kernel argument is a copy of theirs);
-// the walls stand alone.  Each binding goes once no tick in flight reads it, and the interactions put the base mu words back into the
+// the walls stand alone, and so does the event log (no layer reads it and it reads no binding).  Each binding goes once no tick in flight reads it, and the interactions put the base mu words back into the
 // live plant table.  No race, or nothing attached: nothing to do.  _readers: the readers alone, ahead of a layer's replacement
-enum RaceLayer { RACE_HEATS, RACE_INTERACTIONS, RACE_CONTACT, RACE_WALLS };
+enum RaceLayer { RACE_HEATS, RACE_INTERACTIONS, RACE_CONTACT, RACE_WALLS, RACE_EVENTS };
 LPVMPC_HIDDEN int lpvmpc_race_detach(lpvmpc_handle *h, RaceLayer layer);
 LPVMPC_HIDDEN int lpvmpc_race_detach_readers(lpvmpc_handle *h, RaceLayer layer);
 
@@ -139,10 +143,13 @@ template <class Run> int lpvmpc_run_synced(lpvmpc_handle *h, hipStream_t st, Run
 }
 
 // The whole-or-nothing install of a binding built in a local: a failed upload leaves the slot as it was, and the binding that the slot
-// held is freed only after the synchronisation (no tick in flight reads it)
-template <class Q, class Run> int lpvmpc_race_install(lpvmpc_handle *h, hipStream_t st, std::unique_ptr<Q> &slot, std::unique_ptr<Q> &q, Run run) {
+// held is freed only after the synchronisation (no tick in flight reads it).  serial: the slot's serial, where the event log observes
+// the slot (RaceAttachView)
+template <class Q, class Run>
+int lpvmpc_race_install(lpvmpc_handle *h, hipStream_t st, std::unique_ptr<Q> &slot, std::unique_ptr<Q> &q, Run run, uint32_t *serial = nullptr) {
     RC_TRY(lpvmpc_run_synced(h, st, run));
     slot = std::move(q);
+    if (serial) ++*serial;
     return LPVMPC_OK;
 }
 

@@ -87,6 +87,9 @@ extern "C" int lpvmpc_race_restore(lpvmpc_handle *h, const void *buf, int64_t by
     if (s.heats)
         return fail(h, LPVMPC_E_ARG, "%s: heats are attached, and a position history means nothing after a restore; detach them first "
                     "(lpvmpc_race_heats(path, cfg, NULL, NULL))", who);
+    if (s.events)
+        return fail(h, LPVMPC_E_ARG, "%s: an event log is attached, and before and after mean nothing across a restore; detach it first "
+                    "(lpvmpc_race_events(path, NULL))", who);
     if (!buf || bytes < kHeaderBytes) return fail(h, LPVMPC_E_ARG, "%s: the buffer is NULL or shorter than the %d B header (%lld B)", who, kHeaderBytes, (long long)bytes);
     const char *in = (const char *)buf;
     if (std::memcmp(in, kMagic, 8) != 0) return fail(h, LPVMPC_E_ARG, "%s: not a race snapshot (magic)", who);
@@ -135,6 +138,9 @@ extern "C" int lpvmpc_race_clone(lpvmpc_handle *h, const int32_t *src, int32_t *
     if (s.heats)
         return fail(h, LPVMPC_E_ARG, "%s: heats are attached, and their standings do not move with the state; detach them first "
                     "(lpvmpc_race_heats(path, cfg, NULL, NULL))", who);
+    if (s.events)
+        return fail(h, LPVMPC_E_ARG, "%s: an event log is attached, and its before words do not move with the state; detach it first "
+                    "(lpvmpc_race_events(path, NULL))", who);
     if (!src) return fail(h, LPVMPC_E_ARG, "%s: src is NULL", who);
     const int B = s.shape[0];
     std::vector<int32_t> srcv, dstv;

@@ -86,7 +86,7 @@ extern "C" int lpvmpc_race_walls(lpvmpc_handle *h, const lpvmpc_wall_config *cfg
     return lpvmpc_race_install(h, st, *v.walls, q, [&]() -> int {              // (its synchronisation: no tick in flight reads the old binding)
         RC_TRY(pl.blank_carry(h, st, ci.data()));
         return pl.blank_out(h, st, f, i);
-    });
+    }, v.walls_serial);
 }
 
 static Planes read_planes(WallBinding &q) { return lpvmpc_wall_planes(q.d, q.d.B); }

@@ -1114,8 +1114,8 @@ int  lpvmpc_plant_step_disturbed_batch(lpvmpc_handle *h, int32_t B, double *stat
  * track-bound race, track_of[src[b]] != track_of[b] (a pose and a lap table mean nothing on another track).
  *
  * Recorder: restore and clone are refused while a recorder is attached (stop it with lpvmpc_race_record, capacity 0, and start it
- * again afterwards); its ring and per-lap statistics are not carried.  The lap-0 fleet (lpvmpc_cl_*) and the cascade have no
- * snapshot. */
+ * again afterwards); its ring and per-lap statistics are not carried.  The same holds while heats ("Heats") or an event log ("Race
+ * event log") are attached.  The lap-0 fleet (lpvmpc_cl_*) and the cascade have no snapshot. */
 #define LPVMPC_SNAP_VERSION 1
 #define LPVMPC_SNAP_HEADER_BYTES 64
 #define LPVMPC_SNAP_ENTRY_BYTES 40
@@ -1632,6 +1632,129 @@ int  lpvmpc_contact_step_batch(lpvmpc_handle *h, int32_t B, int32_t n_heats, con
                                const double *plant_params /* [B][7] */, const int32_t *nstep /* [B] or NULL: all step */,
                                double *carry_f64, int32_t *carry_i32, double *ccarry_f64, int32_t *ccarry_i32,
                                double *mu_live /* [B] out */, double *f64, int32_t *i32, double *cf64, int32_t *ci32);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Race event log: an ordered record, kept on the device, of what happened on each tick of a race.  The reads above answer "what is
+ * the state after tick t" and the heats and the walls count since their attach; the log says who passed whom on which tick, when a
+ * contact began and how long it lasted, and in what order cars hit the wall, for a race that ran hundreds of ticks in one
+ * lpvmpc_race_tick call.  It is the race's fifth attachment and it only observes: no output of the race or of another attachment
+ * changes by a bit while it is attached, and with nothing attached a tick issues exactly the launches it always did.  While it is
+ * attached a tick issues one more launch, the last of the tick, behind the heats': phase, lap rows, the standings and the walls'
+ * planes of this tick are final by then.  (On the first tick on which the log sees an attachment of the heats one small launch in
+ * front of it fills the log's own table of each vehicle's heat from the heats' member lists.)
+ *
+ * An event is six int32 words and two doubles: i32 [LPVMPC_EVENT_I32] = TICK, KIND, VEHICLE, OTHER, A, B and f64 [LPVMPC_EVENT_F64] =
+ * V0, V1.  TICK is the race's tick number counted before the tick, as the recorder's and the heats'.  An unused integer word is -1,
+ * an unused double NaN.  "Before" and "after" below are the words the log stored at the end of the previous tick and the words that
+ * stand at the end of this one.
+ *
+ * From the race itself:
+ *   1 LAP            the vehicle's lap counter is larger than before.  A = the new lap counter, B = phase after,
+ *                    V0 = (double)lap_step[b][A] as lpvmpc_race_laps returns it after this tick.
+ *   2 FINISH         phase became 2.  A = lap counter.
+ *   3 LOST           phase became 3.  A = lap counter.
+ * From the heats, for a vehicle in a heat, while heats are attached:
+ *   4 PASS           VEHICLE = i, OTHER = j, members of one heat: both are class 1 before and after, i was ordered behind j before
+ *                    (POSITION larger) and is in front after.  A / B = POSITION of i / of j after, V0 = PROGRESS[i] - PROGRESS[j]
+ *                    after (one subtraction).  This is the heats' own rule evaluated on the words the heats wrote, so per vehicle and
+ *                    tick the number of PASS events with VEHICLE = b is the increment of PASSES[b], the number with OTHER = b that of
+ *                    PASSED[b].
+ *   5 CONTACT_BEGIN  the heats' CONTACT word went 0 -> 1.  OTHER = NEAREST, V0 = CLEARANCE.
+ *   6 CONTACT_END    CONTACT went 1 -> 0.  OTHER = the NEAREST of the spell's last contact tick, A = the spell's length in ticks,
+ *                    V0 = the smallest CLEARANCE over the spell's ticks.
+ * From the walls, while walls are attached:
+ *   7 WALL_HIT       HIT went 0 -> 1.  A = SIDE, B = CORNER, V0 = DEPTH, V1 = IMPULSE.
+ *   8 WALL_CLEAR     HIT went 1 -> 0.  A = the spell's length in ticks, V0 = the largest IMPULSE of the spell.
+ *
+ * First sight.  On the first tick after its own attach the log stores the race's rows and emits nothing from them.  The same holds
+ * per source on the first tick on which the log sees a given attachment of the heats or of the walls: one attached or replaced since
+ * the last tick, or one present when the log was attached.  A spell open at first sight is taken as beginning then, without a BEGIN
+ * event; when a source is detached its open spells are dropped without an END event.  The log holds no pointer of another layer:
+ * lpvmpc_race_tick passes the current attachments' output planes and the heats' member lists at each launch, and a serial per slot,
+ * bumped wherever an attachment is installed or detached, tells it which it has seen.  So the log stands alone in the detach chain,
+ * as the walls do: attach and detach are independent of the other four layers, in any order.
+ *
+ * Order.  The events of a race are totally ordered by (TICK, VEHICLE, KIND, OTHER), all ascending; for PASS the VEHICLE is the passer.
+ * This order is the log's contract, the same for every launch shape, batch size and run: a tick's slots come from an exclusive prefix
+ * sum of the vehicles' event counts over the vehicle index, not from an atomic counter.
+ * Ring.  The log keeps the last `capacity` events: the event with global index g (0-based since the attach) lives in slot
+ * g % capacity; total is a 64-bit count of every event since the attach, kept and advanced on the device (a multi-tick lpvmpc_race_tick
+ * does not synchronise).  A tick that produces more events than capacity keeps exactly its last capacity events: an event is written
+ * only when g >= total_after_tick - capacity, so no two writes of one tick meet in a slot.
+ * Kinds mask.  Bit k of kinds selects kind k.  An unselected kind is neither written nor counted; its state is still carried.
+ * Per-vehicle outputs i32 [LPVMPC_EVENT_OUT_I32][B] = COUNT (events with this VEHICLE on the last tick), COUNT_TOTAL (since the
+ * attach); 0 before the first tick.
+ *
+ * lpvmpc_race_events attaches the log from the next tick on; attaching again replaces the binding and its count starts at 0;
+ * cfg == NULL detaches.  Refused with LPVMPC_E_ARG, the race left as it was: no race on the handle, capacity < 1 or a size that
+ * overflows, a kinds bit outside 1 .. 8, reserved != 0.  The binding is built whole and then installed; the race owns it
+ * (lpvmpc_cl_release(path) or destroying a handle frees it, a new race starts without one).  lpvmpc_race_snapshot works while it is
+ * attached and does not contain it; lpvmpc_race_restore and lpvmpc_race_clone are refused while it is attached, as with the heats:
+ * before and after mean nothing across a restore.  lpvmpc_event_default_config: capacity 65536, every kind.
+ *
+ * lpvmpc_race_events_read synchronises and copies the last m = min(n, kept) events, oldest first, with kept = min(total, capacity):
+ * i32 [m][LPVMPC_EVENT_I32], f64 [m][LPVMPC_EVENT_F64], and the output plane out_i32 [LPVMPC_EVENT_OUT_I32][B].  Any pointer may be
+ * NULL.  Refused with LPVMPC_E_ARG for n < 0 and while nothing is attached.
+ *
+ * lpvmpc_event_step_batch is one tick of the same device function on caller-supplied data, on a handle that runs no fleet, cascade or
+ * race: t, phase [B], lap [B], lap_value [B] (the V0 of a LAP event); the heats' side n_heats, heat [B] with indices in [-1, n_heats)
+ * and the heats' two output planes heat_f64 [LPVMPC_HEAT_F64][B] / heat_i32 [LPVMPC_HEAT_I32][B] (all three NULL: no heats); the
+ * walls' two output planes wall_f64 / wall_i32 (both NULL: no walls); kinds; the carry planes carry_f64 [LPVMPC_EVENT_CARRY_F64][B] /
+ * carry_i32 [LPVMPC_EVENT_CARRY_I32][B] in / out; total [1] in / out; max_events and the two event arrays i32 [max_events][6] /
+ * f64 [max_events][2], filled from index 0 with this tick's events in order (only the first max_events are written); n_events [1] =
+ * how many the tick produced; out_i32 the per-vehicle output plane.  An all-zero carry is "just attached".  FLAGS bit 0: the race's
+ * rows are stored; bit 1 / bit 2: the heats' / the walls' words are stored (cleared on a tick without that source, and for a vehicle
+ * in no heat).  COUNT_TOTAL is carried; every other word is the "before" word of its name, the spells' first ticks and extrema. */
+#define LPVMPC_EVENT_I32                 6
+#define LPVMPC_EVENT_TICK                0
+#define LPVMPC_EVENT_KIND                1
+#define LPVMPC_EVENT_VEHICLE             2
+#define LPVMPC_EVENT_OTHER               3
+#define LPVMPC_EVENT_A                   4
+#define LPVMPC_EVENT_B                   5
+#define LPVMPC_EVENT_F64                 2
+#define LPVMPC_EVENT_V0                  0
+#define LPVMPC_EVENT_V1                  1
+#define LPVMPC_EVENT_LAP                 1
+#define LPVMPC_EVENT_FINISH              2
+#define LPVMPC_EVENT_LOST                3
+#define LPVMPC_EVENT_PASS                4
+#define LPVMPC_EVENT_CONTACT_BEGIN       5
+#define LPVMPC_EVENT_CONTACT_END         6
+#define LPVMPC_EVENT_WALL_HIT            7
+#define LPVMPC_EVENT_WALL_CLEAR          8
+#define LPVMPC_EVENT_ALL_KINDS           0x1FEu
+#define LPVMPC_EVENT_OUT_I32             2
+#define LPVMPC_EVENT_COUNT               0
+#define LPVMPC_EVENT_COUNT_TOTAL         1
+#define LPVMPC_EVENT_CARRY_F64           2
+#define LPVMPC_EVENT_CARRY_MIN_CLEARANCE 0  /* smallest CLEARANCE of the open contact spell */
+#define LPVMPC_EVENT_CARRY_MAX_IMPULSE   1  /* largest IMPULSE of the open wall spell */
+#define LPVMPC_EVENT_CARRY_I32          11
+#define LPVMPC_EVENT_CARRY_FLAGS         0
+#define LPVMPC_EVENT_CARRY_PHASE         1
+#define LPVMPC_EVENT_CARRY_LAP           2
+#define LPVMPC_EVENT_CARRY_POSITION      3
+#define LPVMPC_EVENT_CARRY_CLASS         4
+#define LPVMPC_EVENT_CARRY_CONTACT       5
+#define LPVMPC_EVENT_CARRY_NEAREST       6  /* NEAREST of the spell's last contact tick */
+#define LPVMPC_EVENT_CARRY_CONTACT_START 7  /* first tick of the open contact spell, -1: none */
+#define LPVMPC_EVENT_CARRY_HIT           8
+#define LPVMPC_EVENT_CARRY_HIT_START     9  /* first tick of the open wall spell, -1: none */
+#define LPVMPC_EVENT_CARRY_COUNT_TOTAL  10
+typedef struct lpvmpc_event_config {
+    int32_t  capacity;         /* >= 1: events kept */
+    uint32_t kinds;            /* bit k selects kind k, 1 .. 8 */
+    int32_t  reserved[2];      /* 0 */
+} lpvmpc_event_config;
+void lpvmpc_event_default_config(lpvmpc_event_config *cfg);
+int  lpvmpc_race_events(lpvmpc_handle *path, const lpvmpc_event_config *cfg /* NULL: detach */);
+int  lpvmpc_race_events_read(lpvmpc_handle *path, int32_t n, int64_t *total, int32_t *kept, int32_t *i32 /* [m][6] */,
+                             double *f64 /* [m][2] */, int32_t *out_i32 /* [2][B] */);
+int  lpvmpc_event_step_batch(lpvmpc_handle *h, int32_t B, int32_t t, const int32_t *phase, const int32_t *lap, const double *lap_value,
+                             int32_t n_heats, const int32_t *heat, const double *heat_f64, const int32_t *heat_i32,
+                             const double *wall_f64, const int32_t *wall_i32, uint32_t kinds, double *carry_f64, int32_t *carry_i32,
+                             int64_t *total, int32_t max_events, int32_t *i32, double *f64, int32_t *n_events, int32_t *out_i32);
 
 #ifdef __cplusplus
 }
