@@ -7,16 +7,21 @@
 //
 // Design (CDNA4): the whole solve of one instance -- Ruiz equilibration, KKT factorisation, every ADMM
 // iteration, adaptive-rho refactorisations, termination / infeasibility tests and the polish step --
-// runs inside ONE workgroup with all state resident in LDS, so HBM sees only the LPV blocks going in
-// and the trajectory coming out.  The QP is never materialised as sparse matrices: the decision vector
-// is kept stage-interleaved, w_k = (x_k, u_k), which makes
+// runs inside ONE workgroup (one, two, four or eight wavefronts, see below) with all state resident in
+// LDS and registers, so HBM sees only the LPV blocks going in and the trajectory coming out -- and, for
+// an instance that is parked at a termination check (straggler deferral: try_park / restore), its LDS
+// image going to a pool entry and coming back in a later launch.  The QP is never materialised as
+// sparse matrices: the decision vector is kept stage-interleaved, w_k = (x_k, u_k), which makes
 //     K = P + sigma I + A' diag(rho) A
 // block tridiagonal with 8x8 blocks.  K is factored as a block L S L' from both ends of the horizon
 // towards a middle stage; each pivot block is factored S_k = C C' and only the triangular factor is
 // inverted (see "block tridiagonal factorisation" below), so that a KKT solve is two sweeps of tile
 // mat-vecs per chain.
 //
-// Solver<NX, NT, NW, MF, GS, TAIL> is one template for all 21 kernels (DESIGN.md section 4 has the table):
+// The file holds two entries over one Solver: admm_solve_kernel (plain, resume and tail launches) and
+// admm_solve_riders_kernel (a main launch whose first workgroups continue parked instances); the code of an
+// ADMM iteration, between the LPVMPC_HOT_BEGIN / _END markers, is the same text in both.
+// Solver<NX, NT, NW, MF, GS, TAIL> is one template for all 39 kernels (DESIGN.md section 4 has the table):
 //   NW = 1   one wavefront per instance, tiles [i][j] in lane 8 i + j, products through LDS tiles; NT = 0
 //            takes the horizon at run time and keeps the factor tiles in LDS (validation kernels)
 //   NW = 2   the two elimination chains on two wavefronts.  MF: every 8x8 product on the matrix cores
@@ -2601,6 +2606,16 @@ struct Solver {
         q.wi = c_ == 0 ? rinv : (c_ == 1 ? rinv_eq : 1.0 / kRhoMin);
         return q;
     }
+    // The controller's N = 20 kernel takes the pair from the registers cache_box_weights fills (wbx / wbxi) instead: the two-level select
+    // above is 13 32-bit instructions per element and iteration on predicates that only a rho update changes -- 26 of the 118 of the
+    // fused update block, 79 of the 900 between the hot markers.  The same values (cache_box_weights forms both from one test of the
+    // bounds, behind every set_rho), so every output word is unchanged.  With the class word and the selects' temporaries gone the
+    // eight registers fit: 256, no spill.  The planner's kernels of this form keep the select, and their code
+    // (profiles/iteration_mix_ledger.txt has the per-kernel counts).
+    static constexpr bool kRegW = kRegState && kCtrl && NT == 20;
+    __device__ __forceinline__ WW el_weights(int r) const {
+        if constexpr (kRegW) return WW{wbx[r], wbxi[r]}; else return weights_of(r);
+    }
     // want: a termination check or a rho update follows, or the loop ends -- the state and the deltas go to the arrays as well
     template <bool FIRST>
     __device__ __forceinline__ void update_s(double alpha, double oma, bool want) {
@@ -2616,7 +2631,7 @@ struct Solver {
             // (the second element sits in a stage >= 16: bound 0 -- a lane without one repeats its first element, bound included)
             ElInS a0 = el_load_s<FIRST, false>(o.e0, bvar), a1 = el_load_s<FIRST, true>(o.e1c, bvar);
             a1.b = o.e1 >= 0 ? 0.0 : a0.b;
-            const WW w0 = weights_of(0), w1 = weights_of(1);
+            const WW w0 = el_weights(0), w1 = el_weights(1);
             const ElOutS o0 = el_form_s(a0, es_[0], FIRST, alpha, oma, rmask, w0.w, w0.wi), o1 = el_form_s(a1, es_[1], FIRST, alpha, oma, rmask, w1.w, w1.wi);
             ZTd[o.e0] = es_[0].wtd; ZTb[o.e0] = o0.wtb;
             ZTd[o.e1c] = es_[1].wtd; ZTb[o.e1c] = o1.wtb;
@@ -2626,7 +2641,7 @@ struct Solver {
             asm volatile("; LPVMPC_ROLE_END regstate_update");
         } else {
             const ElInS a0 = el_load_s<FIRST, true>(o.e0, bvar);        // (a wavefront without a second round owns elements 64 and up: stages >= 8)
-            const WW w0 = weights_of(0);
+            const WW w0 = el_weights(0);
             const ElOutS o0 = el_form_s(a0, es_[0], FIRST, alpha, oma, rmask, w0.w, w0.wi);
             ZTd[o.e0] = es_[0].wtd; ZTb[o.e0] = o0.wtb;
             if (want) file(o.e0, es_[0], o0);
