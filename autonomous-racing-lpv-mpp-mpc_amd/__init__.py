@@ -13,11 +13,13 @@ from .tuning import check_tuning_rows, sample_tunings, tuning_rows  # noqa: F401
 from .disturbance import check_disturbance_rows, disturbance_rows, rho_from_tau, sample_disturbances  # noqa: F401
 from .sensor_faults import check_fault_rows, fault_rows, sample_faults  # noqa: F401
 from .snapshot import RaceSnapshot, respawn_sources  # noqa: F401
+from .tyre_wear import check_tyre_wear_rows, sample_tyre_wear, tyre_wear_rows  # noqa: F401
 
 __all__ = ["BatchedSolver", "PathFollowingLPV_MPC", "LPV_MPC_Planner", "PlannerHandoff", "body_frame_errors", "handoff_operators",
            "Map", "LpvMpcError", "STATUS_TEXT", "GainScheduledLPVObserver", "observer_config", "observer_vertex_gains", "RaceFleet",
            "actuator_config", "controller_delay", "delay_steps", "plant_params", "sample_plant_params", "tyre_params", "sample_tyre_params",
            "model_params", "sample_model_params", "tuning_rows", "sample_tunings", "check_tuning_rows",
            "disturbance_rows", "sample_disturbances", "check_disturbance_rows", "rho_from_tau",
+           "tyre_wear_rows", "sample_tyre_wear", "check_tyre_wear_rows",
            "fault_rows", "sample_faults", "check_fault_rows",
            "RaceSnapshot", "respawn_sources"]

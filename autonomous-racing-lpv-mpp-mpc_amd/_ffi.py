@@ -213,6 +213,7 @@ TYRE_WORDS = 4                           # LPVMPC_TYRE_WORDS: [kind, B, C, c_f] 
 TYRE_WORD_NAMES = ("kind", "B", "C", "c_f")
 DIST_WORDS, DIST_STATE = 13, 5           # LPVMPC_DIST_WORDS, LPVMPC_DIST_STATE (disturbance.py)
 DIST_STREAM = 0xD157A2B3C4D5E6F7         # LPVMPC_DIST_STREAM
+WEAR_WORDS, WEAR_STATE = 12, 6           # LPVMPC_WEAR_WORDS, LPVMPC_WEAR_STATE (tyre_wear.py)
 FAULT_WORDS, OBS_STATE_WORDS = 12, 18    # LPVMPC_FAULT_WORDS, LPVMPC_OBS_STATE_WORDS (sensor_faults.py)
 FAULT_STREAM = 0x5E4507FA17C0FFEE        # LPVMPC_FAULT_STREAM
 MODEL_WORDS = 7                          # LPVMPC_MODEL_WORDS: the same words, as a controller's / planner's model of the vehicle
@@ -244,6 +245,7 @@ EXPORTS = ("lpvmpc_version", "lpvmpc_default_config", "lpvmpc_create", "lpvmpc_d
            "lpvmpc_set_tracks", "lpvmpc_tracks_read",
            "lpvmpc_disturbance_default_config", "lpvmpc_set_disturbances", "lpvmpc_disturbances_read",
            "lpvmpc_plant_step_disturbed_batch",
+           "lpvmpc_set_tyre_wear", "lpvmpc_tyre_wear_read", "lpvmpc_tyre_wear_fit", "lpvmpc_plant_step_worn_batch",
            "lpvmpc_race_snapshot_size", "lpvmpc_race_snapshot", "lpvmpc_race_restore", "lpvmpc_race_clone",
            "lpvmpc_heats_default_config", "lpvmpc_race_heats", "lpvmpc_race_standings", "lpvmpc_heat_step_batch",
            "lpvmpc_sensor_fault_default_config", "lpvmpc_set_sensor_faults", "lpvmpc_sensor_faults_read", "lpvmpc_sensor_step_batch",
@@ -439,6 +441,16 @@ def load():
         lib.lpvmpc_plant_step_disturbed_batch.argtypes = [vp, _i, vp, vp, vp, _i, _d, _d, P(ActuatorConfig), vp, vp, vp, vp,
                                                           P(DisturbanceConfig), vp, vp]
         for name in ("lpvmpc_set_disturbances", "lpvmpc_disturbances_read", "lpvmpc_plant_step_disturbed_batch"):
+            getattr(lib, name).restype = C.c_int
+    except AttributeError:
+        pass
+    try:        # (nor the tyre wear and temperature)
+        lib.lpvmpc_set_tyre_wear.argtypes = [vp, _i, vp]
+        lib.lpvmpc_tyre_wear_read.argtypes = [vp, vp, vp]
+        lib.lpvmpc_tyre_wear_fit.argtypes = [vp, vp]
+        lib.lpvmpc_plant_step_worn_batch.argtypes = [vp, _i, vp, vp, vp, _i, _d, _d, P(ActuatorConfig), vp, vp, vp, vp,
+                                                     P(DisturbanceConfig), vp, vp, vp, vp]
+        for name in ("lpvmpc_set_tyre_wear", "lpvmpc_tyre_wear_read", "lpvmpc_tyre_wear_fit", "lpvmpc_plant_step_worn_batch"):
             getattr(lib, name).restype = C.c_int
     except AttributeError:
         pass

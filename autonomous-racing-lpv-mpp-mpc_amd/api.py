@@ -363,6 +363,69 @@ class BatchedSolver:
         self._chk(self._lib.lpvmpc_disturbances_read(self._h, ptr(rows), ptr(state)))
         return rows, state
 
+    def plant_step_worn(self, state, u, wear_rows, wear_state=None, rows=None, dist_state=None, seed=0, vehicle_offset=0, n_bound=None,
+                        plant_params=None, tyre_params=None, act_state=None, n_sub=1, dt_sim=0.005, mu_sim=0.05, actuator=None,
+                        delay_a=None, delay_df=None):
+        """plant_step_disturbed with the tyre wear and temperature model behind the disturbances' and in front of the n_sub steps
+        (lpvmpc_plant_step_worn_batch): ``wear_rows`` [B, 12] (tyre_wear.tyre_wear_rows), ``wear_state`` [B, 6] = (W, T, P, g, ticks,
+        E) carried between calls (None: fresh); ``rows`` None: no disturbance model.  Returns (state, act_state, dist_state,
+        wear_state), dist_state None without disturbance rows."""
+        from .disturbance import check_disturbance_rows, disturbance_config
+        from .tyre_wear import check_tyre_wear_rows
+        st = f64(state).reshape(-1, 8).copy(); B = st.shape[0]
+        u = f64(u, (B, 2), "u")
+        prow = _plant_rows(plant_params, B)
+        act = np.zeros((B, _ffi.ACT_WORDS)) if act_state is None else f64(act_state, (B, _ffi.ACT_WORDS), "act_state").copy()
+        wr = check_tyre_wear_rows(wear_rows, B)
+        ws = np.zeros((B, _ffi.WEAR_STATE)) if wear_state is None else f64(wear_state, (B, _ffi.WEAR_STATE), "wear_state").copy()
+        if wear_state is None:
+            ws[:, 1] = wr[:, 11]; ws[:, 3] = 1.0
+        ds = r = None
+        if rows is not None:
+            r = check_disturbance_rows(rows, B)
+            ds = np.zeros((B, _ffi.DIST_STATE)) if dist_state is None else f64(dist_state, (B, _ffi.DIST_STATE), "dist_state").copy()
+            if dist_state is None:
+                ds[:, 4] = 1.0
+        cfg = _ffi.default_actuator_config() if actuator is None else _actuator_cfg(actuator)
+        la, ld = _delay_array(delay_a, B, "delay_a"), _delay_array(delay_df, B, "delay_df")
+        dc = disturbance_config(seed, vehicle_offset, n_bound)
+        self._chk(self._lib.lpvmpc_plant_step_worn_batch(self._h, B, ptr(st), ptr(act), ptr(u), int(n_sub), float(dt_sim), float(mu_sim),
+                                                         C.byref(cfg), ptr(la), ptr(ld), ptr(prow),
+                                                         ptr(None if tyre_params is None else _tyre_rows(tyre_params, B)),
+                                                         C.byref(dc), ptr(r), ptr(ds), ptr(wr), ptr(ws)))
+        return st, act, ds, ws
+
+    def _fleet_B(self):
+        return self._race[0] if getattr(self, "_race", None) is not None else getattr(self, "_cl_B", 0)
+
+    def set_tyre_wear(self, rows):
+        """Attach tyre wear and temperature to the lap-0 fleet or race this engine runs (lpvmpc_set_tyre_wear; the path engine, for a
+        race), from the next tick on: ``rows`` [B, 12] (tyre_wear.tyre_wear_rows / sample_tyre_wear).  The fleet or race must have
+        been started with ``tyre_params`` ("linear": kind 0 rows).  ``None`` detaches: the live words go back to the disturbances'
+        gamma * base, or to the base rows."""
+        from .tyre_wear import check_tyre_wear_rows
+        B = self._fleet_B()
+        if rows is None:
+            self._chk(self._lib.lpvmpc_set_tyre_wear(self._h, B, None))
+            return
+        r = check_tyre_wear_rows(rows, np.asarray(rows).shape[0] if np.asarray(rows).ndim == 2 else B)
+        self._chk(self._lib.lpvmpc_set_tyre_wear(self._h, r.shape[0], ptr(r)))
+
+    def tyre_wear_read(self):
+        """The attached rows [B, 12] and the tyre sets' state [B, 6] = (W, T, P, g, ticks, E) (lpvmpc_tyre_wear_read)."""
+        B = self._fleet_B()
+        rows, state = np.empty((B, _ffi.WEAR_WORDS)), np.empty((B, _ffi.WEAR_STATE))
+        self._chk(self._lib.lpvmpc_tyre_wear_read(self._h, ptr(rows), ptr(state)))
+        return rows, state
+
+    def tyre_wear_fit(self, mask):
+        """A tyre change between ticks (lpvmpc_tyre_wear_fit): the vehicles of ``mask`` [B] start a fresh set (W 0, T_start, P 0, g 1)
+        and keep their tick count and energy."""
+        m = np.ascontiguousarray(np.asarray(mask).astype(bool).astype(np.int32))
+        if m.shape != (self._fleet_B(),):
+            raise ValueError("tyre_wear_fit: mask has shape %s, expected (%d,)" % (m.shape, self._fleet_B()))
+        self._chk(self._lib.lpvmpc_tyre_wear_fit(self._h, ptr(m)))
+
     def set_sensor_faults(self, rows, seed=0, vehicle_offset=0):
         """Attach sensor faults to the lap-0 fleet or race this engine runs (lpvmpc_set_sensor_faults; the path engine, for a race),
         from the next tick on: ``rows`` [B, 12] (sensor_faults.fault_rows / sample_faults).  The fleet or race must have the estimator
@@ -1723,6 +1786,19 @@ class RaceFleet(object):
     def disturbance(self):
         """The attached disturbance rows [B, 13] and the model's state [B, 5] (BatchedSolver.disturbances_read)."""
         return self.path.disturbances_read()
+
+    def wear(self, rows):
+        """Attach tyre wear and temperature from the next tick on (BatchedSolver.set_tyre_wear on the path engine): ``rows`` [B, 12]
+        (tyre_wear.tyre_wear_rows / sample_tyre_wear); ``None`` detaches.  The race must have tyre rows (``tyre_params``)."""
+        self.path.set_tyre_wear(rows)
+
+    def tyre_wear(self):
+        """The attached wear rows [B, 12] and the tyre sets' state [B, 6] = (W, T, P, g, ticks, E) (BatchedSolver.tyre_wear_read)."""
+        return self.path.tyre_wear_read()
+
+    def fit_tyres(self, mask):
+        """A tyre change between ticks for the vehicles of ``mask`` [B] (BatchedSolver.tyre_wear_fit)."""
+        self.path.tyre_wear_fit(mask)
 
     def run(self, n_ticks):
         """Enqueue n_ticks controller ticks (no synchronisation)."""

@@ -88,7 +88,20 @@ static DistBinding *dist_target(lpvmpc_handle *h, lpvmpc::DistDev &t) {
     return &p->dist;
 }
 
-// the live tables' scaled words back from the base copy (the other words never change)
+int lpvmpc_plant_base(lpvmpc_handle *h, const PlantSide &side, std::vector<double> &base_p, std::vector<double> &base_t, hipStream_t st) {
+    if (side.base_p()) { base_p = *side.base_p(); base_t = *side.base_t(); return LPVMPC_OK; }   // a binding is attached: the live words may be scaled
+    const size_t n = side.B;
+    base_p.resize(n * LPVMPC_PLANT_WORDS); base_t.resize(n * LPVMPC_TYRE_WORDS);
+    D2H(base_p.data(), side.veh.d.p, base_p.size() * 8);
+    D2H(base_t.data(), side.tyre.t, base_t.size() * 8);
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (const std::vector<double> *mu = lpvmpc_race_mu_base(h))            // interactions attached: the live mu words are theirs
+        for (size_t b = 0; b < n; ++b) base_p[6 * n + b] = (*mu)[b];
+    return LPVMPC_OK;
+}
+
+// the live tables' scaled words back from the base copy (the other words never change; an attached wear binding scales them again on
+// the next tick that steps the vehicle)
 static int dist_restore(lpvmpc_handle *h, const DistBinding &x, hipStream_t st) {
     const size_t n = x.d.B;
     H2D(x.d.live_p + 4 * n, x.base_p.data() + 4 * n, 2 * n * 8);
@@ -125,15 +138,7 @@ extern "C" int lpvmpc_set_disturbances(lpvmpc_handle *h, int32_t B, const lpvmpc
     x.cfg = c;
     x.rows.assign(rows, rows + n * LPVMPC_DIST_WORDS);
     HIP_TRY(h, hipStreamSynchronize(st));                                  // no tick in flight writes the tables read below
-    if (cur->d.rows) { x.base_p = cur->base_p; x.base_t = cur->base_t; }   // attached already: the live words may be scaled
-    else {
-        x.base_p.resize(n * LPVMPC_PLANT_WORDS); x.base_t.resize(n * LPVMPC_TYRE_WORDS);
-        D2H(x.base_p.data(), t.live_p, x.base_p.size() * 8);
-        D2H(x.base_t.data(), t.live_t, x.base_t.size() * 8);
-        HIP_TRY(h, hipStreamSynchronize(st));
-        if (const std::vector<double> *mu = lpvmpc_race_mu_base(h))        // interactions attached: the live mu words are theirs
-            for (size_t b = 0; b < n; ++b) x.base_p[6 * n + b] = (*mu)[b];
-    }
+    rc = lpvmpc_plant_base(h, *lpvmpc_plant_side(h), x.base_p, x.base_t, st); if (rc) return rc;
     x.d = t;
     dist_cfg(c, x.d);
     rc = dist_upload(h, B, rows_dev, nullptr, x.base_p, x.base_t, x, st); if (rc) return rc;

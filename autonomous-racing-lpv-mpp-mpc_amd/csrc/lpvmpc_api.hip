@@ -836,6 +836,7 @@ extern "C" int lpvmpc_cl_tick(lpvmpc_handle *h, int32_t n_ticks) {
                     nullptr, 0, x0_stride};
         int rc = lpvmpc_launch_solve_warm(h, a, st); if (rc) return rc;
         if (side.dist.d.rows) HIP_TRY(h, lpvmpc::launch_disturbance(h->d_cfg, trk, side.dist.d, st));   // lpvmpc_set_disturbances
+        if (side.wear.d.rows) HIP_TRY(h, lpvmpc::launch_tyre_wear(side.wear_arg(), st));                // lpvmpc_set_tyre_wear
         HIP_TRY(h, step(lpvmpc::FleetStepArgs{h->d_cfg, trk, B, N, h->d_uPred, h->cl_cmd, h->cl_plant, side.pc, side.tpc(), h->cl_hw, h->cl_slack, h->cl_q9,
                                               h->cl_local_next, h->d_uold, h->cfg.steering_delay, lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p,
                                               side.act.d, side.fault.d}, st));

@@ -282,6 +282,24 @@ struct DistDev {
 // trk null: the handle's own track (dcfg, d.hw, d.slack); else every vehicle on its palette entry
 hipError_t launch_disturbance(const DevCfg *dcfg, const TrackDev *trk, const DistDev &d, hipStream_t s);
 
+// tyre wear and temperature (tyre_wear.hip; lpvmpc_set_tyre_wear, include/lpvmpc.h "Tyre wear and temperature"): the binding on the
+// device, passed by value to the one kernel that runs behind the disturbances' and immediately in front of a tick's command / plant
+// kernel.  Every table is word-major [word][B]
+constexpr int kWearWords = 12;               // = LPVMPC_WEAR_WORDS
+constexpr int kWearState = 6;                // = LPVMPC_WEAR_STATE: W, T, P, g, ticks, E
+struct WearDev {
+    const double *rows;                      // [kWearWords][B]: the public words
+    double *state;                           // [kWearState][B]
+    const double *base;                      // [5][B]: Cf, Cr of the base plant rows, c_f of the base tyre rows, lr and m of the base plant rows
+    const double *gamma;                     // [B] the disturbances' gamma of this tick (word 4 of DistDev::state), null: none attached
+    double *live_p, *live_t;                 // the fleet's plant table [kPlantWords][B] and tyre table [kTyreWords][B]
+    const double *plant;                     // [B][8]
+    const int32_t *nstep;                    // [B] plant steps of this tick (a race's), or null: n_fixed for every vehicle
+    int B, n_fixed;
+    double dt;                               // dt_sim
+};
+hipError_t launch_tyre_wear(const WearDev &d, hipStream_t s);
+
 // sensor faults (sensor_faults.hip; lpvmpc_set_sensor_faults, include/lpvmpc.h "Sensor faults"): the binding on the device, passed
 // by value to the faulted fused kernels, which a tick launches in place of its command / plant / observe kernel
 constexpr int kFaultWords = 12;              // = LPVMPC_FAULT_WORDS

@@ -1,7 +1,7 @@
 // lpvmpc_handle.hpp -- private host-side definitions shared by every translation unit that implements the C ABI, the *_api.hip files:
 // lpvmpc_api.hip (solver entry points and the lap-0 fleet), cascade_api.hip (hand-off and planner + controller cascade), race_api.hip
 // (the race engine) and race_state_api.hip (its snapshot, restore and clone); the bindings of a handle or of its engine's plant side
-// (actuator_, plant_params_, tyre_, model_params_, tunings_, observer_design_, tracks_, disturbance_, sensor_faults_api.hip); and,
+// (actuator_, plant_params_, tyre_, model_params_, tunings_, observer_design_, tracks_, disturbance_, tyre_wear_, sensor_faults_api.hip); and,
 // through race_attach.hpp, what attaches to a running race (heats_, interactions_, contact_, walls_api.hip).  No kernel translation
 // unit includes it.
 #pragma once
@@ -23,6 +23,7 @@
 struct lpvmpc_cascade;       // cascade_api.hip
 struct lpvmpc_race;          // race_api.hip
 struct DistStep;             // below: the stand-alone step's disturbance arguments
+struct WearStep;             // below: the stand-alone step's tyre-wear arguments
 
 using lpvmpc::DevCfg;
 using lpvmpc::SolveArgs;
@@ -65,6 +66,15 @@ struct DistBinding {
     std::vector<double> rows, base_p, base_t;
 };
 
+// tyre wear and temperature of a fleet or race (lpvmpc_set_tyre_wear, tyre_wear_api.hip; d.rows null: none attached): the kernel
+// argument with its device memory (rows and state live on the device alone: a race's restore and clone move them), and on the host
+// the base plant / tyre tables [word][B] as the disturbances' binding keeps them
+struct WearBinding {
+    lpvmpc::WearDev d{};
+    DevArena mem;
+    std::vector<double> base_p, base_t;
+};
+
 // sensor faults of a fleet or race (lpvmpc_set_sensor_faults, sensor_faults_api.hip; d.rows null: none attached): the faulted kernels'
 // argument with its device memory, and on the host the configuration and the rows as they were set, for the read-back
 struct FaultBinding {
@@ -85,8 +95,14 @@ struct PlantSide {
     PlantTable veh;                     // started by a _vehicles call: the plant table
     TyreTable tyre;                     // started by a _tyres call: the tyre table as well
     DistBinding dist;                   // lpvmpc_set_disturbances on that engine (freed with it)
+    WearBinding wear;                   // lpvmpc_set_tyre_wear on that engine (freed with it)
     FaultBinding fault;                 // lpvmpc_set_sensor_faults on that engine (freed with it)
     lpvmpc::TyrePlantCfg tpc() const { return tyre_plant(veh, tyre); }
+    // the base plant / tyre tables while a binding rewrites the live Cf / Cr / c_f words (null: none does, the live tables are the base)
+    const std::vector<double> *base_p() const { return dist.d.rows ? &dist.base_p : wear.d.rows ? &wear.base_p : nullptr; }
+    const std::vector<double> *base_t() const { return dist.d.rows ? &dist.base_t : wear.d.rows ? &wear.base_t : nullptr; }
+    // the wear kernel's argument of this tick: the binding with the gamma words of the disturbances as they are attached now
+    lpvmpc::WearDev wear_arg() const { lpvmpc::WearDev w = wear.d; w.gamma = dist.d.rows ? dist.d.state + 4 * (size_t)B : nullptr; return w; }
 };
 
 struct EventRing {                      // ring of event pairs around launches (lpvmpc_set_timing)
@@ -274,7 +290,7 @@ inline lpvmpc::StepForm lpvmpc_step_form(const lpvmpc_handle *h, const PlantSide
 LPVMPC_HIDDEN int lpvmpc_plant_step_rows(lpvmpc_handle *h, int32_t B, double *state, double *act_state, const double *u, int32_t n_sub, double dt_sim,
                                          double mu_sim, const lpvmpc_actuator_config *act, const int32_t *delay_a, const int32_t *delay_df,
                                          const double *plant_params, const std::vector<double> *tyre, const char *who,
-                                         const DistStep *dist = nullptr);
+                                         const DistStep *dist = nullptr, const WearStep *wear = nullptr);
 // tyre_api.hip: tyre rows (lpvmpc_*_tyres).  lpvmpc_tyre_rows checks the host rows [B][4] (null: kind 0 for every vehicle) and returns
 // the device layout [4][B] in t; nothing is allocated.  lpvmpc_tyre_upload allocates and fills the table in y, released first (synchronises)
 LPVMPC_HIDDEN int lpvmpc_tyre_rows(lpvmpc_handle *h, int B, const double *rows, const char *who, std::vector<double> &t);
@@ -298,6 +314,19 @@ LPVMPC_HIDDEN int lpvmpc_dist_step(lpvmpc_handle *h, int B, const DistStep &ds, 
                                    const std::vector<double> &tyre_tab, double *d_plant, const int32_t *d_k, int n_sub, double dt_sim,
                                    double *live_p, double *live_t, DistBinding &tmp, hipStream_t st);
 LPVMPC_HIDDEN int lpvmpc_dist_step_read(lpvmpc_handle *h, int B, const DistStep &ds, const DistBinding &tmp, hipStream_t st);
+// the base tables [word][B] of the engine that h runs, for a binding that is about to rewrite live words: the copy another binding
+// keeps (PlantSide::base_p), else the live tables themselves with the caller's mu words (synchronises)
+LPVMPC_HIDDEN int lpvmpc_plant_base(lpvmpc_handle *h, const PlantSide &side, std::vector<double> &base_p, std::vector<double> &base_t, hipStream_t st);
+// tyre_wear_api.hip: tyre wear and temperature.  lpvmpc_wear_rows checks the host rows [B][LPVMPC_WEAR_WORDS] against the Euler step's
+// bound k_cool * n_max * dt_sim < 1 and returns the device layout [LPVMPC_WEAR_WORDS][B] in t.  lpvmpc_wear_step: the stand-alone step's
+// launch behind the disturbances' (gamma: their word of this tick, or null) and in front of its plant kernel, on tables that live in
+// tmp; wear_state [B][LPVMPC_WEAR_STATE] in (null: fresh), lpvmpc_wear_step_read copies it out after the step
+struct WearStep { const double *rows; double *wear_state; };
+LPVMPC_HIDDEN int lpvmpc_wear_rows(lpvmpc_handle *h, int B, const double *rows, int n_max, double dt_sim, const char *who, std::vector<double> &t);
+LPVMPC_HIDDEN int lpvmpc_wear_step(lpvmpc_handle *h, int B, const WearStep &ws, const std::vector<double> &rows_dev, const std::vector<double> &plant_tab,
+                                   const std::vector<double> &tyre_tab, const double *d_plant, const double *gamma, int n_sub, double dt_sim,
+                                   double *live_p, double *live_t, WearBinding &tmp, hipStream_t st);
+LPVMPC_HIDDEN int lpvmpc_wear_step_read(lpvmpc_handle *h, int B, const WearStep &ws, const WearBinding &tmp, hipStream_t st);
 // model_params_api.hip: lpvmpc_model_check refuses a batch size other than that of the handle's bound model rows (unbound: any);
 // called by every entry point that linearises, before anything is launched
 LPVMPC_HIDDEN int lpvmpc_model_check(lpvmpc_handle *h, int B, const char *who);

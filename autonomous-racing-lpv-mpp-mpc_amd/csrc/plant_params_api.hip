@@ -40,7 +40,8 @@ int lpvmpc_plant_upload(lpvmpc_handle *h, int B, const std::vector<double> &t, d
 
 int lpvmpc_plant_step_rows(lpvmpc_handle *h, int32_t B, double *state, double *act_state, const double *u, int32_t n_sub, double dt_sim,
                            double mu_sim, const lpvmpc_actuator_config *act, const int32_t *delay_a, const int32_t *delay_df,
-                           const double *plant_params, const std::vector<double> *tyre, const char *who, const DistStep *dist) {
+                           const double *plant_params, const std::vector<double> *tyre, const char *who, const DistStep *dist,
+                           const WearStep *wear) {
     if (h && B == 0) return LPVMPC_OK;
     int rc = lpvmpc_check_batch(h, B, who); if (rc) return rc;
     if (!state || !u || n_sub < 1 || !(dt_sim > 0) || (act && !act_state)) return fail(h, LPVMPC_E_ARG, "%s: bad argument", who);
@@ -48,6 +49,8 @@ int lpvmpc_plant_step_rows(lpvmpc_handle *h, int32_t B, double *state, double *a
     rc = lpvmpc_plant_rows(h, B, plant_params, h->cfg, mu_sim, who, tab); if (rc) return rc;
     std::vector<double> dist_rows;                                  // lpvmpc_plant_step_disturbed_batch: the model in front of the step
     if (dist) { rc = lpvmpc_dist_rows(h, B, dist->cfg, dist->rows, who, dist_rows); if (rc) return rc; }
+    std::vector<double> wear_rows;                                  // lpvmpc_plant_step_worn_batch: the wear model behind it
+    if (wear) { rc = lpvmpc_wear_rows(h, B, wear->rows, n_sub, dt_sim, who, wear_rows); if (rc) return rc; }
     lpvmpc_actuator_config off;
     lpvmpc_actuator_default_config(&off);
     if (!act) { act = &off; delay_a = delay_df = nullptr; }
@@ -67,6 +70,7 @@ int lpvmpc_plant_step_rows(lpvmpc_handle *h, int32_t B, double *state, double *a
     PlantTable v;
     TyreTable y;
     DistBinding dtmp;
+    WearBinding wtmp;
     rc = lpvmpc_act_alloc(h, B, act, delay_a, delay_df, dt_sim, who, as); if (rc) return rc;
     const lpvmpc::ActDev &a = as.d;
     rc = lpvmpc_plant_upload(h, B, tab, dt_sim, n_sub, v);
@@ -80,10 +84,16 @@ int lpvmpc_plant_step_rows(lpvmpc_handle *h, int32_t B, double *state, double *a
                                       const_cast<double *>(y.t), dtmp, st);
             if (rd) return rd;
         }
+        if (wear) {
+            int rw = lpvmpc_wear_step(h, B, *wear, wear_rows, tab, *tyre, h->d_xlast, dist ? dtmp.d.state + 4 * b : nullptr, n_sub, dt_sim,
+                                      const_cast<double *>(v.d.p), const_cast<double *>(y.t), wtmp, st);
+            if (rw) return rw;
+        }
         const lpvmpc::PlantStepArgs pa{B, h->d_xlast, h->d_states, lpvmpc::PlantCfg{}, tyre_plant(v, y), a};
         HIP_TRY(h, lpvmpc::plant_step_launcher(lpvmpc::step_form(true, true, y.t, false, false, false, false))(pa, st));
         D2H(state, h->d_xlast, b * 8 * 8);
         if (dist) { int rd = lpvmpc_dist_step_read(h, B, *dist, dtmp, st); if (rd) return rd; }
+        if (wear) { int rw = lpvmpc_wear_step_read(h, B, *wear, wtmp, st); if (rw) return rw; }
         if (act_state) return lpvmpc_act_download(h, a, act_state, st);   // (synchronises)
         HIP_TRY(h, hipStreamSynchronize(st));
         return LPVMPC_OK;
@@ -111,7 +121,7 @@ extern "C" int lpvmpc_plant_params_read(lpvmpc_handle *h, double *plant_params) 
     hipStream_t st = h->stream;
     const size_t B = v->B;
     std::vector<double> t(B * LPVMPC_PLANT_WORDS);
-    if (side->dist.d.rows) t = side->dist.base_p;                        // disturbances attached: the base rows, not the scaled live words
+    if (side->base_p()) t = *side->base_p();                             // disturbances or wear attached: the base rows, not the scaled live words
     else D2H(t.data(), v->p, t.size() * 8);
     HIP_TRY(h, hipStreamSynchronize(st));
     if (const std::vector<double> *mu = lpvmpc_race_mu_base(h))          // interactions attached: the base mu, not the sheltered live word

@@ -262,7 +262,8 @@ bool lpvmpc_race_state(lpvmpc_handle *h, RaceState &s) {
     s.events = r->events != nullptr;
     if (h->trk.tab) s.track_of = &h->trk_of;
     s.features = (d.estv ? LPVMPC_SNAP_HAS_ESTIMATOR : 0u) | (r->side.act.d.ring ? LPVMPC_SNAP_HAS_ACTUATOR : 0u) |
-                 (r->side.dist.d.rows ? LPVMPC_SNAP_HAS_DISTURBANCES : 0u) | (h->trk.tab ? LPVMPC_SNAP_HAS_TRACKS : 0u);
+                 (r->side.dist.d.rows ? LPVMPC_SNAP_HAS_DISTURBANCES : 0u) | (h->trk.tab ? LPVMPC_SNAP_HAS_TRACKS : 0u) |
+                 (r->side.wear.d.rows ? LPVMPC_SNAP_HAS_TYRE_WEAR : 0u);
     auto add = [&s](const char *name, void *ptr, int type, int W, int layout = STATE_VEHICLE_MAJOR) {
         RaceStateDesc e{};
         std::strncpy(e.name, name, 15);
@@ -291,13 +292,17 @@ bool lpvmpc_race_state(lpvmpc_handle *h, RaceState &s) {
     add("plan.x0", p->d_x0, STATE_F64, 5); add("plan.xPred", p->d_xPred, STATE_F64, (Np + 1) * 5); add("plan.uPred", p->d_uPred, STATE_F64, Np * 2);
     add("plan.xlast", p->d_xlast, STATE_F64, Np * 6); add("plan.delta", p->d_delta, STATE_F64, Np);
     add("plan.iters", p->d_iters, STATE_I32, 1); add("plan.status", p->d_status, STATE_I32, 1); add("plan.polish", p->d_polish, STATE_I32, 1);
-    // actuator, estimator, disturbances
+    // actuator, estimator, disturbances, tyre wear
     if (r->side.act.d.ring) {
         add("act.ring", r->side.act.d.ring, STATE_F64, 2 * kActRing, STATE_WORD_MAJOR);
         add("act.servo", r->side.act.d.servo, STATE_F64, 1); add("act.k", r->side.act.d.k, STATE_I32, 1);
     }
     if (d.estv) add("obs.state", h->obs_state, STATE_F64, kObsStride);
     if (r->side.dist.d.rows) add("dist.state", r->side.dist.d.state, STATE_F64, kDistState, STATE_WORD_MAJOR);
+    if (r->side.wear.d.rows) {                                                  // the tyre set travels whole: its state and its rows
+        add("wear.state", r->side.wear.d.state, STATE_F64, kWearState, STATE_WORD_MAJOR);
+        add("wear.rows", const_cast<double *>(r->side.wear.d.rows), STATE_F64, kWearWords, STATE_WORD_MAJOR);
+    }
     return true;
 }
 void lpvmpc_race_set_ticks(lpvmpc_handle *h, int ticks) { if (h->race) h->race->ticks = ticks; }
@@ -415,6 +420,7 @@ extern "C" int lpvmpc_race_tick(lpvmpc_handle *h, int32_t n_ticks) {
             HIP_TRY(h, lpvmpc::launch_interaction_tick(q->d, q->block, r->ticks, st));
         if (const WallBinding *q = r->walls.get())                                  // lpvmpc_race_walls: a shove into a wall is answered on this tick
             HIP_TRY(h, lpvmpc::launch_wall_tick(q->d, r->ticks, st));
+        if (side.wear.d.rows) HIP_TRY(h, lpvmpc::launch_tyre_wear(side.wear_arg(), st));                // lpvmpc_set_tyre_wear: on the state the step starts from
         HIP_TRY(h, step(lpvmpc::RaceStepArgs{d, side.pc, side.tpc(), lpvmpc_observer_vehicles_gains(h), h->obs_state, h->obs_p, side.act.d, side.fault.d}, st));
         if (lpvmpc_race_recorder *q = r->rec.get()) {                               // the recorder (record.hip)
             int slot = -1;

@@ -100,7 +100,7 @@ extern "C" int lpvmpc_race_restore(lpvmpc_handle *h, const void *buf, int64_t by
     const int32_t ticks = get32(in + 12 + 4 * (kShapeWords - 1));
     if (ticks < 0) return fail(h, LPVMPC_E_ARG, "%s: the snapshot's ticks = %d", who, ticks);
     if ((uint32_t)get32(in + 44) != s.features)
-        return fail(h, LPVMPC_E_ARG, "%s: the snapshot's feature word 0x%x (estimator 1, actuator 2, disturbances 4, tracks 8), the race's 0x%x", who,
+        return fail(h, LPVMPC_E_ARG, "%s: the snapshot's feature word 0x%x (estimator 1, actuator 2, disturbances 4, tracks 8, tyre wear 16), the race's 0x%x", who,
                     (unsigned)get32(in + 44), s.features);
     if (get32(in + 48) != (int32_t)s.tab.size())
         return fail(h, LPVMPC_E_ARG, "%s: the snapshot holds %d arrays, the race's state %zu", who, get32(in + 48), s.tab.size());

@@ -71,7 +71,7 @@ extern "C" int lpvmpc_tyre_params_read(lpvmpc_handle *h, double *tyre_params) {
     hipStream_t st = h->stream;
     const size_t B = side->B;
     std::vector<double> v(B * LPVMPC_TYRE_WORDS);
-    if (side->dist.d.rows) v = side->dist.base_t;                        // disturbances attached: the base rows, not the scaled live words
+    if (side->base_t()) v = *side->base_t();                             // disturbances or wear attached: the base rows, not the scaled live words
     else D2H(v.data(), t, v.size() * 8);
     HIP_TRY(h, hipStreamSynchronize(st));
     for (size_t b = 0; b < B; ++b)

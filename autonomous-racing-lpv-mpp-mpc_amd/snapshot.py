@@ -17,6 +17,8 @@ ENTRY_BYTES = 40
 F64, I32 = 0, 1                               # LPVMPC_SNAP_F64 / _I32
 VEHICLE_MAJOR, WORD_MAJOR = 0, 1              # [B][W] / [W][B]
 HAS_ESTIMATOR, HAS_ACTUATOR, HAS_DISTURBANCES, HAS_TRACKS = 1, 2, 4, 8
+HAS_TYRE_WEAR = 16                            # the arrays "wear.state" [B, 6] and "wear.rows" [B, 12] (tyre_wear.py) are carried
+WEAR_ARRAYS = ("wear.state", "wear.rows")
 HEADER_FIELDS = ("version", "B", "N", "Np", "M", "sd", "lap_cols", "laps", "ticks", "features", "count")
 _HEADER = struct.Struct("<8s11i12x")
 _ENTRY = struct.Struct("<16s4iq")

@@ -1073,6 +1073,69 @@ int  lpvmpc_plant_step_disturbed_batch(lpvmpc_handle *h, int32_t B, double *stat
                                        double *dist_state);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Tyre wear and temperature: a tyre-set state per vehicle of a lap-0 fleet or a race -- wear W, temperature T and the sliding energy E
+ * that drives both -- and the grip factor g it gives.  The reference's simulator has none: this is the engine's own definition.  The
+ * model acts at the control tick, on every tick on which a vehicle's plant advances n > 0 simulator steps, behind the disturbances'
+ * kernel (where one is attached; the interactions', the contact model's and the walls' too) and immediately before that tick's
+ * command / plant kernel (one more launch per tick; with nothing attached a tick issues the launches it always did).  Inputs per
+ * vehicle: the ground-truth plant state st = [x y vx vy ax ay yaw psiDot] as the tick's plant steps will start from it; lr and m of
+ * the vehicle's BASE plant row; D = n * dt_sim; the vehicle's row and state.  In this order and with exactly this association, every
+ * product and sum rounded on its own, min(a, b) = a < b ? a : b and max(a, b) = a > b ? a : b:
+ *      v_s = |vx| > 0.2 ? fabs(-vy + lr * psiDot) : 0       the numerator of the plant's rear slip angle, behind the plant's own gate
+ *      F   = m * fabs(ay)                                   st[5]: the last simulator step's total lateral tyre force
+ *      P   = F * v_s
+ *      E   = E + P * D
+ *      h   = max(0, T - T_opt)
+ *      W   = min(1, W + ((k_wear * P) * D) * (1 + k_hot * h))      on the old T
+ *      T   = T + D * (k_heat * P - k_cool * (T - T_amb))
+ *      d   = T - T_opt                                             the new T
+ *      gT  = 1 - (k_temp * d) * d
+ *      gW  = (1 - wear_slope * W) - cliff_slope * max(0, W - cliff_at)
+ *      g   = min(1, max(g_min, gW * gT))
+ *      live Cf, Cr (plant words 4, 5), c_f (tyre word 3) = g * (gamma * base)
+ *      j  += 1
+ * gamma is the disturbances' value of this tick where they are attached; otherwise the factor is absent and live = g * base.  g == 1
+ * leaves gamma * base bit for bit.  Frozen vehicles (finished, lost, n == 0) are not touched and their j stays put, so a vehicle's
+ * state depends on its own history only: not on B, the other vehicles or how a fleet is sharded.  The model uses + - * fabs and
+ * selects alone and the kernel is compiled without contraction: the device words equal a float64 restatement bit for bit.
+ *
+ * Host layouts: rows [B][LPVMPC_WEAR_WORDS] = {k_wear, k_hot, k_heat, k_cool, T_amb, T_opt, k_temp, wear_slope, cliff_at, cliff_slope,
+ * g_min, T_start}; state [B][LPVMPC_WEAR_STATE] = {W, T, P of the last worn tick, g (1 before the first), ticks (= j), E}.  An
+ * all-off row (every k_ and slope 0) gives g == 1 and T == T_start for ever and changes no word of plant or tables.
+ *
+ * lpvmpc_set_tyre_wear attaches rows to the lap-0 fleet or race that h runs (the path handle, for a race), from the next tick on; the
+ * state starts at {0, T_start, 0, 1, 0, 0}.  The fleet or race must have plant and tyre tables (lpvmpc_cl_init_tyres /
+ * lpvmpc_race_init_tyres).  Attaching again replaces the binding and the state starts over.  rows == NULL detaches: the live words go
+ * back to gamma * base where disturbances are attached (their gamma of the last disturbed tick), else to base, and the state is
+ * freed.  lpvmpc_cl_release frees the binding; a new fleet starts unworn.  While a binding is attached lpvmpc_plant_params_read and
+ * lpvmpc_tyre_params_read return the base rows.  Disturbances and wear may be attached and detached in any order: both rewrite the
+ * live words from the base copy on every tick that steps the vehicle, and no product is stored.  Refused with LPVMPC_E_ARG, a running
+ * fleet left exactly as it is: no fleet or race on the handle or one without the tables, another B than the fleet's, a non-finite
+ * word, any of k_wear, k_hot, k_heat, k_cool, k_temp, wear_slope, cliff_slope negative, cliff_at outside [0, 1], g_min outside
+ * (0, 1], k_cool * n_max * dt_sim >= 1 (the Euler step's bound; n_max: the engine's largest steps per tick, of a race the largest of
+ * n_sub_lap0 and n_sub[]).  lpvmpc_cascade_init is not extended.
+ *
+ * lpvmpc_tyre_wear_read: the rows and the state (synchronises); either pointer may be NULL.  The rows are those set, or after a
+ * race's restore or clone those that travelled with the vehicle.
+ *
+ * lpvmpc_tyre_wear_fit: a tyre change between ticks.  The vehicles with mask[b] != 0 (mask [B]) get {0, T_start, 0, 1, j kept, E
+ * kept}; the others are untouched.  Refused without a binding.  Synchronises.
+ *
+ * lpvmpc_plant_step_worn_batch: lpvmpc_plant_step_disturbed_batch with the wear model behind the disturbances' (rows NULL: no
+ * disturbance model, dist_state is not touched) and in front of the n_sub steps; wear_state [B][LPVMPC_WEAR_STATE] is read and
+ * written (NULL: fresh, nothing returned; refused: a non-finite word, a tick count that is not an integer >= 0), n_max = n_sub. */
+#define LPVMPC_WEAR_WORDS 12
+#define LPVMPC_WEAR_STATE 6
+int  lpvmpc_set_tyre_wear(lpvmpc_handle *h, int32_t B, const double *rows);
+int  lpvmpc_tyre_wear_read(lpvmpc_handle *h, double *rows, double *state);
+int  lpvmpc_tyre_wear_fit(lpvmpc_handle *h, const int32_t *mask /* [B] */);
+int  lpvmpc_plant_step_worn_batch(lpvmpc_handle *h, int32_t B, double *state, double *act_state, const double *u, int32_t n_sub,
+                                  double dt_sim, double mu_sim, const lpvmpc_actuator_config *act, const int32_t *delay_a,
+                                  const int32_t *delay_df, const double *plant_params, const double *tyre_params,
+                                  const lpvmpc_disturbance_config *cfg, const double *rows, double *dist_state,
+                                  const double *wear_rows, double *wear_state);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Race snapshot, restore and clone: checkpoint a running race, continue it later (in the same race, or in a freshly initialised
  * one of the same shape, even in another process), and branch it: vehicles take the whole dynamic state of other vehicles.  All
  * calls take the race's path handle and fail with LPVMPC_E_ARG ("call lpvmpc_race_init first") on a handle without a race.  None of
@@ -1081,21 +1144,29 @@ int  lpvmpc_plant_step_disturbed_batch(lpvmpc_handle *h, int32_t B, double *stat
  * State and bindings.  The three calls act on the race's per-vehicle STATE: every device array of which a tick can read a word that an
  * earlier tick, or the init, wrote -- plant, command, measurement, phase and lap bookkeeping, this tick's masks, the planner message
  * and recursion, the carried rows of the three handles' workspaces (u_old, uPred, vel, curv, xPred, iters, status, polish), and
- * where present the estimate view and estimator state, the actuator's ring / servo / step counter and the disturbances' process
- * state -- plus the host's tick counter.  BINDINGS are the caller's business and are never touched: plant, tyre, model, tuning, track,
- * estimator-gain and disturbance rows, actuator delays, the planner's max_ey, the hand-off operators, the live Cf / Cr / c_f words
- * (the disturbance kernel rewrites them on every tick that steps the vehicle), the seeds.  A blob carries state only: to continue a
- * race elsewhere, initialise one with the same bindings first, then restore.  The recorder's ring and statistics are neither.
+ * where present the estimate view and estimator state, the actuator's ring / servo / step counter, the disturbances' process
+ * state and the tyre sets -- plus the host's tick counter.  A tyre set ("Tyre wear and temperature") travels whole: the wear's
+ * state AND its rows are state here, the one binding that moves with the vehicle, because a worn set means nothing on another
+ * set's coefficients.  Restored or cloned wear rows are copied as they are: they were checked when they were set, and the Euler
+ * bound k_cool * n_max * dt_sim < 1 is NOT checked again against the receiving race, so restore a worn blob into a race of the
+ * same dt_sim and step counts only.  All other BINDINGS are the caller's business and are never touched: plant, tyre, model,
+ * tuning, track, estimator-gain and disturbance rows, actuator delays, the planner's max_ey, the hand-off operators, the live
+ * Cf / Cr / c_f words (the disturbance kernel and the tyre wear kernel rewrite them from the base rows on every tick that steps
+ * the vehicle), the seeds.  Apart from the tyre sets a blob carries state only: to continue a race elsewhere, initialise one with
+ * the same bindings first (wear attached, with any rows, if the blob has it), then restore.  The recorder's ring and statistics
+ * are neither.
  *
  * Blob format, version 1.  Little-endian, no pointers, self-describing:
  *   header     LPVMPC_SNAP_HEADER_BYTES = 64 B: char magic[8] = "LPVRACE\0"; then int32 words: version; B, N, Np, M (samples of the
  *              planner message), sd (steeringDelay), lap_cols (= laps + 2), laps, ticks; features (LPVMPC_SNAP_HAS_*: one bit each for
- *              the estimator in the loop, actuator state present, disturbances attached, tracks bound); count (arrays); 3 words zero
+ *              the estimator in the loop, actuator state present, disturbances attached, tracks bound, tyre wear attached); count
+ *              (arrays); 3 words zero
  *   directory  count entries of LPVMPC_SNAP_ENTRY_BYTES = 40 B: char name[16] (NUL-padded, at most 15 characters); int32 type
  *              (LPVMPC_SNAP_F64 / _I32), W (words per vehicle), layout (LPVMPC_SNAP_VEHICLE_MAJOR [B][W] / _WORD_MAJOR [W][B]), zero;
  *              int64 offset of the array from the start of the blob
  *   arrays     each exactly as it lies on the device, B * W elements, each starting on a multiple of 8 B (zero padding)
- * lpvmpc_race_snapshot_size returns the blob's size for the race as it is now (attaching or detaching disturbances changes it).
+ * lpvmpc_race_snapshot_size returns the blob's size for the race as it is now (attaching or detaching disturbances or tyre wear
+ * changes it; a blob of a race without tyre wear is byte for byte what it was before the wear existed).
  *
  * lpvmpc_race_snapshot synchronises the path handle's stream and copies the state into buf (bytes >= the size).  It changes no
  * state and is allowed while a recorder is attached.
@@ -1127,6 +1198,7 @@ int  lpvmpc_plant_step_disturbed_batch(lpvmpc_handle *h, int32_t B, double *stat
 #define LPVMPC_SNAP_HAS_ACTUATOR 2u
 #define LPVMPC_SNAP_HAS_DISTURBANCES 4u
 #define LPVMPC_SNAP_HAS_TRACKS 8u
+#define LPVMPC_SNAP_HAS_TYRE_WEAR 16u
 int  lpvmpc_race_snapshot_size(lpvmpc_handle *path, int64_t *bytes);
 int  lpvmpc_race_snapshot(lpvmpc_handle *path, void *buf, int64_t bytes);
 int  lpvmpc_race_restore(lpvmpc_handle *path, const void *buf, int64_t bytes);
